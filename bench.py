@@ -19,10 +19,20 @@ the timed region.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `value` comes from the un-instrumented timed region; the per-kernel
-durations behind `roofline` come from a second pass of the same K steps with HIP events recorded
-on the launch stream (s360_profile_*), so the numbers can be compared with
-profiles/*kernel_stats* (rocprofv3 --kernel-trace --stats of this same command).
+Rank 0 prints ONE JSON line.  `value` comes from the un-instrumented timed region of K steps and `ms_per_step` is that
+region's time over K.  A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs DIR),
+print the line.  Everything else it can measure runs only with --full: the per-kernel durations behind `kernels` / `roofline`
+(a second pass of the same K steps with HIP events recorded on the launch stream, s360_profile_*, so the numbers can be
+compared with profiles/*kernel_stats*, rocprofv3 --kernel-trace --stats of this same command), the forward-only figure, the
+exposed exchange, the lean-over-upstream list count, the other clouds, the adapter and drop-in legs and the CPU baselines.
+
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full
+    python bench.py --gpus 1 --steps 200 --warmup 20 --dump-outputs DIR
+
+--dump-outputs DIR writes what the timed path computed in its last timed step, as a caller of it receives it, to DIR/<name>.npy
+(float32; rank 0): fwdbwd: the six faces, the stitched ERP, the loss and the gradients of the four parameter tensors (rows of a
+fixed seeded sample of the Gaussians when the cloud has more than DUMP_ROWS); fwd / eval: the faces and the ERP (eval: of the
+last of its three panoramas, plus that panorama's depth faces).  The inputs are seeded: the same arguments give the same inputs.
 """
 from __future__ import annotations
 
@@ -44,6 +54,8 @@ HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 measure
 # VALU issue peak: 256 CUs x 4 SIMDs, one wave64 VALU instruction per 4 cycles per SIMD at 2.4 GHz (MI355X_MICROARCH.md chip
 # table; profiles/ VALU-busy figures use the same 4-cycle slot) = 614.4 G wave-instructions / s
 VALU_PEAK_GINST = 1024 * 2.4 / 4.0
+DUMP_ROWS = 32768             # --dump-outputs: gradient rows written per parameter tensor (11.5 MB in all at deg-4 SH)
+DUMP_IMAGE_BYTES = 8 << 20    # --dump-outputs: an image array beyond this is written as a fixed seeded sample of its elements
 FWD_KERNELS = ("sh_eval", "preprocess", "tile_scan", "emit", "sort_tiles", "render", "cube2erp")
 VALU_BOUND = ("render", "render_bwd")   # the two alpha composites: instruction-issue-bound
 
@@ -60,9 +72,15 @@ def parse():
                     help="eval = BASELINE configs[3] shape: 3 target panoramas x 6 faces, colour + depth, forward only")
     ap.add_argument("--pano-h", type=int, default=512, help="context/target ERP height (width = 2h)")
     ap.add_argument("--face", type=int, default=0, help="cube face size (default pano_h/2)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure (off by default): per-kernel durations and roofline, "
+                         "forward-only figure, exposed exchange, lean-over-upstream list count, the other clouds, the adapter and "
+                         "drop-in legs, the CPU baselines; the options below that select those legs apply with --full only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-baseline", type=int, default=1)
     ap.add_argument("--events-in-timed-region", type=int, default=0,
-                    help="0 (default): the HIP events behind `kernels` / `roofline` are recorded in a second pass of the "
+                    help="--full: 0 (default): the HIP events behind `kernels` / `roofline` are recorded in a second pass of the "
                          "same K steps, so the timed region carries no event records (they cost ~6 %% of the step: "
                          "1.53 vs 1.44 ms); 1: record them during the K timed steps")
     ap.add_argument("--fused-loss", type=int, default=1, help="1: L2 loss + its gradient seed fused into the render epilogue; "
@@ -200,8 +218,45 @@ def cpu_baseline_torch():
                        f"(PyTorch CPU, {cores} threads), {dt:.1f} s")
 
 
+def dump_outputs(d, out, params):
+    """--dump-outputs: what the timed path computed in its last step, as its caller receives it, to d/<name>.npy in float32 (under
+    40 MB in all).  Images: whole, or above DUMP_IMAGE_BYTES the flattened elements at the sorted indices
+    numpy.random.default_rng(1).choice(numel, DUMP_IMAGE_BYTES // 4, replace=False); gradients (fwdbwd): whole, or the rows of a
+    seeded sample of DUMP_ROWS Gaussians, whose indices are written too (grad_rows.npy).  Same seeds every run."""
+    import numpy as np
+    d.mkdir(parents=True, exist_ok=True)
+
+    def save(name, t):
+        np.save(d / f"{name}.npy", t.detach().float().cpu().numpy())
+
+    for name in ("faces", "depth", "erp"):
+        t = out.get(name)
+        if t is None:
+            continue
+        if t.numel() * 4 <= DUMP_IMAGE_BYTES:
+            save(name, t)
+        else:
+            n = DUMP_IMAGE_BYTES // 4
+            idx = torch.from_numpy(np.sort(np.random.default_rng(1).choice(t.numel(), n, replace=False))).to(t.device)
+            save(name, t.reshape(-1).index_select(0, idx))
+    if params is None:
+        return
+    if out.get("loss") is not None:
+        save("loss", out["loss"])
+    G = params[0].shape[0]
+    idx = None
+    if G > DUMP_ROWS:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(G, DUMP_ROWS, replace=False))).to(params[0].device)
+        np.save(d / "grad_rows.npy", idx.cpu().numpy().astype(np.float64))
+    for name, p in zip(("means", "covariances", "harmonics", "opacities"), params):
+        if p.grad is not None:
+            save(f"grad_{name}", p.grad if idx is None else p.grad.index_select(0, idx))
+
+
 def main():
     a = parse()
+    if a.events_in_timed_region and not a.full:
+        raise SystemExit("--events-in-timed-region 1 records the per-kernel figures of --full: pass --full")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a)      # does not return
     rasterizer.ATOMIC_GRADS = bool(a.atomic_grads)
@@ -258,6 +313,8 @@ def main():
                                                   views=decoder.pack_camera_views(e, k, n, f, bg))
             out["erp"] = c2e.stitch_rendered(col)
             out["faces"] = col
+            if a.dump_outputs:
+                out["depth"] = dep
 
     one = torch.ones((), device=dev)
     pending = [None]   # the previous micro-batch's gradient exchange, still in flight (N > 1)
@@ -296,6 +353,8 @@ def main():
             elif world > 1 and not chunked and not local_only[0]:
                 distributed.allreduce_gradients([p.grad for p in params])
         out["faces"] = faces
+        if a.dump_outputs:
+            out["loss"] = loss
 
     forced = bool(a.single_rank_rccl) and world == 1     # one RCCL rank, collectives really issued
     factored = world > 1 and a.mode == "fwdbwd" and a.grad_sync == "factored"
@@ -333,9 +392,11 @@ def main():
     dt = distributed.max_over_ranks(time.perf_counter() - t0, dev)
     ms_per_step = dt / a.steps * 1e3
     st_timed = rasterizer.last_state()     # workspace of the last timed step (a training workspace in fwdbwd mode)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(Path(a.dump_outputs), out, cur["params"] if a.mode == "fwdbwd" else None)
 
     extra = {}
-    if a.mode == "fwdbwd" and a.forward_figure:
+    if a.full and a.mode == "fwdbwd" and a.forward_figure:
         # (1) the forward-only figure of BASELINE configs[1] (north_star: ">= 400 Msplats/s forward") from the same process: K
         # more steps with nothing requiring grad (inference form of the call: no backward state is written)
         frozen = [p.detach() for p in params]   # nothing requires grad: the call takes its inference form (S360_FLAG_FORWARD_ONLY)
@@ -355,7 +416,7 @@ def main():
         dt_f = distributed.max_over_ranks(time.perf_counter() - t1, dev)
         extra["forward_only"] = {"value": G * world / (dt_f / a.steps) / 1e6, "unit": "Msplats/s", "ms_per_step": dt_f / a.steps * 1e3,
                                  "steps": a.steps, "what": "BASELINE configs[1]: fused six-face forward + stitch, inference form of the call"}
-    if a.mode == "fwdbwd":
+    if a.full and a.mode == "fwdbwd":
         if world > 1 or forced:
             # (2) how much of the gradient exchange a step exposes: the same K steps without it
             local_only[0] = True
@@ -389,69 +450,13 @@ def main():
     visible_pairs = int((tt["tiles_touched"] > 0).sum().item())
     assert torch.isfinite(out["faces"]).all() and torch.isfinite(out["erp"]).all()
     # contributing (pixel, entry) pairs of this step's render and the pairs the backward evaluates for them (measurement aid)
-    n_contrib_pairs, n_bwd_pairs = st_timed.count_contributions() if a.mode == "fwdbwd" else (None, None)
+    n_contrib_pairs, n_bwd_pairs = st_timed.count_contributions() if (a.full and a.mode == "fwdbwd") else (None, None)
     # the same call with upstream's 3-sigma rectangles: how much the lean lists remove (identical images; tests/test_gpu_lean.py)
-    L_upstream = L
-    if rasterizer.LEAN_LISTS and a.mode != "eval":
+    L_upstream = L if a.full else None
+    if a.full and rasterizer.LEAN_LISTS and a.mode != "eval":
         with torch.no_grad():
             decoder.render_views_fused(ext, K, near, far, (face_w, face_w), bg, *[p.detach() for p in params], shared_campos=True, lean=False)
         L_upstream = rasterizer.last_state().num_rendered()
-
-    # ---- per-kernel durations: HIP events around every kernel group, recorded on the stream the kernels run on,
-    # in a second pass of the same K steps (default) or inside the timed region itself (--events-in-timed-region 1)
-    if not a.events_in_timed_region:
-        _lib.profile_enable(True)
-        for _ in range(a.steps):
-            step()
-        finish_pending()
-        torch.cuda.synchronize(dev)
-    prof = _lib.profile_collect()
-    _lib.profile_enable(False)
-    kernels = {k: dict(avg_us=ms / n * 1e3, launches=n) for k, (ms, n) in prof.items() if n}
-    dom = max(kernels, key=lambda k: kernels[k]["avg_us"] * kernels[k]["launches"])
-    # kernel-interface (compulsory) bytes per launch, for the per-kernel table
-    hw = 6 * face_w * face_w
-    iface = dict(
-        sh_eval=G * (300 + 12 + 16 + (36 if a.mode == "fwdbwd" else 0)),
-        preprocess=G * (12 + 36 + 4 + 16) + 6 * G * 4 + visible_pairs * 57,
-        render=L * (4 + 48) + hw * (12 + 8),
-        sort_tiles=L * (8 + 8 + 4),
-        emit=6 * G * 4 + visible_pairs * 32 + L * 8,
-        render_bwd=L * (48 + 4) + hw * (12 + 8) + L * 48,
-        gather_slots=L * (4 + 4) + L * 48 + visible_pairs * 48,
-        preprocess_bwd=G * (12 + 36 + 36 + 1) + visible_pairs * (48 + 1) + G * (12 + 36 + 4 + 16),
-        sh_bwd=G * (16 + 12 + 300),
-        cube2erp=hw * 12 + (2 * face_w) * (4 * face_w) * (12 + 12),
-    )
-    for k, v in kernels.items():
-        if k in iface:
-            v["interface_bytes"] = iface[k]
-            v["interface_GBps"] = iface[k] / (v["avg_us"] * 1e-6) / 1e9
-    # SURVEY.md §8(d) compulsory bytes per splat, for THIS workload (350.5 / 684.5 at G = 1 048 576, 1024x512 ERP)
-    face_bytes, erp_bytes = hw * 12, (2 * face_w) * (4 * face_w) * 12
-    BYTES_FWD = 340.0 + (face_bytes + erp_bytes) / G
-    BYTES_BWD = 340.0 + face_bytes / G + 340.0
-    per_splat = BYTES_FWD if dom in FWD_KERNELS else BYTES_BWD
-    dom_s = kernels[dom]["avg_us"] * 1e-6
-    achieved = per_splat * G / dom_s / 1e9
-    traffic = valu_busy = valu_insts = counter_bytes_step = None
-    pmc_note = "no committed PMC profile"
-    pmc = ROOT / "profiles" / "pmc_latest.json"
-    if pmc.exists():   # PMC counters of the committed rocprofv3 passes (scripts/collect_profiles.sh), per launch
-        try:
-            blob = json.loads(pmc.read_text())
-            stamp = blob.get("_meta", {})
-            if stamp.get("source_hash") == _lib.source_hash() and stamp.get("gaussians") == G and stamp.get("face") == face_w:
-                rec = blob.get(dom, {})
-                traffic, valu_busy, valu_insts = rec.get("hbm_bytes_per_launch"), rec.get("valu_busy_frac"), rec.get("valu_insts_per_launch")
-                counter_bytes_step = stamp.get("counter_bytes_per_step")
-                pmc_note = f"PMC counters from profiles/pmc_latest.json (same kernel sources {stamp.get('source_hash')}, same workload)"
-            else:   # never quote counters of other code or another workload: traffic stays null
-                pmc_note = (f"profiles/pmc_latest.json was collected from kernel sources {stamp.get('source_hash')} / G={stamp.get('gaussians')}"
-                            f" (now {_lib.source_hash()} / G={G}): traffic not quoted")
-        except Exception:
-            traffic = None
-    bytes_step = (BYTES_FWD + (BYTES_BWD if a.mode == "fwdbwd" else 0.0)) * G * views_per_step
 
     value = G * views_per_step * world / (dt / a.steps) / 1e6
     erp_w, erp_h = 4 * face_w, 2 * face_w          # the target ERP the six faces stitch into
@@ -463,30 +468,94 @@ def main():
         cfg_name = "BASELINE configs[4] single-rank shape" + (" (G = 2 context panoramas at 2048x1024)" if G == 1 << 22 else " (resolution-decoupled cloud)")
     else:
         cfg_name = "non-BASELINE size"
-    # ---- roofline, exactly as the measurement contract defines it: ALGORITHMIC bytes of the dominant kernel's phase (SURVEY 8(d):
-    # 350.5 B/splat forward, 684.5 B/splat backward at this workload) x the splats one launch processes / that launch's duration
-    # (HIP events on the launch stream), against the 8 TB/s HBM peak.  frac_path = the whole step's algorithmic bytes / step time.
-    # The dominant kernels are alpha composites, whose own limit is VALU issue, so two VALU figures follow as extra keys:
-    # valu_issue_frac = EXECUTED wave64 VALU instructions / issue peak (rises if the kernel executes more instructions: a
-    # utilisation, not an efficiency) and valu_work_frac = the instructions the contributing (pixel, entry) pairs NEED
-    # (pairs x MIN_INST lane-slots / 64) / issue peak — executing more instructions cannot raise that one.
-    MIN_INST = {"render": 26, "render_bwd": 68}   # VALU issue slots per contributing pair (v_exp / v_rcp = 4 slots); DESIGN.md section 4
-    a_inst = None if valu_insts is None else valu_insts / dom_s / 1e9
-    work_inst = None if (n_contrib_pairs is None or dom not in MIN_INST) else n_contrib_pairs * views_per_step * MIN_INST[dom] / 64.0
-    roofline = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                "traffic": traffic,
-                # what the kernel REALLY moves through HBM per unit time (PMC counter bytes / launch time / peak): `frac` prices the
-                # phase's algorithmic bytes against the kernel's duration, as the contract defines it — it is not "42 % of HBM"
-                "hbm_frac_kernel": None if traffic is None else traffic / dom_s / 1e9 / HBM_PEAK_GBPS,
-                "frac_path": bytes_step / (dt / a.steps) / 1e9 / HBM_PEAK_GBPS,
-                "algorithmic_bytes_per_launch": per_splat * G, "launch_us": kernels[dom]["avg_us"],
-                "valu_issue_frac": None if a_inst is None else a_inst / VALU_PEAK_GINST, "valu_insts_per_launch": valu_insts,
-                "valu_work_frac": None if work_inst is None else work_inst / dom_s / 1e9 / VALU_PEAK_GINST,
-                "valu_work_insts_per_launch": work_inst, "contributing_pairs": n_contrib_pairs, "backward_evaluated_pairs": n_bwd_pairs,
-                "valu_peak_Ginst_per_s": VALU_PEAK_GINST, "valu_busy_frac": valu_busy,
-                "note": f"frac = {per_splat:.1f} B/splat (SURVEY 8d, {'fwd' if dom in FWD_KERNELS else 'bwd'} phase) x {G} splats / "
-                        f"{kernels[dom]['avg_us']:.1f} us (avg launch of the dominant kernel group, HIP events) / 8 TB/s; the group is an alpha "
-                        "composite, VALU-issue-bound (DESIGN.md section 4): valu_* are the figures against 1024 SIMDs x 2.4 GHz / 4; " + pmc_note}
+
+    figures = {}   # --full: kernels, roofline, path_roofline
+    if a.full:
+        # ---- per-kernel durations: HIP events around every kernel group, recorded on the stream the kernels run on,
+        # in a second pass of the same K steps (default) or inside the timed region itself (--events-in-timed-region 1)
+        if not a.events_in_timed_region:
+            _lib.profile_enable(True)
+            for _ in range(a.steps):
+                step()
+            finish_pending()
+            torch.cuda.synchronize(dev)
+        prof = _lib.profile_collect()
+        _lib.profile_enable(False)
+        kernels = {k: dict(avg_us=ms / n * 1e3, launches=n) for k, (ms, n) in prof.items() if n}
+        dom = max(kernels, key=lambda k: kernels[k]["avg_us"] * kernels[k]["launches"])
+        # kernel-interface (compulsory) bytes per launch, for the per-kernel table
+        hw = 6 * face_w * face_w
+        iface = dict(
+            sh_eval=G * (300 + 12 + 16 + (36 if a.mode == "fwdbwd" else 0)),
+            preprocess=G * (12 + 36 + 4 + 16) + 6 * G * 4 + visible_pairs * 57,
+            render=L * (4 + 48) + hw * (12 + 8),
+            sort_tiles=L * (8 + 8 + 4),
+            emit=6 * G * 4 + visible_pairs * 32 + L * 8,
+            render_bwd=L * (48 + 4) + hw * (12 + 8) + L * 48,
+            gather_slots=L * (4 + 4) + L * 48 + visible_pairs * 48,
+            preprocess_bwd=G * (12 + 36 + 36 + 1) + visible_pairs * (48 + 1) + G * (12 + 36 + 4 + 16),
+            sh_bwd=G * (16 + 12 + 300),
+            cube2erp=hw * 12 + (2 * face_w) * (4 * face_w) * (12 + 12),
+        )
+        for k, v in kernels.items():
+            if k in iface:
+                v["interface_bytes"] = iface[k]
+                v["interface_GBps"] = iface[k] / (v["avg_us"] * 1e-6) / 1e9
+        # SURVEY.md §8(d) compulsory bytes per splat, for THIS workload (350.5 / 684.5 at G = 1 048 576, 1024x512 ERP)
+        face_bytes, erp_bytes = hw * 12, (2 * face_w) * (4 * face_w) * 12
+        BYTES_FWD = 340.0 + (face_bytes + erp_bytes) / G
+        BYTES_BWD = 340.0 + face_bytes / G + 340.0
+        per_splat = BYTES_FWD if dom in FWD_KERNELS else BYTES_BWD
+        dom_s = kernels[dom]["avg_us"] * 1e-6
+        achieved = per_splat * G / dom_s / 1e9
+        traffic = valu_busy = valu_insts = counter_bytes_step = None
+        pmc_note = "no committed PMC profile"
+        pmc = ROOT / "profiles" / "pmc_latest.json"
+        if pmc.exists():   # PMC counters of the committed rocprofv3 passes (scripts/collect_profiles.sh), per launch
+            try:
+                blob = json.loads(pmc.read_text())
+                stamp = blob.get("_meta", {})
+                if stamp.get("source_hash") == _lib.source_hash() and stamp.get("gaussians") == G and stamp.get("face") == face_w:
+                    rec = blob.get(dom, {})
+                    traffic, valu_busy, valu_insts = rec.get("hbm_bytes_per_launch"), rec.get("valu_busy_frac"), rec.get("valu_insts_per_launch")
+                    counter_bytes_step = stamp.get("counter_bytes_per_step")
+                    pmc_note = f"PMC counters from profiles/pmc_latest.json (same kernel sources {stamp.get('source_hash')}, same workload)"
+                else:   # never quote counters of other code or another workload: traffic stays null
+                    pmc_note = (f"profiles/pmc_latest.json was collected from kernel sources {stamp.get('source_hash')} / G={stamp.get('gaussians')}"
+                                f" (now {_lib.source_hash()} / G={G}): traffic not quoted")
+            except Exception:
+                traffic = None
+        bytes_step = (BYTES_FWD + (BYTES_BWD if a.mode == "fwdbwd" else 0.0)) * G * views_per_step
+        # ---- roofline, exactly as the measurement contract defines it: ALGORITHMIC bytes of the dominant kernel's phase (SURVEY 8(d):
+        # 350.5 B/splat forward, 684.5 B/splat backward at this workload) x the splats one launch processes / that launch's duration
+        # (HIP events on the launch stream), against the 8 TB/s HBM peak.  frac_path = the whole step's algorithmic bytes / step time.
+        # The dominant kernels are alpha composites, whose own limit is VALU issue, so two VALU figures follow as extra keys:
+        # valu_issue_frac = EXECUTED wave64 VALU instructions / issue peak (rises if the kernel executes more instructions: a
+        # utilisation, not an efficiency) and valu_work_frac = the instructions the contributing (pixel, entry) pairs NEED
+        # (pairs x MIN_INST lane-slots / 64) / issue peak — executing more instructions cannot raise that one.
+        MIN_INST = {"render": 26, "render_bwd": 68}   # VALU issue slots per contributing pair (v_exp / v_rcp = 4 slots); DESIGN.md section 4
+        a_inst = None if valu_insts is None else valu_insts / dom_s / 1e9
+        work_inst = None if (n_contrib_pairs is None or dom not in MIN_INST) else n_contrib_pairs * views_per_step * MIN_INST[dom] / 64.0
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                    "traffic": traffic,
+                    # what the kernel REALLY moves through HBM per unit time (PMC counter bytes / launch time / peak): `frac` prices the
+                    # phase's algorithmic bytes against the kernel's duration, as the contract defines it — it is not "42 % of HBM"
+                    "hbm_frac_kernel": None if traffic is None else traffic / dom_s / 1e9 / HBM_PEAK_GBPS,
+                    "frac_path": bytes_step / (dt / a.steps) / 1e9 / HBM_PEAK_GBPS,
+                    "algorithmic_bytes_per_launch": per_splat * G, "launch_us": kernels[dom]["avg_us"],
+                    "valu_issue_frac": None if a_inst is None else a_inst / VALU_PEAK_GINST, "valu_insts_per_launch": valu_insts,
+                    "valu_work_frac": None if work_inst is None else work_inst / dom_s / 1e9 / VALU_PEAK_GINST,
+                    "valu_work_insts_per_launch": work_inst, "contributing_pairs": n_contrib_pairs, "backward_evaluated_pairs": n_bwd_pairs,
+                    "valu_peak_Ginst_per_s": VALU_PEAK_GINST, "valu_busy_frac": valu_busy,
+                    "note": f"frac = {per_splat:.1f} B/splat (SURVEY 8d, {'fwd' if dom in FWD_KERNELS else 'bwd'} phase) x {G} splats / "
+                            f"{kernels[dom]['avg_us']:.1f} us (avg launch of the dominant kernel group, HIP events) / 8 TB/s; the group is an alpha "
+                            "composite, VALU-issue-bound (DESIGN.md section 4): valu_* are the figures against 1024 SIMDs x 2.4 GHz / 4; " + pmc_note}
+        figures = {"roofline": roofline,
+                   "path_roofline": {"bytes_per_step": bytes_step, "achieved_GBps": bytes_step / (dt / a.steps) / 1e9,
+                                     "frac_of_8TBps": bytes_step / (dt / a.steps) / 1e9 / HBM_PEAK_GBPS,
+                                     "counter_bytes_per_step": counter_bytes_step,
+                                     "counter_over_algorithmic": None if counter_bytes_step is None else counter_bytes_step / bytes_step},
+                   "kernels": kernels}
     res = {
         "metric": f"Msplats/s {what} @{gm} Gaussians, {erp_w}x{erp_h} ERP",
         "value": value, "unit": "Msplats/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -503,20 +572,15 @@ def main():
                        f", RCCL exchange inside the backward ({len(ex_bounds)} Gaussian range(s), " + ("ONE coalesced all-gather of packed 40 B/G + dRGB 16 B/G rows per range, summed locally" if ex_mode == "gather" else "all-reduce 40 B/G packed + all-gather dRGB 16 B/G/rank per range") + "; chunked exchange inside the backward)" if chunked else
                        ", RCCL factored grad exchange (all-reduce 40 B/G packed + all-gather dRGB 16 B/G/rank" + (", overlapped with the next micro-batch's forward" if a.overlap_exchange else "") + ")" if factored else
                        ", RCCL all-reduce of Gaussian grads"),
-                   "num_rendered": L, "num_rendered_upstream_lists": L_upstream, "lean_over_upstream": L / max(L_upstream, 1),
+                   "num_rendered": L, "num_rendered_upstream_lists": L_upstream, "lean_over_upstream": None if L_upstream is None else L / max(L_upstream, 1),
                    "visible_pairs": visible_pairs, "split_lists": a.split_lists, "split_flag_set_in_timed_steps": bool(st_timed.prm.flags & _lib.FLAG_SPLIT_LISTS), "split_quadrants": n_split,
                    "wide_rectangles": int(st_timed.header()[4].item()), "coop_walk_flag_set_in_timed_steps": bool(st_timed.prm.flags & _lib.FLAG_COOP_WALK),
                    "workspace_bytes_forward": ws_fwd, "workspace_bytes_backward": ws_bwd if a.mode == "fwdbwd" else 0,
                    "max_instances": int(st_timed.prm.max_instances)},
-        "roofline": roofline,
-        "path_roofline": {"bytes_per_step": bytes_step, "achieved_GBps": bytes_step / (dt / a.steps) / 1e9,
-                          "frac_of_8TBps": bytes_step / (dt / a.steps) / 1e9 / HBM_PEAK_GBPS,
-                          "counter_bytes_per_step": counter_bytes_step,
-                          "counter_over_algorithmic": None if counter_bytes_step is None else counter_bytes_step / bytes_step},
-        "kernels": kernels,
+        **figures,
         **extra,
     }
-    if a.mode == "eval" and rank == 0:
+    if a.full and a.mode == "eval" and rank == 0:
         # the same 18 colour + 18 depth face renders through the reference-style per-face drop-in calls
         from types import SimpleNamespace
         gs = SimpleNamespace(means=params[0][None], covariances=params[1][None], harmonics=params[2][None], opacities=params[3][None])
@@ -533,7 +597,7 @@ def main():
                 dec(gs, e18, k18, n18, f18, (face_w, face_w), depth_mode="depth")
             torch.cuda.synchronize(dev)
         res["per_face_dropin_ms_per_step"] = (time.perf_counter() - t0) / 3 * 1e3
-    if world == 1 and a.mode == "fwdbwd" and a.workloads:
+    if a.full and world == 1 and a.mode == "fwdbwd" and a.workloads:
         # ---- the same training step on two more clouds of the same size (every tuning decision of rounds 1-3 was taken on the
         # encoder-like cloud alone): SURVEY 8(d)'s uniform-random stress cloud, and a surface-like cloud (what a trained encoder
         # emits: spatially coherent depth, opacity >= 0.9 — the first surface hides most of what lies behind it)
@@ -661,7 +725,7 @@ def main():
                                "what": "the same training step through the unchanged reference's decoder loop: six per-face drop-in rasteriser "
                                        "calls (torch camera glue, host sync per call), torch L2 loss, backward — what a user gets without "
                                        "splatter360_amd.install()"}
-    if rank == 0 and a.cpu_baseline and a.mode != "eval":    # N > 1 too: rank 0's host cores, the other ranks wait at the teardown
+    if rank == 0 and a.full and a.cpu_baseline and a.mode != "eval":    # N > 1 too: rank 0's host cores, the other ranks wait at the teardown
         res["cpu_baseline"] = cpu_baseline(cloud, face_w, 0.1, 10.0, a.mode)
         try:
             res["cpu_baseline_torch"] = cpu_baseline_torch()

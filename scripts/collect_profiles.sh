@@ -12,18 +12,18 @@ O=$R/gpurun_out/$ROUND
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 python -c "import sys, json; sys.path.insert(0, '$R'); from splatter360_amd import _lib; print(json.dumps(dict(source_hash=_lib.source_hash(), gaussians=1048576, face=256)))" > $O/meta.json
-timeout 400 python $R/bench.py > $O/bench_fwdbwd.json 2> $O/bench_fwdbwd.err
-timeout 200 python $R/bench.py --mode fwd --cpu-baseline 0 --workloads 0 > $O/bench_fwd.json 2> $O/bench_fwd.err
-timeout 200 python $R/bench.py --steps 10 --warmup 3 --mode eval --cpu-baseline 0 > $O/bench_eval.json 2> /dev/null
-timeout 300 python $R/bench.py --steps 10 --warmup 3 --pano-h 1024 --cpu-baseline 0 --workloads 0 > $O/bench_c5_4m_fwdbwd.json 2> /dev/null
-S360_DIST_BACKEND=gloo S360_FORCE_DEVICE=0 timeout 300 python $R/bench.py --gpus 2 --steps 4 --warmup 2 --cpu-baseline 0 --workloads 0 > $O/bench_2rank_gloo_one_gpu.json 2> /dev/null
-timeout 300 python $R/bench.py --cpu-baseline 0 --workloads 0 --single-rank-rccl 1 > $O/bench_1rank_nccl.json 2> $O/bench_1rank_nccl.err
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python $R/bench.py --steps 20 --warmup 5 --cpu-baseline 0 --forward-figure 0 --workloads 0 > $O/bench_under_rocprof.json 2>/dev/null
+timeout 400 python $R/bench.py --full > $O/bench_fwdbwd.json 2> $O/bench_fwdbwd.err
+timeout 200 python $R/bench.py --full --mode fwd --cpu-baseline 0 --workloads 0 > $O/bench_fwd.json 2> $O/bench_fwd.err
+timeout 200 python $R/bench.py --full --steps 10 --warmup 3 --mode eval --cpu-baseline 0 > $O/bench_eval.json 2> /dev/null
+timeout 300 python $R/bench.py --full --steps 10 --warmup 3 --pano-h 1024 --cpu-baseline 0 --workloads 0 > $O/bench_c5_4m_fwdbwd.json 2> /dev/null
+S360_DIST_BACKEND=gloo S360_FORCE_DEVICE=0 timeout 300 python $R/bench.py --full --gpus 2 --steps 4 --warmup 2 --cpu-baseline 0 --workloads 0 > $O/bench_2rank_gloo_one_gpu.json 2> /dev/null
+timeout 300 python $R/bench.py --full --cpu-baseline 0 --workloads 0 --single-rank-rccl 1 > $O/bench_1rank_nccl.json 2> $O/bench_1rank_nccl.err
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python $R/bench.py --full --steps 20 --warmup 5 --cpu-baseline 0 --forward-figure 0 --workloads 0 > $O/bench_under_rocprof.json 2>/dev/null
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -o pmc -- python $R/bench.py --steps 3 --warmup 1 --cpu-baseline 0 --forward-figure 0 --workloads 0 > /dev/null 2>&1
+  timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -o pmc -- python $R/bench.py --full --steps 3 --warmup 1 --cpu-baseline 0 --forward-figure 0 --workloads 0 > /dev/null 2>&1
 done
-timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $O/pmc_SQ1 -o pmc -- python $R/bench.py --steps 3 --warmup 1 --cpu-baseline 0 --forward-figure 0 --workloads 0 > /dev/null 2>&1
-timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_SQ2 -o pmc -- python $R/bench.py --steps 3 --warmup 1 --cpu-baseline 0 --forward-figure 0 --workloads 0 > /dev/null 2>&1
+timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $O/pmc_SQ1 -o pmc -- python $R/bench.py --full --steps 3 --warmup 1 --cpu-baseline 0 --forward-figure 0 --workloads 0 > /dev/null 2>&1
+timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_SQ2 -o pmc -- python $R/bench.py --full --steps 3 --warmup 1 --cpu-baseline 0 --forward-figure 0 --workloads 0 > /dev/null 2>&1
 # the RCCL single-rank exchange under the kernel trace (RCCL kernels between the backward's per-range kernels)
 S360_RCCL_TEST_W=512 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rccl -o rccl -- python $R/scripts/rccl_single_rank.py > $O/rccl_single_rank.log 2>&1
 # the stand-alone adapter kernels + fused raw path, and the per-face drop-in training step of the unchanged reference
@@ -31,7 +31,7 @@ timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/adapter -
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/dropin -o dropin -- python $R/scripts/prof_adapter_dropin.py dropin > $O/prof_dropin.log 2>&1
 # round 6: the 4 M / 512^2 shape with the stress workloads (surface-like: list splitting inside k_render's launch), and the kernel table of
 # the 1 M surface-like step with splitting off and on
-timeout 400 python $R/bench.py --steps 10 --warmup 3 --pano-h 1024 --cpu-baseline 0 --workloads 1 > $O/bench_c5_4m_workloads.json 2> /dev/null
+timeout 400 python $R/bench.py --full --steps 10 --warmup 3 --pano-h 1024 --cpu-baseline 0 --workloads 1 > $O/bench_c5_4m_workloads.json 2> /dev/null
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/surface -o surface -- python $R/scripts/split_diag.py surface_like 10 > $O/split_diag_surface_like.txt 2>&1
 # per-unit timing of both composites (instrumented build; the box is discarded afterwards)
 S360_HIPCC_EXTRA=-DS360_DBG_TIMING python -c "import sys; sys.path.insert(0, '$R'); from splatter360_amd import _lib; _lib.build(force=True)"

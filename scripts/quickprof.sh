@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/quick
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o q -- python $R/bench.py --steps 20 --warmup 5 --cpu-baseline 0 "$@" > $O/bench.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o q -- python $R/bench.py --steps 20 --warmup 5 --full --cpu-baseline 0 "$@" > $O/bench.json 2>/dev/null
 f=$(find $O -name '*kernel_stats.csv' | head -1)
 python - "$f" <<'PY'
 import csv, sys

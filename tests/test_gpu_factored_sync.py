@@ -253,7 +253,7 @@ def test_bench_two_ranks_on_one_gpu_end_to_end(gpu):
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(S360_DIST_BACKEND="gloo", S360_FORCE_DEVICE="0")
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-baseline", "0",
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--cpu-baseline", "0",
                         "--pano-h", "64", "--face", "64"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

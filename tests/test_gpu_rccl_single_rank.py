@@ -27,7 +27,7 @@ def test_bench_single_rank_rccl_line(gpu):
     communicator — small cloud, the JSON line says which backend ran the collectives and what the exchange cost."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--cpu-baseline", "0",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--cpu-baseline", "0",
                         "--pano-h", "64", "--face", "64", "--workloads", "0", "--single-rank-rccl", "1"], env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -1,54 +1,146 @@
-"""`splatter360_amd.install()` against the reference's own plugin seam (build container only: needs /root/reference).
+"""`splatter360_amd.install()` against the reference's plugin seam, on a stand-in of the reference's own package layout.
 
-The reference's decoder package is imported for real (its __init__ runs: DECODERS, get_decoder —
-/root/reference/src/model/decoder/__init__.py:5-13) under the SURVEY Appendix-B stubs for the absent third-party modules; the
-rasteriser it imports is THIS repository's drop-in `diff_gaussian_rasterization`.  Runs on CPU: construction and registry only —
-the forward of the registered class is exercised on the GPU from the committed capture (tests/test_gpu_install.py)."""
-import importlib
+The stand-in `src` package is written at test time from tests/golden/reference_seam.json (captured from the reference by
+tests/golden/make_golden_seam.py: interface facts only, no source): the registry `DECODERS` / `get_decoder` of
+src/model/decoder/__init__.py:5-13, the `Decoder` base and `DecoderOutput` with the reference's forward parameters, the Gaussians
+containers, and GaussianAdapterERP with its config, forward parameters and non-persistent sh_mask buffer.  It is a real on-disk
+package, so the import hooks of install(lazy=True) see the very import sequence the reference makes; the rasteriser its decoder
+module imports is THIS repository's drop-in `diff_gaussian_rasterization`.  Runs on CPU: construction and registry only — the
+forward of the registered class is exercised on the GPU from the committed capture (tests/test_gpu_install.py)."""
+import json
 import subprocess
 import sys
 import textwrap
-import types
 from pathlib import Path
-from types import SimpleNamespace
 
 import pytest
 
-REF = Path("/root/reference")
 ROOT = Path(__file__).resolve().parent.parent
-pytestmark = pytest.mark.skipif(not (REF / "src/model/decoder/__init__.py").exists(), reason="the reference is only present in the build container")
+SEAM = json.loads((ROOT / "tests" / "golden" / "reference_seam.json").read_text())
 
-PRELUDE = textwrap.dedent(f"""
+
+def _write_standin(root: Path) -> None:
+    """The stand-in package: every module, class, field and parameter name comes from the capture."""
+    d, a = SEAM["decoder"], SEAM["adapter"]
+
+    def put(module: str, text: str = "", package: bool = False) -> None:
+        path = root.joinpath(*module.split("."))
+        path = path / "__init__.py" if package else path.with_suffix(".py")
+        path.parent.mkdir(parents=True, exist_ok=True)
+        for parent in list(path.parents)[1 if package else 0:]:     # every enclosing directory up to root is a package
+            if parent == root:
+                break
+            (parent / "__init__.py").touch()
+        path.write_text(textwrap.dedent(text))
+
+    def dataclass_src(name, names):
+        return f"@dataclasses.dataclass\nclass {name}:\n" + "".join(f"    {n}: object = None\n" for n in names)
+
+    put(d["types_module"], "import dataclasses\n" + dataclass_src("Gaussians", d["gaussians_fields"]))
+    put(d["base_module"], f"""
+        import abc, dataclasses
+        from torch import nn
+        {dataclass_src(d["output"], d["output_fields"]).replace(chr(10), chr(10) + "        ")}
+        class {d["base"]}(nn.Module, abc.ABC):
+            def __init__({", ".join(d["base_init_params"])}):
+                super().__init__()
+                self.cfg, self.dataset_cfg = cfg, dataset_cfg
+
+            @abc.abstractmethod
+            def forward({", ".join(d["forward_params"])}):
+                ...
+    """)
+    put(d["class_module"], f"""
+        import diff_gaussian_rasterization   # the rasteriser the reference's decoder imports
+        from {d["base_module"]} import {d["base"]}
+
+        class {d["class"]}({d["base"]}):
+            def forward({", ".join(d["forward_params"])}):
+                raise NotImplementedError("stand-in")
+    """)
+    put(d["registry_module"], f"""
+        from {d["class_module"]} import {d["class"]}
+        {d["registry_name"]} = {{{d["key"]!r}: {d["class"]}}}
+
+        def {d["factory"]}(decoder_cfg, dataset_cfg):
+            return {d["registry_name"]}[decoder_cfg.name](decoder_cfg, dataset_cfg)
+    """, package=True)
+    buffers = {n: (b["values"], b["persistent"]) for n, b in a["buffers"].items()}
+    put(a["module"], f"""
+        import dataclasses
+        import torch
+        from torch import nn
+        {dataclass_src(a["cfg_class"], a["cfg_fields"]).replace(chr(10), chr(10) + "        ")}
+        {dataclass_src(a["container"], a["container_fields"]).replace(chr(10), chr(10) + "        ")}
+        class {a["class"]}(nn.Module):
+            def __init__({", ".join(a["init_params"])}):
+                super().__init__()
+                self.cfg = cfg
+                for name, (values, persistent) in {buffers!r}.items():
+                    self.register_buffer(name, torch.tensor(values, dtype=torch.float32), persistent=persistent)
+
+            @property
+            def d_sh(self):
+                return {a["d_sh"]}
+
+            @property
+            def d_in(self):
+                return {a["d_in"]}
+
+            def forward({", ".join(a["forward_params"])}):
+                raise NotImplementedError("stand-in")
+    """)
+
+
+@pytest.fixture(scope="module")
+def standin(tmp_path_factory):
+    root = tmp_path_factory.mktemp("reference_seam")
+    _write_standin(root)
+    return root
+
+
+PRELUDE = textwrap.dedent("""
     import sys, types
-    from pathlib import Path
-    REF = {str(REF)!r}
-    jt = types.ModuleType("jaxtyping")
-    class _Ann:
-        def __getitem__(self, item):
-            return object
-    for name in ("Float", "Int", "Int64", "Int32", "UInt8", "Bool", "Shaped"):
-        setattr(jt, name, _Ann())
-    sys.modules["jaxtyping"] = jt
-    sys.modules["cv2"] = types.ModuleType("cv2")
-    ds = types.ModuleType("src.dataset"); ds.__path__ = [REF + "/src/dataset"]; ds.DatasetCfg = object
-    sys.modules["src.dataset"] = ds
-    for pkg in ("src.model.encoder", "src.model.encoder.costvolume"):
-        m = types.ModuleType(pkg); m.__path__ = [REF + "/" + pkg.replace(".", "/")]; sys.modules[pkg] = m
-    sys.path.insert(0, REF)
-    sys.path.insert(0, {str(ROOT)!r})
     from types import SimpleNamespace
-    cfg, dcfg = SimpleNamespace(name="splatting_cuda"), SimpleNamespace(background_color=[0.1, 0.2, 0.3])
+    SEAM = {seam!r}
+    sys.path.insert(0, {standin!r})
+    sys.path.insert(0, {root!r})
+    cfg, dcfg = SimpleNamespace(name=SEAM["decoder"]["key"]), SimpleNamespace(background_color=[0.1, 0.2, 0.3])
 """)
 
 
-def _run(body: str) -> str:
-    r = subprocess.run([sys.executable, "-c", PRELUDE + textwrap.dedent(body)], capture_output=True, text=True, timeout=600)
+def _run(standin: Path, body: str) -> str:
+    prelude = PRELUDE.format(seam=SEAM, standin=str(standin), root=str(ROOT))
+    r = subprocess.run([sys.executable, "-c", prelude + textwrap.dedent(body)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     return r.stdout
 
 
-def test_install_registers_the_fused_decoder_under_the_reference_key():
-    out = _run("""
+def test_the_standin_has_the_reference_layout(standin):
+    """The stand-in is what the capture says the reference is (registry, class names, signatures, containers, buffers)."""
+    out = _run(standin, """
+        import dataclasses, inspect, importlib
+        d, a = SEAM["decoder"], SEAM["adapter"]
+        reg = importlib.import_module(d["registry_module"])
+        cls = getattr(reg, d["registry_name"])[d["key"]]
+        assert cls.__name__ == d["class"] and cls.__module__ == d["class_module"]
+        base = importlib.import_module(d["base_module"])
+        assert issubclass(cls, getattr(base, d["base"]))
+        assert list(inspect.signature(getattr(base, d["base"]).forward).parameters) == d["forward_params"]
+        assert [f.name for f in dataclasses.fields(getattr(base, d["output"]))] == d["output_fields"]
+        assert [f.name for f in dataclasses.fields(importlib.import_module(d["types_module"]).Gaussians)] == d["gaussians_fields"]
+        amod = importlib.import_module(a["module"])
+        ref = getattr(amod, a["class"])(getattr(amod, a["cfg_class"])(**a["cfg"]))
+        assert list(inspect.signature(ref.forward).parameters) == a["forward_params"][1:]
+        assert list(ref.state_dict().keys()) == a["state_dict_keys"] and (ref.d_sh, ref.d_in) == (a["d_sh"], a["d_in"])
+        assert [f.name for f in dataclasses.fields(getattr(amod, a["container"]))] == a["container_fields"]
+        print("ok")
+    """)
+    assert out.strip().endswith("ok")
+
+
+def test_install_registers_the_fused_decoder_under_the_reference_key(standin):
+    out = _run(standin, """
         import splatter360_amd
         cls = splatter360_amd.install()
         from src.model.decoder import DECODERS, get_decoder
@@ -81,8 +173,8 @@ def test_install_registers_the_fused_decoder_under_the_reference_key():
     assert out.strip().endswith("ok")
 
 
-def test_lazy_install_patches_when_the_reference_imports_its_decoder_package():
-    out = _run("""
+def test_lazy_install_patches_when_the_reference_imports_its_decoder_package(standin):
+    out = _run(standin, """
         import splatter360_amd
         assert splatter360_amd.install(lazy=True) is None
         assert "src.model.decoder" not in sys.modules
@@ -94,11 +186,11 @@ def test_lazy_install_patches_when_the_reference_imports_its_decoder_package():
     assert out.strip().endswith("ok")
 
 
-def test_lazy_install_survives_a_competing_finder_that_resolves_src_itself():
+def test_lazy_install_survives_a_competing_finder_that_resolves_src_itself(standin):
     """jaxtyping's install_import_hook (src/main.py:22-36) puts its own finder at sys.meta_path[0] and resolves `src.*`
     through PathFinder directly, so the lazy patcher never sees `src.model.decoder`.  Emulated here; the registry must still be
     patched by the time the imports of that `with` block are over (any non-`src` import after the package triggers it)."""
-    out = _run("""
+    out = _run(standin, """
         import importlib.abc, importlib.machinery
         import splatter360_amd
         assert splatter360_amd.install(lazy=True) is None
@@ -120,22 +212,16 @@ def test_lazy_install_survives_a_competing_finder_that_resolves_src_itself():
 
 
 ADAPTER_PRELUDE = textwrap.dedent("""
-    # the adapter module's own imports under the Appendix-B stubs: e3nn is absent, so rotate_sh's module is a stub (its import
-    # is what pulls e3nn in, src/misc/sh_rotation.py:1-8); the common package's __init__ is not executed
     import torch
-    shr = types.ModuleType("src.misc.sh_rotation")
-    shr.rotate_sh = lambda sh, rotations: sh
-    sys.modules["src.misc.sh_rotation"] = shr
-    m = types.ModuleType("src.model.encoder.common"); m.__path__ = [REF + "/src/model/encoder/common"]; sys.modules["src.model.encoder.common"] = m
 """)
 
 
-def test_install_adapter_replaces_the_class_the_encoder_instantiates():
+def test_install_adapter_replaces_the_class_the_encoder_instantiates(standin):
     """install(adapter=True) BEFORE the reference imports its encoder: the module that defines GaussianAdapterERP
     (gaussian_adapter_erp.py:33) is patched as it loads, so the encoder's own `from .common.gaussian_adapter_erp import
     GaussianAdapterERP` (encoder_costvolume.py:19, instantiated at :185) binds the replacement — a subclass of the reference's class
     with its constructor, `d_sh` / `d_in` and `sh_mask`, returning the reference's own adapter-side container."""
-    out = _run(ADAPTER_PRELUDE + textwrap.dedent("""
+    out = _run(standin, ADAPTER_PRELUDE + textwrap.dedent("""
         import splatter360_amd
         splatter360_amd.install(lazy=True, adapter=True)
         assert "src.model.encoder.common.gaussian_adapter_erp" not in sys.modules
@@ -168,8 +254,8 @@ def test_install_adapter_replaces_the_class_the_encoder_instantiates():
     assert out.strip().endswith("ok")
 
 
-def test_install_adapter_after_the_encoder_was_imported_patches_the_bound_name_too():
-    out = _run(ADAPTER_PRELUDE + textwrap.dedent("""
+def test_install_adapter_after_the_encoder_was_imported_patches_the_bound_name_too(standin):
+    out = _run(standin, ADAPTER_PRELUDE + textwrap.dedent("""
         import importlib
         amod = importlib.import_module("src.model.encoder.common.gaussian_adapter_erp")
         # a stand-in for the encoder module that already executed its `from .common.gaussian_adapter_erp import GaussianAdapterERP`
