@@ -91,14 +91,17 @@ def source_hash() -> str:
     return h.hexdigest()[:16]
 
 
-def build(force: bool = False, verbose: bool = False) -> Path:
-    """hipcc --offload-arch=gfx950 ... -> splatter360_amd/libs360.so (in-tree)."""
-    if not force and not needs_build():
+def build(force: bool = False, verbose: bool = False, out: Path = None, extra=()) -> Path:
+    """hipcc --offload-arch=gfx950 ... -> splatter360_amd/libs360.so (in-tree), or -> `out` (objects beside it) with the further
+    compiler flags `extra` — a schedule variant of the same sources (tests/test_gpu_split_parity.py builds one into a temporary
+    directory)."""
+    target = LIB_PATH if out is None else Path(out)
+    if out is None and not force and not needs_build():
         return LIB_PATH
-    extra = os.environ.get("S360_HIPCC_EXTRA", "").split()
+    extra = [*os.environ.get("S360_HIPCC_EXTRA", "").split(), *extra]
     from concurrent.futures import ThreadPoolExecutor
-    objdir = _PKG / "build"
-    objdir.mkdir(exist_ok=True)
+    objdir = _PKG / "build" if out is None else target.parent / "build"
+    objdir.mkdir(parents=True, exist_ok=True)
 
     def compile_one(src: str):
         obj = objdir / (src + ".o")
@@ -114,14 +117,14 @@ def build(force: bool = False, verbose: bool = False) -> Path:
             print(r.stdout, r.stderr)
         if r.returncode:
             raise RuntimeError("hipcc failed building libs360.so:\n" + r.stderr[-4000:])
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", *[str(o) for o, _, _ in results], "-o", str(LIB_PATH)]
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", *[str(o) for o, _, _ in results], "-o", str(target)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if verbose or r.returncode:
         print(" ".join(cmd))
         print(r.stdout, r.stderr)
     if r.returncode:
         raise RuntimeError("hipcc failed linking libs360.so:\n" + r.stderr[-4000:])
-    return LIB_PATH
+    return target
 
 
 _lib = None

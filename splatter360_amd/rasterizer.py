@@ -381,6 +381,17 @@ class RasterState:
         correct build; the tests and bench.py assert it stays 0."""
         return int(self.header()[7].item())
 
+    def mopup_items(self) -> int:
+        """Host read, after the forward and before the backward (S360_FLAG_SPLIT_LISTS): how many of the header[6] queued segment work
+        items (seg_info) no phase-2 worker of k_render claimed (S360_SEG_CLAIM clear), i.e. the items the mop-up launch
+        k_render_tail composited.  0 on most calls of the product build (it depends on timing); every item on a build with
+        -DS360_P2_GRID=0."""
+        n = int(self.header()[6].item())
+        if n == 0:
+            return 0
+        second = self._arr(self.layout.seg_info, 2 * n, torch.int32).view(n, 2)[:, 1].to(torch.int64)
+        return int(((second & 0x80000000) == 0).sum().item())
+
     def num_rendered(self) -> int:
         """Host read of num_instances (synchronises)."""
         return self._read_header()[0]

@@ -83,3 +83,103 @@ def check_instance_slots(slot_base, slot_pair, tiles_touched, L):
     sp = np.asarray(slot_pair).reshape(-1)[:L].astype(np.int64) & 0xFFFFFFFF
     np.testing.assert_array_equal(sp & 0x7FFFFFFF, owner)
     np.testing.assert_array_equal(sp >> 31, (tt[owner] > 32).astype(np.int64))      # bit 31: a slot of a pair that owns more than 32
+
+
+# ------------------------------------------------------------------------------ split lists: host model + designed scenes
+# Mirrors of the constants of S360_FLAG_SPLIT_LISTS (splatter360_amd/csrc/s360_device.h, s360_forward.hip); tests/test_split_model.py
+# pins them to the sources, so that a retune cannot silently desynchronise the model below.
+SORT_SHORT, SORT_CHUNK = 2048, 4096
+SEG_HEAD, SEG_LEN, SEG_MIN_REST = 1024, 512, 512
+SEG_PER_CHUNK, SEG_K0 = SORT_CHUNK // SEG_LEN, SEG_HEAD // SEG_LEN
+SEG_T_FAR = 1.0 / 16.0
+SUB_W = 8                      # four 8x8 quadrants per 16x16 tile: quadrant w has its origin at (8 (w & 1), 8 (w >> 1))
+SPLIT_MARGIN = 0.02            # |T / SEG_T_FAR - 1| below this: the decision may fall either way in float32 (one 1/255 accept flip is 0.4 %)
+
+
+def seg_slots(cap: int) -> int:
+    """s360_device.h seg_slots: the segment slots of a call without S360Params.max_segments."""
+    return SEG_PER_CHUNK * (cap // 2048 + 1)
+
+
+def chunk_table(ranges):
+    """k_tile_scan's chunk_start[]: sort chunks of the lists longer than SORT_SHORT in front of every tile (tile index order)."""
+    import numpy as np
+    n = np.diff(np.asarray(ranges, np.int64), axis=1)[:, 0]
+    nch = np.where(n > SORT_SHORT, (n + SORT_CHUNK - 1) // SORT_CHUNK, 0)
+    return np.concatenate([[0], np.cumsum(nch)]).astype(np.int64)
+
+
+def split_model(ranges, values, xy, conic_opacity, h: int, w: int, n_slots: int):
+    """Host model of k_render's hand-over decision (s360_forward.hip, the `split_at` / SEG_T_FAR test) for one call of V images.
+
+    ranges / values / xy / conic_opacity: tile ranges over the call's global tile index t = v T + tile (T tiles per image, image-major,
+    as k_tile_scan numbers them — chunk_start runs across the images), the sorted list of record indices, and per record its pixel
+    centre and conic + opacity (one image: the oracle's forward outputs; V images: the per-image records stacked, v P + g).
+    A (tile, quadrant) hands the rest of its list over iff the list has more than SORT_SHORT and at least SEG_HEAD + SEG_MIN_REST
+    entries, some pixel of the quadrant inside the image has not stopped and has T >= SEG_T_FAR after the first SEG_HEAD entries
+    (the oracle's alpha / stop rule, float64), and the tile's segments fit: SEG_PER_CHUNK chunk_start[t] + ceil(n / SEG_LEN) <= n_slots.
+    Returns dict(split=[tiles, 4] bool, clear=[tiles, 4] bool — False where T lands within SPLIT_MARGIN of SEG_T_FAR —, t_far=[tiles, 4]
+    the largest live transmittance after the head (0 where none), n_split (header[5]), n_items (header[6]), chunk_start)."""
+    import numpy as np
+    ranges = np.asarray(ranges, np.int64)
+    nt = ranges.shape[0]
+    gx = (w + 15) // 16
+    T_img = gx * ((h + 15) // 16)
+    assert nt % T_img == 0
+    cs = chunk_table(ranges)
+    split = np.zeros((nt, 4), bool)
+    clear = np.ones((nt, 4), bool)
+    t_far = np.zeros((nt, 4))
+    n_items = 0
+    xy = np.asarray(xy, np.float64)
+    co = np.asarray(conic_opacity, np.float64)
+    for t in range(nt):
+        s, e = int(ranges[t, 0]), int(ranges[t, 1])
+        n = e - s
+        if not (n > SORT_SHORT and n >= SEG_HEAD + SEG_MIN_REST):
+            continue
+        ids = np.asarray(values[s:s + SEG_HEAD], np.int64)
+        ty, tx = divmod(t % T_img, gx)
+        fits = SEG_PER_CHUNK * int(cs[t]) + (n + SEG_LEN - 1) // SEG_LEN <= n_slots
+        for q in range(4):
+            lx, ly = np.meshgrid(np.arange(SUB_W), np.arange(64 // SUB_W))
+            px = (tx * 16 + 8 * (q & 1) + lx).reshape(-1)
+            py = (ty * 16 + 8 * (q >> 1) + ly).reshape(-1)
+            inside = (px < w) & (py < h)
+            if not inside.any():
+                continue
+            px, py = px[inside].astype(np.float64), py[inside].astype(np.float64)
+            dx = xy[ids, 0][:, None] - px[None]
+            dy = xy[ids, 1][:, None] - py[None]
+            c = co[ids]
+            power = -0.5 * (c[:, 0:1] * dx * dx + c[:, 2:3] * dy * dy) - c[:, 1:2] * dx * dy
+            alpha = np.minimum(0.99, c[:, 3:4] * np.exp(power))
+            alpha = np.where((power > 0) | (alpha < 1.0 / 255.0), 0.0, alpha)
+            T = np.prod(1.0 - alpha, axis=0)           # monotone: a pixel stopped in the head iff its full product fell below 1e-4
+            live = T >= 1e-4
+            tf = float(T[live].max()) if live.any() else 0.0
+            t_far[t, q] = tf
+            clear[t, q] = abs(tf / SEG_T_FAR - 1.0) > SPLIT_MARGIN
+            if tf >= SEG_T_FAR and fits:
+                split[t, q] = True
+                n_items += (n + SEG_LEN - 1) // SEG_LEN - SEG_K0
+    return dict(split=split, clear=clear, t_far=t_far, n_split=int(split.sum()), n_items=int(n_items), chunk_start=cs)
+
+
+def pixel_splats(px, py, sigma_px, z, h: int, w: int):
+    """means3D / cov6 of splats centred on pixel coordinates (px, py) with an isotropic screen footprint of sigma_px pixels (before
+    the rasteriser's 0.3 low-pass), at view depth z, for the camera of small_front_scene (identity view, tanfov 1, h x w)."""
+    import numpy as np
+    px, py, z = (np.asarray(a, np.float64) for a in (px, py, z))
+    sig = np.broadcast_to(np.asarray(sigma_px, np.float64), px.shape)
+    fx, fy = w / 2.0, h / 2.0
+    means = np.stack([((2 * px + 1) / w - 1) * z, ((2 * py + 1) / h - 1) * z, z], 1)
+    sx, sy = sig * z / fx, sig * z / fy
+    cov6 = np.zeros((px.shape[0], 6))
+    cov6[:, 0], cov6[:, 3], cov6[:, 5] = sx * sx, sy * sy, (1e-3 * sx) ** 2
+    return means, cov6
+
+
+def tile_box(tx: int, ty: int, r: int = 4):
+    """Centres whose 3-sigma rectangle (radius r pixels) touches tile (tx, ty) only (getRect's rounding): [x0, x1) x [y0, y1)."""
+    return 16 * tx + r, 16 * tx + 17 - r, 16 * ty + r, 16 * ty + 17 - r
