@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define S360_ABI_VERSION 22
+#define S360_ABI_VERSION 23
 #define S360_MAX_VIEWS 8
 #define S360_TILE 16
 
@@ -506,6 +506,24 @@ int s360_cube2erp_forward(const float* faces, const float* grid, float* erp, int
 int s360_cube2erp_backward(const float* d_erp, const float* grid, float* d_faces,
                            int32_t channels, int32_t face_w, int32_t equ_h, int32_t equ_w,
                            const int32_t* face_map_host, const int64_t* strides_host, void* stream);
+
+/*
+ * Mean SSIM per image for the evaluation step: replaces compute_ssim (src/evaluation/metrics.py:38-54), which copies every
+ * face to the host and calls skimage.metrics.structural_similarity(gt, hat, win_size=11, gaussian_weights=True,
+ * channel_axis=0, data_range=1.0) one image at a time.  Same algorithm:
+ *   Gaussian window sigma 1.5, truncate 3.5 (11 taps, normalised);  sample covariance, cov_norm = 121 / 120;
+ *   C1 = (0.01 * 1)^2, C2 = (0.03 * 1)^2;
+ *   S = (2 mx my + C1)(2 vxy + C2) / ((mx^2 + my^2 + C1)(vx + vy + C2)) per pixel;
+ *   per channel the float64 mean of S over the interior rows / columns [5, H-5) x [5, W-5) (the reflect-padded border is
+ *   cropped away and never reaches it), per image the mean over channels.  Inputs are not clipped.
+ *   pred, gt[n_images, channels, height, width] contiguous float32 (the score is symmetric in them);  ssim_out[n_images] float32.
+ *   height or width < 11: S360_E_BADARG (skimage raises ValueError there).
+ * workspace == NULL: *workspace_bytes receives the size of the workspace (8-byte aligned, device memory) and nothing runs.
+ * Otherwise two kernels run on `stream`; no atomics: the result is bit-identical from call to call, and image i's score does
+ * not depend on the other images of the call.
+ */
+int s360_ssim(const float* pred, const float* gt, int32_t n_images, int32_t channels, int32_t height, int32_t width,
+              float* ssim_out, void* workspace, size_t* workspace_bytes, void* stream);
 
 /*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an

@@ -11,6 +11,10 @@ together — in ONE rasteriser call of this library instead of twelve Python-loo
     import splatter360_amd; splatter360_amd.install()        # one line before the reference's `main` runs, or
     PYTHONPATH=/path/to/repo/examples/site python -m src.main +experiment=hm3d ...   # examples/site/sitecustomize.py does it lazily
 
+install(metrics=True) also rebinds the evaluation step's `compute_ssim` (src/evaluation/metrics.py:38-54: skimage, one image at a
+time on the host) to metrics.compute_ssim (one SSIM kernel per batch on the GPU; CPU tensors still go to the replaced function),
+in src.evaluation.metrics and in every module that imported the name: now if they are imported, else by an import hook.
+
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
 """
@@ -188,11 +192,108 @@ def install_adapter(**aopts):
     return None
 
 
-def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, **opts):
+METRICS_MODULE = "src.evaluation.metrics"                              # defines compute_ssim (:38-54)
+METRICS_USERS = ("src.model.model_wrapper_erp",                        # `from ..evaluation.metrics import ... compute_ssim` (:18)
+                 "src.model.model_wrapper_cubemaps",                   # (:19)
+                 "src.evaluation.metric_computer")                     # (:12)
+METRICS_NAME = "compute_ssim"
+
+
+def _native_compute_ssim(replaced):
+    """compute_ssim with the reference's signature: the SSIM kernel for GPU tensors, the replaced function otherwise."""
+    from . import metrics as _metrics
+
+    def compute_ssim(ground_truth, predicted):
+        if ground_truth.is_cuda and predicted.is_cuda:
+            return _metrics.compute_ssim(ground_truth, predicted)
+        return replaced(ground_truth, predicted)
+
+    compute_ssim.replaced = replaced
+    compute_ssim.__doc__ = _metrics.compute_ssim.__doc__
+    return compute_ssim
+
+
+def _patch_metrics(mod):
+    """Rebind compute_ssim in the module that defines it and in every already-imported module that bound the name with
+    `from ... import` (modules imported later bind the replacement themselves).  Idempotent."""
+    cur = getattr(mod, METRICS_NAME)
+    fn = cur if getattr(cur, "replaced", None) is not None else _native_compute_ssim(cur)
+    setattr(mod, METRICS_NAME, fn)
+    for user in METRICS_USERS:
+        um = sys.modules.get(user)
+        if um is not None and getattr(um, METRICS_NAME, None) is fn.replaced:
+            setattr(um, METRICS_NAME, fn)
+    return fn
+
+
+class _MetricsPatcher(importlib.abc.MetaPathFinder):
+    """install(metrics=True) before the reference's metrics module is imported: patch it as it is first loaded, and — for an
+    import made through a finder ahead of this one (jaxtyping's hook at sys.meta_path[0] resolves `src.*` through PathFinder
+    itself, see _LazyPatcher) — at the next import this finder is asked about, before the evaluation step can call it."""
+
+    def __init__(self):
+        self.busy = False
+
+    def _done(self, mod):
+        if self in sys.meta_path:
+            sys.meta_path.remove(self)
+        _patch_metrics(mod)
+
+    def find_spec(self, fullname, path, target=None):
+        if self.busy:
+            return None
+        mod = sys.modules.get(METRICS_MODULE)
+        if mod is not None and hasattr(mod, METRICS_NAME):        # imported behind this finder's back: patch late
+            self.busy = True
+            try:
+                self._done(mod)
+            except Exception as ex:      # never let the failure surface from an unrelated import
+                import warnings
+                warnings.warn(f"splatter360_amd.install(metrics=True): patching {METRICS_MODULE}.{METRICS_NAME} failed ({ex!r}); "
+                              "the reference keeps its own SSIM.", RuntimeWarning)
+            finally:
+                self.busy = False
+            return None
+        if fullname != METRICS_MODULE:
+            return None
+        self.busy = True
+        try:
+            spec = importlib.util.find_spec(fullname)
+        finally:
+            self.busy = False
+        if spec is None or spec.loader is None:
+            return None
+        loader, finder = spec.loader, self
+
+        class _Loader(importlib.abc.Loader):
+            def create_module(self, s):
+                return loader.create_module(s)
+
+            def exec_module(self, module):
+                loader.exec_module(module)
+                finder._done(module)
+
+        spec.loader = _Loader()
+        return spec
+
+
+def install_metrics():
+    """The metrics half of install(metrics=True): rebind compute_ssim now if the reference's metrics module is imported, else as
+    soon as it is (import hook).  Returns the patched function or None."""
+    mod = sys.modules.get(METRICS_MODULE)
+    if mod is not None and hasattr(mod, METRICS_NAME):
+        return _patch_metrics(mod)
+    if not any(isinstance(f, _MetricsPatcher) for f in sys.meta_path):
+        sys.meta_path.insert(0, _MetricsPatcher())
+    return None
+
+
+def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
     HBM); adapter_options: sh_rotation / differentiable_means / lazy of lazy.make_adapter_class.
+    metrics=True: ALSO rebind the evaluation step's compute_ssim to the SSIM kernel (install_metrics; off by default).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -201,6 +302,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     opts: views_per_group (6), shared_campos (None = checked per group with one small read per forward), check ("sync"), glue."""
     if adapter:
         install_adapter(**(adapter_options or {}))
+    if metrics:
+        install_metrics()
     if lazy:
         if REGISTRY_MODULE in sys.modules:
             return _patch(sys.modules[REGISTRY_MODULE], **opts)
@@ -211,8 +314,17 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
 
 
 def uninstall() -> None:
-    """Put the reference's own decoder class back (and drop a pending lazy hook)."""
-    sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, (_LazyPatcher, _AdapterPatcher))]
+    """Put the reference's own decoder class, adapter and compute_ssim back (and drop pending import hooks)."""
+    sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher))]
+    mmod = sys.modules.get(METRICS_MODULE)
+    if mmod is not None:
+        cur = getattr(mmod, METRICS_NAME, None)
+        if getattr(cur, "replaced", None) is not None:
+            setattr(mmod, METRICS_NAME, cur.replaced)
+            for user in METRICS_USERS:
+                um = sys.modules.get(user)
+                if um is not None and getattr(um, METRICS_NAME, None) is cur:
+                    setattr(um, METRICS_NAME, cur.replaced)
     amod = sys.modules.get(ADAPTER_MODULE)
     if amod is not None:
         cur = getattr(amod, ADAPTER_NAME, None)
