@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define S360_ABI_VERSION 23
+#define S360_ABI_VERSION 24
 #define S360_MAX_VIEWS 8
 #define S360_TILE 16
 
@@ -501,9 +501,16 @@ int s360_cube2erp_forward(const float* faces, const float* grid, float* erp, int
                           int32_t face_w, int32_t equ_h, int32_t equ_w,
                           const int32_t* face_map_host, const int64_t* strides_host, void* stream);
 
-/* Adjoint of the stitch: d_faces[6,C,fw,fw] (same face order / face_map as forward) is
- * ZEROED then accumulated with float atomics (non-deterministic summation order). */
-int s360_cube2erp_backward(const float* d_erp, const float* grid, float* d_faces,
+/* Adjoint of the stitch (ABI v24): every element of d_faces[6,C,fw,fw] (same face order / face_map as forward) is WRITTEN,
+ * no memset and no atomics: the result is bit-identical from call to call.
+ *   plan_offsets[6*fw*fw + 1], plan_entries[plan_offsets[6*fw*fw]] (device, int32): the grid's inverse in Cube2Equirec's
+ *   SLOT space — texel t = s*fw*fw + y*fw + x of slot s is read by the pixels plan_entries[plan_offsets[t] .. plan_offsets[t+1])
+ *   as pixel*8 + tap (tap = 4*dz + 2*dy + dx), sorted by pixel; every in-range tap appears once, weight-0 taps included
+ *   (splatter360_amd/stitch.py adjoint_plan builds it from the grid; one plan serves every face_map).  The kernel recomputes
+ *   each weight from `grid` with the forward's float32 expressions and sums a texel's entries in plan order.  A face that no
+ *   slot reads gets zeros.  equ_h * equ_w * 8 must fit in int32.  strides_host must be NULL (dense output only). */
+int s360_cube2erp_backward(const float* d_erp, const float* grid, const int32_t* plan_offsets,
+                           const int32_t* plan_entries, float* d_faces,
                            int32_t channels, int32_t face_w, int32_t equ_h, int32_t equ_w,
                            const int32_t* face_map_host, const int64_t* strides_host, void* stream);
 

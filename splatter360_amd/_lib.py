@@ -32,7 +32,7 @@ FLAG_ATOMIC_GRADS = 256
 FLAG_SPLIT_LISTS = 512
 FLAG_RAW_INPUTS = 1024
 FLAG_COOP_WALK = 2048
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 class S360Params(C.Structure):
@@ -188,7 +188,7 @@ def lib() -> C.CDLL:
     l.s360_cube2erp_forward.restype = C.c_int
     l.s360_cube2erp_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_int64), vp]
     l.s360_cube2erp_backward.restype = C.c_int
-    l.s360_cube2erp_backward.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_int64), vp]
+    l.s360_cube2erp_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_int64), vp]
     l.s360_ssim.restype = C.c_int
     l.s360_ssim.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, C.POINTER(sz), vp]
     l.s360_count_backward_slots.restype = C.c_int

@@ -5,12 +5,19 @@
 // (/root/reference/src/geometry/layers.py:108-116): input [C, D=6, fw, fw], grid (x=u, y=v, z=face),
 // mode trilinear, padding_mode "border", align_corners=True:
 //   i = ((g + 1) / 2) * (size - 1), clipped to [0, size-1]; 8 corner taps with the usual
-//   (1-f) / f weights, taps outside the volume contribute nothing.
+//   (1-f) / f weights; a tap outside the volume is skipped, an in-range tap is added even with weight 0
+//   (so an inf texel under a 0 weight gives NaN, as in torch).
 // The face-z coordinate lands on an integer face +- 6e-8, so up to two faces are blended with
 // a ~1e-7 weight — reproduced here rather than "fixed" (SURVEY.md §8 a10).
+//
+// The adjoint has no atomics: the caller passes the grid's inverse (a CSR "plan", built once per grid on the host:
+// splatter360_amd/stitch.py adjoint_plan) that lists, per texel of the slot-space volume, the (pixel, tap) pairs that read it,
+// sorted by pixel.  One thread per (texel, channel) recomputes each weight with the forward's own expressions (stitch_frac)
+// and sums in plan order: gradients are bit-reproducible.
 #include "s360_device.h"
 #include "s360_prof.h"
 
+#include <climits>
 #include <mutex>
 #include <vector>
 
@@ -27,41 +34,63 @@ __device__ __forceinline__ float unnorm_clip(float g, int size) {
     return fminf((float)(size - 1), fmaxf(i, 0.0f));
 }
 
+// Corner (x0, y0, z0) and the per-axis weights of pixel i: shared by both kernels so the adjoint's weights are the forward's bits.
+struct StitchFrac {
+    int x0, y0, z0;
+    float wx[2], wy[2], wz[2];
+};
+
+__device__ __forceinline__ StitchFrac stitch_frac(const float* __restrict__ grid, size_t i, int fw) {
+    const float ix = unnorm_clip(grid[3 * i], fw), iy = unnorm_clip(grid[3 * i + 1], fw), iz = unnorm_clip(grid[3 * i + 2], 6);
+    const float x0f = floorf(ix), y0f = floorf(iy), z0f = floorf(iz);
+    const float fx = ix - x0f, fy = iy - y0f, fz = iz - z0f;
+    StitchFrac f;
+    f.x0 = (int)x0f;
+    f.y0 = (int)y0f;
+    f.z0 = (int)z0f;
+    f.wx[0] = 1.0f - fx;
+    f.wx[1] = fx;
+    f.wy[0] = 1.0f - fy;
+    f.wy[1] = fy;
+    f.wz[0] = 1.0f - fz;
+    f.wz[1] = fz;
+    return f;
+}
+
 __global__ __launch_bounds__(S360_BLOCK) void k_cube2erp_fwd(const float* __restrict__ faces, const float* __restrict__ grid,
                                                             float* __restrict__ erp, int C, int fw, int eh, int ew, FaceMap fm) {
     const size_t n = (size_t)eh * ew;
     const size_t i = (size_t)blockIdx.x * S360_BLOCK + threadIdx.x;
     if (i >= n) return;
-    const float ix = unnorm_clip(grid[3 * i], fw), iy = unnorm_clip(grid[3 * i + 1], fw), iz = unnorm_clip(grid[3 * i + 2], 6);
-    const float x0f = floorf(ix), y0f = floorf(iy), z0f = floorf(iz);
-    const int x0 = (int)x0f, y0 = (int)y0f, z0 = (int)z0f;
-    const float fx = ix - x0f, fy = iy - y0f, fz = iz - z0f;
-    const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy}, wz[2] = {1.0f - fz, fz};
+    const StitchFrac f = stitch_frac(grid, i, fw);
     // The eight taps once per pixel (offset + weight), then per channel eight INDEPENDENT loads in flight before the first use
     // (the per-channel, per-tap branches of the plain loop nest issued one dependent load at a time: 19 us for 19 MB).  A tap
-    // outside the volume keeps a clamped (valid) address and weight 0: acc + v * 0 == acc for the finite pixels of a render, in the
-    // same dz, dy, dx order as before — bit-identical output.
+    // outside the volume keeps a clamped (valid) address so its load is safe, and its product is not added (a select: acc + v * 0
+    // would turn an inf texel into NaN where grid_sample skips the tap).  For finite inputs this is the same sum in the same
+    // dz, dy, dx order as the old "weight 0" form: acc never holds -0, so dropping a +-0 addend changes no bit.
     size_t off[8];
     float wgt[8];
+    unsigned in_mask = 0u;
 #pragma unroll
     for (int dz = 0; dz < 2; ++dz) {
-        const int z = z0 + dz, zc = min(max(z, 0), 5);
+        const int z = f.z0 + dz, zc = min(max(z, 0), 5);
         const bool zin = z >= 0 && z <= 5;
         const size_t fo = (size_t)fm.src[zc] * fm.fs;
         const bool fl = fm.flip[zc] != 0;
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy) {
-            const int y = y0 + dy, yc = min(max(y, 0), fw - 1);
+            const int y = f.y0 + dy, yc = min(max(y, 0), fw - 1);
             const bool yin = y >= 0 && y < fw;
             const int yy = fl ? fw - 1 - yc : yc;
 #pragma unroll
             for (int dx = 0; dx < 2; ++dx) {
-                const int x = x0 + dx, xc = min(max(x, 0), fw - 1);
+                const int x = f.x0 + dx, xc = min(max(x, 0), fw - 1);
                 const bool xin = x >= 0 && x < fw;
                 const int xx = fl ? fw - 1 - xc : xc;
                 const int k = 4 * dz + 2 * dy + dx;
                 off[k] = fo + (size_t)yy * fm.rs + xx;
-                wgt[k] = (zin && yin && xin) ? wx[dx] * wy[dy] * wz[dz] : 0.0f;
+                wgt[k] = f.wx[dx] * f.wy[dy] * f.wz[dz];
+                in_mask |= (zin && yin && xin) ? 1u << k : 0u;
             }
         }
     }
@@ -72,44 +101,60 @@ __global__ __launch_bounds__(S360_BLOCK) void k_cube2erp_fwd(const float* __rest
         for (int k = 0; k < 8; ++k) v[k] = fp[off[k]];
         float acc = 0.f;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) acc += v[k] * wgt[k];
+        for (int k = 0; k < 8; ++k) acc = (in_mask >> k) & 1u ? acc + v[k] * wgt[k] : acc;
         erp[(size_t)c * n + i] = acc;
     }
 }
 
+// One thread per (texel of the dense [6,C,fw,fw] output, channel = blockIdx.y).  Output face f gathers from every slot s whose
+// source is f (one for a permutation; none leaves the texel 0), reading slot s's texel under s's flip, then that texel's plan
+// entries pixel * 8 + tap in order.  Every output element is written: no memset.
 __global__ __launch_bounds__(S360_BLOCK) void k_cube2erp_bwd(const float* __restrict__ d_erp, const float* __restrict__ grid,
+                                                            const int32_t* __restrict__ plan_off, const int32_t* __restrict__ plan_ent,
                                                             float* __restrict__ d_faces, int C, int fw, int eh, int ew, FaceMap fm) {
+    const int ff = fw * fw;
+    const int t = (int)(blockIdx.x * S360_BLOCK + threadIdx.x);
+    if (t >= 6 * ff) return;
+    const int c = (int)blockIdx.y;
     const size_t n = (size_t)eh * ew;
-    const size_t i = (size_t)blockIdx.x * S360_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const float ix = unnorm_clip(grid[3 * i], fw), iy = unnorm_clip(grid[3 * i + 1], fw), iz = unnorm_clip(grid[3 * i + 2], 6);
-    const float x0f = floorf(ix), y0f = floorf(iy), z0f = floorf(iz);
-    const int x0 = (int)x0f, y0 = (int)y0f, z0 = (int)z0f;
-    const float fx = ix - x0f, fy = iy - y0f, fz = iz - z0f;
-    const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy}, wz[2] = {1.0f - fz, fz};
-    for (int c = 0; c < C; ++c) {
-        const float g = d_erp[(size_t)c * n + i];
+    const int face = t / ff, r = t - face * ff, y = r / fw, x = r - y * fw;
+    const float* gc = d_erp + (size_t)c * n;
+    float acc = 0.f;
+    for (int s = 0; s < 6; ++s) {
+        if (fm.src[s] != face) continue;
+        const int ys = fm.flip[s] ? fw - 1 - y : y, xs = fm.flip[s] ? fw - 1 - x : x;
+        const int ts = s * ff + ys * fw + xs;
+        const int e1 = plan_off[ts + 1];
+        int e = plan_off[ts];
+        // Entries in batches of 8: every load of a batch (entry, grid, d_erp) is in flight before the first use.  The texels under
+        // the poles have up to ~2 900 entries, and one chain of dependent loads per entry made them the kernel's whole duration.
+        // The sum is still taken one entry at a time in plan order.
+        for (; e + 8 <= e1; e += 8) {
+            int pk[8];
+            float g[8], w[8];
 #pragma unroll
-        for (int dz = 0; dz < 2; ++dz) {
-            const int z = z0 + dz;
-            if (z < 0 || z > 5) continue;
-            float* fp = d_faces + (size_t)fm.src[z] * fm.fs + (size_t)c * fm.cs;
+            for (int j = 0; j < 8; ++j) pk[j] = plan_ent[e + j];
 #pragma unroll
-            for (int dy = 0; dy < 2; ++dy) {
-                const int y = y0 + dy;
-                if (y < 0 || y >= fw) continue;
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) {
-                    const int x = x0 + dx;
-                    if (x < 0 || x >= fw) continue;
-                    const float w = wx[dx] * wy[dy] * wz[dz];
-                    if (w == 0.f) continue;
-                    const int yy = fm.flip[z] ? fw - 1 - y : y, xx = fm.flip[z] ? fw - 1 - x : x;
-                    atomicAdd(&fp[(size_t)yy * fm.rs + xx], g * w);
-                }
+            for (int j = 0; j < 8; ++j) {
+                const size_t p = (size_t)(pk[j] >> 3);
+                const int k = pk[j] & 7;
+                const StitchFrac f = stitch_frac(grid, p, fw);
+                w[j] = f.wx[k & 1] * f.wy[(k >> 1) & 1] * f.wz[k >> 2];
+                g[j] = gc[p];
             }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc += g[j] * w[j];
+        }
+        for (; e < e1; ++e) {
+            const int pk = plan_ent[e];
+            const size_t p = (size_t)(pk >> 3);
+            const int k = pk & 7;
+            const StitchFrac f = stitch_frac(grid, p, fw);
+            const float w = f.wx[k & 1] * f.wy[(k >> 1) & 1] * f.wz[k >> 2];
+            acc += gc[p] * w;
         }
     }
+    d_faces[((size_t)face * C + c) * ff + r] = acc;
 }
 
 static bool make_face_map(const int32_t* face_map_host, const int64_t* strides_host, int C, int fw, FaceMap& fm) {
@@ -142,19 +187,22 @@ extern "C" int s360_cube2erp_forward(const float* faces, const float* grid, floa
     return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
 }
 
-extern "C" int s360_cube2erp_backward(const float* d_erp, const float* grid, float* d_faces, int32_t channels,
-                                      int32_t face_w, int32_t equ_h, int32_t equ_w, const int32_t* face_map_host,
-                                      const int64_t* strides_host, void* stream) {
-    if (!d_erp || !grid || !d_faces || channels < 1 || face_w < 1 || equ_h < 1 || equ_w < 1) return S360_E_BADARG;
-    if (strides_host) return S360_E_UNSUPPORTED;  // the adjoint writes a dense [6,C,fw,fw] tensor it zeroes itself
+extern "C" int s360_cube2erp_backward(const float* d_erp, const float* grid, const int32_t* plan_offsets,
+                                      const int32_t* plan_entries, float* d_faces, int32_t channels, int32_t face_w,
+                                      int32_t equ_h, int32_t equ_w, const int32_t* face_map_host, const int64_t* strides_host,
+                                      void* stream) {
+    if (!d_erp || !grid || !plan_offsets || !plan_entries || !d_faces || channels < 1 || channels > 65535 || face_w < 1 ||
+        equ_h < 1 || equ_w < 1)
+        return S360_E_BADARG;
+    // plan entries are pixel * 8 + tap and texel indices 6 * fw * fw + 1 offsets, both int32
+    if ((long long)equ_h * equ_w * 8 > INT_MAX || 6LL * face_w * face_w + 1 > INT_MAX) return S360_E_BADARG;
+    if (strides_host) return S360_E_UNSUPPORTED;  // the adjoint writes a dense [6,C,fw,fw] tensor
     FaceMap fm;
     if (!make_face_map(face_map_host, strides_host, channels, face_w, fm)) return S360_E_BADARG;
-    const size_t n = (size_t)equ_h * equ_w;
+    const size_t texels = (size_t)6 * face_w * face_w;
     ProfScope ps(PS_STITCH_BWD, (hipStream_t)stream);
-    if (hipMemsetAsync(d_faces, 0, (size_t)6 * channels * face_w * face_w * sizeof(float), (hipStream_t)stream) != hipSuccess)
-        return S360_E_LAUNCH;
-    hipLaunchKernelGGL(k_cube2erp_bwd, dim3((unsigned)((n + S360_BLOCK - 1) / S360_BLOCK)), dim3(S360_BLOCK), 0,
-                       (hipStream_t)stream, d_erp, grid, d_faces, channels, face_w, equ_h, equ_w, fm);
+    hipLaunchKernelGGL(k_cube2erp_bwd, dim3((unsigned)((texels + S360_BLOCK - 1) / S360_BLOCK), (unsigned)channels), dim3(S360_BLOCK),
+                       0, (hipStream_t)stream, d_erp, grid, plan_offsets, plan_entries, d_faces, channels, face_w, equ_h, equ_w, fm);
     return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
 }
 

@@ -2,7 +2,9 @@
 src/geometry/layers.py:41-116, and fuses change_order, src/model/model_wrapper_erp.py:135-158).
 
 The sampling grid is host-side numpy restated from layers.py:60-106 (same float32/float64 mix so
-it is bit-identical; pinned by tests/golden/cube2equirec_*.npz); the gather is one HIP kernel.
+it is bit-identical; pinned by tests/golden/cube2equirec_*.npz); the gather is one HIP kernel.  The
+adjoint is a second gather over the grid's inverse (adjoint_plan, built once per grid here): no
+atomics, so gradients through the stitch are bit-reproducible.
 """
 from __future__ import annotations
 
@@ -64,13 +66,52 @@ def sample_grid_numpy(face_w: int, equ_h: int, equ_w: int) -> np.ndarray:
     return np.ascontiguousarray(np.stack([u, v, z], -1).astype(f32))
 
 
+def _unnorm_clip(g: np.ndarray, size: int) -> np.ndarray:
+    """The kernel's float32 unnormalise + border clip (align_corners=True)."""
+    f32 = np.float32
+    i = ((g.astype(f32) + f32(1)) / f32(2)) * f32(size - 1)
+    return np.minimum(f32(size - 1), np.maximum(i, f32(0)))
+
+
+def adjoint_plan(grid: np.ndarray, face_w: int):
+    """The inverse of a sampling grid [H,W,3] (float32) over the [6,fw,fw] slot-space volume, for s360_cube2erp_backward:
+    (offsets int32 [6*fw*fw + 1], entries int32) — texel t = s*fw*fw + y*fw + x is read by the taps
+    entries[offsets[t]:offsets[t+1]] = pixel*8 + (4*dz + 2*dy + dx), sorted by pixel.  Every in-range tap is listed once, weight 0
+    included (grid_sample adds those too); taps outside the volume are not.  It does not depend on the face map."""
+    g = np.ascontiguousarray(grid, dtype=np.float32).reshape(-1, 3)
+    n = g.shape[0]
+    if n * 8 > np.iinfo(np.int32).max:
+        raise ValueError("stitch adjoint plan: equ_h * equ_w * 8 must fit in int32")
+    x0 = np.floor(_unnorm_clip(g[:, 0], face_w)).astype(np.int64)
+    y0 = np.floor(_unnorm_clip(g[:, 1], face_w)).astype(np.int64)
+    z0 = np.floor(_unnorm_clip(g[:, 2], 6)).astype(np.int64)
+    k = np.arange(8)
+    x, y, z = x0[:, None] + (k & 1), y0[:, None] + ((k >> 1) & 1), z0[:, None] + (k >> 2)   # [n, 8] in tap order
+    ok = (x < face_w) & (y < face_w) & (z <= 5)                                              # the lower corners are >= 0
+    tex = ((z * face_w + y) * face_w + x)[ok]
+    tap = np.arange(n * 8, dtype=np.int64).reshape(n, 8)[ok]                                 # pixel*8 + tap, ascending
+    order = np.argsort(tex, kind="stable")                                                   # keeps pixel order per texel
+    texels = 6 * face_w * face_w
+    offsets = np.zeros(texels + 1, np.int64)
+    np.cumsum(np.bincount(tex, minlength=texels), out=offsets[1:])
+    return offsets.astype(np.int32), tap[order].astype(np.int32)
+
+
+@lru_cache(maxsize=4)
+def adjoint_plan_numpy(face_w: int, equ_h: int, equ_w: int):
+    """adjoint_plan of sample_grid_numpy(face_w, equ_h, equ_w), cached like the grid (<= 8 int32 entries per ERP pixel)."""
+    return adjoint_plan(sample_grid_numpy(face_w, equ_h, equ_w), face_w)
+
+
 def _face_map_arr(face_map):
     return None if face_map is None else (C.c_int32 * 6)(*face_map)
 
 
 class _Stitch(torch.autograd.Function):
+    """faces -> ERP through `grid` [eh,ew,3]; `plan` = (offsets, entries) = adjoint_plan(grid) on the same device."""
+
     @staticmethod
-    def forward(ctx, faces, grid, face_map, strides, channels, face_w):
+    def forward(ctx, faces, grid, plan_offsets, plan_entries, face_map, strides, channels, face_w):
         if not faces.is_cuda:
             raise RuntimeError("cube->ERP stitch runs on the GPU only (no CPU path)")
         eh, ew = int(grid.shape[0]), int(grid.shape[1])
@@ -85,26 +126,30 @@ class _Stitch(torch.autograd.Function):
                                                   C.c_void_p(erp.data_ptr()), channels, face_w, eh, ew,
                                                   _face_map_arr(face_map), sarr, st)
         _lib.check(rc, "s360_cube2erp_forward")
-        ctx.save_for_backward(grid)
+        ctx.save_for_backward(grid, plan_offsets, plan_entries)
         ctx.meta = (face_map, strides, channels, face_w, tuple(faces.shape))
         return erp
 
     @staticmethod
     def backward(ctx, d_erp):
-        (grid,) = ctx.saved_tensors
+        grid, offs, ents = ctx.saved_tensors
         face_map, strides, channels, face_w, shape = ctx.meta
         eh, ew = int(grid.shape[0]), int(grid.shape[1])
+        if (offs.dtype, ents.dtype) != (torch.int32, torch.int32) or offs.numel() != 6 * face_w * face_w + 1 \
+                or not (offs.is_cuda and ents.is_cuda and offs.is_contiguous() and ents.is_contiguous()):
+            raise RuntimeError("cube->ERP stitch backward: the adjoint plan does not belong to this grid / device")
         g = d_erp.detach().float().contiguous()
         d_faces = torch.empty((6, channels, face_w, face_w), dtype=torch.float32, device=g.device)
         with torch.cuda.device(g.device):
             st = C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
             rc = _lib.lib().s360_cube2erp_backward(C.c_void_p(g.data_ptr()), C.c_void_p(grid.data_ptr()),
+                                                   C.c_void_p(offs.data_ptr()), C.c_void_p(ents.data_ptr()),
                                                    C.c_void_p(d_faces.data_ptr()), channels, face_w, eh, ew,
                                                    _face_map_arr(face_map), None, st)
         _lib.check(rc, "s360_cube2erp_backward")
         if strides is not None:  # input was [C, fw, 6*fw]
             d_faces = d_faces.permute(1, 2, 0, 3).reshape(shape)
-        return d_faces, None, None, None, None, None
+        return d_faces, None, None, None, None, None, None, None
 
 
 class Cube2Equirec(nn.Module):
@@ -116,6 +161,10 @@ class Cube2Equirec(nn.Module):
         self.face_w, self.equ_h, self.equ_w = face_w, equ_h, equ_w
         grid = torch.from_numpy(sample_grid_numpy(face_w, equ_h, equ_w)).view(1, 1, equ_h, equ_w, 3)
         self.sample_grid = nn.Parameter(grid, requires_grad=False)
+        # the grid's inverse for the backward (not in the state dict: the reference module has only sample_grid)
+        offsets, entries = adjoint_plan_numpy(face_w, equ_h, equ_w)
+        self.register_buffer("plan_offsets", torch.from_numpy(offsets), persistent=False)
+        self.register_buffer("plan_entries", torch.from_numpy(entries), persistent=False)
 
     def forward(self, cube_feat: Tensor) -> Tensor:
         bs, ch, h, w = cube_feat.shape
@@ -124,10 +173,11 @@ class Cube2Equirec(nn.Module):
         x = cube_feat.float().contiguous()
         fw = self.face_w
         strides = (fw, fw * 6 * fw, 6 * fw)
-        return torch.stack([_Stitch.apply(x[b], grid, None, strides, ch, fw) for b in range(bs)])
+        return torch.stack([_Stitch.apply(x[b], grid, self.plan_offsets, self.plan_entries, None, strides, ch, fw) for b in range(bs)])
 
     def stitch_rendered(self, faces: Tensor) -> Tensor:
         """faces[6,C,fw,fw] in the reference's RENDERED order (top, front, left, back, right,
         bottom) -> ERP [C,equ_h,equ_w] = Cube2Equirec(change_order(faces)) without the flip /
         permute / concat copies (model_wrapper_erp.py:393-400)."""
-        return _Stitch.apply(faces, self.sample_grid[0, 0], CHANGE_ORDER_FACE_MAP, None, int(faces.shape[1]), self.face_w)
+        return _Stitch.apply(faces, self.sample_grid[0, 0], self.plan_offsets, self.plan_entries, CHANGE_ORDER_FACE_MAP, None,
+                             int(faces.shape[1]), self.face_w)

@@ -46,6 +46,9 @@ def test_bad_arguments_are_rejected_before_any_gpu_work():
     # null views / images / workspace
     assert lib.s360_forward(C.byref(ok), None, None, None, None, None, None, None, None, None, 0, None) == -1
     assert lib.s360_cube2erp_forward(None, None, None, 3, 64, 128, 256, None, None, None) == -1
+    # ABI v24: the stitch's adjoint takes the grid's inverse (plan offsets + entries); a missing plan is a bad argument
+    assert _lib.ABI_VERSION == 24
+    assert lib.s360_cube2erp_backward(None, None, None, None, None, 3, 64, 128, 256, None, None, None) == -1
     with pytest.raises(RuntimeError):
         _lib.check(-4, "x")
 

@@ -48,9 +48,11 @@ def test_stitch_backward_is_the_adjoint(gpu):
     w = torch.randn(3, eh, ew, device=gpu)
     (mod.stitch_rendered(faces) * w).sum().backward()
     u = torch.randn(6, 3, fw, fw, device=gpu)
-    lhs = (mod.stitch_rendered(u) * w).sum()          # <A u, w>
-    rhs = (u * faces.grad).sum()                      # <u, A^T w>
+    lhs = (mod.stitch_rendered(u).double() * w.double()).sum()          # <A u, w>
+    rhs = (u.double() * faces.grad.double()).sum()                      # <u, A^T w>
+    scale = (mod.stitch_rendered(u.abs()).double() * w.double().abs()).sum()
     assert abs(lhs.item() - rhs.item()) <= 1e-3 * (abs(lhs.item()) + 1.0)
+    assert abs(lhs.item() - rhs.item()) <= 1e-7 * scale.item()   # float32 rounding of both sides only
 
 
 def test_render_depth_cuda_vs_oracle(gpu):
