@@ -533,6 +533,47 @@ int s360_ssim(const float* pred, const float* gt, int32_t n_images, int32_t chan
               float* ssim_out, void* workspace, size_t* workspace_bytes, void* stream);
 
 /*
+ * The training step's context-depth loss (src/model/model_wrapper_erp.py:242-287), forward and backward, on the GPU.
+ *
+ * s360_erode replaces erode (src/model/model_wrapper_helper.py:4-24): out = 1 - max over the ksize x ksize window of (1 - x),
+ * with reflect padding by (ksize - 1) / 2 (index -1 -> 1, H -> H - 2; no longitude wrap), on n_planes contiguous float32
+ * [height, width] planes.  Bit-identical to torch's 1 - max_pool2d(F.pad(1 - x, mode="reflect")) for any input; a NaN in the
+ * window gives NaN.  ksize odd and (ksize - 1) / 2 < height, width, else S360_E_BADARG.
+ *
+ * s360_l1_sphere_forward replaces compute_l1_sphere_loss (model_wrapper_helper.py:63-90):
+ *   loss = sum |t - p| (w_h m) / den',  den' = clamp_away_from(sum w_h m, 0, 1e-10)  (>= 0: max(den, 1e-10), else
+ *   min(den, -1e-10), NaN stays NaN), over [views, height, width] per batch element (keep_batch != 0: loss_out[batch],
+ *   den_out[batch]) or over everything (loss_out[1], den_out[1]).  pred, target, mask[batch, views, height, width] contiguous
+ *   float32 device memory; row_weights[height] = sin((h + 0.5) pi / height) as the caller computes it (the reference's float32
+ *   expression).  Each term is the float32 |t - p| * (w_h * m), summed in float64; num and den are rounded to float32 before the
+ *   clamp and the float32 division.  A zero-weight term is still added (NaN * 0 gives NaN, as in the reference).
+ *   mask == NULL selects the fused closure of model_wrapper_erp.py:245-258: m = erode(target > near_threshold, ksize) and
+ *   t = *far where target < fill_below, else target (target is the unfilled depth; far is a DEVICE float scalar; ksize odd,
+ *   <= 17).  The erosion is unconditional: eroding an all-ones mask gives all ones, so no `.all()` test is needed.  The fused
+ *   loss is bit-identical to this function fed with s360_erode's mask and the filled target.  far, near_threshold,
+ *   fill_below and ksize are ignored when mask != NULL.
+ *   workspace == NULL: *workspace_bytes receives the workspace size (16-byte aligned device memory) and nothing runs.
+ *   Otherwise two kernels run on `stream`; no atomics, no memset, no host synchronisation: results are bit-identical from
+ *   call to call, and with keep_batch element i's loss does not depend on the other elements.
+ *
+ * s360_l1_sphere_backward: torch's autograd chain of the forward, elementwise, given grad_loss (the incoming gradient: [batch]
+ * with keep_batch, else [1]) and den (the forward's den_out):
+ *   grad_pred = -(((grad_loss / den) * (w_h * m)) * sgn(t - p)),  sgn(0) = 0 and sgn(NaN) = 0 (torch's sign),
+ *   grad_target = -grad_pred, written only when grad_target != NULL.
+ * mask, target, far, near_threshold, fill_below and ksize as in the forward (mask == NULL: the fused mode, mask recomputed).
+ * One kernel on `stream`; every element of grad_pred (and grad_target) is written.
+ */
+int s360_erode(const float* x, float* out, int32_t n_planes, int32_t height, int32_t width, int32_t ksize, void* stream);
+int s360_l1_sphere_forward(const float* pred, const float* target, const float* mask, const float* row_weights,
+                           int32_t batch, int32_t views, int32_t height, int32_t width, int32_t keep_batch,
+                           const float* far, float near_threshold, float fill_below, int32_t ksize,
+                           float* loss_out, float* den_out, void* workspace, size_t* workspace_bytes, void* stream);
+int s360_l1_sphere_backward(const float* pred, const float* target, const float* mask, const float* row_weights,
+                            int32_t batch, int32_t views, int32_t height, int32_t width, int32_t keep_batch,
+                            const float* far, float near_threshold, float fill_below, int32_t ksize,
+                            const float* grad_loss, const float* den, float* grad_pred, float* grad_target, void* stream);
+
+/*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an
  * un-synchronised wall clock, src/misc/benchmarker.py:15-33).  While enabled, every kernel group
  * is bracketed by HIP events recorded on the launch stream; s360_profile_collect() synchronises

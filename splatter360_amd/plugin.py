@@ -14,6 +14,8 @@ together — in ONE rasteriser call of this library instead of twelve Python-loo
 install(metrics=True) also rebinds the evaluation step's `compute_ssim` (src/evaluation/metrics.py:38-54: skimage, one image at a
 time on the host) to metrics.compute_ssim (one SSIM kernel per batch on the GPU; CPU tensors still go to the replaced function),
 in src.evaluation.metrics and in every module that imported the name: now if they are imported, else by an import hook.
+install(depth_loss=True) likewise rebinds the training step's compute_l1_sphere_loss and erode (src/model/model_wrapper_helper.py)
+to depth_loss.compute_l1_sphere_loss / depth_loss.erode, in that module and in src.model.model_wrapper_erp.
 
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
@@ -288,12 +290,142 @@ def install_metrics():
     return None
 
 
-def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False, **opts):
+DEPTH_MODULE = "src.model.model_wrapper_helper"                       # defines erode (:4-24) and compute_l1_sphere_loss (:63-90)
+DEPTH_USERS = ("src.model.model_wrapper_erp",)                         # `from .model_wrapper_helper import compute_l1_sphere_loss, erode` (:45)
+DEPTH_NAMES = ("compute_l1_sphere_loss", "erode")
+
+
+def _is_cuda_f32(t) -> bool:
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+
+
+def _native_l1_sphere_loss(replaced):
+    """compute_l1_sphere_loss with the reference's signature: the depth-loss kernels for float32 GPU tensors of one [B,V,H,W]
+    shape with a mask that takes no gradient, the replaced function otherwise (mask=None included: it raises there)."""
+    from . import depth_loss as _dl
+
+    def compute_l1_sphere_loss(y_pred, y_true, mask=None, keep_batch=False):
+        if (mask is not None and all(_is_cuda_f32(t) for t in (y_pred, y_true, mask)) and y_pred.dim() == 4
+                and y_true.shape == y_pred.shape and mask.shape == y_pred.shape and not mask.requires_grad
+                and y_pred.numel() > 0 and y_pred.device == y_true.device == mask.device):
+            return _dl.compute_l1_sphere_loss(y_pred, y_true, mask, keep_batch)
+        return replaced(y_pred, y_true, mask=mask, keep_batch=keep_batch)
+
+    compute_l1_sphere_loss.replaced = replaced
+    compute_l1_sphere_loss.__doc__ = _dl.compute_l1_sphere_loss.__doc__
+    return compute_l1_sphere_loss
+
+
+def _native_erode(replaced):
+    """erode with the reference's signature: the erosion kernel for [C,H,W] / [N,C,H,W] float32 GPU tensors that take no gradient,
+    an odd ksize and a reflect pad below H and W; the replaced function otherwise."""
+    from . import depth_loss as _dl
+
+    def erode(bin_img, ksize=5):
+        if (_is_cuda_f32(bin_img) and bin_img.dim() in (3, 4) and not bin_img.requires_grad and isinstance(ksize, int)
+                and ksize >= 1 and ksize % 2 == 1 and (ksize - 1) // 2 < min(bin_img.shape[-2], bin_img.shape[-1])):
+            return _dl.erode(bin_img, ksize)
+        return replaced(bin_img, ksize)
+
+    erode.replaced = replaced
+    erode.__doc__ = _dl.erode.__doc__
+    return erode
+
+
+_DEPTH_WRAPPERS = {"compute_l1_sphere_loss": _native_l1_sphere_loss, "erode": _native_erode}
+
+
+def _patch_depth_loss(mod):
+    """Rebind compute_l1_sphere_loss and erode in the module that defines them and in every already-imported module that bound
+    the names with `from ... import` (modules imported later bind the replacements themselves).  Idempotent."""
+    out = {}
+    for name in DEPTH_NAMES:
+        cur = getattr(mod, name)
+        fn = cur if getattr(cur, "replaced", None) is not None else _DEPTH_WRAPPERS[name](cur)
+        setattr(mod, name, fn)
+        for user in DEPTH_USERS:
+            um = sys.modules.get(user)
+            if um is not None and getattr(um, name, None) is fn.replaced:
+                setattr(um, name, fn)
+        out[name] = fn
+    return out
+
+
+def _depth_module_ready(mod) -> bool:
+    return mod is not None and all(hasattr(mod, n) for n in DEPTH_NAMES)
+
+
+class _DepthLossPatcher(importlib.abc.MetaPathFinder):
+    """install(depth_loss=True) before the reference's helper module is imported: patch it as it is first loaded, and — for an
+    import made through a finder ahead of this one (jaxtyping's hook, see _MetricsPatcher) — at the next import this finder is
+    asked about, before the training step can call it."""
+
+    def __init__(self):
+        self.busy = False
+
+    def _done(self, mod):
+        if self in sys.meta_path:
+            sys.meta_path.remove(self)
+        _patch_depth_loss(mod)
+
+    def find_spec(self, fullname, path, target=None):
+        if self.busy:
+            return None
+        mod = sys.modules.get(DEPTH_MODULE)
+        if _depth_module_ready(mod):                              # imported behind this finder's back: patch late
+            self.busy = True
+            try:
+                self._done(mod)
+            except Exception as ex:      # never let the failure surface from an unrelated import
+                import warnings
+                warnings.warn(f"splatter360_amd.install(depth_loss=True): patching {DEPTH_MODULE} failed ({ex!r}); the reference "
+                              "keeps its own depth loss.", RuntimeWarning)
+            finally:
+                self.busy = False
+            return None
+        if fullname != DEPTH_MODULE:
+            return None
+        self.busy = True
+        try:
+            spec = importlib.util.find_spec(fullname)
+        finally:
+            self.busy = False
+        if spec is None or spec.loader is None:
+            return None
+        loader, finder = spec.loader, self
+
+        class _Loader(importlib.abc.Loader):
+            def create_module(self, s):
+                return loader.create_module(s)
+
+            def exec_module(self, module):
+                loader.exec_module(module)
+                finder._done(module)
+
+        spec.loader = _Loader()
+        return spec
+
+
+def install_depth_loss():
+    """The depth-loss half of install(depth_loss=True): rebind compute_l1_sphere_loss and erode now if the reference's helper
+    module is imported, else as soon as it is (import hook).  Returns {name: patched function} or None."""
+    mod = sys.modules.get(DEPTH_MODULE)
+    if _depth_module_ready(mod):
+        return _patch_depth_loss(mod)
+    if not any(isinstance(f, _DepthLossPatcher) for f in sys.meta_path):
+        sys.meta_path.insert(0, _DepthLossPatcher())
+    return None
+
+
+def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
+            depth_loss: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
     HBM); adapter_options: sh_rotation / differentiable_means / lazy of lazy.make_adapter_class.
     metrics=True: ALSO rebind the evaluation step's compute_ssim to the SSIM kernel (install_metrics; off by default).
+    depth_loss=True: ALSO rebind the training step's compute_l1_sphere_loss and erode to the depth-loss kernels
+    (install_depth_loss; off by default).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -304,6 +436,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
         install_adapter(**(adapter_options or {}))
     if metrics:
         install_metrics()
+    if depth_loss:
+        install_depth_loss()
     if lazy:
         if REGISTRY_MODULE in sys.modules:
             return _patch(sys.modules[REGISTRY_MODULE], **opts)
@@ -314,8 +448,19 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
 
 
 def uninstall() -> None:
-    """Put the reference's own decoder class, adapter and compute_ssim back (and drop pending import hooks)."""
-    sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher))]
+    """Put the reference's own decoder class, adapter, compute_ssim, compute_l1_sphere_loss and erode back (and drop pending
+    import hooks)."""
+    sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher, _DepthLossPatcher))]
+    dmod = sys.modules.get(DEPTH_MODULE)
+    if dmod is not None:
+        for name in DEPTH_NAMES:
+            cur = getattr(dmod, name, None)
+            if getattr(cur, "replaced", None) is not None:
+                setattr(dmod, name, cur.replaced)
+                for user in DEPTH_USERS:
+                    um = sys.modules.get(user)
+                    if um is not None and getattr(um, name, None) is cur:
+                        setattr(um, name, cur.replaced)
     mmod = sys.modules.get(METRICS_MODULE)
     if mmod is not None:
         cur = getattr(mmod, METRICS_NAME, None)
