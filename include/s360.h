@@ -574,6 +574,45 @@ int s360_l1_sphere_backward(const float* pred, const float* target, const float*
                             const float* grad_loss, const float* den, float* grad_pred, float* grad_target, void* stream);
 
 /*
+ * The other weight-free scores of the evaluation step (csrc/s360_eval_scores.hip).
+ *
+ * s360_depth_metrics replaces compute_depth_metrics_batched (src/scripts/compute_depth_metrics.py:47-116, called at
+ * src/model/model_wrapper_erp.py:526-531) in one pass over gt, pred and the validity, for n_rows rows of n float32 elements:
+ *   row r of gt starts at gt + (r / rows_per_group) * gt_group_stride + (r % rows_per_group) * gt_row_stride (elements), pred
+ *   likewise — [B, N] tensors with a row stride need no copy (rows_per_group = n_rows), and faces 1..5 of every six of a
+ *   [views, 6, H, W] block are rows_per_group = 5 with the pointer at face 1 and a group stride of 6 H W;
+ *   validity: valid[r * valid_row_stride + e] != 0 (uint8 / bool), or, valid == NULL, gt > threshold;
+ *   pred_height > 0: pred rows are [pred_height, pred_width] planes looked up at gt's [gt_height, gt_width] (= n) positions by
+ *   F.interpolate(mode="nearest")'s rule, src = min(floor(float(dst) * (float(pred size) / float(gt size))), pred size - 1);
+ *   pred_height == pred_width == 0: no lookup, the four sizes are ignored.
+ * Per valid element, float32 IEEE operations: d = gt - pred; terms |d|, |d| / gt, (d d) / gt, d d, (log gt - log pred)^2.
+ * metrics_out[12, n_rows] float32, in this order:
+ *   0 abs_diff, 1 abs_rel, 2 sq_rel, 3 rmse, 4 rmse_log: the float64 sum of the term over the valid elements where that term is
+ *     not NaN, divided by their number, rounded to float32 (rmse, rmse_log: then the float32 square root);
+ *   5 a5, 6 a10, 7 a25, 8 a0 (= a10), 9 a1 (= a25), 10 a2, 11 a3: the number of valid elements with gt / pred < t and
+ *     pred / gt < t (a NaN quotient is a miss) for the float32 t = 1.05, 1.10, 1.25, 1.25^2, 1.25^3, divided in float32 by the
+ *     number of valid elements, times 100 in float32 when mult_a != 0.
+ *   A row without a valid element gives NaN twelve times.  valid_count[n_rows] int32: the valid elements per row.
+ * scores_out != NULL: also the evaluation step's reduction over rows (model_wrapper_erp.py:537-541), scores_out[12] float32:
+ *   the float64 sum of each metric over the rows with valid_count > 0, divided by the number of such rows (none: NaN).
+ * workspace == NULL: *workspace_bytes receives the workspace size (8-byte aligned device memory) and nothing runs.  Otherwise
+ * two kernels (three with scores_out) run on `stream`; no atomics, no host synchronisation: results are bit-identical from
+ * call to call, row r's numbers do not depend on the other rows, nor on the alignment or strides of the inputs.
+ *
+ * s360_psnr replaces compute_psnr (src/evaluation/metrics.py:11-21; the evaluation step at model_wrapper_erp.py:485-487, the
+ * training step at :234-238): per image of pred, gt[n_images, channels, height, width] contiguous float32, both clipped to
+ * [0, 1] (NaN stays NaN), the float64 sum of the float32 (gt - pred)^2, the mean rounded to float32, 0 replaced by 1e-10,
+ * psnr_out[n_images] = -10 log10(mean).  Workspace, stream and determinism as above; two kernels.
+ */
+int s360_depth_metrics(const float* gt, const float* pred, const uint8_t* valid, int32_t n_rows, int32_t n,
+                       size_t gt_row_stride, size_t pred_row_stride, size_t valid_row_stride, int32_t rows_per_group,
+                       size_t gt_group_stride, size_t pred_group_stride, float threshold, int32_t gt_height, int32_t gt_width,
+                       int32_t pred_height, int32_t pred_width, int32_t mult_a, float* metrics_out, int32_t* valid_count,
+                       float* scores_out, void* workspace, size_t* workspace_bytes, void* stream);
+int s360_psnr(const float* pred, const float* gt, int32_t n_images, int32_t channels, int32_t height, int32_t width,
+              float* psnr_out, void* workspace, size_t* workspace_bytes, void* stream);
+
+/*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an
  * un-synchronised wall clock, src/misc/benchmarker.py:15-33).  While enabled, every kernel group
  * is bracketed by HIP events recorded on the launch stream; s360_profile_collect() synchronises

@@ -16,6 +16,9 @@ time on the host) to metrics.compute_ssim (one SSIM kernel per batch on the GPU;
 in src.evaluation.metrics and in every module that imported the name: now if they are imported, else by an import hook.
 install(depth_loss=True) likewise rebinds the training step's compute_l1_sphere_loss and erode (src/model/model_wrapper_helper.py)
 to depth_loss.compute_l1_sphere_loss / depth_loss.erode, in that module and in src.model.model_wrapper_erp.
+install(psnr=True) rebinds compute_psnr (src/evaluation/metrics.py:11-21) to metrics.compute_psnr in the same modules as
+compute_ssim, and install(depth_metrics=True) rebinds compute_depth_metrics_batched (src/scripts/compute_depth_metrics.py:47-116)
+to metrics.compute_depth_metrics_batched in that module and in src.model.model_wrapper_erp.
 
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
@@ -417,8 +420,167 @@ def install_depth_loss():
     return None
 
 
+class _Seam:
+    """One rebinding seam: functions `names` defined in `module` and bound with `from ... import` by `users`; wrappers[name](replaced)
+    builds the replacement (which keeps the original as `.replaced`)."""
+
+    def __init__(self, keyword, module, names, users, wrappers):
+        self.keyword, self.module, self.names, self.users, self.wrappers = keyword, module, tuple(names), tuple(users), wrappers
+
+    def ready(self, mod) -> bool:
+        return mod is not None and all(hasattr(mod, n) for n in self.names)
+
+    def patch(self, mod) -> dict:
+        """Rebind the names in the defining module and in every already-imported user that still holds the original (modules
+        imported later bind the replacements themselves).  Idempotent."""
+        out = {}
+        for name in self.names:
+            cur = getattr(mod, name)
+            fn = cur if getattr(cur, "replaced", None) is not None else self.wrappers[name](cur)
+            setattr(mod, name, fn)
+            for user in self.users:
+                um = sys.modules.get(user)
+                if um is not None and getattr(um, name, None) is fn.replaced:
+                    setattr(um, name, fn)
+            out[name] = fn
+        return out
+
+    def restore(self) -> None:
+        mod = sys.modules.get(self.module)
+        if mod is None:
+            return
+        for name in self.names:
+            cur = getattr(mod, name, None)
+            if getattr(cur, "replaced", None) is not None:
+                setattr(mod, name, cur.replaced)
+                for user in self.users:
+                    um = sys.modules.get(user)
+                    if um is not None and getattr(um, name, None) is cur:
+                        setattr(um, name, cur.replaced)
+
+    def install(self):
+        """Patch now if the module is imported, else put a _SeamPatcher on sys.meta_path.  Returns {name: function} or None."""
+        mod = sys.modules.get(self.module)
+        if self.ready(mod):
+            return self.patch(mod)
+        if not any(isinstance(f, _SeamPatcher) and f.seam is self for f in sys.meta_path):
+            sys.meta_path.insert(0, _SeamPatcher(self))
+        return None
+
+
+class _SeamPatcher(importlib.abc.MetaPathFinder):
+    """The import hook of a _Seam installed before its module is imported: patch the module as it is first loaded, and — for an
+    import made through a finder ahead of this one (jaxtyping's hook, see _MetricsPatcher) — at the next import this finder is
+    asked about, before a step can call the functions."""
+
+    def __init__(self, seam):
+        self.seam, self.busy = seam, False
+
+    def _done(self, mod):
+        if self in sys.meta_path:
+            sys.meta_path.remove(self)
+        self.seam.patch(mod)
+
+    def find_spec(self, fullname, path, target=None):
+        if self.busy:
+            return None
+        seam = self.seam
+        mod = sys.modules.get(seam.module)
+        if seam.ready(mod):                                       # imported behind this finder's back: patch late
+            self.busy = True
+            try:
+                self._done(mod)
+            except Exception as ex:      # never let the failure surface from an unrelated import
+                import warnings
+                warnings.warn(f"splatter360_amd.install({seam.keyword}=True): patching {seam.module} failed ({ex!r}); the "
+                              "reference keeps its own functions.", RuntimeWarning)
+            finally:
+                self.busy = False
+            return None
+        if fullname != seam.module:
+            return None
+        self.busy = True
+        try:
+            spec = importlib.util.find_spec(fullname)
+        finally:
+            self.busy = False
+        if spec is None or spec.loader is None:
+            return None
+        loader, finder = spec.loader, self
+
+        class _Loader(importlib.abc.Loader):
+            def create_module(self, s):
+                return loader.create_module(s)
+
+            def exec_module(self, module):
+                loader.exec_module(module)
+                finder._done(module)
+
+        spec.loader = _Loader()
+        return spec
+
+
+DEPTH_METRICS_MODULE = "src.scripts.compute_depth_metrics"            # defines compute_depth_metrics_batched (:47-116)
+DEPTH_METRICS_USERS = ("src.model.model_wrapper_erp",)                 # `from ..scripts.compute_depth_metrics import compute_depth_metrics_batched` (:47)
+DEPTH_METRICS_NAME = "compute_depth_metrics_batched"
+PSNR_NAME = "compute_psnr"                                            # src/evaluation/metrics.py:11-21; METRICS_USERS bind it too
+
+
+def _native_depth_metrics(replaced):
+    """compute_depth_metrics_batched with the reference's signature: the depth-metrics kernels for float32 GPU gt / pred of one
+    [B,N] shape with a bool mask on the same device, the replaced function otherwise."""
+    from . import metrics as _metrics
+
+    def compute_depth_metrics_batched(gt_bN, pred_bN, valid_masks_bN, mult_a=False):
+        if (_is_cuda_f32(gt_bN) and _is_cuda_f32(pred_bN) and isinstance(valid_masks_bN, torch.Tensor) and valid_masks_bN.is_cuda
+                and valid_masks_bN.dtype == torch.bool and gt_bN.dim() == 2 and gt_bN.shape == pred_bN.shape == valid_masks_bN.shape
+                and gt_bN.device == pred_bN.device == valid_masks_bN.device):
+            return _metrics.compute_depth_metrics_batched(gt_bN, pred_bN, valid_masks_bN, mult_a)
+        return replaced(gt_bN, pred_bN, valid_masks_bN, mult_a)
+
+    compute_depth_metrics_batched.replaced = replaced
+    compute_depth_metrics_batched.__doc__ = _metrics.compute_depth_metrics_batched.__doc__
+    return compute_depth_metrics_batched
+
+
+def _native_compute_psnr(replaced):
+    """compute_psnr with the reference's signature: the PSNR kernels for GPU float tensors of one 4-D shape on one device, the
+    replaced function otherwise."""
+    from . import metrics as _metrics
+
+    def compute_psnr(ground_truth, predicted):
+        if (isinstance(ground_truth, torch.Tensor) and isinstance(predicted, torch.Tensor) and ground_truth.is_cuda and predicted.is_cuda
+                and ground_truth.is_floating_point() and predicted.is_floating_point() and ground_truth.dim() == 4
+                and ground_truth.shape == predicted.shape and ground_truth.device == predicted.device):
+            return _metrics.compute_psnr(ground_truth, predicted)
+        return replaced(ground_truth, predicted)
+
+    compute_psnr.replaced = replaced
+    compute_psnr.__doc__ = _metrics.compute_psnr.__doc__
+    return compute_psnr
+
+
+DEPTH_METRICS_SEAM = _Seam("depth_metrics", DEPTH_METRICS_MODULE, (DEPTH_METRICS_NAME,), DEPTH_METRICS_USERS,
+                           {DEPTH_METRICS_NAME: _native_depth_metrics})
+PSNR_SEAM = _Seam("psnr", METRICS_MODULE, (PSNR_NAME,), METRICS_USERS, {PSNR_NAME: _native_compute_psnr})
+
+
+def install_depth_metrics():
+    """The half of install(depth_metrics=True): rebind compute_depth_metrics_batched now if the reference's module is imported,
+    else as soon as it is (import hook).  Returns the patched function or None."""
+    out = DEPTH_METRICS_SEAM.install()
+    return None if out is None else out[DEPTH_METRICS_NAME]
+
+
+def install_psnr():
+    """The half of install(psnr=True): rebind compute_psnr now if the reference's metrics module is imported, else as soon as it
+    is (import hook).  Returns the patched function or None."""
+    out = PSNR_SEAM.install()
+    return None if out is None else out[PSNR_NAME]
+
+
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
-            depth_loss: bool = False, **opts):
+            depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
@@ -426,6 +588,10 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     metrics=True: ALSO rebind the evaluation step's compute_ssim to the SSIM kernel (install_metrics; off by default).
     depth_loss=True: ALSO rebind the training step's compute_l1_sphere_loss and erode to the depth-loss kernels
     (install_depth_loss; off by default).
+    depth_metrics=True: ALSO rebind the evaluation step's compute_depth_metrics_batched to the depth-metrics kernels
+    (install_depth_metrics; off by default).
+    psnr=True: ALSO rebind compute_psnr (evaluation and training step) to the PSNR kernels (install_psnr; off by default;
+    metrics=True alone keeps meaning compute_ssim only).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -438,6 +604,10 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
         install_metrics()
     if depth_loss:
         install_depth_loss()
+    if depth_metrics:
+        install_depth_metrics()
+    if psnr:
+        install_psnr()
     if lazy:
         if REGISTRY_MODULE in sys.modules:
             return _patch(sys.modules[REGISTRY_MODULE], **opts)
@@ -448,9 +618,12 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
 
 
 def uninstall() -> None:
-    """Put the reference's own decoder class, adapter, compute_ssim, compute_l1_sphere_loss and erode back (and drop pending
-    import hooks)."""
-    sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher, _DepthLossPatcher))]
+    """Put the reference's own decoder class, adapter, compute_ssim, compute_psnr, compute_depth_metrics_batched,
+    compute_l1_sphere_loss and erode back (and drop pending import hooks)."""
+    sys.meta_path[:] = [f for f in sys.meta_path
+                        if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher, _DepthLossPatcher, _SeamPatcher))]
+    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM):
+        seam.restore()
     dmod = sys.modules.get(DEPTH_MODULE)
     if dmod is not None:
         for name in DEPTH_NAMES:
