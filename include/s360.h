@@ -613,6 +613,48 @@ int s360_psnr(const float* pred, const float* gt, int32_t n_images, int32_t chan
               float* psnr_out, void* workspace, size_t* workspace_bytes, void* stream);
 
 /*
+ * The encoder's spherical plane-sweep cost volume (csrc/s360_cost_volume.hip): the closure of the reference's
+ * src/model/encoder/costvolume/depth_predictor_multiview_360.py:588-630 — warp_with_pose_depth_candidates (:159-214), the product
+ * with the own view's features and the sum over channels — without the [n, C, D, h, w] warped tensor.
+ *
+ * s360_cost_volume_forward:
+ *   out[i, d, y, x] = scale * sum_{k < pairs} sum_c f_own[i, c, y, x] * bilinear(f_partner[partner_slot[k, i], c], warp(k, i, d, y, x))
+ *   f_own[n, C, h, w], f_partner[m, C, h, w], out[n, D, h, w]: contiguous float32 device memory (f_partner may be f_own);
+ *   partner_slot[pairs, n] int32 device memory (NULL: slot i, needs m == n; an entry outside [0, m) contributes nothing);
+ *   poses[pairs, n, 4, 4] float32 row-major, partner from own; depths[n, D] float32 depth candidates.
+ *   The reference's volume is scale = 1 / (pairs sqrt(C)) with every rolled pairing in one call; one pairing's sum over channels
+ *   is pairs = 1, scale = 1.
+ *   warp, convention S360_CV_HM3D ('hm3d' and 'replica' of src/geometry/utils360.py:93-104,148-153,193-198,250-263; the only value,
+ *   anything else is S360_E_BADARG): theta = (0.5 - (x + 0.5) / w) 2 pi, phi = -((y + 0.5) / h - 0.5) pi, p = (cos phi sin theta,
+ *   sin phi, cos phi cos theta) depth, q = R p + t, theta' = atan2(q_x, q_z), phi' = atan2(q_y, sqrt(q_x^2 + q_z^2)),
+ *   x' = (-theta' / 2 pi + 0.5) w - 0.5, u = (x' + 0.5) / w * 2 - 1, ix = (u + 1) / 2 * (w - 1) (y likewise with pi and h): the
+ *   reference's normalisation fed to an align_corners=True sampler, off by half on purpose.  Evaluated in float64 from the float32
+ *   inputs.  Taps outside the map contribute zero; so does a sample whose position is not finite.
+ *   workspace == NULL: *workspace_bytes receives the workspace size (16-byte aligned device memory: channels-last copies of the
+ *   features; nothing in either direction has C * D elements) and nothing runs.  h, w <= 65534.
+ *   Kernels run on `stream`; no atomics, no host synchronisation: bit-identical from call to call and stream to stream, and
+ *   slot i's numbers depend on no other slot of f_own.
+ * s360_cost_volume_backward: given grad_out[n, D, h, w], writes every element of
+ *   grad_own[i, c, y, x]    = scale * sum_k sum_d grad_out[i, d, y, x] * bilinear(f_partner[slot, c], warp)   (deterministic)
+ *   grad_partner[s, c, tap] = scale * sum over the samples that touch the tap of grad_out * weight * f_own      (float32 atomics:
+ *   arrival order shows in the last bits)
+ *   as two tensors; a caller whose f_partner is f_own adds them.  Poses and depths take no gradient.  Workspace as above.
+ * s360_cost_volume_warp: warped[n, C, D, h, w] = bilinear(f_partner[partner_slot[i], c], warp(i, d, y, x)) for one pairing
+ *   (poses[n, 4, 4], partner_slot[n] or NULL): the materialised tensor of warp_with_pose_depth_candidates, for callers that use
+ *   that function alone.  One kernel, no workspace.
+ */
+#define S360_CV_HM3D 0
+int s360_cost_volume_forward(const float* f_own, const float* f_partner, const int32_t* partner_slot, const float* poses,
+                             const float* depths, int32_t n, int32_t m, int32_t pairs, int32_t C, int32_t h, int32_t w, int32_t D,
+                             int32_t convention, float scale, float* out, void* workspace, size_t* workspace_bytes, void* stream);
+int s360_cost_volume_backward(const float* f_own, const float* f_partner, const int32_t* partner_slot, const float* poses,
+                              const float* depths, int32_t n, int32_t m, int32_t pairs, int32_t C, int32_t h, int32_t w, int32_t D,
+                              int32_t convention, float scale, const float* grad_out, float* grad_own, float* grad_partner,
+                              void* workspace, size_t* workspace_bytes, void* stream);
+int s360_cost_volume_warp(const float* f_partner, const int32_t* partner_slot, const float* poses, const float* depths, int32_t n,
+                          int32_t m, int32_t C, int32_t h, int32_t w, int32_t D, int32_t convention, float* warped, void* stream);
+
+/*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an
  * un-synchronised wall clock, src/misc/benchmarker.py:15-33).  While enabled, every kernel group
  * is bracketed by HIP events recorded on the launch stream; s360_profile_collect() synchronises

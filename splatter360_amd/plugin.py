@@ -19,6 +19,9 @@ to depth_loss.compute_l1_sphere_loss / depth_loss.erode, in that module and in s
 install(psnr=True) rebinds compute_psnr (src/evaluation/metrics.py:11-21) to metrics.compute_psnr in the same modules as
 compute_ssim, and install(depth_metrics=True) rebinds compute_depth_metrics_batched (src/scripts/compute_depth_metrics.py:47-116)
 to metrics.compute_depth_metrics_batched in that module and in src.model.model_wrapper_erp.
+install(cost_volume=True) rebinds the encoder's warp_with_pose_depth_candidates
+(src/model/encoder/costvolume/depth_predictor_multiview_360.py:73-214) to a lazy handle, so that the predictor's own forward
+builds its correlation volume with the fused kernels of cost_volume.py and never forms the [v b, C, D, h, w] warped tensor.
 
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
@@ -565,6 +568,42 @@ DEPTH_METRICS_SEAM = _Seam("depth_metrics", DEPTH_METRICS_MODULE, (DEPTH_METRICS
 PSNR_SEAM = _Seam("psnr", METRICS_MODULE, (PSNR_NAME,), METRICS_USERS, {PSNR_NAME: _native_compute_psnr})
 
 
+COST_VOLUME_MODULE = "src.model.encoder.costvolume.depth_predictor_multiview_360"   # defines warp_with_pose_depth_candidates (:73-214)
+COST_VOLUME_NAME = "warp_with_pose_depth_candidates"                  # DepthPredictorMultiView360.forward calls the module-level name (:606)
+COST_VOLUME_DATASETS = ("hm3d", "replica")
+
+
+def _native_cost_volume_warp(replaced):
+    """warp_with_pose_depth_candidates with the reference's signature: for float32 GPU features, pose and candidates of the
+    'hm3d' / 'replica' convention with zeros padding it returns a cost_volume.LazyWarp, whose product with feat01.unsqueeze(2)
+    summed over dim 1 is the fused kernel (DepthPredictorMultiView360.forward :621-625 then divides, stacks and averages
+    [v b, D, h, w] tensors unchanged); the replaced function otherwise.  With wo_cost_volume the reference never calls it."""
+    from . import cost_volume as _cv
+
+    def warp_with_pose_depth_candidates(utils360, feature1, pose, depth, *args, **kwargs):
+        if (not args and all(_is_cuda_f32(t) for t in (feature1, pose, depth)) and feature1.device == pose.device == depth.device
+                and getattr(utils360, "dataset", None) in COST_VOLUME_DATASETS and feature1.dim() == 4 and depth.dim() == 4
+                and tuple(pose.shape) == (feature1.shape[0], 4, 4) and depth.shape[0] == feature1.shape[0]
+                and tuple(depth.shape[2:]) == tuple(feature1.shape[2:]) and feature1.numel() > 0
+                and kwargs.get("warp_padding_mode", "zeros") == "zeros" and not kwargs.get("debug", False)):
+            return _cv.LazyWarp(utils360, feature1, pose, depth, replaced, kwargs)
+        return replaced(utils360, feature1, pose, depth, *args, **kwargs)
+
+    warp_with_pose_depth_candidates.replaced = replaced
+    warp_with_pose_depth_candidates.__doc__ = _cv.LazyWarp.__doc__
+    return warp_with_pose_depth_candidates
+
+
+COST_VOLUME_SEAM = _Seam("cost_volume", COST_VOLUME_MODULE, (COST_VOLUME_NAME,), (), {COST_VOLUME_NAME: _native_cost_volume_warp})
+
+
+def install_cost_volume():
+    """The half of install(cost_volume=True): rebind the encoder module's warp_with_pose_depth_candidates now if the module is
+    imported, else as soon as it is (import hook).  Returns the patched function or None."""
+    out = COST_VOLUME_SEAM.install()
+    return None if out is None else out[COST_VOLUME_NAME]
+
+
 def install_depth_metrics():
     """The half of install(depth_metrics=True): rebind compute_depth_metrics_batched now if the reference's module is imported,
     else as soon as it is (import hook).  Returns the patched function or None."""
@@ -580,7 +619,7 @@ def install_psnr():
 
 
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
-            depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, **opts):
+            depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
@@ -592,6 +631,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     (install_depth_metrics; off by default).
     psnr=True: ALSO rebind compute_psnr (evaluation and training step) to the PSNR kernels (install_psnr; off by default;
     metrics=True alone keeps meaning compute_ssim only).
+    cost_volume=True: ALSO rebind the encoder's warp_with_pose_depth_candidates so that DepthPredictorMultiView360.forward builds
+    raw_correlation_in with the fused cost-volume kernels (install_cost_volume; off by default).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -608,6 +649,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
         install_depth_metrics()
     if psnr:
         install_psnr()
+    if cost_volume:
+        install_cost_volume()
     if lazy:
         if REGISTRY_MODULE in sys.modules:
             return _patch(sys.modules[REGISTRY_MODULE], **opts)
@@ -619,10 +662,10 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
 
 def uninstall() -> None:
     """Put the reference's own decoder class, adapter, compute_ssim, compute_psnr, compute_depth_metrics_batched,
-    compute_l1_sphere_loss and erode back (and drop pending import hooks)."""
+    compute_l1_sphere_loss, erode and warp_with_pose_depth_candidates back (and drop pending import hooks)."""
     sys.meta_path[:] = [f for f in sys.meta_path
                         if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher, _DepthLossPatcher, _SeamPatcher))]
-    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM):
+    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM):
         seam.restore()
     dmod = sys.modules.get(DEPTH_MODULE)
     if dmod is not None:
