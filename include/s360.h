@@ -655,6 +655,36 @@ int s360_cost_volume_warp(const float* f_partner, const int32_t* partner_slot, c
                           int32_t m, int32_t C, int32_t h, int32_t w, int32_t D, int32_t convention, float* warped, void* stream);
 
 /*
+ * The encoder's softmax depth head (csrc/s360_depth_head.hip): the other end of the plane sweep, the reference's
+ * src/model/encoder/costvolume/depth_predictor_multiview_360.py:643-651 — softmax over the D logits of a pixel, the expected
+ * depth under it and its largest probability — without the [n, D, h, w] softmax.  An additive entry pair: the ABI version stays.
+ *
+ * s360_depth_head_forward: with pdf = softmax(logits, dim 1),
+ *   depth[i, y, x] = sum_d candidates[i, d] pdf[i, d, y, x],   pmax[i, y, x] = max_d pdf[i, d, y, x] = 1 / sum_d exp(z_d - max z),
+ *   lse[i, y, x] = max z + log sum_d exp(z_d - max z),          argmax[i, y, x] = the first d that attains max z.
+ *   logits[n, D, h, w], candidates[n, D], depth, pmax, lse [n, h, w] float32, argmax[n, h, w] int32: contiguous device memory.
+ *   One read of the logits (the running maximum is moved and the sums rescaled as the walk goes); D is split over the four waves
+ *   of a block, whose partial (max, argmax, sums) are merged in a fixed order, on equal maxima the lower index.  exp, sums and
+ *   quotients in float64, one rounding to float32 per output.  Finite logits of any size give finite outputs; non-finite logits
+ *   give unspecified values with argmax still in [0, D).  n <= 65535, h w < 2^30.
+ * s360_depth_head_backward: given g_depth, g_pmax [n, h, w] (either may be NULL: zero), writes every element of
+ *   g_logits[i, d, y, x] = p_d (g_depth (c_d - depth) - g_pmax pmax) + [d == argmax] g_pmax pmax,   p_d = exp(z_d - lse),
+ *   from the forward's lse, depth and argmax.  The kernel does not take the float32 lse and depth at their word: half an ulp of
+ *   |lse| is a relative error of every p_d (3.8e-6 at |z| = 75).  It first sums q = sum_d exp(z_d - lse) and
+ *   r = sum_d (c_d - depth) exp(z_d - lse) / q over the block's logits (1 and 0 for exact scalars; the second pass finds the
+ *   logits in cache), takes pmax = exp(z_argmax - lse) / q, and evaluates the formula with p_d / q and (c_d - depth) - r, in
+ *   float64.  float4 loads and stores along x when h w is a multiple of 4 and the pointers are 16-byte aligned, scalar otherwise.
+ *   An argmax entry outside [0, D) contributes no pmax term.  The candidates take no gradient.
+ * Both: kernels run on `stream`; no workspace, no memset, no atomics, no host synchronisation: bit-identical from call to call
+ * and stream to stream.  Null required pointers or non-positive sizes: S360_E_BADARG before any GPU work.
+ */
+int s360_depth_head_forward(const float* logits, const float* candidates, int32_t n, int32_t d, int32_t h, int32_t w, float* depth,
+                            float* pmax, float* lse, int32_t* argmax, void* stream);
+int s360_depth_head_backward(const float* logits, const float* candidates, const float* lse, const float* depth, const int32_t* argmax,
+                             const float* g_depth, const float* g_pmax, int32_t n, int32_t d, int32_t h, int32_t w, float* g_logits,
+                             void* stream);
+
+/*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an
  * un-synchronised wall clock, src/misc/benchmarker.py:15-33).  While enabled, every kernel group
  * is bracketed by HIP events recorded on the launch stream; s360_profile_collect() synchronises

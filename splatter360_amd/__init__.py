@@ -3,7 +3,9 @@ library is loaded on first use (splatter360_amd._lib) and there is no CPU fallba
 
 
 def install(**opts):
-    """Register the fused decoder in the unchanged reference's decoder registry (splatter360_amd.plugin.install)."""
+    """Register the fused decoder in the unchanged reference's decoder registry (splatter360_amd.plugin.install).  Keywords
+    switch the other native seams on, each off by default: adapter, metrics, depth_loss, depth_metrics, psnr, cost_volume and
+    depth_head (the encoder's softmax depth head, splatter360_amd.depth_head)."""
     from .plugin import install as _install
     return _install(**opts)
 

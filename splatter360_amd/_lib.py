@@ -15,7 +15,7 @@ _PKG = Path(__file__).resolve().parent
 _CSRC = _PKG / "csrc"
 LIB_PATH = _PKG / "libs360.so"
 SOURCES = ("s360_forward.hip", "s360_backward.hip", "s360_backward_em.hip", "s360_stitch.hip", "s360_views.hip", "s360_adapter.hip", "s360_metrics.hip",
-           "s360_depth_loss.hip", "s360_eval_scores.hip", "s360_cost_volume.hip")
+           "s360_depth_loss.hip", "s360_eval_scores.hip", "s360_cost_volume.hip", "s360_depth_head.hip")
 # per-source extra flags (s360_backward_em.hip: see the launcher comment in csrc/s360_bwd_em.h)
 SOURCE_FLAGS = {"s360_backward_em.hip": ("-fno-slp-vectorize",)}
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result")
@@ -61,7 +61,7 @@ EXPORTS = ("s360_forward_raw", "s360_backward_raw", "s360_backward_raw_tail", "s
            "s360_cube2erp_forward", "s360_cube2erp_backward", "s360_count_contributions", "s360_count_backward_slots", "s360_profile_slots", "s360_profile_slot_name",
            "s360_profile_enable", "s360_profile_collect", "s360_ssim", "s360_erode", "s360_l1_sphere_forward",
            "s360_l1_sphere_backward", "s360_depth_metrics", "s360_psnr", "s360_cost_volume_forward", "s360_cost_volume_backward",
-           "s360_cost_volume_warp")
+           "s360_cost_volume_warp", "s360_depth_head_forward", "s360_depth_head_backward")
 
 
 def _hipcc() -> str:
@@ -210,6 +210,10 @@ def lib() -> C.CDLL:
     l.s360_cost_volume_backward.argtypes = [vp] * 5 + [i32] * 8 + [f32, vp, vp, vp, vp, C.POINTER(sz), vp]
     l.s360_cost_volume_warp.restype = C.c_int
     l.s360_cost_volume_warp.argtypes = [vp] * 4 + [i32] * 7 + [vp, vp]
+    l.s360_depth_head_forward.restype = C.c_int
+    l.s360_depth_head_forward.argtypes = [vp, vp] + [i32] * 4 + [vp] * 5
+    l.s360_depth_head_backward.restype = C.c_int
+    l.s360_depth_head_backward.argtypes = [vp] * 7 + [i32] * 4 + [vp, vp]
     l.s360_count_backward_slots.restype = C.c_int
     l.s360_count_backward_slots.argtypes = [C.POINTER(S360Params), vp, sz, vp, vp]
     l.s360_count_contributions.restype = C.c_int

@@ -22,6 +22,9 @@ to metrics.compute_depth_metrics_batched in that module and in src.model.model_w
 install(cost_volume=True) rebinds the encoder's warp_with_pose_depth_candidates
 (src/model/encoder/costvolume/depth_predictor_multiview_360.py:73-214) to a lazy handle, so that the predictor's own forward
 builds its correlation volume with the fused kernels of cost_volume.py and never forms the [v b, C, D, h, w] warped tensor.
+install(depth_head=True) rebinds the name `F` (torch.nn.functional) of that same module to a proxy whose softmax(x, dim=1) returns
+a lazy handle, so that the predictor's softmax, expected depth and pdf maximum (:643-651) run as the one fused reduction of
+depth_head.py and the [v b, D, h, w] softmax is never stored; every other attribute of the proxy is torch.nn.functional's own.
 
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
@@ -597,6 +600,28 @@ def _native_cost_volume_warp(replaced):
 COST_VOLUME_SEAM = _Seam("cost_volume", COST_VOLUME_MODULE, (COST_VOLUME_NAME,), (), {COST_VOLUME_NAME: _native_cost_volume_warp})
 
 
+DEPTH_HEAD_NAME = "F"                                                 # `import torch.nn.functional as F` (:5); F.softmax at :643
+
+
+def _native_functional(replaced):
+    """The proxy for the predictor module's `F`: softmax(x, dim=1) of a 4-D float32 GPU tensor returns a depth_head.LazyPdf, whose
+    product with the [v b, D, 1, 1] candidates summed over dim 1 and whose torch.max over dim 1 (both keepdim=True,
+    DepthPredictorMultiView360.forward :646-651) are one run of the fused kernel; every other call of softmax (another dim or
+    dtype, CPU, extra arguments) and every other attribute (interpolate, grid_sample, ...) is the replaced module's own."""
+    from . import depth_head as _dh
+    return _dh.FunctionalProxy(replaced)
+
+
+DEPTH_HEAD_SEAM = _Seam("depth_head", COST_VOLUME_MODULE, (DEPTH_HEAD_NAME,), (), {DEPTH_HEAD_NAME: _native_functional})
+
+
+def install_depth_head():
+    """The half of install(depth_head=True): rebind the encoder module's `F` to the softmax proxy now if the module is imported,
+    else as soon as it is (import hook).  Returns the proxy or None."""
+    out = DEPTH_HEAD_SEAM.install()
+    return None if out is None else out[DEPTH_HEAD_NAME]
+
+
 def install_cost_volume():
     """The half of install(cost_volume=True): rebind the encoder module's warp_with_pose_depth_candidates now if the module is
     imported, else as soon as it is (import hook).  Returns the patched function or None."""
@@ -619,7 +644,7 @@ def install_psnr():
 
 
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
-            depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, **opts):
+            depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, depth_head: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
@@ -633,6 +658,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     metrics=True alone keeps meaning compute_ssim only).
     cost_volume=True: ALSO rebind the encoder's warp_with_pose_depth_candidates so that DepthPredictorMultiView360.forward builds
     raw_correlation_in with the fused cost-volume kernels (install_cost_volume; off by default).
+    depth_head=True: ALSO rebind that module's `F` so that its softmax, expected depth and pdf maximum run as the fused depth-head
+    kernels (install_depth_head; off by default).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -651,6 +678,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
         install_psnr()
     if cost_volume:
         install_cost_volume()
+    if depth_head:
+        install_depth_head()
     if lazy:
         if REGISTRY_MODULE in sys.modules:
             return _patch(sys.modules[REGISTRY_MODULE], **opts)
@@ -662,10 +691,11 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
 
 def uninstall() -> None:
     """Put the reference's own decoder class, adapter, compute_ssim, compute_psnr, compute_depth_metrics_batched,
-    compute_l1_sphere_loss, erode and warp_with_pose_depth_candidates back (and drop pending import hooks)."""
+    compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates and the predictor module's `F` (torch.nn.functional itself) back
+    (and drop pending import hooks)."""
     sys.meta_path[:] = [f for f in sys.meta_path
                         if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher, _DepthLossPatcher, _SeamPatcher))]
-    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM):
+    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM, DEPTH_HEAD_SEAM):
         seam.restore()
     dmod = sys.modules.get(DEPTH_MODULE)
     if dmod is not None:
