@@ -190,8 +190,8 @@ typedef struct S360Layout {
     size_t depths;              /* float[V*P]   view-space z of visible pairs (sort key) */
     size_t tile_count;          /* uint32[V*T] */
     size_t slot_ticket;         /* per-image instance-slot tickets, 256 B apart (cleared together with tile_count) */
-    size_t merge_done;          /* uint32[V*T][4] completion counters of the global merge passes of the long lists
-                                   (cleared together with tile_count) */
+    size_t merge_done;          /* uint32[V*T][4] completion counters of the merge passes of the long lists, + 1 ticket counter of the
+                                   merge units, + uint32[V*T] sorted 4 096-key chunks per tile (cleared together with tile_count) */
     size_t seg_flag;            /* uint32[V*T*4] S360_FLAG_SPLIT_LISTS: 1 = this (tile, quadrant) handed the rest of its list over to
                                    segment waves after SEG_HEAD entries (cleared together with tile_count) */
     size_t seg_arrive;          /* uint32[V*T*4] segment waves of a split quadrant that have delivered their phase-1 result (the

@@ -76,6 +76,8 @@ __host__ __device__ inline size_t seg_slots_of(const S360Params* prm) {
 #define S360_HDR_SEGWORK 6   /* header word: (tile, quadrant, segment) work items k_render queued for k_render_tail (seg_info[]) */
 #define S360_HDR_TILES_DONE 24  /* header word: tile workgroups of k_render<.., SPLIT> whose four quadrant waves have all retired (cleared by k_tile_scan) */
 #define S360_HDR_NLONG 25       /* header word: tiles with more than SORT_SHORT keys (k_tile_scan) */
+#define S360_HDR_SORT_ERR_TILE 26  /* header words: tile and pass of the first merge workgroup of k_sort_stage1 whose bounded wait expired */
+#define S360_HDR_SORT_ERR_PASS 27  /* (valid while header[7] >> 24 is non-zero; cleared by k_tile_scan) */
 #define S360_SEG_CLAIM 0x80000000u  /* bit 31 of a work item's second word: a segment wave has taken the item */
 #define S360_HDR_SEGBUFS 32  /* header words [32, 64): the segment-state pointers (SegBufs), written by k_tile_scan for k_render */
 

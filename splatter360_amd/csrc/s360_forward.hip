@@ -8,10 +8,9 @@
 //   k_tile_scan      exclusive scan of the per-tile instance counts -> tile ranges (+ sort-chunk table)
 //   k_emit           scatter (depth bits << 32 | pair) keys into their tile's bucket; training calls: reserve the
 //                    pairs' instance slots (one atomic per block) and write the slot owner table
-//   k_sort_stage1 / k_merge_all
-//                    per-tile ascending sort of the unique 64-bit keys (== stable radix sort by
+//   k_sort_stage1    per-tile ascending sort of the unique 64-bit keys (== stable radix sort by
 //                    (tile, depth) with ascending-index emission): LDS merge sort per list or per
-//                    4096-key chunk, global merge-path passes for multi-chunk lists
+//                    4096-key chunk, merge-path passes for multi-chunk lists inside the same launch
 //   k_render         1 workgroup per 16x16 tile = 4 autonomous waves of 8x8 pixels (no LDS, no barriers)
 #include "s360_device.h"
 #include "s360_prof.h"
@@ -768,7 +767,7 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* l
 
 // single block: tile_start[0..nt] = exclusive scan of tile_count; header bookkeeping.
 // Lists longer than SORT_SHORT keys are sorted as chunks of SORT_CHUNK keys (k_sort_stage1: one 512-thread
-// workgroup per chunk) followed, when there is more than one chunk, by global merge passes (k_merge_all);
+// workgroup per chunk) followed, when there is more than one chunk, by merge passes inside the same launch (its merge-role workgroups);
 // chunk_start[t] = number of such chunks before tile t (0 chunks for the short tiles, which have their own class).
 #ifndef S360_SORT_THREADS
 #define S360_SORT_THREADS 512   // workgroup of the sort kernels; a chunk is 8 keys per thread
@@ -779,12 +778,12 @@ constexpr uint32_t SORT_CHUNK = 8 * SORT_THREADS;
 static_assert(SORT_SHORT % SORT_THREADS == 0 && SORT_SHORT <= SORT_CHUNK, "short lists: SORT_SHORT / SORT_THREADS keys per thread");
 constexpr uint32_t MAX_PASSES = 4;
 __device__ __forceinline__ uint32_t ceil_log2_u32(uint32_t x) { return x <= 1 ? 0u : 32u - (uint32_t)__builtin_clz(x - 1); }
-// Lists of 2 .. LDSM_CHUNKS chunks (up to 16 384 keys: every long list of the encoder-like cloud, most of the surface-like one's) are
-// finished by ONE workgroup in LDS (merge_tile_lds: 128 KB of keys + padding, two in-LDS merge passes) — ONE write step after the chunk
-// sorts, so they count as one pass in the ping-pong parity; longer lists take ceil(log2 chunks) global merge passes.
-constexpr uint32_t LDSM_CHUNKS = 4;
-constexpr int LDSM_E = 32;   // outputs per thread and pass: SORT_THREADS * LDSM_E == LDSM_CHUNKS * SORT_CHUNK
-__device__ __forceinline__ uint32_t merge_passes_of(uint32_t nch) { return nch <= 1 ? 0u : nch <= LDSM_CHUNKS ? 1u : ceil_log2_u32(nch); }
+// Every multi-chunk list takes ceil(log2 chunks) merge passes of (pass, chunk) units (merge_unit), ping-ponging between `keys` and `alt`.
+__device__ __forceinline__ uint32_t merge_passes_of(uint32_t nch) { return ceil_log2_u32(nch); }
+#ifndef S360_SEGS_SPINS
+#define S360_SEGS_SPINS 600     // polls (~1.7 us apart) without finding anything before a waiting wave gives up: ~1 ms (the split workers of
+                                // k_render and the merge workgroups of k_sort_stage1: a guard against a hang, not a tuning knob)
+#endif
 
 // S360_FLAG_SPLIT_LISTS state (S360Layout part_* / seg_*), by value into the composites
 struct SegBufs {
@@ -860,7 +859,7 @@ __global__ __launch_bounds__(TS_BLOCK) void k_tile_scan(const uint32_t* __restri
         header[0] = carry;                    // num_instances ("num_rendered")
         header[1] = carry > cap ? 1u : 0u;    // overflow flag
         header[2] = lds_max;                  // longest tile list
-        {   // merge passes the longest (capacity-clamped) list needs: k_merge_all enters no pass beyond it
+        {   // merge passes the longest (capacity-clamped) list needs: k_sort_stage1 hands out no unit of a pass beyond it
             const uint32_t nmax = min(lds_max, cap);
             const uint32_t nch = nmax > SORT_SHORT ? (nmax + SORT_CHUNK - 1) / SORT_CHUNK : 0u;
             header[3] = merge_passes_of(nch);
@@ -872,6 +871,7 @@ __global__ __launch_bounds__(TS_BLOCK) void k_tile_scan(const uint32_t* __restri
         *reinterpret_cast<SegBufs*>(header + S360_HDR_SEGBUFS) = sg_in;
         header[S360_HDR_SPLIT] = 0;           // split (tile, quadrant) units (k_render counts them)
         header[6] = header[7] = 0;
+        header[S360_HDR_SORT_ERR_TILE] = header[S360_HDR_SORT_ERR_PASS] = 0;   // (with header[7], whose bits 24 and up are the sort's)
         // S360Params.header_mirror: the count and the overflow flag as ONE 64-bit store into host-visible memory — the caller's
         // next call sizes its buffers from it without ever synchronising with the device
         if (header_mirror) __hip_atomic_store(header_mirror, (unsigned long long)carry | ((unsigned long long)(carry > cap ? 1u : 0u) << 32) |
@@ -1074,6 +1074,13 @@ __global__ __launch_bounds__(S360_BLOCK) void k_emit(KParams kp, const uint32_t*
 }
 
 // ------------------------------------------------------------------------------ per-tile sort
+// Device-coherent 64-bit accesses (sc1: served by / written through to memory, not a per-XCD L2 line): what k_sort_stage1 uses
+// for the runs one workgroup writes and another — possibly behind a different XCD's L2 — reads in the same launch.
+// (Agent-scope release / acquire FENCES instead write back / invalidate the whole 4-MB L2: 1 024 workgroups doing that made the
+// merge stage 75 us slower than separate launches.)
+__device__ __forceinline__ uint64_t ld_dev(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_dev(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
 // Merge sort of one tile's bucket in LDS: every thread sorts E keys in registers (odd-even transposition
 // network), then log2(THREADS) merge passes; in each pass a thread finds its slice of the two runs being
 // merged with a merge-path binary search and merges E outputs serially.  ~2 barriers and ~(2E + log n)
@@ -1082,7 +1089,8 @@ __global__ __launch_bounds__(S360_BLOCK) void k_emit(KParams kp, const uint32_t*
 // by (tile, depth), index-ordered emission).  Measured alternatives that were slower on this workload:
 // 4-ary merge-path search + in-register bitonic merge of 2E candidates (more instructions; the kernel is
 // issue-bound on 64-bit compares/selects, not LDS-latency-bound), and an LDS radix sort.
-template <int THREADS, int E>
+// DEV: the sorted keys are stored device-coherently (st_dev) — for chunks another workgroup merges within the same launch.
+template <int THREADS, int E, bool DEV = false>
 __device__ __forceinline__ void block_merge_sort(const uint64_t* __restrict__ in, uint64_t* __restrict__ out,
                                                  uint32_t* __restrict__ list, uint32_t n, uint64_t* lds_m) {
     // [CAP + CAP/E]: one pad slot per E keys.  Threads walk the runs with a stride of ~E (or ~E/2) keys;
@@ -1174,19 +1182,18 @@ __device__ __forceinline__ void block_merge_sort(const uint64_t* __restrict__ in
         const uint32_t i = (uint32_t)(tid * E + q);
         if (i < n) {
             const uint64_t kq = lds_m[S360_PHYS(i)];
-            out[i] = kq;
+            if (DEV) st_dev(out + i, kq); else out[i] = kq;
             if (list) list[i] = (uint32_t)kq;
         }
     }
 #undef S360_PHYS
 }
 
-// ---- long lists (n > SORT_CHUNK): chunk sort + global merge passes ------------------------------------------
+// ---- long lists (n > SORT_SHORT): chunk sort + merge passes -------------------------------------------------
 // Work unit = one SORT_CHUNK-sized output chunk (t, k) of a long tile, found from the block index by a binary
 // search over chunk_start[].  A tile with c chunks needs P = ceil(log2 c) merge passes; it ping-pongs between
 // `keys` and `alt` such that the LAST pass lands in `keys`: the buffer holding the runs before pass i is
 // `alt` when (P - i) is odd.  Tiles needing more than max_passes passes are left to the global-memory network (sort_tiles_global_body).
-
 
 struct ChunkUnit {
     uint32_t s, n, k, passes, t;  // tile start (clamped), tile length, chunk index inside the tile, merge passes of the tile, tile
@@ -1219,53 +1226,9 @@ __device__ __forceinline__ ChunkUnit chunk_unit(const uint32_t* __restrict__ til
     return u;
 }
 
-// ONE launch for the first sorting stage: chunk blocks first in the grid (their results feed the merge passes, the critical
-// path), then one block per tile for the short lists, and a last block that deals the composite's tile order — round 1
-// ran the short-list sort and the ordering on a process-wide side stream (fork / join events, a host mutex): ~25 us of
-// cross-stream latency inside a 100-us stage, and library-global state.
-__global__ __launch_bounds__(SORT_THREADS) void k_sort_stage1(const uint32_t* __restrict__ tile_start, const uint32_t* __restrict__ chunk_start,
-                                                    int nt, uint64_t* __restrict__ keys, uint64_t* __restrict__ alt,
-                                                    uint32_t* __restrict__ list, uint32_t cap, uint32_t max_passes, uint32_t cgrid,
-                                                    const uint32_t* __restrict__ tile_count, uint32_t* __restrict__ tile_order,
-                                                    const uint32_t* __restrict__ header, unsigned long long* __restrict__ wide_mirror) {
-    extern __shared__ __attribute__((aligned(16))) uint64_t lds_m[];
-    const uint32_t bid = blockIdx.x;
-    if (bid < cgrid) {  // 4 096-key chunks of the long lists, grid-stride over the chunk table
-        const uint32_t nchunks = chunk_start[nt];
-        for (uint32_t b = bid; b < nchunks; b += cgrid) {
-            const ChunkUnit u = chunk_unit(tile_start, chunk_start, nt, cap, b);
-            if (u.valid && u.passes <= max_passes) {
-                const uint32_t c0 = u.k * SORT_CHUNK, len = min(SORT_CHUNK, u.n - c0);
-                uint64_t* dst = ((u.passes & 1u) ? alt : keys) + u.s + c0;
-                block_merge_sort<SORT_THREADS, 8>(keys + u.s + c0, dst, u.passes == 0 ? list + u.s : nullptr, len, lds_m);
-            }
-            __syncthreads();
-        }
-        return;
-    }
-    if (bid < cgrid + (uint32_t)nt) {  // lists of up to 2 048 keys: one workgroup each
-        const uint32_t tile = bid - cgrid;
-        const uint32_t s = min(tile_start[tile], cap), e = min(tile_start[tile + 1], cap);
-        const uint32_t n = e - s;
-        if (n == 0 || n > SORT_SHORT) return;
-        block_merge_sort<SORT_THREADS, (int)(SORT_SHORT / SORT_THREADS)>(keys + s, keys + s, list + s, n, lds_m);
-        return;
-    }
-    // S360Params.header_mirror word 2: (Gaussian, view) pairs binned over more than 32 tiles (k_emit, the previous launch, counted them)
-    if (wide_mirror && threadIdx.x == 0) __hip_atomic_store(wide_mirror, (unsigned long long)header[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (tile_order) order_units_body<SORT_THREADS>(tile_count, tile_order, nt);  // longest list first (dispatch order of k_render)
-}
-
 // Merge path over two sorted runs in global memory: number of A elements among the first d outputs.  Executed by
 // one whole wave as a 64-ary search (64 probes per round, the ballot of the monotone predicate locates the
 // boundary): 2-3 dependent global-memory round trips instead of the ~13 of a binary search.
-// Device-coherent 64-bit accesses (sc1: served by / written through to memory, not a per-XCD L2 line): what the persistent merge
-// kernel uses for the runs one workgroup writes and another — possibly behind a different XCD's L2 — reads in the same launch.
-// (Agent-scope release / acquire FENCES instead write back / invalidate the whole 4-MB L2: 1 024 workgroups doing that made the
-// merge stage 75 us slower than separate launches.)
-__device__ __forceinline__ uint64_t ld_dev(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_dev(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 __device__ __forceinline__ uint32_t merge_path_global_wave(const uint64_t* __restrict__ A, uint32_t la,
                                                            const uint64_t* __restrict__ B, uint32_t lb, uint32_t d, int lane) {
     uint32_t lo = d > lb ? d - lb : 0u, hi = d < la ? d : la;  // answer in [lo, hi]; pred(a) := A[a] <= B[d-1-a]  (answer > a)
@@ -1285,23 +1248,10 @@ __device__ __forceinline__ uint32_t merge_path_global_wave(const uint64_t* __res
     return lo;
 }
 
-// ONE launch for everything after the chunk sorts (round 3: four k_merge_pass launches + k_sort_tiles_global, 40 us of which
-// two and a half launches found nothing to do).  Work units = (pass, chunk) in pass-major order, handed out by a ticket counter
-// to whichever workgroup is free; a unit of pass p >= 1 waits until ALL chunks of its tile have finished pass p - 1
-// (merge_done[tile][p-1], one device-scope counter per (tile, pass); the runs themselves are written and read with
-// device-coherent accesses, so no cache-wide fence is needed: stores complete, workgroup barrier, one relaxed atomic).  A unit only ever waits for units with LOWER tickets, and a ticket is only taken by
-// a workgroup that is running, so the schedule cannot deadlock whatever share of the grid is resident.  Passes beyond header[3]
-// (what the longest list of THIS call needs) get no tickets; lists beyond SORT_CHUNK << max_passes keys fall through to the
-// global-memory network at the end of the same launch.
-#ifndef S360_MERGE_GRID
-#define S360_MERGE_GRID 256   // one workgroup per CU: the kernel's 135 KB of LDS (merge_tile_lds) admit no more, and workgroups beyond
-                              // the resident ones would each be dispatched, take one void ticket and exit — three more rounds (1 024: +9 us)
-#endif
-__device__ __forceinline__ void merge_unit(const ChunkUnit& u, uint32_t pass, const uint64_t* __restrict__ keys_c, uint64_t* __restrict__ keys,
+__device__ __forceinline__ void merge_unit(const ChunkUnit& u, uint32_t pass, uint64_t* __restrict__ keys,
                                            uint64_t* __restrict__ alt, uint32_t* __restrict__ list, uint64_t* lds_m, uint32_t* s_part) {
     constexpr int THREADS = SORT_THREADS, E = 8;
 #define S360_PHYS(i) ((i) + (i) / E)
-    (void)keys_c;
     const uint32_t R = SORT_CHUNK << pass;
     const uint32_t o_tile = u.k * SORT_CHUNK, len = min(SORT_CHUNK, u.n - o_tile);
     const uint32_t pair0 = o_tile / (2 * R) * (2 * R);
@@ -1365,94 +1315,15 @@ __device__ __forceinline__ void merge_unit(const ChunkUnit& u, uint32_t pass, co
 #undef S360_PHYS
 }
 
-// Whole-list merge in LDS for a tile of 2 .. LDSM_CHUNKS sorted chunks (n <= 16 384 keys): ONE workgroup loads the chunk-sorted runs
-// (written by k_sort_stage1, the previous launch: plain loads), merges neighbouring runs in LDS until one remains — every thread finds
-// its LDSM_E consecutive outputs with a merge-path binary search and merges them serially into registers, barrier, write back — and
-// stores the sorted keys and the list.  Replaces two global merge passes (each: two 64-ary searches with device-coherent loads, a
-// 4 096-key LDS merge, write-through stores, a drain and a counter another workgroup polls: ~15 us a pass, 3 % VALU-busy) by ~10 us of
-// one workgroup's time with no cross-workgroup traffic at all.  Runs may be ragged (the last one short or missing).
-static_assert(SORT_THREADS * LDSM_E == (int)(LDSM_CHUNKS * SORT_CHUNK), "a thread merges LDSM_E outputs per pass");
-constexpr size_t LDSM_LDS_BYTES = (size_t)(LDSM_CHUNKS * SORT_CHUNK + LDSM_CHUNKS * SORT_CHUNK / LDSM_E) * 8;   // one pad slot per LDSM_E keys
-__device__ __forceinline__ void merge_tile_lds(uint32_t n, const uint64_t* __restrict__ src, uint64_t* __restrict__ dst, uint32_t* __restrict__ lst,
-                                               uint64_t* lds_m) {
-    constexpr int E = LDSM_E;
-#define S360_PHYS(i) ((i) + (i) / E)
-    {   // all of a thread's (up to E) loads in flight at once: a load-then-store loop pays the memory latency per iteration (27 x ~0.7 us)
-        uint64_t k[E];
-#pragma unroll
-        for (int q = 0; q < E; ++q) {
-            const uint32_t i = (uint32_t)threadIdx.x + (uint32_t)q * SORT_THREADS;
-            k[q] = i < n ? src[i] : 0ull;
-        }
-#pragma unroll
-        for (int q = 0; q < E; ++q) {
-            const uint32_t i = (uint32_t)threadIdx.x + (uint32_t)q * SORT_THREADS;
-            if (i < n) lds_m[S360_PHYS(i)] = k[q];
-        }
-    }
-    __syncthreads();
-    const uint32_t out0 = (uint32_t)threadIdx.x * E;
-    for (uint32_t width = SORT_CHUNK; width < n; width <<= 1) {
-        uint64_t k[E];
-        if (out0 < n) {   // (threads past the end only take part in the barriers)
-            const uint32_t pa = out0 / (2 * width) * (2 * width), pb = pa + width;
-            const uint32_t la = min(width, n - pa), lb = pb < n ? min(width, n - pb) : 0u;
-            const uint32_t diag = out0 - pa;
-            uint32_t lo = diag > lb ? diag - lb : 0u, hi = diag < la ? diag : la;
-            while (lo < hi) {   // merge path: first a with A[a] > B[diag - 1 - a]
-                const uint32_t mid = (lo + hi) >> 1;
-                if (lds_m[S360_PHYS(pa + mid)] <= lds_m[S360_PHYS(pb + (diag - 1 - mid))]) lo = mid + 1; else hi = mid;
-            }
-            uint32_t a = lo, b = diag - lo;
-            uint64_t ka = a < la ? lds_m[S360_PHYS(pa + a)] : ~0ull, kb = b < lb ? lds_m[S360_PHYS(pb + b)] : ~0ull;
-#pragma unroll
-            for (int q = 0; q < E; ++q) {
-                const bool take_a = ka <= kb;
-                k[q] = take_a ? ka : kb;
-                if (take_a) {
-                    ++a;
-                    ka = a < la ? lds_m[S360_PHYS(pa + a)] : ~0ull;
-                } else {
-                    ++b;
-                    kb = b < lb ? lds_m[S360_PHYS(pb + b)] : ~0ull;
-                }
-            }
-        }
-        __syncthreads();          // every read of this pass precedes its writes
-        if (out0 < n) {
-#pragma unroll
-            for (int q = 0; q < E; ++q)
-                if (out0 + q < n) lds_m[S360_PHYS(out0 + q)] = k[q];
-        }
-        __syncthreads();
-    }
-    {   // (LDS reads batched like the loads above: as a read-then-store loop every iteration waits for its own LDS read)
-        uint64_t k[E];
-#pragma unroll
-        for (int q = 0; q < E; ++q) {
-            const uint32_t i = (uint32_t)threadIdx.x + (uint32_t)q * SORT_THREADS;
-            k[q] = i < n ? lds_m[S360_PHYS(i)] : 0ull;
-        }
-#pragma unroll
-        for (int q = 0; q < E; ++q) {
-            const uint32_t i = (uint32_t)threadIdx.x + (uint32_t)q * SORT_THREADS;
-            if (i < n) {
-                dst[i] = k[q];
-                lst[i] = (uint32_t)k[q];
-            }
-        }
-    }
-#undef S360_PHYS
-}
-
 // Fallback for tile lists beyond the merge-pass budget (> SORT_CHUNK << MAX_PASSES keys): one workgroup sorts directly in global memory with
 // the ascending-only form of the bitonic network (first sub-step of every stage compares mirrored
 // positions), which tolerates VIRTUAL +inf padding at indices >= n: an ascending compare-exchange never
 // moves a padding key inwards, so nothing outside [0, n) is ever read or written.  Rare and slow.
 template <int THREADS>
 __device__ __forceinline__ void sort_tiles_global_body(const uint32_t* __restrict__ tile_start, uint64_t* __restrict__ keys,
-                                                       uint32_t* __restrict__ list, uint32_t lo, uint32_t cap, int nt) {
-  for (int tile = blockIdx.x; tile < nt; tile += gridDim.x) {   // grid-stride over the tiles: almost always nothing to do
+                                                       uint32_t* __restrict__ list, uint32_t lo, uint32_t cap, int nt,
+                                                       uint32_t first, uint32_t stride) {
+  for (int tile = (int)first; tile < nt; tile += (int)stride) {   // workgroup `first` of `stride`, striding over the tiles: almost always nothing to do
     const uint32_t s = min(tile_start[tile], cap), e = min(tile_start[tile + 1], cap);
     const uint32_t n = e - s;
     if (n <= lo) continue;   // block-uniform
@@ -1494,52 +1365,125 @@ __device__ __forceinline__ void sort_tiles_global_body(const uint32_t* __restric
   }
 }
 
-__global__ __launch_bounds__(SORT_THREADS) void k_merge_all(const uint32_t* __restrict__ tile_start, const uint32_t* __restrict__ chunk_start,
-                                                  int nt, uint64_t* __restrict__ keys, uint64_t* __restrict__ alt,
-                                                  uint32_t* __restrict__ list, uint32_t cap, uint32_t max_passes,
-                                                  const uint32_t* __restrict__ header, uint32_t* __restrict__ merge_done,
-                                                  uint32_t global_lo) {
-    extern __shared__ __attribute__((aligned(16))) uint64_t lds_m[];  // LDSM_LDS_BYTES: [SORT_CHUNK + SORT_CHUNK/E] skewed for the pair merges, the whole list for merge_tile_lds
-    __shared__ uint32_t s_part[2];
-    __shared__ uint32_t s_ticket;
-    const uint32_t npass = min(header[3], max_passes);   // merge passes the longest (capacity-clamped) list of this call needs
-    const uint32_t nchunks = npass ? chunk_start[nt] : 0u;
-    const uint32_t nunits = npass * nchunks;
-    uint32_t* const queue = merge_done + (size_t)nt * MAX_PASSES;   // the work queue's ticket counter (cleared with the counters)
-    for (;;) {
-        if (threadIdx.x == 0) s_ticket = nunits ? __hip_atomic_fetch_add(queue, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        __syncthreads();
-        const uint32_t tk = s_ticket;
-        __syncthreads();
-        if (tk >= nunits) break;
-        const uint32_t pass = tk / nchunks, blk = tk - pass * nchunks;
-        const ChunkUnit u = chunk_unit(tile_start, chunk_start, nt, cap, blk);
-        if (!u.valid || u.passes > max_passes || pass >= u.passes) continue;  // block-uniform
-        const uint32_t nch = (u.n + SORT_CHUNK - 1) / SORT_CHUNK;
-        if (nch <= LDSM_CHUNKS) {   // (one pass by merge_passes_of: only pass 0 gets here) the whole list, by the unit of its first chunk
-            if (u.k == 0) merge_tile_lds(u.n, alt + u.s, keys + u.s, list + u.s, lds_m);
-            continue;               // (the barrier behind the next ticket separates this unit's LDS reads from the next one's writes)
-        }
-        if (pass > 0) {
-            if (threadIdx.x == 0) {
-                while (__hip_atomic_load(&merge_done[(size_t)u.t * MAX_PASSES + pass - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nch)
-                    __builtin_amdgcn_s_sleep(4);
+// ONE launch for the whole sort.  Roles by block index:
+//   [0, cgrid)                 chunk blocks: the 4 096-key chunks of the long lists, first in the grid (their results feed the merge
+//                              passes, the critical path);
+//   [cgrid, cgrid + mgrid)     merge blocks: the (pass, chunk) merge units of every multi-chunk list (merge_unit), in pass-major order
+//                              from a ticket counter, and — once the tickets have run out — the global-memory fallback for lists beyond
+//                              SORT_CHUNK << max_passes keys;
+//   [cgrid + mgrid, .. + nt)   one block per tile for the lists of up to 2 048 keys: the bulk of the launch's time, under which the
+//                              handful of merge units runs (as a launch of their own they were 23 us of a nearly idle chip);
+//   the last block             deals the composite's tile order.
+// Runs that cross workgroups inside the launch — the sorted chunks of a list that has merge passes, and every merge pass's output — are
+// stored device-coherently, each thread drains its stores (s_waitcnt vmcnt(0)), workgroup barrier, then ONE relaxed agent-scope
+// increment: chunks_sorted[tile] by a chunk block, merge_done[tile][pass] by a merge unit.  No cache-wide fence anywhere.
+//
+// Waiting.  A pass-0 unit waits for chunks_sorted[tile] == the tile's chunk count, a pass-p unit for merge_done[tile][p - 1] == the same.
+// Neither wait can deadlock, whatever share of the grid is resident:
+//   * chunks_sorted is advanced only by chunk blocks.  They wait for nothing, and their block indices are below every merge block's.
+//     The grid's workgroups are dealt to the XCDs, and each XCD starts its share in index order — not in lockstep with the others: a
+//     merge block may run on one XCD while a chunk block is still waiting for a slot on another.  But everything that can hold a slot
+//     in front of that chunk block on its own XCD has a lower index, so it is a chunk block too, waits for nothing and ends: every
+//     chunk block is started and finishes, whatever the merge blocks are doing meanwhile.
+//   * merge_done[.][p - 1] is advanced only by units of pass p - 1, whose tickets (pass-major: pass * nchunks + chunk) are strictly lower
+//     than the waiting unit's.  A ticket is only ever taken by a workgroup that is running, and that workgroup in turn waits only for
+//     still lower tickets or for chunk blocks: by induction over the ticket every wait ends.
+// Every wait is bounded all the same (S360_SEGS_SPINS polls, ~1 ms: the bound of the split workers): a workgroup whose bound expires
+// adds 0x1000000 to header[7] (RasterState.split_errors / sort_errors), leaves (tile, pass) in header[S360_HDR_SORT_ERR_TILE / _PASS] and returns; the lists of
+// such a call are invalid.  Passes beyond header[3] (what the longest list of THIS call needs) get no tickets.
+#ifndef S360_MERGE_BLOCKS
+#define S360_MERGE_BLOCKS 256   // upper bound of the merge blocks; those beyond the call's unit count return at once
+#endif
+__device__ __forceinline__ bool wait_count(const uint32_t* counter, uint32_t need) {   // one thread; false: gave up
+    uint32_t spins = 0;
+    while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
+        if (++spins > (uint32_t)S360_SEGS_SPINS) return false;
+        __builtin_amdgcn_s_sleep(32);
+    }
+    return true;
+}
+// every thread drains its device-coherent stores, then the workgroup meets: what follows the call may publish them with one counter.
+// (A workgroup-scope release fence alone compiles to `s_waitcnt lgkmcnt(0)` on gfx950 — the sc1 global stores were not waited on, and
+// a workgroup behind another XCD could read a run before it had landed.  No cache-wide write-back is needed: the
+// stores are device-coherent themselves.)
+__device__ __forceinline__ void drain_stores_and_sync() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+}
+__global__ __launch_bounds__(SORT_THREADS) void k_sort_stage1(const uint32_t* __restrict__ tile_start, const uint32_t* __restrict__ chunk_start,
+                                                    int nt, uint64_t* __restrict__ keys, uint64_t* __restrict__ alt,
+                                                    uint32_t* __restrict__ list, uint32_t cap, uint32_t max_passes, uint32_t cgrid,
+                                                    const uint32_t* __restrict__ tile_count, uint32_t* __restrict__ tile_order,
+                                                    uint32_t* __restrict__ header, unsigned long long* __restrict__ wide_mirror,
+                                                    uint32_t* __restrict__ merge_done, uint32_t mgrid, uint32_t global_lo) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds_m[];   // [SORT_CHUNK + SORT_CHUNK / 8], skewed
+    uint32_t* const queue = merge_done + (size_t)nt * MAX_PASSES;   // the merge units' ticket counter
+    uint32_t* const chunks_sorted = queue + 1;                      // [nt]: sorted chunks per tile (all three cleared with tile_count)
+    const uint32_t bid = blockIdx.x;
+    if (bid < cgrid) {  // 4 096-key chunks of the long lists, grid-stride over the chunk table
+        const uint32_t nchunks = chunk_start[nt];
+        for (uint32_t b = bid; b < nchunks; b += cgrid) {
+            const ChunkUnit u = chunk_unit(tile_start, chunk_start, nt, cap, b);
+            if (u.valid && u.passes <= max_passes) {
+                const uint32_t c0 = u.k * SORT_CHUNK, len = min(SORT_CHUNK, u.n - c0);
+                uint64_t* dst = ((u.passes & 1u) ? alt : keys) + u.s + c0;
+                if (u.passes == 0) {   // the whole list (2 049 .. 4 096 keys): nobody reads it before the next launch
+                    block_merge_sort<SORT_THREADS, 8>(keys + u.s + c0, dst, list + u.s, len, lds_m);
+                } else {               // a run of pass 0, read by a merge block of this launch
+                    block_merge_sort<SORT_THREADS, 8, true>(keys + u.s + c0, dst, nullptr, len, lds_m);
+                    drain_stores_and_sync();
+                    if (threadIdx.x == 0) __hip_atomic_fetch_add(&chunks_sorted[u.t], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
             }
             __syncthreads();
         }
-        merge_unit(u, pass, keys, keys, alt, list, lds_m, s_part);   // runs read and written with device-coherent accesses
-        // Every thread DRAINS its own write-through stores (s_waitcnt vmcnt(0): a store's counter is released when the memory side
-        // has acknowledged it) before the workgroup barrier, and only then does thread 0 publish the pass.  A workgroup-scope
-        // release fence alone compiles to `s_waitcnt lgkmcnt(0)` on gfx950 — the sc1 global stores were not waited on, and a
-        // workgroup behind another XCD could read a run before it had landed.  No cache-wide write-back is
-        // needed: the stores are device-coherent themselves.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __syncthreads();                                              // (also: LDS and s_part are reused next)
-        if (threadIdx.x == 0 && pass + 1 < u.passes)
-            __hip_atomic_fetch_add(&merge_done[(size_t)u.t * MAX_PASSES + pass], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
     }
-    if (header[2] > global_lo) sort_tiles_global_body<SORT_THREADS>(tile_start, keys, list, global_lo, cap, nt);
+    if (bid < cgrid + mgrid) {  // merge units of the multi-chunk lists
+        __shared__ uint32_t s_part[2];
+        __shared__ uint32_t s_ticket;
+        const uint32_t npass = min(header[3], max_passes);   // merge passes the longest (capacity-clamped) list of this call needs
+        const uint32_t nchunks = npass ? chunk_start[nt] : 0u;
+        const uint32_t nunits = npass * nchunks;
+        while (bid - cgrid < nunits) {   // (a block beyond the unit count would only take a void ticket)
+            if (threadIdx.x == 0) s_ticket = __hip_atomic_fetch_add(queue, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();
+            const uint32_t tk = s_ticket;
+            __syncthreads();
+            if (tk >= nunits) break;
+            const uint32_t pass = tk / nchunks, blk = tk - pass * nchunks;
+            const ChunkUnit u = chunk_unit(tile_start, chunk_start, nt, cap, blk);
+            if (!u.valid || u.passes > max_passes || pass >= u.passes) continue;  // block-uniform
+            const uint32_t nch = (u.n + SORT_CHUNK - 1) / SORT_CHUNK;
+            if (threadIdx.x == 0) {
+                const bool ok = wait_count(pass ? &merge_done[(size_t)u.t * MAX_PASSES + pass - 1] : &chunks_sorted[u.t], nch);
+                if (!ok && atomicAdd(&header[7], 0x1000000u) < 0x1000000u) { header[S360_HDR_SORT_ERR_TILE] = u.t; header[S360_HDR_SORT_ERR_PASS] = pass; }
+                s_ticket = ok ? 1u : 0u;
+            }
+            __syncthreads();
+            const bool ok = s_ticket != 0u;
+            __syncthreads();
+            if (!ok) return;
+            merge_unit(u, pass, keys, alt, list, lds_m, s_part);   // runs read and written with device-coherent accesses
+            drain_stores_and_sync();                                      // (also: LDS and s_part are reused next)
+            if (threadIdx.x == 0 && pass + 1 < u.passes)
+                __hip_atomic_fetch_add(&merge_done[(size_t)u.t * MAX_PASSES + pass], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (header[2] > global_lo) sort_tiles_global_body<SORT_THREADS>(tile_start, keys, list, global_lo, cap, nt, bid - cgrid, mgrid);
+        return;
+    }
+    if (bid < cgrid + mgrid + (uint32_t)nt) {  // lists of up to 2 048 keys: one workgroup each
+        const uint32_t tile = bid - cgrid - mgrid;
+        const uint32_t s = min(tile_start[tile], cap), e = min(tile_start[tile + 1], cap);
+        const uint32_t n = e - s;
+        if (n == 0 || n > SORT_SHORT) return;
+        block_merge_sort<SORT_THREADS, (int)(SORT_SHORT / SORT_THREADS)>(keys + s, keys + s, list + s, n, lds_m);
+        return;
+    }
+    // S360Params.header_mirror word 2: (Gaussian, view) pairs binned over more than 32 tiles (k_emit, the previous launch, counted them)
+    if (wide_mirror && threadIdx.x == 0) __hip_atomic_store(wide_mirror, (unsigned long long)header[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (tile_order) order_units_body<SORT_THREADS>(tile_count, tile_order, nt);  // longest list first (dispatch order of k_render)
 }
 
 // ------------------------------------------------------------------------------ composite
@@ -1800,9 +1744,6 @@ __device__ __forceinline__ void seg_item(const KParams& kp, const S360View* __re
 #endif
 #ifndef S360_P2_GRID
 #define S360_P2_GRID 1024
-#endif
-#ifndef S360_SEGS_SPINS
-#define S360_SEGS_SPINS 600     // polls (~1.7 us apart) without finding anything before a segment wave gives up: ~1 ms
 #endif
 template <bool WITH_DEPTH, bool SPLIT>
 __global__ __launch_bounds__(S360_BLOCK) __attribute__((amdgpu_waves_per_eu(SPLIT ? S360_SPLIT_WAVES : 6, SPLIT ? S360_SPLIT_WAVES : 6))) void k_render(KParams kp, const S360View* __restrict__ views,
@@ -2287,7 +2228,7 @@ __global__ __launch_bounds__(S360_BLOCK) __attribute__((amdgpu_waves_per_eu(SPLI
 // that differs from the sequential product only by floating-point association (T_in is a product of segment products): images
 // within 1e-6 of the unsplit composite, stop decisions identical except where a product lands within rounding of 1e-4.
 // No wave ever waits for another: the phase-1 results come from the previous launch, and the combine is done by whoever arrives last
-// (device-coherent stores, drained with s_waitcnt vmcnt(0), then ONE agent-scope counter — the pattern of k_merge_all).  The
+// (device-coherent stores, drained with s_waitcnt vmcnt(0), then ONE agent-scope counter — the pattern of k_sort_stage1's merge units).  The
 // arrival count is broadcast BY VALUE (__shfl), never v_readfirstlane: a build that handed out work through a ticket loop the
 // compiler treated as divergent left the lanes that are not lane 0 with ticket 0 for ever and hung the GPU.
 #ifndef S360_TAIL_GRID
@@ -2596,7 +2537,7 @@ extern "C" int s360_layout(const S360Params* prm, S360Layout* out) {
     out->depths = take(np * 4);
     out->tile_count = take(nt * 4);
     out->slot_ticket = take((size_t)prm->V * 256);  // per-image instance-slot tickets, 256 B apart; cleared with tile_count
-    out->merge_done = take((nt * MAX_PASSES + 1) * 4);   // completion counters of the merge passes, one per (tile, pass), + the ticket counter of their work queue; cleared with tile_count
+    out->merge_done = take((nt * MAX_PASSES + 1 + nt) * 4);   // completion counters of the merge passes, one per (tile, pass), + the ticket counter of their work queue + sorted chunks per tile; cleared with tile_count
     out->seg_flag = take(nt * 4 * 4);                    // S360_FLAG_SPLIT_LISTS: split mark / arrival counters per (tile, quadrant); cleared with tile_count
     out->seg_arrive = take(nt * 4 * 4);
     out->seg_arrive2 = take((nt * 4 + 1) * 4);           // ... + the ticket counter of k_render_tail's work queue
@@ -2812,35 +2753,22 @@ static int forward_impl(const S360Params* prm, const S360View* views, const floa
         ProfScope ps(PS_SORT, st);
         {
             // Lists of up to 2 048 keys (the bulk) are sorted by one workgroup each; longer ones as 4 096-key chunks followed,
-            // for multi-chunk lists, by `passes` global merge passes (k_merge_all).  The upper bound of the pass count is fixed on
+            // for multi-chunk lists, by up to `passes` merge passes, all in ONE launch.  The upper bound of the pass count is fixed on
             // the host (no read-back): enough for the longest possible list, capped at MAX_PASSES (4 096 << 4 = 65 536 keys);
-            // passes no list of the call needs return at once (header[3]); anything longer falls through to the global network.
+            // passes no list of the call needs get no units (header[3]); anything longer falls through to the global network,
+            // the merge blocks' last role.
             const size_t cap_keys = kp.cap < (uint32_t)kp.P ? kp.cap : (size_t)kp.P;   // a tile holds a Gaussian at most once
             uint32_t passes = 0;
             while (passes < MAX_PASSES && ((size_t)SORT_CHUNK << passes) < cap_keys) ++passes;
             const uint32_t global_lo = SORT_CHUNK << passes;  // lists longer than this go to the global-memory network
             // the chunk blocks walk the chunk table grid-stride, so a moderate grid serves any count
             const unsigned cgrid = (unsigned)min((size_t)1024, (size_t)kp.cap / SORT_CHUNK + (size_t)kp.cap / SORT_SHORT + 2);
+            const unsigned mgrid = passes == 0 ? 0u : cgrid < (unsigned)S360_MERGE_BLOCKS ? cgrid : (unsigned)S360_MERGE_BLOCKS;
             const size_t lds512 = (size_t)(SORT_CHUNK + SORT_CHUNK / 8) * 8;
-            hipLaunchKernelGGL(k_sort_stage1, dim3(cgrid + nt + 1), dim3(SORT_THREADS), lds512, st, tile_start, chunk_start, nt, keys, keys_alt, list,
+            hipLaunchKernelGGL(k_sort_stage1, dim3(cgrid + mgrid + nt + 1), dim3(SORT_THREADS), lds512, st, tile_start, chunk_start, nt, keys, keys_alt, list,
                                kp.cap, passes, cgrid, tile_count, tile_order, header,
-                               prm->header_mirror ? (unsigned long long*)prm->header_mirror + 2 : (unsigned long long*)nullptr);
-            // everything after the chunk sorts in ONE launch: persistent workgroups, pass by pass behind per-tile completion
-            // counters; passes no list of the call needs are never entered, the global-memory fallback runs in the same launch
-            if (passes > 0) {
-                const unsigned mgrid = cgrid < (unsigned)S360_MERGE_GRID ? cgrid : (unsigned)S360_MERGE_GRID;
-                {   // 135 KB of dynamic LDS needs the opt-in, once per device (idempotent: a race sets it twice)
-                    static bool attr_done[64] = {};
-                    int dev = 0;
-                    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && !attr_done[dev]) {
-                        (void)hipFuncSetAttribute((const void*)k_merge_all, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSM_LDS_BYTES);
-                        (void)hipGetLastError();
-                        attr_done[dev] = true;
-                    }
-                }
-                hipLaunchKernelGGL(k_merge_all, dim3(mgrid), dim3(SORT_THREADS), LDSM_LDS_BYTES, st, tile_start, chunk_start, nt, keys, keys_alt, list,
-                                   kp.cap, passes, header, (uint32_t*)(ws + L.merge_done), (size_t)global_lo < cap_keys ? global_lo : 0xFFFFFFFFu);
-            }
+                               prm->header_mirror ? (unsigned long long*)prm->header_mirror + 2 : (unsigned long long*)nullptr,
+                               (uint32_t*)(ws + L.merge_done), mgrid, (size_t)global_lo < cap_keys ? global_lo : 0xFFFFFFFFu);
         }
         S360_CHECK_LAUNCH();
     }

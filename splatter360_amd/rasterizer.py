@@ -378,8 +378,19 @@ class RasterState:
     def split_errors(self) -> int:
         """header[7] (host read): 0 unless k_render_tail met a corrupt segment work item (it then skips the item; the images of such a
         call are invalid).  No wave of the split path ever waits for another one, so there is no time-out any more.  Never seen on a
-        correct build; the tests and bench.py assert it stays 0."""
+        correct build; the tests and bench.py assert it stays 0.  Bits 24 and up belong to the sort (sort_errors): they make this word
+        non-zero too, so every check of it covers both."""
         return int(self.header()[7].item())
+
+    def sort_errors(self) -> int:
+        """header[7] >> 24 (host read): merge workgroups of k_sort_stage1 whose bounded wait for the runs of a long tile list (another
+        workgroup's chunk sorts or previous merge pass) expired; header[26] / header[27] (S360_HDR_SORT_ERR_TILE / _PASS) hold the first
+        one's tile and pass.  The tile lists, and with them the images, of such a call are invalid: a workgroup that gives up leaves
+        its units unmerged, and the units that depend on them give up in turn.  The bound is wall time (~1 ms of polling), not
+        progress: 0 on a correct build with the device to itself — every such wait is for a workgroup that is already running or
+        about to be dispatched — but a non-zero value can also mean a starved device (one time-sliced with other processes, or a
+        call whose chunk sorts alone outlast the bound), so callers that cannot rule that out check it, or split_errors(), per call."""
+        return int(self.header()[7].item()) >> 24
 
     def mopup_items(self) -> int:
         """Host read, after the forward and before the backward (S360_FLAG_SPLIT_LISTS): how many of the header[6] queued segment work
