@@ -685,6 +685,55 @@ int s360_depth_head_backward(const float* logits, const float* candidates, const
                              void* stream);
 
 /*
+ * The encoder's fine-depth and opacity tail (csrc/s360_depth_tail.hip): the elementwise stretch between the depth head and the
+ * adapter.  Additive entries: the ABI version stays.  All of them: contiguous float32 device memory, kernels on `stream`, float64
+ * arithmetic rounded once per output, no workspace, no memset, no atomics, no host synchronisation, every output element written:
+ * bit-identical from call to call and stream to stream.  Null required pointers, non-positive sizes, s < 1, an unknown mode,
+ * gpp < 1, v < 1, n % v != 0 or an exponent that is not finite and positive: S360_E_BADARG before any GPU work.  n <= 65535 and
+ * fewer than 2^30 pixels per map.
+ *
+ * s360_upsample_forward (depth_predictor_multiview_360.py:650-658, one map per call): dst[n, 1, h s, w s] from src[n, 1, h, w].
+ *   mode S360_UP_NEAREST: dst[Y, X] = src[Y / s, X / s] (integer division; F.interpolate(src, scale_factor=s)).
+ *   mode S360_UP_BILINEAR: F.interpolate(..., mode="bilinear", align_corners=True) with the source coordinate exact in 64-bit
+ *   integers: t = Y (h - 1), y0 = t / (H - 1), upper weight (t % (H - 1)) / (H - 1), upper neighbour min(y0 + 1, h - 1); H == 1: y0 = 0,
+ *   weight 0; the same along x.  reciprocal != 0 samples 1 / src (:650, coarse_disps = 1 / coarse_depths, never stored).
+ * s360_upsample_backward: the adjoint, gathered: g_src[y, x] = sum over the fine (Y, X) whose taps include (y, x), in ascending
+ *   (Y, X), of their weights times g_dst[Y, X] — the forward's own index rule read the other way, at most about 2s x 2s terms —
+ *   times -1 / src^2 if reciprocal.  src is read only then and may be NULL otherwise.
+ * s360_depth_tail_forward (:694-719 and encoder_costvolume.py:228-241, :420): fullres_disps[n, 1, H, W] and
+ *   delta_density[n, 2 gpp, H, W] (disparity deltas, then density logits) in the reference's (v b) order, n = v b; lo[n] = 1 / far,
+ *   hi[n] = 1 / near as the caller computed them in float32.  Per pixel and surface k < gpp:
+ *     fine = clamp(fullres + delta[k], lo, hi) of the unrounded sum,  depth = 1 / fine;
+ *     p = sigmoid(delta[gpp + k]),  opacity = (1 - (1 - p)^exponent + p^(1 / exponent)) / (2 gpp),  density = p.
+ *   depths_out, opacities_out, densities_out (may be NULL): [b, v, H W, 1, gpp], the layout the adapter and the raw render path
+ *   consume: the (v b) -> (b v) transposition and the channel-last move happen in the store.
+ * s360_depth_tail_backward: from the same inputs alone and g_depths, g_opacities, g_densities [b, v, H W, 1, gpp] (each may be NULL:
+ *   zero), writes g_delta_density[n, 2 gpp, H, W]: its disparity half is -g_depth / fine^2 where lo <= sum <= hi and 0 elsewhere,
+ *   with sum = float32(fullres + delta[k]) and the bounds included: torch's clamp backward decides on that same float32 sum, so
+ *   the two agree on every element; its density half is g_opacity d opacity / d x + g_density p (1 - p) with
+ *     d opacity / d x = (e (1 - p)^e p + (1 / e) p^(1 / e) (1 - p)) / (2 gpp),
+ *   formed from log p and log(1 - p): finite for every finite logit, where the float32 statement's autograd gives NaN once the
+ *   sigmoid rounds to 0 or 1.  g_fullres_disps[n, 1, H, W] is the sum of the disparity half over k = 0 .. gpp - 1 in that order.
+ *   exponent is a float32, as torch takes a Python scalar for a float32 tensor; the kernels widen it to float64.
+ * s360_opacity_map_forward / _backward (encoder_costvolume.py:241 alone, on count probabilities): out = (1 - (1 - p)^e + p^(1 / e)) / 2,
+ *   g_pdf = g_out (e (1 - p)^(e - 1) + p^(1 / e - 1) / e) / 2: the derivative in p, infinite where the float64 statement's is.
+ */
+#define S360_UP_NEAREST 0
+#define S360_UP_BILINEAR 1
+int s360_upsample_forward(const float* src, float* dst, int32_t n, int32_t h, int32_t w, int32_t s, int32_t mode, int32_t reciprocal,
+                          void* stream);
+int s360_upsample_backward(const float* g_dst, const float* src, float* g_src, int32_t n, int32_t h, int32_t w, int32_t s, int32_t mode,
+                           int32_t reciprocal, void* stream);
+int s360_depth_tail_forward(const float* fullres_disps, const float* delta_density, const float* lo, const float* hi, float exponent,
+                            int32_t gpp, int32_t v, float* depths_out, float* opacities_out, float* densities_out, int32_t n, int32_t H,
+                            int32_t W, void* stream);
+int s360_depth_tail_backward(const float* g_depths, const float* g_opacities, const float* g_densities, const float* fullres_disps,
+                             const float* delta_density, const float* lo, const float* hi, float exponent, int32_t gpp, int32_t v,
+                             float* g_fullres_disps, float* g_delta_density, int32_t n, int32_t H, int32_t W, void* stream);
+int s360_opacity_map_forward(const float* pdf, float* out, size_t count, float exponent, void* stream);
+int s360_opacity_map_backward(const float* pdf, const float* g_out, float* g_pdf, size_t count, float exponent, void* stream);
+
+/*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an
  * un-synchronised wall clock, src/misc/benchmarker.py:15-33).  While enabled, every kernel group
  * is bracketed by HIP events recorded on the launch stream; s360_profile_collect() synchronises

@@ -4,8 +4,9 @@ library is loaded on first use (splatter360_amd._lib) and there is no CPU fallba
 
 def install(**opts):
     """Register the fused decoder in the unchanged reference's decoder registry (splatter360_amd.plugin.install).  Keywords
-    switch the other native seams on, each off by default: adapter, metrics, depth_loss, depth_metrics, psnr, cost_volume and
-    depth_head (the encoder's softmax depth head, splatter360_amd.depth_head)."""
+    switch the other native seams on, each off by default: adapter, metrics, depth_loss, depth_metrics, psnr, cost_volume,
+    depth_head (the encoder's softmax depth head, splatter360_amd.depth_head) and depth_tail (its two interpolations and
+    map_pdf_to_opacity, splatter360_amd.depth_tail, whose fine_depth_tail is the direct API for the rest of that stretch)."""
     from .plugin import install as _install
     return _install(**opts)
 

@@ -25,6 +25,10 @@ builds its correlation volume with the fused kernels of cost_volume.py and never
 install(depth_head=True) rebinds the name `F` (torch.nn.functional) of that same module to a proxy whose softmax(x, dim=1) returns
 a lazy handle, so that the predictor's softmax, expected depth and pdf maximum (:643-651) run as the one fused reduction of
 depth_head.py and the [v b, D, h, w] softmax is never stored; every other attribute of the proxy is torch.nn.functional's own.
+install(depth_tail=True) rebinds the same `F` to a proxy whose interpolate runs the upsampling kernels of depth_tail.py for the
+predictor's two calls (:652-658), and EncoderCostVolume.map_pdf_to_opacity (src/model/encoder/encoder_costvolume.py:228-241) to the
+opacity-map kernel; the two `F` proxies stack in either order.  The predictor's :694-719 have no seam; depth_tail.fine_depth_tail
+is the direct API for them.
 
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
@@ -487,21 +491,32 @@ class _SeamPatcher(importlib.abc.MetaPathFinder):
             sys.meta_path.remove(self)
         self.seam.patch(mod)
 
+    def _late(self) -> bool:
+        """Patch now if the module was imported behind this finder's back.  True if it was."""
+        seam = self.seam
+        mod = sys.modules.get(seam.module)
+        if self.busy or not seam.ready(mod):
+            return False
+        self.busy = True
+        try:
+            self._done(mod)
+        except Exception as ex:      # never let the failure surface from an unrelated import
+            import warnings
+            warnings.warn(f"splatter360_amd.install({seam.keyword}=True): patching {seam.module} failed ({ex!r}); the "
+                          "reference keeps its own functions.", RuntimeWarning)
+        finally:
+            self.busy = False
+        return True
+
     def find_spec(self, fullname, path, target=None):
         if self.busy:
             return None
         seam = self.seam
-        mod = sys.modules.get(seam.module)
-        if seam.ready(mod):                                       # imported behind this finder's back: patch late
-            self.busy = True
-            try:
-                self._done(mod)
-            except Exception as ex:      # never let the failure surface from an unrelated import
-                import warnings
-                warnings.warn(f"splatter360_amd.install({seam.keyword}=True): patching {seam.module} failed ({ex!r}); the "
-                              "reference keeps its own functions.", RuntimeWarning)
-            finally:
-                self.busy = False
+        if self._late():
+            # this finder has just left sys.meta_path, the list the import system is walking: the walk skips the entry after
+            # it, so the other pending seams are served here and not at some later import
+            for other in [f for f in sys.meta_path if isinstance(f, _SeamPatcher)]:
+                other._late()
             return None
         if fullname != seam.module:
             return None
@@ -612,7 +627,123 @@ def _native_functional(replaced):
     return _dh.FunctionalProxy(replaced)
 
 
-DEPTH_HEAD_SEAM = _Seam("depth_head", COST_VOLUME_MODULE, (DEPTH_HEAD_NAME,), (), {DEPTH_HEAD_NAME: _native_functional})
+class _LayerSeam(_Seam):
+    """A seam on a name that two options share (the predictor module's `F`): each option wraps whatever is bound in a proxy of
+    its own class, whose `.replaced` is what it wrapped, so the proxies stack in either order of installation.  patch() adds this
+    seam's layer unless the stack holds one already; restore() takes this seam's layer out of the stack wherever it sits."""
+
+    def __init__(self, keyword, module, name, wrapper, layer_type):
+        super().__init__(keyword, module, (name,), (), {name: wrapper})
+        self.layer_type = layer_type                              # () -> the proxy's class (imported on demand)
+
+    def _layers(self, mod):
+        cur = getattr(mod, self.names[0], None)
+        while getattr(cur, "replaced", None) is not None:
+            yield cur
+            cur = cur.replaced
+
+    def patch(self, mod) -> dict:
+        name = self.names[0]
+        if not any(type(layer) is self.layer_type() for layer in self._layers(mod)):
+            setattr(mod, name, self.wrappers[name](getattr(mod, name)))
+        return {name: getattr(mod, name)}
+
+    def restore(self) -> None:
+        mod = sys.modules.get(self.module)
+        if mod is None:
+            return
+        name, above = self.names[0], None
+        for layer in list(self._layers(mod)):
+            if type(layer) is self.layer_type():
+                if above is None:
+                    setattr(mod, name, layer.replaced)
+                else:
+                    above.replaced = layer.replaced
+            else:
+                above = layer
+
+
+def _depth_head_layer():
+    from . import depth_head as _dh
+    return _dh.FunctionalProxy
+
+
+DEPTH_HEAD_SEAM = _LayerSeam("depth_head", COST_VOLUME_MODULE, DEPTH_HEAD_NAME, _native_functional, _depth_head_layer)
+
+
+DEPTH_TAIL_MODULE = "src.model.encoder.encoder_costvolume"            # defines EncoderCostVolume (:228-241 map_pdf_to_opacity, used at :420)
+DEPTH_TAIL_CLASS = "EncoderCostVolume"
+DEPTH_TAIL_METHOD = "map_pdf_to_opacity"
+
+
+def _native_interpolate(replaced):
+    """The proxy for the predictor module's `F` whose interpolate runs depth_tail.upsample for the predictor's two calls
+    (:652-658: a float32 GPU [v b, 1, h, w] map, an integer scale_factor, nearest or bilinear with align_corners=True) and the
+    replaced interpolate for every other call; every other attribute is the replaced object's own."""
+    from . import depth_tail as _dt
+    return _dt.InterpolateProxy(replaced)
+
+
+def _depth_tail_layer():
+    from . import depth_tail as _dt
+    return _dt.InterpolateProxy
+
+
+def _native_map_pdf_to_opacity(replaced):
+    """EncoderCostVolume.map_pdf_to_opacity with the reference's signature: the exponent from self.cfg.opacity_mapping exactly as
+    the method computes it, then the opacity-map kernel for a float32 GPU pdf; the replaced method otherwise."""
+    from . import depth_tail as _dt
+
+    def map_pdf_to_opacity(self, pdf, global_step):
+        if _is_cuda_f32(pdf) and pdf.numel() > 0:
+            cfg = self.cfg.opacity_mapping
+            return _dt.map_pdf_to_opacity(pdf, _dt.opacity_exponent(cfg.initial, cfg.final, cfg.warm_up, global_step))
+        return replaced(self, pdf, global_step)
+
+    map_pdf_to_opacity.replaced = replaced
+    map_pdf_to_opacity.__doc__ = _dt.map_pdf_to_opacity.__doc__
+    return map_pdf_to_opacity
+
+
+class _MethodSeam(_Seam):
+    """A seam on a method: `names` are attributes of the class `cls_name` that `module` defines."""
+
+    def __init__(self, keyword, module, cls_name, names, wrappers):
+        super().__init__(keyword, module, names, (), wrappers)
+        self.cls_name = cls_name
+
+    def ready(self, mod) -> bool:
+        cls = getattr(mod, self.cls_name, None) if mod is not None else None
+        return cls is not None and all(hasattr(cls, n) for n in self.names)
+
+    def patch(self, mod) -> dict:
+        cls, out = getattr(mod, self.cls_name), {}
+        for name in self.names:
+            cur = cls.__dict__.get(name, getattr(cls, name))
+            out[name] = cur if getattr(cur, "replaced", None) is not None else self.wrappers[name](cur)
+            setattr(cls, name, out[name])
+        return out
+
+    def restore(self) -> None:
+        cls = getattr(sys.modules.get(self.module), self.cls_name, None)
+        for name in self.names if cls is not None else ():
+            cur = cls.__dict__.get(name)
+            if getattr(cur, "replaced", None) is not None:
+                setattr(cls, name, cur.replaced)
+
+
+DEPTH_TAIL_F_SEAM = _LayerSeam("depth_tail", COST_VOLUME_MODULE, DEPTH_HEAD_NAME, _native_interpolate, _depth_tail_layer)
+DEPTH_TAIL_METHOD_SEAM = _MethodSeam("depth_tail", DEPTH_TAIL_MODULE, DEPTH_TAIL_CLASS, (DEPTH_TAIL_METHOD,),
+                                     {DEPTH_TAIL_METHOD: _native_map_pdf_to_opacity})
+
+
+def install_depth_tail():
+    """The half of install(depth_tail=True): rebind the predictor module's `F` to the interpolate proxy and
+    EncoderCostVolume.map_pdf_to_opacity to the opacity-map wrapper, each now if its module is imported, else as soon as it is
+    (import hooks).  Returns (proxy or None, method or None).  The predictor's :694-719 have no seam (inline arithmetic that ends in
+    einops.repeat): depth_tail.fine_depth_tail is the direct API for them."""
+    f, m = DEPTH_TAIL_F_SEAM.install(), DEPTH_TAIL_METHOD_SEAM.install()
+    return (None if f is None else f[DEPTH_HEAD_NAME]), (None if m is None else m[DEPTH_TAIL_METHOD])
 
 
 def install_depth_head():
@@ -644,7 +775,7 @@ def install_psnr():
 
 
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
-            depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, depth_head: bool = False, **opts):
+            depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, depth_head: bool = False, depth_tail: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
@@ -660,6 +791,9 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     raw_correlation_in with the fused cost-volume kernels (install_cost_volume; off by default).
     depth_head=True: ALSO rebind that module's `F` so that its softmax, expected depth and pdf maximum run as the fused depth-head
     kernels (install_depth_head; off by default).
+    depth_tail=True: ALSO rebind that module's `F` so that its two F.interpolate calls run the upsampling kernels, and
+    EncoderCostVolume.map_pdf_to_opacity to the opacity-map kernel (install_depth_tail; off by default; composes with depth_head in
+    either order).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -680,6 +814,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
         install_cost_volume()
     if depth_head:
         install_depth_head()
+    if depth_tail:
+        install_depth_tail()
     if lazy:
         if REGISTRY_MODULE in sys.modules:
             return _patch(sys.modules[REGISTRY_MODULE], **opts)
@@ -691,11 +827,11 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
 
 def uninstall() -> None:
     """Put the reference's own decoder class, adapter, compute_ssim, compute_psnr, compute_depth_metrics_batched,
-    compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates and the predictor module's `F` (torch.nn.functional itself) back
-    (and drop pending import hooks)."""
+    compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates, EncoderCostVolume.map_pdf_to_opacity and the predictor module's
+    `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
     sys.meta_path[:] = [f for f in sys.meta_path
                         if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher, _DepthLossPatcher, _SeamPatcher))]
-    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM, DEPTH_HEAD_SEAM):
+    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM, DEPTH_HEAD_SEAM, DEPTH_TAIL_F_SEAM, DEPTH_TAIL_METHOD_SEAM):
         seam.restore()
     dmod = sys.modules.get(DEPTH_MODULE)
     if dmod is not None:
