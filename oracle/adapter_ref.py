@@ -39,10 +39,11 @@ def sh_mask(d_sh: int) -> Tensor:
     return m
 
 
-def erp_directions(h: int, w: int, device=None, dataset_name: str = "hm3d") -> Tensor:
-    """utils360.py: get_xy_coords :21-35, equi_2_spherical :37-104, spherical_2_cartesian :106-153, per dataset name."""
-    x = torch.linspace(0, w - 1, w, device=device)
-    y = torch.linspace(0, h - 1, h, device=device)
+def erp_directions(h: int, w: int, device=None, dataset_name: str = "hm3d", dtype=torch.float32) -> Tensor:
+    """utils360.py: get_xy_coords :21-35, equi_2_spherical :37-104, spherical_2_cartesian :106-153, per dataset name.
+    `dtype`: the pixel grid's and so the rays' precision (float32 = the reference's; float64 for a float64 reference run)."""
+    x = torch.linspace(0, w - 1, w, device=device, dtype=dtype)
+    y = torch.linspace(0, h - 1, h, device=device, dtype=dtype)
     y, x = torch.meshgrid(y, x, indexing="ij")
     if dataset_name in ("hm3d", "replica"):
         theta = (0.5 - (x + 0.5) / w) * 2 * math.pi
@@ -107,7 +108,7 @@ def adapter_tail_torch(extrinsics: Tensor, depths: Tensor, opacities: Tensor, ra
     cov = r @ s @ s.transpose(-1, -2) @ r.transpose(-1, -2)
     c2w = extrinsics[:, None, :3, :3]
     cov = c2w @ cov @ c2w.transpose(-1, -2)
-    dirs = erp_directions(h, w, depths.device, dataset_name).repeat_interleave(per_ray, 0)          # [Gv,3]
+    dirs = erp_directions(h, w, depths.device, dataset_name, depths.dtype).repeat_interleave(per_ray, 0)   # [Gv,3]
     dm = depths if differentiable_means else depths.detach()   # sphere_projection.py:14: the reference computes means under no_grad
     pts = dirs[None] * dm[..., None]
     means = torch.einsum("vij,vgj->vgi", extrinsics[:, :3, :3], pts) + extrinsics[:, None, :3, 3]
