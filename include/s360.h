@@ -734,6 +734,53 @@ int s360_opacity_map_forward(const float* pdf, float* out, size_t count, float e
 int s360_opacity_map_backward(const float* pdf, const float* g_out, float* g_pdf, size_t count, float exponent, void* stream);
 
 /*
+ * Equirectangular -> cube resampler (csrc/s360_equirec2cube.hip): the opposite direction of s360_cube2erp_forward.  Replaces
+ * Equirec2Cube.sample_equirec / run (src/geometry/util.py:71-96: numpy + scipy.ndimage.map_coordinates per channel on the host,
+ * called per frame at src/dataset/dataset_hm3d.py:67,200) and, through face_map_host and strides_host, the reorder + flip that
+ * makes image_cubes_supervise (dataset_hm3d.py:204-213).  Additive entries: the ABI version stays.  One launch per call on
+ * `stream`, no workspace, no memset, no atomics, no host synchronisation, every output element written.
+ *   erp[B, C, H, W] (float32, or uint8 when dtype == S360_E2C_UINT8) -> cube, the same element type.
+ *   coor[fw, 6 fw, 2] float32 (y, x): Equirec2Cube.coor_y / coor_x (util.py:59-69), six faces side by side in slot order F R B L U D.
+ *   mode S360_E2C_BILINEAR (map_coordinates order=1) or S360_E2C_NEAREST (order=0).
+ *   boundary S360_E2C_REFERENCE: the two pole rows of util.py:72-74 (row H = row H-1 rolled by W/2, row H+1 = row 0 rolled by W/2)
+ *     and scipy's mode='wrap', whose period is n - 1 over n = H + 2 rows and n = W columns:
+ *       s = n - 1;  c < 0: c += s (trunc(-c / s) + 1);  c > n - 1: c -= s trunc(c / s);
+ *       i0 = floor(c), upper weight c - i0, i1 = i0 + 1 and, if i1 > n - 1, i1 -= s (i1 / s);  nearest: floor(c + 0.5).
+ *   boundary S360_E2C_PERIODIC: x modulo W with taps floor(x) mod W and (floor(x) + 1) mod W; y held in [-1, H], row -1 = row 0
+ *     rolled by W/2 and row H = row H-1 rolled by W/2.  Both rules agree wherever no coordinate leaves [0, n - 1].
+ *   Arithmetic after the float32 coordinate is float64 in scipy's order, t = sum over (ky, kx) of (v wy) wx; rounded once to
+ *   float32, or floor(t + 0.5) clipped to 0..255 for uint8 (util.py's uint8 image contract).  Every tap index is clamped into the
+ *   plane after conversion: no value in coor makes a read leave erp.
+ *   scale[fw, 6 fw] float32 (may be NULL; float32 only, else S360_E_UNSUPPORTED): each texel's value is multiplied by it before the
+ *     rounding — Equirec2Cube.cosmaps with S360_E2C_NEAREST is run(equ_img, equ_dep)'s z-depth (util.py:22-24,93-96).
+ *   face_map_host (HOST, 6 x int32, may be NULL = identity): output face j shows slot face_map[j] & 7, flipped on both image axes
+ *     when bit 3 is set (the encoding of the stitch's face_map); {4|8, 2, 3, 0, 1, 5|8} gives the rendered order U B L F R D.
+ *   strides_host (HOST, 4 x int64, element units, may be NULL = dense [B, C, fw, 6 fw]): strides between batches, faces, channels
+ *     and rows of `cube`; {6 C fw fw, C fw fw, fw fw, fw} writes [B, 6, C, fw, fw] directly.
+ * s360_erp2cube_backward (float32): d_erp[B, C, H, W] from d_cube (face map and strides as in the forward).
+ *   plan_offsets[H W + 1], plan_entries[plan_offsets[H W]] (device, int32): the inverse of coor for this boundary and mode — ERP
+ *   texel e = row W + col is read by plan_entries[plan_offsets[e] .. plan_offsets[e + 1]) = cube_texel * 4 + tap, sorted, with
+ *   cube_texel the index into the [fw, 6 fw] slot plane, tap = 2 ky + kx (0 for nearest) and pole-row taps already folded onto
+ *   their real texel; weight-0 taps are listed.  Each weight is recomputed from coor with the forward's expressions; a texel's
+ *   terms are summed in float64 in plan order and rounded once: bit-identical from call to call.  A texel nobody reads gets 0.
+ * Null required pointers, non-positive sizes, equ_w < 2, an unknown mode / boundary / dtype, a face code outside 0..5 (| 8), a
+ * negative stride, H W + 1 or 24 fw fw beyond int32, or more than 4 x 65535 planes in the backward: S360_E_BADARG.
+ */
+#define S360_E2C_BILINEAR 0
+#define S360_E2C_NEAREST 1
+#define S360_E2C_REFERENCE 0
+#define S360_E2C_PERIODIC 1
+#define S360_E2C_FLOAT32 0
+#define S360_E2C_UINT8 1
+int s360_erp2cube_forward(const void* erp, const float* coor, const float* scale, void* cube, int32_t batch, int32_t channels,
+                          int32_t equ_h, int32_t equ_w, int32_t face_w, int32_t mode, int32_t boundary, int32_t dtype,
+                          const int32_t* face_map_host, const int64_t* strides_host, void* stream);
+int s360_erp2cube_backward(const float* d_cube, const float* coor, const float* scale, const int32_t* plan_offsets,
+                           const int32_t* plan_entries, float* d_erp, int32_t batch, int32_t channels, int32_t equ_h, int32_t equ_w,
+                           int32_t face_w, int32_t mode, int32_t boundary, const int32_t* face_map_host, const int64_t* strides_host,
+                           void* stream);
+
+/*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an
  * un-synchronised wall clock, src/misc/benchmarker.py:15-33).  While enabled, every kernel group
  * is bracketed by HIP events recorded on the launch stream; s360_profile_collect() synchronises

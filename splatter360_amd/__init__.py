@@ -14,3 +14,12 @@ def install(**opts):
 def uninstall():
     from .plugin import uninstall as _uninstall
     return _uninstall()
+
+
+def __getattr__(name):
+    """splatter360_amd.Equirec2Cube: the ERP -> cube resampler (splatter360_amd.equirec2cube), imported on first use so that
+    importing the package stays light.  It has no install() seam: the reference calls it in data-loader workers on numpy arrays."""
+    if name == "Equirec2Cube":
+        from .equirec2cube import Equirec2Cube
+        return Equirec2Cube
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
