@@ -8,6 +8,7 @@ single bytes 32 B each are real write amplification, not counter error)."""
 import collections, csv, json, sys
 FETCH_CORRECTION = 2.0
 SLOT = {"k_preprocess<": "preprocess", "k_render<": "render", "k_preprocess_bwd<": "preprocess_bwd", "k_sh_bwd<": "sh_bwd",
+        "k_gaussians_bwd_sh<": "preprocess_bwd",   # the fused kernel runs under the geometry backward's profile slot
         "k_sh_eval": "sh_eval", "k_render_bwd_em<": "render_bwd", "k_emit<": "emit", "k_gather_slots": "gather_slots",
         "k_cube2erp_fwd": "cube2erp", "k_sort_stage1": "sort_tiles"}
 

@@ -13,6 +13,8 @@
 //   k_sh_bwd           streaming SH backward for views sharing one camera centre (and for the N gathered
 //                      factors of the multi-GPU exchange): dL/dSH = Y (x) dRGB (the view-direction term of dL/dmean comes
 //                      from the forward's sh_jac inside k_preprocess_bwd)
+//   k_gaussians_bwd_sh the two above in one pass, for the local step with one camera centre (s360_backward with dL/dSH wanted):
+//                      k_preprocess_bwd's per-Gaussian body, then k_sh_bwd's one-group product from registers
 // No float atomics anywhere: gradients are bit-reproducible run to run.
 #include "s360_device.h"
 #include "s360_prof.h"
@@ -141,10 +143,330 @@ __global__ __launch_bounds__(S360_BLOCK) void k_gather_slots(uint32_t cap, const
     }
 }
 
-// SH_PASS = true : SH backward inside this kernel (slab through LDS; required when the views have different
-//                   camera centres).  SH_PASS = false (shared camera centre): the kernel only exports the
-//                   clamp-masked sum of dL/dRGB per Gaussian and k_sh_bwd streams the SH slabs afterwards —
-//                   two lean kernels instead of one register- and LDS-bound one.
+// Per-Gaussian body of the backward, shared by k_preprocess_bwd and k_gaussians_bwd_sh (one statement of the arithmetic: the
+// two kernels cannot drift): geometry chains over the visible views, the depth-value chain, the clamp-masked sum of dL/dRGB,
+// the view-direction term of dL/dmean and the stores of dL/dmean, dL/dcov, dL/dopacity (and d_means2D).  Returns what a
+// following SH product needs: the mean, the summed dL/dRGB and the first visible view (-1: visible nowhere).
+// SH_PASS = true : SH backward inside this body (the Gaussian's slab in LDS; required when the views have different
+//                   camera centres).  SH_PASS = false (shared camera centre): only the clamp-masked sum of dL/dRGB per
+//                   Gaussian leaves it — exported for k_sh_bwd, or turned into dL/dSH by the calling k_gaussians_bwd_sh.
+struct GaussBwd {
+    float mean[3];
+    float drgb[3];
+    int first_visible;
+};
+
+template <bool USE_SH, bool SH_PASS>
+__device__ __forceinline__ GaussBwd gaussian_bwd(
+    const KParams& kp, const S360View* __restrict__ views, const float* __restrict__ means, const float* __restrict__ cov6,
+    const uint8_t* __restrict__ vis_mask, const uint8_t* __restrict__ clamped, const float4* __restrict__ pairgrad,
+    float* __restrict__ d_means3D, float* __restrict__ d_means2D, float* __restrict__ d_cov6, float* __restrict__ d_opac,
+    float* __restrict__ d_colors, float4* __restrict__ drgb_out, int depth_mode, const float* __restrict__ sh_jac,
+    float* __restrict__ d_packed, int view_stamp, float* lds_sh, float* lds_drgb, int tid, int g) {
+    const bool want_sh = USE_SH && SH_PASS;  // runs even when d_shs == NULL: dL/dmean needs the view-direction term
+    const bool shared_cam = (kp.flags & S360_FLAG_SHARED_CAMPOS) != 0;
+    const int n_sh = (kp.deg + 1) * (kp.deg + 1);
+    const float mx0 = means[3 * g], my0 = means[3 * g + 1], mz0 = means[3 * g + 2];
+    float c60[6];
+    const bool cov9 = (kp.flags & S360_FLAG_COV9) != 0;
+    // SH element (k, c) inside this Gaussian's slab for either layout
+    const int sk = (kp.flags & S360_FLAG_SH_CHANNEL_MAJOR) ? 1 : 3;
+    const int sc_ = (kp.flags & S360_FLAG_SH_CHANNEL_MAJOR) ? kp.M : 1;
+    load_cov6(cov6, g, cov9, c60);
+    float dm0 = 0.f, dm1 = 0.f, dm2 = 0.f, dop = 0.f;
+    float dc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float drgb_sum[3] = {0.f, 0.f, 0.f};  // clamp-masked, summed over views
+    float dcol_sum[3] = {0.f, 0.f, 0.f};  // colors_precomp gradient
+    bool any_visible = false;
+    int first_visible = -1;
+    const uint32_t vis = vis_mask[g];  // bit v: visible in view v (one byte instead of V tiles_touched words)
+
+    for (int v = 0; v < kp.V; ++v) {
+        const size_t p = (size_t)v * kp.P + g;
+        float gx_ = 0.f, gy_ = 0.f;
+        float drgb_v[3] = {0.f, 0.f, 0.f};
+        // gradients w.r.t. the scaled cloud of this view; folded back with scale / scale^2 below
+        const float sc = views[v].scale, sc2 = sc * sc;
+        const float mx = mx0 * sc, my = my0 * sc, mz = mz0 * sc;
+        float c6[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) c6[k] = c60[k] * sc2;
+        float dmv0 = 0.f, dmv1 = 0.f, dmv2 = 0.f;
+        float dcv[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if ((vis >> v) & 1u) {
+            any_visible = true;
+            if (first_visible < 0) first_visible = v;
+            const float4 r0 = pairgrad[p * 3], r1 = pairgrad[p * 3 + 1], r2 = pairgrad[p * 3 + 2];
+            gx_ = r0.x; gy_ = r0.y;
+            const float gA = r0.z, gB = r0.w, gC = r1.x, gop = r1.y, gr = r1.z, gg = r1.w, gb = r2.x;
+            dop += gop;
+            const S360View& vw = views[v];
+            if (depth_mode >= 0) {
+                // fused depth channel: value = depth_value(z_u), z_u = camera z in UNSCALED units = R_row2 . mean + t_z / scale
+                // (render_depth_cuda, cuda_splatting.py:239-251), so dz_u / dmean (unscaled) = third row of the rotation
+                const float* Vm = vw.viewmatrix;
+                const float tzs = Vm[2] * mx + Vm[6] * my + Vm[10] * mz + Vm[14];
+                const float dzu = r2.y * depth_value_grad(tzs * (1.0f / sc), vw.near_plane, vw.far_plane, depth_mode);
+                dm0 += Vm[2] * dzu;
+                dm1 += Vm[6] * dzu;
+                dm2 += Vm[10] * dzu;
+            }
+            const float* V = vw.viewmatrix;
+            if (kp.flags & S360_FLAG_SPHERICAL) {
+                // native equirectangular splat: chain through geo_sph (oracle backward_one_sph)
+                GeoS gs;
+                geo_sph(V, kp.W, kp.H, mx, my, mz, c6, gs);
+                const float a = gs.a, b = gs.b, c = gs.c;
+                const float det = a * c - b * b;
+                const float d2inv = 1.0f / (det * det + 0.0000001f);
+                float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
+                if (d2inv != 0.f) {
+                    dL_da = d2inv * (-c * c * gA + b * c * gB + (det - a * c) * gC);
+                    dL_dc = d2inv * (-a * a * gC + a * b * gB + (det - a * c) * gA);
+                    dL_db = d2inv * (2.f * b * c * gA - (det + 2.f * b * b) * gB + 2.f * a * b * gC);
+                    const float *M0 = gs.M0, *M1 = gs.M1;
+                    dcv[0] += M0[0] * M0[0] * dL_da + M0[0] * M1[0] * dL_db + M1[0] * M1[0] * dL_dc;
+                    dcv[3] += M0[1] * M0[1] * dL_da + M0[1] * M1[1] * dL_db + M1[1] * M1[1] * dL_dc;
+                    dcv[5] += M0[2] * M0[2] * dL_da + M0[2] * M1[2] * dL_db + M1[2] * M1[2] * dL_dc;
+                    dcv[1] += 2.f * M0[0] * M0[1] * dL_da + (M0[0] * M1[1] + M0[1] * M1[0]) * dL_db + 2.f * M1[0] * M1[1] * dL_dc;
+                    dcv[2] += 2.f * M0[0] * M0[2] * dL_da + (M0[0] * M1[2] + M0[2] * M1[0]) * dL_db + 2.f * M1[0] * M1[2] * dL_dc;
+                    dcv[4] += 2.f * M0[1] * M0[2] * dL_da + (M0[1] * M1[2] + M0[2] * M1[1]) * dL_db + 2.f * M1[1] * M1[2] * dL_dc;
+                }
+                float dJ00 = 0.f, dJ02 = 0.f, dJ10 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const float dM0 = 2.f * dL_da * gs.v0[j] + dL_db * gs.v1[j];
+                    const float dM1 = 2.f * dL_dc * gs.v1[j] + dL_db * gs.v0[j];
+                    dJ00 += dM0 * V[j * 4 + 0];
+                    dJ02 += dM0 * V[j * 4 + 2];
+                    dJ10 += dM1 * V[j * 4 + 0];
+                    dJ11 += dM1 * V[j * 4 + 1];
+                    dJ12 += dM1 * V[j * 4 + 2];
+                }
+                const float t0 = gs.t0, t1 = gs.t1, t2 = gs.t2, rc = gs.rc, r2 = gs.r2;
+                const float c0 = -(float)kp.W / 6.283185307179586f, c1 = -(float)kp.H / 3.141592653589793f;
+                const float A = 1.0f / (rc * rc), Bq = 1.0f / (r2 * rc);
+                float dt0 = -(c0 * A) * dJ02 - (c1 * t1 * Bq) * dJ10;
+                float dt1 = -(c1 * Bq) * (t0 * dJ10 + t2 * dJ12);
+                float dt2 = (c0 * A) * dJ00 - (c1 * t1 * Bq) * dJ12;
+                const float dA = c0 * (dJ00 * t2 - dJ02 * t0);
+                const float dB = -(c1 * t1) * (dJ10 * t0 + dJ12 * t2);
+                const float dC = c1 * dJ11;
+                const float drc = dA * (-2.0f / (rc * rc * rc)) + dB * (-1.0f / (r2 * rc * rc)) + dC / r2;
+                const float dr2 = dB * (-1.0f / (r2 * r2 * rc)) + dC * (-rc / (r2 * r2));
+                dt0 += 2.0f * t0 * dr2;
+                dt1 += 2.0f * t1 * dr2;
+                dt2 += 2.0f * t2 * dr2;
+                if (gs.clamped) {
+                    dt0 += drc * (0.05f * t0 / gs.r);
+                    dt1 += drc * (0.05f * t1 / gs.r);
+                    dt2 += drc * (0.05f * t2 / gs.r);
+                } else {
+                    dt0 += drc * (t0 / gs.rho);
+                    dt2 += drc * (t2 / gs.rho);
+                }
+                const float iu = c0 / gs.rho2, iv = c1 / (r2 * gs.rho);   // centre: (u, v) with the TRUE rho; pixel units
+                dt0 += gx_ * (iu * t2) + gy_ * (-(iv * t0 * t1));
+                dt1 += gy_ * (c1 * gs.rho / r2);
+                dt2 += gx_ * (-(iu * t0)) + gy_ * (-(iv * t2 * t1));
+                dmv0 += V[0] * dt0 + V[1] * dt1 + V[2] * dt2;
+                dmv1 += V[4] * dt0 + V[5] * dt1 + V[6] * dt2;
+                dmv2 += V[8] * dt0 + V[9] * dt1 + V[10] * dt2;
+            } else {
+                Geo ge;
+                geo_compute(V, vw.tanfovx, vw.tanfovy, kp.W, kp.H, mx, my, mz, c6, ge);
+                const float a = ge.a, b = ge.b, c = ge.c;
+                const float det = a * c - b * b;
+                const float d2inv = 1.0f / (det * det + 0.0000001f);
+                float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
+                if (d2inv != 0.f) {
+                    dL_da = d2inv * (-c * c * gA + b * c * gB + (det - a * c) * gC);
+                    dL_dc = d2inv * (-a * a * gC + a * b * gB + (det - a * c) * gA);
+                    dL_db = d2inv * (2.f * b * c * gA - (det + 2.f * b * b) * gB + 2.f * a * b * gC);
+                    const float *M0 = ge.M0, *M1 = ge.M1;
+                    dcv[0] += M0[0] * M0[0] * dL_da + M0[0] * M1[0] * dL_db + M1[0] * M1[0] * dL_dc;
+                    dcv[3] += M0[1] * M0[1] * dL_da + M0[1] * M1[1] * dL_db + M1[1] * M1[1] * dL_dc;
+                    dcv[5] += M0[2] * M0[2] * dL_da + M0[2] * M1[2] * dL_db + M1[2] * M1[2] * dL_dc;
+                    dcv[1] += 2.f * M0[0] * M0[1] * dL_da + (M0[0] * M1[1] + M0[1] * M1[0]) * dL_db + 2.f * M1[0] * M1[1] * dL_dc;
+                    dcv[2] += 2.f * M0[0] * M0[2] * dL_da + (M0[0] * M1[2] + M0[2] * M1[0]) * dL_db + 2.f * M1[0] * M1[2] * dL_dc;
+                    dcv[4] += 2.f * M0[1] * M0[2] * dL_da + (M0[1] * M1[2] + M0[2] * M1[1]) * dL_db + 2.f * M1[1] * M1[2] * dL_dc;
+                }
+                float dM0[3], dM1[3];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    dM0[j] = 2.f * dL_da * ge.v0[j] + dL_db * ge.v1[j];
+                    dM1[j] = 2.f * dL_dc * ge.v1[j] + dL_db * ge.v0[j];
+                }
+                float dJ00 = 0.f, dJ02 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    dJ00 += dM0[j] * V[j * 4 + 0];
+                    dJ02 += dM0[j] * V[j * 4 + 2];
+                    dJ11 += dM1[j] * V[j * 4 + 1];
+                    dJ12 += dM1[j] * V[j * 4 + 2];
+                }
+                const float tz = 1.f / ge.tz, tz2 = tz * tz, tz3 = tz2 * tz;
+                const float dt0 = (ge.xin ? 1.f : 0.f) * (-ge.fx * tz2 * dJ02);
+                const float dt1 = (ge.yin ? 1.f : 0.f) * (-ge.fy * tz2 * dJ12);
+                const float dt2 = -ge.fx * tz2 * dJ00 - ge.fy * tz2 * dJ11 + (2.f * ge.fx * ge.txc) * tz3 * dJ02 +
+                                  (2.f * ge.fy * ge.tyc) * tz3 * dJ12;
+                dmv0 += V[0] * dt0 + V[1] * dt1 + V[2] * dt2;
+                dmv1 += V[4] * dt0 + V[5] * dt1 + V[6] * dt2;
+                dmv2 += V[8] * dt0 + V[9] * dt1 + V[10] * dt2;
+                // projection chain (NDC-scaled screen-space gradient)
+                const float m2x = gx_ * (0.5f * (float)kp.W), m2y = gy_ * (0.5f * (float)kp.H);
+                gx_ = m2x;
+                gy_ = m2y;
+                const float* Pm = vw.projmatrix;
+                const float mhx = Pm[0] * mx + Pm[4] * my + Pm[8] * mz + Pm[12];
+                const float mhy = Pm[1] * mx + Pm[5] * my + Pm[9] * mz + Pm[13];
+                const float mhw = Pm[3] * mx + Pm[7] * my + Pm[11] * mz + Pm[15];
+                const float mw = 1.f / (mhw + 0.0000001f);
+                const float mul1 = mhx * mw * mw, mul2 = mhy * mw * mw;
+                dmv0 += (Pm[0] * mw - Pm[3] * mul1) * m2x + (Pm[1] * mw - Pm[3] * mul2) * m2y;
+                dmv1 += (Pm[4] * mw - Pm[7] * mul1) * m2x + (Pm[5] * mw - Pm[7] * mul2) * m2y;
+                dmv2 += (Pm[8] * mw - Pm[11] * mul1) * m2x + (Pm[9] * mw - Pm[11] * mul2) * m2y;
+            }
+            if (USE_SH) {
+                const uint32_t cb = clamped[p];
+                drgb_v[0] = (cb & 1u) ? 0.f : gr;
+                drgb_v[1] = (cb & 2u) ? 0.f : gg;
+                drgb_v[2] = (cb & 4u) ? 0.f : gb;
+                drgb_sum[0] += drgb_v[0];
+                drgb_sum[1] += drgb_v[1];
+                drgb_sum[2] += drgb_v[2];
+            } else {
+                dcol_sum[0] += gr;
+                dcol_sum[1] += gg;
+                dcol_sum[2] += gb;
+            }
+        }
+        if (d_means2D) {
+            d_means2D[3 * p] = gx_;
+            d_means2D[3 * p + 1] = gy_;
+            d_means2D[3 * p + 2] = 0.f;
+        }
+        if (want_sh && !shared_cam) {
+            // view-direction term per view (campos differs); dRGB kept for the dSH pass
+            float* dr = lds_drgb + (tid * kp.V + v) * 3;
+            dr[0] = drgb_v[0]; dr[1] = drgb_v[1]; dr[2] = drgb_v[2];
+            if ((vis >> v) & 1u) {
+                const S360View& vw = views[v];
+                const float ddx = mx - vw.campos[0], ddy = my - vw.campos[1], ddz = mz - vw.campos[2];
+                const float inv = 1.f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
+                const float x = ddx * inv, y = ddy * inv, z = ddz * inv;
+                float bx[25], by[25], bz[25];
+                sh_basis_grad(kp.deg, x, y, z, bx, by, bz);
+                const float* sh = lds_sh + tid * kp.M * 3;
+                float q0 = 0.f, q1 = 0.f, q2 = 0.f;
+                for (int k = 0; k < n_sh; ++k) {
+                    const float s = sh[k * sk] * drgb_v[0] + sh[k * sk + sc_] * drgb_v[1] + sh[k * sk + 2 * sc_] * drgb_v[2];
+                    q0 += bx[k] * s; q1 += by[k] * s; q2 += bz[k] * s;
+                }
+                const float dot = x * q0 + y * q1 + z * q2;
+                dmv0 += (q0 - x * dot) * inv;
+                dmv1 += (q1 - y * dot) * inv;
+                dmv2 += (q2 - z * dot) * inv;
+            }
+        }
+        dm0 += sc * dmv0;
+        dm1 += sc * dmv1;
+        dm2 += sc * dmv2;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) dc[k] += sc2 * dcv[k];
+    }
+
+    if (want_sh) {
+        float* sh = lds_sh + tid * kp.M * 3;
+        if (shared_cam) {
+            if (any_visible) {
+                const S360View& vw = views[first_visible];
+                const float sc = vw.scale;
+                const float ddx = mx0 * sc - vw.campos[0], ddy = my0 * sc - vw.campos[1], ddz = mz0 * sc - vw.campos[2];
+                const float inv = 1.f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
+                const float x = ddx * inv, y = ddy * inv, z = ddz * inv;
+                float Y[25], bx[25], by[25], bz[25];
+                sh_basis(kp.deg, x, y, z, Y);
+                sh_basis_grad(kp.deg, x, y, z, bx, by, bz);
+                float q0 = 0.f, q1 = 0.f, q2 = 0.f;
+                for (int k = 0; k < n_sh; ++k) {
+                    const float s = sh[k * sk] * drgb_sum[0] + sh[k * sk + sc_] * drgb_sum[1] + sh[k * sk + 2 * sc_] * drgb_sum[2];
+                    q0 += bx[k] * s; q1 += by[k] * s; q2 += bz[k] * s;
+                    sh[k * sk] = Y[k] * drgb_sum[0];
+                    sh[k * sk + sc_] = Y[k] * drgb_sum[1];
+                    sh[k * sk + 2 * sc_] = Y[k] * drgb_sum[2];
+                }
+                for (int k = n_sh; k < kp.M; ++k) sh[k * sk] = sh[k * sk + sc_] = sh[k * sk + 2 * sc_] = 0.f;
+                const float dot = x * q0 + y * q1 + z * q2;
+                dm0 += sc * ((q0 - x * dot) * inv);
+                dm1 += sc * ((q1 - y * dot) * inv);
+                dm2 += sc * ((q2 - z * dot) * inv);
+            } else {
+                for (int k = 0; k < kp.M * 3; ++k) sh[k] = 0.f;
+            }
+        } else {
+            for (int k = 0; k < kp.M * 3; ++k) sh[k] = 0.f;
+            for (int v = 0; v < kp.V; ++v) {
+                if (!((vis >> v) & 1u)) continue;
+                const S360View& vw = views[v];
+                const float sc = vw.scale;
+                const float ddx = mx0 * sc - vw.campos[0], ddy = my0 * sc - vw.campos[1], ddz = mz0 * sc - vw.campos[2];
+                const float inv = 1.f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
+                float Y[25];
+                sh_basis(kp.deg, ddx * inv, ddy * inv, ddz * inv, Y);
+                const float* dr = lds_drgb + (tid * kp.V + v) * 3;
+                for (int k = 0; k < n_sh; ++k) {
+                    sh[k * sk] += Y[k] * dr[0];
+                    sh[k * sk + sc_] += Y[k] * dr[1];
+                    sh[k * sk + 2 * sc_] += Y[k] * dr[2];
+                }
+            }
+        }
+    }
+    if (USE_SH && !SH_PASS && sh_jac && any_visible) {
+        // view-direction term of dL/dmean from the forward's d(rgb)/d(mean) (k_sh_eval): no SH slab re-read
+        const float* J = sh_jac + 9 * (size_t)g;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            dm0 += drgb_sum[ch] * J[3 * ch];
+            dm1 += drgb_sum[ch] * J[3 * ch + 1];
+            dm2 += drgb_sum[ch] * J[3 * ch + 2];
+        }
+    }
+    if (USE_SH && !SH_PASS && drgb_out)
+        drgb_out[g] = make_float4(drgb_sum[0], drgb_sum[1], drgb_sum[2],
+                                  __int_as_float(view_stamp >= 0 && first_visible >= 0 ? view_stamp : first_visible));
+    if (d_packed) {
+        float* o = d_packed + 10 * (size_t)g;
+        o[0] = dm0; o[1] = dm1; o[2] = dm2;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) o[3 + k] = dc[k];
+        o[9] = dop;
+    } else {
+        d_means3D[3 * g] = dm0;
+        d_means3D[3 * g + 1] = dm1;
+        d_means3D[3 * g + 2] = dm2;
+        if (cov9) {
+            // adjoint of the upper-triangle gather: lower triangle receives no gradient
+            float* o = d_cov6 + 9 * (size_t)g;
+            o[0] = dc[0]; o[1] = dc[1]; o[2] = dc[2];
+            o[3] = 0.f;   o[4] = dc[3]; o[5] = dc[4];
+            o[6] = 0.f;   o[7] = 0.f;   o[8] = dc[5];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) d_cov6[6 * (size_t)g + k] = dc[k];
+        }
+        d_opac[g] = dop;
+    }
+    if (!USE_SH && d_colors) {
+        d_colors[3 * g] = dcol_sum[0];
+        d_colors[3 * g + 1] = dcol_sum[1];
+        d_colors[3 * g + 2] = dcol_sum[2];
+    }
+    return GaussBwd{{mx0, my0, mz0}, {drgb_sum[0], drgb_sum[1], drgb_sum[2]}, first_visible};
+}
+
+// 1 thread per Gaussian.  SH_PASS: see gaussian_bwd.
 template <bool USE_SH, bool SH_PASS>
 __global__ __launch_bounds__(S360_BLOCK) void k_preprocess_bwd(
     KParams kp, const S360View* __restrict__ views, const float* __restrict__ means, const float* __restrict__ cov6,
@@ -165,7 +487,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_preprocess_bwd(
     const int nb = min(S360_BLOCK, P - g0);
     const int nfl = nb * kp.M * 3;
     float* lds_drgb = lds_sh + S360_BLOCK * kp.M * 3;  // per-thread, per-view dRGB (non-shared campos)
-    const bool want_sh = USE_SH && SH_PASS;  // runs even when d_shs == NULL: dL/dmean needs the view-direction term
+    const bool want_sh = USE_SH && SH_PASS;
 
     if (want_sh) {
         const float* src = shs + (size_t)g0 * kp.M * 3;
@@ -181,307 +503,9 @@ __global__ __launch_bounds__(S360_BLOCK) void k_preprocess_bwd(
         __syncthreads();
     }
 
-    const bool shared_cam = (kp.flags & S360_FLAG_SHARED_CAMPOS) != 0;
-    const int n_sh = (kp.deg + 1) * (kp.deg + 1);
-    if (g < P) {
-        const float mx0 = means[3 * g], my0 = means[3 * g + 1], mz0 = means[3 * g + 2];
-        float c60[6];
-        const bool cov9 = (kp.flags & S360_FLAG_COV9) != 0;
-        // SH element (k, c) inside this Gaussian's slab for either layout
-        const int sk = (kp.flags & S360_FLAG_SH_CHANNEL_MAJOR) ? 1 : 3;
-        const int sc_ = (kp.flags & S360_FLAG_SH_CHANNEL_MAJOR) ? kp.M : 1;
-        load_cov6(cov6, g, cov9, c60);
-        float dm0 = 0.f, dm1 = 0.f, dm2 = 0.f, dop = 0.f;
-        float dc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        float drgb_sum[3] = {0.f, 0.f, 0.f};  // clamp-masked, summed over views
-        float dcol_sum[3] = {0.f, 0.f, 0.f};  // colors_precomp gradient
-        bool any_visible = false;
-        int first_visible = -1;
-        const uint32_t vis = vis_mask[g];  // bit v: visible in view v (one byte instead of V tiles_touched words)
-
-        for (int v = 0; v < kp.V; ++v) {
-            const size_t p = (size_t)v * kp.P + g;
-            float gx_ = 0.f, gy_ = 0.f;
-            float drgb_v[3] = {0.f, 0.f, 0.f};
-            // gradients w.r.t. the scaled cloud of this view; folded back with scale / scale^2 below
-            const float sc = views[v].scale, sc2 = sc * sc;
-            const float mx = mx0 * sc, my = my0 * sc, mz = mz0 * sc;
-            float c6[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) c6[k] = c60[k] * sc2;
-            float dmv0 = 0.f, dmv1 = 0.f, dmv2 = 0.f;
-            float dcv[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if ((vis >> v) & 1u) {
-                any_visible = true;
-                if (first_visible < 0) first_visible = v;
-                const float4 r0 = pairgrad[p * 3], r1 = pairgrad[p * 3 + 1], r2 = pairgrad[p * 3 + 2];
-                gx_ = r0.x; gy_ = r0.y;
-                const float gA = r0.z, gB = r0.w, gC = r1.x, gop = r1.y, gr = r1.z, gg = r1.w, gb = r2.x;
-                dop += gop;
-                const S360View& vw = views[v];
-                if (depth_mode >= 0) {
-                    // fused depth channel: value = depth_value(z_u), z_u = camera z in UNSCALED units = R_row2 . mean + t_z / scale
-                    // (render_depth_cuda, cuda_splatting.py:239-251), so dz_u / dmean (unscaled) = third row of the rotation
-                    const float* Vm = vw.viewmatrix;
-                    const float tzs = Vm[2] * mx + Vm[6] * my + Vm[10] * mz + Vm[14];
-                    const float dzu = r2.y * depth_value_grad(tzs * (1.0f / sc), vw.near_plane, vw.far_plane, depth_mode);
-                    dm0 += Vm[2] * dzu;
-                    dm1 += Vm[6] * dzu;
-                    dm2 += Vm[10] * dzu;
-                }
-                const float* V = vw.viewmatrix;
-                if (kp.flags & S360_FLAG_SPHERICAL) {
-                    // native equirectangular splat: chain through geo_sph (oracle backward_one_sph)
-                    GeoS gs;
-                    geo_sph(V, kp.W, kp.H, mx, my, mz, c6, gs);
-                    const float a = gs.a, b = gs.b, c = gs.c;
-                    const float det = a * c - b * b;
-                    const float d2inv = 1.0f / (det * det + 0.0000001f);
-                    float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
-                    if (d2inv != 0.f) {
-                        dL_da = d2inv * (-c * c * gA + b * c * gB + (det - a * c) * gC);
-                        dL_dc = d2inv * (-a * a * gC + a * b * gB + (det - a * c) * gA);
-                        dL_db = d2inv * (2.f * b * c * gA - (det + 2.f * b * b) * gB + 2.f * a * b * gC);
-                        const float *M0 = gs.M0, *M1 = gs.M1;
-                        dcv[0] += M0[0] * M0[0] * dL_da + M0[0] * M1[0] * dL_db + M1[0] * M1[0] * dL_dc;
-                        dcv[3] += M0[1] * M0[1] * dL_da + M0[1] * M1[1] * dL_db + M1[1] * M1[1] * dL_dc;
-                        dcv[5] += M0[2] * M0[2] * dL_da + M0[2] * M1[2] * dL_db + M1[2] * M1[2] * dL_dc;
-                        dcv[1] += 2.f * M0[0] * M0[1] * dL_da + (M0[0] * M1[1] + M0[1] * M1[0]) * dL_db + 2.f * M1[0] * M1[1] * dL_dc;
-                        dcv[2] += 2.f * M0[0] * M0[2] * dL_da + (M0[0] * M1[2] + M0[2] * M1[0]) * dL_db + 2.f * M1[0] * M1[2] * dL_dc;
-                        dcv[4] += 2.f * M0[1] * M0[2] * dL_da + (M0[1] * M1[2] + M0[2] * M1[1]) * dL_db + 2.f * M1[1] * M1[2] * dL_dc;
-                    }
-                    float dJ00 = 0.f, dJ02 = 0.f, dJ10 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        const float dM0 = 2.f * dL_da * gs.v0[j] + dL_db * gs.v1[j];
-                        const float dM1 = 2.f * dL_dc * gs.v1[j] + dL_db * gs.v0[j];
-                        dJ00 += dM0 * V[j * 4 + 0];
-                        dJ02 += dM0 * V[j * 4 + 2];
-                        dJ10 += dM1 * V[j * 4 + 0];
-                        dJ11 += dM1 * V[j * 4 + 1];
-                        dJ12 += dM1 * V[j * 4 + 2];
-                    }
-                    const float t0 = gs.t0, t1 = gs.t1, t2 = gs.t2, rc = gs.rc, r2 = gs.r2;
-                    const float c0 = -(float)kp.W / 6.283185307179586f, c1 = -(float)kp.H / 3.141592653589793f;
-                    const float A = 1.0f / (rc * rc), Bq = 1.0f / (r2 * rc);
-                    float dt0 = -(c0 * A) * dJ02 - (c1 * t1 * Bq) * dJ10;
-                    float dt1 = -(c1 * Bq) * (t0 * dJ10 + t2 * dJ12);
-                    float dt2 = (c0 * A) * dJ00 - (c1 * t1 * Bq) * dJ12;
-                    const float dA = c0 * (dJ00 * t2 - dJ02 * t0);
-                    const float dB = -(c1 * t1) * (dJ10 * t0 + dJ12 * t2);
-                    const float dC = c1 * dJ11;
-                    const float drc = dA * (-2.0f / (rc * rc * rc)) + dB * (-1.0f / (r2 * rc * rc)) + dC / r2;
-                    const float dr2 = dB * (-1.0f / (r2 * r2 * rc)) + dC * (-rc / (r2 * r2));
-                    dt0 += 2.0f * t0 * dr2;
-                    dt1 += 2.0f * t1 * dr2;
-                    dt2 += 2.0f * t2 * dr2;
-                    if (gs.clamped) {
-                        dt0 += drc * (0.05f * t0 / gs.r);
-                        dt1 += drc * (0.05f * t1 / gs.r);
-                        dt2 += drc * (0.05f * t2 / gs.r);
-                    } else {
-                        dt0 += drc * (t0 / gs.rho);
-                        dt2 += drc * (t2 / gs.rho);
-                    }
-                    const float iu = c0 / gs.rho2, iv = c1 / (r2 * gs.rho);   // centre: (u, v) with the TRUE rho; pixel units
-                    dt0 += gx_ * (iu * t2) + gy_ * (-(iv * t0 * t1));
-                    dt1 += gy_ * (c1 * gs.rho / r2);
-                    dt2 += gx_ * (-(iu * t0)) + gy_ * (-(iv * t2 * t1));
-                    dmv0 += V[0] * dt0 + V[1] * dt1 + V[2] * dt2;
-                    dmv1 += V[4] * dt0 + V[5] * dt1 + V[6] * dt2;
-                    dmv2 += V[8] * dt0 + V[9] * dt1 + V[10] * dt2;
-                } else {
-                    Geo ge;
-                    geo_compute(V, vw.tanfovx, vw.tanfovy, kp.W, kp.H, mx, my, mz, c6, ge);
-                    const float a = ge.a, b = ge.b, c = ge.c;
-                    const float det = a * c - b * b;
-                    const float d2inv = 1.0f / (det * det + 0.0000001f);
-                    float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
-                    if (d2inv != 0.f) {
-                        dL_da = d2inv * (-c * c * gA + b * c * gB + (det - a * c) * gC);
-                        dL_dc = d2inv * (-a * a * gC + a * b * gB + (det - a * c) * gA);
-                        dL_db = d2inv * (2.f * b * c * gA - (det + 2.f * b * b) * gB + 2.f * a * b * gC);
-                        const float *M0 = ge.M0, *M1 = ge.M1;
-                        dcv[0] += M0[0] * M0[0] * dL_da + M0[0] * M1[0] * dL_db + M1[0] * M1[0] * dL_dc;
-                        dcv[3] += M0[1] * M0[1] * dL_da + M0[1] * M1[1] * dL_db + M1[1] * M1[1] * dL_dc;
-                        dcv[5] += M0[2] * M0[2] * dL_da + M0[2] * M1[2] * dL_db + M1[2] * M1[2] * dL_dc;
-                        dcv[1] += 2.f * M0[0] * M0[1] * dL_da + (M0[0] * M1[1] + M0[1] * M1[0]) * dL_db + 2.f * M1[0] * M1[1] * dL_dc;
-                        dcv[2] += 2.f * M0[0] * M0[2] * dL_da + (M0[0] * M1[2] + M0[2] * M1[0]) * dL_db + 2.f * M1[0] * M1[2] * dL_dc;
-                        dcv[4] += 2.f * M0[1] * M0[2] * dL_da + (M0[1] * M1[2] + M0[2] * M1[1]) * dL_db + 2.f * M1[1] * M1[2] * dL_dc;
-                    }
-                    float dM0[3], dM1[3];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        dM0[j] = 2.f * dL_da * ge.v0[j] + dL_db * ge.v1[j];
-                        dM1[j] = 2.f * dL_dc * ge.v1[j] + dL_db * ge.v0[j];
-                    }
-                    float dJ00 = 0.f, dJ02 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        dJ00 += dM0[j] * V[j * 4 + 0];
-                        dJ02 += dM0[j] * V[j * 4 + 2];
-                        dJ11 += dM1[j] * V[j * 4 + 1];
-                        dJ12 += dM1[j] * V[j * 4 + 2];
-                    }
-                    const float tz = 1.f / ge.tz, tz2 = tz * tz, tz3 = tz2 * tz;
-                    const float dt0 = (ge.xin ? 1.f : 0.f) * (-ge.fx * tz2 * dJ02);
-                    const float dt1 = (ge.yin ? 1.f : 0.f) * (-ge.fy * tz2 * dJ12);
-                    const float dt2 = -ge.fx * tz2 * dJ00 - ge.fy * tz2 * dJ11 + (2.f * ge.fx * ge.txc) * tz3 * dJ02 +
-                                      (2.f * ge.fy * ge.tyc) * tz3 * dJ12;
-                    dmv0 += V[0] * dt0 + V[1] * dt1 + V[2] * dt2;
-                    dmv1 += V[4] * dt0 + V[5] * dt1 + V[6] * dt2;
-                    dmv2 += V[8] * dt0 + V[9] * dt1 + V[10] * dt2;
-                    // projection chain (NDC-scaled screen-space gradient)
-                    const float m2x = gx_ * (0.5f * (float)kp.W), m2y = gy_ * (0.5f * (float)kp.H);
-                    gx_ = m2x;
-                    gy_ = m2y;
-                    const float* Pm = vw.projmatrix;
-                    const float mhx = Pm[0] * mx + Pm[4] * my + Pm[8] * mz + Pm[12];
-                    const float mhy = Pm[1] * mx + Pm[5] * my + Pm[9] * mz + Pm[13];
-                    const float mhw = Pm[3] * mx + Pm[7] * my + Pm[11] * mz + Pm[15];
-                    const float mw = 1.f / (mhw + 0.0000001f);
-                    const float mul1 = mhx * mw * mw, mul2 = mhy * mw * mw;
-                    dmv0 += (Pm[0] * mw - Pm[3] * mul1) * m2x + (Pm[1] * mw - Pm[3] * mul2) * m2y;
-                    dmv1 += (Pm[4] * mw - Pm[7] * mul1) * m2x + (Pm[5] * mw - Pm[7] * mul2) * m2y;
-                    dmv2 += (Pm[8] * mw - Pm[11] * mul1) * m2x + (Pm[9] * mw - Pm[11] * mul2) * m2y;
-                }
-                if (USE_SH) {
-                    const uint32_t cb = clamped[p];
-                    drgb_v[0] = (cb & 1u) ? 0.f : gr;
-                    drgb_v[1] = (cb & 2u) ? 0.f : gg;
-                    drgb_v[2] = (cb & 4u) ? 0.f : gb;
-                    drgb_sum[0] += drgb_v[0];
-                    drgb_sum[1] += drgb_v[1];
-                    drgb_sum[2] += drgb_v[2];
-                } else {
-                    dcol_sum[0] += gr;
-                    dcol_sum[1] += gg;
-                    dcol_sum[2] += gb;
-                }
-            }
-            if (d_means2D) {
-                d_means2D[3 * p] = gx_;
-                d_means2D[3 * p + 1] = gy_;
-                d_means2D[3 * p + 2] = 0.f;
-            }
-            if (want_sh && !shared_cam) {
-                // view-direction term per view (campos differs); dRGB kept for the dSH pass
-                float* dr = lds_drgb + (tid * kp.V + v) * 3;
-                dr[0] = drgb_v[0]; dr[1] = drgb_v[1]; dr[2] = drgb_v[2];
-                if ((vis >> v) & 1u) {
-                    const S360View& vw = views[v];
-                    const float ddx = mx - vw.campos[0], ddy = my - vw.campos[1], ddz = mz - vw.campos[2];
-                    const float inv = 1.f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
-                    const float x = ddx * inv, y = ddy * inv, z = ddz * inv;
-                    float bx[25], by[25], bz[25];
-                    sh_basis_grad(kp.deg, x, y, z, bx, by, bz);
-                    const float* sh = lds_sh + tid * kp.M * 3;
-                    float q0 = 0.f, q1 = 0.f, q2 = 0.f;
-                    for (int k = 0; k < n_sh; ++k) {
-                        const float s = sh[k * sk] * drgb_v[0] + sh[k * sk + sc_] * drgb_v[1] + sh[k * sk + 2 * sc_] * drgb_v[2];
-                        q0 += bx[k] * s; q1 += by[k] * s; q2 += bz[k] * s;
-                    }
-                    const float dot = x * q0 + y * q1 + z * q2;
-                    dmv0 += (q0 - x * dot) * inv;
-                    dmv1 += (q1 - y * dot) * inv;
-                    dmv2 += (q2 - z * dot) * inv;
-                }
-            }
-            dm0 += sc * dmv0;
-            dm1 += sc * dmv1;
-            dm2 += sc * dmv2;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) dc[k] += sc2 * dcv[k];
-        }
-
-        if (want_sh) {
-            float* sh = lds_sh + tid * kp.M * 3;
-            if (shared_cam) {
-                if (any_visible) {
-                    const S360View& vw = views[first_visible];
-                    const float sc = vw.scale;
-                    const float ddx = mx0 * sc - vw.campos[0], ddy = my0 * sc - vw.campos[1], ddz = mz0 * sc - vw.campos[2];
-                    const float inv = 1.f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
-                    const float x = ddx * inv, y = ddy * inv, z = ddz * inv;
-                    float Y[25], bx[25], by[25], bz[25];
-                    sh_basis(kp.deg, x, y, z, Y);
-                    sh_basis_grad(kp.deg, x, y, z, bx, by, bz);
-                    float q0 = 0.f, q1 = 0.f, q2 = 0.f;
-                    for (int k = 0; k < n_sh; ++k) {
-                        const float s = sh[k * sk] * drgb_sum[0] + sh[k * sk + sc_] * drgb_sum[1] + sh[k * sk + 2 * sc_] * drgb_sum[2];
-                        q0 += bx[k] * s; q1 += by[k] * s; q2 += bz[k] * s;
-                        sh[k * sk] = Y[k] * drgb_sum[0];
-                        sh[k * sk + sc_] = Y[k] * drgb_sum[1];
-                        sh[k * sk + 2 * sc_] = Y[k] * drgb_sum[2];
-                    }
-                    for (int k = n_sh; k < kp.M; ++k) sh[k * sk] = sh[k * sk + sc_] = sh[k * sk + 2 * sc_] = 0.f;
-                    const float dot = x * q0 + y * q1 + z * q2;
-                    dm0 += sc * ((q0 - x * dot) * inv);
-                    dm1 += sc * ((q1 - y * dot) * inv);
-                    dm2 += sc * ((q2 - z * dot) * inv);
-                } else {
-                    for (int k = 0; k < kp.M * 3; ++k) sh[k] = 0.f;
-                }
-            } else {
-                for (int k = 0; k < kp.M * 3; ++k) sh[k] = 0.f;
-                for (int v = 0; v < kp.V; ++v) {
-                    if (!((vis >> v) & 1u)) continue;
-                    const S360View& vw = views[v];
-                    const float sc = vw.scale;
-                    const float ddx = mx0 * sc - vw.campos[0], ddy = my0 * sc - vw.campos[1], ddz = mz0 * sc - vw.campos[2];
-                    const float inv = 1.f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
-                    float Y[25];
-                    sh_basis(kp.deg, ddx * inv, ddy * inv, ddz * inv, Y);
-                    const float* dr = lds_drgb + (tid * kp.V + v) * 3;
-                    for (int k = 0; k < n_sh; ++k) {
-                        sh[k * sk] += Y[k] * dr[0];
-                        sh[k * sk + sc_] += Y[k] * dr[1];
-                        sh[k * sk + 2 * sc_] += Y[k] * dr[2];
-                    }
-                }
-            }
-        }
-        if (USE_SH && !SH_PASS && sh_jac && any_visible) {
-            // view-direction term of dL/dmean from the forward's d(rgb)/d(mean) (k_sh_eval): no SH slab re-read
-            const float* J = sh_jac + 9 * (size_t)g;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                dm0 += drgb_sum[ch] * J[3 * ch];
-                dm1 += drgb_sum[ch] * J[3 * ch + 1];
-                dm2 += drgb_sum[ch] * J[3 * ch + 2];
-            }
-        }
-        if (USE_SH && !SH_PASS && drgb_out)
-            drgb_out[g] = make_float4(drgb_sum[0], drgb_sum[1], drgb_sum[2],
-                                      __int_as_float(view_stamp >= 0 && first_visible >= 0 ? view_stamp : first_visible));
-        if (d_packed) {
-            float* o = d_packed + 10 * (size_t)g;
-            o[0] = dm0; o[1] = dm1; o[2] = dm2;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) o[3 + k] = dc[k];
-            o[9] = dop;
-        } else {
-            d_means3D[3 * g] = dm0;
-            d_means3D[3 * g + 1] = dm1;
-            d_means3D[3 * g + 2] = dm2;
-            if (cov9) {
-                // adjoint of the upper-triangle gather: lower triangle receives no gradient
-                float* o = d_cov6 + 9 * (size_t)g;
-                o[0] = dc[0]; o[1] = dc[1]; o[2] = dc[2];
-                o[3] = 0.f;   o[4] = dc[3]; o[5] = dc[4];
-                o[6] = 0.f;   o[7] = 0.f;   o[8] = dc[5];
-            } else {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) d_cov6[6 * (size_t)g + k] = dc[k];
-            }
-            d_opac[g] = dop;
-        }
-        if (!USE_SH && d_colors) {
-            d_colors[3 * g] = dcol_sum[0];
-            d_colors[3 * g + 1] = dcol_sum[1];
-            d_colors[3 * g + 2] = dcol_sum[2];
-        }
-    }
+    if (g < P)
+        gaussian_bwd<USE_SH, SH_PASS>(kp, views, means, cov6, vis_mask, clamped, pairgrad, d_means3D, d_means2D, d_cov6, d_opac, d_colors,
+                                      drgb_out, depth_mode, sh_jac, d_packed, view_stamp, lds_sh, lds_drgb, tid, g);
     if (want_sh && d_shs) {
         __syncthreads();
         float* dst = d_shs + (size_t)g0 * kp.M * 3;
@@ -497,6 +521,37 @@ __global__ __launch_bounds__(S360_BLOCK) void k_preprocess_bwd(
     }
 }
 
+// A lane's first (or only) product into its LDS slab, one store per element: 0.0f + Y_k * dRGB_c — the addition turns a -0
+// product into +0, the value that accumulating into a zero-filled slab gave — and +0 for the coefficients beyond the degree.
+template <bool CH_MAJOR>
+__device__ __forceinline__ void sh_slab_set(float* mine, const float* Y, float dr, float dg, float db, int n_sh, int M) {
+    const int sk = CH_MAJOR ? 1 : 3, sc_ = CH_MAJOR ? M : 1;
+#pragma unroll
+    for (int k = 0; k < 25; ++k) {
+        if (k < n_sh) {
+            mine[k * sk] = 0.0f + Y[k] * dr;
+            mine[k * sk + sc_] = 0.0f + Y[k] * dg;
+            mine[k * sk + 2 * sc_] = 0.0f + Y[k] * db;
+        }
+    }
+    for (int k = n_sh; k < M; ++k) mine[k * sk] = mine[k * sk + sc_] = mine[k * sk + 2 * sc_] = 0.f;
+}
+
+// nfl floats of finished slabs, LDS -> their (contiguous) place in dL/dSH, by one wave.
+__device__ __forceinline__ void sh_slabs_store(const float* lds_o, float* __restrict__ dst, int nfl, int lane) {
+    if ((((uintptr_t)dst) & 15) == 0) {
+        const int n4 = nfl >> 2;
+        // non-temporal stores: the 315 MB of dL/dSH are consumed by the optimiser / the exchange, never by this library — kept
+        // out of L2 / Infinity Cache they no longer sit, dirty, in front of the next step's SH read (k_sh_eval3_jac measured
+        // 98 us right behind this kernel's plain stores, 72 us on its own)
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        for (int i = lane; i < n4; i += 64) __builtin_nontemporal_store(reinterpret_cast<const f4v*>(lds_o)[i], reinterpret_cast<f4v*>(dst) + i);
+        for (int i = (n4 << 2) + lane; i < nfl; i += 64) dst[i] = lds_o[i];
+    } else {
+        for (int i = lane; i < nfl; i += 64) dst[i] = lds_o[i];
+    }
+}
+
 // dL/dSH for views sharing one camera centre: a pure streaming WRITE kernel, ONE WAVE per workgroup so that the
 // compute / store phases of the (up to 8) waves on a CU overlap freely.  Per Gaussian a lane reads the summed dL/dRGB
 // (16 B) and its mean (12 B), evaluates the SH basis at the view direction and forms dL/dSH = Y_k * dRGB_c; the 64 output
@@ -504,7 +559,8 @@ __global__ __launch_bounds__(S360_BLOCK) void k_preprocess_bwd(
 // (lane-strided stores of partial lines cost ~2x here).  The SH coefficients themselves are NOT read: the view-direction
 // term of dL/dmean they used to be needed for comes from the forward's sh_jac (k_preprocess_bwd).
 // n_groups (view, summed dL/dRGB) pairs per Gaussian: 1 for a local backward; N when the factors of the rank-1 products
-// Y (x) dRGB of N ranks were all-gathered instead of all-reducing N full SH gradients (slab accumulated in LDS).
+// Y (x) dRGB of N ranks were all-gathered instead of all-reducing N full SH gradients (slab accumulated in LDS: the first
+// contributing group is stored, the later ones are added — 0 + a + b ... in group order, as into a zero-filled slab).
 template <bool CH_MAJOR>
 __global__ __launch_bounds__(64) void k_sh_bwd(KParams kp, const S360View* __restrict__ views, const float* __restrict__ means,
                                               const float4* __restrict__ drgb_in, int n_groups, float* __restrict__ d_shs) {
@@ -517,8 +573,8 @@ __global__ __launch_bounds__(64) void k_sh_bwd(KParams kp, const S360View* __res
     const int n_sh = (kp.deg + 1) * (kp.deg + 1);
     const int sk = CH_MAJOR ? 1 : 3, sc_ = CH_MAJOR ? kp.M : 1;
     if (g < kp.P) {
-        for (int k = 0; k < slab; ++k) mine[k] = 0.f;
         const float m0 = means[3 * g], m1 = means[3 * g + 1], m2 = means[3 * g + 2];
+        bool first = true;  // no group has contributed yet: the slab is not initialised (no zero-fill pass)
 #pragma unroll 1
         for (int j = 0; j < n_groups; ++j) {
             const float4 dr = drgb_in[(size_t)j * kp.P + g];
@@ -530,6 +586,11 @@ __global__ __launch_bounds__(64) void k_sh_bwd(KParams kp, const S360View* __res
             const float inv = 1.f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
             float Y[25];
             sh_basis(kp.deg, ddx * inv, ddy * inv, ddz * inv, Y);
+            if (first) {
+                sh_slab_set<CH_MAJOR>(mine, Y, dr.x, dr.y, dr.z, n_sh, kp.M);
+                first = false;
+                continue;
+            }
 #pragma unroll
             for (int k = 0; k < 25; ++k) {
                 if (k < n_sh) {
@@ -539,21 +600,63 @@ __global__ __launch_bounds__(64) void k_sh_bwd(KParams kp, const S360View* __res
                 }
             }
         }
+        if (first)
+            for (int k = 0; k < slab; ++k) mine[k] = 0.f;
     }
     __syncthreads();  // single wave: orders the LDS writes above before the cooperative read below
-    const int nb = min(64, kp.P - g0);
-    const int nfl = nb * slab;
-    float* dst = d_shs + (size_t)g0 * slab;
-    if ((((uintptr_t)dst) & 15) == 0) {
-        const int n4 = nfl >> 2;
-        // non-temporal stores: the 315 MB of dL/dSH are consumed by the optimiser / the exchange, never by this library — kept
-        // out of L2 / Infinity Cache they no longer sit, dirty, in front of the next step's SH read (k_sh_eval3_jac measured
-        // 98 us right behind this kernel's plain stores, 72 us on its own)
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        for (int i = lane; i < n4; i += 64) __builtin_nontemporal_store(reinterpret_cast<const f4v*>(lds_o)[i], reinterpret_cast<f4v*>(dst) + i);
-        for (int i = (n4 << 2) + lane; i < nfl; i += 64) dst[i] = lds_o[i];
-    } else {
-        for (int i = lane; i < nfl; i += 64) dst[i] = lds_o[i];
+    sh_slabs_store(lds_o, d_shs + (size_t)g0 * slab, min(64, kp.P - g0) * slab, lane);
+}
+
+// The whole per-Gaussian backward of a local step whose views share one camera centre, in ONE pass over the Gaussians:
+// gaussian_bwd<true, false> (what k_preprocess_bwd<true, false> runs) and then, in the same lane, k_sh_bwd's one-group product
+// dL/dSH = Y(dir) (x) sum dL/dRGB, from the mean, the sum and the first visible view still in registers — the 16-byte
+// (sum dL/dRGB, first view) record is neither written nor read back, the mean is read once, and one launch goes.  One wave per
+// workgroup, as k_sh_bwd.  PASSES = 2 (the default): 32 slabs staged at a time (9.6 KB of LDS at M = 25), so that 16 waves per
+// CU keep the geometry's loads in flight as k_preprocess_bwd's 16 do — the kernel has to stay within 128 VGPRs for that;
+// PASSES = 1: the wave's 64 slabs at once (19.2 KB: 8 waves per CU), 14 us slower on the headline step (DESIGN_HISTORY D r8).
+// Same bits as the two kernels.  d_packed is NULL at every launch (the packed form keeps k_preprocess_bwd) and is a run-time
+// argument all the same: with that branch of gaussian_bwd folded away at compile time this compiler's allocation of the very
+// same geometry comes out at 132 VGPRs (3 waves per SIMD), or spills 20 bytes at the 128-register bound.
+template <bool CH_MAJOR, int PASSES>
+__global__ __launch_bounds__(64, 2 * PASSES) void k_gaussians_bwd_sh(
+    KParams kp, const S360View* __restrict__ views, const float* __restrict__ means, const float* __restrict__ cov6,
+    const uint8_t* __restrict__ vis_mask, const uint8_t* __restrict__ clamped, const float4* __restrict__ pairgrad,
+    float* __restrict__ d_means3D, float* __restrict__ d_means2D, float* __restrict__ d_cov6, float* __restrict__ d_opac,
+    float* __restrict__ d_shs, int depth_mode, const float* __restrict__ sh_jac, float* __restrict__ d_packed) {
+    extern __shared__ __attribute__((aligned(16))) float lds_o[];  // [64 / PASSES][M*3]
+    constexpr int ROWS = 64 / PASSES;
+    const int lane = threadIdx.x;
+    const int g0 = blockIdx.x * 64;
+    const int g = g0 + lane;
+    const int slab = kp.M * 3;
+    const int n_sh = (kp.deg + 1) * (kp.deg + 1);
+    GaussBwd gb;
+    gb.first_visible = -1;
+    if (g < kp.P)
+        gb = gaussian_bwd<true, false>(kp, views, means, cov6, vis_mask, clamped, pairgrad, d_means3D, d_means2D, d_cov6, d_opac,
+                                       nullptr, nullptr, depth_mode, sh_jac, d_packed, -1, nullptr, nullptr, lane, g);
+    float Y[25];
+    if (gb.first_visible >= 0) {
+        const S360View& vw = views[gb.first_visible];
+        const float sc = vw.scale;
+        const float ddx = gb.mean[0] * sc - vw.campos[0], ddy = gb.mean[1] * sc - vw.campos[1], ddz = gb.mean[2] * sc - vw.campos[2];
+        const float inv = 1.f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
+        sh_basis(kp.deg, ddx * inv, ddy * inv, ddz * inv, Y);
+    }
+#pragma unroll
+    for (int h = 0; h < PASSES; ++h) {
+        const int r = lane - h * ROWS;  // this lane's row of the pass's slabs
+        if (r >= 0 && r < ROWS && g < kp.P) {
+            float* mine = lds_o + r * slab;
+            if (gb.first_visible >= 0)
+                sh_slab_set<CH_MAJOR>(mine, Y, gb.drgb[0], gb.drgb[1], gb.drgb[2], n_sh, kp.M);
+            else
+                for (int k = 0; k < slab; ++k) mine[k] = 0.f;
+        }
+        __syncthreads();  // single wave: orders the LDS writes above before the cooperative read below
+        const int gh = g0 + h * ROWS;
+        if (gh < kp.P) sh_slabs_store(lds_o, d_shs + (size_t)gh * slab, min(ROWS, kp.P - gh) * slab, lane);
+        if (h + 1 < PASSES) __syncthreads();  // the next pass overwrites the slabs
     }
 }
 
@@ -761,6 +864,14 @@ using namespace s360;
         }                                                                                            \
     } while (0)
 
+// Slab passes of k_gaussians_bwd_sh (1 or 2: see the kernel).  -DS360_FUSED_SH_PASSES=1 builds the other schedule of the same
+// sources for a measurement.
+#ifndef S360_FUSED_SH_PASSES
+#define S360_FUSED_SH_PASSES 2
+#endif
+constexpr int FUSED_SH_PASSES = S360_FUSED_SH_PASSES;
+static_assert(FUSED_SH_PASSES == 1 || FUSED_SH_PASSES == 2, "k_gaussians_bwd_sh stages 64 or 32 slabs at a time");
+
 static int launch_sh_bwd(const KParams& kp, const S360View* views, const float* means3D, const float4* drgb, int n_groups,
                          float* d_shs, hipStream_t st) {
     const int wblk = (kp.P + 63) / 64;
@@ -873,7 +984,8 @@ static int backward_composite(const BwdCtx& c, const S360View* views, const void
 }
 
 // Per-Gaussian part for Gaussians [g_begin, g_end): geometry chains of the V views (+ the SH pass unless the views share a
-// camera centre, where k_sh_bwd follows or the caller defers it).
+// camera centre: there k_gaussians_bwd_sh does both in one launch for the whole cloud of a local step, and otherwise k_sh_bwd
+// follows or the caller defers it).
 static int backward_gaussians(const BwdCtx& c, const S360View* views, const float* means3D, const float* cov6, const float* shs,
                               const void* workspace, bool with_depth, int depth_mode, int g_begin, int g_end, float* d_means3D,
                               float* d_means2D, float* d_cov6, float* d_opacities, float* d_shs, float* d_colors, float* d_rgb_sum,
@@ -894,6 +1006,17 @@ static int backward_gaussians(const BwdCtx& c, const S360View* views, const floa
         if (shared) {
             // dRGB/d(view direction) reaches dL/dmean here (from the forward's sh_jac), whether or not dL/dSH is wanted
             // (harmonics frozen: d_shs == NULL), as upstream does
+            if (d_shs && !d_rgb_sum && !d_packed && g_begin == 0 && g_end == kp.P && (size_t)64 * kp.M * 3 * 4 <= 64 * 1024) {
+                // the local step: geometry and dL/dSH in one pass (every other form keeps the two kernels below)
+                const size_t flds = (size_t)(64 / FUSED_SH_PASSES) * kp.M * 3 * 4;
+                const bool chm = (kp.flags & S360_FLAG_SH_CHANNEL_MAJOR) != 0;
+                ProfScope ps(PS_PREPROCESS_BWD, st);
+                hipLaunchKernelGGL((chm ? k_gaussians_bwd_sh<true, FUSED_SH_PASSES> : k_gaussians_bwd_sh<false, FUSED_SH_PASSES>),
+                                   dim3((kp.P + 63) / 64), dim3(64), flds, st, kp, views, means3D, cov6, vis_mask, clamped, c.pairgrad,
+                                   d_means3D, d_means2D, d_cov6, d_opacities, d_shs, dmode, (const float*)(ws + L.sh_jac), d_packed);
+                S360_CHECK_LAUNCH();
+                return S360_OK;
+            }
             {
                 ProfScope ps(PS_PREPROCESS_BWD, st);
                 hipLaunchKernelGGL((k_preprocess_bwd<true, false>), dim3(nblk), dim3(S360_BLOCK), 0, st, kp, views, means3D, cov6, shs,
