@@ -515,6 +515,54 @@ int s360_cube2erp_backward(const float* d_erp, const float* grid, const int32_t*
                            const int32_t* face_map_host, const int64_t* strides_host, void* stream);
 
 /*
+ * z-depth -> ray distance (csrc/s360_stitch.hip): replaces depth_to_distance_map_batch
+ * (/root/reference/src/geometry/z_depth_to_distance.py:4-34), sqrt(X^2 + Y^2 + d^2) with X = (u - cx) d / fx, Y = (v - cy) d / fy,
+ * computed as |d| s, s = sqrt(((u - cx) / fx)^2 + ((v - cy) / fy)^2 + 1), in float64 from the float32 inputs and rounded once.
+ * Additive entries: the ABI version stays.  One launch per call on `stream`, no workspace, no atomics, no host synchronisation.
+ *   depth[n, height, width] float32; fxfycxcy[n, 4] float32 (fx, fy, cx, cy in pixels), one row per map, read on the device (the
+ *   reference's [n, 4, h, w] broadcast, src/model/model_wrapper_erp.py:450-455, is never formed); distance[n, height, width].
+ *   convention S360_D2D_REFERENCE: u is the ROW index and v the column index, as the reference's "ij" meshgrid of
+ *     (arange(width), arange(height)) pairs them (:18-21); height == width is required, as it is for the reference to broadcast.
+ *   convention S360_D2D_PIXEL: u is the column (x with fx, cx), v the row (y with fy, cy); any height, width.
+ *   d = 0 gives 0, d < 0 gives |d| s, inf and NaN propagate.
+ * s360_depth_to_distance_backward: d_depth = d_distance sign(d) s in float64, rounded once; 0 at d = 0, where torch's autograd of
+ *   the reference's sqrt gives NaN.  The intrinsics take no gradient.
+ * Null pointers, sizes < 1, an unknown convention, height != width under S360_D2D_REFERENCE: S360_E_BADARG before any GPU work.
+ */
+#define S360_D2D_REFERENCE 0
+#define S360_D2D_PIXEL 1
+int s360_depth_to_distance_forward(const float* depth, const float* fxfycxcy, float* distance, int32_t n, int32_t height,
+                                   int32_t width, int32_t convention, void* stream);
+int s360_depth_to_distance_backward(const float* d_distance, const float* depth, const float* fxfycxcy, float* d_depth, int32_t n,
+                                    int32_t height, int32_t width, int32_t convention, void* stream);
+
+/*
+ * Depth faces -> ERP distance panorama in one launch: replaces change_order_batch, depth_to_distance_map_batch and Cube2Equirec as
+ * the evaluation step chains them (/root/reference/src/model/model_wrapper_erp.py:445-463, :147-158), without the flipped /
+ * reordered copy, the distance faces or the intrinsics broadcast, and without writing to the input.  It is s360_cube2erp_forward
+ * with one channel, n panoramas (gridDim.y) and each tap value replaced by float32(|d_tap| s): bit-identical to
+ * s360_depth_to_distance_forward followed by s360_cube2erp_forward.
+ *   depth_faces[n, 6, fw, fw] float32, face order / face_map_host as for s360_cube2erp_forward; fxfycxcy[n, 6, 4]; grid[eh, ew, 3];
+ *   erp[n, eh, ew].
+ *   convention S360_D2D_REFERENCE: converted in SLOT space, after the reorder, as the reference does — slot s uses row s of
+ *     fxfycxcy and the slot-space texel position (u = row), so a flipped face sees (fw - 1 - u) - cx where its own image has u - cx.
+ *   convention S360_D2D_PIXEL: each face converted in its own image — slot s uses row face_map[s] & 7 and the source texel position.
+ *   strides_host (HOST, 3 x int64, element units, may be NULL = dense): strides between panoramas, faces and rows of depth_faces.
+ * s360_cube2erp_distance_backward: d_depth_faces[n, 6, fw, fw], every element written, no atomics — per slot-space texel the
+ *   plan-ordered float32 sum of s360_cube2erp_backward (same plan_offsets / plan_entries), then one multiply by sign(d) s in
+ *   float64, rounded once.  strides_host must be NULL (S360_E_UNSUPPORTED otherwise).
+ * Null pointers, sizes < 1, n > 65535, n eh ew 8 or 6 fw fw + 1 beyond int32, a face-map source > 5, an unknown convention:
+ * S360_E_BADARG before any GPU work.
+ */
+int s360_cube2erp_distance_forward(const float* depth_faces, const float* fxfycxcy, const float* grid, float* erp, int32_t n,
+                                   int32_t face_w, int32_t equ_h, int32_t equ_w, int32_t convention,
+                                   const int32_t* face_map_host, const int64_t* strides_host, void* stream);
+int s360_cube2erp_distance_backward(const float* d_erp, const float* depth_faces, const float* fxfycxcy, const float* grid,
+                                    const int32_t* plan_offsets, const int32_t* plan_entries, float* d_depth_faces, int32_t n,
+                                    int32_t face_w, int32_t equ_h, int32_t equ_w, int32_t convention,
+                                    const int32_t* face_map_host, const int64_t* strides_host, void* stream);
+
+/*
  * Mean SSIM per image for the evaluation step: replaces compute_ssim (src/evaluation/metrics.py:38-54), which copies every
  * face to the host and calls skimage.metrics.structural_similarity(gt, hat, win_size=11, gaussian_weights=True,
  * channel_axis=0, data_range=1.0) one image at a time.  Same algorithm:

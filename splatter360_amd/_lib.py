@@ -63,7 +63,8 @@ EXPORTS = ("s360_forward_raw", "s360_backward_raw", "s360_backward_raw_tail", "s
            "s360_l1_sphere_backward", "s360_depth_metrics", "s360_psnr", "s360_cost_volume_forward", "s360_cost_volume_backward",
            "s360_cost_volume_warp", "s360_depth_head_forward", "s360_depth_head_backward", "s360_upsample_forward", "s360_upsample_backward",
            "s360_depth_tail_forward", "s360_depth_tail_backward", "s360_opacity_map_forward", "s360_opacity_map_backward",
-           "s360_erp2cube_forward", "s360_erp2cube_backward")
+           "s360_erp2cube_forward", "s360_erp2cube_backward", "s360_depth_to_distance_forward", "s360_depth_to_distance_backward",
+           "s360_cube2erp_distance_forward", "s360_cube2erp_distance_backward")
 
 
 def _hipcc() -> str:
@@ -232,6 +233,14 @@ def lib() -> C.CDLL:
     l.s360_erp2cube_forward.argtypes = [vp] * 4 + [i32] * 8 + [C.POINTER(i32), C.POINTER(C.c_int64), vp]
     l.s360_erp2cube_backward.restype = C.c_int
     l.s360_erp2cube_backward.argtypes = [vp] * 6 + [i32] * 7 + [C.POINTER(i32), C.POINTER(C.c_int64), vp]
+    l.s360_depth_to_distance_forward.restype = C.c_int
+    l.s360_depth_to_distance_forward.argtypes = [vp] * 3 + [i32] * 4 + [vp]
+    l.s360_depth_to_distance_backward.restype = C.c_int
+    l.s360_depth_to_distance_backward.argtypes = [vp] * 4 + [i32] * 4 + [vp]
+    l.s360_cube2erp_distance_forward.restype = C.c_int
+    l.s360_cube2erp_distance_forward.argtypes = [vp] * 4 + [i32] * 5 + [C.POINTER(i32), C.POINTER(C.c_int64), vp]
+    l.s360_cube2erp_distance_backward.restype = C.c_int
+    l.s360_cube2erp_distance_backward.argtypes = [vp] * 7 + [i32] * 5 + [C.POINTER(i32), C.POINTER(C.c_int64), vp]
     l.s360_count_backward_slots.restype = C.c_int
     l.s360_count_backward_slots.argtypes = [C.POINTER(S360Params), vp, sz, vp, vp]
     l.s360_count_contributions.restype = C.c_int

@@ -29,6 +29,10 @@ install(depth_tail=True) rebinds the same `F` to a proxy whose interpolate runs 
 predictor's two calls (:652-658), and EncoderCostVolume.map_pdf_to_opacity (src/model/encoder/encoder_costvolume.py:228-241) to the
 opacity-map kernel; the two `F` proxies stack in either order.  The predictor's :694-719 have no seam; depth_tail.fine_depth_tail
 is the direct API for them.
+install(erp_distance=True) rebinds depth_to_distance_map_batch (src/geometry/z_depth_to_distance.py:4-34) to the z-depth -> distance
+kernel of stitch.py, in that module and in src.model.model_wrapper_erp (:48), for the call the evaluation step makes (:457: square
+float32 GPU maps, intrinsics broadcast by einops.repeat).  The step's reorder, conversion and stitch (:446-463) are inline
+statements with no seam of their own; stitch.Cube2Equirec.stitch_distance_rendered is the direct API for the three as one kernel.
 
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
@@ -586,6 +590,35 @@ DEPTH_METRICS_SEAM = _Seam("depth_metrics", DEPTH_METRICS_MODULE, (DEPTH_METRICS
 PSNR_SEAM = _Seam("psnr", METRICS_MODULE, (PSNR_NAME,), METRICS_USERS, {PSNR_NAME: _native_compute_psnr})
 
 
+ERP_DISTANCE_MODULE = "src.geometry.z_depth_to_distance"              # defines depth_to_distance_map_batch (:4-34)
+ERP_DISTANCE_USERS = ("src.model.model_wrapper_erp",)                  # `from ..geometry.z_depth_to_distance import depth_to_distance_map_batch` (:48)
+ERP_DISTANCE_NAME = "depth_to_distance_map_batch"
+
+
+def _native_depth_to_distance(replaced):
+    """depth_to_distance_map_batch with the reference's signature: the z-depth -> distance kernel (convention "reference") for
+    float32 GPU depth maps [N, h, h] with fxfycxcy a float32 [N, 4, h, h] tensor on the same device whose last two strides are 0 —
+    what the reference's einops.repeat of the [N, 4] rows yields (model_wrapper_erp.py:454-455), so one row per map is the whole
+    content; the replaced function otherwise."""
+    from . import stitch as _st
+
+    def depth_to_distance_map_batch(depth_maps, fxfycxcy):
+        if (_is_cuda_f32(depth_maps) and _is_cuda_f32(fxfycxcy) and depth_maps.dim() == 3 and depth_maps.numel() > 0
+                and depth_maps.shape[1] == depth_maps.shape[2] and fxfycxcy.device == depth_maps.device
+                and tuple(fxfycxcy.shape) == (depth_maps.shape[0], 4, depth_maps.shape[1], depth_maps.shape[2])
+                and tuple(fxfycxcy.stride()[2:]) == (0, 0)):
+            return _st.depth_to_distance(depth_maps, fxfycxcy[:, :, 0, 0], "reference")
+        return replaced(depth_maps, fxfycxcy)
+
+    depth_to_distance_map_batch.replaced = replaced
+    depth_to_distance_map_batch.__doc__ = _st.depth_to_distance.__doc__
+    return depth_to_distance_map_batch
+
+
+ERP_DISTANCE_SEAM = _Seam("erp_distance", ERP_DISTANCE_MODULE, (ERP_DISTANCE_NAME,), ERP_DISTANCE_USERS,
+                          {ERP_DISTANCE_NAME: _native_depth_to_distance})
+
+
 COST_VOLUME_MODULE = "src.model.encoder.costvolume.depth_predictor_multiview_360"   # defines warp_with_pose_depth_candidates (:73-214)
 COST_VOLUME_NAME = "warp_with_pose_depth_candidates"                  # DepthPredictorMultiView360.forward calls the module-level name (:606)
 COST_VOLUME_DATASETS = ("hm3d", "replica")
@@ -746,6 +779,14 @@ def install_depth_tail():
     return (None if f is None else f[DEPTH_HEAD_NAME]), (None if m is None else m[DEPTH_TAIL_METHOD])
 
 
+def install_erp_distance():
+    """The half of install(erp_distance=True): rebind depth_to_distance_map_batch now if the reference's module is imported, else
+    as soon as it is (import hook).  Returns the patched function or None.  The evaluation step's reorder + conversion + stitch
+    (model_wrapper_erp.py:446-463) are inline statements: stitch.Cube2Equirec.stitch_distance_rendered is the direct API for them."""
+    out = ERP_DISTANCE_SEAM.install()
+    return None if out is None else out[ERP_DISTANCE_NAME]
+
+
 def install_depth_head():
     """The half of install(depth_head=True): rebind the encoder module's `F` to the softmax proxy now if the module is imported,
     else as soon as it is (import hook).  Returns the proxy or None."""
@@ -775,7 +816,8 @@ def install_psnr():
 
 
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
-            depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, depth_head: bool = False, depth_tail: bool = False, **opts):
+            depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, depth_head: bool = False, depth_tail: bool = False,
+            erp_distance: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
@@ -794,6 +836,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     depth_tail=True: ALSO rebind that module's `F` so that its two F.interpolate calls run the upsampling kernels, and
     EncoderCostVolume.map_pdf_to_opacity to the opacity-map kernel (install_depth_tail; off by default; composes with depth_head in
     either order).
+    erp_distance=True: ALSO rebind the evaluation step's depth_to_distance_map_batch (z_depth_to_distance.py:4-34, bound by
+    model_wrapper_erp.py:48) to the z-depth -> distance kernel (install_erp_distance; off by default).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -816,6 +860,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
         install_depth_head()
     if depth_tail:
         install_depth_tail()
+    if erp_distance:
+        install_erp_distance()
     if lazy:
         if REGISTRY_MODULE in sys.modules:
             return _patch(sys.modules[REGISTRY_MODULE], **opts)
@@ -827,11 +873,11 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
 
 def uninstall() -> None:
     """Put the reference's own decoder class, adapter, compute_ssim, compute_psnr, compute_depth_metrics_batched,
-    compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates, EncoderCostVolume.map_pdf_to_opacity and the predictor module's
-    `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
+    compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates, depth_to_distance_map_batch, EncoderCostVolume.map_pdf_to_opacity
+    and the predictor module's `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
     sys.meta_path[:] = [f for f in sys.meta_path
                         if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher, _DepthLossPatcher, _SeamPatcher))]
-    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM, DEPTH_HEAD_SEAM, DEPTH_TAIL_F_SEAM, DEPTH_TAIL_METHOD_SEAM):
+    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM, DEPTH_HEAD_SEAM, DEPTH_TAIL_F_SEAM, DEPTH_TAIL_METHOD_SEAM, ERP_DISTANCE_SEAM):
         seam.restore()
     dmod = sys.modules.get(DEPTH_MODULE)
     if dmod is not None:

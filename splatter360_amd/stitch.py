@@ -5,6 +5,10 @@ The sampling grid is host-side numpy restated from layers.py:60-106 (same float3
 it is bit-identical; pinned by tests/golden/cube2equirec_*.npz); the gather is one HIP kernel.  The
 adjoint is a second gather over the grid's inverse (adjoint_plan, built once per grid here): no
 atomics, so gradients through the stitch are bit-reproducible.
+
+depth_to_distance and Cube2Equirec.stitch_distance_rendered are the depth channel's counterpart: z-depth -> ray distance
+(depth_to_distance_map_batch, src/geometry/z_depth_to_distance.py:4-34) alone, and fused into the stitch for the evaluation
+step's depth panorama (model_wrapper_erp.py:445-463).
 """
 from __future__ import annotations
 
@@ -107,6 +111,141 @@ def _face_map_arr(face_map):
     return None if face_map is None else (C.c_int32 * 6)(*face_map)
 
 
+# z-depth -> distance conventions (include/s360.h S360_D2D_*)
+DISTANCE_CONVENTIONS = {"reference": 0, "pixel": 1}
+
+
+def _convention_code(convention: str) -> int:
+    if convention not in DISTANCE_CONVENTIONS:
+        raise ValueError(f"convention must be one of {sorted(DISTANCE_CONVENTIONS)}, not {convention!r}")
+    return DISTANCE_CONVENTIONS[convention]
+
+
+def _check_gpu_f32(what: str, **tensors) -> None:
+    """RuntimeError for CPU tensors (GPU only, no CPU path), ValueError for another dtype or mismatched devices."""
+    first = None
+    for name, t in tensors.items():
+        if not isinstance(t, Tensor):
+            raise ValueError(f"{what}: {name} must be a tensor")
+        if not t.is_cuda:
+            raise RuntimeError(f"{what} runs on the GPU only (no CPU path): {name} is on {t.device}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be float32, not {t.dtype}")
+        first = t if first is None else first
+        if t.device != first.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, not {first.device}")
+
+
+def fxfycxcy_from_intrinsics(intrinsics: Tensor, h: int, w: int) -> Tensor:
+    """K[..., 3, 3] normalised intrinsics -> [..., 4] (fx, fy, cx, cy) in pixels of an h x w image, with the reference's own
+    multiplications in K's dtype (model_wrapper_erp.py:450-454: fx = K[0,0] * width, fy = K[1,1] * height, cx = K[0,2] * width,
+    cy = K[1,2] * height)."""
+    if intrinsics.dim() < 2 or tuple(intrinsics.shape[-2:]) != (3, 3):
+        raise ValueError(f"intrinsics must be [..., 3, 3], not {tuple(intrinsics.shape)}")
+    return torch.stack([intrinsics[..., 0, 0] * w, intrinsics[..., 1, 1] * h, intrinsics[..., 0, 2] * w, intrinsics[..., 1, 2] * h], dim=-1)
+
+
+class _DepthToDistance(torch.autograd.Function):
+    """depth [N,H,W], k4 [N,4] (contiguous float32 on one GPU) -> distance [N,H,W]."""
+
+    @staticmethod
+    def forward(ctx, depth, k4, conv):
+        n, h, w = depth.shape
+        dist = torch.empty_like(depth)
+        with torch.cuda.device(depth.device):
+            st = C.c_void_p(torch.cuda.current_stream(depth.device).cuda_stream)
+            rc = _lib.lib().s360_depth_to_distance_forward(C.c_void_p(depth.data_ptr()), C.c_void_p(k4.data_ptr()),
+                                                           C.c_void_p(dist.data_ptr()), n, h, w, conv, st)
+        _lib.check(rc, "s360_depth_to_distance_forward")
+        ctx.save_for_backward(depth, k4)
+        ctx.conv = conv
+        return dist
+
+    @staticmethod
+    def backward(ctx, d_dist):
+        depth, k4 = ctx.saved_tensors
+        n, h, w = depth.shape
+        g = d_dist.detach().float().contiguous()
+        d_depth = torch.empty_like(depth)
+        with torch.cuda.device(depth.device):
+            st = C.c_void_p(torch.cuda.current_stream(depth.device).cuda_stream)
+            rc = _lib.lib().s360_depth_to_distance_backward(C.c_void_p(g.data_ptr()), C.c_void_p(depth.data_ptr()),
+                                                            C.c_void_p(k4.data_ptr()), C.c_void_p(d_depth.data_ptr()), n, h, w,
+                                                            ctx.conv, st)
+        _lib.check(rc, "s360_depth_to_distance_backward")
+        return d_depth, None, None
+
+
+def depth_to_distance(depth: Tensor, fxfycxcy: Tensor, convention: str = "reference") -> Tensor:
+    """z-depth maps depth[..., H, W] -> ray distance |d| s, s = sqrt(((u - cx) / fx)^2 + ((v - cy) / fy)^2 + 1), the same shape:
+    depth_to_distance_map_batch (z_depth_to_distance.py:4-34) in one kernel, float64 arithmetic rounded once.  fxfycxcy[N, 4] holds
+    (fx, fy, cx, cy) in pixels, one row per map (N = the product of depth's leading dimensions); it takes no gradient.  The input
+    is not modified.
+    convention="reference": u is the ROW index and v the column index — what the reference's "ij" meshgrid pairs with cx / fx and
+      cy / fy; H == W is required, as it is for the reference to broadcast.
+    convention="pixel": u is the column (x with fx, cx) and v the row (y with fy, cy); any H, W.
+    d = 0 gives 0 and a negative d gives |d| s.  The gradient is sign(d) s, and 0 at d = 0: finite, where torch's autograd of the
+    reference's sqrt gives NaN."""
+    what = "depth_to_distance"
+    conv = _convention_code(convention)
+    _check_gpu_f32(what, depth=depth, fxfycxcy=fxfycxcy)
+    if depth.dim() < 2 or fxfycxcy.dim() != 2 or fxfycxcy.shape[1] != 4:
+        raise ValueError(f"{what}: depth must be [..., H, W] and fxfycxcy [N, 4], not {tuple(depth.shape)} and {tuple(fxfycxcy.shape)}")
+    h, w = int(depth.shape[-2]), int(depth.shape[-1])
+    n = int(fxfycxcy.shape[0])
+    lead = 1
+    for s in depth.shape[:-2]:
+        lead *= int(s)
+    if lead != n:
+        raise ValueError(f"{what}: depth {tuple(depth.shape)} holds {lead} maps, fxfycxcy {n} rows")
+    if conv == DISTANCE_CONVENTIONS["reference"] and h != w:
+        raise ValueError(f"{what}: convention='reference' needs square maps (the reference only broadcasts for H == W), not {h} x {w}")
+    if depth.numel() == 0:
+        return torch.empty_like(depth)
+    out = _DepthToDistance.apply(depth.contiguous().view(n, h, w), fxfycxcy.detach().contiguous(), conv)
+    return out.view(depth.shape)
+
+
+class _StitchDistance(torch.autograd.Function):
+    """depth faces [N,6,fw,fw], k4 [N,6,4] (contiguous float32 on one GPU) -> ERP distance [N,eh,ew] through `grid` / its plan."""
+
+    @staticmethod
+    def forward(ctx, depth, k4, grid, plan_offsets, plan_entries, face_map, conv):
+        n, fw = int(depth.shape[0]), int(depth.shape[-1])
+        eh, ew = int(grid.shape[0]), int(grid.shape[1])
+        erp = torch.empty((n, eh, ew), dtype=torch.float32, device=depth.device)
+        with torch.cuda.device(depth.device):
+            st = C.c_void_p(torch.cuda.current_stream(depth.device).cuda_stream)
+            rc = _lib.lib().s360_cube2erp_distance_forward(C.c_void_p(depth.data_ptr()), C.c_void_p(k4.data_ptr()),
+                                                           C.c_void_p(grid.data_ptr()), C.c_void_p(erp.data_ptr()), n, fw, eh, ew, conv,
+                                                           _face_map_arr(face_map), None, st)
+        _lib.check(rc, "s360_cube2erp_distance_forward")
+        ctx.save_for_backward(depth, k4, grid, plan_offsets, plan_entries)
+        ctx.meta = (face_map, conv)
+        return erp
+
+    @staticmethod
+    def backward(ctx, d_erp):
+        depth, k4, grid, offs, ents = ctx.saved_tensors
+        face_map, conv = ctx.meta
+        n, fw = int(depth.shape[0]), int(depth.shape[-1])
+        eh, ew = int(grid.shape[0]), int(grid.shape[1])
+        if (offs.dtype, ents.dtype) != (torch.int32, torch.int32) or offs.numel() != 6 * fw * fw + 1 \
+                or not (offs.is_cuda and ents.is_cuda and offs.is_contiguous() and ents.is_contiguous()):
+            raise RuntimeError("cube->ERP distance stitch backward: the adjoint plan does not belong to this grid / device")
+        g = d_erp.detach().float().contiguous()
+        d_depth = torch.empty_like(depth)
+        with torch.cuda.device(depth.device):
+            st = C.c_void_p(torch.cuda.current_stream(depth.device).cuda_stream)
+            rc = _lib.lib().s360_cube2erp_distance_backward(C.c_void_p(g.data_ptr()), C.c_void_p(depth.data_ptr()),
+                                                            C.c_void_p(k4.data_ptr()), C.c_void_p(grid.data_ptr()),
+                                                            C.c_void_p(offs.data_ptr()), C.c_void_p(ents.data_ptr()),
+                                                            C.c_void_p(d_depth.data_ptr()), n, fw, eh, ew, conv,
+                                                            _face_map_arr(face_map), None, st)
+        _lib.check(rc, "s360_cube2erp_distance_backward")
+        return d_depth, None, None, None, None, None, None
+
+
 class _Stitch(torch.autograd.Function):
     """faces -> ERP through `grid` [eh,ew,3]; `plan` = (offsets, entries) = adjoint_plan(grid) on the same device."""
 
@@ -181,3 +320,37 @@ class Cube2Equirec(nn.Module):
         permute / concat copies (model_wrapper_erp.py:393-400)."""
         return _Stitch.apply(faces, self.sample_grid[0, 0], self.plan_offsets, self.plan_entries, CHANGE_ORDER_FACE_MAP, None,
                              int(faces.shape[1]), self.face_w)
+
+    def stitch_distance_rendered(self, depth_faces: Tensor, fxfycxcy: Tensor, convention: str = "reference") -> Tensor:
+        """z-depth faces[N,6,fw,fw] in the reference's RENDERED order (top, front, left, back, right, bottom) with per-face
+        intrinsics fxfycxcy[N,6,4] (fx, fy, cx, cy in pixels, rendered order) -> ERP ray-distance panoramas [N,equ_h,equ_w]:
+        Cube2Equirec(depth_to_distance_map_batch(change_order_batch(depth))) of model_wrapper_erp.py:445-463 in ONE kernel for all N
+        panoramas, without the distance faces, the reordered copy or the intrinsics broadcast, and without writing to the input
+        (change_order_batch flips faces 0 and 5 of its argument in place).  faces[6,fw,fw] with fxfycxcy[6,4] or [1,6,4] gives
+        [equ_h,equ_w].  Bit-identical to depth_to_distance followed by the stitch; the backward has no atomics.
+        convention="reference": the reference's lines as they are — the conversion happens AFTER the reorder with the intrinsics
+          still in rendered order, so slot s uses fxfycxcy[:, s] and the slot-space texel position with u = the ROW index; the two
+          flipped faces (0 and 5) therefore see (fw - 1 - u) - cx where their own image has u - cx.
+        convention="pixel": each face is converted in its own image with its own intrinsics row before the reorder, x (column)
+          with fx, cx and y (row) with fy, cy.
+        The gradient with respect to a depth texel is the stitch's adjoint times sign(d) s, and 0 at d = 0 (finite, where torch's
+        autograd of the reference's sqrt gives NaN).  fxfycxcy takes no gradient."""
+        what = "stitch_distance_rendered"
+        conv = _convention_code(convention)
+        _check_gpu_f32(what, depth_faces=depth_faces, fxfycxcy=fxfycxcy)
+        fw = self.face_w
+        single = depth_faces.dim() == 3
+        d = depth_faces[None] if single else depth_faces
+        k = fxfycxcy[None] if single and fxfycxcy.dim() == 2 else fxfycxcy
+        if d.dim() != 4 or tuple(d.shape[1:]) != (6, fw, fw):
+            raise ValueError(f"{what}: depth_faces must be [N, 6, {fw}, {fw}] or [6, {fw}, {fw}], not {tuple(depth_faces.shape)}")
+        if tuple(k.shape) != (d.shape[0], 6, 4):
+            raise ValueError(f"{what}: fxfycxcy must be [{d.shape[0]}, 6, 4], not {tuple(fxfycxcy.shape)}")
+        grid = self.sample_grid[0, 0]
+        if grid.device != d.device:
+            raise ValueError(f"{what}: depth_faces is on {d.device}, the module on {grid.device}")
+        if d.shape[0] == 0:
+            return torch.empty((0, self.equ_h, self.equ_w), dtype=torch.float32, device=d.device)
+        erp = _StitchDistance.apply(d.contiguous(), k.detach().contiguous(), grid, self.plan_offsets, self.plan_entries,
+                                    CHANGE_ORDER_FACE_MAP, conv)
+        return erp[0] if single else erp
