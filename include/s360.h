@@ -829,6 +829,60 @@ int s360_erp2cube_backward(const float* d_cube, const float* coor, const float* 
                            void* stream);
 
 /*
+ * The pictures of the evaluation step (csrc/s360_visualize.hip): depth colour maps, colour tables, 8-bit frames and error maps
+ * without a sort and without the host.  Additive entries: the ABI version stays.  All of them: float32 device memory in, kernels
+ * on `stream`, no float atomics, no global atomics, no memset, no host synchronisation, every output element written:
+ * bit-identical from call to call.  tests/depth_vis_reference.py is the numpy statement of each.
+ * Colour maps (color_map): S360_CMAP_TURBO, S360_CMAP_VIRIDIS, S360_CMAP_INFERNO, 256 colours each from matplotlib
+ * (csrc/s360_colormap_tables.h, written by scripts/make_colormap_tables.py).  The colour of a float32 x is row
+ *   NaN: the "bad" colour, RGB 0 0 0;  otherwise min(floor(clip(x, 0, 1) * 256), 255)   (matplotlib's rule for float input)
+ * as float32 (the float64 entry rounded) or as the byte trunc(float32 * 255) that prep_image makes of that float.
+ *
+ * s360_depth_colormap replaces depth_map (src/model/model_wrapper_erp.py:122-133: two torch.quantile sorts, log, normalise) with
+ * apply_color_map_to_image(., "turbo") (src/visualization/color_map.py:9-27: a host round trip through matplotlib) and,
+ * for bytes_out, the prep_image that follows (src/misc/image_io.py:38-54), for n_maps maps in one call, each normalised on its own.
+ *   depth: map i is the height x width contiguous float32 elements at depth + i * map_stride (map_stride >= height * width,
+ *     in elements: a strided selection of faces is read in place).  A map of more than 16 000 000 elements: S360_E_UNSUPPORTED
+ *     (the reference truncates what it hands to torch.quantile there; that is not reproduced).
+ *   pos = the elements > 0, n_pos their number.  n_pos > 0:
+ *     near_q = Q(sort(pos), 0.01), far_q = Q(sort(all), 0.99) (NaN if the map holds a NaN), Q ATen's linear rule:
+ *       rank = float32(q) * float32(n - 1) (a float32 product), lo = floor, hi = ceil, w = float32(rank - lo),
+ *       a + w (b - a) if w < 0.5 else b - (b - a)(1 - w) in float64, rounded once to float32;
+ *     ln = float32(log near_q), lf = float32(log far_q), L = float32(log(float64 d)) per pixel,
+ *     x = float32(1 - (L - ln) / (lf - ln)), subtraction and division in float64.
+ *   n_pos == 0 (the reference's except branch): near_q = min, far_q = max (NaN if the map holds a NaN),
+ *     x = float32(1 - (d - near_q) / (far_q - near_q)) in float64.
+ *   So a zero depth takes colour 255, a negative one the NaN colour, inf colour 0, and a constant map is all NaN colour.
+ *   The quantiles are an exact selection (radix select on the order-preserving key, digits of 11, 11 and 10 bits, four ranks in
+ *   the same passes, integer histograms in LDS, per-workgroup partial histograms in the workspace summed by the next launch).
+ *   Outputs, each may be NULL (not all three): rgb_out[n_maps, 3, height, width] float32; bytes_out[n_maps, height, width, 3]
+ *   uint8; range_out[n_maps, 4] float32 = near_q, far_q, ln, lf (ln, lf NaN when n_pos == 0).
+ *   workspace == NULL: *workspace_bytes receives the workspace size (16-byte aligned device memory, contents need no
+ *   initialisation) and nothing runs.  Otherwise four kernels (five with rgb_out or bytes_out) for any n_maps.
+ * s360_colorize replaces apply_color_map (color_map.py:9-19) for count float32 elements: rgb_out / bytes_out (either may be NULL)
+ *   hold [count, 3], or with channels_first != 0 [count / plane, 3, plane] (count a multiple of plane).
+ * s360_prep_image replaces prep_image (image_io.py:38-54): image[batch, channels, height, width], channels 1, 3 or 4 ->
+ *   bytes_out[height, batch * width, 3 or 4] uint8, batch entries side by side, one channel replicated to three,
+ *   trunc(float32(clip(v, 0, 1)) * 255), NaN -> 0 (the reference's cast of NaN is undefined).
+ * s360_error_map replaces |a - b|.mean(0) -> convert_single_colormap (model_wrapper_erp.py:369-371, :109-120, get_colormap :88-92):
+ *   a, b[3, height, width] -> bytes_out[height, width, 3] uint8, viridis with the byte (float64 c * 255).astype(uint8) of
+ *   get_colormap, at the row of m = float32(((|a0 - b0| + |a1 - b1|) + |a2 - b2|) / 3) in float64; Normalize(0, 1) does not clip,
+ *   so m > 1 takes the last colour.
+ * Null required pointers, sizes < 1, channels outside {1, 3, 4}, an unknown colour map, map_stride < height * width, or more
+ * than 2^31 work-items: S360_E_BADARG before any GPU work; a workspace smaller than reported: S360_E_WORKSPACE.
+ */
+#define S360_CMAP_TURBO 0
+#define S360_CMAP_VIRIDIS 1
+#define S360_CMAP_INFERNO 2
+int s360_depth_colormap(const float* depth, int32_t n_maps, int32_t height, int32_t width, size_t map_stride, float* rgb_out,
+                        uint8_t* bytes_out, float* range_out, void* workspace, size_t* workspace_bytes, void* stream);
+int s360_colorize(const float* x, size_t count, size_t plane, int32_t color_map, int32_t channels_first, float* rgb_out,
+                  uint8_t* bytes_out, void* stream);
+int s360_prep_image(const float* image, int32_t batch, int32_t channels, int32_t height, int32_t width, uint8_t* bytes_out,
+                    void* stream);
+int s360_error_map(const float* a, const float* b, int32_t height, int32_t width, uint8_t* bytes_out, void* stream);
+
+/*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an
  * un-synchronised wall clock, src/misc/benchmarker.py:15-33).  While enabled, every kernel group
  * is bracketed by HIP events recorded on the launch stream; s360_profile_collect() synchronises

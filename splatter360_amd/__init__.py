@@ -6,7 +6,8 @@ def install(**opts):
     """Register the fused decoder in the unchanged reference's decoder registry (splatter360_amd.plugin.install).  Keywords
     switch the other native seams on, each off by default: adapter, metrics, depth_loss, depth_metrics, psnr, cost_volume,
     depth_head (the encoder's softmax depth head, splatter360_amd.depth_head) and depth_tail (its two interpolations and
-    map_pdf_to_opacity, splatter360_amd.depth_tail, whose fine_depth_tail is the direct API for the rest of that stretch)."""
+    map_pdf_to_opacity, splatter360_amd.depth_tail, whose fine_depth_tail is the direct API for the rest of that stretch),
+    erp_distance and visualization (the evaluation step's depth_map, prep_image and apply_color_map, splatter360_amd.visualize)."""
     from .plugin import install as _install
     return _install(**opts)
 
@@ -19,6 +20,9 @@ def uninstall():
 def __getattr__(name):
     """splatter360_amd.Equirec2Cube: the ERP -> cube resampler (splatter360_amd.equirec2cube), imported on first use so that
     importing the package stays light.  It has no install() seam: the reference calls it in data-loader workers on numpy arrays."""
+    if name == "visualize":                                   # depth_map, depth_range, colorize, prep_image, error_map
+        import importlib
+        return importlib.import_module(".visualize", __name__)
     if name == "Equirec2Cube":
         from .equirec2cube import Equirec2Cube
         return Equirec2Cube

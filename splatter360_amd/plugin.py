@@ -619,6 +619,71 @@ ERP_DISTANCE_SEAM = _Seam("erp_distance", ERP_DISTANCE_MODULE, (ERP_DISTANCE_NAM
                           {ERP_DISTANCE_NAME: _native_depth_to_distance})
 
 
+VIS_DEPTH_MODULE = "src.model.model_wrapper_erp"                      # defines depth_map (:122-133) and calls it as a global
+VIS_DEPTH_NAME = "depth_map"
+VIS_PREP_MODULE = "src.misc.image_io"                                 # defines prep_image (:38-54); save_image / save_video call it as a global
+VIS_PREP_USERS = ("src.model.model_wrapper_erp", "src.model.model_wrapper_cubemaps")   # `from ..misc.image_io import prep_image, ...` (:22, :23)
+VIS_PREP_NAME = "prep_image"
+VIS_COLOR_MODULE = "src.visualization.color_map"                      # defines apply_color_map (:9-19); apply_color_map_to_image calls it as a global
+VIS_COLOR_USERS = ("src.model.encoder.visualization.encoder_visualizer_costvolume",)   # binds apply_color_map by name (:15)
+VIS_COLOR_NAME = "apply_color_map"
+
+
+def _native_depth_map(replaced):
+    """depth_map with the reference's signature: the depth colour-map kernels for a float32 GPU tensor of at least two dims and
+    at most 16 000 000 elements -> float32 [..., 3, h, w] on the device; the reference normalises over the WHOLE argument, so a
+    [lead, h, w] argument is one map of lead h w elements (visualize.depth_map_whole).  The replaced function otherwise."""
+    from . import visualize as _vis
+
+    def depth_map(result):
+        if _is_cuda_f32(result) and result.dim() >= 2 and 0 < result.numel() <= _vis.MAX_MAP_ELEMENTS:
+            return _vis.depth_map_whole(result)
+        return replaced(result)
+
+    depth_map.replaced = replaced
+    depth_map.__doc__ = _vis.depth_map_whole.__doc__
+    return depth_map
+
+
+def _native_prep_image(replaced):
+    """prep_image with the reference's signature: for a float32 GPU tensor [h, w], [c, h, w] or [b, c, h, w] with c in
+    {1, 3, 4} the frame is made on the device and crosses the bus as bytes (visualize.prep_image(...).cpu().numpy(), the
+    uint8 [h, b w, c] array save_image / save_video consume); the replaced function otherwise."""
+    from . import visualize as _vis
+
+    def prep_image(image):
+        if (_is_cuda_f32(image) and image.dim() in (2, 3, 4) and image.numel() > 0
+                and (image.dim() == 2 or image.shape[-3] in (1, 3, 4))):
+            return _vis.prep_image(image).cpu().numpy()
+        return replaced(image)
+
+    prep_image.replaced = replaced
+    prep_image.__doc__ = _vis.prep_image.__doc__
+    return prep_image
+
+
+def _native_apply_color_map(replaced):
+    """apply_color_map with the reference's signature: the colour-table kernel for a float32 GPU tensor and one of the tables
+    turbo, viridis, inferno -> float32 [..., 3] on the device; the replaced function otherwise (CPU, other dtypes, any other
+    matplotlib map)."""
+    from . import visualize as _vis
+
+    def apply_color_map(x, color_map="inferno"):
+        if _is_cuda_f32(x) and x.numel() > 0 and isinstance(color_map, str) and color_map in _vis.COLOR_MAPS:
+            return _vis.colorize(x, color_map)
+        return replaced(x, color_map)
+
+    apply_color_map.replaced = replaced
+    apply_color_map.__doc__ = _vis.colorize.__doc__
+    return apply_color_map
+
+
+VIS_DEPTH_SEAM = _Seam("visualization", VIS_DEPTH_MODULE, (VIS_DEPTH_NAME,), (), {VIS_DEPTH_NAME: _native_depth_map})
+VIS_PREP_SEAM = _Seam("visualization", VIS_PREP_MODULE, (VIS_PREP_NAME,), VIS_PREP_USERS, {VIS_PREP_NAME: _native_prep_image})
+VIS_COLOR_SEAM = _Seam("visualization", VIS_COLOR_MODULE, (VIS_COLOR_NAME,), VIS_COLOR_USERS, {VIS_COLOR_NAME: _native_apply_color_map})
+VIS_SEAMS = (VIS_DEPTH_SEAM, VIS_PREP_SEAM, VIS_COLOR_SEAM)
+
+
 COST_VOLUME_MODULE = "src.model.encoder.costvolume.depth_predictor_multiview_360"   # defines warp_with_pose_depth_candidates (:73-214)
 COST_VOLUME_NAME = "warp_with_pose_depth_candidates"                  # DepthPredictorMultiView360.forward calls the module-level name (:606)
 COST_VOLUME_DATASETS = ("hm3d", "replica")
@@ -787,6 +852,18 @@ def install_erp_distance():
     return None if out is None else out[ERP_DISTANCE_NAME]
 
 
+def install_visualization():
+    """The half of install(visualization=True): rebind the evaluation step's depth_map (model_wrapper_erp.py:122-133), prep_image
+    (image_io.py:38-54) and apply_color_map (color_map.py:9-19), each now if its module is imported, else as soon as it is (import
+    hooks).  Returns {name: patched function or None}.  convert_single_colormap returns a CPU tensor by contract and the per-frame
+    loops of test_step are inline: visualize.error_map and the batched visualize.depth_map are the direct API for them."""
+    out = {}
+    for seam in VIS_SEAMS:
+        got = seam.install()
+        out[seam.names[0]] = None if got is None else got[seam.names[0]]
+    return out
+
+
 def install_depth_head():
     """The half of install(depth_head=True): rebind the encoder module's `F` to the softmax proxy now if the module is imported,
     else as soon as it is (import hook).  Returns the proxy or None."""
@@ -817,7 +894,7 @@ def install_psnr():
 
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
             depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, depth_head: bool = False, depth_tail: bool = False,
-            erp_distance: bool = False, **opts):
+            erp_distance: bool = False, visualization: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
@@ -838,6 +915,9 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     either order).
     erp_distance=True: ALSO rebind the evaluation step's depth_to_distance_map_batch (z_depth_to_distance.py:4-34, bound by
     model_wrapper_erp.py:48) to the z-depth -> distance kernel (install_erp_distance; off by default).
+    visualization=True: ALSO rebind the evaluation step's depth_map, prep_image and apply_color_map to the kernels of
+    splatter360_amd.visualize, so that a depth picture takes no sort and a frame crosses the bus as bytes (install_visualization;
+    off by default).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -862,6 +942,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
         install_depth_tail()
     if erp_distance:
         install_erp_distance()
+    if visualization:
+        install_visualization()
     if lazy:
         if REGISTRY_MODULE in sys.modules:
             return _patch(sys.modules[REGISTRY_MODULE], **opts)
@@ -873,11 +955,12 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
 
 def uninstall() -> None:
     """Put the reference's own decoder class, adapter, compute_ssim, compute_psnr, compute_depth_metrics_batched,
-    compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates, depth_to_distance_map_batch, EncoderCostVolume.map_pdf_to_opacity
-    and the predictor module's `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
+    compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates, depth_to_distance_map_batch, depth_map, prep_image,
+    apply_color_map, EncoderCostVolume.map_pdf_to_opacity and the predictor module's `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
     sys.meta_path[:] = [f for f in sys.meta_path
                         if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher, _DepthLossPatcher, _SeamPatcher))]
-    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM, DEPTH_HEAD_SEAM, DEPTH_TAIL_F_SEAM, DEPTH_TAIL_METHOD_SEAM, ERP_DISTANCE_SEAM):
+    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM, DEPTH_HEAD_SEAM, DEPTH_TAIL_F_SEAM, DEPTH_TAIL_METHOD_SEAM, ERP_DISTANCE_SEAM,
+                 *VIS_SEAMS):
         seam.restore()
     dmod = sys.modules.get(DEPTH_MODULE)
     if dmod is not None:
