@@ -622,6 +622,48 @@ int s360_l1_sphere_backward(const float* pred, const float* target, const float*
                             const float* grad_loss, const float* den, float* grad_pred, float* grad_target, void* stream);
 
 /*
+ * The training step's depth-smoothness loss, LossDepth (src/loss/loss_depth.py:26-60), forward and backward, on the GPU
+ * (csrc/s360_depth_smooth.hip).
+ *
+ * s360_depth_smooth_forward: depth[batch, views, height, width] contiguous float32 device memory; log_near, log_far
+ * [batch, bound_views] float32 device memory, the natural logs of the bounds as the caller computes them (the reference's
+ * float32 .log()); bound_views divides views and view v uses bound v / (views / bound_views).  Per pixel, in float64 on those
+ * float32 values and with no FMA contraction:
+ *   n = (max(min(d, log_far), log_near) - log_near) / (log_far - log_near)  (torch's minimum / maximum: a NaN stays a NaN);
+ *   dx[x] = n[x + 1] - n[x] along width, dy likewise along height;  S360_DS_SECOND: dx[x] = (n[x + 2] - n[x + 1]) - (n[x + 1] - n[x]);
+ *   S360_DS_BILATERAL: image[batch, views, channels, height, width] contiguous float32 (never written), c[x] = max over channels
+ *   of the SIGNED difference image[x + 1] - image[x] (with S360_DS_SECOND: max(c[x + 1], c[x])), t = dx exp(-c sigma_image);
+ *   else t = dx and image, channels and sigma_image are ignored;
+ *   loss[1] = sum |tx| / Nx + sum |ty| / Ny, Nx = batch views height (width - order), Ny = batch views (height - order) width,
+ *   order 1 or 2: float64 sums, rounded to float32 once.  log_near >= log_far or a non-finite bound gives a non-finite loss, as in
+ *   the reference.
+ *   workspace == NULL: *workspace_bytes receives the workspace size (16-byte aligned device memory) and nothing runs.
+ *   Otherwise two kernels run on `stream`: every 32 x 64 tile writes its float64 pair to its own slot, one workgroup adds the
+ *   slots in index order.  No atomics, no memset, no host synchronisation: the loss is bit-identical from call to call and
+ *   from stream to stream.
+ *
+ * s360_depth_smooth_backward: torch's autograd chain of the forward as a gather, given grad_loss (a DEVICE float scalar):
+ *   grad_depth = grad_loss (Sx / Nx + Sy / Ny) gate / (log_far - log_near),  S = sum over the terms of the axis that hold the
+ *   pixel of coef sgn(t) e, coef (+1, -1) for the first and (+1, -2, +1) for the second derivative, e = exp(-c sigma_image) (or 1),
+ *   sgn(0) = sgn(NaN) = 0, gate = (d > log_far ? 0 : d == log_far ? 0.5 : 1) (m < log_near ? 0 : m == log_near ? 0.5 : 1) with
+ *   m = min(d, log_far): the halves torch's minimum / maximum give at a tie.  Float64, rounded to float32 once; nothing but the
+ *   inputs is read.  One kernel on `stream`, no atomics; every element of grad_depth is written.  The image takes no gradient.
+ *
+ * Both: bound_views not dividing views, height or width <= the derivative order, channels < 1 with S360_DS_BILATERAL, an unknown
+ * flag, a size < 1, a null required pointer or more than 2^31 / 256 tiles: S360_E_BADARG before any GPU work; a workspace
+ * smaller than reported: S360_E_WORKSPACE.
+ */
+#define S360_DS_SECOND 1    /* flags bit 0: second derivative */
+#define S360_DS_BILATERAL 2 /* flags bit 1: weight every term with exp(-c sigma_image) from `image` */
+int s360_depth_smooth_forward(const float* depth, const float* log_near, const float* log_far, const float* image, int32_t batch,
+                              int32_t views, int32_t bound_views, int32_t channels, int32_t height, int32_t width,
+                              float sigma_image, int32_t flags, float* loss, void* workspace, size_t* workspace_bytes,
+                              void* stream);
+int s360_depth_smooth_backward(const float* depth, const float* log_near, const float* log_far, const float* image, int32_t batch,
+                               int32_t views, int32_t bound_views, int32_t channels, int32_t height, int32_t width,
+                               float sigma_image, int32_t flags, const float* grad_loss, float* grad_depth, void* stream);
+
+/*
  * The other weight-free scores of the evaluation step (csrc/s360_eval_scores.hip).
  *
  * s360_depth_metrics replaces compute_depth_metrics_batched (src/scripts/compute_depth_metrics.py:47-116, called at

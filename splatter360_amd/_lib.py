@@ -15,7 +15,8 @@ _PKG = Path(__file__).resolve().parent
 _CSRC = _PKG / "csrc"
 LIB_PATH = _PKG / "libs360.so"
 SOURCES = ("s360_forward.hip", "s360_backward.hip", "s360_backward_em.hip", "s360_stitch.hip", "s360_views.hip", "s360_adapter.hip", "s360_metrics.hip",
-           "s360_depth_loss.hip", "s360_eval_scores.hip", "s360_cost_volume.hip", "s360_depth_head.hip", "s360_depth_tail.hip", "s360_equirec2cube.hip", "s360_visualize.hip")
+           "s360_depth_loss.hip", "s360_eval_scores.hip", "s360_cost_volume.hip", "s360_depth_head.hip", "s360_depth_tail.hip", "s360_equirec2cube.hip", "s360_visualize.hip",
+           "s360_depth_smooth.hip")
 # per-source extra flags (s360_backward_em.hip: see the launcher comment in csrc/s360_bwd_em.h)
 SOURCE_FLAGS = {"s360_backward_em.hip": ("-fno-slp-vectorize",)}
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result")
@@ -33,6 +34,8 @@ FLAG_ATOMIC_GRADS = 256
 FLAG_SPLIT_LISTS = 512
 FLAG_RAW_INPUTS = 1024
 FLAG_COOP_WALK = 2048
+DS_SECOND = 1        # s360_depth_smooth_*: flags
+DS_BILATERAL = 2
 ABI_VERSION = 24
 
 
@@ -65,7 +68,8 @@ EXPORTS = ("s360_forward_raw", "s360_backward_raw", "s360_backward_raw_tail", "s
            "s360_depth_tail_forward", "s360_depth_tail_backward", "s360_opacity_map_forward", "s360_opacity_map_backward",
            "s360_erp2cube_forward", "s360_erp2cube_backward", "s360_depth_to_distance_forward", "s360_depth_to_distance_backward",
            "s360_cube2erp_distance_forward", "s360_cube2erp_distance_backward",
-           "s360_depth_colormap", "s360_colorize", "s360_prep_image", "s360_error_map")
+           "s360_depth_colormap", "s360_colorize", "s360_prep_image", "s360_error_map",
+           "s360_depth_smooth_forward", "s360_depth_smooth_backward")
 
 
 def _hipcc() -> str:
@@ -250,6 +254,10 @@ def lib() -> C.CDLL:
     l.s360_prep_image.argtypes = [vp] + [i32] * 4 + [vp, vp]
     l.s360_error_map.restype = C.c_int
     l.s360_error_map.argtypes = [vp, vp, i32, i32, vp, vp]
+    l.s360_depth_smooth_forward.restype = C.c_int
+    l.s360_depth_smooth_forward.argtypes = [vp] * 4 + [i32] * 6 + [f32, i32, vp, vp, C.POINTER(sz), vp]
+    l.s360_depth_smooth_backward.restype = C.c_int
+    l.s360_depth_smooth_backward.argtypes = [vp] * 4 + [i32] * 6 + [f32, i32, vp, vp, vp]
     l.s360_count_backward_slots.restype = C.c_int
     l.s360_count_backward_slots.argtypes = [C.POINTER(S360Params), vp, sz, vp, vp]
     l.s360_count_contributions.restype = C.c_int

@@ -33,6 +33,8 @@ install(erp_distance=True) rebinds depth_to_distance_map_batch (src/geometry/z_d
 kernel of stitch.py, in that module and in src.model.model_wrapper_erp (:48), for the call the evaluation step makes (:457: square
 float32 GPU maps, intrinsics broadcast by einops.repeat).  The step's reorder, conversion and stitch (:446-463) are inline
 statements with no seam of their own; stitch.Cube2Equirec.stitch_distance_rendered is the direct API for the three as one kernel.
+install(depth_smoothness=True) rebinds LossDepth.forward (src/loss/loss_depth.py:27-60) to the depth-smoothness kernels of
+depth_smooth.py for float32 GPU batches; every other call reaches the replaced method.
 
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
@@ -835,6 +837,69 @@ DEPTH_TAIL_METHOD_SEAM = _MethodSeam("depth_tail", DEPTH_TAIL_MODULE, DEPTH_TAIL
                                      {DEPTH_TAIL_METHOD: _native_map_pdf_to_opacity})
 
 
+DEPTH_SMOOTH_MODULE = "src.loss.loss_depth"                          # defines LossDepth (:26-60)
+DEPTH_SMOOTH_CLASS = "LossDepth"
+DEPTH_SMOOTH_METHOD = "forward"
+
+
+def _native_depth_smooth_call(cfg, prediction, batch):
+    """The arguments of depth_smooth.depth_smoothness_loss for a LossDepth.forward call the kernels can take, else None:
+    prediction.depth a float32 CUDA [B,V,H,W] tensor with H, W above the derivative order; batch["target"]["near"] / ["far"]
+    float32 CUDA [B,Vn] on the same device with Vn in {1, V} (the shapes the reference's own broadcast accepts); with
+    cfg.sigma_image not None, batch["target"]["image"] a float32 CUDA [B,V,C,H,W] tensor on that device that takes no gradient.
+    The decision reads only configuration, devices, dtypes and shapes."""
+    try:
+        depth, target = prediction.depth, batch["target"]
+        near, far = target["near"], target["far"]
+        sigma, second, weight = cfg.sigma_image, bool(cfg.use_second_derivative), cfg.weight
+        image = target["image"] if sigma is not None else None
+    except (AttributeError, KeyError, TypeError):
+        return None
+    order = 2 if second else 1
+    if not (_is_cuda_f32(depth) and depth.dim() == 4 and depth.numel() > 0 and min(depth.shape[2:]) > order):
+        return None
+    b, v, h, w = depth.shape
+    if not (_is_cuda_f32(near) and _is_cuda_f32(far) and near.dim() == 2 and near.shape == far.shape and near.shape[0] == b
+            and near.shape[1] in (1, v) and near.device == far.device == depth.device):
+        return None
+    if sigma is not None:
+        if not (isinstance(sigma, (int, float)) and _is_cuda_f32(image) and image.dim() == 5 and image.shape[2] >= 1
+                and (image.shape[0], image.shape[1], image.shape[3], image.shape[4]) == (b, v, h, w)
+                and image.device == depth.device and not image.requires_grad):
+            return None
+    if not isinstance(weight, (int, float)):
+        return None
+    return (depth, near, far, image), dict(sigma_image=sigma, use_second_derivative=second, weight=weight)
+
+
+def _native_loss_depth_forward(replaced):
+    """LossDepth.forward with the reference's signature: the depth-smoothness kernels of depth_smooth.py for the calls
+    _native_depth_smooth_call accepts, the replaced method otherwise (so every error the reference raises is still raised)."""
+    from . import depth_smooth as _ds
+
+    def forward(self, prediction, batch, gaussians, global_step):
+        call = _native_depth_smooth_call(self.cfg, prediction, batch)
+        if call is not None:
+            return _ds.depth_smoothness_loss(*call[0], **call[1])
+        return replaced(self, prediction, batch, gaussians, global_step)
+
+    forward.replaced = replaced
+    forward.__doc__ = _ds.depth_smoothness_loss.__doc__
+    return forward
+
+
+DEPTH_SMOOTH_SEAM = _MethodSeam("depth_smoothness", DEPTH_SMOOTH_MODULE, DEPTH_SMOOTH_CLASS, (DEPTH_SMOOTH_METHOD,),
+                                {DEPTH_SMOOTH_METHOD: _native_loss_depth_forward})
+
+
+def install_depth_smoothness():
+    """The half of install(depth_smoothness=True): rebind LossDepth.forward (src/loss/loss_depth.py:27-60) to the wrapper around
+    the depth-smoothness kernels now if the reference's module is imported, else as soon as it is (import hook).  Returns the
+    patched method or None."""
+    out = DEPTH_SMOOTH_SEAM.install()
+    return None if out is None else out[DEPTH_SMOOTH_METHOD]
+
+
 def install_depth_tail():
     """The half of install(depth_tail=True): rebind the predictor module's `F` to the interpolate proxy and
     EncoderCostVolume.map_pdf_to_opacity to the opacity-map wrapper, each now if its module is imported, else as soon as it is
@@ -894,7 +959,7 @@ def install_psnr():
 
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
             depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, depth_head: bool = False, depth_tail: bool = False,
-            erp_distance: bool = False, visualization: bool = False, **opts):
+            erp_distance: bool = False, visualization: bool = False, depth_smoothness: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
@@ -917,6 +982,9 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     model_wrapper_erp.py:48) to the z-depth -> distance kernel (install_erp_distance; off by default).
     visualization=True: ALSO rebind the evaluation step's depth_map, prep_image and apply_color_map to the kernels of
     splatter360_amd.visualize, so that a depth picture takes no sort and a frame crosses the bus as bytes (install_visualization;
+    off by default).
+    depth_smoothness=True: ALSO rebind the training step's LossDepth.forward (src/loss/loss_depth.py:27-60, the `depth` entry of
+    the reference's loss registry) to the depth-smoothness kernels of splatter360_amd.depth_smooth (install_depth_smoothness;
     off by default).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
@@ -944,6 +1012,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
         install_erp_distance()
     if visualization:
         install_visualization()
+    if depth_smoothness:
+        install_depth_smoothness()
     if lazy:
         if REGISTRY_MODULE in sys.modules:
             return _patch(sys.modules[REGISTRY_MODULE], **opts)
@@ -956,11 +1026,11 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
 def uninstall() -> None:
     """Put the reference's own decoder class, adapter, compute_ssim, compute_psnr, compute_depth_metrics_batched,
     compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates, depth_to_distance_map_batch, depth_map, prep_image,
-    apply_color_map, EncoderCostVolume.map_pdf_to_opacity and the predictor module's `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
+    apply_color_map, EncoderCostVolume.map_pdf_to_opacity, LossDepth.forward and the predictor module's `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
     sys.meta_path[:] = [f for f in sys.meta_path
                         if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher, _DepthLossPatcher, _SeamPatcher))]
     for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM, DEPTH_HEAD_SEAM, DEPTH_TAIL_F_SEAM, DEPTH_TAIL_METHOD_SEAM, ERP_DISTANCE_SEAM,
-                 *VIS_SEAMS):
+                 DEPTH_SMOOTH_SEAM, *VIS_SEAMS):
         seam.restore()
     dmod = sys.modules.get(DEPTH_MODULE)
     if dmod is not None:
