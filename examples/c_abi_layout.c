@@ -30,6 +30,13 @@ int main(void) {
     }
     printf("abi %d forward_workspace_bytes %zu backward_workspace_bytes %zu keys_offset %zu\n", s360_abi_version(),
            lay.total_bytes, lay.backward_bytes, lay.keys);
+    {
+        /* where the backward leaves its per-pair raster-gradient records: host arithmetic on the address, nothing is dereferenced */
+        size_t off = 0;
+        rc = s360_backward_pair_records(&prm, (const void*)&lay, lay.backward_bytes, &off);
+        printf("pair_records rc %d offset %zu of %zu\n", rc, off, lay.backward_bytes);
+        if (rc != 0 || off + (size_t)prm.V * (size_t)prm.P * 48u > lay.backward_bytes) return 4;
+    }
     prm.V = 99; /* invalid: must be rejected with an error code, not a crash */
     rc = s360_layout(&prm, &lay);
     printf("bad V -> %d (%s)\n", rc, s360_error_string(rc));

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define S360_ABI_VERSION 24
+#define S360_ABI_VERSION 25
 #define S360_MAX_VIEWS 8
 #define S360_TILE 16
 
@@ -387,6 +387,15 @@ int s360_backward_gaussians(const S360Params* prm, const S360View* views, const 
                             float* d_means2D, float* d_rgb_sum, void* bwd_workspace, size_t bwd_workspace_bytes, void* stream);
 int s360_unpack_gradients(const float* packed, int32_t P, int32_t cov9, float* d_means3D, float* d_cov, float* d_opacities,
                           void* stream);
+/* Where s360_backward* leave the per-pair raster-gradient records inside bwd_workspace (ABI v25): byte offset of float[V*P][12],
+ * pair v P + g — words 0..1 dL/dx, dL/dy of the centre in pixels | 2..4 dL/dA, dL/dB, dL/dC of the conic | 5 dL/dopacity |
+ * 6..8 dL/dr, g, b | 9 dL/d(depth value) | 10..11 unused —, valid after s360_backward_composite or any s360_backward* call on that
+ * workspace (the per-Gaussian kernels only read them; records of pairs the forward culled are never written nor read).  The
+ * records start on a 256-byte boundary of the ADDRESS, so the offset belongs to the bwd_workspace pointer it was asked for.
+ * Host arithmetic only; launches nothing and dereferences nothing.  A null prm / bwd_workspace / byte_offset or a
+ * S360_FLAG_FORWARD_ONLY parameter set: S360_E_BADARG; bwd_workspace_bytes < backward_bytes: S360_E_WORKSPACE.  For tests and
+ * diagnostics: it covers the S360_FLAG_ATOMIC_GRADS layout and the default one. */
+int s360_backward_pair_records(const S360Params* prm, const void* bwd_workspace, size_t bwd_workspace_bytes, size_t* byte_offset);
 /* The all-gather form of the exchange (up to two ranks: one collective per Gaussian range instead of two): packed_blocks holds n_blocks
  * gathered [g_count,10] row blocks, one per rank, back to back; their sum (rank order: the same bits on every rank) is written to rows
  * [g_begin, g_begin + g_count) of d_means3D / d_cov / d_opacities — the local reduction and s360_unpack_gradients in one pass. */

@@ -48,9 +48,13 @@ def _lib(dtype):
     lib.orc_num_rendered.argtypes = [C.c_void_p]
     lib.orc_backward.argtypes = [C.c_void_p] * 8
     lib.orc_set_parallel_backward.argtypes = [C.c_int]
+    lib.orc_backward_gaussians.argtypes = [C.c_void_p] * 7
+    lib.orc_set_raster_grads.argtypes = [C.c_void_p] * 5
+    lib.orc_set_depth_seed.argtypes = [C.c_void_p] * 3
     for fn in ("radii", "tiles_touched", "offsets", "rect", "xy", "depth", "conic_opacity", "rgb",
                "clamped", "keys", "values", "ranges", "image", "final_T", "n_contrib",
-               "grad_xy_pix", "grad_conic", "grad_opacity_raster", "grad_rgb"):
+               "grad_xy_pix", "grad_conic", "grad_opacity_raster", "grad_rgb", "grad_xy_pix_abs", "grad_conic_abs",
+               "grad_opacity_raster_abs", "grad_rgb_abs", "grad_depth_value", "grad_depth_value_abs", "decision_margin"):
         f = getattr(lib, "orc_" + fn)
         f.restype = C.c_void_p
         f.argtypes = [C.c_void_p]
@@ -146,12 +150,46 @@ class OracleRasterizer:
             "image": _view(lib.orc_image(h), (3, H, W), dt),
             "final_T": _view(lib.orc_final_T(h), (H, W), dt),
             "n_contrib": _view(lib.orc_n_contrib(h), (H, W), np.uint32),
+            # distance of each pixel's nearest discontinuous decision (alpha skip, power skip, stop test; inf: none evaluated)
+            "decision_margin": _view(lib.orc_decision_margin(h), (H, W), dt),
         }
         return out
 
-    def backward(self, dL_dimage) -> dict:
+    def _outputs(self):
+        P, dt = self.P, self.dt
+        n = max(P, 1)
+        d_sh = np.zeros((n, max(self.M, 1), 3), dt) if self.use_sh else None
+        d_col = None if self.use_sh else np.zeros((n, 3), dt)
+        return np.zeros((n, 3), dt), np.zeros((n, 3), dt), np.zeros((n, 6), dt), d_sh, d_col, np.zeros((n,), dt)
+
+    def backward_gaussians(self, raster_xy_pix, raster_conic, raster_opacity, raster_rgb) -> dict:
+        """The per-Gaussian part of backward() alone (orc_backward's second loop), from raster gradients the caller supplies
+        ([NP,2] pixels, [NP,3] true d/dA, d/dB, d/dC, [NP], [NP,3]); needs forward().  dL/dSH is always computed when SH is
+        used: the view-direction term of dL/dmean lives in that branch."""
+        P, dt = self.P, self.dt
+        a = lambda x, shape: np.ascontiguousarray(np.asarray(x, dtype=dt).reshape(shape))
+        rin = (a(raster_xy_pix, (self.NP, 2)), a(raster_conic, (self.NP, 3)), a(raster_opacity, (self.NP,)), a(raster_rgb, (self.NP, 3)))
+        self.lib.orc_set_raster_grads(self.h, *[r.ctypes.data for r in rin])
+        d_means3D, d_means2D, d_cov6, d_sh, d_col, d_op = self._outputs()
+        p = lambda arr: arr.ctypes.data if arr is not None else None
+        self.lib.orc_backward_gaussians(self.h, p(d_means3D), p(d_means2D), p(d_cov6), p(d_sh), p(d_col), p(d_op))
+        return {
+            "means3D": d_means3D[:P], "means2D": d_means2D[:P], "cov3D": d_cov6[:P],
+            "opacities": d_op[:P].reshape(P, 1),
+            "shs": None if d_sh is None else d_sh[:P, : self.M],
+            "colors_precomp": None if d_col is None else d_col[:P],
+        }
+
+    def backward(self, dL_dimage, dL_ddepth=None, depth_values=None) -> dict:
+        """dL_ddepth [H,W] (optional): the seed of the fused depth image, composited like a fourth colour channel with background
+        0.  It fills raster_depth_value = sum over pixels of alpha T dL_ddepth, the depth channel's record per pair, and — when
+        depth_values [NP] (each pair's value in that image) is given — enters dL/dalpha and with it every other gradient.  The
+        chain from the value to the mean is the caller's."""
         P, dt = self.P, self.dt
         g = np.ascontiguousarray(np.asarray(dL_dimage, dtype=dt).reshape(3, self.H, self.W))
+        gz = None if dL_ddepth is None else np.ascontiguousarray(np.asarray(dL_ddepth, dtype=dt).reshape(self.H, self.W))
+        zv = None if (gz is None or depth_values is None) else np.ascontiguousarray(np.asarray(depth_values, dtype=dt).reshape(self.NP))
+        self.lib.orc_set_depth_seed(self.h, None if gz is None else gz.ctypes.data, None if zv is None else zv.ctypes.data)
         n = max(P, 1)
         d_means3D = np.zeros((n, 3), dt)
         d_means2D = np.zeros((n, 3), dt)
@@ -161,6 +199,7 @@ class OracleRasterizer:
         d_col = None if self.use_sh else np.zeros((n, 3), dt)
         p = lambda arr: arr.ctypes.data if arr is not None else None
         self.lib.orc_backward(self.h, p(g), p(d_means3D), p(d_means2D), p(d_cov6), p(d_sh), p(d_col), p(d_op))
+        self.lib.orc_set_depth_seed(self.h, None, None)
         lib, h = self.lib, self.h
         return {
             "means3D": d_means3D[:P], "means2D": d_means2D[:P], "cov3D": d_cov6[:P],
@@ -171,6 +210,13 @@ class OracleRasterizer:
             "raster_conic": _view(lib.orc_grad_conic(h), (self.NP, 3), dt),
             "raster_opacity": _view(lib.orc_grad_opacity_raster(h), (self.NP,), dt),
             "raster_rgb": _view(lib.orc_grad_rgb(h), (self.NP, 3), dt),
+            # sum |term| of the same sums: the condition of each record word
+            "raster_xy_pix_abs": _view(lib.orc_grad_xy_pix_abs(h), (self.NP, 2), dt),
+            "raster_conic_abs": _view(lib.orc_grad_conic_abs(h), (self.NP, 3), dt),
+            "raster_opacity_abs": _view(lib.orc_grad_opacity_raster_abs(h), (self.NP,), dt),
+            "raster_rgb_abs": _view(lib.orc_grad_rgb_abs(h), (self.NP, 3), dt),
+            "raster_depth_value": _view(lib.orc_grad_depth_value(h), (self.NP,), dt),
+            "raster_depth_value_abs": _view(lib.orc_grad_depth_value_abs(h), (self.NP,), dt),
         }
 
 

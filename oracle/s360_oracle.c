@@ -100,6 +100,13 @@ typedef struct {
     uint32_t *n_contrib;
     /* per-Gaussian raster gradients (backward intermediates) */
     real *g_xy, *g_conic, *g_op, *g_rgb;
+    /* sum |term| next to every sum above (the condition of each sum: what a float32 summation can be held to), and the depth
+     * channel's record: g_z[id] = sum over pixels of alpha T * depth_seed[pix] (0 without a seed) */
+    real *g_xy_abs, *g_conic_abs, *g_op_abs, *g_rgb_abs, *g_z, *g_z_abs;
+    const real* depth_seed; /* borrowed, [H,W] or NULL: orc_set_depth_seed */
+    const real* depth_val;  /* borrowed, [NP] or NULL: each pair's value in the depth image (a fourth colour channel) */
+    /* per pixel: distance of the nearest discontinuous decision of render_forward (see there) */
+    real* margin;
 } Orc;
 
 /* x' = V p with V(i,j) = m[j*4+i]  (row-vector convention: memory is the transposed matrix) */
@@ -526,16 +533,24 @@ static void render_forward(Orc* o) {
         real T = R(1), C[3] = {R(0), R(0), R(0)};
         uint32_t contributor = 0, last = 0;
         real pxf = (real)px, pyf = (real)py;
+        /* decision margin: over the entries this pixel evaluates before it stops, the smallest of |power| (the power > 0 skip),
+         * |255 alpha - 1| (the alpha < 1/255 skip) and |test_T / 1e-4 - 1| / 100 (the stop; 1 - alpha just below the 0.99 clamp
+         * amplifies alpha's rounding a hundredfold).  Below a few float32 roundings of these, a float32 evaluation of the same
+         * pixel may decide otherwise.  Infinity: nothing evaluated. */
+        real margin = (real)INFINITY;
         for (uint32_t j = s; j < e; ++j) {
             ++contributor;
             uint32_t id = o->vals[j];
             real dx = o->xy[2 * id] - pxf, dy = o->xy[2 * id + 1] - pyf;
             const real* co = o->conic_op + 4 * id;
             real power = -R(0.5) * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
+            margin = r_min(margin, power < R(0) ? -power : power);
             if (power > R(0)) continue;
             real alpha = r_min(R(0.99), co[3] * r_exp(power));
+            { real m_ = R(255) * alpha - R(1); margin = r_min(margin, m_ < R(0) ? -m_ : m_); }
             if (alpha < R(1.0) / R(255.0)) continue;
             real test_T = T * (R(1) - alpha);
+            { real m_ = (test_T / R(0.0001) - R(1)) / R(100); margin = r_min(margin, m_ < R(0) ? -m_ : m_); }
             if (test_T < R(0.0001)) break;
             for (int c = 0; c < 3; ++c) C[c] += o->rgb[3 * id + c] * alpha * T;
             T = test_T;
@@ -543,6 +558,7 @@ static void render_forward(Orc* o) {
         }
         o->final_T[pix] = T;
         o->n_contrib[pix] = last;
+        o->margin[pix] = margin;
         for (int c = 0; c < 3; ++c) o->image[(size_t)c * H * W + pix] = C[c] + T * p->bg[c];
     }
 }
@@ -589,6 +605,13 @@ EXPORT Orc* orc_create(const OrcParams* prm, const real* means, const real* cov6
     o->g_conic = (real*)calloc(np * 3, sizeof(real));
     o->g_op = (real*)calloc(np, sizeof(real));
     o->g_rgb = (real*)calloc(np * 3, sizeof(real));
+    o->g_xy_abs = (real*)calloc(np * 2, sizeof(real));
+    o->g_conic_abs = (real*)calloc(np * 3, sizeof(real));
+    o->g_op_abs = (real*)calloc(np, sizeof(real));
+    o->g_rgb_abs = (real*)calloc(np * 3, sizeof(real));
+    o->g_z = (real*)calloc(np, sizeof(real));
+    o->g_z_abs = (real*)calloc(np, sizeof(real));
+    o->margin = (real*)calloc(npix + 1, sizeof(real));
     return o;
 }
 
@@ -599,6 +622,8 @@ EXPORT void orc_destroy(Orc* o) {
     free(o->depth); free(o->conic_op); free(o->rgb); free(o->clamped); free(o->keys);
     free(o->vals); free(o->ranges); free(o->image); free(o->final_T); free(o->n_contrib);
     free(o->g_xy); free(o->g_conic); free(o->g_op); free(o->g_rgb);
+    free(o->g_xy_abs); free(o->g_conic_abs); free(o->g_op_abs); free(o->g_rgb_abs); free(o->g_z); free(o->g_z_abs);
+    free(o->margin);
     free(o);
 }
 
@@ -633,6 +658,28 @@ EXPORT const real* orc_grad_xy_pix(Orc* o) { return o->g_xy; }
 EXPORT const real* orc_grad_conic(Orc* o) { return o->g_conic; }
 EXPORT const real* orc_grad_opacity_raster(Orc* o) { return o->g_op; }
 EXPORT const real* orc_grad_rgb(Orc* o) { return o->g_rgb; }
+EXPORT const real* orc_grad_xy_pix_abs(Orc* o) { return o->g_xy_abs; }
+EXPORT const real* orc_grad_conic_abs(Orc* o) { return o->g_conic_abs; }
+EXPORT const real* orc_grad_opacity_raster_abs(Orc* o) { return o->g_op_abs; }
+EXPORT const real* orc_grad_rgb_abs(Orc* o) { return o->g_rgb_abs; }
+EXPORT const real* orc_grad_depth_value(Orc* o) { return o->g_z; }
+EXPORT const real* orc_grad_depth_value_abs(Orc* o) { return o->g_z_abs; }
+EXPORT const real* orc_decision_margin(Orc* o) { return o->margin; }
+/* The fused depth channel in the next orc_backward's pixel loop (borrowed pointers; NULL, NULL: none): the depth image is
+ * composited like a fourth colour channel, sum_j alpha_j T_j value_j with background 0.  dL_ddepth[H,W] is its seed; it fills
+ * orc_grad_depth_value (dL/dvalue per pair) and, when depth_values[NP] (each pair's value) is given, enters dL/dalpha and through
+ * it the centre, conic and opacity gradients.  The chain from the value to the mean is not part of this oracle. */
+EXPORT void orc_set_depth_seed(Orc* o, const real* dL_ddepth, const real* depth_values) {
+    o->depth_seed = dL_ddepth;
+    o->depth_val = dL_ddepth ? depth_values : NULL;
+}
+/* Raster gradients for orc_backward_gaussians from the caller instead of orc_backward's pixel loop ([NP,2], [NP,3], [NP], [NP,3]). */
+EXPORT void orc_set_raster_grads(Orc* o, const real* g_xy, const real* g_conic, const real* g_op, const real* g_rgb) {
+    memcpy(o->g_xy, g_xy, sizeof(real) * 2 * (size_t)o->NP);
+    memcpy(o->g_conic, g_conic, sizeof(real) * 3 * (size_t)o->NP);
+    memcpy(o->g_op, g_op, sizeof(real) * (size_t)o->NP);
+    memcpy(o->g_rgb, g_rgb, sizeof(real) * 3 * (size_t)o->NP);
+}
 
 /* Per-Gaussian backward of the spherical mode: raster gradients of the main pair i and the ghost pair P + i add (the
  * ghost's centre is the main one shifted by a constant), then chain through geo_sph.  d_means2D = (dL/du, dL/dv, 0)
@@ -755,18 +802,29 @@ static void backward_one_sph(Orc* o, int i, real* dm, real* dm2, real* dc, real*
 static int g_parallel_backward = 0;
 EXPORT void orc_set_parallel_backward(int on) { g_parallel_backward = on; }
 
+EXPORT void orc_backward_gaussians(Orc* o, real* d_means3D, real* d_means2D, real* d_cov6, real* d_sh, real* d_colors,
+                                   real* d_opacity);
+
 EXPORT void orc_backward(Orc* o, const real* dL_dimage, real* d_means3D, real* d_means2D,
                          real* d_cov6, real* d_sh, real* d_colors, real* d_opacity) {
     const OrcParams* p = &o->prm;
-    int P = p->P, H = p->H, W = p->W;
+    int H = p->H, W = p->W;
     int gx = (W + TILE - 1) / TILE;
     memset(o->g_xy, 0, sizeof(real) * 2 * (size_t)o->NP);
     memset(o->g_conic, 0, sizeof(real) * 3 * (size_t)o->NP);
     memset(o->g_op, 0, sizeof(real) * (size_t)o->NP);
     memset(o->g_rgb, 0, sizeof(real) * 3 * (size_t)o->NP);
+    memset(o->g_xy_abs, 0, sizeof(real) * 2 * (size_t)o->NP);
+    memset(o->g_conic_abs, 0, sizeof(real) * 3 * (size_t)o->NP);
+    memset(o->g_op_abs, 0, sizeof(real) * (size_t)o->NP);
+    memset(o->g_rgb_abs, 0, sizeof(real) * 3 * (size_t)o->NP);
+    memset(o->g_z, 0, sizeof(real) * (size_t)o->NP);
+    memset(o->g_z_abs, 0, sizeof(real) * (size_t)o->NP);
     /* --- render backward: back-to-front replay per pixel --- */
     const int par = g_parallel_backward;
 #define ACC(dst, val) do { real v_ = (val); if (par) { _Pragma("omp atomic") dst += v_; } else dst += v_; } while (0)
+/* ACC + the same term's magnitude into the parallel _abs array */
+#define ACC2(arr, idx, val) do { real w_ = (val); ACC(o->arr[idx], w_); ACC(o->arr##_abs[idx], w_ < R(0) ? -w_ : w_); } while (0)
 #pragma omp parallel for schedule(dynamic, 64) if (par)
     for (int pix = 0; pix < H * W; ++pix) {
         int py = pix / W, px = pix % W;
@@ -778,8 +836,9 @@ EXPORT void orc_backward(Orc* o, const real* dL_dimage, real* d_means3D, real* d
         real dpix[3] = {dL_dimage[pix], dL_dimage[(size_t)H * W + pix], dL_dimage[(size_t)2 * H * W + pix]};
         real bg_dot = p->bg[0] * dpix[0] + p->bg[1] * dpix[1] + p->bg[2] * dpix[2];
         real accum[3] = {R(0), R(0), R(0)}, last_color[3] = {R(0), R(0), R(0)};
-        real last_alpha = R(0);
+        real last_alpha = R(0), accum_z = R(0), last_z = R(0);
         real pxf = (real)px, pyf = (real)py;
+        const real dz = o->depth_seed ? o->depth_seed[pix] : R(0);
         for (uint32_t k = last; k-- > 0;) {
             uint32_t id = o->vals[s + k];
             real dx = o->xy[2 * id] - pxf, dy = o->xy[2 * id + 1] - pyf;
@@ -797,7 +856,13 @@ EXPORT void orc_backward(Orc* o, const real* dL_dimage, real* d_means3D, real* d
                 accum[c] = last_alpha * last_color[c] + (R(1) - last_alpha) * accum[c];
                 last_color[c] = col;
                 dL_dalpha += (col - accum[c]) * dpix[c];
-                ACC(o->g_rgb[3 * id + c], dchannel_dcolor * dpix[c]);
+                ACC2(g_rgb, 3 * id + c, dchannel_dcolor * dpix[c]);
+            }
+            if (o->depth_seed) ACC2(g_z, id, dchannel_dcolor * dz);
+            if (o->depth_val) {
+                accum_z = last_alpha * last_z + (R(1) - last_alpha) * accum_z;
+                last_z = o->depth_val[id];
+                dL_dalpha += (last_z - accum_z) * dz;
             }
             dL_dalpha *= T;
             last_alpha = alpha;
@@ -806,14 +871,24 @@ EXPORT void orc_backward(Orc* o, const real* dL_dimage, real* d_means3D, real* d
             real gdx = G * dx, gdy = G * dy;
             real dG_ddelx = -gdx * co[0] - gdy * co[1];
             real dG_ddely = -gdy * co[2] - gdx * co[1];
-            ACC(o->g_xy[2 * id], dL_dG * dG_ddelx);
-            ACC(o->g_xy[2 * id + 1], dL_dG * dG_ddely);
-            ACC(o->g_conic[3 * id + 0], -R(0.5) * gdx * dx * dL_dG);
-            ACC(o->g_conic[3 * id + 1], -gdx * dy * dL_dG); /* true d/dB (no half factor) */
-            ACC(o->g_conic[3 * id + 2], -R(0.5) * gdy * dy * dL_dG);
-            ACC(o->g_op[id], G * dL_dalpha);
+            ACC2(g_xy, 2 * id, dL_dG * dG_ddelx);
+            ACC2(g_xy, 2 * id + 1, dL_dG * dG_ddely);
+            ACC2(g_conic, 3 * id + 0, -R(0.5) * gdx * dx * dL_dG);
+            ACC2(g_conic, 3 * id + 1, -gdx * dy * dL_dG); /* true d/dB (no half factor) */
+            ACC2(g_conic, 3 * id + 2, -R(0.5) * gdy * dy * dL_dG);
+            ACC2(g_op, id, G * dL_dalpha);
         }
     }
+    orc_backward_gaussians(o, d_means3D, d_means2D, d_cov6, d_sh, d_colors, d_opacity);
+}
+
+/* The per-Gaussian part of orc_backward alone: from the raster gradients in o (left by orc_backward's pixel loop, or given with
+ * orc_set_raster_grads) to the outputs of orc_backward.  Linear in the raster gradients.  Needs orc_forward's state. */
+EXPORT void orc_backward_gaussians(Orc* o, real* d_means3D, real* d_means2D, real* d_cov6, real* d_sh, real* d_colors,
+                                   real* d_opacity) {
+    const OrcParams* p = &o->prm;
+    int P = p->P, H = p->H, W = p->W;
+    const int par = g_parallel_backward;
     /* --- per-Gaussian backward --- */
 #pragma omp parallel for schedule(static, 1024) if (par)
     for (int i = 0; i < P; ++i) {

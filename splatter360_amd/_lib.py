@@ -36,7 +36,7 @@ FLAG_RAW_INPUTS = 1024
 FLAG_COOP_WALK = 2048
 DS_SECOND = 1        # s360_depth_smooth_*: flags
 DS_BILATERAL = 2
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class S360Params(C.Structure):
@@ -60,7 +60,7 @@ class S360RawInputs(C.Structure):
                 ("erp_convention", C.c_int32), ("scale_min", C.c_float), ("scale_max", C.c_float), ("eps", C.c_float)]
 
 
-EXPORTS = ("s360_forward_raw", "s360_backward_raw", "s360_backward_raw_tail", "s360_abi_version", "s360_error_string", "s360_layout", "s360_forward", "s360_forward_depth", "s360_forward_mse", "s360_backward", "s360_backward_split", "s360_backward_composite", "s360_backward_gaussians", "s360_unpack_gradients", "s360_reduce_unpack_gradients", "s360_sh_backward", "s360_pack_views", "s360_adapter_forward", "s360_adapter_backward", "s360_sh_rotation_blocks",
+EXPORTS = ("s360_forward_raw", "s360_backward_raw", "s360_backward_raw_tail", "s360_abi_version", "s360_error_string", "s360_layout", "s360_forward", "s360_forward_depth", "s360_forward_mse", "s360_backward", "s360_backward_split", "s360_backward_composite", "s360_backward_gaussians", "s360_backward_pair_records", "s360_unpack_gradients", "s360_reduce_unpack_gradients", "s360_sh_backward", "s360_pack_views", "s360_adapter_forward", "s360_adapter_backward", "s360_sh_rotation_blocks",
            "s360_cube2erp_forward", "s360_cube2erp_backward", "s360_count_contributions", "s360_count_backward_slots", "s360_profile_slots", "s360_profile_slot_name",
            "s360_profile_enable", "s360_profile_collect", "s360_ssim", "s360_erode", "s360_l1_sphere_forward",
            "s360_l1_sphere_backward", "s360_depth_metrics", "s360_psnr", "s360_cost_volume_forward", "s360_cost_volume_backward",
@@ -175,6 +175,8 @@ def lib() -> C.CDLL:
     l.s360_backward_composite.argtypes = [C.POINTER(S360Params), vp, vp, sz, vp, vp, vp, i32, vp, sz, vp]
     l.s360_backward_gaussians.restype = C.c_int
     l.s360_backward_gaussians.argtypes = [C.POINTER(S360Params), vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
+    l.s360_backward_pair_records.restype = C.c_int
+    l.s360_backward_pair_records.argtypes = [C.POINTER(S360Params), vp, sz, C.POINTER(sz)]
     l.s360_reduce_unpack_gradients.restype = C.c_int
     l.s360_reduce_unpack_gradients.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
     l.s360_unpack_gradients.restype = C.c_int

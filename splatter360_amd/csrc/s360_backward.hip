@@ -897,13 +897,14 @@ struct BwdCtx {
     size_t n_slots;       // segment slots of the forward workspace
 };
 
-static int bwd_ctx(const S360Params* prm, const void* workspace, size_t workspace_bytes, void* bwd_workspace,
-                   size_t bwd_workspace_bytes, BwdCtx& c) {
-    if (!prm || !workspace || !bwd_workspace) return S360_E_BADARG;
+// Pointer layout of the backward workspace (the one statement of it: bwd_ctx and s360_backward_pair_records both come here).
+// Host arithmetic only.
+static int bwd_pointers(const S360Params* prm, void* bwd_workspace, size_t bwd_workspace_bytes, BwdCtx& c) {
+    if (!prm || !bwd_workspace) return S360_E_BADARG;
     if (prm->flags & S360_FLAG_FORWARD_ONLY) return S360_E_BADARG;
     int rc = s360_layout(prm, &c.L);
     if (rc) return rc;
-    if (workspace_bytes < c.L.total_bytes || bwd_workspace_bytes < c.L.backward_bytes) return S360_E_WORKSPACE;
+    if (bwd_workspace_bytes < c.L.backward_bytes) return S360_E_WORKSPACE;
     KParams& kp = c.kp;
     kp.P = prm->P; kp.V = prm->V; kp.H = prm->H; kp.W = prm->W; kp.deg = s360_effective_degree(prm); kp.M = prm->M;
     kp.gx = (prm->W + 15) / 16; kp.gy = (prm->H + 15) / 16; kp.T = kp.gx * kp.gy;
@@ -929,6 +930,24 @@ static int bwd_ctx(const S360Params* prm, const void* workspace, size_t workspac
         char* e = (char*)(c.pairgrad + (size_t)kp.V * (kp.P > 0 ? kp.P : 1) * 3 + (size_t)(kp.P > 0 ? kp.P : 1));
         c.seg_list = (uint32_t*)(e + 256 - ((uintptr_t)e & 255)) + 32;   // 32 words in front of it hold the SegBwd record
     }
+    return S360_OK;
+}
+
+static int bwd_ctx(const S360Params* prm, const void* workspace, size_t workspace_bytes, void* bwd_workspace,
+                   size_t bwd_workspace_bytes, BwdCtx& c) {
+    if (!workspace) return S360_E_BADARG;
+    const int rc = bwd_pointers(prm, bwd_workspace, bwd_workspace_bytes, c);
+    if (rc) return rc;
+    return workspace_bytes < c.L.total_bytes ? S360_E_WORKSPACE : S360_OK;
+}
+
+extern "C" int s360_backward_pair_records(const S360Params* prm, const void* bwd_workspace, size_t bwd_workspace_bytes,
+                                          size_t* byte_offset) {
+    if (!byte_offset) return S360_E_BADARG;
+    BwdCtx c;
+    const int rc = bwd_pointers(prm, const_cast<void*>(bwd_workspace), bwd_workspace_bytes, c);   // dereferences nothing
+    if (rc) return rc;
+    *byte_offset = (size_t)((const char*)c.pairgrad - (const char*)bwd_workspace);
     return S360_OK;
 }
 

@@ -47,10 +47,41 @@ def test_bad_arguments_are_rejected_before_any_gpu_work():
     assert lib.s360_forward(C.byref(ok), None, None, None, None, None, None, None, None, None, 0, None) == -1
     assert lib.s360_cube2erp_forward(None, None, None, 3, 64, 128, 256, None, None, None) == -1
     # ABI v24: the stitch's adjoint takes the grid's inverse (plan offsets + entries); a missing plan is a bad argument
-    assert _lib.ABI_VERSION == 24
+    assert _lib.ABI_VERSION == 25
     assert lib.s360_cube2erp_backward(None, None, None, None, None, 3, 64, 128, 256, None, None, None) == -1
     with pytest.raises(RuntimeError):
         _lib.check(-4, "x")
+
+
+@pytest.mark.parametrize("flags", [_lib.FLAG_SHARED_CAMPOS, _lib.FLAG_SHARED_CAMPOS | _lib.FLAG_ATOMIC_GRADS,
+                                   _lib.FLAG_SHARED_CAMPOS | _lib.FLAG_LEAN_LISTS | _lib.FLAG_SPLIT_LISTS])
+def test_pair_records_accessor_is_aligned_fits_and_rejects_bad_arguments(flags):
+    """s360_backward_pair_records (ABI v25): host arithmetic on an address it never dereferences, so any base will do.  The records
+    start on a 256-byte boundary of the address and end inside backward_bytes, in the default and in the atomic layout."""
+    lib = _lib.lib()
+    prm = _lib.S360Params(P=1000, V=6, H=64, W=80, sh_degree=4, M=25, flags=flags, max_instances=5000)
+    lay = _lib.layout(prm)
+    offs = set()
+    for base in (1 << 20, (1 << 20) + 16, (1 << 20) + 255):
+        off = C.c_size_t(123)
+        assert lib.s360_backward_pair_records(C.byref(prm), C.c_void_p(base), lay.backward_bytes, C.byref(off)) == 0
+        assert (base + off.value) % 256 == 0
+        assert off.value + prm.V * prm.P * 48 <= lay.backward_bytes
+        offs.add(off.value)
+    assert len(offs) == 3                                   # the offset belongs to the pointer it was asked for
+    atomic = bool(flags & _lib.FLAG_ATOMIC_GRADS)
+    assert (min(offs) < 5000 * 4 * 48) == atomic            # default layout: behind the [cap] x 4 partial records; atomic: no such block
+    off = C.c_size_t(123)
+    base = C.c_void_p(1 << 20)
+    assert lib.s360_backward_pair_records(None, base, lay.backward_bytes, C.byref(off)) == -1
+    assert lib.s360_backward_pair_records(C.byref(prm), None, lay.backward_bytes, C.byref(off)) == -1
+    assert lib.s360_backward_pair_records(C.byref(prm), base, lay.backward_bytes, None) == -1
+    assert lib.s360_backward_pair_records(C.byref(prm), base, lay.backward_bytes - 1, C.byref(off)) == -2
+    fwd_only = _lib.S360Params(P=1000, V=6, H=64, W=80, sh_degree=4, M=25, flags=flags | _lib.FLAG_FORWARD_ONLY, max_instances=5000)
+    assert lib.s360_backward_pair_records(C.byref(fwd_only), base, lay.backward_bytes, C.byref(off)) == -1
+    bad_v = _lib.S360Params(P=1000, V=9, H=64, W=80, sh_degree=4, M=25, flags=flags, max_instances=5000)
+    assert lib.s360_backward_pair_records(C.byref(bad_v), base, lay.backward_bytes, C.byref(off)) == -1
+    assert off.value == 123                                 # a refused call writes nothing
 
 
 def test_rasterizer_refuses_cpu_tensors():

@@ -79,7 +79,7 @@ def test_abi_has_the_cost_volume_entry_points_and_they_reject_bad_arguments():
     lib = _lib.lib()
     for name in ("s360_cost_volume_forward", "s360_cost_volume_backward", "s360_cost_volume_warp"):
         assert name in _lib.EXPORTS and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 24 and "s360_cost_volume.hip" in _lib.SOURCES
+    assert _lib.ABI_VERSION == 25 and "s360_cost_volume.hip" in _lib.SOURCES
     n = C.c_size_t(0)
     dims = (2, 2, 1, 128, 128, 256, 128)
     # the workspace query: a null workspace with a size pointer; channels-last copies only, nothing with C * D elements

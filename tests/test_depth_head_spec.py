@@ -49,7 +49,7 @@ def test_abi_has_the_depth_head_entry_points_and_they_reject_bad_arguments():
     for name in NAMES:
         assert name in _lib.EXPORTS and hasattr(lib, name) and re.search(rf"\bint\s+{name}\s*\(", header)
     assert "s360_depth_head.hip" in _lib.SOURCES and (ROOT / "splatter360_amd" / "csrc" / "s360_depth_head.hip").exists()
-    assert _lib.ABI_VERSION == 24 and lib.s360_abi_version() == 24                  # additive: the version stays
+    assert _lib.ABI_VERSION == 25 and lib.s360_abi_version() == 25                  # additive: the version stays
     p = C.c_void_p(16)                                                              # never dereferenced: every call below is refused
     # null required pointers and non-positive sizes come back as -1 before any GPU work
     assert lib.s360_depth_head_forward(None, None, 2, 128, 128, 256, None, None, None, None, None) == -1

@@ -58,7 +58,7 @@ def test_entry_points_are_exported_declared_and_built_from_the_new_source():
         assert hasattr(_lib.lib(), name)
     header = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "s360.h").read_text(), flags=re.S)
     assert re.search(r"\bint\s+s360_depth_smooth_forward\s*\(", header) and re.search(r"\bint\s+s360_depth_smooth_backward\s*\(", header)
-    assert _lib.ABI_VERSION == 24 and "#define S360_ABI_VERSION 24" in (ROOT / "include" / "s360.h").read_text()
+    assert _lib.ABI_VERSION == 25 and "#define S360_ABI_VERSION 25" in (ROOT / "include" / "s360.h").read_text()
     assert "s360_depth_smooth.hip" in _lib.SOURCES and (ROOT / "splatter360_amd" / "csrc" / "s360_depth_smooth.hip").is_file()
 
 

@@ -80,7 +80,7 @@ def test_abi_has_the_depth_tail_entry_points_and_they_reject_bad_arguments():
     for name in NAMES:
         assert name in _lib.EXPORTS and hasattr(lib, name) and re.search(rf"\bint\s+{name}\s*\(", header)
     assert "s360_depth_tail.hip" in _lib.SOURCES and (ROOT / "splatter360_amd" / "csrc" / "s360_depth_tail.hip").exists()
-    assert _lib.ABI_VERSION == 24 and lib.s360_abi_version() == 24                  # additive: the version stays
+    assert _lib.ABI_VERSION == 25 and lib.s360_abi_version() == 25                  # additive: the version stays
     p = C.c_void_p(16)                                                              # never dereferenced: every call below is refused
     nan, inf = float("nan"), float("inf")
     up_f, up_b = lib.s360_upsample_forward, lib.s360_upsample_backward

@@ -144,7 +144,7 @@ def test_tables_in_the_header_are_the_generators(tmp_path):
 def test_abi_size_query_and_bad_arguments():
     from splatter360_amd import _lib
     lib = _lib.lib()
-    assert lib.s360_abi_version() == 24
+    assert lib.s360_abi_version() == 25
     OK, BADARG, UNSUPPORTED = 0, -1, -4
     n = C.c_size_t(0)
     assert lib.s360_depth_colormap(None, 18, 256, 256, 65536, None, None, None, None, C.byref(n), None) == OK and n.value > 0

@@ -203,7 +203,7 @@ def test_module_buffers_are_not_persistent_and_cpu_tensors_raise():
 
 def test_abi_entries_reject_null_pointers_and_bad_sizes():
     lib = _lib.lib()
-    assert {"s360_erp2cube_forward", "s360_erp2cube_backward"} <= set(_lib.EXPORTS) and _lib.ABI_VERSION == 24
+    assert {"s360_erp2cube_forward", "s360_erp2cube_backward"} <= set(_lib.EXPORTS) and _lib.ABI_VERSION == 25
     bad = -1                                                           # S360_E_BADARG
     assert lib.s360_erp2cube_forward(None, None, None, None, 1, 3, 12, 24, 5, 0, 0, 0, None, None, None) == bad
     assert lib.s360_erp2cube_backward(None, None, None, None, None, None, 1, 3, 12, 24, 5, 0, 0, None, None, None) == bad

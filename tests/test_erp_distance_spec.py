@@ -152,7 +152,7 @@ def test_entry_points_are_declared_exported_and_additive():
     lib = _lib.lib()
     for name in NAMES:
         assert name in _lib.EXPORTS and re.search(rf"\bint\s+{name}\s*\(", header) and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 24 and lib.s360_abi_version() == 24 and "#define S360_ABI_VERSION 24" in header
+    assert _lib.ABI_VERSION == 25 and lib.s360_abi_version() == 25 and "#define S360_ABI_VERSION 25" in header
     assert "#define S360_D2D_REFERENCE 0" in header and "#define S360_D2D_PIXEL 1" in header
     assert stitch.DISTANCE_CONVENTIONS == {"reference": 0, "pixel": 1}
 
