@@ -755,8 +755,9 @@ static void backward_one_sph(Orc* o, int i, real* dm, real* dm2, real* dc, real*
         dt[0] += drc * (t0 / g.rho);
         dt[2] += drc * (t2 / g.rho);
     }
-    /* centre: (u, v) with the TRUE rho */
-    const real iu = c0 / g.rho2, iv = c1 / (r2 * g.rho);
+    /* centre: (u, v) with the TRUE rho.  Exactly on the axis (rho == 0) the azimuth is the constant s_atan2(0, 0) = 0 and the
+     * direction of d(phi)/d(t0, t2) does not exist: both factors are 0 there instead of inf (inf x 0 would make dL/dmean NaN) */
+    const real iu = g.rho2 > R(0) ? c0 / g.rho2 : R(0), iv = g.rho > R(0) ? c1 / (r2 * g.rho) : R(0);
     dt[0] += gxy[0] * (iu * t2) + gxy[1] * (-(iv * t0 * t1));
     dt[1] += gxy[1] * (c1 * g.rho / r2);
     dt[2] += gxy[0] * (-(iu * t0)) + gxy[1] * (-(iv * t2 * t1));

@@ -265,7 +265,9 @@ __device__ __forceinline__ GaussBwd gaussian_bwd(
                     dt0 += drc * (t0 / gs.rho);
                     dt2 += drc * (t2 / gs.rho);
                 }
-                const float iu = c0 / gs.rho2, iv = c1 / (r2 * gs.rho);   // centre: (u, v) with the TRUE rho; pixel units
+                // centre: (u, v) with the TRUE rho; pixel units.  On the axis (rho == 0) both factors are 0, as in the oracle: inf x 0
+                // would make dL/dmean NaN
+                const float iu = gs.rho2 > 0.0f ? c0 / gs.rho2 : 0.0f, iv = gs.rho > 0.0f ? c1 / (r2 * gs.rho) : 0.0f;
                 dt0 += gx_ * (iu * t2) + gy_ * (-(iv * t0 * t1));
                 dt1 += gy_ * (c1 * gs.rho / r2);
                 dt2 += gx_ * (-(iu * t0)) + gy_ * (-(iv * t2 * t1));

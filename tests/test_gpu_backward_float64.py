@@ -22,7 +22,8 @@ depth-value chain in numpy; the condition D of each output element comes from ni
 invisible ones, the lower triangle of a [P,3,3] covariance gradient and SH beyond the degree have D = 0 and must be exactly 0.
 Output buffers start as NaN, so an element nobody writes fails.
 
-Out of scope: S360_FLAG_SPHERICAL (geo_sph) and the raw-input backward (s360_backward_raw*).
+Elsewhere: S360_FLAG_SPHERICAL (geo_sph, the pole clamp, the seam ghost) in tests/test_gpu_spherical_float64.py, the raw-input path
+(s360_forward_raw, s360_backward_raw*) in tests/test_gpu_raw_float64.py; both share tests/backward_reference.py with this file.
 
 Measured on an MI355X (kernel / float32 oracle, units of 2^-24; worst, mean):
   composite, per pair [pairgrad64]        group worst kernel/oracle32  mean kernel/oracle32

@@ -236,3 +236,82 @@ def test_the_chain_reference_is_linear_and_its_condition_bounds_it():
     assert (D["means"][~vo.visible.any(0)] == 0).all() and (~vo.visible.any(0)).any()
     assert not np.array_equal(plain["means"], want["means"])                          # the depth column is there
     assert vo.S[0]["scale"] == pytest.approx(10.0)                                    # near = 0.1: the folds are not 1
+
+
+# ------------------------------------------------------------------------------------- the raw-tail reference (tests/test_gpu_raw_float64.py)
+def _tiny_raw_case(seed=0, v=2, h=2, w=3, n_groups=2):
+    import torch
+    from oracle import adapter_ref
+    from splatter360_amd import synthetic
+    rng = np.random.default_rng(seed)
+    gv = h * w
+    ext = np.tile(np.eye(4, dtype=np.float32), (v, 1, 1))
+    ext[:, :3, :3] = synthetic._random_rotations(rng, v)
+    ext[:, :3, 3] = rng.uniform(-1, 1, (v, 3))
+    dep = np.exp(rng.uniform(np.log(0.5), np.log(8.0), (v, gv))).astype(np.float32)
+    raw = rng.standard_normal((v, gv, 82)).astype(np.float32)
+    rot = adapter_ref.wigner_blocks(ext[:, :3, :3], 25).astype(np.float32)
+    views = br.cube_views(n_groups)
+    rgb = rng.standard_normal((n_groups, v * gv, 4)).astype(np.float32)
+    w_ = (np.arange(v * gv)[None, :] + np.arange(n_groups)[:, None]) % (n_groups + 1) - 1          # -1, 0, 1, ... : some groups see nothing
+    rgb[..., 3] = w_.astype(np.int32).view(np.float32)
+    t = torch.tensor
+    return dict(ext=t(ext), dep=t(dep), raw=t(raw), rot=t(rot), views=views, d_cov6=rng.standard_normal((v * gv, 6)).astype(np.float32),
+                d_rgb=rgb, d_means=rng.standard_normal((v * gv, 3)).astype(np.float32), hw=(h, w), v=v, gv=gv)
+
+
+def test_the_raw_tail_reference_agrees_with_central_differences():
+    """Float64 autograd of backward_reference.raw_tail_reference against central differences of the scalar it differentiates,
+    <cov6, d_cov6> + <harmonics, g_harm> + <means, d_means>, at a tiny shape, with the SH rotation and differentiable means."""
+    import torch
+    from oracle import adapter_ref
+    c = _tiny_raw_case()
+    tt = torch.float64
+    means32 = adapter_ref.adapter_tail_torch(c["ext"], c["dep"], c["dep"], c["raw"], c["hw"], 0.5, 15.0, sh_rotation=c["rot"]).means.reshape(-1, 3)
+    ref = br.raw_tail_reference(tt, c["ext"], c["dep"], c["raw"], c["rot"], means32, c["views"], c["d_cov6"], c["d_rgb"], c["d_means"], c["hw"])
+    g_harm = ref.g_harm
+    r_, c_ = torch.triu_indices(3, 3)
+
+    def scalar(dep, raw):
+        o = adapter_ref.adapter_tail_torch(c["ext"].to(tt), dep, torch.zeros_like(dep), raw, c["hw"], 0.5, 15.0, sh_rotation=c["rot"].to(tt),
+                                           differentiable_means=True)
+        return float((o.covariances[:, :, r_, c_] * torch.tensor(c["d_cov6"]).to(tt).reshape(c["v"], c["gv"], 6)).sum() + (o.harmonics * g_harm).sum()
+                     + (o.means * torch.tensor(c["d_means"]).to(tt).reshape(c["v"], c["gv"], 3)).sum())
+
+    rng = np.random.default_rng(1)
+    dep0, raw0 = c["dep"].to(tt), c["raw"].to(tt)
+    eps = 1e-6
+    noise = 8 * 2.0 ** -53 * abs(scalar(dep0, raw0)) / eps                  # the rounding of the two scalars in the difference quotient
+    for which, grad, base in (("dep", ref.d_dep, dep0), ("raw", ref.d_raw, raw0)):
+        idx = rng.choice(base.numel(), size=6 if which == "dep" else 40, replace=False)
+        for i in idx:
+            hi, lo = base.clone(), base.clone()
+            hi.view(-1)[i] += eps
+            lo.view(-1)[i] -= eps
+            num = (scalar(hi, raw0) - scalar(lo, raw0)) / (2 * eps) if which == "dep" else (scalar(dep0, hi) - scalar(dep0, lo)) / (2 * eps)
+            ana = float(grad.reshape(-1)[i])
+            assert abs(num - ana) <= 1e-6 * max(abs(num), abs(ana)) + noise, (which, int(i), num, ana, noise)
+    assert float(ref.d_raw[..., 7:].abs().max()) > 0 and float(ref.d_raw[..., :7].abs().max()) > 0
+    # a group whose .w is -1 contributes nothing: zeroing its dRGB changes nothing
+    rgb2 = c["d_rgb"].copy()
+    rgb2[..., :3][rgb2[..., 3].view(np.int32) < 0] = 0
+    assert torch.equal(br.raw_rank1_harmonics(tt, means32, c["views"], rgb2), g_harm.reshape(-1, 3, 25)) and (c["d_rgb"][..., 3].view(np.int32) < 0).any()
+
+
+def test_the_rank_one_harmonics_gradient_is_the_oracles_dL_dSH():
+    """One view, float64: g_harm[c][k] = Y_k(dir) x (the clamp-masked dL/dRGB) equals the oracle's dL/dSH to 1e-12 of its largest entry."""
+    import torch
+    sc = br.scene("small")
+    b, f = sc["b64"], sc["f64"]
+    P = sc["means"].shape[0]
+    vis = f["radii"] > 0
+    rgb = np.zeros((1, P, 4), np.float32)
+    masked = np.where(f["clamped"].astype(bool), 0.0, b["raster_rgb"])
+    # the cotangent must be float32 (the kernels' d_rgb_sum): feed the oracle's second loop the very same rounded numbers
+    rgb[0, :, :3] = masked
+    rgb[0, :, 3] = np.where(vis, 0, -1).astype(np.int32).view(np.float32)
+    want = sc["orc64"].backward_gaussians(b["raster_xy_pix"], b["raster_conic"], b["raster_opacity"], rgb[0, :, :3].astype(np.float64))["shs"]
+    got = br.raw_rank1_harmonics(torch.float64, sc["means"], sc["views"], rgb).numpy().transpose(0, 2, 1)            # [P,25,3]
+    assert float(sc["views"][0, 40]) == 1.0 and vis.sum() > 30
+    assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max() and np.abs(want).max() > 0
+    assert (got[~vis] == 0).all()
