@@ -934,6 +934,48 @@ int s360_prep_image(const float* image, int32_t batch, int32_t channels, int32_t
 int s360_error_map(const float* a, const float* b, int32_t height, int32_t width, uint8_t* bytes_out, void* stream);
 
 /*
+ * The multi-view transformer's single-head (shifted-)window attention, forward and backward (the reference's
+ * single_head_split_window_attention and single_head_full_attention, src/model/encoder/backbone/multiview_transformer.py:8-16,
+ * :60-210): roll, window split, q k^T / sqrt(C), shifted-window mask, softmax, times v, merge and roll back as ONE kernel; no
+ * [B K^2, Lw, Lk] score tensor and no mask tensor is formed, forward or backward.
+ *   q[batch, L, channels], L = height * width tokens in (y, x) order; k, v[batch, M, L, channels] with M = max(partners, 1):
+ *   partners = 0 is the reference's same-shape branch (k.dim() == 3), partners >= 1 its multi-view branch, whose window keys are
+ *   ordered j = p * M + u (window token p, view u fastest); partners 0 and 1 index identically.
+ *   K = num_splits must divide height and width; wh = height / K, ww = width / K, Lw = wh * ww, Lk = Lw * M.  Token p = i * ww + j
+ *   of window (wy, wx) sits at the ROLLED position ry = wy * wh + i, rx = wx * ww + j and is the original token
+ *   ((ry + sh) mod height) * width + (rx + sw) mod width, sh = wh / 2, sw = ww / 2 if with_shift, else 0.
+ *   score = float32((q . k) / sqrt(channels)) + mask, q . k summed in float64 over float32 fma chains of 8 channels.  With with_shift, mask = 0 where region(query) == region(key) and the
+ *   FINITE -100.0f elsewhere (the reference's value: a masked key keeps its weight), region(ry, rx) = 3 r(ry, height, wh, sh) +
+ *   r(rx, width, ww, sw), r(i, n, win, s) = [i >= n - win] + [i >= n - s].  mask_rule S360_WA_MASK_REFERENCE gives key j the region
+ *   of window token j mod Lw (the reference applies its [K^2, Lw, Lw] mask as attn_mask.repeat(b, 1, m), which tiles it);
+ *   S360_WA_MASK_ALIGNED gives it the region of its own token j / M.  The two coincide for M = 1 and without shift.
+ *   out[batch, L, channels] = softmax over the window's keys times v, written at the query's original token; lse[batch, L]
+ *   FLOAT64 = max + log(sum exp(score - max)) of the query's row (float32 running maximum, float64 running sum).
+ * Products run on v_mfma_f32_32x32x2_f32: the scores and dP as float32 fma chains of 8 channels whose results are added in float64
+ * and rounded once, the products over the keys as exact float32 fma chains (in tiles of 32); exp is the accurate float32 one.
+ * s360_window_attention_backward takes the forward's lse and g_out[batch, L, channels] and writes g_q[batch, L, channels],
+ * g_k and g_v[batch, M, L, channels]; any of the three may be null and its part is skipped.  Probabilities are recomputed as
+ * exp(score - lse), dS = P (dP - Delta).  delta[batch, L] FLOAT64 is scratch the call fills, when g_q or g_k is asked for,
+ * with Delta = sum_k P dP per query — from the dP values dS subtracts it from, as torch's softmax backward does (at rows with
+ * few effective keys the rounding of dP cancels; rowsum(g_out * out) is the same number with independent rounding, and the
+ * forward's out is therefore not an argument).  The pass owned by query tiles runs first (Delta, then g_q), the pass owned by
+ * key tiles second (g_k / g_v): every output element is written once, by one wave, in a fixed order — no atomics,
+ * bit-identical from run to run and across streams.
+ * No host synchronisation, no allocation.  channels outside {32, 64, 96, 128}: S360_E_UNSUPPORTED.  Null required pointers,
+ * pointers not 16-byte aligned, sizes < 1, num_splits not dividing height and width, an unknown mask_rule, or 2^31 or more rows
+ * or workgroups: S360_E_BADARG before any GPU work.
+ */
+#define S360_WA_MASK_REFERENCE 0
+#define S360_WA_MASK_ALIGNED 1
+int s360_window_attention_forward(const float* q, const float* k, const float* v, int32_t batch, int32_t partners, int32_t height,
+                                  int32_t width, int32_t channels, int32_t num_splits, int32_t with_shift, int32_t mask_rule,
+                                  float* out, double* lse, void* stream);
+int s360_window_attention_backward(const float* q, const float* k, const float* v, const double* lse, const float* g_out,
+                                   int32_t batch, int32_t partners, int32_t height, int32_t width, int32_t channels,
+                                   int32_t num_splits, int32_t with_shift, int32_t mask_rule, double* delta, float* g_q, float* g_k,
+                                   float* g_v, void* stream);
+
+/*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an
  * un-synchronised wall clock, src/misc/benchmarker.py:15-33).  While enabled, every kernel group
  * is bracketed by HIP events recorded on the launch stream; s360_profile_collect() synchronises

@@ -1,0 +1,560 @@
+// s360_window_attention.hip — the multi-view transformer's single-head (shifted-)window attention, forward and backward (the
+// reference's single_head_split_window_attention and single_head_full_attention,
+// src/model/encoder/backbone/multiview_transformer.py:8-16, :60-210).  gfx950 only.
+//
+//   tokens   q[B, L, C], k, v[B, M, L, C], L = H W in (y, x) order; K = num_splits, wh = H / K, ww = W / K, Lw = wh ww, Lk = Lw M
+//   window   (wy, wx) holds the ROLLED positions ry = wy wh + i, rx = wx ww + j; its token p = i ww + j is the original token
+//            ((ry + sh) mod H) W + (rx + sw) mod W, sh = wh / 2, sw = ww / 2 with shift, else 0 (roll by -shift, split); the
+//            output row goes back to that token (merge, roll back).  Key j of the window is token p = j / M of partner view
+//            u = j mod M.
+//   score    float32((q . k) / sqrt(C)) + mask, q . k summed in float64 over float32 chunks of 8 channels (wa_dot); with shift,
+//            mask = 0 where region(query) == region(key), else -100.0 (finite,
+//            as the reference's), region(ry, rx) = 3 r(ry, H, wh, sh) + r(rx, W, ww, sw), r(i, n, win, s) = [i >= n - win] +
+//            [i >= n - s]; the key's region is that of window token j mod Lw (rule 0, the reference's tiled mask) or j / M (rule 1)
+//   out      softmax over the window's keys, times v; lse = max + log(sum) per query, float64
+//
+// Every product runs on v_mfma_f32_32x32x2_f32 (exact f32 fma chains; the score and dP chains are 8 channels long and are
+// added in float64, wa_dot).  A wave owns 32 rows ("owner": queries in the forward
+// and the g_q pass, keys in the g_k / g_v pass) and walks the other side in tiles of 32; a workgroup is four waves on four
+// consecutive owner tiles of ONE window, so its waves walk the same tiles and share their (row, region) table in LDS.
+// Orientation: the score tile is computed with the WALKED index on the accumulator's rows (registers) and the owner on the
+// lanes — forward S^T = K Q^T — so that (a) softmax statistics, lse and Delta of the owner are per lane, one exchange with
+// lane ^ 32 completes a row reduction, and (b) the tile is, register by register, the B operand of the second product, which
+// sums over the walked index: O^T = V^T P^T with A = one value of V per lane.  No lane movement, no LDS for the tile.
+// The contraction order over channels is free (it only has to match between the two operands): lane half h of a row holds
+// channels [h C/2, (h+1) C/2), read with dwordx4 loads (one per chunk); output channel slot i of block cb is channel (C/32) i + cb, so the 16
+// rows a lane holds of an output tile are C/32 consecutive channels each: vector loads of V and vector stores of the result.
+// Gathered rows (roll, split) are read straight from [B, L, C]; ragged last tiles are masked by index.
+// No atomics: each output row is written by one wave.  Backward: P = exp(score - lse) recomputed (float64 difference, float32
+// exp), dS = P (dP - Delta), Delta = sum_k P dP (float64 sum) from a first sweep of the query-owned pass.
+#include "s360_device.h"
+
+namespace s360 {
+
+typedef float wa_f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int WA_T = 32;                                      // rows of an MFMA tile
+constexpr int WA_WAVES = S360_BLOCK / S360_WAVE;              // owner tiles of a workgroup
+constexpr int WA_ROWS = WA_T * WA_WAVES;
+
+struct WAArgs {
+    const float* q;
+    const float* k;
+    const float* v;
+    int B, M, H, W, C, K, wh, ww, sh, sw, Lw, Lk, L;
+    int shift, aligned;
+    float scale;                                              // float32(sqrt(C)): divides g_q and g_k
+    double inv_scale;                                         // 1 / sqrt(C): multiplies the float64 score sums
+};
+
+// original token and mask region of window token p of window (wy, wx)
+__device__ __forceinline__ void wa_token(const WAArgs& a, int wy, int wx, int p, int& tok, int& region) {
+    const int i = p / a.ww, j = p - i * a.ww;
+    const int ry = wy * a.wh + i, rx = wx * a.ww + j;
+    int oy = ry + a.sh, ox = rx + a.sw;
+    if (oy >= a.H) oy -= a.H;
+    if (ox >= a.W) ox -= a.W;
+    tok = oy * a.W + ox;
+    region = 3 * ((ry >= a.H - a.wh) + (ry >= a.H - a.sh)) + (rx >= a.W - a.ww) + (rx >= a.W - a.sw);
+}
+
+// row of k / v (in units of C floats) and mask region of window key j < Lk of batch element b
+__device__ __forceinline__ void wa_key(const WAArgs& a, int b, int wy, int wx, int j, int& row, int& region) {
+    const int p = j / a.M, u = j - p * a.M;
+    int tok, reg;
+    wa_token(a, wy, wx, p, tok, reg);
+    row = (b * a.M + u) * a.L + tok;
+    region = reg;
+    if (!a.aligned && a.M > 1) {
+        int t2;
+        wa_token(a, wy, wx, j % a.Lw, t2, region);
+    }
+}
+
+// N4 dwordx4 loads of 4 N4 consecutive floats (p 16-byte aligned), or zeros for p == null
+template <int N4>
+__device__ __forceinline__ void wa_load(const float* p, float* x) {
+#pragma unroll
+    for (int i = 0; i < N4; ++i) {
+        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (p) t = reinterpret_cast<const float4*>(p)[i];
+        x[4 * i] = t.x; x[4 * i + 1] = t.y; x[4 * i + 2] = t.z; x[4 * i + 3] = t.w;
+    }
+}
+
+// NCB consecutive floats (p aligned to NCB floats for NCB 2 and 4), or zeros
+template <int NCB>
+__device__ __forceinline__ void wa_load_c(const float* p, float* x) {
+#pragma unroll
+    for (int i = 0; i < NCB; ++i) x[i] = 0.f;
+    if (!p) return;
+    if constexpr (NCB == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
+    } else if constexpr (NCB == 2) {
+        const float2 t = *reinterpret_cast<const float2*>(p);
+        x[0] = t.x; x[1] = t.y;
+    } else {
+#pragma unroll
+        for (int i = 0; i < NCB; ++i) x[i] = p[i];
+    }
+}
+
+template <int NCB>
+__device__ __forceinline__ void wa_store_c(float* p, const float* x) {
+    if constexpr (NCB == 4) *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
+    else if constexpr (NCB == 2) *reinterpret_cast<float2*>(p) = make_float2(x[0], x[1]);
+    else {
+#pragma unroll
+        for (int i = 0; i < NCB; ++i) p[i] = x[i];
+    }
+}
+
+// row of the accumulator tile that register r of a lane of half hf holds
+__device__ __forceinline__ int wa_acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
+
+// tile = float32(mul * sum over the lane's HC channels of A-row x B-row) (the two halves of a wave cover all C channels).  The
+// sum runs in chunks of WA_CHUNK MFMA steps (2 WA_CHUNK channels): a chunk is one float32 fma chain from zero, whose partial
+// sums stay small, and the chunks are added in FLOAT64; the result is rounded once.  One chain over all C channels rounds at
+// the full size of the sum at every step; in its largest elements it misses the accuracy rule of the tests, and so did four
+// float32 chains added pairwise.  The forward and both backward passes form every score and every dP through this one
+// arithmetic (wa_dot, wa_dot_mem), so the recomputed tiles are the forward's bit for bit.
+constexpr int WA_CHUNK = 4;
+__device__ __forceinline__ float4 wa_ld4(const float* p, int chunk) {
+    return p ? reinterpret_cast<const float4*>(p)[chunk] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+__device__ __forceinline__ wa_f32x16 wa_round(const double* sum, double mul) {
+    wa_f32x16 out;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) out[r] = (float)(sum[r] * mul);
+    return out;
+}
+
+__device__ __forceinline__ wa_f32x16 wa_chunk(const float4& x, const float4& y, float z) {
+    wa_f32x16 t;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t[r] = z;
+    t = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x, y.x, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x2f32(x.y, y.y, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x2f32(x.z, y.z, t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x2f32(x.w, y.w, t, 0, 0, 0);
+    return t;
+}
+
+// The forward's form: the walked row `arow` (null: zeros) is read chunk by chunk, the owner's row `b` is held in HC registers.
+// Left to itself the compiler issues the MFMAs of all chunks first and keeps 16 tiles alive (256 accumulator registers and
+// 0.5 KB of scratch per lane, measured); so each chunk's zero tile passes an empty asm statement that depends on the sums as
+// they stand (chunks up to c - 2 added): at most three tiles are live, and the float64 adds of chunk c - 1 run under the
+// MFMAs of chunk c.
+template <int HC>
+__device__ __forceinline__ wa_f32x16 wa_dot(const float* arow, const float* b, double mul) {
+    static_assert(WA_CHUNK == 4 && HC % WA_CHUNK == 0, "a chunk is one dwordx4 of a row");
+    double sum[16];
+    wa_f32x16 prev;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sum[r] = 0.0, prev[r] = 0.f;
+#pragma unroll
+    for (int c = 0; c < HC / WA_CHUNK; ++c) {
+        float z = 0.f;
+        asm volatile("" : "+v"(z) : "v"(sum[15]));
+        const wa_f32x16 t = wa_chunk(wa_ld4(arow, c), make_float4(b[4 * c], b[4 * c + 1], b[4 * c + 2], b[4 * c + 3]), z);
+        if (c > 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sum[r] += (double)prev[r];
+        }
+        prev = t;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sum[r] += (double)prev[r];
+    return wa_round(sum, mul);
+}
+
+// The backward passes' form: both rows are read from memory chunk by chunk (either may be null: zeros) — their two products,
+// the float64 sums and two or four output tiles do not fit the 256 VALU-visible registers with the owner's rows resident
+// (measured: 0.8 to 1.5 KB of scratch per lane); the owner's rows are the same every tile and stay in cache.  A real loop,
+// not an unrolled one, with the loads three chunks (768 MFMA cycles) in front of their use in rotating registers.
+template <int HC>
+__device__ __forceinline__ wa_f32x16 wa_dot_mem(const float* arow, const float* brow, double mul) {
+    constexpr int NCH = HC / WA_CHUNK;
+    static_assert(WA_CHUNK == 4 && HC % WA_CHUNK == 0 && NCH >= 3, "a chunk is one dwordx4 of a row");
+    double sum[16];
+    wa_f32x16 prev;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sum[r] = 0.0, prev[r] = 0.f;
+    float4 a0 = wa_ld4(arow, 0), b0 = wa_ld4(brow, 0), a1 = wa_ld4(arow, 1), b1 = wa_ld4(brow, 1), a2 = wa_ld4(arow, 2), b2 = wa_ld4(brow, 2);
+#pragma unroll 1
+    for (int c = 0; c < NCH; ++c) {
+        const bool more = c + 3 < NCH;
+        const float4 a3 = wa_ld4(more ? arow : nullptr, c + 3), b3 = wa_ld4(more ? brow : nullptr, c + 3);
+        const wa_f32x16 t = wa_chunk(a0, b0, 0.f);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sum[r] += (double)prev[r];      // chunk c - 1 (zeros at c = 0), under the MFMAs of chunk c
+        prev = t;
+        a0 = a1; b0 = b1; a1 = a2; b1 = b2; a2 = a3; b2 = b3;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sum[r] += (double)prev[r];
+    return wa_round(sum, mul);
+}
+
+// block decomposition shared by the three kernels: owner block ob of window (wy, wx) of batch element b
+struct WABlock { int ob, b, wy, wx; };
+__device__ __forceinline__ WABlock wa_block(const WAArgs& a, int owner_rows) {
+    const int oblocks = (owner_rows + WA_ROWS - 1) / WA_ROWS;
+    int blk = blockIdx.x;
+    WABlock w;
+    w.ob = blk % oblocks; blk /= oblocks;
+    const int win = blk % (a.K * a.K);
+    w.b = blk / (a.K * a.K);
+    w.wy = win / a.K; w.wx = win - w.wy * a.K;
+    return w;
+}
+
+// Forward.  Owner: queries.  Walks the window's key tiles with a running maximum (float32: it is one of the scores) and a
+// running sum (float64).
+template <int NCB>
+__global__ __launch_bounds__(S360_BLOCK) void k_wa_forward(WAArgs a, float* __restrict__ out, double* __restrict__ lse) {
+    constexpr int HC = 16 * NCB;
+    __shared__ int s_row[2][WA_T], s_reg[2][WA_T];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const WABlock w = wa_block(a, a.Lw);
+    const int qp = w.ob * WA_ROWS + wave * WA_T + l31;
+    const bool qvalid = qp < a.Lw;
+    int qtok = 0, qreg = 0;
+    if (qvalid) wa_token(a, w.wy, w.wx, qp, qtok, qreg);
+    const size_t qrow = (size_t)w.b * a.L + qtok;
+    float qB[HC];
+    wa_load<HC / 4>(qvalid ? a.q + qrow * a.C + hf * HC : nullptr, qB);
+    wa_f32x16 o[NCB];
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[cb][r] = 0.f;
+    float m = -INFINITY;
+    double lsum = 0.0;
+    const int ntiles = (a.Lk + WA_T - 1) / WA_T;
+    for (int t = 0; t < ntiles; ++t) {
+        if (tid < WA_T) {
+            const int j = t * WA_T + tid;
+            int row = -1, reg = 0;
+            if (j < a.Lk) wa_key(a, w.b, w.wy, w.wx, j, row, reg);
+            s_row[t & 1][tid] = row;
+            s_reg[t & 1][tid] = reg;
+        }
+        __syncthreads();                                      // one barrier per tile: the table is double-buffered
+        const int* srow = s_row[t & 1];
+        const int* sreg = s_reg[t & 1];
+        const int kr31 = srow[l31];
+        const wa_f32x16 s = wa_dot<HC>(kr31 >= 0 ? a.k + (size_t)kr31 * a.C + hf * HC : nullptr, qB, a.inv_scale);  // S^T / sqrt(C): rows = keys, lane = query
+        float p[16];
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int kk = wa_acc_row(r, hf);
+            float x = s[r];
+            if (a.shift && sreg[kk] != qreg) x += -100.0f;
+            if (srow[kk] < 0) x = -INFINITY;
+            p[r] = x;
+            tmax = fmaxf(tmax, x);
+        }
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+        const float mnew = fmaxf(m, tmax);                    // finite: key 0 of every tile exists
+        const float alpha = expf(m - mnew);                   // 0 at the first tile
+        float rs = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            p[r] = expf(p[r] - mnew);
+            rs += p[r];
+        }
+        rs += __shfl_xor(rs, 32);
+        lsum = lsum * (double)alpha + (double)rs;
+        m = mnew;
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[cb][r] *= alpha;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {                        // O^T += V^T P^T, two keys (one per lane half) a step
+            const int kr = srow[wa_acc_row(r, hf)];
+            float vv[NCB];
+            wa_load_c<NCB>(kr >= 0 ? a.v + (size_t)kr * a.C + NCB * l31 : nullptr, vv);
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) o[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[cb], p[r], o[cb], 0, 0, 0);
+        }
+    }
+    if (!qvalid) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float x[NCB];
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) x[cb] = (float)((double)o[cb][r] / lsum);
+        wa_store_c<NCB>(out + qrow * a.C + NCB * wa_acc_row(r, hf), x);
+    }
+    if (hf == 0) lse[qrow] = (double)m + log(lsum);
+}
+
+// Backward, Delta and g_q.  Owner: queries (as the forward).  First sweep over the key tiles: Delta = sum_k P dP per query, float64,
+// written to delta[] for the key-owned pass; second sweep (WANT_Q): dS^T = P (dP - Delta), g_q^T += K^T dS^T.  Delta is formed
+// from the very dP values dS subtracts it from (the same fma chains in both sweeps and in the key-owned pass), as torch's
+// softmax backward forms it: at a row with few effective keys the rounding of dP then cancels in dP - Delta.  rowsum(g_out out),
+// the cheaper form, does not have that property and misses the accuracy rule of the tests at such rows.
+template <int NCB, bool WANT_Q>
+__global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_q(WAArgs a, const double* __restrict__ lse, const float* __restrict__ g_out,
+                                                              double* __restrict__ delta, float* __restrict__ g_q) {
+    constexpr int HC = 16 * NCB;
+    __shared__ int s_row[2][WA_T], s_reg[2][WA_T];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const WABlock w = wa_block(a, a.Lw);
+    const int qp = w.ob * WA_ROWS + wave * WA_T + l31;
+    const bool qvalid = qp < a.Lw;
+    int qtok = 0, qreg = 0;
+    if (qvalid) wa_token(a, w.wy, w.wx, qp, qtok, qreg);
+    const size_t qrow = (size_t)w.b * a.L + qtok;
+    const float* qB = qvalid ? a.q + qrow * a.C + hf * HC : nullptr;            // the owner's two rows (read per chunk by wa_dot_mem)
+    const float* gB = qvalid ? g_out + qrow * a.C + hf * HC : nullptr;
+    const double lq = qvalid ? lse[qrow] : 0.0;
+    double dsum = 0.0;
+    wa_f32x16 acc[NCB];
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[cb][r] = 0.f;
+    const int ntiles = (a.Lk + WA_T - 1) / WA_T;
+    int it = 0;                                               // parity of the double-buffered table, across both sweeps
+    for (int sweep = 0; sweep < (WANT_Q ? 2 : 1); ++sweep) {
+        for (int t = 0; t < ntiles; ++t, ++it) {
+            if (tid < WA_T) {
+                const int j = t * WA_T + tid;
+                int row = -1, reg = 0;
+                if (j < a.Lk) wa_key(a, w.b, w.wy, w.wx, j, row, reg);
+                s_row[it & 1][tid] = row;
+                s_reg[it & 1][tid] = reg;
+            }
+            __syncthreads();
+            const int* srow = s_row[it & 1];
+            const int* sreg = s_reg[it & 1];
+            wa_f32x16 s, dp;
+            {
+                const int kr = srow[l31];
+                s = wa_dot_mem<HC>(kr >= 0 ? a.k + (size_t)kr * a.C + hf * HC : nullptr, qB, a.inv_scale);      // S^T / sqrt(C)
+                dp = wa_dot_mem<HC>(kr >= 0 ? a.v + (size_t)kr * a.C + hf * HC : nullptr, gB, 1.0);             // dP^T = V dO^T
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int kk = wa_acc_row(r, hf);
+                const int kr = srow[kk];
+                float x = s[r];
+                if (a.shift && sreg[kk] != qreg) x += -100.0f;
+                const float p = (kr >= 0 && qvalid) ? expf((float)((double)x - lq)) : 0.f;
+                if (sweep == 0) {
+                    dsum += (double)p * (double)dp[r];
+                } else {
+                    const float ds = p * (float)((double)dp[r] - dsum);
+                    float kv[NCB];
+                    wa_load_c<NCB>(kr >= 0 ? a.k + (size_t)kr * a.C + NCB * l31 : nullptr, kv);
+#pragma unroll
+                    for (int cb = 0; cb < NCB; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[cb], ds, acc[cb], 0, 0, 0);
+                }
+            }
+        }
+        if (sweep == 0) {
+            dsum += __shfl_xor(dsum, 32);
+            if (qvalid && hf == 0) delta[qrow] = dsum;
+        }
+    }
+    if (!qvalid || !WANT_Q) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float x[NCB];
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) x[cb] = acc[cb][r] / a.scale;
+        wa_store_c<NCB>(g_q + qrow * a.C + NCB * wa_acc_row(r, hf), x);
+    }
+}
+
+// Backward, g_k and / or g_v.  Owner: keys; walks the window's query tiles.  S = Q K^T (rows = queries, lane = key),
+// g_v^T += dO^T P, g_k^T += Q^T dS.
+template <int NCB, bool WANT_K, bool WANT_V>
+__global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_kv(WAArgs a, const double* __restrict__ lse, const double* __restrict__ delta,
+                                                               const float* __restrict__ g_out, float* __restrict__ g_k,
+                                                               float* __restrict__ g_v) {
+    constexpr int HC = 16 * NCB;
+    __shared__ int s_row[2][WA_T], s_reg[2][WA_T];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const WABlock w = wa_block(a, a.Lk);
+    const int kj = w.ob * WA_ROWS + wave * WA_T + l31;
+    const bool kvalid = kj < a.Lk;
+    int krow_i = 0, kreg = 0;
+    if (kvalid) wa_key(a, w.b, w.wy, w.wx, kj, krow_i, kreg);
+    const size_t krow = (size_t)krow_i;
+    const float* kB = kvalid ? a.k + krow * a.C + hf * HC : nullptr;             // the owner's two rows (read per chunk by wa_dot_mem)
+    const float* vB = kvalid ? a.v + krow * a.C + hf * HC : nullptr;
+    wa_f32x16 dk[NCB], dv[NCB];
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dk[cb][r] = dv[cb][r] = 0.f;
+    const int ntiles = (a.Lw + WA_T - 1) / WA_T;
+    for (int t = 0; t < ntiles; ++t) {
+        if (tid < WA_T) {
+            const int p = t * WA_T + tid;
+            int row = -1, reg = 0;
+            if (p < a.Lw) {
+                int tok;
+                wa_token(a, w.wy, w.wx, p, tok, reg);
+                row = w.b * a.L + tok;
+            }
+            s_row[t & 1][tid] = row;
+            s_reg[t & 1][tid] = reg;
+        }
+        __syncthreads();
+        const int* srow = s_row[t & 1];
+        const int* sreg = s_reg[t & 1];
+        wa_f32x16 s, dp;
+        {
+            const int qr = srow[l31];
+            s = wa_dot_mem<HC>(qr >= 0 ? a.q + (size_t)qr * a.C + hf * HC : nullptr, kB, a.inv_scale);              // S / sqrt(C): rows = queries, lane = key; the forward's chain, bit for bit
+            if constexpr (WANT_K) {
+                dp = wa_dot_mem<HC>(qr >= 0 ? g_out + (size_t)qr * a.C + hf * HC : nullptr, vB, 1.0);                 // dP = dO V^T
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int qq = wa_acc_row(r, hf);
+            const int qr = srow[qq];
+            float x = s[r];
+            if (a.shift && sreg[qq] != kreg) x += -100.0f;
+            float p = 0.f;
+            if (qr >= 0 && kvalid) p = expf((float)((double)x - lse[qr]));
+            if constexpr (WANT_V) {
+                float gv[NCB];
+                wa_load_c<NCB>(qr >= 0 ? g_out + (size_t)qr * a.C + NCB * l31 : nullptr, gv);
+#pragma unroll
+                for (int cb = 0; cb < NCB; ++cb) dv[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(gv[cb], p, dv[cb], 0, 0, 0);
+            }
+            if constexpr (WANT_K) {
+                const float ds = p * (float)((double)dp[r] - (qr >= 0 ? delta[qr] : 0.0));
+                float qv[NCB];
+                wa_load_c<NCB>(qr >= 0 ? a.q + (size_t)qr * a.C + NCB * l31 : nullptr, qv);
+#pragma unroll
+                for (int cb = 0; cb < NCB; ++cb) dk[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(qv[cb], ds, dk[cb], 0, 0, 0);
+            }
+        }
+    }
+    if (!kvalid) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float x[NCB];
+        if constexpr (WANT_V) {
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) x[cb] = dv[cb][r];
+            wa_store_c<NCB>(g_v + krow * a.C + NCB * wa_acc_row(r, hf), x);
+        }
+        if constexpr (WANT_K) {
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) x[cb] = dk[cb][r] / a.scale;
+            wa_store_c<NCB>(g_k + krow * a.C + NCB * wa_acc_row(r, hf), x);
+        }
+    }
+}
+
+static bool wa_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// shared argument check; fills the kernel arguments
+static int wa_setup(const float* q, const float* k, const float* v, int32_t batch, int32_t partners, int32_t height, int32_t width,
+                    int32_t channels, int32_t num_splits, int32_t with_shift, int32_t mask_rule, WAArgs& a) {
+    if (!q || !k || !v || batch < 1 || partners < 0 || height < 1 || width < 1 || num_splits < 1) return S360_E_BADARG;
+    if (channels < 32 || channels > 128 || channels % 32 != 0) return S360_E_UNSUPPORTED;
+    if (height % num_splits != 0 || width % num_splits != 0 || (mask_rule != 0 && mask_rule != 1)) return S360_E_BADARG;
+    if (!wa_aligned16(q) || !wa_aligned16(k) || !wa_aligned16(v)) return S360_E_BADARG;
+    const int64_t M = partners > 0 ? partners : 1, L = (int64_t)height * width;
+    const int64_t Lw = L / ((int64_t)num_splits * num_splits);
+    if (batch * M * L >= (int64_t)1 << 31 || Lw * M >= (int64_t)1 << 31) return S360_E_BADARG;
+    const int64_t wins = (int64_t)batch * num_splits * num_splits;
+    if (wins * ((Lw * M + WA_ROWS - 1) / WA_ROWS) >= (int64_t)1 << 31) return S360_E_BADARG;
+    a.q = q; a.k = k; a.v = v;
+    a.B = batch; a.M = (int)M; a.H = height; a.W = width; a.C = channels; a.K = num_splits;
+    a.wh = height / num_splits; a.ww = width / num_splits;
+    a.shift = with_shift ? 1 : 0;
+    a.sh = a.shift ? a.wh / 2 : 0; a.sw = a.shift ? a.ww / 2 : 0;
+    a.Lw = (int)Lw; a.Lk = (int)(Lw * M); a.L = (int)L;
+    a.aligned = mask_rule;
+    a.scale = (float)sqrt((double)channels);
+    a.inv_scale = 1.0 / sqrt((double)channels);
+    return S360_OK;
+}
+
+static unsigned wa_grid(const WAArgs& a, int owner_rows) {
+    return (unsigned)((int64_t)a.B * a.K * a.K * ((owner_rows + WA_ROWS - 1) / WA_ROWS));
+}
+
+template <int NCB>
+static void wa_launch_kv(const WAArgs& a, const double* lse, const double* delta, const float* g_out, float* g_k, float* g_v,
+                         hipStream_t st) {
+    const dim3 grid(wa_grid(a, a.Lk)), block(S360_BLOCK);
+    if (g_k && g_v) hipLaunchKernelGGL((k_wa_backward_kv<NCB, true, true>), grid, block, 0, st, a, lse, delta, g_out, g_k, g_v);
+    else if (g_k) hipLaunchKernelGGL((k_wa_backward_kv<NCB, true, false>), grid, block, 0, st, a, lse, delta, g_out, g_k, g_v);
+    else hipLaunchKernelGGL((k_wa_backward_kv<NCB, false, true>), grid, block, 0, st, a, lse, delta, g_out, g_k, g_v);
+}
+
+}  // namespace s360
+
+using namespace s360;
+
+extern "C" int s360_window_attention_forward(const float* q, const float* k, const float* v, int32_t batch, int32_t partners,
+                                             int32_t height, int32_t width, int32_t channels, int32_t num_splits, int32_t with_shift,
+                                             int32_t mask_rule, float* out, double* lse, void* stream) {
+    WAArgs a;
+    const int rc = wa_setup(q, k, v, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, a);
+    if (rc != S360_OK) return rc;
+    if (!out || !lse || !wa_aligned16(out)) return S360_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
+    switch (channels / 32) {
+        case 1: hipLaunchKernelGGL((k_wa_forward<1>), grid, block, 0, st, a, out, lse); break;
+        case 2: hipLaunchKernelGGL((k_wa_forward<2>), grid, block, 0, st, a, out, lse); break;
+        case 3: hipLaunchKernelGGL((k_wa_forward<3>), grid, block, 0, st, a, out, lse); break;
+        default: hipLaunchKernelGGL((k_wa_forward<4>), grid, block, 0, st, a, out, lse); break;
+    }
+    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+}
+
+template <int NCB>
+static void wa_launch_q(const WAArgs& a, const double* lse, const float* g_out, double* delta, float* g_q, hipStream_t st) {
+    const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
+    if (g_q) hipLaunchKernelGGL((k_wa_backward_q<NCB, true>), grid, block, 0, st, a, lse, g_out, delta, g_q);
+    else hipLaunchKernelGGL((k_wa_backward_q<NCB, false>), grid, block, 0, st, a, lse, g_out, delta, g_q);
+}
+
+extern "C" int s360_window_attention_backward(const float* q, const float* k, const float* v, const double* lse, const float* g_out,
+                                              int32_t batch, int32_t partners, int32_t height, int32_t width, int32_t channels,
+                                              int32_t num_splits, int32_t with_shift, int32_t mask_rule, double* delta, float* g_q,
+                                              float* g_k, float* g_v, void* stream) {
+    WAArgs a;
+    const int rc = wa_setup(q, k, v, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, a);
+    if (rc != S360_OK) return rc;
+    if (!lse || !g_out || !delta || !wa_aligned16(g_out)) return S360_E_BADARG;
+    if ((g_q && !wa_aligned16(g_q)) || (g_k && !wa_aligned16(g_k)) || (g_v && !wa_aligned16(g_v))) return S360_E_BADARG;
+    if (!g_q && !g_k && !g_v) return S360_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (g_q || g_k) {                                         // the query-owned pass first: it writes Delta for the key-owned one
+        switch (channels / 32) {
+            case 1: wa_launch_q<1>(a, lse, g_out, delta, g_q, st); break;
+            case 2: wa_launch_q<2>(a, lse, g_out, delta, g_q, st); break;
+            case 3: wa_launch_q<3>(a, lse, g_out, delta, g_q, st); break;
+            default: wa_launch_q<4>(a, lse, g_out, delta, g_q, st); break;
+        }
+        if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    }
+    if (g_k || g_v) {
+        switch (channels / 32) {
+            case 1: wa_launch_kv<1>(a, lse, delta, g_out, g_k, g_v, st); break;
+            case 2: wa_launch_kv<2>(a, lse, delta, g_out, g_k, g_v, st); break;
+            case 3: wa_launch_kv<3>(a, lse, delta, g_out, g_k, g_v, st); break;
+            default: wa_launch_kv<4>(a, lse, delta, g_out, g_k, g_v, st); break;
+        }
+        if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    }
+    return S360_OK;
+}
