@@ -322,6 +322,12 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_q(WAArgs a, const do
         for (int r = 0; r < 16; ++r) acc[cb][r] = 0.f;
     const int ntiles = (a.Lk + WA_T - 1) / WA_T;
     int it = 0;                                               // parity of the double-buffered table, across both sweeps
+    // The two sweeps are two loops in the code (unrolled: `sweep` is a constant in each).  As one loop over a run-time `sweep`
+    // the compiler kept both bodies in one tile loop and moved the g_q accumulator between two register tiles after every
+    // MFMA; at C = 32 it then read the tile back at the head of the next key tile 7 wait states after the last MFMA of the
+    // previous one (a 16-pass MFMA needs 18), and register 15 — channels 27 and 31 of g_q — came back stale whenever a window
+    // had more than one key tile (tests/test_gpu_window_attention_float64.py, cases "edge" and "m5").
+#pragma unroll
     for (int sweep = 0; sweep < (WANT_Q ? 2 : 1); ++sweep) {
         for (int t = 0; t < ntiles; ++t, ++it) {
             if (tid < WA_T) {
