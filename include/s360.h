@@ -976,6 +976,49 @@ int s360_window_attention_backward(const float* q, const float* k, const float* 
                                    float* g_v, void* stream);
 
 /*
+ * The encoder's normalise-then-activate pair, forward and backward: GroupNorm (the reference's GroupNorm8 / GroupNorm4,
+ * src/model/encoder/costvolume/ldm_unet/util.py:199-238, and nn.GroupNorm at depth_predictor_multiview_360.py:425-427, :480-482)
+ * or InstanceNorm2d without affine (groups == channels; backbone/unimatch/backbone.py:28-36), the activation that follows it
+ * (SiLU in ResBlock, ldm_unet/unet.py:217-222, :249-256; GELU; ReLU; none in the postnorm AttentionBlock, :370-380) and the
+ * residual add behind it (:307, :380) as ONE operator; the activation's input is never stored, forward or backward.
+ *   x[n, channels, spatial] float32 contiguous, spatial the product of all trailing dims; cpg = channels / groups; the slab of
+ *   (i, g) is the M = cpg * spatial contiguous floats of channels g cpg .. (g + 1) cpg - 1 of batch element i.
+ *   mu and var are the slab's mean and BIASED variance, r = 1 / sqrt(var + eps), xh = (x - mu) r, z = xh weight[c] + bias[c]
+ *   (weight and bias [channels], both or neither; neither is weight = 1, bias = 0), out = residual + a(z) (residual[n, channels,
+ *   spatial] or NULL), a = identity, max(z, 0), z / (1 + exp(-z)) or 0.5 z erfc(-z / sqrt 2) (the erf form, nn.GELU()'s default).
+ *   stats[n * groups, 2] FLOAT64 receives (mu, r) of every slab.
+ * A workgroup takes one chunk of 4096 floats of one (i, c) row — a fixed split, whatever the device.  The forward is two
+ * launches: per-chunk (mean, M2) from sums shifted by the chunk's first element into scratch, then every workgroup merges its
+ * slab's chunks in a fixed order (mu = sum n_k mean_k / M, var = sum (M2_k + n_k (mean_k - mu)^2) / M: a constant slab gives
+ * var = 0 and mu exactly, a large mean over a small spread loses nothing) and streams x (and residual) to out.
+ * s360_group_norm_backward takes the forward's stats and g_out[n, channels, spatial]: dz = g_out a'(z) with z recomputed,
+ * m1 = sum_c weight[c] sum dz / M and m2 = sum_c weight[c] sum dz xh / M over the slab, g_x = r (weight[c] dz - m1 - xh m2),
+ * g_weight[c] = sum dz xh and g_bias[c] = sum dz over i and spatial.  Launches: per-chunk (sum dz, sum dz xh) into scratch; the
+ * sweep that writes g_x (skipped when g_x is NULL); one workgroup per channel for g_weight / g_bias (skipped when both are NULL).
+ * Any of the three may be NULL; g_weight / g_bias need weight.  The residual's gradient is g_out itself and has no kernel.
+ * Every per-element operation and every sum is float64 on the float32 inputs, rounded once; rows move as 16-byte vectors where
+ * all pointers of the launch are 16-byte aligned (scalar head and tail per row), element by element otherwise.  Every output
+ * element is written once, sums run in a fixed order: no atomics, bit-identical from run to run and across streams.
+ * eps is a HOST pointer to one float64, read before the first launch (scalars of this ABI are 32-bit integers, size_t and float32;
+ * a float32 1e-5 is 2.5e-8 away from the float64 one, which a slab of zero variance shows in full).
+ * No host synchronisation, no allocation.  scratch: s360_group_norm_scratch_doubles(n, channels, spatial) doubles of device
+ * memory (8-byte aligned, contents need no initialisation; 0 is returned for sizes < 1); forward and backward may share it.
+ * Null required pointers, sizes < 1, channels % groups != 0, only one of weight and bias, out or g_x overlapping x, an unknown
+ * activation, eps null or *eps <= 0 (or NaN), g_weight / g_bias without weight, or 2^31 or more workgroups: S360_E_BADARG before any GPU work.
+ */
+#define S360_GN_ACT_NONE 0
+#define S360_GN_ACT_RELU 1
+#define S360_GN_ACT_SILU 2
+#define S360_GN_ACT_GELU 3
+size_t s360_group_norm_scratch_doubles(int32_t n, int32_t channels, int64_t spatial);
+int s360_group_norm_forward(const float* x, const float* weight, const float* bias, const float* residual, int32_t n, int32_t channels,
+                            size_t spatial, int32_t groups, const double* eps, int32_t activation, double* scratch, double* stats,
+                            float* out, void* stream);
+int s360_group_norm_backward(const float* x, const float* weight, const float* bias, const double* stats, const float* g_out, int32_t n,
+                             int32_t channels, size_t spatial, int32_t groups, const double* eps, int32_t activation, double* scratch,
+                             float* g_x, float* g_weight, float* g_bias, void* stream);
+
+/*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an
  * un-synchronised wall clock, src/misc/benchmarker.py:15-33).  While enabled, every kernel group
  * is bracketed by HIP events recorded on the launch stream; s360_profile_collect() synchronises

@@ -7,8 +7,10 @@ def install(**opts):
     switch the other native seams on, each off by default: adapter, metrics, depth_loss, depth_metrics, psnr, cost_volume,
     depth_head (the encoder's softmax depth head, splatter360_amd.depth_head) and depth_tail (its two interpolations and
     map_pdf_to_opacity, splatter360_amd.depth_tail, whose fine_depth_tail is the direct API for the rest of that stretch),
-    erp_distance, visualization (the evaluation step's depth_map, prep_image and apply_color_map, splatter360_amd.visualize) and
-    depth_smoothness (the training step's LossDepth.forward, splatter360_amd.depth_smooth)."""
+    erp_distance, visualization (the evaluation step's depth_map, prep_image and apply_color_map, splatter360_amd.visualize),
+    depth_smoothness (the training step's LossDepth.forward, splatter360_amd.depth_smooth), window_attention (the multi-view
+    transformer's attention, splatter360_amd.window_attention) and group_norm (the encoder's norm + activation + residual sites,
+    splatter360_amd.group_norm)."""
     from .plugin import install as _install
     return _install(**opts)
 

@@ -35,6 +35,10 @@ float32 GPU maps, intrinsics broadcast by einops.repeat).  The step's reorder, c
 statements with no seam of their own; stitch.Cube2Equirec.stitch_distance_rendered is the direct API for the three as one kernel.
 install(depth_smoothness=True) rebinds LossDepth.forward (src/loss/loss_depth.py:27-60) to the depth-smoothness kernels of
 depth_smooth.py for float32 GPU batches; every other call reaches the replaced method.
+install(group_norm=True) rebinds ResBlock._forward and AttentionBlock._forward (src/model/encoder/costvolume/ldm_unet/unet.py),
+ResidualBlock.forward (src/model/encoder/backbone/unimatch/backbone.py) and DepthPredictorMultiView360.__init__ so that the
+encoder's norm + activation (+ residual) sites run the fused kernels of group_norm.py; every form the wrappers do not recognise
+reaches the replaced method.
 
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
@@ -997,6 +1001,140 @@ def install_window_attention():
     return WINDOW_ATTENTION_SEAM.install()
 
 
+GROUP_NORM_UNET_MODULE = "src.model.encoder.costvolume.ldm_unet.unet"   # defines ResBlock (:176-307) and AttentionBlock (:310-380)
+GROUP_NORM_RESBLOCK = "ResBlock"
+GROUP_NORM_ATTENTION = "AttentionBlock"
+GROUP_NORM_UNET_METHOD = "_forward"                                   # both forwards reach it through util.checkpoint, looked up per call
+GROUP_NORM_PREDICTOR_CLASS = "DepthPredictorMultiView360"             # COST_VOLUME_MODULE :405-520 builds the two U-Nets' heads
+GROUP_NORM_PREDICTOR_METHOD = "__init__"
+GROUP_NORM_PREDICTOR_NETS = ("corr_refine_net", "refine_unet")        # :424-444, :479-497: Conv2d -> nn.GroupNorm -> GELU -> UNetModel
+GROUP_NORM_BACKBONE_MODULE = "src.model.encoder.backbone.unimatch.backbone"   # defines ResidualBlock (:6-36)
+GROUP_NORM_RESIDUAL = "ResidualBlock"
+GROUP_NORM_BACKBONE_METHOD = "forward"
+
+
+def _norm_pair(layers):
+    """(conv, norm) if `layers` is the postnorm ResBlock's nn.Sequential(conv, GroupNorm, SiLU) — or what group_norm.fuse_pairs
+    makes of it, (conv, FusedGroupNormAct with silu, Identity) — else None."""
+    from . import group_norm as _gn
+    nn = torch.nn
+    if not isinstance(layers, nn.Sequential) or len(layers) != 3 or not isinstance(layers[1], nn.GroupNorm) or isinstance(layers[0], nn.GroupNorm):
+        return None
+    if isinstance(layers[1], _gn.FusedGroupNormAct):
+        ok = (layers[1].activation == "silu" and isinstance(layers[2], nn.Identity)) or \
+             (layers[1].activation == "none" and isinstance(layers[2], nn.SiLU))
+    else:
+        ok = isinstance(layers[2], nn.SiLU)
+    return (layers[0], layers[1]) if ok else None
+
+
+def _native_resblock_forward(replaced):
+    """ResBlock._forward with the reference's signature: for a block without up / down sampling whose in_layers and out_layers are
+    (conv, GroupNorm, SiLU), h = gn_silu(conv(x)) and skip_connection(x) + gn_silu(conv(h)) with the add inside the second
+    kernel; the replaced method otherwise (prenorm, updown).  group_norm.norm_act runs the kernels for contiguous float32 GPU
+    tensors and the block's own modules for everything else."""
+    from . import group_norm as _gn
+
+    def _forward(self, x, emb=None):
+        first = _norm_pair(getattr(self, "in_layers", None)) if not getattr(self, "updown", True) else None
+        second = _norm_pair(getattr(self, "out_layers", None)) if first is not None else None
+        if second is None:
+            return replaced(self, x, emb)
+        h = _gn.norm_act(first[1], first[0](x), "silu")
+        return _gn.norm_act(second[1], second[0](h), "silu", residual=self.skip_connection(x))
+
+    _forward.replaced = replaced
+    _forward.__doc__ = _gn.group_norm_act.__doc__
+    return _forward
+
+
+def _native_attention_block_forward(replaced):
+    """AttentionBlock._forward with the reference's signature: for a postnorm block, x + norm(proj_out(attention(qkv(x)))) with
+    the norm and the add as one kernel (activation none, residual x); qkv, attention and proj_out are the module's own.  The
+    replaced method otherwise (prenorm)."""
+    from . import group_norm as _gn
+
+    def _forward(self, x):
+        if not getattr(self, "postnorm", False) or not isinstance(getattr(self, "norm", None), torch.nn.GroupNorm) or x.dim() < 2:
+            return replaced(self, x)
+        b, c, *spatial = x.shape
+        x = x.reshape(b, c, -1)
+        h = self.proj_out(self.attention(self.qkv(x)))
+        return _gn.norm_act(self.norm, h, "none", residual=x).reshape(b, c, *spatial)
+
+    _forward.replaced = replaced
+    _forward.__doc__ = _gn.group_norm_act.__doc__
+    return _forward
+
+
+def _native_predictor_init(replaced):
+    """DepthPredictorMultiView360.__init__ with the reference's signature: the replaced constructor, then group_norm.fuse_pairs on
+    corr_refine_net and refine_unet where they are nn.Sequential (the ablations build a bare Conv2d): Conv2d -> nn.GroupNorm ->
+    GELU becomes Conv2d -> FusedGroupNormAct -> Identity with the same Parameter objects at the same indices, so the reference's
+    checkpoints load unchanged."""
+    import functools
+
+    from . import group_norm as _gn
+
+    @functools.wraps(replaced)
+    def __init__(self, *args, **kwargs):
+        replaced(self, *args, **kwargs)
+        for name in GROUP_NORM_PREDICTOR_NETS:
+            net = getattr(self, name, None)
+            if isinstance(net, torch.nn.Sequential):
+                _gn.fuse_pairs(net)
+
+    __init__.replaced = replaced
+    return __init__
+
+
+def _native_residual_block_forward(replaced):
+    """ResidualBlock.forward with the reference's signature: for norm1 and norm2 an nn.InstanceNorm2d without affine and without
+    running statistics and a 4-D input, y = in_relu(conv1(x)), y = in_relu(conv2(y)) with the instance norm and the ReLU as one
+    kernel; the downsample branch and the final relu(x + y) stay torch.  The replaced method otherwise (BatchNorm, affine)."""
+    from . import group_norm as _gn
+
+    def plain(norm) -> bool:
+        return isinstance(norm, torch.nn.InstanceNorm2d) and not norm.affine and not norm.track_running_stats
+
+    def forward(self, x):
+        if not (plain(getattr(self, "norm1", None)) and plain(getattr(self, "norm2", None)) and isinstance(x, torch.Tensor) and x.dim() == 4):
+            return replaced(self, x)
+        y = _gn.norm_act(self.norm1, self.conv1(x), "relu")
+        y = _gn.norm_act(self.norm2, self.conv2(y), "relu")
+        if self.downsample is not None:
+            x = self.downsample(x)
+        return self.relu(x + y)
+
+    forward.replaced = replaced
+    forward.__doc__ = _gn.instance_norm_act.__doc__
+    return forward
+
+
+GROUP_NORM_RESBLOCK_SEAM = _MethodSeam("group_norm", GROUP_NORM_UNET_MODULE, GROUP_NORM_RESBLOCK, (GROUP_NORM_UNET_METHOD,),
+                                       {GROUP_NORM_UNET_METHOD: _native_resblock_forward})
+GROUP_NORM_ATTENTION_SEAM = _MethodSeam("group_norm", GROUP_NORM_UNET_MODULE, GROUP_NORM_ATTENTION, (GROUP_NORM_UNET_METHOD,),
+                                        {GROUP_NORM_UNET_METHOD: _native_attention_block_forward})
+GROUP_NORM_PREDICTOR_SEAM = _MethodSeam("group_norm", COST_VOLUME_MODULE, GROUP_NORM_PREDICTOR_CLASS, (GROUP_NORM_PREDICTOR_METHOD,),
+                                        {GROUP_NORM_PREDICTOR_METHOD: _native_predictor_init})
+GROUP_NORM_RESIDUAL_SEAM = _MethodSeam("group_norm", GROUP_NORM_BACKBONE_MODULE, GROUP_NORM_RESIDUAL, (GROUP_NORM_BACKBONE_METHOD,),
+                                       {GROUP_NORM_BACKBONE_METHOD: _native_residual_block_forward})
+GROUP_NORM_SEAMS = (GROUP_NORM_RESBLOCK_SEAM, GROUP_NORM_ATTENTION_SEAM, GROUP_NORM_PREDICTOR_SEAM, GROUP_NORM_RESIDUAL_SEAM)
+
+
+def install_group_norm():
+    """The half of install(group_norm=True): rebind ResBlock._forward and AttentionBlock._forward (ldm_unet/unet.py),
+    DepthPredictorMultiView360.__init__ and the CNN backbone's ResidualBlock.forward to the wrappers around the fused
+    norm + activation (+ residual) kernels of group_norm.py, each now if its module is imported, else as soon as it is (import
+    hooks).  Returns {"Class.method": patched method or None}.  Modules built before the call keep their (norm, activation) pairs;
+    group_norm.fuse_pairs(module) is the direct API for them."""
+    out = {}
+    for seam in GROUP_NORM_SEAMS:
+        got = seam.install()
+        out[f"{seam.cls_name}.{seam.names[0]}"] = None if got is None else got[seam.names[0]]
+    return out
+
+
 def install_depth_smoothness():
     """The half of install(depth_smoothness=True): rebind LossDepth.forward (src/loss/loss_depth.py:27-60) to the wrapper around
     the depth-smoothness kernels now if the reference's module is imported, else as soon as it is (import hook).  Returns the
@@ -1065,7 +1203,7 @@ def install_psnr():
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
             depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, depth_head: bool = False, depth_tail: bool = False,
             erp_distance: bool = False, visualization: bool = False, depth_smoothness: bool = False, window_attention: bool = False,
-            **opts):
+            group_norm: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
@@ -1096,6 +1234,10 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     single_head_full_attention (src/model/encoder/backbone/multiview_transformer.py:8-16, :60-210) to the fused window-attention
     kernels of splatter360_amd.window_attention, and generate_shift_window_attn_mask to return a ShiftMask handle in place of
     the [K^2, Lw, Lw] tensor (install_window_attention; off by default).
+    group_norm=True: ALSO rebind the two U-Nets' ResBlock._forward and AttentionBlock._forward (ldm_unet/unet.py), the CNN
+    backbones' ResidualBlock.forward and DepthPredictorMultiView360.__init__ so that every conv -> GroupNorm / InstanceNorm2d ->
+    SiLU / GELU / ReLU (-> + skip) of the encoder runs the fused kernels of splatter360_amd.group_norm (install_group_norm; off
+    by default).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -1126,6 +1268,8 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
         install_depth_smoothness()
     if window_attention:
         install_window_attention()
+    if group_norm:
+        install_group_norm()
     if lazy:
         if REGISTRY_MODULE in sys.modules:
             return _patch(sys.modules[REGISTRY_MODULE], **opts)
@@ -1138,12 +1282,13 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
 def uninstall() -> None:
     """Put the reference's own decoder class, adapter, compute_ssim, compute_psnr, compute_depth_metrics_batched,
     compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates, depth_to_distance_map_batch, depth_map, prep_image,
-    apply_color_map, EncoderCostVolume.map_pdf_to_opacity, LossDepth.forward, the backbone module's four attention functions and the
-    predictor module's `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
+    apply_color_map, EncoderCostVolume.map_pdf_to_opacity, LossDepth.forward, the backbone module's four attention functions,
+    ResBlock._forward, AttentionBlock._forward, ResidualBlock.forward, DepthPredictorMultiView360.__init__ and the predictor
+    module's `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
     sys.meta_path[:] = [f for f in sys.meta_path
                         if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher, _DepthLossPatcher, _SeamPatcher))]
     for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM, DEPTH_HEAD_SEAM, DEPTH_TAIL_F_SEAM, DEPTH_TAIL_METHOD_SEAM, ERP_DISTANCE_SEAM,
-                 DEPTH_SMOOTH_SEAM, WINDOW_ATTENTION_SEAM, *VIS_SEAMS):
+                 DEPTH_SMOOTH_SEAM, WINDOW_ATTENTION_SEAM, *GROUP_NORM_SEAMS, *VIS_SEAMS):
         seam.restore()
     dmod = sys.modules.get(DEPTH_MODULE)
     if dmod is not None:
