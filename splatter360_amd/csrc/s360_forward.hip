@@ -1189,6 +1189,156 @@ __device__ __forceinline__ void block_merge_sort(const uint64_t* __restrict__ in
 #undef S360_PHYS
 }
 
+// One-pass distribution sort on the depth word, same contract as block_merge_sort (in, out, list, n, the same dynamic LDS; `in`
+// may be `out`: every key is in registers before the first store).  The keys are unique, so the ascending order is ONE order and
+// what this writes is bit-identical to the merge sort's, whatever order the LDS atomics arrive in:
+//   1. block min / max of the high (depth) words;
+//   2. bucket = min(NB - 1, (uint)(float(hi - lo) * scale)), scale = NB / (float(max - lo) + 1) — monotone non-decreasing in hi:
+//      hi - lo is (lo is the block's minimum: no wrap), uint -> float rounds monotonically, so does the product with the positive
+//      constant `scale`, float -> uint truncates monotonically, and so does the clamp.  The product never exceeds NB (1 + 2^-22),
+//      so the conversion is in range; no 64-bit multiply or divide per key;
+//   3. rank inside the bucket = what a returning LDS atomic increment of the bucket's counter hands back;
+//   4. exclusive scan of the NB counters (NB / THREADS per thread, wave scan, NW partials), the largest count on the way: if any
+//      bucket holds more than S360_SORT_BMAX keys (ties in depth, one far outlier stretching the range, a range narrower than the
+//      list), the whole workgroup — one __syncthreads_or, block-uniform — takes block_merge_sort on the same, still untouched input;
+//   5. scatter to start[bucket] + rank: ordered by bucket, unordered inside one;
+//   6. final position = start[bucket] + number of keys of the bucket below this key (full 64-bit compare; ~2 candidates on the
+//      encoder-like cloud); the keys go there in LDS and leave with coalesced stores.
+// Work is proportional to n (strided ownership: key i belongs to thread i % THREADS), apart from clearing and scanning the NB
+// counters; nothing is padded to the capacity.  LDS: THREADS * E keys, then the counters — or, where both do not fit the
+// allocation (E = 8, NB = 4 096), the counters in front of the key buffer, which is then filled one barrier later.
+#ifndef S360_SORT_BMAX
+#define S360_SORT_BMAX 16   // largest power of two below the measured crossover with the merge-sort branch
+#endif
+constexpr size_t SORT_LDS_BYTES = (size_t)(8 * S360_SORT_THREADS + S360_SORT_THREADS) * 8;   // k_sort_stage1's dynamic allocation
+template <int THREADS, int E, int NB, bool DEV = false>
+__device__ __forceinline__ void block_bucket_sort(const uint64_t* __restrict__ in, uint64_t* __restrict__ out,
+                                                  uint32_t* __restrict__ list, uint32_t n, uint64_t* lds_m) {
+    constexpr int KEYS = THREADS * E, NW = THREADS / 64, C = NB / THREADS;
+    constexpr bool ALIAS = (size_t)KEYS * 8 + (size_t)NB * 4 + 256 > SORT_LDS_BYTES;
+    static_assert(NB % THREADS == 0 && (C == 4 || C == 8) && NW <= 16, "counters per thread: one or two 16-byte LDS accesses");
+    static_assert((size_t)KEYS * 8 + 256 <= SORT_LDS_BYTES && (size_t)NB * 4 <= (size_t)KEYS * 8, "LDS budget");
+    static_assert(KEYS <= 0x10000 && NB <= 0x10000 && KEYS <= 0x2000 && S360_SORT_BMAX < 0x80, "bucket | rank << 16; start | rank << 13 | count << 20");
+    uint64_t* const buf = lds_m;
+    uint32_t* const cnt = ALIAS ? (uint32_t*)lds_m : (uint32_t*)(lds_m + KEYS);
+    uint32_t* const red = ALIAS ? (uint32_t*)(lds_m + KEYS) : cnt + NB;   // [48]: wave minima, wave maxima, wave totals
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint64_t k[E];
+    uint32_t mn = ~0u, mx = 0u;
+#pragma unroll
+    for (int q = 0; q < E; ++q) {
+        const uint32_t i = (uint32_t)(tid + q * THREADS);
+        k[q] = in[min(i, n - 1u)];   // n >= 1; unconditional: the E loads are in flight together
+    }
+#pragma unroll
+    for (int j = 0; j < C / 4; ++j) ((uint4*)cnt)[tid * (C / 4) + j] = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+    for (int q = 0; q < E; ++q) {   // (a key read twice through the clamp changes neither extreme)
+        const uint32_t h = (uint32_t)(k[q] >> 32);
+        mn = min(mn, h);
+        mx = max(mx, h);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mn = min(mn, (uint32_t)__shfl_xor((int)mn, off));
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, off));
+    }
+    if (lane == 0) {
+        red[wave] = mn;
+        red[16 + wave] = mx;
+    }
+    __syncthreads();
+    uint32_t lo = ~0u, top = 0u;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        lo = min(lo, red[w]);
+        top = max(top, red[16 + w]);
+    }
+    const float scale = (float)NB / ((float)(top - lo) + 1.0f);
+    uint32_t pk[E];   // bucket | rank inside it << 16; then bucket start | rank << 13 | bucket count << 20; then the final position
+#pragma unroll
+    for (int q = 0; q < E; ++q) {
+        const uint32_t i = (uint32_t)(tid + q * THREADS);
+        if (i < n) {
+            const uint32_t b = min((uint32_t)((float)((uint32_t)(k[q] >> 32) - lo) * scale), (uint32_t)(NB - 1));
+            pk[q] = b | (atomicAdd(&cnt[b], 1u) << 16);
+        }
+    }
+    __syncthreads();
+    uint32_t c[C], sum = 0u, big = 0u;
+#pragma unroll
+    for (int j = 0; j < C / 4; ++j) {
+        const uint4 v = ((const uint4*)cnt)[tid * (C / 4) + j];
+        c[4 * j] = v.x, c[4 * j + 1] = v.y, c[4 * j + 2] = v.z, c[4 * j + 3] = v.w;
+    }
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        sum += c[j];
+        big = max(big, c[j]);
+    }
+    uint32_t incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, off);
+        if (lane >= off) incl += up;
+    }
+    if (lane == 63) red[32 + wave] = incl;
+    if (__syncthreads_or(big > (uint32_t)S360_SORT_BMAX)) {   // (also the barrier in front of the wave totals)
+        block_merge_sort<THREADS, E, DEV>(in, out, list, n, lds_m);
+        return;
+    }
+    uint32_t run = incl - sum;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) run += w < wave ? red[32 + w] : 0u;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        const uint32_t cj = c[j];
+        c[j] = run | (cj << 20);
+        run += cj;
+    }
+#pragma unroll
+    for (int j = 0; j < C / 4; ++j) ((uint4*)cnt)[tid * (C / 4) + j] = make_uint4(c[4 * j], c[4 * j + 1], c[4 * j + 2], c[4 * j + 3]);
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < E; ++q) {
+        const uint32_t i = (uint32_t)(tid + q * THREADS);
+        if (i < n) pk[q] = cnt[pk[q] & 0xFFFFu] | (pk[q] >> 16 << 13);   // rank < count <= S360_SORT_BMAX here
+    }
+    if (ALIAS) __syncthreads();   // the key buffer lies over the counters
+#pragma unroll
+    for (int q = 0; q < E; ++q) {
+        const uint32_t i = (uint32_t)(tid + q * THREADS);
+        if (i < n) buf[(pk[q] & 0x1FFFu) + ((pk[q] >> 13) & 0x7Fu)] = k[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < E; ++q) {
+        const uint32_t i = (uint32_t)(tid + q * THREADS);
+        if (i < n) {
+            const uint32_t s = pk[q] & 0x1FFFu, e = s + (pk[q] >> 20);
+            uint32_t below = 0u;
+            for (uint32_t j = s; j < e; ++j) below += buf[j] < k[q] ? 1u : 0u;
+            pk[q] = s + below;
+        }
+    }
+    __syncthreads();   // every read of the bucket order precedes the writes of the final one
+#pragma unroll
+    for (int q = 0; q < E; ++q) {
+        const uint32_t i = (uint32_t)(tid + q * THREADS);
+        if (i < n) buf[pk[q]] = k[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < E; ++q) {
+        const uint32_t i = (uint32_t)(tid + q * THREADS);
+        if (i < n) {
+            const uint64_t kq = buf[i];
+            if (DEV) st_dev(out + i, kq); else out[i] = kq;
+            if (list) list[i] = (uint32_t)kq;
+        }
+    }
+}
+
 // ---- long lists (n > SORT_SHORT): chunk sort + merge passes -------------------------------------------------
 // Work unit = one SORT_CHUNK-sized output chunk (t, k) of a long tile, found from the block index by a binary
 // search over chunk_start[].  A tile with c chunks needs P = ceil(log2 c) merge passes; it ping-pongs between
@@ -1367,11 +1517,11 @@ __device__ __forceinline__ void sort_tiles_global_body(const uint32_t* __restric
 
 // ONE launch for the whole sort.  Roles by block index:
 //   [0, cgrid)                 chunk blocks: the 4 096-key chunks of the long lists, first in the grid (their results feed the merge
-//                              passes, the critical path);
+//                              passes, the critical path: what ends the launch), block_bucket_sort with 4 096 buckets;
 //   [cgrid, cgrid + mgrid)     merge blocks: the (pass, chunk) merge units of every multi-chunk list (merge_unit), in pass-major order
 //                              from a ticket counter, and — once the tickets have run out — the global-memory fallback for lists beyond
 //                              SORT_CHUNK << max_passes keys;
-//   [cgrid + mgrid, .. + nt)   one block per tile for the lists of up to 2 048 keys: the bulk of the launch's time, under which the
+//   [cgrid + mgrid, .. + nt)   one block per tile for the lists of up to 2 048 keys (block_bucket_sort, 2 048 buckets), under which the
 //                              handful of merge units runs (as a launch of their own they were 23 us of a nearly idle chip);
 //   the last block             deals the composite's tile order.
 // Runs that cross workgroups inside the launch — the sorted chunks of a list that has merge passes, and every merge pass's output — are
@@ -1411,6 +1561,18 @@ __device__ __forceinline__ void drain_stores_and_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
 }
+#ifndef S360_SORT_BUCKET_CHUNKS
+#define S360_SORT_BUCKET_CHUNKS 1   // the 4 096-key chunks of the long lists: 1 = bucket sort (4 096 buckets), 0 = merge sort (measured: DESIGN.md section 4)
+#endif
+template <bool DEV>
+__device__ __forceinline__ void sort_chunk(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint32_t* __restrict__ list,
+                                           uint32_t n, uint64_t* lds_m) {
+#if S360_SORT_BUCKET_CHUNKS
+    block_bucket_sort<SORT_THREADS, 8, (int)SORT_CHUNK, DEV>(in, out, list, n, lds_m);
+#else
+    block_merge_sort<SORT_THREADS, 8, DEV>(in, out, list, n, lds_m);
+#endif
+}
 __global__ __launch_bounds__(SORT_THREADS) void k_sort_stage1(const uint32_t* __restrict__ tile_start, const uint32_t* __restrict__ chunk_start,
                                                     int nt, uint64_t* __restrict__ keys, uint64_t* __restrict__ alt,
                                                     uint32_t* __restrict__ list, uint32_t cap, uint32_t max_passes, uint32_t cgrid,
@@ -1429,9 +1591,9 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_stage1(const uint32_t* __
                 const uint32_t c0 = u.k * SORT_CHUNK, len = min(SORT_CHUNK, u.n - c0);
                 uint64_t* dst = ((u.passes & 1u) ? alt : keys) + u.s + c0;
                 if (u.passes == 0) {   // the whole list (2 049 .. 4 096 keys): nobody reads it before the next launch
-                    block_merge_sort<SORT_THREADS, 8>(keys + u.s + c0, dst, list + u.s, len, lds_m);
+                    sort_chunk<false>(keys + u.s + c0, dst, list + u.s, len, lds_m);
                 } else {               // a run of pass 0, read by a merge block of this launch
-                    block_merge_sort<SORT_THREADS, 8, true>(keys + u.s + c0, dst, nullptr, len, lds_m);
+                    sort_chunk<true>(keys + u.s + c0, dst, nullptr, len, lds_m);
                     drain_stores_and_sync();
                     if (threadIdx.x == 0) __hip_atomic_fetch_add(&chunks_sorted[u.t], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
@@ -1478,7 +1640,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_stage1(const uint32_t* __
         const uint32_t s = min(tile_start[tile], cap), e = min(tile_start[tile + 1], cap);
         const uint32_t n = e - s;
         if (n == 0 || n > SORT_SHORT) return;
-        block_merge_sort<SORT_THREADS, (int)(SORT_SHORT / SORT_THREADS)>(keys + s, keys + s, list + s, n, lds_m);
+        block_bucket_sort<SORT_THREADS, (int)(SORT_SHORT / SORT_THREADS), (int)SORT_SHORT>(keys + s, keys + s, list + s, n, lds_m);
         return;
     }
     // S360Params.header_mirror word 2: (Gaussian, view) pairs binned over more than 32 tiles (k_emit, the previous launch, counted them)
