@@ -94,358 +94,14 @@ def make_decoder_class(base_cls, output_cls, *, views_per_group: int = 6, shared
     return _Fused
 
 
-def _patch(pkg, **opts):
-    base = importlib.import_module(REGISTRY_MODULE + ".decoder")
-    cls = make_decoder_class(base.Decoder, base.DecoderOutput, **opts)
-    cls.replaced = pkg.DECODERS.get(REGISTRY_KEY)       # the reference's own class stays reachable
-    pkg.DECODERS[REGISTRY_KEY] = cls
-    return cls
-
-
-class _LazyPatcher(importlib.abc.MetaPathFinder):
-    """Patches the registry right after the reference's decoder package has been imported by whoever imports it first."""
-
-    def __init__(self, opts):
-        self.opts, self.busy = opts, False
-
-    def find_spec(self, fullname, path, target=None):
-        if self.busy:
-            return None
-        if fullname != REGISTRY_MODULE:
-            # ANY later import is a chance to patch: the reference imports its packages inside jaxtyping's install_import_hook
-            # (/root/reference/src/main.py:22-36), whose own finder is inserted at sys.meta_path[0] afterwards and resolves every
-            # `src.*` module by calling PathFinder directly — this finder is then never asked for `src.model.decoder` itself
-            # (ADVICE r04), but it is asked for the first non-`src` module imported after it (the encoder's third-party
-            # imports, still inside that `with` block and long before get_decoder runs at main.py:168).
-            pkg = sys.modules.get(REGISTRY_MODULE)
-            if pkg is not None and isinstance(getattr(pkg, "DECODERS", None), dict) and REGISTRY_KEY in pkg.DECODERS:
-                if self in sys.meta_path:
-                    sys.meta_path.remove(self)
-                self.busy = True
-                try:
-                    _patch(pkg, **self.opts)
-                except Exception as ex:     # never let the failure surface from an unrelated third-party import (ADVICE r05)
-                    import warnings
-                    warnings.warn(f"splatter360_amd.install(lazy=True): patching the reference's decoder registry failed ({ex!r}); the "
-                                  "reference keeps its own decoder. Call splatter360_amd.install() explicitly to see the error.", RuntimeWarning)
-                    self.failed = ex
-                finally:
-                    self.busy = False
-            return None
-        self.busy = True
-        try:
-            spec = importlib.util.find_spec(fullname)
-        finally:
-            self.busy = False
-        if spec is None or spec.loader is None:
-            return None
-        loader, opts, finder = spec.loader, self.opts, self
-
-        class _Loader(importlib.abc.Loader):
-            def create_module(self, s):
-                return loader.create_module(s)
-
-            def exec_module(self, module):
-                loader.exec_module(module)
-                if finder in sys.meta_path:
-                    sys.meta_path.remove(finder)
-                _patch(module, **opts)
-
-        spec.loader = _Loader()
-        return spec
-
-
-def _patch_adapter(mod, **aopts):
-    """Replace the class the reference's encoder instantiates (encoder_costvolume.py:185) in the module that defines it and in every
-    already-imported module that bound the name with `from ... import`."""
-    from . import lazy as _lz
-    cur = getattr(mod, ADAPTER_NAME)
-    if getattr(cur, "replaced", None) is not None:       # idempotent
-        return cur
-    cls = _lz.make_adapter_class(cur, getattr(mod, "Gaussians", None), **aopts)
-    cls.replaced = cur
-    setattr(mod, ADAPTER_NAME, cls)
-    for user in ADAPTER_USERS:
-        um = sys.modules.get(user)
-        if um is not None and getattr(um, ADAPTER_NAME, None) is cur:
-            setattr(um, ADAPTER_NAME, cls)
-    return cls
-
-
-class _AdapterPatcher(importlib.abc.MetaPathFinder):
-    """install(adapter=True) before the reference's encoder package is imported: patch the adapter module as it is first loaded —
-    the encoder's own `from .common.gaussian_adapter_erp import GaussianAdapterERP` (encoder_costvolume.py:19) then binds the
-    replacement."""
-
-    def __init__(self, aopts):
-        self.aopts, self.busy = aopts, False
-
-    def find_spec(self, fullname, path, target=None):
-        if self.busy or fullname != ADAPTER_MODULE:
-            return None
-        self.busy = True
-        try:
-            spec = importlib.util.find_spec(fullname)
-        finally:
-            self.busy = False
-        if spec is None or spec.loader is None:
-            return None
-        loader, aopts, finder = spec.loader, self.aopts, self
-
-        class _Loader(importlib.abc.Loader):
-            def create_module(self, s):
-                return loader.create_module(s)
-
-            def exec_module(self, module):
-                loader.exec_module(module)
-                if finder in sys.meta_path:
-                    sys.meta_path.remove(finder)
-                _patch_adapter(module, **aopts)
-
-        spec.loader = _Loader()
-        return spec
-
-
-def install_adapter(**aopts):
-    """The adapter half of install(adapter=True): see lazy.py.  Patches now if the reference's adapter module is already imported,
-    else as soon as it is (import hook).  aopts: sh_rotation ("native"), differentiable_means (False), lazy (True)."""
-    mod = sys.modules.get(ADAPTER_MODULE)
-    if mod is not None and hasattr(mod, ADAPTER_NAME):
-        return _patch_adapter(mod, **aopts)
-    if not any(isinstance(f, _AdapterPatcher) for f in sys.meta_path):
-        sys.meta_path.insert(0, _AdapterPatcher(aopts))
-    return None
-
-
-METRICS_MODULE = "src.evaluation.metrics"                              # defines compute_ssim (:38-54)
-METRICS_USERS = ("src.model.model_wrapper_erp",                        # `from ..evaluation.metrics import ... compute_ssim` (:18)
-                 "src.model.model_wrapper_cubemaps",                   # (:19)
-                 "src.evaluation.metric_computer")                     # (:12)
-METRICS_NAME = "compute_ssim"
-
-
-def _native_compute_ssim(replaced):
-    """compute_ssim with the reference's signature: the SSIM kernel for GPU tensors, the replaced function otherwise."""
-    from . import metrics as _metrics
-
-    def compute_ssim(ground_truth, predicted):
-        if ground_truth.is_cuda and predicted.is_cuda:
-            return _metrics.compute_ssim(ground_truth, predicted)
-        return replaced(ground_truth, predicted)
-
-    compute_ssim.replaced = replaced
-    compute_ssim.__doc__ = _metrics.compute_ssim.__doc__
-    return compute_ssim
-
-
-def _patch_metrics(mod):
-    """Rebind compute_ssim in the module that defines it and in every already-imported module that bound the name with
-    `from ... import` (modules imported later bind the replacement themselves).  Idempotent."""
-    cur = getattr(mod, METRICS_NAME)
-    fn = cur if getattr(cur, "replaced", None) is not None else _native_compute_ssim(cur)
-    setattr(mod, METRICS_NAME, fn)
-    for user in METRICS_USERS:
-        um = sys.modules.get(user)
-        if um is not None and getattr(um, METRICS_NAME, None) is fn.replaced:
-            setattr(um, METRICS_NAME, fn)
-    return fn
-
-
-class _MetricsPatcher(importlib.abc.MetaPathFinder):
-    """install(metrics=True) before the reference's metrics module is imported: patch it as it is first loaded, and — for an
-    import made through a finder ahead of this one (jaxtyping's hook at sys.meta_path[0] resolves `src.*` through PathFinder
-    itself, see _LazyPatcher) — at the next import this finder is asked about, before the evaluation step can call it."""
-
-    def __init__(self):
-        self.busy = False
-
-    def _done(self, mod):
-        if self in sys.meta_path:
-            sys.meta_path.remove(self)
-        _patch_metrics(mod)
-
-    def find_spec(self, fullname, path, target=None):
-        if self.busy:
-            return None
-        mod = sys.modules.get(METRICS_MODULE)
-        if mod is not None and hasattr(mod, METRICS_NAME):        # imported behind this finder's back: patch late
-            self.busy = True
-            try:
-                self._done(mod)
-            except Exception as ex:      # never let the failure surface from an unrelated import
-                import warnings
-                warnings.warn(f"splatter360_amd.install(metrics=True): patching {METRICS_MODULE}.{METRICS_NAME} failed ({ex!r}); "
-                              "the reference keeps its own SSIM.", RuntimeWarning)
-            finally:
-                self.busy = False
-            return None
-        if fullname != METRICS_MODULE:
-            return None
-        self.busy = True
-        try:
-            spec = importlib.util.find_spec(fullname)
-        finally:
-            self.busy = False
-        if spec is None or spec.loader is None:
-            return None
-        loader, finder = spec.loader, self
-
-        class _Loader(importlib.abc.Loader):
-            def create_module(self, s):
-                return loader.create_module(s)
-
-            def exec_module(self, module):
-                loader.exec_module(module)
-                finder._done(module)
-
-        spec.loader = _Loader()
-        return spec
-
-
-def install_metrics():
-    """The metrics half of install(metrics=True): rebind compute_ssim now if the reference's metrics module is imported, else as
-    soon as it is (import hook).  Returns the patched function or None."""
-    mod = sys.modules.get(METRICS_MODULE)
-    if mod is not None and hasattr(mod, METRICS_NAME):
-        return _patch_metrics(mod)
-    if not any(isinstance(f, _MetricsPatcher) for f in sys.meta_path):
-        sys.meta_path.insert(0, _MetricsPatcher())
-    return None
-
-
-DEPTH_MODULE = "src.model.model_wrapper_helper"                       # defines erode (:4-24) and compute_l1_sphere_loss (:63-90)
-DEPTH_USERS = ("src.model.model_wrapper_erp",)                         # `from .model_wrapper_helper import compute_l1_sphere_loss, erode` (:45)
-DEPTH_NAMES = ("compute_l1_sphere_loss", "erode")
-
-
-def _is_cuda_f32(t) -> bool:
-    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
-
-
-def _native_l1_sphere_loss(replaced):
-    """compute_l1_sphere_loss with the reference's signature: the depth-loss kernels for float32 GPU tensors of one [B,V,H,W]
-    shape with a mask that takes no gradient, the replaced function otherwise (mask=None included: it raises there)."""
-    from . import depth_loss as _dl
-
-    def compute_l1_sphere_loss(y_pred, y_true, mask=None, keep_batch=False):
-        if (mask is not None and all(_is_cuda_f32(t) for t in (y_pred, y_true, mask)) and y_pred.dim() == 4
-                and y_true.shape == y_pred.shape and mask.shape == y_pred.shape and not mask.requires_grad
-                and y_pred.numel() > 0 and y_pred.device == y_true.device == mask.device):
-            return _dl.compute_l1_sphere_loss(y_pred, y_true, mask, keep_batch)
-        return replaced(y_pred, y_true, mask=mask, keep_batch=keep_batch)
-
-    compute_l1_sphere_loss.replaced = replaced
-    compute_l1_sphere_loss.__doc__ = _dl.compute_l1_sphere_loss.__doc__
-    return compute_l1_sphere_loss
-
-
-def _native_erode(replaced):
-    """erode with the reference's signature: the erosion kernel for [C,H,W] / [N,C,H,W] float32 GPU tensors that take no gradient,
-    an odd ksize and a reflect pad below H and W; the replaced function otherwise."""
-    from . import depth_loss as _dl
-
-    def erode(bin_img, ksize=5):
-        if (_is_cuda_f32(bin_img) and bin_img.dim() in (3, 4) and not bin_img.requires_grad and isinstance(ksize, int)
-                and ksize >= 1 and ksize % 2 == 1 and (ksize - 1) // 2 < min(bin_img.shape[-2], bin_img.shape[-1])):
-            return _dl.erode(bin_img, ksize)
-        return replaced(bin_img, ksize)
-
-    erode.replaced = replaced
-    erode.__doc__ = _dl.erode.__doc__
-    return erode
-
-
-_DEPTH_WRAPPERS = {"compute_l1_sphere_loss": _native_l1_sphere_loss, "erode": _native_erode}
-
-
-def _patch_depth_loss(mod):
-    """Rebind compute_l1_sphere_loss and erode in the module that defines them and in every already-imported module that bound
-    the names with `from ... import` (modules imported later bind the replacements themselves).  Idempotent."""
-    out = {}
-    for name in DEPTH_NAMES:
-        cur = getattr(mod, name)
-        fn = cur if getattr(cur, "replaced", None) is not None else _DEPTH_WRAPPERS[name](cur)
-        setattr(mod, name, fn)
-        for user in DEPTH_USERS:
-            um = sys.modules.get(user)
-            if um is not None and getattr(um, name, None) is fn.replaced:
-                setattr(um, name, fn)
-        out[name] = fn
-    return out
-
-
-def _depth_module_ready(mod) -> bool:
-    return mod is not None and all(hasattr(mod, n) for n in DEPTH_NAMES)
-
-
-class _DepthLossPatcher(importlib.abc.MetaPathFinder):
-    """install(depth_loss=True) before the reference's helper module is imported: patch it as it is first loaded, and — for an
-    import made through a finder ahead of this one (jaxtyping's hook, see _MetricsPatcher) — at the next import this finder is
-    asked about, before the training step can call it."""
-
-    def __init__(self):
-        self.busy = False
-
-    def _done(self, mod):
-        if self in sys.meta_path:
-            sys.meta_path.remove(self)
-        _patch_depth_loss(mod)
-
-    def find_spec(self, fullname, path, target=None):
-        if self.busy:
-            return None
-        mod = sys.modules.get(DEPTH_MODULE)
-        if _depth_module_ready(mod):                              # imported behind this finder's back: patch late
-            self.busy = True
-            try:
-                self._done(mod)
-            except Exception as ex:      # never let the failure surface from an unrelated import
-                import warnings
-                warnings.warn(f"splatter360_amd.install(depth_loss=True): patching {DEPTH_MODULE} failed ({ex!r}); the reference "
-                              "keeps its own depth loss.", RuntimeWarning)
-            finally:
-                self.busy = False
-            return None
-        if fullname != DEPTH_MODULE:
-            return None
-        self.busy = True
-        try:
-            spec = importlib.util.find_spec(fullname)
-        finally:
-            self.busy = False
-        if spec is None or spec.loader is None:
-            return None
-        loader, finder = spec.loader, self
-
-        class _Loader(importlib.abc.Loader):
-            def create_module(self, s):
-                return loader.create_module(s)
-
-            def exec_module(self, module):
-                loader.exec_module(module)
-                finder._done(module)
-
-        spec.loader = _Loader()
-        return spec
-
-
-def install_depth_loss():
-    """The depth-loss half of install(depth_loss=True): rebind compute_l1_sphere_loss and erode now if the reference's helper
-    module is imported, else as soon as it is (import hook).  Returns {name: patched function} or None."""
-    mod = sys.modules.get(DEPTH_MODULE)
-    if _depth_module_ready(mod):
-        return _patch_depth_loss(mod)
-    if not any(isinstance(f, _DepthLossPatcher) for f in sys.meta_path):
-        sys.meta_path.insert(0, _DepthLossPatcher())
-    return None
-
-
 class _Seam:
     """One rebinding seam: functions `names` defined in `module` and bound with `from ... import` by `users`; wrappers[name](replaced)
-    builds the replacement (which keeps the original as `.replaced`)."""
+    builds the replacement (which keeps the original as `.replaced`).  With context=True the wrapper is called as
+    wrappers[name](replaced, defining module, **options), options being those of the install() call that placed the seam."""
 
-    def __init__(self, keyword, module, names, users, wrappers):
+    def __init__(self, keyword, module, names, users, wrappers, context=False):
         self.keyword, self.module, self.names, self.users, self.wrappers = keyword, module, tuple(names), tuple(users), wrappers
+        self.context, self.options = context, {}
 
     def ready(self, mod) -> bool:
         return mod is not None and all(hasattr(mod, n) for n in self.names)
@@ -456,7 +112,10 @@ class _Seam:
         out = {}
         for name in self.names:
             cur = getattr(mod, name)
-            fn = cur if getattr(cur, "replaced", None) is not None else self.wrappers[name](cur)
+            if getattr(cur, "replaced", None) is not None:
+                fn = cur
+            else:
+                fn = self.wrappers[name](cur, mod, **self.options) if self.context else self.wrappers[name](cur)
             setattr(mod, name, fn)
             for user in self.users:
                 um = sys.modules.get(user)
@@ -478,20 +137,28 @@ class _Seam:
                     if um is not None and getattr(um, name, None) is cur:
                         setattr(um, name, cur.replaced)
 
-    def install(self):
-        """Patch now if the module is imported, else put a _SeamPatcher on sys.meta_path.  Returns {name: function} or None."""
+    def install(self, **options):
+        """Patch now if the module is imported, else put a _SeamPatcher on sys.meta_path.  Returns {name: function} or None.
+        A pending hook keeps the options of the call that placed it."""
         mod = sys.modules.get(self.module)
         if self.ready(mod):
+            self.options = options
             return self.patch(mod)
         if not any(isinstance(f, _SeamPatcher) and f.seam is self for f in sys.meta_path):
+            self.options = options
             sys.meta_path.insert(0, _SeamPatcher(self))
         return None
 
 
 class _SeamPatcher(importlib.abc.MetaPathFinder):
     """The import hook of a _Seam installed before its module is imported: patch the module as it is first loaded, and — for an
-    import made through a finder ahead of this one (jaxtyping's hook, see _MetricsPatcher) — at the next import this finder is
-    asked about, before a step can call the functions."""
+    import made through a finder ahead of this one — at the next import this finder is asked about, before a step can call the
+    functions.  ANY later import is a chance to patch: the reference imports its packages inside jaxtyping's install_import_hook
+    (the reference's src/main.py:22-36), whose own finder is inserted at sys.meta_path[0] afterwards and resolves every `src.*`
+    module by calling PathFinder directly — this finder is then never asked for the seam's module itself, but it is
+    asked for the first non-`src` module imported after it (the encoder's third-party imports, still inside that `with` block and
+    long before get_decoder runs at main.py:168).  A failure on that late path warns and never surfaces from the unrelated
+    third-party import; a failure while the seam's own module loads through this finder's loader propagates."""
 
     def __init__(self, seam):
         self.seam, self.busy = seam, False
@@ -551,6 +218,116 @@ class _SeamPatcher(importlib.abc.MetaPathFinder):
         return spec
 
 
+class _RegistrySeam(_Seam):
+    """The seam on the reference's decoder registry: the patched thing is the dict entry DECODERS[REGISTRY_KEY] of `module`, and
+    the options are those of make_decoder_class."""
+
+    def __init__(self, keyword, module, key):
+        super().__init__(keyword, module, (key,), (), {})
+
+    def ready(self, mod) -> bool:
+        return isinstance(getattr(mod, "DECODERS", None), dict) and self.names[0] in mod.DECODERS
+
+    def patch(self, mod) -> dict:
+        """Register a fused class built with the latest options from the reference's own class, which stays reachable as
+        `.replaced` however often the registry is patched."""
+        key = self.names[0]
+        cur = mod.DECODERS.get(key)
+        base = importlib.import_module(self.module + ".decoder")
+        cls = make_decoder_class(base.Decoder, base.DecoderOutput, **self.options)
+        cls.replaced = getattr(cur, "replaced", None) or cur
+        mod.DECODERS[key] = cls
+        return {key: cls}
+
+    def restore(self) -> None:
+        mod = sys.modules.get(self.module)
+        cur = mod.DECODERS[self.names[0]] if self.ready(mod) else None
+        if getattr(cur, "replaced", None) is not None:
+            mod.DECODERS[self.names[0]] = cur.replaced
+
+
+DECODER_SEAM = _RegistrySeam("lazy", REGISTRY_MODULE, REGISTRY_KEY)
+
+
+def _native_adapter(replaced, mod, **aopts):
+    """The class the reference's encoder instantiates (encoder_costvolume.py:185) on the lazy-field path of lazy.py: a subclass of
+    the replaced class that returns the defining module's own adapter-side container."""
+    from . import lazy as _lz
+    cls = _lz.make_adapter_class(replaced, getattr(mod, "Gaussians", None), **aopts)
+    cls.replaced = replaced
+    return cls
+
+
+ADAPTER_SEAM = _Seam("adapter", ADAPTER_MODULE, (ADAPTER_NAME,), ADAPTER_USERS, {ADAPTER_NAME: _native_adapter}, context=True)
+
+
+METRICS_MODULE = "src.evaluation.metrics"                              # defines compute_ssim (:38-54)
+METRICS_USERS = ("src.model.model_wrapper_erp",                        # `from ..evaluation.metrics import ... compute_ssim` (:18)
+                 "src.model.model_wrapper_cubemaps",                   # (:19)
+                 "src.evaluation.metric_computer")                     # (:12)
+METRICS_NAME = "compute_ssim"
+
+
+def _native_compute_ssim(replaced):
+    """compute_ssim with the reference's signature: the SSIM kernel for GPU tensors, the replaced function otherwise."""
+    from . import metrics as _metrics
+
+    def compute_ssim(ground_truth, predicted):
+        if ground_truth.is_cuda and predicted.is_cuda:
+            return _metrics.compute_ssim(ground_truth, predicted)
+        return replaced(ground_truth, predicted)
+
+    compute_ssim.replaced = replaced
+    compute_ssim.__doc__ = _metrics.compute_ssim.__doc__
+    return compute_ssim
+
+
+DEPTH_MODULE = "src.model.model_wrapper_helper"                       # defines erode (:4-24) and compute_l1_sphere_loss (:63-90)
+DEPTH_USERS = ("src.model.model_wrapper_erp",)                         # `from .model_wrapper_helper import compute_l1_sphere_loss, erode` (:45)
+DEPTH_NAMES = ("compute_l1_sphere_loss", "erode")
+
+
+def _is_cuda_f32(t) -> bool:
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+
+
+def _native_l1_sphere_loss(replaced):
+    """compute_l1_sphere_loss with the reference's signature: the depth-loss kernels for float32 GPU tensors of one [B,V,H,W]
+    shape with a mask that takes no gradient, the replaced function otherwise (mask=None included: it raises there)."""
+    from . import depth_loss as _dl
+
+    def compute_l1_sphere_loss(y_pred, y_true, mask=None, keep_batch=False):
+        if (mask is not None and all(_is_cuda_f32(t) for t in (y_pred, y_true, mask)) and y_pred.dim() == 4
+                and y_true.shape == y_pred.shape and mask.shape == y_pred.shape and not mask.requires_grad
+                and y_pred.numel() > 0 and y_pred.device == y_true.device == mask.device):
+            return _dl.compute_l1_sphere_loss(y_pred, y_true, mask, keep_batch)
+        return replaced(y_pred, y_true, mask=mask, keep_batch=keep_batch)
+
+    compute_l1_sphere_loss.replaced = replaced
+    compute_l1_sphere_loss.__doc__ = _dl.compute_l1_sphere_loss.__doc__
+    return compute_l1_sphere_loss
+
+
+def _native_erode(replaced):
+    """erode with the reference's signature: the erosion kernel for [C,H,W] / [N,C,H,W] float32 GPU tensors that take no gradient,
+    an odd ksize and a reflect pad below H and W; the replaced function otherwise."""
+    from . import depth_loss as _dl
+
+    def erode(bin_img, ksize=5):
+        if (_is_cuda_f32(bin_img) and bin_img.dim() in (3, 4) and not bin_img.requires_grad and isinstance(ksize, int)
+                and ksize >= 1 and ksize % 2 == 1 and (ksize - 1) // 2 < min(bin_img.shape[-2], bin_img.shape[-1])):
+            return _dl.erode(bin_img, ksize)
+        return replaced(bin_img, ksize)
+
+    erode.replaced = replaced
+    erode.__doc__ = _dl.erode.__doc__
+    return erode
+
+
+_DEPTH_WRAPPERS = {"compute_l1_sphere_loss": _native_l1_sphere_loss, "erode": _native_erode}
+DEPTH_LOSS_SEAM = _Seam("depth_loss", DEPTH_MODULE, DEPTH_NAMES, DEPTH_USERS, _DEPTH_WRAPPERS)
+
+
 DEPTH_METRICS_MODULE = "src.scripts.compute_depth_metrics"            # defines compute_depth_metrics_batched (:47-116)
 DEPTH_METRICS_USERS = ("src.model.model_wrapper_erp",)                 # `from ..scripts.compute_depth_metrics import compute_depth_metrics_batched` (:47)
 DEPTH_METRICS_NAME = "compute_depth_metrics_batched"
@@ -593,6 +370,7 @@ def _native_compute_psnr(replaced):
 
 DEPTH_METRICS_SEAM = _Seam("depth_metrics", DEPTH_METRICS_MODULE, (DEPTH_METRICS_NAME,), DEPTH_METRICS_USERS,
                            {DEPTH_METRICS_NAME: _native_depth_metrics})
+SSIM_SEAM = _Seam("metrics", METRICS_MODULE, (METRICS_NAME,), METRICS_USERS, {METRICS_NAME: _native_compute_ssim})
 PSNR_SEAM = _Seam("psnr", METRICS_MODULE, (PSNR_NAME,), METRICS_USERS, {PSNR_NAME: _native_compute_psnr})
 
 
@@ -994,13 +772,6 @@ WINDOW_ATTENTION_SEAM = _Seam("window_attention", WINDOW_ATTENTION_MODULE, WINDO
                                WINDOW_ATTENTION_MASK: _native_shift_mask, WINDOW_ATTENTION_MULTI: _native_multi_head_attention})
 
 
-def install_window_attention():
-    """The half of install(window_attention=True): rebind the backbone module's single_head_split_window_attention,
-    single_head_full_attention, generate_shift_window_attn_mask and multi_head_split_window_attention now if the module is
-    imported, else as soon as it is (import hook).  Returns {name: patched function} or None."""
-    return WINDOW_ATTENTION_SEAM.install()
-
-
 GROUP_NORM_UNET_MODULE = "src.model.encoder.costvolume.ldm_unet.unet"   # defines ResBlock (:176-307) and AttentionBlock (:310-380)
 GROUP_NORM_RESBLOCK = "ResBlock"
 GROUP_NORM_ATTENTION = "AttentionBlock"
@@ -1122,25 +893,74 @@ GROUP_NORM_RESIDUAL_SEAM = _MethodSeam("group_norm", GROUP_NORM_BACKBONE_MODULE,
 GROUP_NORM_SEAMS = (GROUP_NORM_RESBLOCK_SEAM, GROUP_NORM_ATTENTION_SEAM, GROUP_NORM_PREDICTOR_SEAM, GROUP_NORM_RESIDUAL_SEAM)
 
 
+# install()'s option keywords -> their seams, in installation order; the decoder registry (DECODER_SEAM) comes after them.
+# uninstall() restores exactly these, so a new seam is a new entry here and nothing else.
+OPTION_SEAMS = {
+    "adapter": (ADAPTER_SEAM,),
+    "metrics": (SSIM_SEAM,),
+    "depth_loss": (DEPTH_LOSS_SEAM,),
+    "depth_metrics": (DEPTH_METRICS_SEAM,),
+    "psnr": (PSNR_SEAM,),
+    "cost_volume": (COST_VOLUME_SEAM,),
+    "depth_head": (DEPTH_HEAD_SEAM,),
+    "depth_tail": (DEPTH_TAIL_F_SEAM, DEPTH_TAIL_METHOD_SEAM),
+    "erp_distance": (ERP_DISTANCE_SEAM,),
+    "visualization": VIS_SEAMS,
+    "depth_smoothness": (DEPTH_SMOOTH_SEAM,),
+    "window_attention": (WINDOW_ATTENTION_SEAM,),
+    "group_norm": GROUP_NORM_SEAMS,
+}
+
+
+def _installed(keyword, **options) -> list:
+    """Install every seam of one option; per seam, what its first name is bound to now, or None while its hook is pending."""
+    bound = []
+    for seam in OPTION_SEAMS[keyword]:
+        out = seam.install(**options)
+        bound.append(None if out is None else out[seam.names[0]])
+    return bound
+
+
+def install_adapter(**aopts):
+    """The adapter half of install(adapter=True): see lazy.py.  Patches now if the reference's adapter module is already imported,
+    else as soon as it is (import hook).  Returns the class or None.  aopts: sh_rotation ("native"), differentiable_means (False),
+    lazy (True)."""
+    return _installed("adapter", **aopts)[0]
+
+
+def install_metrics():
+    """The metrics half of install(metrics=True): rebind compute_ssim now if the reference's metrics module is imported, else as
+    soon as it is (import hook).  Returns the patched function or None."""
+    return _installed("metrics")[0]
+
+
+def install_depth_loss():
+    """The depth-loss half of install(depth_loss=True): rebind compute_l1_sphere_loss and erode now if the reference's helper
+    module is imported, else as soon as it is (import hook).  Returns {name: patched function} or None."""
+    return DEPTH_LOSS_SEAM.install()
+
+
+def install_window_attention():
+    """The half of install(window_attention=True): rebind the backbone module's single_head_split_window_attention,
+    single_head_full_attention, generate_shift_window_attn_mask and multi_head_split_window_attention now if the module is
+    imported, else as soon as it is (import hook).  Returns {name: patched function} or None."""
+    return WINDOW_ATTENTION_SEAM.install()
+
+
 def install_group_norm():
     """The half of install(group_norm=True): rebind ResBlock._forward and AttentionBlock._forward (ldm_unet/unet.py),
     DepthPredictorMultiView360.__init__ and the CNN backbone's ResidualBlock.forward to the wrappers around the fused
     norm + activation (+ residual) kernels of group_norm.py, each now if its module is imported, else as soon as it is (import
     hooks).  Returns {"Class.method": patched method or None}.  Modules built before the call keep their (norm, activation) pairs;
     group_norm.fuse_pairs(module) is the direct API for them."""
-    out = {}
-    for seam in GROUP_NORM_SEAMS:
-        got = seam.install()
-        out[f"{seam.cls_name}.{seam.names[0]}"] = None if got is None else got[seam.names[0]]
-    return out
+    return dict(zip((f"{seam.cls_name}.{seam.names[0]}" for seam in GROUP_NORM_SEAMS), _installed("group_norm")))
 
 
 def install_depth_smoothness():
     """The half of install(depth_smoothness=True): rebind LossDepth.forward (src/loss/loss_depth.py:27-60) to the wrapper around
     the depth-smoothness kernels now if the reference's module is imported, else as soon as it is (import hook).  Returns the
     patched method or None."""
-    out = DEPTH_SMOOTH_SEAM.install()
-    return None if out is None else out[DEPTH_SMOOTH_METHOD]
+    return _installed("depth_smoothness")[0]
 
 
 def install_depth_tail():
@@ -1148,16 +968,14 @@ def install_depth_tail():
     EncoderCostVolume.map_pdf_to_opacity to the opacity-map wrapper, each now if its module is imported, else as soon as it is
     (import hooks).  Returns (proxy or None, method or None).  The predictor's :694-719 have no seam (inline arithmetic that ends in
     einops.repeat): depth_tail.fine_depth_tail is the direct API for them."""
-    f, m = DEPTH_TAIL_F_SEAM.install(), DEPTH_TAIL_METHOD_SEAM.install()
-    return (None if f is None else f[DEPTH_HEAD_NAME]), (None if m is None else m[DEPTH_TAIL_METHOD])
+    return tuple(_installed("depth_tail"))
 
 
 def install_erp_distance():
     """The half of install(erp_distance=True): rebind depth_to_distance_map_batch now if the reference's module is imported, else
     as soon as it is (import hook).  Returns the patched function or None.  The evaluation step's reorder + conversion + stitch
     (model_wrapper_erp.py:446-463) are inline statements: stitch.Cube2Equirec.stitch_distance_rendered is the direct API for them."""
-    out = ERP_DISTANCE_SEAM.install()
-    return None if out is None else out[ERP_DISTANCE_NAME]
+    return _installed("erp_distance")[0]
 
 
 def install_visualization():
@@ -1165,39 +983,32 @@ def install_visualization():
     (image_io.py:38-54) and apply_color_map (color_map.py:9-19), each now if its module is imported, else as soon as it is (import
     hooks).  Returns {name: patched function or None}.  convert_single_colormap returns a CPU tensor by contract and the per-frame
     loops of test_step are inline: visualize.error_map and the batched visualize.depth_map are the direct API for them."""
-    out = {}
-    for seam in VIS_SEAMS:
-        got = seam.install()
-        out[seam.names[0]] = None if got is None else got[seam.names[0]]
-    return out
+    return dict(zip((seam.names[0] for seam in VIS_SEAMS), _installed("visualization")))
 
 
 def install_depth_head():
     """The half of install(depth_head=True): rebind the encoder module's `F` to the softmax proxy now if the module is imported,
     else as soon as it is (import hook).  Returns the proxy or None."""
-    out = DEPTH_HEAD_SEAM.install()
-    return None if out is None else out[DEPTH_HEAD_NAME]
+    return _installed("depth_head")[0]
 
 
 def install_cost_volume():
     """The half of install(cost_volume=True): rebind the encoder module's warp_with_pose_depth_candidates now if the module is
     imported, else as soon as it is (import hook).  Returns the patched function or None."""
-    out = COST_VOLUME_SEAM.install()
-    return None if out is None else out[COST_VOLUME_NAME]
+    return _installed("cost_volume")[0]
 
 
 def install_depth_metrics():
     """The half of install(depth_metrics=True): rebind compute_depth_metrics_batched now if the reference's module is imported,
     else as soon as it is (import hook).  Returns the patched function or None."""
-    out = DEPTH_METRICS_SEAM.install()
-    return None if out is None else out[DEPTH_METRICS_NAME]
+    return _installed("depth_metrics")[0]
 
 
 def install_psnr():
     """The half of install(psnr=True): rebind compute_psnr now if the reference's metrics module is imported, else as soon as it
     is (import hook).  Returns the patched function or None."""
-    out = PSNR_SEAM.install()
-    return None if out is None else out[PSNR_NAME]
+    return _installed("psnr")[0]
+
 
 
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
@@ -1244,39 +1055,16 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     the fused decoder.  lazy=True: only installs an import hook that patches the registry when the reference itself first imports
     the package (for a sitecustomize that runs before sys.path is set up).  Idempotent.
     opts: views_per_group (6), shared_campos (None = checked per group with one small read per forward), check ("sync"), glue."""
-    if adapter:
-        install_adapter(**(adapter_options or {}))
-    if metrics:
-        install_metrics()
-    if depth_loss:
-        install_depth_loss()
-    if depth_metrics:
-        install_depth_metrics()
-    if psnr:
-        install_psnr()
-    if cost_volume:
-        install_cost_volume()
-    if depth_head:
-        install_depth_head()
-    if depth_tail:
-        install_depth_tail()
-    if erp_distance:
-        install_erp_distance()
-    if visualization:
-        install_visualization()
-    if depth_smoothness:
-        install_depth_smoothness()
-    if window_attention:
-        install_window_attention()
-    if group_norm:
-        install_group_norm()
+    given = locals()
+    for keyword, seams in OPTION_SEAMS.items():
+        if given[keyword]:
+            for seam in seams:
+                seam.install(**(given.get(keyword + "_options") or {}))
     if lazy:
-        if REGISTRY_MODULE in sys.modules:
-            return _patch(sys.modules[REGISTRY_MODULE], **opts)
-        if not any(isinstance(f, _LazyPatcher) for f in sys.meta_path):
-            sys.meta_path.insert(0, _LazyPatcher(opts))
-        return None
-    return _patch(importlib.import_module(REGISTRY_MODULE), **opts)
+        out = DECODER_SEAM.install(**opts)
+        return None if out is None else out[REGISTRY_KEY]
+    DECODER_SEAM.options = opts
+    return DECODER_SEAM.patch(importlib.import_module(REGISTRY_MODULE))[REGISTRY_KEY]      # any error propagates
 
 
 def uninstall() -> None:
@@ -1285,41 +1073,7 @@ def uninstall() -> None:
     apply_color_map, EncoderCostVolume.map_pdf_to_opacity, LossDepth.forward, the backbone module's four attention functions,
     ResBlock._forward, AttentionBlock._forward, ResidualBlock.forward, DepthPredictorMultiView360.__init__ and the predictor
     module's `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
-    sys.meta_path[:] = [f for f in sys.meta_path
-                        if not isinstance(f, (_LazyPatcher, _AdapterPatcher, _MetricsPatcher, _DepthLossPatcher, _SeamPatcher))]
-    for seam in (DEPTH_METRICS_SEAM, PSNR_SEAM, COST_VOLUME_SEAM, DEPTH_HEAD_SEAM, DEPTH_TAIL_F_SEAM, DEPTH_TAIL_METHOD_SEAM, ERP_DISTANCE_SEAM,
-                 DEPTH_SMOOTH_SEAM, WINDOW_ATTENTION_SEAM, *GROUP_NORM_SEAMS, *VIS_SEAMS):
-        seam.restore()
-    dmod = sys.modules.get(DEPTH_MODULE)
-    if dmod is not None:
-        for name in DEPTH_NAMES:
-            cur = getattr(dmod, name, None)
-            if getattr(cur, "replaced", None) is not None:
-                setattr(dmod, name, cur.replaced)
-                for user in DEPTH_USERS:
-                    um = sys.modules.get(user)
-                    if um is not None and getattr(um, name, None) is cur:
-                        setattr(um, name, cur.replaced)
-    mmod = sys.modules.get(METRICS_MODULE)
-    if mmod is not None:
-        cur = getattr(mmod, METRICS_NAME, None)
-        if getattr(cur, "replaced", None) is not None:
-            setattr(mmod, METRICS_NAME, cur.replaced)
-            for user in METRICS_USERS:
-                um = sys.modules.get(user)
-                if um is not None and getattr(um, METRICS_NAME, None) is cur:
-                    setattr(um, METRICS_NAME, cur.replaced)
-    amod = sys.modules.get(ADAPTER_MODULE)
-    if amod is not None:
-        cur = getattr(amod, ADAPTER_NAME, None)
-        if getattr(cur, "replaced", None) is not None:
-            setattr(amod, ADAPTER_NAME, cur.replaced)
-            for user in ADAPTER_USERS:
-                um = sys.modules.get(user)
-                if um is not None and getattr(um, ADAPTER_NAME, None) is cur:
-                    setattr(um, ADAPTER_NAME, cur.replaced)
-    pkg = sys.modules.get(REGISTRY_MODULE)
-    if pkg is not None:
-        cur = pkg.DECODERS.get(REGISTRY_KEY)
-        if getattr(cur, "replaced", None) is not None:
-            pkg.DECODERS[REGISTRY_KEY] = cur.replaced
+    sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, _SeamPatcher)]
+    for seams in (*OPTION_SEAMS.values(), (DECODER_SEAM,)):
+        for seam in seams:
+            seam.restore()

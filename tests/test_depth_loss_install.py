@@ -62,7 +62,7 @@ PRELUDE = textwrap.dedent("""
 
     def hooks():
         from splatter360_amd import plugin
-        return [f for f in sys.meta_path if isinstance(f, plugin._DepthLossPatcher)]
+        return [f for f in sys.meta_path if isinstance(f, plugin._SeamPatcher) and f.seam is plugin.DEPTH_LOSS_SEAM]
 """)
 
 

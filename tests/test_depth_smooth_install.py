@@ -64,7 +64,7 @@ PRELUDE = textwrap.dedent("""
         return sys.modules[MOD].LossDepth.__dict__["forward"]
 
     def hooks():
-        return [f.seam for f in sys.meta_path if isinstance(f, plugin._SeamPatcher)]
+        return [f.seam for f in sys.meta_path if isinstance(f, plugin._SeamPatcher) and f.seam is plugin.DEPTH_SMOOTH_SEAM]
 
     def call(loss, depth, near, far, image=None):
         return loss(types.SimpleNamespace(depth=depth), {{"target": {{"near": near, "far": far, "image": image}}}}, None, 0)

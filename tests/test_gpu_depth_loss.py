@@ -266,7 +266,7 @@ def test_installed_wrappers_run_the_kernels(gpu):
         return torch_loss(y_pred, y_true, mask, keep_batch)
 
     mod.erode, mod.compute_l1_sphere_loss = erode, compute_l1_sphere_loss
-    fns = plugin._patch_depth_loss(mod)
+    fns = plugin.DEPTH_LOSS_SEAM.patch(mod)
     pred, target, mask, depth, _ = _inputs((2, 2, 32, 64), gpu, seed=4)
     m = (depth > 0.1).float().view(4, 1, 32, 64)
     assert _bits_equal(mod.erode(m), depth_loss.erode(m))

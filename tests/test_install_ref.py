@@ -205,10 +205,108 @@ def test_lazy_install_survives_a_competing_finder_that_resolves_src_itself(stand
         import colorsys                                                            # any later non-src import (main.py: the encoder's)
         dec = get_decoder(cfg, dcfg)
         assert type(dec).__name__ == "DecoderSplattingFusedMI355X", type(dec)
-        assert not any(type(f).__name__ == "_LazyPatcher" for f in sys.meta_path)
+        from splatter360_amd import plugin
+        assert not any(isinstance(f, plugin._SeamPatcher) and f.seam is plugin.DECODER_SEAM for f in sys.meta_path)
         print("ok")
     """)
     assert out.strip().endswith("ok")
+
+
+COMPETING = textwrap.dedent("""
+    import importlib.abc, importlib.machinery
+    class Competing(importlib.abc.MetaPathFinder):          # what jaxtyping's hook does: first in line, PathFinder for src.*
+        def find_spec(self, fullname, path, target=None):
+            if fullname == "src" or fullname.startswith("src."):
+                return importlib.machinery.PathFinder.find_spec(fullname, path, target)
+            return None
+""")
+
+
+def test_adapter_install_survives_a_competing_finder_that_resolves_src_itself(standin):
+    """behind jaxtyping's finder the adapter's hook never sees the adapter module either.  The next import it is asked
+    about replaces the class, in the defining module and in the encoder module that already bound the name, and the hook leaves
+    sys.meta_path."""
+    out = _run(standin, COMPETING + textwrap.dedent("""
+        import splatter360_amd
+        from splatter360_amd import plugin
+        assert splatter360_amd.install(lazy=True, adapter=True) is None
+        sys.meta_path.insert(0, Competing())
+        import src.model.encoder.common.gaussian_adapter_erp as amod
+        ref_cls = amod.GaussianAdapterERP
+        assert ref_cls.__name__ == "GaussianAdapterERP" and getattr(ref_cls, "replaced", None) is None    # the hook was bypassed
+        # a stand-in for the encoder module that already executed its `from .common.gaussian_adapter_erp import GaussianAdapterERP`
+        enc = types.ModuleType("src.model.encoder.encoder_costvolume"); enc.GaussianAdapterERP = ref_cls
+        sys.modules["src.model.encoder.encoder_costvolume"] = enc
+        assert "colorsys" not in sys.modules
+        import colorsys                                          # any later import the hook is asked about
+        assert amod.GaussianAdapterERP.__name__ == "GaussianAdapterERPFusedMI355X", amod.GaussianAdapterERP
+        assert amod.GaussianAdapterERP.replaced is ref_cls and enc.GaussianAdapterERP is amod.GaussianAdapterERP
+        assert not any(isinstance(f, plugin._SeamPatcher) and f.seam is plugin.ADAPTER_SEAM for f in sys.meta_path)
+        splatter360_amd.uninstall()
+        assert amod.GaussianAdapterERP is ref_cls and enc.GaussianAdapterERP is ref_cls
+        print("ok")
+    """))
+    assert out.strip().endswith("ok")
+
+
+def test_every_pending_hook_is_served_at_the_same_import(standin):
+    """A hook that patches late leaves sys.meta_path while the import system walks it, and the walk skips the next entry: the
+    hook serves the other pending ones itself, so the registry and the adapter are both patched after ONE later import."""
+    out = _run(standin, COMPETING + textwrap.dedent("""
+        import splatter360_amd
+        from splatter360_amd import plugin
+        assert splatter360_amd.install(lazy=True, adapter=True) is None
+        assert sum(isinstance(f, plugin._SeamPatcher) for f in sys.meta_path) == 2
+        sys.meta_path.insert(0, Competing())
+        from src.model.decoder import DECODERS
+        import src.model.encoder.common.gaussian_adapter_erp as amod
+        ref_dec, ref_cls = DECODERS["splatting_cuda"], amod.GaussianAdapterERP
+        assert ref_dec.__name__ == "DecoderSplattingCUDA" and ref_cls.__name__ == "GaussianAdapterERP"   # both hooks were bypassed
+        assert "colorsys" not in sys.modules
+        import colorsys
+        assert DECODERS["splatting_cuda"].__name__ == "DecoderSplattingFusedMI355X" and DECODERS["splatting_cuda"].replaced is ref_dec
+        assert amod.GaussianAdapterERP.__name__ == "GaussianAdapterERPFusedMI355X" and amod.GaussianAdapterERP.replaced is ref_cls
+        assert not any(isinstance(f, plugin._SeamPatcher) for f in sys.meta_path)
+        print("ok")
+    """))
+    assert out.strip().endswith("ok")
+
+
+def test_install_twice_uninstall_once_restores_the_reference_decoder(standin):
+    """A repeated install() rebuilds the fused class from the reference's class with the latest call's options: `.replaced` never
+    is a fused class, and one uninstall() puts the reference's class back."""
+    out = _run(standin, """
+        import splatter360_amd
+        first = splatter360_amd.install()
+        from src.model.decoder import DECODERS, get_decoder
+        ref_dec = first.replaced
+        assert ref_dec.__name__ == "DecoderSplattingCUDA" and get_decoder(cfg, dcfg).fused.check == "sync"
+        second = splatter360_amd.install(check="lazy")
+        assert DECODERS["splatting_cuda"] is second and second is not first
+        assert second.replaced is ref_dec, second.replaced
+        assert get_decoder(cfg, dcfg).fused.check == "lazy"
+        splatter360_amd.uninstall()
+        assert DECODERS["splatting_cuda"] is ref_dec
+        print("ok")
+    """)
+    assert out.strip().endswith("ok")
+
+
+def test_the_option_table_holds_every_seam_and_every_keyword():
+    """uninstall() restores the seams of plugin.OPTION_SEAMS and the decoder seam, nothing else: a seam defined in the module but
+    missing from the table would never be undone, and a keyword of install() missing from it would never be installed."""
+    import inspect
+
+    from splatter360_amd import plugin
+    defined = []
+    for value in vars(plugin).values():
+        defined += [s for s in (value if isinstance(value, tuple) else (value,)) if isinstance(s, plugin._Seam)]
+    table = [s for seams in plugin.OPTION_SEAMS.values() for s in seams]
+    assert len(set(map(id, table))) == len(table) and plugin.DECODER_SEAM not in table
+    assert {id(s) for s in defined} == {id(s) for s in table} | {id(plugin.DECODER_SEAM)}
+    assert all(s.keyword == keyword for keyword, seams in plugin.OPTION_SEAMS.items() for s in seams)
+    params = inspect.signature(plugin.install).parameters.values()
+    assert {p.name for p in params if p.kind is p.KEYWORD_ONLY} == set(plugin.OPTION_SEAMS) | {"lazy", "adapter_options"}
 
 
 ADAPTER_PRELUDE = textwrap.dedent("""

@@ -102,7 +102,7 @@ def test_install_before_import_patches_on_first_import(standin):
         assert len(fns) == 4 and all_native(fns) and len(set(fns.values())) == 1, fns
         # the hook is gone once it has patched
         from splatter360_amd import plugin
-        assert not any(isinstance(f, plugin._MetricsPatcher) for f in sys.meta_path)
+        assert not any(isinstance(f, plugin._SeamPatcher) and f.seam is plugin.SSIM_SEAM for f in sys.meta_path)
         splatter360_amd.uninstall()
         original = sys.modules["src.evaluation.metrics"].compute_ssim
         assert getattr(original, "replaced", None) is None and all(f is original for f in bound().values())
@@ -145,9 +145,9 @@ def test_uninstall_drops_a_pending_hook(standin):
         import splatter360_amd
         from splatter360_amd import plugin
         splatter360_amd.install(metrics=True)
-        assert any(isinstance(f, plugin._MetricsPatcher) for f in sys.meta_path)
+        assert any(isinstance(f, plugin._SeamPatcher) and f.seam is plugin.SSIM_SEAM for f in sys.meta_path)
         splatter360_amd.uninstall()
-        assert not any(isinstance(f, plugin._MetricsPatcher) for f in sys.meta_path)
+        assert not any(isinstance(f, plugin._SeamPatcher) and f.seam is plugin.SSIM_SEAM for f in sys.meta_path)
         import src.model.model_wrapper_erp
         assert not all_native(bound()) and len(bound()) == 2
         print("ok")
@@ -165,7 +165,7 @@ def test_default_install_leaves_compute_ssim_alone(standin):
         assert DECODERS["splatting_cuda"].__name__ == "DecoderSplattingFusedMI355X"
         assert all(f is original for f in bound().values())
         from splatter360_amd import plugin
-        assert not any(isinstance(f, plugin._MetricsPatcher) for f in sys.meta_path)
+        assert not any(isinstance(f, plugin._SeamPatcher) and f.seam is plugin.SSIM_SEAM for f in sys.meta_path)
         import src.model.model_wrapper_cubemaps
         assert all(f is original for f in bound().values()) and len(bound()) == 3
         print("ok")
