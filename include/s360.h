@@ -976,6 +976,38 @@ int s360_window_attention_backward(const float* q, const float* k, const float* 
                                    float* g_v, void* stream);
 
 /*
+ * The U-Nets' multi-head QKV attention, forward and backward (the reference's QKVAttentionLegacy and QKVAttention,
+ * src/model/encoder/costvolume/ldm_unet/unet.py:527-599), on the channel-major qkv tensor where it lies: no [b heads, L, L]
+ * weight tensor, no softmax of it and no permuted copy of q, k, v or the output is formed, forward or backward.
+ *   qkv[rows, heads * 3 * ch, tokens] float32 contiguous; B = rows / views batch elements.  The joint sequence of batch element bi
+ *   has L = views * tokens tokens; joint token s is token s mod tokens of view u = s / tokens and lives in row u * B + bi (the
+ *   reference's "(v b) n t -> b n (v t)"); views = 1 is attention within every row (use_cross_view_self_attn off).
+ *   order S360_QKV_LEGACY: head hd owns channel rows [hd * 3 * ch, (hd + 1) * 3 * ch), ch rows of q, then k, then v;
+ *   S360_QKV_NEW: the channel axis is q | k | v chunks of heads * ch rows and head hd owns [hd * ch, (hd + 1) * ch) of each.
+ *   score = float32((q . k) / sqrt(ch)) (the reference scales q and k by ch^-1/4 each; here the scale is applied once, to the sum),
+ *   q . k summed in float64 over float32 fma chains of 8 channels; out[rows, heads * ch, tokens] = softmax over the L keys times v,
+ *   in the rows' order of qkv; lse[B, heads, L] FLOAT64 = max + log(sum exp(score - max)) (float32 running maximum, float64 running sum).
+ * Products run on v_mfma_f32_32x32x2_f32 exactly as in s360_window_attention_* above, with the scores kept in float64 until the
+ * maximum or lse is subtracted and the products over the keys added in float64 from float32 chains of 32 keys.  A workgroup is
+ * four waves on one tile of 32 queries (keys in the key-owned pass): each wave walks every fourth tile of the other side, staged
+ * through LDS from reads along the token axis, one dword per lane, so tokens may be any number and rows need no alignment; the
+ * four partial results are combined in a fixed order.
+ * s360_qkv_attention_backward takes the forward's lse and g_out[rows, heads * ch, tokens] and writes g_qkv in qkv's layout:
+ * probabilities recomputed as exp(score - lse), dS = P (dP - Delta); delta[B, heads, L] FLOAT64 is scratch the call fills with
+ * Delta = sum_s P dP / sum_s P per query (sum P is 1 but for rounding; dividing by it makes sum_s dS = 0 hold for the P in use).  The pass owned by query tiles runs first (Delta, then the q rows), the pass owned by key tiles
+ * second (the k and v rows): every element of g_qkv is written once, by one wave, in a fixed order — no atomics, bit-identical
+ * from run to run and across streams.
+ * No host synchronisation, no allocation.  ch != 32: S360_E_UNSUPPORTED.  Null pointers, sizes < 1, views not dividing
+ * rows, an unknown order, g_qkv == qkv, or 2^31 or more joint tokens or workgroups: S360_E_BADARG before any GPU work.
+ */
+#define S360_QKV_LEGACY 0
+#define S360_QKV_NEW 1
+int s360_qkv_attention_forward(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens, int32_t order,
+                               float* out, double* lse, void* stream);
+int s360_qkv_attention_backward(const float* qkv, const double* lse, const float* g_out, int32_t rows, int32_t views, int32_t heads,
+                                int32_t ch, int32_t tokens, int32_t order, double* delta, float* g_qkv, void* stream);
+
+/*
  * The encoder's normalise-then-activate pair, forward and backward: GroupNorm (the reference's GroupNorm8 / GroupNorm4,
  * src/model/encoder/costvolume/ldm_unet/util.py:199-238, and nn.GroupNorm at depth_predictor_multiview_360.py:425-427, :480-482)
  * or InstanceNorm2d without affine (groups == channels; backbone/unimatch/backbone.py:28-36), the activation that follows it

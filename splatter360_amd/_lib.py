@@ -16,7 +16,7 @@ _CSRC = _PKG / "csrc"
 LIB_PATH = _PKG / "libs360.so"
 SOURCES = ("s360_forward.hip", "s360_backward.hip", "s360_backward_em.hip", "s360_stitch.hip", "s360_views.hip", "s360_adapter.hip", "s360_metrics.hip",
            "s360_depth_loss.hip", "s360_eval_scores.hip", "s360_cost_volume.hip", "s360_depth_head.hip", "s360_depth_tail.hip", "s360_equirec2cube.hip", "s360_visualize.hip",
-           "s360_depth_smooth.hip", "s360_window_attention.hip", "s360_group_norm.hip")
+           "s360_depth_smooth.hip", "s360_window_attention.hip", "s360_group_norm.hip", "s360_qkv_attention.hip")
 # per-source extra flags (s360_backward_em.hip: see the launcher comment in csrc/s360_bwd_em.h)
 SOURCE_FLAGS = {"s360_backward_em.hip": ("-fno-slp-vectorize",)}
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result")
@@ -37,6 +37,7 @@ FLAG_COOP_WALK = 2048
 DS_SECOND = 1        # s360_depth_smooth_*: flags
 DS_BILATERAL = 2
 GN_ACT_NONE, GN_ACT_RELU, GN_ACT_SILU, GN_ACT_GELU = 0, 1, 2, 3   # s360_group_norm_*: activation
+QKV_LEGACY, QKV_NEW = 0, 1                                        # s360_qkv_attention_*: order
 ABI_VERSION = 25
 
 
@@ -72,7 +73,8 @@ EXPORTS = ("s360_forward_raw", "s360_backward_raw", "s360_backward_raw_tail", "s
            "s360_depth_colormap", "s360_colorize", "s360_prep_image", "s360_error_map",
            "s360_depth_smooth_forward", "s360_depth_smooth_backward",
            "s360_window_attention_forward", "s360_window_attention_backward",
-           "s360_group_norm_scratch_doubles", "s360_group_norm_forward", "s360_group_norm_backward")
+           "s360_group_norm_scratch_doubles", "s360_group_norm_forward", "s360_group_norm_backward",
+           "s360_qkv_attention_forward", "s360_qkv_attention_backward")
 
 
 def _hipcc() -> str:
@@ -273,6 +275,10 @@ def lib() -> C.CDLL:
     l.s360_group_norm_forward.argtypes = [vp] * 4 + [i32, i32, sz, i32, C.POINTER(C.c_double), i32] + [vp] * 4
     l.s360_group_norm_backward.restype = C.c_int
     l.s360_group_norm_backward.argtypes = [vp] * 5 + [i32, i32, sz, i32, C.POINTER(C.c_double), i32] + [vp] * 5
+    l.s360_qkv_attention_forward.restype = C.c_int
+    l.s360_qkv_attention_forward.argtypes = [vp] + [i32] * 6 + [vp] * 3
+    l.s360_qkv_attention_backward.restype = C.c_int
+    l.s360_qkv_attention_backward.argtypes = [vp] * 3 + [i32] * 6 + [vp] * 3
     l.s360_count_backward_slots.restype = C.c_int
     l.s360_count_backward_slots.argtypes = [C.POINTER(S360Params), vp, sz, vp, vp]
     l.s360_count_contributions.restype = C.c_int

@@ -1,0 +1,466 @@
+// s360_qkv_attention.hip — the U-Nets' multi-head QKV attention, forward and backward (the reference's QKVAttentionLegacy and
+// QKVAttention, src/model/encoder/costvolume/ldm_unet/unet.py:527-599), read from and written to the channel-major qkv tensor
+// where it lies.  gfx950 only.
+//
+//   qkv      [N, heads 3 ch, T] float32, channel-major, ch = 32; B = N / views batch elements.  Joint token s < L = views T of
+//            batch element bi is token s mod T of view u = s / T and lives in batch row u B + bi (the reference's
+//            "(v b) n t -> b n (v t)"); views = 1 is attention within a row.
+//   order    legacy (0): head hd owns channel rows [hd 3 ch, (hd + 1) 3 ch), q then k then v; new (1): the channel axis is
+//            q | k | v chunks of heads ch rows and head hd owns [hd ch, (hd + 1) ch) of each.
+//   score    (q . k) / sqrt(ch) — the reference's (q ch^-1/4) . (k ch^-1/4) with the scale applied once — q . k summed in float64
+//            over float32 fma chains of 8 channels (qa_dot) and kept in float64 until the maximum or lse is subtracted
+//   out      a[N, heads ch, T] = softmax over the L joint keys, times v, in the rows' (v b) order; lse[B, heads, L] float64
+//
+// The arithmetic is the window attention's (s360_window_attention.hip): every product on v_mfma_f32_32x32x2_f32; 32 "owner" rows
+// (queries in the forward and the g_q pass, keys in the g_k / g_v pass) sit on the lanes and the other side is walked in tiles
+// of 32 that sit on the accumulator's rows, so the score tile is, register by register, the B operand of the second product,
+// and the softmax statistics of the owner are per lane.  What is new is the layout and the split of the walk.
+// Layout.  In channel-major memory a token tile of one channel is 32 consecutive floats, so everything that wants the TOKEN on
+// the lanes is a coalesced 128-byte read: the owner's rows (held in registers, channel 2 j + hf at MFMA step j of lane half hf)
+// and the score product's walked operand.  The second product wants the CHANNEL on the lanes (A[i = channel][k = walked token]),
+// a stride of T floats between lanes in memory.  So each walked tile pair (K and V; Q and dO in the key-owned pass) goes through
+// LDS once: read along t, one dword per lane (any T, any alignment, a tile may straddle two views), into [channel][token] tiles
+// of row stride 33, then read token-on-lanes for the score / dP chains (rows 2 j and 2 j + 1 of a step, 32 consecutive floats
+// each) and channel-on-lanes for the second product (the odd stride keeps the 32 channels of a lane half on 32 banks).
+// Split.  At the U-Nets' shapes there is ONE batch element with 4 or 1 heads and L = 4096: owner tiles alone are 512 or 128 waves
+// for 1024 SIMDs, each walking 128 tiles in sequence.  So a workgroup is four waves on ONE owner tile: wave w walks tiles w, w + 4,
+// w + 8, ... with buffers of its own (the loads of its next tile are issued before the products of the current one, and no
+// workgroup barrier stands in the loop), and the four partial results are combined through LDS in the fixed order w = 0..3 —
+// the forward's (max, sum, O) triples rescaled to the common maximum, Delta and the gradients' tiles by plain float64 addition.
+// No atomics: the query-owned pass writes Delta and the q rows of g_qkv, the key-owned pass the k and v rows, every element once,
+// by one wave, in place in the interleaved layout.  Backward: P = exp(score - lse) recomputed through the same chains (bit for
+// bit the forward's), dS = P (dP - Delta), Delta = sum_s P dP / sum_s P (float64) from a first sweep of the query-owned pass
+// over the very dP values dS subtracts it from.
+#include "s360_device.h"
+
+namespace s360 {
+
+typedef float qa_f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int QA_CH = 32;                                     // channels per head
+constexpr int QA_T = 32;                                      // rows of an MFMA tile
+constexpr int QA_WAVES = S360_BLOCK / S360_WAVE;              // waves that share the walk of one owner tile
+constexpr int QA_LD = QA_T + 1;                               // row stride of a staged tile in LDS (floats)
+constexpr int QA_TILE = QA_CH * QA_LD;                        // floats of a staged tile
+constexpr int QA_ND = 17;                                     // float64 values per lane a wave hands to the combine (16 + the sum)
+// one buffer serves the waves' staged tile pairs in the walk and their partial results in the combine
+constexpr int QA_RAW = QA_WAVES * QA_ND * S360_WAVE;          // float64 words
+static_assert(QA_RAW * 8 >= QA_WAVES * 2 * QA_TILE * 4, "the combine area covers the staging area");
+
+struct QAArgs {
+    const float* qkv;
+    int B, views, heads, T, L, W;                             // W = heads 3 ch channel rows of qkv
+    int order;
+    double inv_scale;                                         // 1 / sqrt(ch): multiplies the float64 score sums and g_q, g_k
+};
+
+// element offset of (channel row 0, joint token s) of batch element bi in a [N, width, T] tensor
+__device__ __forceinline__ size_t qa_token(const QAArgs& a, int bi, int s, int width) {
+    const int u = s / a.T, t = s - u * a.T;
+    return ((size_t)(u * a.B + bi) * width) * a.T + t;
+}
+
+// first channel rows of head hd's q, k and v
+__device__ __forceinline__ void qa_head(const QAArgs& a, int hd, int& qo, int& ko, int& vo) {
+    if (a.order == 0) { qo = hd * 3 * QA_CH; ko = qo + QA_CH; vo = ko + QA_CH; }
+    else { qo = hd * QA_CH; ko = a.heads * QA_CH + qo; vo = 2 * a.heads * QA_CH + qo; }
+}
+
+// row of the accumulator tile that register r of a lane of half hf holds
+__device__ __forceinline__ int qa_acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
+
+// channel rows hf, hf + 2, ... of one token (p: its channel row 0; null: zeros): the owner's row — channel 2 j + hf is the lane's
+// operand of MFMA step j — and a lane's share of a staged tile, whose token l31 it reads: a wave's load is two coalesced
+// 128-byte rows
+__device__ __forceinline__ void qa_load_rows(const float* p, int T, int hf, float* x) {
+#pragma unroll
+    for (int j = 0; j < QA_CH / 2; ++j) x[j] = p ? p[(size_t)(2 * j + hf) * T] : 0.f;
+}
+
+// the wave's share of walked tile `tile` of a [N, width, T] tensor, channel rows from coff; tokens past L read as zeros
+__device__ __forceinline__ void qa_stage_load(const QAArgs& a, const float* src, int width, int bi, int coff, int tile, int l31, int hf,
+                                              float* x) {
+    const int s = tile * QA_T + l31;
+    qa_load_rows(s < a.L ? src + qa_token(a, bi, s, width) + (size_t)coff * a.T : nullptr, a.T, hf, x);
+}
+
+__device__ __forceinline__ void qa_stage_store(float* buf, int l31, int hf, const float* x) {
+    float* p = buf + hf * QA_LD + l31;
+#pragma unroll
+    for (int j = 0; j < QA_CH / 2; ++j) p[2 * j * QA_LD] = x[j];
+}
+
+// Between a wave's writes of its own LDS buffer and its reads of it (and back): the LDS serves one wave's instructions in the
+// order they were issued, so no hardware barrier is needed; this keeps the compiler from moving them across each other.
+__device__ __forceinline__ void qa_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// out = mul * sum over the channels of walked-token row x owner row, in FLOAT64.  `tile` points at (channel hf, token l31) of a
+// staged tile, b holds the owner's channels 2 j + hf.  The sum runs in chunks of 4 MFMA steps (8 channels): a chunk is one
+// float32 fma chain from zero and the chunks are added in float64 (the window attention's wa_dot).  The sum is NOT rounded to
+// float32: a score goes into exp as the float32 of (score - max) or (score - lse), a difference taken in float64, so that the
+// rounding is relative to the difference and not to the score (at logits of +-100 the rounding of the score itself is 4e-6 in
+// the exponent, which two keys of comparable weight show in full in dS), and dP meets Delta in float64.  The forward and both
+// backward passes form every score and every dP through this one function, with the operands' roles exchanged in the key-owned
+// pass (the products commute, their order does not change): recomputed tiles are the forward's bit for bit.  Each chunk's zero
+// tile passes an empty asm statement that depends on the sums as they stand, so that at most three tiles are live and the
+// float64 adds of chunk c - 1 run under the MFMAs of chunk c.
+__device__ __forceinline__ void qa_dot(const float* tile, const float* b, double mul, double* out) {
+    double sum[16];
+    qa_f32x16 prev;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sum[r] = 0.0, prev[r] = 0.f;
+#pragma unroll
+    for (int c = 0; c < QA_CH / 8; ++c) {
+        float z = 0.f;
+        asm volatile("" : "+v"(z) : "v"(sum[15]));
+        qa_f32x16 t;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) t[r] = z;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t = __builtin_amdgcn_mfma_f32_32x32x2f32(tile[2 * (4 * c + i) * QA_LD], b[4 * c + i], t, 0, 0, 0);
+        if (c > 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sum[r] += (double)prev[r];
+        }
+        prev = t;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) out[r] = (sum[r] + (double)prev[r]) * mul;
+}
+
+// acc^T[channel][owner] += sum over the tile's 32 walked tokens of tile[channel][token] x w[token][owner]: `tile` points at
+// (channel l31, token 4 hf) of a staged tile, w is a score-shaped tile held register by register.  The 32 tokens of a tile are
+// one float32 fma chain from zero; the tiles are added in FLOAT64 (a float32 chain over all L tokens rounds at the size of the
+// running sum at every step: at L = 640 it missed the accuracy rule of the tests in out).
+__device__ __forceinline__ void qa_accumulate(const float* tile, const float* w, double* acc) {
+    qa_f32x16 t;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t[r] = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t = __builtin_amdgcn_mfma_f32_32x32x2f32(tile[(r & 3) + 8 * (r >> 2)], w[r], t, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] += (double)t[r];
+}
+
+// workgroup decomposition shared by the three kernels: owner tile ot of head hd of batch element bi
+struct QABlock { int ot, hd, bi; };
+__device__ __forceinline__ QABlock qa_block(const QAArgs& a) {
+    const int otiles = (a.L + QA_T - 1) / QA_T;
+    int blk = blockIdx.x;
+    QABlock w;
+    w.ot = blk % otiles; blk /= otiles;
+    w.hd = blk % a.heads;
+    w.bi = blk / a.heads;
+    return w;
+}
+
+// the combine: wave `wave` hands x[0..n) per lane to the workgroup; callers put a barrier in front (the area is the waves'
+// staging buffers) and behind
+__device__ __forceinline__ void qa_hand_over(double* raw, int wave, int lane, const double* x, int n) {
+#pragma unroll
+    for (int i = 0; i < QA_ND; ++i)
+        if (i < n) raw[(wave * QA_ND + i) * S360_WAVE + lane] = x[i];
+}
+__device__ __forceinline__ double qa_handed(const double* raw, int wave, int lane, int i) { return raw[(wave * QA_ND + i) * S360_WAVE + lane]; }
+
+// Forward.  Owner: 32 queries.  Each wave walks its key tiles with a running maximum (float32: it is one of the scores) and a
+// running sum (float64); wave 0 merges the four (m, sum, O) in the order w = 0..3 and writes.
+__global__ __launch_bounds__(S360_BLOCK) void k_qa_forward(QAArgs a, float* __restrict__ out, double* __restrict__ lse) {
+    __shared__ double s_raw[QA_RAW];
+    __shared__ float s_m[QA_WAVES][S360_WAVE];
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const QABlock w = qa_block(a);
+    int qo, ko, vo;
+    qa_head(a, w.hd, qo, ko, vo);
+    const int sq = w.ot * QA_T + l31;
+    const bool qvalid = sq < a.L;
+    float qB[QA_CH / 2];
+    qa_load_rows(qvalid ? a.qkv + qa_token(a, w.bi, sq, a.W) + (size_t)qo * a.T : nullptr, a.T, hf, qB);
+    double o[QA_ND];                                          // O^T, and the running sum in o[16]
+#pragma unroll
+    for (int r = 0; r < QA_ND; ++r) o[r] = 0.0;
+    float m = -INFINITY;
+    const int ntiles = (a.L + QA_T - 1) / QA_T;
+    float* ks = reinterpret_cast<float*>(s_raw) + wave * 2 * QA_TILE;
+    float* vs = ks + QA_TILE;
+    float rk[QA_CH / 2], rv[QA_CH / 2];
+    if (wave < ntiles) {
+        qa_stage_load(a, a.qkv, a.W, w.bi, ko, wave, l31, hf, rk);
+        qa_stage_load(a, a.qkv, a.W, w.bi, vo, wave, l31, hf, rv);
+    }
+    for (int t = wave; t < ntiles; t += QA_WAVES) {
+        qa_stage_store(ks, l31, hf, rk);
+        qa_stage_store(vs, l31, hf, rv);
+        qa_wave_sync();
+        if (t + QA_WAVES < ntiles) {
+            qa_stage_load(a, a.qkv, a.W, w.bi, ko, t + QA_WAVES, l31, hf, rk);
+            qa_stage_load(a, a.qkv, a.W, w.bi, vo, t + QA_WAVES, l31, hf, rv);
+        }
+        double s[16];
+        qa_dot(ks + hf * QA_LD + l31, qB, a.inv_scale, s);    // S^T / sqrt(ch): rows = keys, lane = query
+        float p[16];
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (t * QA_T + qa_acc_row(r, hf) < a.L) tmax = fmaxf(tmax, (float)s[r]);
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+        const float mnew = fmaxf(m, tmax);                    // finite: key 0 of every tile exists
+        const float alpha = expf(m - mnew);                   // 0 at the wave's first tile
+        float rs = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            p[r] = t * QA_T + qa_acc_row(r, hf) < a.L ? expf((float)(s[r] - (double)mnew)) : 0.f;
+            rs += p[r];
+        }
+        rs += __shfl_xor(rs, 32);
+        m = mnew;
+#pragma unroll
+        for (int r = 0; r < QA_ND; ++r) o[r] *= (double)alpha;
+        o[16] += (double)rs;
+        qa_accumulate(vs + l31 * QA_LD + 4 * hf, p, o);       // O^T += V P^T, two keys (one per lane half) a step
+        qa_wave_sync();
+    }
+    __syncthreads();                                          // every wave has left its staging buffers
+    qa_hand_over(s_raw, wave, lane, o, QA_ND);
+    s_m[wave][lane] = m;
+    __syncthreads();
+    if (wave != 0 || !qvalid) return;
+    float mall = m;                                           // wave 0 has tile 0: finite
+#pragma unroll
+    for (int u = 1; u < QA_WAVES; ++u) mall = fmaxf(mall, s_m[u][lane]);
+#pragma unroll
+    for (int r = 0; r < QA_ND; ++r) o[r] = 0.0;
+#pragma unroll
+    for (int u = 0; u < QA_WAVES; ++u) {
+        const double f = (double)expf(s_m[u][lane] - mall);   // 0 for a wave without tiles (its maximum is -inf)
+#pragma unroll
+        for (int r = 0; r < QA_ND; ++r) o[r] += qa_handed(s_raw, u, lane, r) * f;
+    }
+    float* po = out + qa_token(a, w.bi, sq, a.heads * QA_CH) + (size_t)(w.hd * QA_CH) * a.T;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) po[(size_t)qa_acc_row(r, hf) * a.T] = (float)(o[r] / o[16]);
+    if (hf == 0) lse[((size_t)w.bi * a.heads + w.hd) * a.L + sq] = (double)mall + log(o[16]);
+}
+
+// Backward, Delta and the q rows of g_qkv.  Owner: 32 queries (as the forward).  First sweep over the key tiles: sum_s P dP and
+// sum_s P per query, float64 (the waves' partial sums added in the order w = 0..3); Delta = sum P dP / sum P is written to delta[]
+// for the key-owned pass; second sweep: dS^T = P (dP - Delta), g_q^T += K dS^T.  Delta is formed from the very dP values dS
+// subtracts it from (the same fma chains in both sweeps and in the key-owned pass), as torch's softmax backward forms it;
+// rowsum(g_out out) does not have that property (s360_window_attention.hip, k_wa_backward_q).  The division by sum P, which is
+// 1 but for the roundings of lse and of the recomputed exponentials (1e-7), makes sum_s dS = 0 hold for the P that are used: a
+// common factor 1 + e on a row's P then costs dS a relative e, where P (dP - sum P dP) is off by e P Delta — the whole of dS
+// at a row whose weight sits on one key, where dP - Delta is a small difference of large numbers (the 5-token case of the tests
+// at logits of +-100 showed it: 2.4e-6 on gradients of 3e-6).  The two sweeps are two loops in the code (`sweep` is a constant in each).
+__global__ __launch_bounds__(S360_BLOCK) void k_qa_backward_q(QAArgs a, const double* __restrict__ lse, const float* __restrict__ g_out,
+                                                              double* __restrict__ delta, float* __restrict__ g_qkv) {
+    __shared__ double s_raw[QA_RAW];
+    __shared__ double s_sum[2][QA_WAVES][S360_WAVE];
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const QABlock w = qa_block(a);
+    int qo, ko, vo;
+    qa_head(a, w.hd, qo, ko, vo);
+    const int sq = w.ot * QA_T + l31;
+    const bool qvalid = sq < a.L;
+    const size_t qtok = qvalid ? qa_token(a, w.bi, sq, a.W) + (size_t)qo * a.T : 0;
+    const size_t stat = ((size_t)w.bi * a.heads + w.hd) * a.L + sq;
+    float qB[QA_CH / 2], gB[QA_CH / 2];
+    qa_load_rows(qvalid ? a.qkv + qtok : nullptr, a.T, hf, qB);
+    qa_load_rows(qvalid ? g_out + qa_token(a, w.bi, sq, a.heads * QA_CH) + (size_t)(w.hd * QA_CH) * a.T : nullptr, a.T, hf, gB);
+    const double lq = qvalid ? lse[stat] : 0.0;
+    double dsum = 0.0, psum = 0.0;
+    double acc[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0;
+    const int ntiles = (a.L + QA_T - 1) / QA_T;
+    float* ks = reinterpret_cast<float*>(s_raw) + wave * 2 * QA_TILE;
+    float* vs = ks + QA_TILE;
+    float rk[QA_CH / 2], rv[QA_CH / 2];
+#pragma unroll
+    for (int sweep = 0; sweep < 2; ++sweep) {
+        if (wave < ntiles) {
+            qa_stage_load(a, a.qkv, a.W, w.bi, ko, wave, l31, hf, rk);
+            qa_stage_load(a, a.qkv, a.W, w.bi, vo, wave, l31, hf, rv);
+        }
+        for (int t = wave; t < ntiles; t += QA_WAVES) {
+            qa_stage_store(ks, l31, hf, rk);
+            qa_stage_store(vs, l31, hf, rv);
+            qa_wave_sync();
+            if (t + QA_WAVES < ntiles) {
+                qa_stage_load(a, a.qkv, a.W, w.bi, ko, t + QA_WAVES, l31, hf, rk);
+                qa_stage_load(a, a.qkv, a.W, w.bi, vo, t + QA_WAVES, l31, hf, rv);
+            }
+            double s[16], dp[16];
+            float ds[16];
+            qa_dot(ks + hf * QA_LD + l31, qB, a.inv_scale, s);                           // S^T / sqrt(ch)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const bool kvalid = t * QA_T + qa_acc_row(r, hf) < a.L;
+                ds[r] = (kvalid && qvalid) ? expf((float)(s[r] - lq)) : 0.f;             // P^T
+            }
+            qa_dot(vs + hf * QA_LD + l31, gB, 1.0, dp);                                  // dP^T = V^T dO
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                if (sweep == 0) dsum += (double)ds[r] * dp[r], psum += (double)ds[r];
+                else ds[r] *= (float)(dp[r] - dsum);
+            }
+            if (sweep == 1) qa_accumulate(ks + l31 * QA_LD + 4 * hf, ds, acc);           // g_q^T += K dS^T
+            qa_wave_sync();
+        }
+        if (sweep == 0) {
+            dsum += __shfl_xor(dsum, 32);
+            psum += __shfl_xor(psum, 32);
+            s_sum[0][wave][lane] = dsum;
+            s_sum[1][wave][lane] = psum;
+            __syncthreads();
+            dsum = psum = 0.0;
+#pragma unroll
+            for (int u = 0; u < QA_WAVES; ++u) dsum += s_sum[0][u][lane], psum += s_sum[1][u][lane];
+            dsum = psum > 0.0 ? dsum / psum : 0.0;                                       // the same Delta in every wave; a query past L has no P
+            if (wave == 0 && qvalid && hf == 0) delta[stat] = dsum;
+        }
+    }
+    __syncthreads();                                          // every wave has left its staging buffers
+    qa_hand_over(s_raw, wave, lane, acc, 16);
+    __syncthreads();
+    if (wave != 0 || !qvalid) return;
+    float* pg = g_qkv + qtok;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        double x = 0.0;
+#pragma unroll
+        for (int u = 0; u < QA_WAVES; ++u) x += qa_handed(s_raw, u, lane, r);
+        pg[(size_t)qa_acc_row(r, hf) * a.T] = (float)(x * a.inv_scale);
+    }
+}
+
+// Backward, the k and v rows of g_qkv.  Owner: 32 keys; the waves walk the query tiles, whose q and dO rows are staged with
+// their lse and Delta.  S = Q^T K (rows = queries, lane = key), g_v^T += dO P, g_k^T += Q dS; the waves' partial tiles are added
+// in the order w = 0..3, g_v first, then g_k through the same area.
+__global__ __launch_bounds__(S360_BLOCK) void k_qa_backward_kv(QAArgs a, const double* __restrict__ lse, const double* __restrict__ delta,
+                                                               const float* __restrict__ g_out, float* __restrict__ g_qkv) {
+    __shared__ double s_raw[QA_RAW];
+    __shared__ double s_stat[QA_WAVES][S360_WAVE];            // per wave: lse of the tile's 32 queries, then their Delta
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const QABlock w = qa_block(a);
+    int qo, ko, vo;
+    qa_head(a, w.hd, qo, ko, vo);
+    const int sk = w.ot * QA_T + l31;
+    const bool kvalid = sk < a.L;
+    const size_t ktok = kvalid ? qa_token(a, w.bi, sk, a.W) : 0;
+    const size_t stat = ((size_t)w.bi * a.heads + w.hd) * a.L;
+    const double* stats = hf ? delta : lse;
+    const int GW = a.heads * QA_CH, go = w.hd * QA_CH;
+    float kB[QA_CH / 2], vB[QA_CH / 2];
+    qa_load_rows(kvalid ? a.qkv + ktok + (size_t)ko * a.T : nullptr, a.T, hf, kB);
+    qa_load_rows(kvalid ? a.qkv + ktok + (size_t)vo * a.T : nullptr, a.T, hf, vB);
+    double dk[16], dv[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dk[r] = dv[r] = 0.0;
+    const int ntiles = (a.L + QA_T - 1) / QA_T;
+    float* qs = reinterpret_cast<float*>(s_raw) + wave * 2 * QA_TILE;
+    float* gs = qs + QA_TILE;
+    const double* sl = s_stat[wave];
+    const double* sd = s_stat[wave] + QA_T;
+    float rq[QA_CH / 2], rg[QA_CH / 2];
+    double rs = 0.0;
+    if (wave < ntiles) {
+        qa_stage_load(a, a.qkv, a.W, w.bi, qo, wave, l31, hf, rq);
+        qa_stage_load(a, g_out, GW, w.bi, go, wave, l31, hf, rg);
+        rs = wave * QA_T + l31 < a.L ? stats[stat + wave * QA_T + l31] : 0.0;
+    }
+    for (int t = wave; t < ntiles; t += QA_WAVES) {
+        qa_stage_store(qs, l31, hf, rq);
+        qa_stage_store(gs, l31, hf, rg);
+        s_stat[wave][lane] = rs;
+        qa_wave_sync();
+        if (t + QA_WAVES < ntiles) {
+            const int tn = t + QA_WAVES;
+            qa_stage_load(a, a.qkv, a.W, w.bi, qo, tn, l31, hf, rq);
+            qa_stage_load(a, g_out, GW, w.bi, go, tn, l31, hf, rg);
+            rs = tn * QA_T + l31 < a.L ? stats[stat + tn * QA_T + l31] : 0.0;
+        }
+        double s[16];
+        float p[16];
+        qa_dot(qs + hf * QA_LD + l31, kB, a.inv_scale, s);    // S / sqrt(ch): rows = queries, lane = key; the forward's chain, bit for bit
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int qq = qa_acc_row(r, hf);
+            p[r] = (kvalid && t * QA_T + qq < a.L) ? expf((float)(s[r] - sl[qq])) : 0.f;
+        }
+        qa_accumulate(gs + l31 * QA_LD + 4 * hf, p, dv);      // g_v^T += dO P
+        qa_dot(gs + hf * QA_LD + l31, vB, 1.0, s);            // dP = dO^T V
+#pragma unroll
+        for (int r = 0; r < 16; ++r) p[r] *= (float)(s[r] - sd[qa_acc_row(r, hf)]);      // dS = P (dP - Delta)
+        qa_accumulate(qs + l31 * QA_LD + 4 * hf, p, dk);      // g_k^T += Q dS
+        qa_wave_sync();
+    }
+    float* pk = g_qkv + ktok + (size_t)ko * a.T;
+    float* pv = g_qkv + ktok + (size_t)vo * a.T;
+#pragma unroll
+    for (int part = 0; part < 2; ++part) {
+        __syncthreads();                                      // every wave has left its staging buffers / wave 0 has read part 0
+        qa_hand_over(s_raw, wave, lane, part == 0 ? dv : dk, 16);
+        __syncthreads();
+        if (wave == 0 && kvalid) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                double x = 0.0;
+#pragma unroll
+                for (int u = 0; u < QA_WAVES; ++u) x += qa_handed(s_raw, u, lane, r);
+                const size_t c = (size_t)qa_acc_row(r, hf) * a.T;
+                if (part == 0) pv[c] = (float)x;
+                else pk[c] = (float)(x * a.inv_scale);
+            }
+        }
+    }
+}
+
+// shared argument check; fills the kernel arguments
+static int qa_setup(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens, int32_t order, QAArgs& a) {
+    if (!qkv || rows < 1 || views < 1 || heads < 1 || ch < 1 || tokens < 1 || (order != 0 && order != 1)) return S360_E_BADARG;
+    if (rows % views != 0) return S360_E_BADARG;
+    if (ch != QA_CH) return S360_E_UNSUPPORTED;
+    const int64_t L = (int64_t)views * tokens, B = rows / views;
+    if (L >= (int64_t)1 << 31 || (int64_t)heads * 3 * ch >= (int64_t)1 << 31) return S360_E_BADARG;
+    if (B * heads * ((L + QA_T - 1) / QA_T) >= (int64_t)1 << 31) return S360_E_BADARG;
+    a.qkv = qkv;
+    a.B = (int)B; a.views = views; a.heads = heads; a.T = tokens; a.L = (int)L; a.W = heads * 3 * ch;
+    a.order = order;
+    a.inv_scale = 1.0 / sqrt((double)ch);
+    return S360_OK;
+}
+
+static unsigned qa_grid(const QAArgs& a) { return (unsigned)((int64_t)a.B * a.heads * ((a.L + QA_T - 1) / QA_T)); }
+
+}  // namespace s360
+
+using namespace s360;
+
+extern "C" int s360_qkv_attention_forward(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens,
+                                          int32_t order, float* out, double* lse, void* stream) {
+    QAArgs a;
+    const int rc = qa_setup(qkv, rows, views, heads, ch, tokens, order, a);
+    if (rc != S360_OK) return rc;
+    if (!out || !lse) return S360_E_BADARG;
+    hipLaunchKernelGGL(k_qa_forward, dim3(qa_grid(a)), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, out, lse);
+    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+}
+
+extern "C" int s360_qkv_attention_backward(const float* qkv, const double* lse, const float* g_out, int32_t rows, int32_t views,
+                                           int32_t heads, int32_t ch, int32_t tokens, int32_t order, double* delta, float* g_qkv,
+                                           void* stream) {
+    QAArgs a;
+    const int rc = qa_setup(qkv, rows, views, heads, ch, tokens, order, a);
+    if (rc != S360_OK) return rc;
+    if (!lse || !g_out || !delta || !g_qkv || g_qkv == qkv) return S360_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(qa_grid(a)), block(S360_BLOCK);
+    // the query-owned pass first: it writes Delta for the key-owned one
+    hipLaunchKernelGGL(k_qa_backward_q, grid, block, 0, st, a, lse, g_out, delta, g_qkv);
+    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    hipLaunchKernelGGL(k_qa_backward_kv, grid, block, 0, st, a, lse, delta, g_out, g_qkv);
+    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+}

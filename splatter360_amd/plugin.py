@@ -39,6 +39,9 @@ install(group_norm=True) rebinds ResBlock._forward and AttentionBlock._forward (
 ResidualBlock.forward (src/model/encoder/backbone/unimatch/backbone.py) and DepthPredictorMultiView360.__init__ so that the
 encoder's norm + activation (+ residual) sites run the fused kernels of group_norm.py; every form the wrappers do not recognise
 reaches the replaced method.
+install(unet_attention=True) rebinds QKVAttentionLegacy.forward and QKVAttention.forward (ldm_unet/unet.py:527-599) to the fused
+QKV-attention kernels of qkv_attention.py for float32 GPU qkv with 32 channels per head; every other call reaches the
+replaced method.
 
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
@@ -893,6 +896,56 @@ GROUP_NORM_RESIDUAL_SEAM = _MethodSeam("group_norm", GROUP_NORM_BACKBONE_MODULE,
 GROUP_NORM_SEAMS = (GROUP_NORM_RESBLOCK_SEAM, GROUP_NORM_ATTENTION_SEAM, GROUP_NORM_PREDICTOR_SEAM, GROUP_NORM_RESIDUAL_SEAM)
 
 
+UNET_ATTENTION_MODULE = GROUP_NORM_UNET_MODULE                        # defines QKVAttentionLegacy (:527-565) and QKVAttention (:572-599)
+UNET_ATTENTION_LEGACY = "QKVAttentionLegacy"
+UNET_ATTENTION_NEW = "QKVAttention"
+UNET_ATTENTION_METHOD = "forward"                                     # AttentionBlock._forward calls self.attention(qkv) (:372, :377)
+
+
+def _unet_attention_call(qkv, n_heads, views) -> bool:
+    """True if the QKV-attention kernels take the call: qkv a float32 CUDA [N, heads 3 ch, T] tensor outside autocast, a supported
+    ch, `views` dividing N.  Reads devices, dtypes and shapes."""
+    from . import qkv_attention as _qa
+    if not _is_cuda_f32(qkv) or qkv.dim() != 3 or qkv.numel() == 0 or torch.is_autocast_enabled():
+        return False
+    if not all(isinstance(x, int) and not isinstance(x, bool) and x >= 1 for x in (n_heads, views)):
+        return False
+    width = int(qkv.shape[1])
+    return width % (3 * n_heads) == 0 and _qa.supported_head_channels(width // (3 * n_heads)) and qkv.shape[0] % views == 0
+
+
+def _native_qkv_attention_forward(order):
+    """QKVAttentionLegacy.forward (order "legacy": n_heads, n_frames, use_cross_view_self_attn of the module) or
+    QKVAttention.forward (order "new": n_heads) with the reference's signature: the fused kernels of qkv_attention.py for the calls
+    _unet_attention_call accepts, the replaced method otherwise (half precision, autocast, CPU, other ch — and every error the
+    reference raises).  `forward.native_calls` counts the calls the kernels took."""
+    def wrapper(replaced):
+        from . import qkv_attention as _qa
+
+        def forward(self, qkv):
+            heads = getattr(self, "n_heads", None)
+            cross = bool(getattr(self, "use_cross_view_self_attn", False)) if order == "legacy" else False
+            frames = getattr(self, "n_frames", 1) if cross else 1
+            if _unet_attention_call(qkv, heads, frames):
+                forward.native_calls += 1
+                return _qa.qkv_attention(qkv, heads, n_frames=frames, cross_view=cross, order=order)
+            return replaced(self, qkv)
+
+        forward.replaced = replaced
+        forward.native_calls = 0
+        forward.__doc__ = _qa.qkv_attention.__doc__
+        return forward
+
+    return wrapper
+
+
+UNET_ATTENTION_LEGACY_SEAM = _MethodSeam("unet_attention", UNET_ATTENTION_MODULE, UNET_ATTENTION_LEGACY, (UNET_ATTENTION_METHOD,),
+                                         {UNET_ATTENTION_METHOD: _native_qkv_attention_forward("legacy")})
+UNET_ATTENTION_NEW_SEAM = _MethodSeam("unet_attention", UNET_ATTENTION_MODULE, UNET_ATTENTION_NEW, (UNET_ATTENTION_METHOD,),
+                                      {UNET_ATTENTION_METHOD: _native_qkv_attention_forward("new")})
+UNET_ATTENTION_SEAMS = (UNET_ATTENTION_LEGACY_SEAM, UNET_ATTENTION_NEW_SEAM)
+
+
 # install()'s option keywords -> their seams, in installation order; the decoder registry (DECODER_SEAM) comes after them.
 # uninstall() restores exactly these, so a new seam is a new entry here and nothing else.
 OPTION_SEAMS = {
@@ -909,6 +962,7 @@ OPTION_SEAMS = {
     "depth_smoothness": (DEPTH_SMOOTH_SEAM,),
     "window_attention": (WINDOW_ATTENTION_SEAM,),
     "group_norm": GROUP_NORM_SEAMS,
+    "unet_attention": UNET_ATTENTION_SEAMS,
 }
 
 
@@ -954,6 +1008,13 @@ def install_group_norm():
     hooks).  Returns {"Class.method": patched method or None}.  Modules built before the call keep their (norm, activation) pairs;
     group_norm.fuse_pairs(module) is the direct API for them."""
     return dict(zip((f"{seam.cls_name}.{seam.names[0]}" for seam in GROUP_NORM_SEAMS), _installed("group_norm")))
+
+
+def install_unet_attention():
+    """The half of install(unet_attention=True): rebind QKVAttentionLegacy.forward and QKVAttention.forward (ldm_unet/unet.py:527-599)
+    to the wrappers around the fused QKV-attention kernels of qkv_attention.py now if the module is imported, else as soon as it
+    is (import hook).  Returns {"Class.forward": patched method or None}."""
+    return dict(zip((f"{seam.cls_name}.{seam.names[0]}" for seam in UNET_ATTENTION_SEAMS), _installed("unet_attention")))
 
 
 def install_depth_smoothness():
@@ -1014,7 +1075,7 @@ def install_psnr():
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
             depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, depth_head: bool = False, depth_tail: bool = False,
             erp_distance: bool = False, visualization: bool = False, depth_smoothness: bool = False, window_attention: bool = False,
-            group_norm: bool = False, **opts):
+            group_norm: bool = False, unet_attention: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
@@ -1049,6 +1110,10 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     backbones' ResidualBlock.forward and DepthPredictorMultiView360.__init__ so that every conv -> GroupNorm / InstanceNorm2d ->
     SiLU / GELU / ReLU (-> + skip) of the encoder runs the fused kernels of splatter360_amd.group_norm (install_group_norm; off
     by default).
+    unet_attention=True: ALSO rebind the two U-Nets' QKVAttentionLegacy.forward and QKVAttention.forward (ldm_unet/unet.py:527-599)
+    to the fused QKV-attention kernels of splatter360_amd.qkv_attention, which read the channel-major qkv tensor in place and form
+    no [b heads, L, L] weight tensor (install_unet_attention; off by default; composes with group_norm, whose AttentionBlock._forward
+    calls self.attention, and with the reference's checkpoint).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -1071,7 +1136,8 @@ def uninstall() -> None:
     """Put the reference's own decoder class, adapter, compute_ssim, compute_psnr, compute_depth_metrics_batched,
     compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates, depth_to_distance_map_batch, depth_map, prep_image,
     apply_color_map, EncoderCostVolume.map_pdf_to_opacity, LossDepth.forward, the backbone module's four attention functions,
-    ResBlock._forward, AttentionBlock._forward, ResidualBlock.forward, DepthPredictorMultiView360.__init__ and the predictor
+    ResBlock._forward, AttentionBlock._forward, ResidualBlock.forward, DepthPredictorMultiView360.__init__,
+    QKVAttentionLegacy.forward, QKVAttention.forward and the predictor
     module's `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
     sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, _SeamPatcher)]
     for seams in (*OPTION_SEAMS.values(), (DECODER_SEAM,)):

@@ -1,0 +1,133 @@
+"""The U-Nets' multi-head QKV attention on the GPU, forward and backward (csrc/s360_qkv_attention.hip).
+
+The reference's AttentionBlocks (src/model/encoder/costvolume/ldm_unet/unet.py:310-380) run QKVAttentionLegacy (:527-565) — or
+QKVAttention (:572-599) with use_new_attention_order — on the output of a 1x1 convolution, qkv [N, heads 3 ch, T]: with
+use_cross_view_self_attn the views move from the batch rows into the sequence ("(v b) n t -> b n (v t)"), a float32
+[b heads, L, L] weight tensor and its softmax are formed (268 MB each per batch element at the hm3d shape: 4 heads, L = 4 096),
+autograd keeps them, and the reference's checkpoint forms them again in the backward.  `qkv_attention` computes the same function
+with one fused kernel pair that reads qkv where it lies — channel-major, heads interleaved, the joint sequence spread over the
+(v b) rows — and writes `a` and g_qkv where they belong: no score-sized tensor and no permuted copy exists, forward or backward,
+and the autograd node saves qkv and one float64 log-sum-exp per (batch element, head, joint token).  The firm gain is memory;
+speed against torch's rocBLAS path is what profiles/qkv_attention_timing.json says it is.  Float32 GPU tensors with ch = 32
+(what both U-Nets use); there is no CPU path (the installed seam keeps the replaced methods for everything else).  Forward and backward are
+bit-identical from run to run: fixed order, no atomics.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+from torch import Tensor
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from .cost_volume import _ptr, _stream
+
+ORDERS = {"legacy": _lib.QKV_LEGACY, "new": _lib.QKV_NEW}
+HEAD_CHANNELS = (32,)
+
+
+def supported_head_channels(ch: int) -> bool:
+    return ch in HEAD_CHANNELS
+
+
+def _checked(what: str, qkv, n_heads, n_frames, cross_view, order) -> tuple:
+    """Shape, dtype and device checks of a call; returns (rows, views, heads, ch, tokens, order code)."""
+    if order not in ORDERS:
+        raise ValueError(f"{what} knows the orders {sorted(ORDERS)}, got order={order!r}")
+    if not isinstance(qkv, Tensor):
+        raise ValueError(f"{what}: qkv must be a tensor, got {type(qkv).__name__}")
+    if qkv.dim() != 3:
+        raise ValueError(f"{what} expects qkv [N, heads * 3 * ch, T], got shape {tuple(qkv.shape)}")
+    if isinstance(n_heads, bool) or not isinstance(n_heads, int) or n_heads < 1:
+        raise ValueError(f"{what}: n_heads must be a positive integer, got {n_heads!r}")
+    if isinstance(n_frames, bool) or not isinstance(n_frames, int) or n_frames < 1:
+        raise ValueError(f"{what}: n_frames must be a positive integer, got {n_frames!r}")
+    rows, width, tokens = (int(s) for s in qkv.shape)
+    if qkv.numel() == 0:
+        raise ValueError(f"{what}: qkv is empty, shape {tuple(qkv.shape)}")
+    if width % (3 * n_heads) != 0:
+        raise ValueError(f"{what}: qkv has {width} channel rows, not a multiple of 3 * n_heads = {3 * n_heads}")
+    ch = width // (3 * n_heads)
+    if not supported_head_channels(ch):
+        raise ValueError(f"{what} takes qkv with ch = {HEAD_CHANNELS[0]} channels per head, got ch = {ch}")
+    views = n_frames if cross_view else 1
+    if rows % views != 0:
+        raise ValueError(f"{what}: n_frames = {n_frames} must divide the {rows} rows of qkv for cross-view attention")
+    if not qkv.is_cuda:
+        raise ValueError(f"{what}: qkv must be a GPU tensor (there is no CPU path), got device {qkv.device}")
+    if qkv.dtype != torch.float32:
+        raise ValueError(f"{what}: qkv must be float32, got {qkv.dtype}")
+    return rows, views, n_heads, ch, tokens, ORDERS[order]
+
+
+def attention_forward(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: bool = False, order: str = "legacy") -> tuple:
+    """s360_qkv_attention_forward -> (out [N, heads ch, T] float32, lse [N / views, heads, views T] float64)."""
+    rows, views, heads, ch, tokens, code = _checked("attention_forward", qkv, n_heads, n_frames, cross_view, order)
+    qkv = qkv.detach().contiguous()
+    out = torch.empty(rows, heads * ch, tokens, dtype=torch.float32, device=qkv.device)
+    lse = torch.empty(rows // views, heads, views * tokens, dtype=torch.float64, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        rc = _lib.lib().s360_qkv_attention_forward(_ptr(qkv), rows, views, heads, ch, tokens, code, _ptr(out), _ptr(lse),
+                                                   _stream(qkv.device))
+    _lib.check(rc, "s360_qkv_attention_forward")
+    return out, lse
+
+
+def attention_backward(qkv: Tensor, lse: Tensor, g_out: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: bool = False,
+                       order: str = "legacy", g_qkv: Optional[Tensor] = None) -> Tensor:
+    """s360_qkv_attention_backward -> g_qkv in qkv's shape and layout.  `g_qkv`: a contiguous float32 buffer of qkv's shape on its
+    device to write into (every element is written); allocated when None."""
+    rows, views, heads, ch, tokens, code = _checked("attention_backward", qkv, n_heads, n_frames, cross_view, order)
+    if not isinstance(g_out, Tensor) or not g_out.is_cuda or g_out.dtype != torch.float32 or g_out.device != qkv.device \
+            or tuple(g_out.shape) != (rows, heads * ch, tokens):
+        raise ValueError(f"attention_backward: g_out must be a float32 [{rows}, {heads * ch}, {tokens}] tensor on {qkv.device}")
+    if not isinstance(lse, Tensor) or lse.dtype != torch.float64 or lse.device != qkv.device \
+            or tuple(lse.shape) != (rows // views, heads, views * tokens):
+        raise ValueError("attention_backward: lse must be the forward's float64 [N / views, heads, views * T] tensor")
+    qkv, lse, g_out = (t.detach().contiguous() for t in (qkv, lse, g_out))
+    if g_qkv is None:
+        g_qkv = torch.empty_like(qkv)
+    elif not isinstance(g_qkv, Tensor) or g_qkv.dtype != torch.float32 or g_qkv.device != qkv.device \
+            or tuple(g_qkv.shape) != tuple(qkv.shape) or not g_qkv.is_contiguous() or g_qkv.data_ptr() == qkv.data_ptr():
+        raise ValueError("attention_backward: g_qkv must be a contiguous float32 buffer of qkv's shape on its device, not qkv itself")
+    delta = torch.empty_like(lse)
+    with torch.cuda.device(qkv.device):
+        rc = _lib.lib().s360_qkv_attention_backward(_ptr(qkv), _ptr(lse), _ptr(g_out), rows, views, heads, ch, tokens, code,
+                                                    _ptr(delta), _ptr(g_qkv), _stream(qkv.device))
+    _lib.check(rc, "s360_qkv_attention_backward")
+    return g_qkv
+
+
+class _QKVAttention(torch.autograd.Function):
+    """a of qkv; saves qkv and lse, nothing score-sized (the backward forms Delta from the recomputed probabilities, so not even
+    the output is kept)."""
+
+    @staticmethod
+    def forward(ctx, qkv, n_heads, n_frames, cross_view, order):
+        qkv = qkv.detach().contiguous()
+        opts = dict(n_frames=n_frames, cross_view=cross_view, order=order)
+        out, lse = attention_forward(qkv, n_heads, **opts)
+        ctx.save_for_backward(qkv, lse)
+        ctx.n_heads, ctx.opts = n_heads, opts
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        qkv, lse = ctx.saved_tensors
+        return attention_backward(qkv, lse, g_out.to(torch.float32), ctx.n_heads, **ctx.opts), None, None, None, None
+
+
+def qkv_attention(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: bool = False, order: str = "legacy") -> Tensor:
+    """The reference's QKVAttentionLegacy(n_heads, n_frames, use_cross_view_self_attn).forward (order "legacy", unet.py:527-565)
+    or QKVAttention(n_heads).forward (order "new", :572-599) without its temporaries.
+
+    qkv [N, heads 3 ch, T].  "legacy": head hd owns channel rows [hd 3 ch, (hd + 1) 3 ch), q then k then v; "new": q | k | v chunks of
+    heads ch rows, head hd owns [hd ch, (hd + 1) ch) of each.  With cross_view the n_frames views of a batch element, which lie
+    in rows u N / n_frames + bi (the reference's (v b) order), form one joint sequence of n_frames T tokens; without it n_frames
+    is not used and every row attends within itself.  weight = softmax((q ch^-1/4) . (k ch^-1/4)) over the keys,
+    a[c, t] = sum_s weight[t, s] v[c, s].  Returns a [N, heads ch, T] in qkv's row order.  Differentiable (once) in qkv.  Float32
+    GPU tensors, ch = 32; no CPU path; a non-contiguous qkv is copied once."""
+    _checked("qkv_attention", qkv, n_heads, n_frames, cross_view, order)
+    return _QKVAttention.apply(qkv, int(n_heads), int(n_frames), bool(cross_view), order)
