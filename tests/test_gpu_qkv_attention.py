@@ -16,6 +16,11 @@ weight on one key, gradients of 3e-6 from dP of 30 — missed the bound in g_q a
 and 1.4e-6: the rounding of lse, 1e-7, times Delta); with the quotient they are 4.8e-12 and 4.1e-12.  What remains at parity with
 the yardstick is a row that two keys share at logits of +-100: dS there follows the rounding of the two scores' 8-channel chains,
 as it does the rounding of torch's float32 scores.
+
+tests/test_gpu_qkv_attention_float64.py holds the same kernels to float64 per (batch element, head, token) row, lse and Delta
+included, through the C ABI into NaN-filled buffers between sentinels; the two files complement each other (its docstring).  The
+`isfinite` assertion of _check_rule below does not alone prove a write: `out` comes from torch.empty, and stale finite memory
+passes it; that every element is written, and nothing beside it, is shown there.
 """
 import functools
 import sys
@@ -88,7 +93,7 @@ def _check_rule(tag, names, want, lines, got):
     failures = []
     for n, w64, l32, x in zip(names, want, lines, got):
         assert x.dtype == torch.float32 and x.shape == w64.shape, (tag, n)
-        assert torch.isfinite(x).all(), (tag, n)                                    # no NaN tolerated: every element was written
+        assert torch.isfinite(x).all(), (tag, n)                                    # no NaN tolerated (alone no proof of a write: the docstring)
         (kmax, kmean), (lmax, lmean) = _errors(x, w64), _errors(l32, w64)
         floor = 2.0 ** -24 * w64.abs().max().item()
         print(f"{tag} {n}: kernel max {kmax:.3e} mean {kmean:.3e} | float32 lines max {lmax:.3e} mean {lmean:.3e} | floor {floor:.3e}"
