@@ -1051,6 +1051,58 @@ int s360_group_norm_backward(const float* x, const float* weight, const float* b
                              float* g_x, float* g_weight, float* g_bias, void* stream);
 
 /*
+ * The tail of the multi-view transformer's TransformerLayer behind its attention (the reference's
+ * src/model/encoder/backbone/multiview_transformer.py:407-414: message = norm1(merge(message)); message = mlp(cat([source, message], -1));
+ * message = norm2(message); return source + message), forward and backward, without the [tokens, 2 * channels] concatenation and
+ * without either [tokens, hidden] activation, and that of the layer with no_ffn (source + norm1(merge(message))).
+ *   source[tokens, channels], m[tokens, channels] (merge's output, before norm1) float32 contiguous; norm1 / norm2 weight and bias
+ *   [channels]; w1[hidden, 2 * channels] and w2[channels, hidden] in nn.Linear's layout, no biases; channels = 128, hidden = 1024.
+ *   LN(x) = (x - mean) rstd weight + bias over the channels, mean and the BIASED variance in float64 (two passes),
+ *   rstd = 1 / sqrt(var + eps), every element formed in float64 and rounded once; eps is a HOST pointer to one float64, read before
+ *   the launch (as in s360_group_norm_*).
+ *   X = cat(source, LN1(m)); h = gelu(X w1^T), gelu(v) = 0.5 v erfc(-v / sqrt 2) (the erf form, nn.GELU()'s default); z = h w2^T;
+ *   out[tokens, channels] = source + LN2(z).  The call also writes z[tokens, channels] (float32; norm2's statistics are those of
+ *   these float32 values) and stats[2, tokens, 2] FLOAT64: (mean, rstd) per token of norm1, then of norm2.
+ * Products run on v_mfma_f32_32x32x2_f32.  A workgroup owns 128 tokens, 32 per wave, on the lanes; the hidden width is walked in
+ * chunks of 32 units whose slices of w1 and w2 are staged once per workgroup in LDS; X w1^T is float32 chains of 64 channels
+ * added in float64 (32 in the weight-owned backward pass; the backward's dz w2c: chains of 8), z one float32 chain per chunk added in float64; norm2 and the residual are the epilogue.
+ * s360_ffn_tail_backward takes the forward's inputs, z, stats and g_out[tokens, channels] and recomputes the hidden activations:
+ * a pass owned by token tiles (norm2's backward, dH = (dz w2c) gelu'(X w1c^T), dX += dH w1c, one float32 chain per chunk added in float32,
+ * g_source = g_out + dX[:, :channels], norm1's backward on dX[:, channels:] -> g_m, and float64 partial sums of the four LayerNorm
+ * parameter gradients per workgroup, of which at most 512 walk the tiles) and a pass owned by (128 hidden units, token chunk)
+ * (g_w1[j, :] = sum_t dH[t, j] X[t, :], g_w2[:, j] = sum_t dz[t, :] h[t, j], float32 over a chunk's tokens) that writes per-chunk
+ * partials into scratch; a last launch adds the partials in the order 0, 1, ... in float64.  The token chunks are
+ * s360_ffn_tail_weight_chunks(tokens) <= 16 runs of a multiple of 32 tokens.  Every output element is written once — g_source and
+ * g_m by the token pass, the six parameter gradients by the last launch; no atomics; bit-identical from run to run and across streams.
+ * s360_layer_norm_residual_forward: out = residual + LN(x) (one launch), stats[tokens, 2] FLOAT64;
+ * s360_layer_norm_residual_backward: g_x, g_residual (= g_out, written by the call), g_weight, g_bias from the same row code and the
+ * same chunked float64 reduction (two launches).
+ * Measured on one MI355X (profiles/transformer_ffn_timing.json; medians of 50 calls, launch overhead included; this / float32 torch):
+ * 65 536 tokens forward 1.071 / 0.677 ms, forward + backward 6.429 / 2.448 ms — BEHIND torch by 1.58 x and 2.63 x; the forward is
+ * 48.1 TFLOP/s, 30.7 % of the float32 MFMA peak; forward + backward peak memory 223 / 962 MiB.  The gain is memory, not time.
+ * No host synchronisation, no allocation.  scratch: s360_ffn_tail_scratch_bytes(tokens) bytes of device memory for either backward
+ * (16-byte aligned, contents need no initialisation; 0 for tokens < 1; at most 26 MiB whatever tokens); smaller: S360_E_WORKSPACE.
+ * channels != 128 or hidden != 1024: S360_E_UNSUPPORTED.  Null pointers, sizes < 1, eps null or *eps <= 0, a pointer that is not
+ * 16-byte aligned, an output that is an input or another output, or 2^31 or more elements or workgroups: S360_E_BADARG before any
+ * GPU work.
+ */
+size_t s360_ffn_tail_scratch_bytes(int32_t tokens);
+int s360_ffn_tail_weight_chunks(int32_t tokens);
+int s360_ffn_tail_forward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias, const float* w1,
+                          const float* w2, const float* norm2_weight, const float* norm2_bias, int32_t tokens, int32_t channels,
+                          int32_t hidden, const double* eps, float* out, float* z, double* stats, void* stream);
+int s360_ffn_tail_backward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias, const float* w1,
+                           const float* w2, const float* norm2_weight, const float* norm2_bias, const float* z, const double* stats,
+                           const float* g_out, int32_t tokens, int32_t channels, int32_t hidden, const double* eps, void* scratch,
+                           size_t scratch_bytes, float* g_source, float* g_m, float* g_w1, float* g_w2, float* g_norm1_weight,
+                           float* g_norm1_bias, float* g_norm2_weight, float* g_norm2_bias, void* stream);
+int s360_layer_norm_residual_forward(const float* x, const float* weight, const float* bias, const float* residual, int32_t tokens,
+                                     int32_t channels, const double* eps, float* out, double* stats, void* stream);
+int s360_layer_norm_residual_backward(const float* x, const float* weight, const double* stats, const float* g_out, int32_t tokens,
+                                      int32_t channels, void* scratch, size_t scratch_bytes, float* g_x, float* g_residual,
+                                      float* g_weight, float* g_bias, void* stream);
+
+/*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an
  * un-synchronised wall clock, src/misc/benchmarker.py:15-33).  While enabled, every kernel group
  * is bracketed by HIP events recorded on the launch stream; s360_profile_collect() synchronises

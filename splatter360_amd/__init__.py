@@ -10,7 +10,8 @@ def install(**opts):
     erp_distance, visualization (the evaluation step's depth_map, prep_image and apply_color_map, splatter360_amd.visualize),
     depth_smoothness (the training step's LossDepth.forward, splatter360_amd.depth_smooth), window_attention (the multi-view
     transformer's attention, splatter360_amd.window_attention), group_norm (the encoder's norm + activation + residual sites,
-    splatter360_amd.group_norm) and unet_attention (the two U-Nets' multi-head QKV attention, splatter360_amd.qkv_attention)."""
+    splatter360_amd.group_norm), unet_attention (the two U-Nets' multi-head QKV attention, splatter360_amd.qkv_attention) and
+    transformer_ffn (the multi-view transformer layers' norm / mlp / norm tail, splatter360_amd.transformer_ffn)."""
     from .plugin import install as _install
     return _install(**opts)
 

@@ -16,7 +16,8 @@ _CSRC = _PKG / "csrc"
 LIB_PATH = _PKG / "libs360.so"
 SOURCES = ("s360_forward.hip", "s360_backward.hip", "s360_backward_em.hip", "s360_stitch.hip", "s360_views.hip", "s360_adapter.hip", "s360_metrics.hip",
            "s360_depth_loss.hip", "s360_eval_scores.hip", "s360_cost_volume.hip", "s360_depth_head.hip", "s360_depth_tail.hip", "s360_equirec2cube.hip", "s360_visualize.hip",
-           "s360_depth_smooth.hip", "s360_window_attention.hip", "s360_group_norm.hip", "s360_qkv_attention.hip")
+           "s360_depth_smooth.hip", "s360_window_attention.hip", "s360_group_norm.hip", "s360_qkv_attention.hip",
+           "s360_transformer_ffn.hip")
 # per-source extra flags (s360_backward_em.hip: see the launcher comment in csrc/s360_bwd_em.h)
 SOURCE_FLAGS = {"s360_backward_em.hip": ("-fno-slp-vectorize",)}
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result")
@@ -74,7 +75,9 @@ EXPORTS = ("s360_forward_raw", "s360_backward_raw", "s360_backward_raw_tail", "s
            "s360_depth_smooth_forward", "s360_depth_smooth_backward",
            "s360_window_attention_forward", "s360_window_attention_backward",
            "s360_group_norm_scratch_doubles", "s360_group_norm_forward", "s360_group_norm_backward",
-           "s360_qkv_attention_forward", "s360_qkv_attention_backward")
+           "s360_qkv_attention_forward", "s360_qkv_attention_backward",
+           "s360_ffn_tail_scratch_bytes", "s360_ffn_tail_weight_chunks", "s360_ffn_tail_forward", "s360_ffn_tail_backward",
+           "s360_layer_norm_residual_forward", "s360_layer_norm_residual_backward")
 
 
 def _hipcc() -> str:
@@ -279,6 +282,18 @@ def lib() -> C.CDLL:
     l.s360_qkv_attention_forward.argtypes = [vp] + [i32] * 6 + [vp] * 3
     l.s360_qkv_attention_backward.restype = C.c_int
     l.s360_qkv_attention_backward.argtypes = [vp] * 3 + [i32] * 6 + [vp] * 3
+    l.s360_ffn_tail_scratch_bytes.restype = sz
+    l.s360_ffn_tail_scratch_bytes.argtypes = [i32]
+    l.s360_ffn_tail_weight_chunks.restype = C.c_int
+    l.s360_ffn_tail_weight_chunks.argtypes = [i32]
+    l.s360_ffn_tail_forward.restype = C.c_int
+    l.s360_ffn_tail_forward.argtypes = [vp] * 8 + [i32] * 3 + [C.POINTER(C.c_double)] + [vp] * 4
+    l.s360_ffn_tail_backward.restype = C.c_int
+    l.s360_ffn_tail_backward.argtypes = [vp] * 11 + [i32] * 3 + [C.POINTER(C.c_double), vp, sz] + [vp] * 9
+    l.s360_layer_norm_residual_forward.restype = C.c_int
+    l.s360_layer_norm_residual_forward.argtypes = [vp] * 4 + [i32, i32, C.POINTER(C.c_double)] + [vp] * 3
+    l.s360_layer_norm_residual_backward.restype = C.c_int
+    l.s360_layer_norm_residual_backward.argtypes = [vp] * 4 + [i32, i32, vp, sz] + [vp] * 5
     l.s360_count_backward_slots.restype = C.c_int
     l.s360_count_backward_slots.argtypes = [C.POINTER(S360Params), vp, sz, vp, vp]
     l.s360_count_contributions.restype = C.c_int

@@ -42,6 +42,11 @@ reaches the replaced method.
 install(unet_attention=True) rebinds QKVAttentionLegacy.forward and QKVAttention.forward (ldm_unet/unet.py:527-599) to the fused
 QKV-attention kernels of qkv_attention.py for float32 GPU qkv with 32 channels per head; every other call reaches the
 replaced method.
+install(transformer_ffn=True) rebinds TransformerLayer.forward (src/model/encoder/backbone/multiview_transformer.py:334-414) so that
+everything behind the layer's attention — norm1, the concatenation, the two-Linear GELU mlp, norm2 and the residual — runs the fused
+kernels of transformer_ffn.py; the projections and merge stay the layer's own nn.Linears and the attention is called through the
+module's globals, so window_attention=True composes in either order; every form the wrapper does not recognise reaches the
+replaced method.
 
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
@@ -946,6 +951,85 @@ UNET_ATTENTION_NEW_SEAM = _MethodSeam("unet_attention", UNET_ATTENTION_MODULE, U
 UNET_ATTENTION_SEAMS = (UNET_ATTENTION_LEGACY_SEAM, UNET_ATTENTION_NEW_SEAM)
 
 
+TRANSFORMER_FFN_MODULE = WINDOW_ATTENTION_MODULE                      # defines TransformerLayer (:292-414)
+TRANSFORMER_FFN_CLASS = "TransformerLayer"
+TRANSFORMER_FFN_METHOD = "forward"
+
+
+def _plain_linear(layer, n_in, n_out) -> bool:
+    return type(layer) is torch.nn.Linear and layer.bias is None and (layer.in_features, layer.out_features) == (n_in, n_out)
+
+
+def _affine_norm(norm, c) -> bool:
+    return (type(norm) is torch.nn.LayerNorm and tuple(norm.normalized_shape) == (c,) and norm.elementwise_affine
+            and norm.weight is not None and norm.bias is not None)
+
+
+def _transformer_ffn_call(layer, source, target, kwargs) -> bool:
+    """True if the wrapper takes the call: a single-head layer without per-view attention and without an attn_type keyword,
+    float32 CUDA source [B, L, C] and target on one device outside autocast, d_model = C = 128, norm1 (and, with an FFN, norm2 of
+    the same eps) a LayerNorm with affine parameters, and the mlp (Linear 2C -> 8C without bias, erf GELU, Linear 8C -> C without
+    bias).  Reads attributes, devices, dtypes and shapes."""
+    from . import transformer_ffn as _tf
+    if "attn_type" in kwargs or getattr(layer, "nhead", None) != 1 or getattr(layer, "add_per_view_attn", True):
+        return False
+    if not (_is_cuda_f32(source) and _is_cuda_f32(target) and source.device == target.device) or torch.is_autocast_enabled():
+        return False
+    c = getattr(layer, "dim", None)
+    if source.dim() != 3 or source.numel() == 0 or source.shape[-1] != c or not _tf.supported_widths(c, 8 * c):
+        return False
+    if not _affine_norm(getattr(layer, "norm1", None), c) or not all(_plain_linear(getattr(layer, n, None), c, c)
+                                                                      for n in ("q_proj", "k_proj", "v_proj", "merge")):
+        return False
+    if getattr(layer, "no_ffn", None) is True:
+        return True
+    mlp = getattr(layer, "mlp", None)
+    if layer.no_ffn is not False or not isinstance(mlp, torch.nn.Sequential) or len(mlp) != 3:
+        return False
+    if not (_plain_linear(mlp[0], 2 * c, 8 * c) and type(mlp[1]) is torch.nn.GELU and mlp[1].approximate == "none"
+            and _plain_linear(mlp[2], 8 * c, c)):
+        return False
+    return _affine_norm(getattr(layer, "norm2", None), c) and layer.norm2.eps == layer.norm1.eps
+
+
+def _native_transformer_layer_forward(replaced):
+    """TransformerLayer.forward with the reference's signature: for the calls _transformer_ffn_call accepts, the layer's own
+    q_proj / k_proj / v_proj, the attention function the replaced method would call — looked up in the module's globals at call
+    time, so the window-attention seam composes in either installation order — the layer's own merge, and then
+    transformer_ffn.ffn_tail (layer_norm_residual with no_ffn) in place of :408-414.  The replaced method otherwise (several
+    heads, per-view attention, the epipolar path's attn_type, CPU or half precision, another width or mlp).
+    `forward.native_calls` counts the calls the kernels took."""
+    from . import transformer_ffn as _tf
+
+    def forward(self, source, target, height=None, width=None, shifted_window_attn_mask=None, attn_num_splits=None, **kwargs):
+        if not _transformer_ffn_call(self, source, target, kwargs):
+            return replaced(self, source, target, height=height, width=width, shifted_window_attn_mask=shifted_window_attn_mask,
+                            attn_num_splits=attn_num_splits, **kwargs)
+        g = sys.modules[TRANSFORMER_FFN_MODULE].__dict__
+        query, key, value = self.q_proj(source), self.k_proj(target), self.v_proj(target)
+        if self.attention_type == "swin" and attn_num_splits > 1:
+            message = g[WINDOW_ATTENTION_SPLIT](query, key, value, num_splits=attn_num_splits, with_shift=self.with_shift, h=height,
+                                                w=width, attn_mask=shifted_window_attn_mask)
+        else:
+            message = g[WINDOW_ATTENTION_FULL](query, key, value)
+        message = self.merge(message)
+        forward.native_calls += 1
+        n1 = self.norm1
+        if self.no_ffn:
+            return _tf.layer_norm_residual(message, n1.weight, n1.bias, source, n1.eps)
+        return _tf.ffn_tail(source, message, n1.weight, n1.bias, self.mlp[0].weight, self.mlp[2].weight, self.norm2.weight,
+                            self.norm2.bias, n1.eps)
+
+    forward.replaced = replaced
+    forward.native_calls = 0
+    forward.__doc__ = _tf.ffn_tail.__doc__
+    return forward
+
+
+TRANSFORMER_FFN_SEAM = _MethodSeam("transformer_ffn", TRANSFORMER_FFN_MODULE, TRANSFORMER_FFN_CLASS, (TRANSFORMER_FFN_METHOD,),
+                                   {TRANSFORMER_FFN_METHOD: _native_transformer_layer_forward})
+
+
 # install()'s option keywords -> their seams, in installation order; the decoder registry (DECODER_SEAM) comes after them.
 # uninstall() restores exactly these, so a new seam is a new entry here and nothing else.
 OPTION_SEAMS = {
@@ -963,6 +1047,7 @@ OPTION_SEAMS = {
     "window_attention": (WINDOW_ATTENTION_SEAM,),
     "group_norm": GROUP_NORM_SEAMS,
     "unet_attention": UNET_ATTENTION_SEAMS,
+    "transformer_ffn": (TRANSFORMER_FFN_SEAM,),
 }
 
 
@@ -1015,6 +1100,13 @@ def install_unet_attention():
     to the wrappers around the fused QKV-attention kernels of qkv_attention.py now if the module is imported, else as soon as it
     is (import hook).  Returns {"Class.forward": patched method or None}."""
     return dict(zip((f"{seam.cls_name}.{seam.names[0]}" for seam in UNET_ATTENTION_SEAMS), _installed("unet_attention")))
+
+
+def install_transformer_ffn():
+    """The half of install(transformer_ffn=True): rebind TransformerLayer.forward (multiview_transformer.py:334-414) to the wrapper
+    around the fused kernels of transformer_ffn.py now if the module is imported, else as soon as it is (import hook).  Returns the
+    patched method or None."""
+    return _installed("transformer_ffn")[0]
 
 
 def install_depth_smoothness():
@@ -1075,7 +1167,7 @@ def install_psnr():
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
             depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, depth_head: bool = False, depth_tail: bool = False,
             erp_distance: bool = False, visualization: bool = False, depth_smoothness: bool = False, window_attention: bool = False,
-            group_norm: bool = False, unet_attention: bool = False, **opts):
+            group_norm: bool = False, unet_attention: bool = False, transformer_ffn: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
@@ -1114,6 +1206,10 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     to the fused QKV-attention kernels of splatter360_amd.qkv_attention, which read the channel-major qkv tensor in place and form
     no [b heads, L, L] weight tensor (install_unet_attention; off by default; composes with group_norm, whose AttentionBlock._forward
     calls self.attention, and with the reference's checkpoint).
+    transformer_ffn=True: ALSO rebind the multi-view transformer's TransformerLayer.forward (multiview_transformer.py:334-414) so
+    that norm1, cat([source, message]), the mlp, norm2 and the residual behind the layer's attention run the fused kernels of
+    splatter360_amd.transformer_ffn, which form no [T, 2C] or [T, 8C] tensor (install_transformer_ffn; off by default; composes
+    with window_attention in either order; state_dict keys are unchanged).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -1137,7 +1233,7 @@ def uninstall() -> None:
     compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates, depth_to_distance_map_batch, depth_map, prep_image,
     apply_color_map, EncoderCostVolume.map_pdf_to_opacity, LossDepth.forward, the backbone module's four attention functions,
     ResBlock._forward, AttentionBlock._forward, ResidualBlock.forward, DepthPredictorMultiView360.__init__,
-    QKVAttentionLegacy.forward, QKVAttention.forward and the predictor
+    QKVAttentionLegacy.forward, QKVAttention.forward, TransformerLayer.forward and the predictor
     module's `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
     sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, _SeamPatcher)]
     for seams in (*OPTION_SEAMS.values(), (DECODER_SEAM,)):

@@ -1,0 +1,249 @@
+"""The tail of the multi-view transformer's TransformerLayer on the GPU, forward and backward (csrc/s360_transformer_ffn.hip).
+
+Behind its attention the reference's TransformerLayer.forward (src/model/encoder/backbone/multiview_transformer.py:407-414) runs
+
+    message = norm1(merge(message))
+    message = mlp(cat([source, message], -1))      # Linear 2C -> 8C, GELU, Linear 8C -> C, no biases
+    message = norm2(message)
+    return source + message
+
+and, with no_ffn, `source + norm1(merge(message))`.  Autograd of those lines keeps the [T, 2C] concatenation and both [T, 8C]
+activations per layer (0.6 GB at the ERP shape, T = 65 536).  `ffn_tail` computes the same function with one fused forward kernel and
+a three-launch backward that recompute the hidden activations: the autograd node saves source, m, the second Linear's output z
+[T, C], one float64 (mean, rstd) pair per token and norm, and the parameters.  `layer_norm_residual` is the no_ffn tail.  The firm
+gain is memory; speed against torch's rocBLAS path is what profiles/transformer_ffn_timing.json says it is.  Float32 GPU tensors,
+C = 128 and hidden width 1024 (what both backbones use); there is no CPU path (the installed seam keeps the replaced method for
+everything else).  Forward and backward are bit-identical from run to run: fixed order, no atomics.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence
+
+import torch
+from torch import Tensor
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from .cost_volume import _ptr, _stream
+
+CHANNELS = 128
+HIDDEN = 1024
+FFN_GRADIENTS = ("g_source", "g_m", "g_norm1_weight", "g_norm1_bias", "g_w1", "g_w2", "g_norm2_weight", "g_norm2_bias")
+NORM_GRADIENTS = ("g_x", "g_weight", "g_bias", "g_residual")
+
+
+def supported_widths(channels: int, hidden: int = HIDDEN) -> bool:
+    return channels == CHANNELS and hidden == HIDDEN
+
+
+def weight_chunks(tokens: int) -> int:
+    """How many token chunks the weight-gradient pass of ffn_tail's backward uses for `tokens` tokens (at most 16, each a multiple
+    of 32 tokens but for the last)."""
+    if isinstance(tokens, bool) or not isinstance(tokens, int) or tokens < 1:
+        raise ValueError(f"weight_chunks: tokens must be a positive integer, got {tokens!r}")
+    return int(_lib.lib().s360_ffn_tail_weight_chunks(tokens))
+
+
+def _tensor(what: str, name: str, t, shape=None, dtype=torch.float32, device=None) -> None:
+    if not isinstance(t, Tensor):
+        raise ValueError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: {name} must be a GPU tensor (there is no CPU path), got device {t.device}")
+    if t.dtype != dtype:
+        raise ValueError(f"{what}: {name} must be {str(dtype).replace('torch.', '')}, got {t.dtype}")
+    if device is not None and t.device != device:
+        raise ValueError(f"{what}: {name} is on {t.device}, expected {device}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _eps(what: str, eps) -> float:
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps > 0:
+        raise ValueError(f"{what}: eps must be a positive number, got {eps!r}")
+    return float(eps)
+
+
+def _rows(what: str, name: str, t) -> int:
+    """Tokens of a [..., C] tensor with C = 128."""
+    _tensor(what, name, t)
+    if t.dim() < 1 or t.shape[-1] != CHANNELS:
+        raise ValueError(f"{what} takes {name} [..., C] with C = {CHANNELS}, got shape {tuple(t.shape)}")
+    if t.numel() == 0:
+        raise ValueError(f"{what}: {name} is empty, shape {tuple(t.shape)}")
+    return t.numel() // CHANNELS
+
+
+def _checked_ffn(what: str, source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps) -> int:
+    tokens = _rows(what, "source", source)
+    _tensor(what, "m", m, source.shape, device=source.device)
+    _tensor(what, "w1", w1, device=source.device)
+    _tensor(what, "w2", w2, device=source.device)
+    if tuple(w1.shape) != (HIDDEN, 2 * CHANNELS) or tuple(w2.shape) != (CHANNELS, HIDDEN):
+        raise ValueError(f"{what} takes w1 [{HIDDEN}, {2 * CHANNELS}] and w2 [{CHANNELS}, {HIDDEN}] (hidden width {HIDDEN}), got "
+                         f"{tuple(w1.shape)} and {tuple(w2.shape)}")
+    for name, t in (("norm1_weight", norm1_weight), ("norm1_bias", norm1_bias), ("norm2_weight", norm2_weight), ("norm2_bias", norm2_bias)):
+        _tensor(what, name, t, (CHANNELS,), device=source.device)
+    _eps(what, eps)
+    return tokens
+
+
+def _checked_norm(what: str, x, weight, bias, residual, eps) -> int:
+    tokens = _rows(what, "x", x)
+    _tensor(what, "residual", residual, x.shape, device=x.device)
+    _tensor(what, "weight", weight, (CHANNELS,), device=x.device)
+    _tensor(what, "bias", bias, (CHANNELS,), device=x.device)
+    _eps(what, eps)
+    return tokens
+
+
+def _flat(t: Tensor) -> Tensor:
+    """Detached, contiguous and 16-byte aligned: a non-contiguous (or misaligned) input is copied once."""
+    t = t.detach().contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _buffers(what: str, names: Sequence[str], like: Sequence[Tensor], given: Optional[dict]) -> list:
+    """The output buffers of a backward: `given` maps names to contiguous float32 buffers of the right shape on the device to write
+    into (every element is written); the others are allocated."""
+    given = dict(given or {})
+    unknown = set(given) - set(names)
+    if unknown:
+        raise ValueError(f"{what}: unknown buffers {sorted(unknown)}; the outputs are {list(names)}")
+    out = []
+    for name, ref in zip(names, like):
+        buf = given.get(name)
+        if buf is None:
+            buf = torch.empty(ref.shape, dtype=torch.float32, device=ref.device)
+        else:
+            _tensor(what, name, buf, ref.shape, device=ref.device)
+            if not buf.is_contiguous() or buf.data_ptr() % 16:
+                raise ValueError(f"{what}: the buffer {name} must be contiguous and 16-byte aligned")
+        out.append(buf)
+    return out
+
+
+def _scratch(tokens: int, device) -> Tensor:
+    return torch.empty(int(_lib.lib().s360_ffn_tail_scratch_bytes(tokens)), dtype=torch.uint8, device=device)
+
+
+def ffn_tail_forward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bias: Tensor, w1: Tensor, w2: Tensor, norm2_weight: Tensor,
+                     norm2_bias: Tensor, eps: float = 1e-5) -> tuple:
+    """s360_ffn_tail_forward -> (out in source's shape, z [T, C] float32, stats [2, T, 2] float64)."""
+    tokens = _checked_ffn("ffn_tail_forward", source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps)
+    args = [_flat(t) for t in (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias)]
+    out = torch.empty(source.shape, dtype=torch.float32, device=source.device)
+    z = torch.empty(tokens, CHANNELS, dtype=torch.float32, device=source.device)
+    stats = torch.empty(2, tokens, 2, dtype=torch.float64, device=source.device)
+    with torch.cuda.device(source.device):
+        rc = _lib.lib().s360_ffn_tail_forward(*(_ptr(t) for t in args), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))),
+                                              _ptr(out), _ptr(z), _ptr(stats), _stream(source.device))
+    _lib.check(rc, "s360_ffn_tail_forward")
+    return out, z, stats
+
+
+def ffn_tail_backward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bias: Tensor, w1: Tensor, w2: Tensor, norm2_weight: Tensor,
+                      norm2_bias: Tensor, z: Tensor, stats: Tensor, g_out: Tensor, eps: float = 1e-5, *, buffers: Optional[dict] = None) -> tuple:
+    """s360_ffn_tail_backward -> the gradients in FFN_GRADIENTS' order (the order of ffn_tail's arguments).  `buffers`: {name:
+    contiguous float32 buffer} for any of them to write into; the others are allocated."""
+    what = "ffn_tail_backward"
+    tokens = _checked_ffn(what, source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps)
+    _tensor(what, "g_out", g_out, source.shape, device=source.device)
+    _tensor(what, "z", z, (tokens, CHANNELS), device=source.device)
+    _tensor(what, "stats", stats, (2, tokens, 2), dtype=torch.float64, device=source.device)
+    ins = [_flat(t) for t in (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, z, stats, g_out)]
+    outs = dict(zip(FFN_GRADIENTS, _buffers(what, FFN_GRADIENTS, (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias),
+                                            buffers)))
+    scratch = _scratch(tokens, source.device)
+    order = ("g_source", "g_m", "g_w1", "g_w2", "g_norm1_weight", "g_norm1_bias", "g_norm2_weight", "g_norm2_bias")
+    with torch.cuda.device(source.device):
+        rc = _lib.lib().s360_ffn_tail_backward(*(_ptr(t) for t in ins), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))),
+                                               _ptr(scratch), scratch.numel(), *(_ptr(outs[n]) for n in order), _stream(source.device))
+    _lib.check(rc, "s360_ffn_tail_backward")
+    return tuple(outs[n] for n in FFN_GRADIENTS)
+
+
+def layer_norm_residual_forward(x: Tensor, weight: Tensor, bias: Tensor, residual: Tensor, eps: float = 1e-5) -> tuple:
+    """s360_layer_norm_residual_forward -> (out in x's shape, stats [T, 2] float64)."""
+    tokens = _checked_norm("layer_norm_residual_forward", x, weight, bias, residual, eps)
+    args = [_flat(t) for t in (x, weight, bias, residual)]
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    stats = torch.empty(tokens, 2, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().s360_layer_norm_residual_forward(*(_ptr(t) for t in args), tokens, CHANNELS, C.byref(C.c_double(float(eps))),
+                                                         _ptr(out), _ptr(stats), _stream(x.device))
+    _lib.check(rc, "s360_layer_norm_residual_forward")
+    return out, stats
+
+
+def layer_norm_residual_backward(x: Tensor, weight: Tensor, stats: Tensor, g_out: Tensor, *, buffers: Optional[dict] = None) -> tuple:
+    """s360_layer_norm_residual_backward -> (g_x, g_weight, g_bias, g_residual), NORM_GRADIENTS' order."""
+    what = "layer_norm_residual_backward"
+    tokens = _rows(what, "x", x)
+    _tensor(what, "weight", weight, (CHANNELS,), device=x.device)
+    _tensor(what, "g_out", g_out, x.shape, device=x.device)
+    _tensor(what, "stats", stats, (tokens, 2), dtype=torch.float64, device=x.device)
+    ins = [_flat(t) for t in (x, weight, stats, g_out)]
+    outs = dict(zip(NORM_GRADIENTS, _buffers(what, NORM_GRADIENTS, (x, weight, weight, x), buffers)))
+    scratch = _scratch(tokens, x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().s360_layer_norm_residual_backward(*(_ptr(t) for t in ins), tokens, CHANNELS, _ptr(scratch), scratch.numel(),
+                                                          _ptr(outs["g_x"]), _ptr(outs["g_residual"]), _ptr(outs["g_weight"]),
+                                                          _ptr(outs["g_bias"]), _stream(x.device))
+    _lib.check(rc, "s360_layer_norm_residual_backward")
+    return tuple(outs[n] for n in NORM_GRADIENTS)
+
+
+class _FFNTail(torch.autograd.Function):
+    """Saves source, m, z [T, C], the statistics and the parameters: nothing of size [T, 2C] or [T, 8C]."""
+
+    @staticmethod
+    def forward(ctx, source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps):
+        args = [_flat(t) for t in (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias)]
+        out, z, stats = ffn_tail_forward(*args, eps)
+        ctx.save_for_backward(*args, z, stats)
+        ctx.eps = eps
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        *args, z, stats = ctx.saved_tensors
+        return (*ffn_tail_backward(*args, z, stats, g_out.to(torch.float32), ctx.eps), None)
+
+
+class _LayerNormResidual(torch.autograd.Function):
+    """Saves x, the weight and one (mean, rstd) pair per token."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, eps):
+        x, weight = _flat(x), _flat(weight)
+        out, stats = layer_norm_residual_forward(x, weight, bias, residual, eps)
+        ctx.save_for_backward(x, weight, stats)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        x, weight, stats = ctx.saved_tensors
+        return (*layer_norm_residual_backward(x, weight, stats, g_out.to(torch.float32)), None)
+
+
+def ffn_tail(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bias: Tensor, w1: Tensor, w2: Tensor, norm2_weight: Tensor,
+             norm2_bias: Tensor, eps: float = 1e-5) -> Tensor:
+    """source + LN2(gelu(cat([source, LN1(m)], -1) w1^T) w2^T): the reference's TransformerLayer.forward :408-414 behind
+    `message = self.merge(message)`, m being that message.
+
+    source, m [..., C] with any leading dimensions; norm1 / norm2 weight and bias [C] (nn.LayerNorm's affine parameters, biased
+    variance, eps); w1 [8C, 2C] and w2 [C, 8C] (nn.Linear's layout, no biases); GELU in the erf form.  Returns a tensor of
+    source's shape.  Differentiable (once) in all eight tensors.  Float32 GPU tensors, C = 128 and 8C = 1024; no CPU path; a
+    non-contiguous input is copied once."""
+    _checked_ffn("ffn_tail", source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps)
+    return _FFNTail.apply(source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, float(eps))
+
+
+def layer_norm_residual(x: Tensor, weight: Tensor, bias: Tensor, residual: Tensor, eps: float = 1e-5) -> Tensor:
+    """residual + LN(x) weight + bias over the last axis: the tail of the reference's TransformerLayer with no_ffn (:408, :414).
+    x, residual [..., C]; weight, bias [C].  Differentiable (once) in all four.  Float32 GPU tensors, C = 128."""
+    _checked_norm("layer_norm_residual", x, weight, bias, residual, eps)
+    return _LayerNormResidual.apply(x, weight, bias, residual, float(eps))
