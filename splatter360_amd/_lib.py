@@ -63,21 +63,85 @@ class S360RawInputs(C.Structure):
                 ("erp_convention", C.c_int32), ("scale_min", C.c_float), ("scale_max", C.c_float), ("eps", C.c_float)]
 
 
-EXPORTS = ("s360_forward_raw", "s360_backward_raw", "s360_backward_raw_tail", "s360_abi_version", "s360_error_string", "s360_layout", "s360_forward", "s360_forward_depth", "s360_forward_mse", "s360_backward", "s360_backward_split", "s360_backward_composite", "s360_backward_gaussians", "s360_backward_pair_records", "s360_unpack_gradients", "s360_reduce_unpack_gradients", "s360_sh_backward", "s360_pack_views", "s360_adapter_forward", "s360_adapter_backward", "s360_sh_rotation_blocks",
-           "s360_cube2erp_forward", "s360_cube2erp_backward", "s360_count_contributions", "s360_count_backward_slots", "s360_profile_slots", "s360_profile_slot_name",
-           "s360_profile_enable", "s360_profile_collect", "s360_ssim", "s360_erode", "s360_l1_sphere_forward",
-           "s360_l1_sphere_backward", "s360_depth_metrics", "s360_psnr", "s360_cost_volume_forward", "s360_cost_volume_backward",
-           "s360_cost_volume_warp", "s360_depth_head_forward", "s360_depth_head_backward", "s360_upsample_forward", "s360_upsample_backward",
-           "s360_depth_tail_forward", "s360_depth_tail_backward", "s360_opacity_map_forward", "s360_opacity_map_backward",
-           "s360_erp2cube_forward", "s360_erp2cube_backward", "s360_depth_to_distance_forward", "s360_depth_to_distance_backward",
-           "s360_cube2erp_distance_forward", "s360_cube2erp_distance_backward",
-           "s360_depth_colormap", "s360_colorize", "s360_prep_image", "s360_error_map",
-           "s360_depth_smooth_forward", "s360_depth_smooth_backward",
-           "s360_window_attention_forward", "s360_window_attention_backward",
-           "s360_group_norm_scratch_doubles", "s360_group_norm_forward", "s360_group_norm_backward",
-           "s360_qkv_attention_forward", "s360_qkv_attention_backward",
-           "s360_ffn_tail_scratch_bytes", "s360_ffn_tail_weight_chunks", "s360_ffn_tail_forward", "s360_ffn_tail_backward",
-           "s360_layer_norm_residual_forward", "s360_layer_norm_residual_backward")
+_int, _i32, _i64, _sz, _f32, _vp = C.c_int, C.c_int32, C.c_int64, C.c_size_t, C.c_float, C.c_void_p
+_prm, _raw = C.POINTER(S360Params), C.POINTER(S360RawInputs)
+_p32, _p64, _psz, _pf64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_size_t), C.POINTER(C.c_double)
+
+# Every function include/s360.h declares: name -> (restype, argtypes).  lib() applies it; tests/test_abi.py holds it to the header.
+SIGNATURES = {
+    "s360_abi_version": (_int, []),
+    "s360_error_string": (C.c_char_p, [_int]),
+    "s360_layout": (_int, [_prm, C.POINTER(S360Layout)]),
+    "s360_forward": (_int, [_prm] + [_vp] * 9 + [_sz, _vp]),
+    "s360_forward_depth": (_int, [_prm] + [_vp] * 8 + [_i32, _vp, _vp, _sz, _vp]),
+    "s360_forward_mse": (_int, [_prm] + [_vp] * 8 + [_i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "s360_backward": (_int, [_prm] + [_vp] * 7 + [_sz] + [_vp] * 3 + [_i32] + [_vp] * 7 + [_sz, _vp]),
+    "s360_backward_split": (_int, [_prm] + [_vp] * 6 + [_sz] + [_vp] * 3 + [_i32] + [_vp] * 6 + [_sz, _vp]),
+    "s360_backward_composite": (_int, [_prm, _vp, _vp, _sz, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "s360_backward_gaussians": (_int, [_prm, _vp, _vp, _vp, _vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "s360_backward_pair_records": (_int, [_prm, _vp, _sz, _psz]),
+    "s360_reduce_unpack_gradients": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "s360_unpack_gradients": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "s360_sh_backward": (_int, [_prm, _i32] + [_vp] * 5),
+    "s360_forward_raw": (_int, [_prm, _vp, _raw] + [_vp] * 5 + [_i32, _vp, _vp, _f32] + [_vp] * 4 + [_sz, _vp]),
+    "s360_backward_raw_tail": (_int, [_prm, _vp, _i32, _raw, _vp, _vp, _sz] + [_vp] * 6),
+    "s360_backward_raw": (_int, [_prm, _vp, _raw] + [_vp] * 4 + [_sz] + [_vp] * 3 + [_i32, _i32] + [_vp] * 7 + [_sz, _vp]),
+    "s360_pack_views": (_int, [_vp] * 5 + [_i32, _i32, _i32, _vp, _vp]),
+    "s360_adapter_forward": (_int, [_vp] * 4 + [_i32] * 6 + [_f32] * 3 + [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "s360_adapter_backward": (_int, [_vp] * 4 + [_i32] * 6 + [_f32] * 3 + [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "s360_sh_rotation_blocks": (_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "s360_cube2erp_forward": (_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _p32, _p64, _vp]),
+    "s360_cube2erp_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _p32, _p64, _vp]),
+    "s360_ssim": (_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _psz, _vp]),
+    "s360_erode": (_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "s360_l1_sphere_forward": (_int, [_vp] * 4 + [_i32] * 5 + [_vp, _f32, _f32, _i32, _vp, _vp, _vp, _psz, _vp]),
+    "s360_l1_sphere_backward": (_int, [_vp] * 4 + [_i32] * 5 + [_vp, _f32, _f32, _i32] + [_vp] * 5),
+    "s360_depth_metrics": (_int, [_vp] * 3 + [_i32, _i32] + [_sz] * 3 + [_i32, _sz, _sz, _f32] + [_i32] * 5 + [_vp] * 4 + [_psz, _vp]),
+    "s360_psnr": (_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _psz, _vp]),
+    "s360_cost_volume_forward": (_int, [_vp] * 5 + [_i32] * 8 + [_f32, _vp, _vp, _psz, _vp]),
+    "s360_cost_volume_backward": (_int, [_vp] * 5 + [_i32] * 8 + [_f32, _vp, _vp, _vp, _vp, _psz, _vp]),
+    "s360_cost_volume_warp": (_int, [_vp] * 4 + [_i32] * 7 + [_vp, _vp]),
+    "s360_depth_head_forward": (_int, [_vp, _vp] + [_i32] * 4 + [_vp] * 5),
+    "s360_depth_head_backward": (_int, [_vp] * 7 + [_i32] * 4 + [_vp, _vp]),
+    "s360_upsample_forward": (_int, [_vp, _vp] + [_i32] * 6 + [_vp]),
+    "s360_upsample_backward": (_int, [_vp] * 3 + [_i32] * 6 + [_vp]),
+    "s360_depth_tail_forward": (_int, [_vp] * 4 + [_f32, _i32, _i32] + [_vp] * 3 + [_i32] * 3 + [_vp]),
+    "s360_depth_tail_backward": (_int, [_vp] * 7 + [_f32, _i32, _i32, _vp, _vp] + [_i32] * 3 + [_vp]),
+    "s360_opacity_map_forward": (_int, [_vp, _vp, _sz, _f32, _vp]),
+    "s360_opacity_map_backward": (_int, [_vp, _vp, _vp, _sz, _f32, _vp]),
+    "s360_erp2cube_forward": (_int, [_vp] * 4 + [_i32] * 8 + [_p32, _p64, _vp]),
+    "s360_erp2cube_backward": (_int, [_vp] * 6 + [_i32] * 7 + [_p32, _p64, _vp]),
+    "s360_depth_to_distance_forward": (_int, [_vp] * 3 + [_i32] * 4 + [_vp]),
+    "s360_depth_to_distance_backward": (_int, [_vp] * 4 + [_i32] * 4 + [_vp]),
+    "s360_cube2erp_distance_forward": (_int, [_vp] * 4 + [_i32] * 5 + [_p32, _p64, _vp]),
+    "s360_cube2erp_distance_backward": (_int, [_vp] * 7 + [_i32] * 5 + [_p32, _p64, _vp]),
+    "s360_depth_colormap": (_int, [_vp, _i32, _i32, _i32, _sz, _vp, _vp, _vp, _vp, _psz, _vp]),
+    "s360_colorize": (_int, [_vp, _sz, _sz, _i32, _i32, _vp, _vp, _vp]),
+    "s360_prep_image": (_int, [_vp] + [_i32] * 4 + [_vp, _vp]),
+    "s360_error_map": (_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "s360_depth_smooth_forward": (_int, [_vp] * 4 + [_i32] * 6 + [_f32, _i32, _vp, _vp, _psz, _vp]),
+    "s360_depth_smooth_backward": (_int, [_vp] * 4 + [_i32] * 6 + [_f32, _i32, _vp, _vp, _vp]),
+    "s360_window_attention_forward": (_int, [_vp] * 3 + [_i32] * 8 + [_vp] * 3),
+    "s360_window_attention_backward": (_int, [_vp] * 5 + [_i32] * 8 + [_vp] * 5),
+    "s360_group_norm_scratch_doubles": (_sz, [_i32, _i32, _i64]),
+    "s360_group_norm_forward": (_int, [_vp] * 4 + [_i32, _i32, _sz, _i32, _pf64, _i32] + [_vp] * 4),
+    "s360_group_norm_backward": (_int, [_vp] * 5 + [_i32, _i32, _sz, _i32, _pf64, _i32] + [_vp] * 5),
+    "s360_qkv_attention_forward": (_int, [_vp] + [_i32] * 6 + [_vp] * 3),
+    "s360_qkv_attention_backward": (_int, [_vp] * 3 + [_i32] * 6 + [_vp] * 3),
+    "s360_ffn_tail_scratch_bytes": (_sz, [_i32]),
+    "s360_ffn_tail_weight_chunks": (_int, [_i32]),
+    "s360_ffn_tail_forward": (_int, [_vp] * 8 + [_i32] * 3 + [_pf64] + [_vp] * 4),
+    "s360_ffn_tail_backward": (_int, [_vp] * 11 + [_i32] * 3 + [_pf64, _vp, _sz] + [_vp] * 9),
+    "s360_layer_norm_residual_forward": (_int, [_vp] * 4 + [_i32, _i32, _pf64] + [_vp] * 3),
+    "s360_layer_norm_residual_backward": (_int, [_vp] * 4 + [_i32, _i32, _vp, _sz] + [_vp] * 5),
+    "s360_count_backward_slots": (_int, [_prm, _vp, _sz, _vp, _vp]),
+    "s360_count_contributions": (_int, [_prm, _vp, _sz, _vp, _vp]),
+    "s360_profile_slots": (_int, []),
+    "s360_profile_slot_name": (C.c_char_p, [_int]),
+    "s360_profile_enable": (_int, [_int]),
+    "s360_profile_collect": (_int, [C.POINTER(_f32), _p32]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 def _hipcc() -> str:
@@ -163,145 +227,9 @@ def lib() -> C.CDLL:
             f"{LIB_PATH} is missing: the HIP rasteriser was not built. Run "
             "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). There is no CPU fallback.")
     l = C.CDLL(str(LIB_PATH))
-    vp, i32, sz = C.c_void_p, C.c_int32, C.c_size_t
-    l.s360_abi_version.restype = C.c_int
-    l.s360_error_string.restype = C.c_char_p
-    l.s360_error_string.argtypes = [C.c_int]
-    l.s360_layout.restype = C.c_int
-    l.s360_layout.argtypes = [C.POINTER(S360Params), C.POINTER(S360Layout)]
-    l.s360_forward.restype = C.c_int
-    l.s360_forward.argtypes = [C.POINTER(S360Params)] + [vp] * 9 + [sz, vp]
-    l.s360_forward_depth.restype = C.c_int
-    l.s360_forward_depth.argtypes = [C.POINTER(S360Params)] + [vp] * 8 + [i32, vp, vp, sz, vp]
-    l.s360_forward_mse.restype = C.c_int
-    l.s360_forward_mse.argtypes = [C.POINTER(S360Params)] + [vp] * 8 + [i32, vp, vp, C.c_float, vp, vp, vp, vp, sz, vp]
-    l.s360_backward.restype = C.c_int
-    l.s360_backward.argtypes = [C.POINTER(S360Params)] + [vp] * 7 + [sz] + [vp] * 3 + [i32] + [vp] * 7 + [sz, vp]
-    l.s360_backward_split.restype = C.c_int
-    l.s360_backward_split.argtypes = [C.POINTER(S360Params)] + [vp] * 6 + [sz] + [vp] * 3 + [i32] + [vp] * 6 + [sz, vp]
-    l.s360_backward_composite.restype = C.c_int
-    l.s360_backward_composite.argtypes = [C.POINTER(S360Params), vp, vp, sz, vp, vp, vp, i32, vp, sz, vp]
-    l.s360_backward_gaussians.restype = C.c_int
-    l.s360_backward_gaussians.argtypes = [C.POINTER(S360Params), vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]
-    l.s360_backward_pair_records.restype = C.c_int
-    l.s360_backward_pair_records.argtypes = [C.POINTER(S360Params), vp, sz, C.POINTER(sz)]
-    l.s360_reduce_unpack_gradients.restype = C.c_int
-    l.s360_reduce_unpack_gradients.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    l.s360_unpack_gradients.restype = C.c_int
-    l.s360_unpack_gradients.argtypes = [vp, i32, i32, vp, vp, vp, vp]
-    l.s360_sh_backward.restype = C.c_int
-    l.s360_sh_backward.argtypes = [C.POINTER(S360Params), i32] + [vp] * 5
-    l.s360_forward_raw.restype = C.c_int
-    l.s360_forward_raw.argtypes = [C.POINTER(S360Params), vp, C.POINTER(S360RawInputs)] + [vp] * 5 + [i32, vp, vp, C.c_float] + [vp] * 4 + [sz, vp]
-    l.s360_backward_raw_tail.restype = C.c_int
-    l.s360_backward_raw_tail.argtypes = [C.POINTER(S360Params), vp, i32, C.POINTER(S360RawInputs), vp, vp, sz] + [vp] * 6
-    l.s360_backward_raw.restype = C.c_int
-    l.s360_backward_raw.argtypes = [C.POINTER(S360Params), vp, C.POINTER(S360RawInputs)] + [vp] * 4 + [sz] + [vp] * 3 + [i32, i32] + [vp] * 7 + [sz, vp]
-    l.s360_pack_views.restype = C.c_int
-    l.s360_pack_views.argtypes = [vp] * 5 + [i32, i32, i32, vp, vp]
-    f32 = C.c_float
-    l.s360_adapter_forward.restype = C.c_int
-    l.s360_adapter_forward.argtypes = [vp] * 4 + [i32] * 6 + [f32] * 3 + [vp, vp, i32, vp, vp, vp, i32, vp]
-    l.s360_adapter_backward.restype = C.c_int
-    l.s360_adapter_backward.argtypes = [vp] * 4 + [i32] * 6 + [f32] * 3 + [vp, vp, i32, vp, vp, vp, i32, vp]
-    l.s360_sh_rotation_blocks.restype = C.c_int
-    l.s360_sh_rotation_blocks.argtypes = [vp, i32, i32, i32, vp, vp]
-    l.s360_cube2erp_forward.restype = C.c_int
-    l.s360_cube2erp_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_int64), vp]
-    l.s360_cube2erp_backward.restype = C.c_int
-    l.s360_cube2erp_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_int64), vp]
-    l.s360_ssim.restype = C.c_int
-    l.s360_ssim.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, C.POINTER(sz), vp]
-    l.s360_erode.restype = C.c_int
-    l.s360_erode.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-    l.s360_l1_sphere_forward.restype = C.c_int
-    l.s360_l1_sphere_forward.argtypes = [vp] * 4 + [i32] * 5 + [vp, f32, f32, i32, vp, vp, vp, C.POINTER(sz), vp]
-    l.s360_l1_sphere_backward.restype = C.c_int
-    l.s360_l1_sphere_backward.argtypes = [vp] * 4 + [i32] * 5 + [vp, f32, f32, i32] + [vp] * 5
-    l.s360_depth_metrics.restype = C.c_int
-    l.s360_depth_metrics.argtypes = [vp] * 3 + [i32, i32] + [sz] * 3 + [i32, sz, sz, f32] + [i32] * 5 + [vp] * 4 + [C.POINTER(sz), vp]
-    l.s360_psnr.restype = C.c_int
-    l.s360_psnr.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, C.POINTER(sz), vp]
-    l.s360_cost_volume_forward.restype = C.c_int
-    l.s360_cost_volume_forward.argtypes = [vp] * 5 + [i32] * 8 + [f32, vp, vp, C.POINTER(sz), vp]
-    l.s360_cost_volume_backward.restype = C.c_int
-    l.s360_cost_volume_backward.argtypes = [vp] * 5 + [i32] * 8 + [f32, vp, vp, vp, vp, C.POINTER(sz), vp]
-    l.s360_cost_volume_warp.restype = C.c_int
-    l.s360_cost_volume_warp.argtypes = [vp] * 4 + [i32] * 7 + [vp, vp]
-    l.s360_depth_head_forward.restype = C.c_int
-    l.s360_depth_head_forward.argtypes = [vp, vp] + [i32] * 4 + [vp] * 5
-    l.s360_depth_head_backward.restype = C.c_int
-    l.s360_depth_head_backward.argtypes = [vp] * 7 + [i32] * 4 + [vp, vp]
-    l.s360_upsample_forward.restype = C.c_int
-    l.s360_upsample_forward.argtypes = [vp, vp] + [i32] * 6 + [vp]
-    l.s360_upsample_backward.restype = C.c_int
-    l.s360_upsample_backward.argtypes = [vp] * 3 + [i32] * 6 + [vp]
-    l.s360_depth_tail_forward.restype = C.c_int
-    l.s360_depth_tail_forward.argtypes = [vp] * 4 + [f32, i32, i32] + [vp] * 3 + [i32] * 3 + [vp]
-    l.s360_depth_tail_backward.restype = C.c_int
-    l.s360_depth_tail_backward.argtypes = [vp] * 7 + [f32, i32, i32, vp, vp] + [i32] * 3 + [vp]
-    l.s360_opacity_map_forward.restype = C.c_int
-    l.s360_opacity_map_forward.argtypes = [vp, vp, sz, f32, vp]
-    l.s360_opacity_map_backward.restype = C.c_int
-    l.s360_opacity_map_backward.argtypes = [vp, vp, vp, sz, f32, vp]
-    l.s360_erp2cube_forward.restype = C.c_int
-    l.s360_erp2cube_forward.argtypes = [vp] * 4 + [i32] * 8 + [C.POINTER(i32), C.POINTER(C.c_int64), vp]
-    l.s360_erp2cube_backward.restype = C.c_int
-    l.s360_erp2cube_backward.argtypes = [vp] * 6 + [i32] * 7 + [C.POINTER(i32), C.POINTER(C.c_int64), vp]
-    l.s360_depth_to_distance_forward.restype = C.c_int
-    l.s360_depth_to_distance_forward.argtypes = [vp] * 3 + [i32] * 4 + [vp]
-    l.s360_depth_to_distance_backward.restype = C.c_int
-    l.s360_depth_to_distance_backward.argtypes = [vp] * 4 + [i32] * 4 + [vp]
-    l.s360_cube2erp_distance_forward.restype = C.c_int
-    l.s360_cube2erp_distance_forward.argtypes = [vp] * 4 + [i32] * 5 + [C.POINTER(i32), C.POINTER(C.c_int64), vp]
-    l.s360_cube2erp_distance_backward.restype = C.c_int
-    l.s360_cube2erp_distance_backward.argtypes = [vp] * 7 + [i32] * 5 + [C.POINTER(i32), C.POINTER(C.c_int64), vp]
-    l.s360_depth_colormap.restype = C.c_int
-    l.s360_depth_colormap.argtypes = [vp, i32, i32, i32, sz, vp, vp, vp, vp, C.POINTER(sz), vp]
-    l.s360_colorize.restype = C.c_int
-    l.s360_colorize.argtypes = [vp, sz, sz, i32, i32, vp, vp, vp]
-    l.s360_prep_image.restype = C.c_int
-    l.s360_prep_image.argtypes = [vp] + [i32] * 4 + [vp, vp]
-    l.s360_error_map.restype = C.c_int
-    l.s360_error_map.argtypes = [vp, vp, i32, i32, vp, vp]
-    l.s360_depth_smooth_forward.restype = C.c_int
-    l.s360_depth_smooth_forward.argtypes = [vp] * 4 + [i32] * 6 + [f32, i32, vp, vp, C.POINTER(sz), vp]
-    l.s360_depth_smooth_backward.restype = C.c_int
-    l.s360_depth_smooth_backward.argtypes = [vp] * 4 + [i32] * 6 + [f32, i32, vp, vp, vp]
-    l.s360_window_attention_forward.restype = C.c_int
-    l.s360_window_attention_forward.argtypes = [vp] * 3 + [i32] * 8 + [vp] * 3
-    l.s360_window_attention_backward.restype = C.c_int
-    l.s360_window_attention_backward.argtypes = [vp] * 5 + [i32] * 8 + [vp] * 5
-    l.s360_group_norm_scratch_doubles.restype = sz
-    l.s360_group_norm_scratch_doubles.argtypes = [i32, i32, C.c_int64]
-    l.s360_group_norm_forward.restype = C.c_int
-    l.s360_group_norm_forward.argtypes = [vp] * 4 + [i32, i32, sz, i32, C.POINTER(C.c_double), i32] + [vp] * 4
-    l.s360_group_norm_backward.restype = C.c_int
-    l.s360_group_norm_backward.argtypes = [vp] * 5 + [i32, i32, sz, i32, C.POINTER(C.c_double), i32] + [vp] * 5
-    l.s360_qkv_attention_forward.restype = C.c_int
-    l.s360_qkv_attention_forward.argtypes = [vp] + [i32] * 6 + [vp] * 3
-    l.s360_qkv_attention_backward.restype = C.c_int
-    l.s360_qkv_attention_backward.argtypes = [vp] * 3 + [i32] * 6 + [vp] * 3
-    l.s360_ffn_tail_scratch_bytes.restype = sz
-    l.s360_ffn_tail_scratch_bytes.argtypes = [i32]
-    l.s360_ffn_tail_weight_chunks.restype = C.c_int
-    l.s360_ffn_tail_weight_chunks.argtypes = [i32]
-    l.s360_ffn_tail_forward.restype = C.c_int
-    l.s360_ffn_tail_forward.argtypes = [vp] * 8 + [i32] * 3 + [C.POINTER(C.c_double)] + [vp] * 4
-    l.s360_ffn_tail_backward.restype = C.c_int
-    l.s360_ffn_tail_backward.argtypes = [vp] * 11 + [i32] * 3 + [C.POINTER(C.c_double), vp, sz] + [vp] * 9
-    l.s360_layer_norm_residual_forward.restype = C.c_int
-    l.s360_layer_norm_residual_forward.argtypes = [vp] * 4 + [i32, i32, C.POINTER(C.c_double)] + [vp] * 3
-    l.s360_layer_norm_residual_backward.restype = C.c_int
-    l.s360_layer_norm_residual_backward.argtypes = [vp] * 4 + [i32, i32, vp, sz] + [vp] * 5
-    l.s360_count_backward_slots.restype = C.c_int
-    l.s360_count_backward_slots.argtypes = [C.POINTER(S360Params), vp, sz, vp, vp]
-    l.s360_count_contributions.restype = C.c_int
-    l.s360_count_contributions.argtypes = [C.POINTER(S360Params), vp, sz, vp, vp]
-    l.s360_profile_slot_name.restype = C.c_char_p
-    l.s360_profile_slot_name.argtypes = [C.c_int]
-    l.s360_profile_enable.argtypes = [C.c_int]
-    l.s360_profile_collect.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(l, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if l.s360_abi_version() != ABI_VERSION:
         raise RuntimeError("libs360.so ABI version mismatch")
     _lib = l

@@ -30,7 +30,7 @@ from typing import Optional
 import torch
 from torch import Tensor
 
-from . import _lib
+from ._call import call, ptr
 
 
 @dataclass
@@ -69,10 +69,6 @@ def wigner_blocks_e3nn(c2w_rotations: Tensor, d_sh: int) -> Tensor:
     return out
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def sh_rotation_blocks(rotations: Tensor, d_sh: int) -> Tensor:
     """[V,3,3] rotations (or [V,4,4] poses: their rotation part) -> [V,d_sh,d_sh] block-diagonal matrices of rotate_sh
     (sh_rotation.py:19-24) from s360_sh_rotation_blocks: one launch, no host synchronisation, no e3nn.  Not differentiable
@@ -84,10 +80,7 @@ def sh_rotation_blocks(rotations: Tensor, d_sh: int) -> Tensor:
         raise RuntimeError(f"rotations must be [V,3,3] or [V,4,4], got {tuple(r.shape)}")
     v = int(r.shape[0])
     out = torch.empty((v, d_sh, d_sh), dtype=torch.float32, device=r.device)
-    with torch.cuda.device(r.device):
-        stream = C.c_void_p(torch.cuda.current_stream(r.device).cuda_stream)
-        rc = _lib.lib().s360_sh_rotation_blocks(_ptr(r), 9 if r.shape[-1] == 3 else 16, v, int(d_sh), _ptr(out), stream)
-    _lib.check(rc, "s360_sh_rotation_blocks")
+    call("s360_sh_rotation_blocks", r.device, ptr(r), 9 if r.shape[-1] == 3 else 16, v, int(d_sh), ptr(out))
     return out
 
 
@@ -112,12 +105,9 @@ class _AdapterTail(torch.autograd.Function):
         harm = torch.empty((v, gv, 3, d_sh), dtype=torch.float32, device=dev)
         scales = torch.empty((v, gv, 3), dtype=torch.float32, device=dev)
         rots = torch.empty((v, gv, 4), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            rc = _lib.lib().s360_adapter_forward(_ptr(ext), _ptr(dep), _ptr(rw), _ptr(rot), v, gv, h, w, per_ray, d_sh,
-                                                 C.c_float(smin), C.c_float(smax), C.c_float(eps), _ptr(means), _ptr(cov),
-                                                 int(not cov6), _ptr(harm), _ptr(scales), _ptr(rots), conv, stream)
-        _lib.check(rc, "s360_adapter_forward")
+        call("s360_adapter_forward", dev, ptr(ext), ptr(dep), ptr(rw), ptr(rot), v, gv, h, w, per_ray, d_sh,
+             C.c_float(smin), C.c_float(smax), C.c_float(eps), ptr(means), ptr(cov),
+             int(not cov6), ptr(harm), ptr(scales), ptr(rots), conv)
         ctx.cfg = (h, w, per_ray, smin, smax, eps, cov6, v, gv, d_sh, diff_means, conv)
         ctx.save_for_backward(ext, dep, rw, rot)
         if diff_means:
@@ -137,12 +127,9 @@ class _AdapterTail(torch.autograd.Function):
         d_harm = z(d_harm, (v, gv, 3, d_sh))
         d_dep = torch.empty_like(dep)
         d_raw = torch.empty_like(rw)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            rc = _lib.lib().s360_adapter_backward(_ptr(ext), _ptr(dep), _ptr(rw), _ptr(rot), v, gv, h, w, per_ray, d_sh,
-                                                  C.c_float(smin), C.c_float(smax), C.c_float(eps), _ptr(d_means), _ptr(d_cov),
-                                                  int(not cov6), _ptr(d_harm), _ptr(d_dep), _ptr(d_raw), conv, stream)
-        _lib.check(rc, "s360_adapter_backward")
+        call("s360_adapter_backward", dev, ptr(ext), ptr(dep), ptr(rw), ptr(rot), v, gv, h, w, per_ray, d_sh,
+             C.c_float(smin), C.c_float(smax), C.c_float(eps), ptr(d_means), ptr(d_cov),
+             int(not cov6), ptr(d_harm), ptr(d_dep), ptr(d_raw), conv)
         return None, d_dep, d_raw, None, None
 
 

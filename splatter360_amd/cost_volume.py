@@ -15,28 +15,10 @@ import torch
 from torch import Tensor
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from ._call import _check_cuda_f32, call, invoke, ptr
 
 CONVENTIONS = {"hm3d": 0, "replica": 0}        # S360_CV_HM3D serves both (src/geometry/utils360.py:93, :148, :193, :250)
 SAMPLINGS = ("inverse_depth", "log_depth", "linear_depth")
-
-
-def _ptr(t) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
-
-
-def _stream(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _check_cuda_f32(what: str, *ts: Tensor) -> None:
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError(f"{what} runs on the GPU only (no CPU path)")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{what} takes float32 tensors, got {t.dtype}")
-        if t.device != ts[0].device:
-            raise ValueError(f"{what}: tensors on different devices ({ts[0].device}, {t.device})")
 
 
 def _convention(dataset_name: str) -> int:
@@ -100,9 +82,9 @@ def partner_slots(b: int, v: int, device) -> Tensor:
     return torch.stack(rows, dim=0).to(torch.int32).to(device)
 
 
-def _workspace(fn, args, device) -> tuple:
+def _workspace(name, args, device) -> tuple:
     nbytes = C.c_size_t(0)
-    _lib.check(fn(*args, None, C.byref(nbytes), None), fn.__name__ + " (workspace size)")
+    invoke(name, *args, None, C.byref(nbytes), None)
     return torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=device), nbytes
 
 
@@ -112,13 +94,10 @@ def correlation_forward(f_own: Tensor, f_partner: Tensor, slots, poses: Tensor, 
     n, c, h, w = (int(s) for s in f_own.shape)
     m, pairs, d = int(f_partner.shape[0]), int(poses.shape[0]), int(depths.shape[1])
     out = torch.empty(n, d, h, w, dtype=torch.float32, device=f_own.device)
-    fn = _lib.lib().s360_cost_volume_forward
     dims = (n, m, pairs, c, h, w, d, convention, C.c_float(scale))
-    ws, nbytes = _workspace(fn, (None, None, None, None, None, *dims, None), f_own.device)
-    with torch.cuda.device(f_own.device):
-        rc = fn(_ptr(f_own), _ptr(f_partner), _ptr(slots), _ptr(poses), _ptr(depths), *dims, _ptr(out), _ptr(ws), C.byref(nbytes),
-                _stream(f_own.device))
-    _lib.check(rc, "s360_cost_volume_forward")
+    ws, nbytes = _workspace("s360_cost_volume_forward", (None, None, None, None, None, *dims, None), f_own.device)
+    call("s360_cost_volume_forward", f_own.device, ptr(f_own), ptr(f_partner), ptr(slots), ptr(poses), ptr(depths), *dims, ptr(out),
+         ptr(ws), C.byref(nbytes))
     return out
 
 
@@ -129,13 +108,10 @@ def correlation_backward(g: Tensor, f_own: Tensor, f_partner: Tensor, slots, pos
     m, pairs, d = int(f_partner.shape[0]), int(poses.shape[0]), int(depths.shape[1])
     g = g.to(torch.float32).contiguous()
     g_own, g_partner = torch.empty_like(f_own), torch.empty_like(f_partner)
-    fn = _lib.lib().s360_cost_volume_backward
     dims = (n, m, pairs, c, h, w, d, convention, C.c_float(scale))
-    ws, nbytes = _workspace(fn, (None, None, None, None, None, *dims, None, None, None), f_own.device)
-    with torch.cuda.device(f_own.device):
-        rc = fn(_ptr(f_own), _ptr(f_partner), _ptr(slots), _ptr(poses), _ptr(depths), *dims, _ptr(g), _ptr(g_own), _ptr(g_partner),
-                _ptr(ws), C.byref(nbytes), _stream(f_own.device))
-    _lib.check(rc, "s360_cost_volume_backward")
+    ws, nbytes = _workspace("s360_cost_volume_backward", (None, None, None, None, None, *dims, None, None, None), f_own.device)
+    call("s360_cost_volume_backward", f_own.device, ptr(f_own), ptr(f_partner), ptr(slots), ptr(poses), ptr(depths), *dims, ptr(g),
+         ptr(g_own), ptr(g_partner), ptr(ws), C.byref(nbytes))
     return g_own, g_partner
 
 
@@ -249,10 +225,8 @@ def warp_with_pose_depth_candidates(utils360, feature1: Tensor, pose: Tensor, de
         raise ValueError(f"warp_with_pose_depth_candidates: depth {tuple(depth.shape)} does not match feature1 {tuple(feature1.shape)}")
     f = feature1.detach().contiguous()
     out = torch.empty(n, c, d, h, w, dtype=torch.float32, device=f.device)
-    with torch.cuda.device(f.device):
-        rc = _lib.lib().s360_cost_volume_warp(_ptr(f), None, _ptr(pose.detach().contiguous()), _ptr(depth.detach()[:, :, 0, 0].contiguous()),
-                                              n, n, c, h, w, d, convention, _ptr(out), _stream(f.device))
-    _lib.check(rc, "s360_cost_volume_warp")
+    call("s360_cost_volume_warp", f.device, ptr(f), None, ptr(pose.detach().contiguous()), ptr(depth.detach()[:, :, 0, 0].contiguous()),
+         n, n, c, h, w, d, convention, ptr(out))
     return out
 
 

@@ -18,8 +18,7 @@ import torch.nn.functional as F
 from torch import Tensor
 from torch.autograd.function import once_differentiable
 
-from . import _lib
-from .cost_volume import _check_cuda_f32, _ptr, _stream
+from ._call import _check_cuda_f32, call, ptr
 
 
 def head_forward(logits: Tensor, candidates: Tensor) -> tuple:
@@ -28,10 +27,7 @@ def head_forward(logits: Tensor, candidates: Tensor) -> tuple:
     n, d, h, w = (int(s) for s in logits.shape)
     depth, pmax, lse = (torch.empty(n, 1, h, w, dtype=torch.float32, device=logits.device) for _ in range(3))
     argmax = torch.empty(n, 1, h, w, dtype=torch.int32, device=logits.device)
-    with torch.cuda.device(logits.device):
-        rc = _lib.lib().s360_depth_head_forward(_ptr(logits), _ptr(candidates), n, d, h, w, _ptr(depth), _ptr(pmax), _ptr(lse), _ptr(argmax),
-                                                _stream(logits.device))
-    _lib.check(rc, "s360_depth_head_forward")
+    call("s360_depth_head_forward", logits.device, ptr(logits), ptr(candidates), n, d, h, w, ptr(depth), ptr(pmax), ptr(lse), ptr(argmax))
     return depth, pmax, lse, argmax
 
 
@@ -40,10 +36,8 @@ def head_backward(logits: Tensor, candidates: Tensor, lse: Tensor, depth: Tensor
     n, d, h, w = (int(s) for s in logits.shape)
     g_depth, g_pmax = (None if g is None else g.to(torch.float32).contiguous() for g in (g_depth, g_pmax))
     g_logits = torch.empty_like(logits)
-    with torch.cuda.device(logits.device):
-        rc = _lib.lib().s360_depth_head_backward(_ptr(logits), _ptr(candidates), _ptr(lse), _ptr(depth), _ptr(argmax), _ptr(g_depth),
-                                                 _ptr(g_pmax), n, d, h, w, _ptr(g_logits), _stream(logits.device))
-    _lib.check(rc, "s360_depth_head_backward")
+    call("s360_depth_head_backward", logits.device, ptr(logits), ptr(candidates), ptr(lse), ptr(depth), ptr(argmax), ptr(g_depth),
+         ptr(g_pmax), n, d, h, w, ptr(g_logits))
     return g_logits
 
 

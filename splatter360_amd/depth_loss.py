@@ -16,7 +16,7 @@ import torch
 from torch import Tensor
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from ._call import _check_cuda_f32, call, invoke, ptr
 
 FUSED_MAX_KSIZE = 17
 _WEIGHTS = {}
@@ -33,24 +33,6 @@ def row_weights(height: int, device) -> Tensor:
         w = torch.sin((w + 0.5) * torch.pi / height)
         _WEIGHTS[key] = w
     return w
-
-
-def _ptr(t: Tensor) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
-
-
-def _stream(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _check_cuda_f32(what: str, *ts: Tensor) -> None:
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError(f"{what} runs on the GPU only (no CPU path)")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{what} takes float32 tensors, got {t.dtype}")
-        if t.device != ts[0].device:
-            raise ValueError(f"{what}: tensors on different devices ({ts[0].device}, {t.device})")
 
 
 def erode(bin_img: Tensor, ksize: int = 5) -> Tensor:
@@ -72,9 +54,7 @@ def erode(bin_img: Tensor, ksize: int = 5) -> Tensor:
     planes = x.numel() // max(h * w, 1)
     if planes == 0:
         return out
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().s360_erode(_ptr(x), _ptr(out), planes, h, w, ksize, _stream(x.device))
-    _lib.check(rc, "s360_erode")
+    call("s360_erode", x.device, ptr(x), ptr(out), planes, h, w, ksize)
     return out
 
 
@@ -83,17 +63,12 @@ def _forward(pred, target, mask, keep_batch, far, near, fill, ksize):
     n = b if keep_batch else 1
     loss = torch.empty(n, dtype=torch.float32, device=pred.device)
     den = torch.empty(n, dtype=torch.float32, device=pred.device)
-    l = _lib.lib()
     wts = row_weights(h, pred.device)
     nbytes = C.c_size_t(0)
-    args = (_ptr(wts), b, v, h, w, int(keep_batch), _ptr(far), C.c_float(near), C.c_float(fill), int(ksize))
-    _lib.check(l.s360_l1_sphere_forward(None, None, _ptr(mask) if mask is not None else None, *args, None, None, None,
-                                        C.byref(nbytes), None), "s360_l1_sphere_forward (workspace size)")
+    args = (ptr(wts), b, v, h, w, int(keep_batch), ptr(far), C.c_float(near), C.c_float(fill), int(ksize))
+    invoke("s360_l1_sphere_forward", None, None, ptr(mask), *args, None, None, None, C.byref(nbytes), None)
     ws = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=pred.device)
-    with torch.cuda.device(pred.device):
-        rc = l.s360_l1_sphere_forward(_ptr(pred), _ptr(target), _ptr(mask), *args, _ptr(loss), _ptr(den), _ptr(ws), C.byref(nbytes),
-                                      _stream(pred.device))
-    _lib.check(rc, "s360_l1_sphere_forward")
+    call("s360_l1_sphere_forward", pred.device, ptr(pred), ptr(target), ptr(mask), *args, ptr(loss), ptr(den), ptr(ws), C.byref(nbytes))
     return loss, den
 
 
@@ -102,11 +77,8 @@ def _backward(g, pred, target, mask, den, keep_batch, far, near, fill, ksize, ne
     g = g.to(torch.float32).reshape(-1).contiguous()
     gp = torch.empty_like(pred)
     gt = torch.empty_like(pred) if need_target else None
-    with torch.cuda.device(pred.device):
-        rc = _lib.lib().s360_l1_sphere_backward(_ptr(pred), _ptr(target), _ptr(mask), _ptr(row_weights(h, pred.device)), b, v, h, w,
-                                                int(keep_batch), _ptr(far), C.c_float(near), C.c_float(fill), int(ksize), _ptr(g),
-                                                _ptr(den), _ptr(gp), _ptr(gt), _stream(pred.device))
-    _lib.check(rc, "s360_l1_sphere_backward")
+    call("s360_l1_sphere_backward", pred.device, ptr(pred), ptr(target), ptr(mask), ptr(row_weights(h, pred.device)), b, v, h, w,
+         int(keep_batch), ptr(far), C.c_float(near), C.c_float(fill), int(ksize), ptr(g), ptr(den), ptr(gp), ptr(gt))
     return gp, gt
 
 

@@ -17,41 +17,29 @@ from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-
-
-def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
-
-
-def _stream(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+from ._call import call, invoke, ptr
 
 
 def _args(depth, ln, lf, image, sigma, flags):
     b, v, h, w = (int(s) for s in depth.shape)
     c = int(image.shape[2]) if image is not None else 0
-    return (_ptr(depth), _ptr(ln), _ptr(lf), _ptr(image), b, v, int(ln.shape[1]), c, h, w, C.c_float(sigma), int(flags))
+    return (ptr(depth), ptr(ln), ptr(lf), ptr(image), b, v, int(ln.shape[1]), c, h, w, C.c_float(sigma), int(flags))
 
 
 def _forward(depth, ln, lf, image, sigma, flags) -> Tensor:
-    l = _lib.lib()
     loss = torch.empty((), dtype=torch.float32, device=depth.device)
     args = _args(depth, ln, lf, image, sigma, flags)
     nbytes = C.c_size_t(0)
-    _lib.check(l.s360_depth_smooth_forward(*args, None, None, C.byref(nbytes), None), "s360_depth_smooth_forward (workspace size)")
+    invoke("s360_depth_smooth_forward", *args, None, None, C.byref(nbytes), None)
     ws = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=depth.device)
-    with torch.cuda.device(depth.device):
-        rc = l.s360_depth_smooth_forward(*args, _ptr(loss), _ptr(ws), C.byref(nbytes), _stream(depth.device))
-    _lib.check(rc, "s360_depth_smooth_forward")
+    call("s360_depth_smooth_forward", depth.device, *args, ptr(loss), ptr(ws), C.byref(nbytes))
     return loss
 
 
 def _backward(g, depth, ln, lf, image, sigma, flags) -> Tensor:
     g = g.to(torch.float32).reshape(1).contiguous()
     grad = torch.empty_like(depth)
-    with torch.cuda.device(depth.device):
-        rc = _lib.lib().s360_depth_smooth_backward(*_args(depth, ln, lf, image, sigma, flags), _ptr(g), _ptr(grad), _stream(depth.device))
-    _lib.check(rc, "s360_depth_smooth_backward")
+    call("s360_depth_smooth_backward", depth.device, *_args(depth, ln, lf, image, sigma, flags), ptr(g), ptr(grad))
     return grad
 
 

@@ -25,8 +25,7 @@ import torch
 from torch import Tensor
 from torch.autograd.function import once_differentiable
 
-from . import _lib
-from .cost_volume import _check_cuda_f32, _ptr, _stream
+from ._call import _check_cuda_f32, call, ptr
 
 MODES = {"nearest": 0, "bilinear": 1}
 
@@ -49,9 +48,7 @@ class _Upsample(torch.autograd.Function):
         x = x.detach().contiguous()
         n, _, h, w = (int(d) for d in x.shape)
         out = torch.empty(n, 1, h * s, w * s, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = _lib.lib().s360_upsample_forward(_ptr(x), _ptr(out), n, h, w, s, mode, int(reciprocal), _stream(x.device))
-        _lib.check(rc, "s360_upsample_forward")
+        call("s360_upsample_forward", x.device, ptr(x), ptr(out), n, h, w, s, mode, int(reciprocal))
         ctx.save_for_backward(*((x,) if reciprocal else ()))
         ctx.args = (n, h, w, s, mode, bool(reciprocal))
         ctx.set_materialize_grads(False)
@@ -66,9 +63,7 @@ class _Upsample(torch.autograd.Function):
         x = ctx.saved_tensors[0] if reciprocal else None
         g_out = _grad(g_out)
         g_x = torch.empty(n, 1, h, w, dtype=torch.float32, device=g_out.device)
-        with torch.cuda.device(g_out.device):
-            rc = _lib.lib().s360_upsample_backward(_ptr(g_out), _ptr(x), _ptr(g_x), n, h, w, s, mode, int(reciprocal), _stream(g_out.device))
-        _lib.check(rc, "s360_upsample_backward")
+        call("s360_upsample_backward", g_out.device, ptr(g_out), ptr(x), ptr(g_x), n, h, w, s, mode, int(reciprocal))
         return g_x, None, None, None
 
 
@@ -118,11 +113,8 @@ class _FineDepthTail(torch.autograd.Function):
         fullres, delta_density = fullres.detach().contiguous(), delta_density.detach().contiguous()
         n, _, h, w = (int(d) for d in fullres.shape)
         outs = tuple(torch.empty(n // v, v, h * w, 1, gpp, dtype=torch.float32, device=fullres.device) for _ in range(3 if return_densities else 2))
-        with torch.cuda.device(fullres.device):
-            rc = _lib.lib().s360_depth_tail_forward(_ptr(fullres), _ptr(delta_density), _ptr(lo), _ptr(hi), exponent, gpp, v, _ptr(outs[0]),
-                                                    _ptr(outs[1]), _ptr(outs[2] if return_densities else None), n, h, w,
-                                                    _stream(fullres.device))
-        _lib.check(rc, "s360_depth_tail_forward")
+        call("s360_depth_tail_forward", fullres.device, ptr(fullres), ptr(delta_density), ptr(lo), ptr(hi), exponent, gpp, v, ptr(outs[0]),
+             ptr(outs[1]), ptr(outs[2] if return_densities else None), n, h, w)
         ctx.save_for_backward(fullres, delta_density, lo, hi)
         ctx.args = (n, h, w, v, gpp, exponent)
         ctx.set_materialize_grads(False)                        # an unused output hands None, which the kernel takes as zero
@@ -137,10 +129,8 @@ class _FineDepthTail(torch.autograd.Function):
         n, h, w, v, gpp, exponent = ctx.args
         g = [_grad(x) for x in g_outs] + [None] * (3 - len(g_outs))
         g_fullres, g_delta = torch.empty_like(fullres), torch.empty_like(delta_density)
-        with torch.cuda.device(fullres.device):
-            rc = _lib.lib().s360_depth_tail_backward(_ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(fullres), _ptr(delta_density), _ptr(lo), _ptr(hi),
-                                                     exponent, gpp, v, _ptr(g_fullres), _ptr(g_delta), n, h, w, _stream(fullres.device))
-        _lib.check(rc, "s360_depth_tail_backward")
+        call("s360_depth_tail_backward", fullres.device, ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(fullres), ptr(delta_density), ptr(lo), ptr(hi),
+             exponent, gpp, v, ptr(g_fullres), ptr(g_delta), n, h, w)
         return g_fullres, g_delta, None, None, None, None, None, None
 
 
@@ -179,9 +169,7 @@ class _OpacityMap(torch.autograd.Function):
     def forward(ctx, pdf, exponent):
         pdf = pdf.detach().contiguous()
         out = torch.empty_like(pdf)
-        with torch.cuda.device(pdf.device):
-            rc = _lib.lib().s360_opacity_map_forward(_ptr(pdf), _ptr(out), pdf.numel(), exponent, _stream(pdf.device))
-        _lib.check(rc, "s360_opacity_map_forward")
+        call("s360_opacity_map_forward", pdf.device, ptr(pdf), ptr(out), pdf.numel(), exponent)
         ctx.save_for_backward(pdf)
         ctx.exponent = exponent
         ctx.set_materialize_grads(False)
@@ -195,9 +183,7 @@ class _OpacityMap(torch.autograd.Function):
         (pdf,) = ctx.saved_tensors
         g_out = _grad(g_out)
         g_pdf = torch.empty_like(pdf)
-        with torch.cuda.device(pdf.device):
-            rc = _lib.lib().s360_opacity_map_backward(_ptr(pdf), _ptr(g_out), _ptr(g_pdf), pdf.numel(), ctx.exponent, _stream(pdf.device))
-        _lib.check(rc, "s360_opacity_map_backward")
+        call("s360_opacity_map_backward", pdf.device, ptr(pdf), ptr(g_out), ptr(g_pdf), pdf.numel(), ctx.exponent)
         return g_pdf, None
 
 

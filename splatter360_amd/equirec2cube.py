@@ -16,7 +16,7 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
-from . import _lib
+from ._call import call, ptr
 
 # Output face j shows slot (F R B L U D) code & 7, flipped on both image axes when bit 3 is set (the encoding of
 # stitch.CHANGE_ORDER_FACE_MAP, of which this is the inverse): rendered order U B L F R D, faces 0 and 5 flipped.
@@ -138,13 +138,9 @@ def _i32x6(face_map):
 
 def _launch_forward(x: Tensor, coor: Tensor, scale, out: Tensor, fw: int, mode: int, boundary: int, face_map, strides):
     b, c, h, w = x.shape
-    with torch.cuda.device(x.device):
-        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        rc = _lib.lib().s360_erp2cube_forward(C.c_void_p(x.data_ptr()), C.c_void_p(coor.data_ptr()),
-                                              None if scale is None else C.c_void_p(scale.data_ptr()), C.c_void_p(out.data_ptr()),
-                                              b, c, h, w, fw, mode, boundary, int(x.dtype == torch.uint8), _i32x6(face_map),
-                                              None if strides is None else (C.c_int64 * 4)(*strides), st)
-    _lib.check(rc, "s360_erp2cube_forward")
+    call("s360_erp2cube_forward", x.device, ptr(x), ptr(coor), ptr(scale), ptr(out),
+         b, c, h, w, fw, mode, boundary, int(x.dtype == torch.uint8), _i32x6(face_map),
+         None if strides is None else (C.c_int64 * 4)(*strides))
 
 
 class _Resample(torch.autograd.Function):
@@ -173,14 +169,10 @@ class _Resample(torch.autograd.Function):
             raise RuntimeError("equirec2cube backward: the adjoint plan does not belong to this plane / device")
         g = d_cube.detach().float().contiguous()
         d_erp = torch.empty((b, c, h, w), dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            st = C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
-            rc = _lib.lib().s360_erp2cube_backward(C.c_void_p(g.data_ptr()), C.c_void_p(coor.data_ptr()),
-                                                   C.c_void_p(rest[0].data_ptr()) if rest else None, C.c_void_p(offs.data_ptr()),
-                                                   C.c_void_p(ents.data_ptr()), C.c_void_p(d_erp.data_ptr()), b, c, h, w,
-                                                   int(coor.shape[0]), mode, boundary, _i32x6(face_map),
-                                                   None if strides is None else (C.c_int64 * 4)(*strides), st)
-        _lib.check(rc, "s360_erp2cube_backward")
+        call("s360_erp2cube_backward", g.device, ptr(g), ptr(coor), ptr(rest[0]) if rest else None, ptr(offs),
+             ptr(ents), ptr(d_erp), b, c, h, w,
+             int(coor.shape[0]), mode, boundary, _i32x6(face_map),
+             None if strides is None else (C.c_int64 * 4)(*strides))
         return d_erp, None, None, None, None, None, None, None, None
 
 

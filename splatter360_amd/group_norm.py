@@ -22,7 +22,7 @@ from torch import Tensor, nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .cost_volume import _check_cuda_f32, _ptr, _stream
+from ._call import _check_cuda_f32, call, ptr
 
 ROW_CHUNK = 4096                                              # GN_ROW_CHUNK of the kernels: floats of one (n, c) row per workgroup
 ACTIVATIONS = {"none": _lib.GN_ACT_NONE, "relu": _lib.GN_ACT_RELU, "silu": _lib.GN_ACT_SILU, "gelu": _lib.GN_ACT_GELU}
@@ -82,10 +82,8 @@ def norm_forward(x: Tensor, num_groups: int, weight: Optional[Tensor] = None, bi
     out = torch.empty_like(x)
     stats = torch.empty(n * num_groups, 2, dtype=torch.float64, device=x.device)
     scratch = torch.empty(scratch_doubles(n, c, s), dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().s360_group_norm_forward(_ptr(x), _ptr(weight), _ptr(bias), _ptr(residual), n, c, s, num_groups, C.byref(C.c_double(float(eps))), act,
-                                                _ptr(scratch), _ptr(stats), _ptr(out), _stream(x.device))
-    _lib.check(rc, "s360_group_norm_forward")
+    call("s360_group_norm_forward", x.device, ptr(x), ptr(weight), ptr(bias), ptr(residual), n, c, s, num_groups, C.byref(C.c_double(float(eps))), act,
+         ptr(scratch), ptr(stats), ptr(out))
     return out, stats
 
 
@@ -107,10 +105,8 @@ def norm_backward(x: Tensor, num_groups: int, weight: Optional[Tensor], bias: Op
     if g_x is None and g_w is None and g_b is None:
         return None, None, None
     scratch = torch.empty(scratch_doubles(n, c, s), dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().s360_group_norm_backward(_ptr(x), _ptr(weight), _ptr(bias), _ptr(stats), _ptr(g_out), n, c, s, num_groups,
-                                                 C.byref(C.c_double(float(eps))), act, _ptr(scratch), _ptr(g_x), _ptr(g_w), _ptr(g_b), _stream(x.device))
-    _lib.check(rc, "s360_group_norm_backward")
+    call("s360_group_norm_backward", x.device, ptr(x), ptr(weight), ptr(bias), ptr(stats), ptr(g_out), n, c, s, num_groups,
+         C.byref(C.c_double(float(eps))), act, ptr(scratch), ptr(g_x), ptr(g_w), ptr(g_b))
     return g_x, g_w, g_b
 
 

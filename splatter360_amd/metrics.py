@@ -19,7 +19,7 @@ import ctypes as C
 import torch
 from torch import Tensor
 
-from . import _lib
+from ._call import call, invoke, ptr
 
 WIN_SIZE = 11
 
@@ -43,15 +43,8 @@ def ssim(pred: Tensor, gt: Tensor) -> Tensor:
         return out
     x = pred.detach().float().contiguous()
     y = gt.detach().float().contiguous()
-    l = _lib.lib()
-    nbytes = C.c_size_t(0)
-    _lib.check(l.s360_ssim(None, None, n, c, h, w, None, None, C.byref(nbytes), None), "s360_ssim (workspace size)")
-    ws = torch.empty(max(int(nbytes.value), 8), dtype=torch.uint8, device=pred.device)
-    with torch.cuda.device(pred.device):
-        st = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-        rc = l.s360_ssim(C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), n, c, h, w, C.c_void_p(out.data_ptr()),
-                         C.c_void_p(ws.data_ptr()), C.byref(nbytes), st)
-    _lib.check(rc, "s360_ssim")
+    ws, nbytes = _workspace(pred.device, "s360_ssim", None, None, n, c, h, w, None, None)
+    call("s360_ssim", pred.device, ptr(x), ptr(y), n, c, h, w, ptr(out), ptr(ws), C.byref(nbytes))
     return out
 
 
@@ -65,9 +58,10 @@ def compute_ssim(ground_truth: Tensor, predicted: Tensor) -> Tensor:
 DEPTH_METRIC_KEYS = ("abs_diff", "abs_rel", "sq_rel", "rmse", "rmse_log", "a5", "a10", "a25", "a0", "a1", "a2", "a3")
 
 
-def _workspace(query, device) -> tuple:
+def _workspace(device, name, *args) -> tuple:
+    """The size query of entry point `name` (null pointers in `args`, no launch) and a workspace of that size."""
     nbytes = C.c_size_t(0)
-    query(C.byref(nbytes))
+    invoke(name, *args, C.byref(nbytes), None)
     return torch.empty(max(int(nbytes.value), 8), dtype=torch.uint8, device=device), nbytes
 
 
@@ -79,10 +73,6 @@ def _rows(t: Tensor) -> Tensor:
     if t.shape[1] > 1 and t.stride(1) != 1:
         t = t.contiguous()
     return t
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def psnr(pred: Tensor, gt: Tensor) -> Tensor:
@@ -103,13 +93,8 @@ def psnr(pred: Tensor, gt: Tensor) -> Tensor:
         return out
     x = pred.detach().float().contiguous()
     y = gt.detach().float().contiguous()
-    l = _lib.lib()
-    ws, nbytes = _workspace(lambda ref: _lib.check(l.s360_psnr(None, None, n, c, h, w, None, None, ref, None),
-                                                   "s360_psnr (workspace size)"), pred.device)
-    with torch.cuda.device(pred.device):
-        st = C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)
-        rc = l.s360_psnr(_p(x), _p(y), n, c, h, w, _p(out), _p(ws), C.byref(nbytes), st)
-    _lib.check(rc, "s360_psnr")
+    ws, nbytes = _workspace(pred.device, "s360_psnr", None, None, n, c, h, w, None, None)
+    call("s360_psnr", pred.device, ptr(x), ptr(y), n, c, h, w, ptr(out), ptr(ws), C.byref(nbytes))
     return out
 
 
@@ -125,18 +110,9 @@ def _depth_metrics_call(gt, pred, valid, n_rows, n, strides, rows_per_group, gro
     out = torch.empty((len(DEPTH_METRIC_KEYS), n_rows), dtype=torch.float32, device=dev)
     count = torch.empty(n_rows, dtype=torch.int32, device=dev)
     red = torch.empty(len(DEPTH_METRIC_KEYS), dtype=torch.float32, device=dev) if scores else None
-    l = _lib.lib()
-
-    def call(gp, pp, vp, op, cp, rp, wp, ref, st):
-        return l.s360_depth_metrics(gp, pp, vp, n_rows, n, *strides, rows_per_group, *group_strides, float(threshold), *lookup,
-                                    int(bool(mult_a)), op, cp, rp, wp, ref, st)
-
-    ws, nbytes = _workspace(lambda ref: _lib.check(call(None, None, None, None, None, None, None, ref, None),
-                                                   "s360_depth_metrics (workspace size)"), dev)
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = call(_p(gt), _p(pred), _p(valid), _p(out), _p(count), _p(red), _p(ws), C.byref(nbytes), st)
-    _lib.check(rc, "s360_depth_metrics")
+    dims = (n_rows, n, *strides, rows_per_group, *group_strides, float(threshold), *lookup, int(bool(mult_a)))
+    ws, nbytes = _workspace(dev, "s360_depth_metrics", None, None, None, *dims, None, None, None, None)
+    call("s360_depth_metrics", dev, ptr(gt), ptr(pred), ptr(valid), *dims, ptr(out), ptr(count), ptr(red), ptr(ws), C.byref(nbytes))
     return out, count, red
 
 

@@ -21,7 +21,7 @@ from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .cost_volume import _ptr, _stream
+from ._call import call, ptr
 
 ORDERS = {"legacy": _lib.QKV_LEGACY, "new": _lib.QKV_NEW}
 HEAD_CHANNELS = (32,)
@@ -67,10 +67,7 @@ def attention_forward(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_vie
     qkv = qkv.detach().contiguous()
     out = torch.empty(rows, heads * ch, tokens, dtype=torch.float32, device=qkv.device)
     lse = torch.empty(rows // views, heads, views * tokens, dtype=torch.float64, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        rc = _lib.lib().s360_qkv_attention_forward(_ptr(qkv), rows, views, heads, ch, tokens, code, _ptr(out), _ptr(lse),
-                                                   _stream(qkv.device))
-    _lib.check(rc, "s360_qkv_attention_forward")
+    call("s360_qkv_attention_forward", qkv.device, ptr(qkv), rows, views, heads, ch, tokens, code, ptr(out), ptr(lse))
     return out, lse
 
 
@@ -92,10 +89,8 @@ def attention_backward(qkv: Tensor, lse: Tensor, g_out: Tensor, n_heads: int, *,
             or tuple(g_qkv.shape) != tuple(qkv.shape) or not g_qkv.is_contiguous() or g_qkv.data_ptr() == qkv.data_ptr():
         raise ValueError("attention_backward: g_qkv must be a contiguous float32 buffer of qkv's shape on its device, not qkv itself")
     delta = torch.empty_like(lse)
-    with torch.cuda.device(qkv.device):
-        rc = _lib.lib().s360_qkv_attention_backward(_ptr(qkv), _ptr(lse), _ptr(g_out), rows, views, heads, ch, tokens, code,
-                                                    _ptr(delta), _ptr(g_qkv), _stream(qkv.device))
-    _lib.check(rc, "s360_qkv_attention_backward")
+    call("s360_qkv_attention_backward", qkv.device, ptr(qkv), ptr(lse), ptr(g_out), rows, views, heads, ch, tokens, code,
+         ptr(delta), ptr(g_qkv))
     return g_qkv
 
 

@@ -14,7 +14,8 @@ from typing import NamedTuple, Optional
 import torch
 from torch import Tensor, nn
 
-from . import _lib
+from . import _call, _lib
+from ._call import call, invoke, ptr
 
 VIEW_FLOATS = 44
 
@@ -133,11 +134,8 @@ def pack_views_native(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far:
     if int(k.shape[0]) != n:
         raise RuntimeError("extrinsics / intrinsics view counts differ")
     out = torch.empty((n, VIEW_FLOATS), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = _lib.lib().s360_pack_views(_ptr(ext), _ptr(k), _ptr(nr), _ptr(fr), _ptr(bg), int(bool(per_view)), n,
-                                        int(bool(scale_invariant)), _ptr(out), stream)
-    _lib.check(rc, "s360_pack_views")
+    call("s360_pack_views", dev, ptr(ext), ptr(k), ptr(nr), ptr(fr), ptr(bg), int(bool(per_view)), n,
+         int(bool(scale_invariant)), ptr(out))
     return out
 
 
@@ -353,10 +351,7 @@ class RasterState:
         """(contributing (pixel, entry) pairs, pairs the backward composite evaluates): s360_count_contributions on this training
         workspace (host read; a measurement aid, see include/s360.h)."""
         out = torch.zeros(2, dtype=torch.int64, device=self.workspace.device)
-        with torch.cuda.device(self.workspace.device):
-            stream = C.c_void_p(torch.cuda.current_stream(self.workspace.device).cuda_stream)
-            _lib.check(_lib.lib().s360_count_contributions(C.byref(self.prm), _ptr(self.workspace), self.layout.total_bytes, _ptr(out), stream),
-                       "s360_count_contributions")
+        call("s360_count_contributions", self.workspace.device, C.byref(self.prm), ptr(self.workspace), self.layout.total_bytes, ptr(out))
         a, b = out.cpu().tolist()
         return int(a), int(b)
 
@@ -366,10 +361,7 @@ class RasterState:
         quadrant's upper 8x4 half / its lower half / both (the composites' own box test), [29] records, [30] 8-run iterations of a
         composite that would walk the two halves side by side on 32 + 32 lanes (round 6: counted before building it — see DESIGN.md)."""
         out = torch.zeros(32, dtype=torch.int64, device=self.workspace.device)
-        with torch.cuda.device(self.workspace.device):
-            stream = C.c_void_p(torch.cuda.current_stream(self.workspace.device).cuda_stream)
-            _lib.check(_lib.lib().s360_count_backward_slots(C.byref(self.prm), _ptr(self.workspace), self.layout.total_bytes, _ptr(out), stream),
-                       "s360_count_backward_slots")
+        call("s360_count_backward_slots", self.workspace.device, C.byref(self.prm), ptr(self.workspace), self.layout.total_bytes, ptr(out))
         c = [int(x) for x in out.cpu().tolist()]
         return dict(executed=c[0], padding=c[1], stopped=c[2], miss=c[3], contributing=c[4], skipped_runs=c[5], units=c[6], groups=c[7],
                     by_unit_hit_decile=c[8:18], runs_by_active_records=dict(zip(("0", "1-4", "5-8", "9-16", "17-24", "25-32", "33-48", "49-64"), c[18:26])),
@@ -411,10 +403,6 @@ class RasterState:
         return self._read_header()[1]
 
 
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _f32c(t: Tensor, name: str) -> Tensor:
     if not t.is_cuda:
         raise RuntimeError(f"{name} must live on the GPU (hip device); the rasteriser has no CPU path")
@@ -428,7 +416,7 @@ def _forward_call(prm, views, means3D, cov6, opac, shs, colors, want_radii: bool
     n_img = prm.V // 2 if (prm.flags & _lib.FLAG_SPHERICAL) else prm.V     # spherical: views = (camera, seam ghost) pairs
     images = torch.empty((n_img, 3, prm.H, prm.W), dtype=torch.float32, device=dev)
     radii = torch.empty((prm.V, prm.P), dtype=torch.int32, device=dev) if want_radii else None
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = _call.stream(dev)
     depth = None
     if mse is not None:     # (target[V,3,H,W], grad_scale): loss epilogue fused into the composite store
         target, grad_scale = mse
@@ -438,23 +426,21 @@ def _forward_call(prm, views, means3D, cov6, opac, shs, colors, want_radii: bool
         nquads = prm.V * ((prm.H + 15) // 16) * ((prm.W + 15) // 16) * 4   # one partial per wave footprint (8x8 px)
         partials = torch.empty((nquads, 2), dtype=torch.float32, device=dev)
         loss_out = torch.empty((1 + prm.V,), dtype=torch.float32, device=dev)   # loss, clipped MSE per view (same call)
-        rc = _lib.lib().s360_forward_mse(C.byref(prm), _ptr(views), _ptr(means3D), _ptr(cov6), _ptr(opac), _ptr(shs),
-                                         _ptr(colors), _ptr(images), _ptr(depth), DEPTH_MODES.get(depth_mode, 0), _ptr(radii),
-                                         _ptr(target), C.c_float(grad_scale), _ptr(d_images), _ptr(partials), _ptr(loss_out),
-                                         _ptr(ws), lay.total_bytes, stream)
-        _lib.check(rc, "s360_forward_mse")
+        invoke("s360_forward_mse", C.byref(prm), ptr(views), ptr(means3D), ptr(cov6), ptr(opac), ptr(shs),
+               ptr(colors), ptr(images), ptr(depth), DEPTH_MODES.get(depth_mode, 0), ptr(radii),
+               ptr(target), C.c_float(grad_scale), ptr(d_images), ptr(partials), ptr(loss_out),
+               ptr(ws), lay.total_bytes, stream)
         st = RasterState(prm, lay, ws)
         st.d_images, st.mse_partials, st.mse_out = d_images, partials, loss_out
         return images, radii, st, depth
     if depth_mode is None:
-        rc = _lib.lib().s360_forward(C.byref(prm), _ptr(views), _ptr(means3D), _ptr(cov6), _ptr(opac), _ptr(shs),
-                                     _ptr(colors), _ptr(images), _ptr(radii), _ptr(ws), lay.total_bytes, stream)
+        invoke("s360_forward", C.byref(prm), ptr(views), ptr(means3D), ptr(cov6), ptr(opac), ptr(shs),
+               ptr(colors), ptr(images), ptr(radii), ptr(ws), lay.total_bytes, stream)
     else:
         depth = torch.empty((n_img, prm.H, prm.W), dtype=torch.float32, device=dev)
-        rc = _lib.lib().s360_forward_depth(C.byref(prm), _ptr(views), _ptr(means3D), _ptr(cov6), _ptr(opac), _ptr(shs),
-                                           _ptr(colors), _ptr(images), _ptr(depth), DEPTH_MODES[depth_mode], _ptr(radii),
-                                           _ptr(ws), lay.total_bytes, stream)
-    _lib.check(rc, "s360_forward")
+        invoke("s360_forward_depth", C.byref(prm), ptr(views), ptr(means3D), ptr(cov6), ptr(opac), ptr(shs),
+               ptr(colors), ptr(images), ptr(depth), DEPTH_MODES[depth_mode], ptr(radii),
+               ptr(ws), lay.total_bytes, stream)
     return images, radii, RasterState(prm, lay, ws), depth
 
 
@@ -575,25 +561,22 @@ class _RasterizeViews(torch.autograd.Function):
             d_sh = torch.empty_like(sh) if (sh is not None and need[2]) else None
             d_col = torch.empty((p, 3), dtype=torch.float32, device=dev) if (col is not None and need[3]) else None
             bws = torch.empty(lay.backward_bytes, dtype=torch.uint8, device=dev)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _call.stream(dev)
             if ctx.exchange is not None:
                 # multi-GPU: the per-Gaussian gradients leave this node already SUMMED over the ranks — composite once, then
                 # the per-Gaussian tail range by range with every range's collectives in flight behind the next one
                 from . import distributed
                 ex = ctx.exchange
-                lib = _lib.lib()
-                rc = lib.s360_backward_composite(C.byref(prm), _ptr(vw), _ptr(state.workspace), lay.total_bytes, _ptr(g), _ptr(g_scale),
-                                                 _ptr(gd), dm, _ptr(bws), lay.backward_bytes, stream)
-                _lib.check(rc, "s360_backward_composite")
+                invoke("s360_backward_composite", C.byref(prm), ptr(vw), ptr(state.workspace), lay.total_bytes, ptr(g), ptr(g_scale),
+                       ptr(gd), dm, ptr(bws), lay.backward_bytes, stream)
                 packed = torch.empty((p, 10), dtype=torch.float32, device=dev)
                 rgb = torch.empty((p, 4), dtype=torch.float32, device=dev)
                 rank = ex.rank()
 
                 def produce(lo, hi):
-                    _lib.check(lib.s360_backward_gaussians(C.byref(prm), _ptr(vw), _ptr(m3), _ptr(c6), _ptr(sh), _ptr(state.workspace),
-                                                           lay.total_bytes, int(gd is not None), dm, lo, hi - lo, rank, _ptr(packed),
-                                                           _ptr(d_m2), _ptr(rgb), _ptr(bws), lay.backward_bytes, stream),
-                               "s360_backward_gaussians")
+                    invoke("s360_backward_gaussians", C.byref(prm), ptr(vw), ptr(m3), ptr(c6), ptr(sh), ptr(state.workspace),
+                           lay.total_bytes, int(gd is not None), dm, lo, hi - lo, rank, ptr(packed),
+                           ptr(d_m2), ptr(rgb), ptr(bws), lay.backward_bytes, stream)
 
                 slab = sh.shape[1] * sh.shape[2]
 
@@ -601,15 +584,13 @@ class _RasterizeViews(torch.autograd.Function):
                     sub = _lib.S360Params()
                     C.memmove(C.byref(sub), C.byref(prm), C.sizeof(sub))
                     sub.P, sub.V = hi - lo, int(rep_all.shape[0])
-                    st2 = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                    _lib.check(lib.s360_sh_backward(C.byref(sub), int(rgb_all.shape[0]), _ptr(rep_all.contiguous()),
-                                                    C.c_void_p(m3.data_ptr() + 12 * lo), _ptr(rgb_all.contiguous()),
-                                                    C.c_void_p(d_sh.data_ptr() + 4 * slab * lo), st2), "s360_sh_backward")
+                    invoke("s360_sh_backward", C.byref(sub), int(rgb_all.shape[0]), ptr(rep_all.contiguous()),
+                           C.c_void_p(m3.data_ptr() + 12 * lo), ptr(rgb_all.contiguous()),
+                           C.c_void_p(d_sh.data_ptr() + 4 * slab * lo), _call.stream(dev))
 
                 def reduce_rows(lo, hi, rows):      # "gather" form: sum the ranks' rows + unpack, one pass
-                    _lib.check(lib.s360_reduce_unpack_gradients(_ptr(rows), int(rows.shape[0]), lo, hi - lo, int(c6.dim() == 3), _ptr(d_m3), _ptr(d_c6),
-                                                                _ptr(d_op), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                               "s360_reduce_unpack_gradients")
+                    invoke("s360_reduce_unpack_gradients", ptr(rows), int(rows.shape[0]), lo, hi - lo, int(c6.dim() == 3), ptr(d_m3), ptr(d_c6),
+                           ptr(d_op), _call.stream(dev))
 
                 # harmonics frozen (need[2] False — on every rank, it is the same model): no dL/dRGB gathers, no dL/dSH rebuild
                 form = distributed.exchange_chunked(p, packed, rgb, vw[0], produce, rebuild_sh if d_sh is not None else None,
@@ -617,8 +598,7 @@ class _RasterizeViews(torch.autograd.Function):
                                                     force_collectives=getattr(ex, "force_collectives", False), mode=getattr(ex, "mode", None),
                                                     reduce_rows=reduce_rows)
                 if form != "gather":
-                    _lib.check(lib.s360_unpack_gradients(_ptr(packed), p, int(c6.dim() == 3), _ptr(d_m3), _ptr(d_c6), _ptr(d_op), stream),
-                               "s360_unpack_gradients")
+                    invoke("s360_unpack_gradients", ptr(packed), p, int(c6.dim() == 3), ptr(d_m3), ptr(d_c6), ptr(d_op), stream)
                 if d_m2 is not None:
                     d_m2 = d_m2.sum(0) if v > 1 else d_m2[0]
                 return d_m3, d_m2, d_sh, None, d_op.view(-1, 1), d_c6, None, None, None
@@ -626,20 +606,18 @@ class _RasterizeViews(torch.autograd.Function):
                 # multi-GPU factored form: no SH pass here; the caller exchanges d_rgb_sum and finishes with
                 # finish_deferred_sh() (see distributed.sync_gradients_factored)
                 d_rgb = torch.empty((p, 4), dtype=torch.float32, device=dev)
-                rc = _lib.lib().s360_backward_split(
-                    C.byref(prm), _ptr(vw), _ptr(m3), _ptr(c6), _ptr(op), _ptr(sh), _ptr(state.workspace), lay.total_bytes,
-                    _ptr(g), _ptr(g_scale), _ptr(gd), dm, _ptr(d_m3), _ptr(d_m2), _ptr(d_c6), _ptr(d_op), _ptr(d_rgb),
-                    _ptr(bws), lay.backward_bytes, stream)
-                _lib.check(rc, "s360_backward_split")
+                invoke("s360_backward_split",
+                       C.byref(prm), ptr(vw), ptr(m3), ptr(c6), ptr(op), ptr(sh), ptr(state.workspace), lay.total_bytes,
+                       ptr(g), ptr(g_scale), ptr(gd), dm, ptr(d_m3), ptr(d_m2), ptr(d_c6), ptr(d_op), ptr(d_rgb),
+                       ptr(bws), lay.backward_bytes, stream)
                 ctx.holder["deferred"] = _RasterizeViews.last_deferred = DeferredSH(prm, vw, m3, sh, d_rgb)
                 if d_m2 is not None:
                     d_m2 = d_m2.sum(0) if v > 1 else d_m2[0]
                 return d_m3, d_m2, None, None, d_op.view(-1, 1), d_c6, None, None, None
-            rc = _lib.lib().s360_backward(
-                C.byref(prm), _ptr(vw), _ptr(m3), _ptr(c6), _ptr(op), _ptr(sh), _ptr(col), _ptr(state.workspace),
-                lay.total_bytes, _ptr(g), _ptr(g_scale), _ptr(gd), dm, _ptr(d_m3), _ptr(d_m2), _ptr(d_c6),
-                _ptr(d_op), _ptr(d_sh), _ptr(d_col), _ptr(bws), lay.backward_bytes, stream)
-            _lib.check(rc, "s360_backward")
+            invoke("s360_backward",
+                   C.byref(prm), ptr(vw), ptr(m3), ptr(c6), ptr(op), ptr(sh), ptr(col), ptr(state.workspace),
+                   lay.total_bytes, ptr(g), ptr(g_scale), ptr(gd), dm, ptr(d_m3), ptr(d_m2), ptr(d_c6),
+                   ptr(d_op), ptr(d_sh), ptr(d_col), ptr(bws), lay.backward_bytes, stream)
         if d_m2 is not None:
             d_m2 = d_m2.sum(0) if v > 1 else d_m2[0]
         return d_m3, d_m2, d_sh, d_col, d_op.view(-1, 1), d_c6, None, None, None
@@ -690,9 +668,9 @@ class _RasterizeRaw(torch.autograd.Function):
                                      int(ch), int(cw), int(per_ray), int(conv), float(smin), float(smax), float(eps))
             means = torch.empty((p, 3), dtype=torch.float32, device=dev)
             cov6 = torch.empty((p, 6), dtype=torch.float32, device=dev)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _call.stream(dev)
 
-            def call():
+            def launch():
                 lay = _lib.layout(prm)
                 ws = torch.empty(lay.total_bytes, dtype=torch.uint8, device=dev)
                 images = torch.empty((v, 3, prm.H, prm.W), dtype=torch.float32, device=dev)
@@ -708,16 +686,15 @@ class _RasterizeRaw(torch.autograd.Function):
                     partials = torch.empty((v * ((prm.H + 15) // 16) * ((prm.W + 15) // 16) * 4, 2), dtype=torch.float32, device=dev)
                     loss_out = torch.empty((1 + v,), dtype=torch.float32, device=dev)
                     st.d_images, st.mse_partials, st.mse_out = d_images, partials, loss_out
-                rc = _lib.lib().s360_forward_raw(C.byref(prm), _ptr(vw), C.byref(rin), _ptr(op), _ptr(means), _ptr(cov6), _ptr(images), _ptr(depth),
-                                                 DEPTH_MODES.get(depth_mode, 0), None, _ptr(tgt), C.c_float(gs), _ptr(d_images), _ptr(partials),
-                                                 _ptr(loss_out), _ptr(ws), lay.total_bytes, stream)
-                _lib.check(rc, "s360_forward_raw")
+                invoke("s360_forward_raw", C.byref(prm), ptr(vw), C.byref(rin), ptr(op), ptr(means), ptr(cov6), ptr(images), ptr(depth),
+                       DEPTH_MODES.get(depth_mode, 0), None, ptr(tgt), C.c_float(gs), ptr(d_images), ptr(partials),
+                       ptr(loss_out), ptr(ws), lay.total_bytes, stream)
                 return images, depth, st
 
-            images, depth, state = call()
+            images, depth, state = launch()
             if check == "sync" and state.overflowed():
                 prm.max_instances = state.num_rendered()
-                images, depth, state = call()
+                images, depth, state = launch()
         ctx.set_materialize_grads(False)
         ctx.state, ctx.rin_cfg, ctx.depth_mode, ctx.diff_means = state, (nv, ch, cw, per_ray, conv, smin, smax, eps), depth_mode, bool(diff_means)
         ctx.in_shapes = (tuple(depths.shape), tuple(opacities.shape), tuple(raw.shape))   # gradients go back in the callers' shapes
@@ -763,33 +740,32 @@ class _RasterizeRaw(torch.autograd.Function):
             d_dep = torch.empty((p,), dtype=torch.float32, device=dev)
             d_raw = torch.empty((p, 82), dtype=torch.float32, device=dev)
             bws = torch.empty(lay.backward_bytes, dtype=torch.uint8, device=dev)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _call.stream(dev)
             if ctx.exchange is not None:
                 # multi-GPU (one target panorama per rank, the same raw cloud on every rank): the rows the exchange moves — packed
                 # [P,10] (dL/dmean | dL/dcov6 | dL/dopacity) and the clamp-masked dL/dRGB sums [P,4] — are exactly what k_raw_bwd takes,
                 # so after the exchange ONE launch forms dL/d(raw record) from the summed rows and the N ranks' dL/dRGB factors
                 from . import distributed
                 ex = ctx.exchange
-                lib = _lib.lib()
-                _lib.check(lib.s360_backward_composite(C.byref(prm), _ptr(vw), _ptr(state.workspace), lay.total_bytes, _ptr(g), _ptr(g_scale),
-                                                       _ptr(gd), dm, _ptr(bws), lay.backward_bytes, stream), "s360_backward_composite")
+                invoke("s360_backward_composite", C.byref(prm), ptr(vw), ptr(state.workspace), lay.total_bytes, ptr(g), ptr(g_scale),
+                       ptr(gd), dm, ptr(bws), lay.backward_bytes, stream)
                 packed = torch.empty((p, 10), dtype=torch.float32, device=dev)
                 rgb = torch.empty((p, 4), dtype=torch.float32, device=dev)
                 rank = ex.rank()
                 gathered = {}
 
                 def produce(lo, hi):
-                    _lib.check(lib.s360_backward_gaussians(C.byref(prm), _ptr(vw), _ptr(means), _ptr(cov6), _ptr(rw), _ptr(state.workspace),
-                                                           lay.total_bytes, int(gd is not None), dm, lo, hi - lo, rank, _ptr(packed),
-                                                           None, _ptr(rgb), _ptr(bws), lay.backward_bytes, stream), "s360_backward_gaussians")
+                    invoke("s360_backward_gaussians", C.byref(prm), ptr(vw), ptr(means), ptr(cov6), ptr(rw), ptr(state.workspace),
+                           lay.total_bytes, int(gd is not None), dm, lo, hi - lo, rank, ptr(packed),
+                           None, ptr(rgb), ptr(bws), lay.backward_bytes, stream)
 
                 def collect(lo, hi, rgb_all, rep_all):      # keep every range's gathered factors: k_raw_bwd runs once, over all of them
                     gathered[(lo, hi)] = rgb_all
                     gathered["rep"] = rep_all
 
                 def reduce_rows(lo, hi, rows):      # "gather" form: sum the ranks' rows + unpack, one pass
-                    _lib.check(lib.s360_reduce_unpack_gradients(_ptr(rows), int(rows.shape[0]), lo, hi - lo, 0, _ptr(d_m3), _ptr(d_c6), _ptr(d_op),
-                                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "s360_reduce_unpack_gradients")
+                    invoke("s360_reduce_unpack_gradients", ptr(rows), int(rows.shape[0]), lo, hi - lo, 0, ptr(d_m3), ptr(d_c6), ptr(d_op),
+                           _call.stream(dev))
 
                 form = distributed.exchange_chunked(p, packed, rgb, vw[0], produce, collect, n_chunks=ex.n_chunks, group=ex.group,
                                                     group_gather=ex.group_gather, force_collectives=getattr(ex, "force_collectives", False),
@@ -803,16 +779,15 @@ class _RasterizeRaw(torch.autograd.Function):
                     for (lo, hi), t in gathered.items():
                         rgb_all[:, lo:hi] = t
                 if form != "gather":
-                    _lib.check(lib.s360_unpack_gradients(_ptr(packed), p, 0, _ptr(d_m3), _ptr(d_c6), _ptr(d_op), stream), "s360_unpack_gradients")
-                _lib.check(lib.s360_backward_raw_tail(C.byref(prm), _ptr(rep_all), world, C.byref(rin), _ptr(means), _ptr(state.workspace),
-                                                      lay.total_bytes, _ptr(d_m3) if ctx.diff_means else None, _ptr(d_c6), _ptr(rgb_all),
-                                                      _ptr(d_dep), _ptr(d_raw), stream), "s360_backward_raw_tail")
+                    invoke("s360_unpack_gradients", ptr(packed), p, 0, ptr(d_m3), ptr(d_c6), ptr(d_op), stream)
+                invoke("s360_backward_raw_tail", C.byref(prm), ptr(rep_all), world, C.byref(rin), ptr(means), ptr(state.workspace),
+                       lay.total_bytes, ptr(d_m3) if ctx.diff_means else None, ptr(d_c6), ptr(rgb_all),
+                       ptr(d_dep), ptr(d_raw), stream)
                 sd, so, sr = ctx.in_shapes
                 return d_dep.view(sd), d_op.view(so), d_raw.view(sr), None, None, None, None, None
-            rc = _lib.lib().s360_backward_raw(C.byref(prm), _ptr(vw), C.byref(rin), _ptr(means), _ptr(cov6), _ptr(op), _ptr(state.workspace),
-                                              lay.total_bytes, _ptr(g), _ptr(g_scale), _ptr(gd), dm, int(ctx.diff_means), _ptr(d_m3), _ptr(d_c6),
-                                              _ptr(d_op), _ptr(d_rgb), _ptr(d_dep), _ptr(d_raw), _ptr(bws), lay.backward_bytes, stream)
-            _lib.check(rc, "s360_backward_raw")
+            invoke("s360_backward_raw", C.byref(prm), ptr(vw), C.byref(rin), ptr(means), ptr(cov6), ptr(op), ptr(state.workspace),
+                   lay.total_bytes, ptr(g), ptr(g_scale), ptr(gd), dm, int(ctx.diff_means), ptr(d_m3), ptr(d_c6),
+                   ptr(d_op), ptr(d_rgb), ptr(d_dep), ptr(d_raw), ptr(bws), lay.backward_bytes, stream)
         sd, so, sr = ctx.in_shapes
         return d_dep.view(sd), d_op.view(so), d_raw.view(sr), None, None, None, None, None
 
@@ -861,11 +836,8 @@ def finish_deferred_sh(prm, views: Tensor, means3D: Tensor, shs: Tensor, d_rgb_s
     template here: the kernel reads neither the coefficients nor any gradient buffer)."""
     d_sh = torch.empty_like(shs)
     n = int(d_rgb_sums.shape[0])
-    with torch.cuda.device(shs.device):
-        stream = C.c_void_p(torch.cuda.current_stream(shs.device).cuda_stream)
-        rc = _lib.lib().s360_sh_backward(C.byref(prm), n, _ptr(views.contiguous()), _ptr(means3D),
-                                         _ptr(d_rgb_sums.contiguous()), _ptr(d_sh), stream)
-    _lib.check(rc, "s360_sh_backward")
+    call("s360_sh_backward", shs.device, C.byref(prm), n, ptr(views.contiguous()), ptr(means3D),
+         ptr(d_rgb_sums.contiguous()), ptr(d_sh))
     return d_sh
 
 

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
-from . import _lib
+from ._call import call, ptr
 
 # Cube2Equirec slot order is (F R B L U D); faces rendered in the order (top, front, left, back,
 # right, bottom) are mapped by the reference's change_order(): flip faces 0 and 5 on both image
@@ -152,11 +152,7 @@ class _DepthToDistance(torch.autograd.Function):
     def forward(ctx, depth, k4, conv):
         n, h, w = depth.shape
         dist = torch.empty_like(depth)
-        with torch.cuda.device(depth.device):
-            st = C.c_void_p(torch.cuda.current_stream(depth.device).cuda_stream)
-            rc = _lib.lib().s360_depth_to_distance_forward(C.c_void_p(depth.data_ptr()), C.c_void_p(k4.data_ptr()),
-                                                           C.c_void_p(dist.data_ptr()), n, h, w, conv, st)
-        _lib.check(rc, "s360_depth_to_distance_forward")
+        call("s360_depth_to_distance_forward", depth.device, ptr(depth), ptr(k4), ptr(dist), n, h, w, conv)
         ctx.save_for_backward(depth, k4)
         ctx.conv = conv
         return dist
@@ -167,12 +163,7 @@ class _DepthToDistance(torch.autograd.Function):
         n, h, w = depth.shape
         g = d_dist.detach().float().contiguous()
         d_depth = torch.empty_like(depth)
-        with torch.cuda.device(depth.device):
-            st = C.c_void_p(torch.cuda.current_stream(depth.device).cuda_stream)
-            rc = _lib.lib().s360_depth_to_distance_backward(C.c_void_p(g.data_ptr()), C.c_void_p(depth.data_ptr()),
-                                                            C.c_void_p(k4.data_ptr()), C.c_void_p(d_depth.data_ptr()), n, h, w,
-                                                            ctx.conv, st)
-        _lib.check(rc, "s360_depth_to_distance_backward")
+        call("s360_depth_to_distance_backward", depth.device, ptr(g), ptr(depth), ptr(k4), ptr(d_depth), n, h, w, ctx.conv)
         return d_depth, None, None
 
 
@@ -214,12 +205,8 @@ class _StitchDistance(torch.autograd.Function):
         n, fw = int(depth.shape[0]), int(depth.shape[-1])
         eh, ew = int(grid.shape[0]), int(grid.shape[1])
         erp = torch.empty((n, eh, ew), dtype=torch.float32, device=depth.device)
-        with torch.cuda.device(depth.device):
-            st = C.c_void_p(torch.cuda.current_stream(depth.device).cuda_stream)
-            rc = _lib.lib().s360_cube2erp_distance_forward(C.c_void_p(depth.data_ptr()), C.c_void_p(k4.data_ptr()),
-                                                           C.c_void_p(grid.data_ptr()), C.c_void_p(erp.data_ptr()), n, fw, eh, ew, conv,
-                                                           _face_map_arr(face_map), None, st)
-        _lib.check(rc, "s360_cube2erp_distance_forward")
+        call("s360_cube2erp_distance_forward", depth.device, ptr(depth), ptr(k4), ptr(grid), ptr(erp), n, fw, eh, ew, conv,
+             _face_map_arr(face_map), None)
         ctx.save_for_backward(depth, k4, grid, plan_offsets, plan_entries)
         ctx.meta = (face_map, conv)
         return erp
@@ -235,14 +222,8 @@ class _StitchDistance(torch.autograd.Function):
             raise RuntimeError("cube->ERP distance stitch backward: the adjoint plan does not belong to this grid / device")
         g = d_erp.detach().float().contiguous()
         d_depth = torch.empty_like(depth)
-        with torch.cuda.device(depth.device):
-            st = C.c_void_p(torch.cuda.current_stream(depth.device).cuda_stream)
-            rc = _lib.lib().s360_cube2erp_distance_backward(C.c_void_p(g.data_ptr()), C.c_void_p(depth.data_ptr()),
-                                                            C.c_void_p(k4.data_ptr()), C.c_void_p(grid.data_ptr()),
-                                                            C.c_void_p(offs.data_ptr()), C.c_void_p(ents.data_ptr()),
-                                                            C.c_void_p(d_depth.data_ptr()), n, fw, eh, ew, conv,
-                                                            _face_map_arr(face_map), None, st)
-        _lib.check(rc, "s360_cube2erp_distance_backward")
+        call("s360_cube2erp_distance_backward", depth.device, ptr(g), ptr(depth), ptr(k4), ptr(grid), ptr(offs), ptr(ents),
+             ptr(d_depth), n, fw, eh, ew, conv, _face_map_arr(face_map), None)
         return d_depth, None, None, None, None, None, None
 
 
@@ -258,13 +239,8 @@ class _Stitch(torch.autograd.Function):
         if strides is None:
             x = x.contiguous()
         erp = torch.empty((channels, eh, ew), dtype=torch.float32, device=faces.device)
-        with torch.cuda.device(faces.device):
-            st = C.c_void_p(torch.cuda.current_stream(faces.device).cuda_stream)
-            sarr = None if strides is None else (C.c_int64 * 3)(*strides)
-            rc = _lib.lib().s360_cube2erp_forward(C.c_void_p(x.data_ptr()), C.c_void_p(grid.data_ptr()),
-                                                  C.c_void_p(erp.data_ptr()), channels, face_w, eh, ew,
-                                                  _face_map_arr(face_map), sarr, st)
-        _lib.check(rc, "s360_cube2erp_forward")
+        sarr = None if strides is None else (C.c_int64 * 3)(*strides)
+        call("s360_cube2erp_forward", faces.device, ptr(x), ptr(grid), ptr(erp), channels, face_w, eh, ew, _face_map_arr(face_map), sarr)
         ctx.save_for_backward(grid, plan_offsets, plan_entries)
         ctx.meta = (face_map, strides, channels, face_w, tuple(faces.shape))
         return erp
@@ -279,13 +255,8 @@ class _Stitch(torch.autograd.Function):
             raise RuntimeError("cube->ERP stitch backward: the adjoint plan does not belong to this grid / device")
         g = d_erp.detach().float().contiguous()
         d_faces = torch.empty((6, channels, face_w, face_w), dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            st = C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
-            rc = _lib.lib().s360_cube2erp_backward(C.c_void_p(g.data_ptr()), C.c_void_p(grid.data_ptr()),
-                                                   C.c_void_p(offs.data_ptr()), C.c_void_p(ents.data_ptr()),
-                                                   C.c_void_p(d_faces.data_ptr()), channels, face_w, eh, ew,
-                                                   _face_map_arr(face_map), None, st)
-        _lib.check(rc, "s360_cube2erp_backward")
+        call("s360_cube2erp_backward", g.device, ptr(g), ptr(grid), ptr(offs), ptr(ents), ptr(d_faces), channels, face_w, eh, ew,
+             _face_map_arr(face_map), None)
         if strides is not None:  # input was [C, fw, 6*fw]
             d_faces = d_faces.permute(1, 2, 0, 3).reshape(shape)
         return d_faces, None, None, None, None, None, None, None

@@ -25,7 +25,7 @@ from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .cost_volume import _ptr, _stream
+from ._call import call, ptr
 
 CHANNELS = 128
 HIDDEN = 1024
@@ -135,10 +135,8 @@ def ffn_tail_forward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bias
     out = torch.empty(source.shape, dtype=torch.float32, device=source.device)
     z = torch.empty(tokens, CHANNELS, dtype=torch.float32, device=source.device)
     stats = torch.empty(2, tokens, 2, dtype=torch.float64, device=source.device)
-    with torch.cuda.device(source.device):
-        rc = _lib.lib().s360_ffn_tail_forward(*(_ptr(t) for t in args), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))),
-                                              _ptr(out), _ptr(z), _ptr(stats), _stream(source.device))
-    _lib.check(rc, "s360_ffn_tail_forward")
+    call("s360_ffn_tail_forward", source.device, *(ptr(t) for t in args), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))),
+         ptr(out), ptr(z), ptr(stats))
     return out, z, stats
 
 
@@ -156,10 +154,8 @@ def ffn_tail_backward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bia
                                             buffers)))
     scratch = _scratch(tokens, source.device)
     order = ("g_source", "g_m", "g_w1", "g_w2", "g_norm1_weight", "g_norm1_bias", "g_norm2_weight", "g_norm2_bias")
-    with torch.cuda.device(source.device):
-        rc = _lib.lib().s360_ffn_tail_backward(*(_ptr(t) for t in ins), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))),
-                                               _ptr(scratch), scratch.numel(), *(_ptr(outs[n]) for n in order), _stream(source.device))
-    _lib.check(rc, "s360_ffn_tail_backward")
+    call("s360_ffn_tail_backward", source.device, *(ptr(t) for t in ins), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))),
+         ptr(scratch), scratch.numel(), *(ptr(outs[n]) for n in order))
     return tuple(outs[n] for n in FFN_GRADIENTS)
 
 
@@ -169,10 +165,8 @@ def layer_norm_residual_forward(x: Tensor, weight: Tensor, bias: Tensor, residua
     args = [_flat(t) for t in (x, weight, bias, residual)]
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     stats = torch.empty(tokens, 2, dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().s360_layer_norm_residual_forward(*(_ptr(t) for t in args), tokens, CHANNELS, C.byref(C.c_double(float(eps))),
-                                                         _ptr(out), _ptr(stats), _stream(x.device))
-    _lib.check(rc, "s360_layer_norm_residual_forward")
+    call("s360_layer_norm_residual_forward", x.device, *(ptr(t) for t in args), tokens, CHANNELS, C.byref(C.c_double(float(eps))),
+         ptr(out), ptr(stats))
     return out, stats
 
 
@@ -186,11 +180,8 @@ def layer_norm_residual_backward(x: Tensor, weight: Tensor, stats: Tensor, g_out
     ins = [_flat(t) for t in (x, weight, stats, g_out)]
     outs = dict(zip(NORM_GRADIENTS, _buffers(what, NORM_GRADIENTS, (x, weight, weight, x), buffers)))
     scratch = _scratch(tokens, x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().s360_layer_norm_residual_backward(*(_ptr(t) for t in ins), tokens, CHANNELS, _ptr(scratch), scratch.numel(),
-                                                          _ptr(outs["g_x"]), _ptr(outs["g_residual"]), _ptr(outs["g_weight"]),
-                                                          _ptr(outs["g_bias"]), _stream(x.device))
-    _lib.check(rc, "s360_layer_norm_residual_backward")
+    call("s360_layer_norm_residual_backward", x.device, *(ptr(t) for t in ins), tokens, CHANNELS, ptr(scratch), scratch.numel(),
+         ptr(outs["g_x"]), ptr(outs["g_residual"]), ptr(outs["g_weight"]), ptr(outs["g_bias"]))
     return tuple(outs[n] for n in NORM_GRADIENTS)
 
 

@@ -19,14 +19,10 @@ import ctypes as C
 import torch
 from torch import Tensor
 
-from . import _lib
+from ._call import call, invoke, ptr
 
 COLOR_MAPS = ("turbo", "viridis", "inferno")                 # S360_CMAP_*
 MAX_MAP_ELEMENTS = 16_000_000
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _gpu_f32(t, what: str) -> Tensor:
@@ -71,15 +67,10 @@ def _maps(depth: Tensor, what: str):
 
 
 def _depth_call(d3, n, h, w, stride, rgb, u8, rng):
-    l = _lib.lib()
     nbytes = C.c_size_t(0)
-    _lib.check(l.s360_depth_colormap(None, n, h, w, stride, None, None, None, None, C.byref(nbytes), None),
-               "s360_depth_colormap (workspace size)")
+    invoke("s360_depth_colormap", None, n, h, w, stride, None, None, None, None, C.byref(nbytes), None)
     ws = torch.empty(max(int(nbytes.value), 16), dtype=torch.uint8, device=d3.device)
-    with torch.cuda.device(d3.device):
-        st = C.c_void_p(torch.cuda.current_stream(d3.device).cuda_stream)
-        rc = l.s360_depth_colormap(_p(d3), n, h, w, stride, _p(rgb), _p(u8), _p(rng), _p(ws), C.byref(nbytes), st)
-    _lib.check(rc, "s360_depth_colormap")
+    call("s360_depth_colormap", d3.device, ptr(d3), n, h, w, stride, ptr(rgb), ptr(u8), ptr(rng), ptr(ws), C.byref(nbytes))
 
 
 def depth_map(depth: Tensor, out: str = "float") -> Tensor:
@@ -141,11 +132,8 @@ def colorize(x: Tensor, color_map: str = "inferno", channels: str = "last", out:
         return res
     v = v.contiguous()
     plane = int(v.shape[-2] * v.shape[-1]) if first else 0
-    with torch.cuda.device(v.device):
-        st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
-        rc = _lib.lib().s360_colorize(_p(v), v.numel(), plane, COLOR_MAPS.index(color_map), int(first),
-                                      _p(res) if out == "float" else None, _p(res) if out == "uint8" else None, st)
-    _lib.check(rc, "s360_colorize")
+    call("s360_colorize", v.device, ptr(v), v.numel(), plane, COLOR_MAPS.index(color_map), int(first),
+         ptr(res) if out == "float" else None, ptr(res) if out == "uint8" else None)
     return res
 
 
@@ -164,10 +152,7 @@ def prep_image(image: Tensor) -> Tensor:
     b, c, h, w = (int(s) for s in v.shape)
     v = v.contiguous()
     res = torch.empty((h, b * w, 4 if c == 4 else 3), dtype=torch.uint8, device=v.device)
-    with torch.cuda.device(v.device):
-        st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
-        rc = _lib.lib().s360_prep_image(_p(v), b, c, h, w, _p(res), st)
-    _lib.check(rc, "s360_prep_image")
+    call("s360_prep_image", v.device, ptr(v), b, c, h, w, ptr(res))
     return res
 
 
@@ -183,8 +168,5 @@ def error_map(pred: Tensor, gt: Tensor) -> Tensor:
     a, b = a.contiguous(), b.contiguous()
     h, w = int(a.shape[1]), int(a.shape[2])
     res = torch.empty((h, w, 3), dtype=torch.uint8, device=a.device)
-    with torch.cuda.device(a.device):
-        st = C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-        rc = _lib.lib().s360_error_map(_p(a), _p(b), h, w, _p(res), st)
-    _lib.check(rc, "s360_error_map")
+    call("s360_error_map", a.device, ptr(a), ptr(b), h, w, ptr(res))
     return res

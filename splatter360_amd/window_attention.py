@@ -17,8 +17,7 @@ import torch
 from torch import Tensor
 from torch.autograd.function import once_differentiable
 
-from . import _lib
-from .cost_volume import _check_cuda_f32, _ptr, _stream
+from ._call import _check_cuda_f32, call, ptr
 
 MASK_RULES = {"reference": 0, "aligned": 1}
 MIN_CHANNELS, MAX_CHANNELS, CHANNEL_STEP = 32, 128, 32
@@ -69,10 +68,8 @@ def attention_forward(q: Tensor, k: Tensor, v: Tensor, *, height: int, width: in
     b, l, c = (int(s) for s in q.shape)
     out = torch.empty_like(q)
     lse = torch.empty(b, l, dtype=torch.float64, device=q.device)
-    with torch.cuda.device(q.device):
-        rc = _lib.lib().s360_window_attention_forward(_ptr(q), _ptr(k), _ptr(v), b, partners, int(height), int(width), c, int(num_splits),
-                                                      int(bool(with_shift)), rule, _ptr(out), _ptr(lse), _stream(q.device))
-    _lib.check(rc, "s360_window_attention_forward")
+    call("s360_window_attention_forward", q.device, ptr(q), ptr(k), ptr(v), b, partners, int(height), int(width), c, int(num_splits),
+         int(bool(with_shift)), rule, ptr(out), ptr(lse))
     return out, lse
 
 
@@ -92,11 +89,9 @@ def attention_backward(q: Tensor, k: Tensor, v: Tensor, lse: Tensor, g_out: Tens
     if g_q is None and g_k is None and g_v is None:
         return None, None, None
     delta = torch.empty(b, l, dtype=torch.float64, device=q.device)
-    with torch.cuda.device(q.device):
-        rc = _lib.lib().s360_window_attention_backward(_ptr(q), _ptr(k), _ptr(v), _ptr(lse), _ptr(g_out), b, partners,
-                                                       int(height), int(width), c, int(num_splits), int(bool(with_shift)), rule,
-                                                       _ptr(delta), _ptr(g_q), _ptr(g_k), _ptr(g_v), _stream(q.device))
-    _lib.check(rc, "s360_window_attention_backward")
+    call("s360_window_attention_backward", q.device, ptr(q), ptr(k), ptr(v), ptr(lse), ptr(g_out), b, partners,
+         int(height), int(width), c, int(num_splits), int(bool(with_shift)), rule,
+         ptr(delta), ptr(g_q), ptr(g_k), ptr(g_v))
     return g_q, g_k, g_v
 
 

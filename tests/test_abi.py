@@ -116,18 +116,22 @@ def test_header_is_plain_c_and_a_c_program_can_call_the_library(tmp_path):
 
 
 def test_ctypes_argtypes_match_the_header_prototypes():
-    """Every entry point's ctypes argtypes (splatter360_amd/_lib.py) has as many parameters as its prototype in
-    include/s360.h, pointers where the header has pointers and sizes / integers / floats where it has those: a
-    signature changed on one side only (the ABI moved twice in round 2) fails here, on CPU."""
+    """Every function include/s360.h declares has an entry in _lib.SIGNATURES, and the loaded library carries it: the header's
+    return type, as many parameters as the prototype (none for `void`), pointers where the header has pointers and sizes /
+    integers / 64-bit integers / floats where it has those: a signature changed on one side only (the ABI moved twice in
+    round 2) fails here, on CPU."""
     import ctypes as C
     text = re.sub(r"/\*.*?\*/", " ", (ROOT / "include" / "s360.h").read_text(), flags=re.S)
     lib = _lib.lib()
-    checked = 0
-    for m in re.finditer(r"\b(?:int|const char\s*\*)\s+(s360_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, params = m.group(1), m.group(2).strip()
+    restypes = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
+    checked = set()
+    for m in re.finditer(r"\b(int|size_t|const char\s*\*)\s+(s360_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
+        ret, name, params = re.sub(r"\s+\*", "*", m.group(1)), m.group(2), m.group(3).strip()
+        assert name in _lib.SIGNATURES, f"{name}: declared in the header, missing in _lib.SIGNATURES"
         fn = getattr(lib, name)
-        if fn.argtypes is None:
-            continue
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), f"{name}: lib() did not apply the table"
+        assert restype is restypes[ret], f"{name}: header returns {ret}, ctypes {restype}"
         plist = [] if params in ("", "void") else [p.strip() for p in params.split(",")]
         assert len(plist) == len(fn.argtypes), f"{name}: header has {len(plist)} parameters, ctypes {len(fn.argtypes)}"
         for p, a in zip(plist, fn.argtypes):
@@ -139,10 +143,57 @@ def test_ctypes_argtypes_match_the_header_prototypes():
                     assert a is C.c_float, f"{name}: '{p}' vs {a}"
                 elif "size_t" in p:
                     assert a in (C.c_size_t, C.c_uint64), f"{name}: '{p}' vs {a}"
+                elif "int64_t" in p:
+                    assert a is C.c_int64, f"{name}: '{p}' vs {a}"
                 else:
                     assert a in (C.c_int, C.c_int32, C.c_uint32), f"{name}: '{p}' vs {a}"
-        checked += 1
-    assert checked >= 12
+        checked.add(name)
+    assert checked == set(_declared()) == set(_lib.SIGNATURES) and len(checked) >= 71
+
+
+class _StubLibrary:
+    """Stands in for the loaded library: every entry point records its arguments and returns `code`."""
+
+    def __init__(self, code):
+        self.code, self.calls = code, []
+
+    def s360_error_string(self, code):
+        return b"stub says no"
+
+    def __getattr__(self, name):
+        return lambda *args: self.calls.append((name, args)) or self.code
+
+
+def test_call_helper_checks_the_status_and_names_the_entry_point(monkeypatch):
+    """_call.invoke reaches the library through _lib.lib() at call time, returns on 0, and on another code raises RuntimeError
+    naming the entry point with s360_error_string's text; ptr(None) is None (NULL for c_void_p and POINTER parameters)."""
+    from splatter360_amd import _call
+    ok = _StubLibrary(0)
+    monkeypatch.setattr(_lib, "lib", lambda: ok)
+    assert _call.invoke("s360_anything", 1, None, 2.5) is None
+    assert ok.calls == [("s360_anything", (1, None, 2.5))]
+    bad = _StubLibrary(-3)
+    monkeypatch.setattr(_lib, "lib", lambda: bad)               # replaced after import: the helper must not have cached a handle
+    with pytest.raises(RuntimeError, match=r"s360_forward_depth failed: stub says no \(-3\)"):
+        _call.invoke("s360_forward_depth", 7)
+    assert bad.calls == [("s360_forward_depth", (7,))] and len(ok.calls) == 1
+    assert _call.ptr(None) is None
+
+
+def test_native_calls_go_through_the_one_helper():
+    """The package's sources: only _call.py takes a stream's handle, no module defines a pointer / stream / float32-check helper of
+    its own (_call.py holds the one _check_cuda_f32), and none imports a private name from the cost volume."""
+    sources = {f.name: f.read_text() for f in sorted((ROOT / "splatter360_amd").glob("*.py"))}
+    assert "_call.py" in sources and len(sources) >= 20
+    assert [n for n, s in sources.items() if "cuda_stream" in s] == ["_call.py"]
+    defined = {n: sorted(set(re.findall(r"^\s*(?:def\s+(_ptr|_p|_stream|_check_cuda_f32)\b|(_ptr|_p|_stream|_check_cuda_f32)\s*=)", s, flags=re.M)))
+               for n, s in sources.items()}
+    defined = {n: sorted({a or b for a, b in d}) for n, d in defined.items() if d}
+    assert defined == {"_call.py": ["_check_cuda_f32"]}, defined
+    for n, s in sources.items():
+        for m in re.finditer(r"^\s*from\s+\.cost_volume\s+import\s+(\([^)]*\)|[^\n]*)", s, flags=re.M):
+            names = [x.strip().split(" as ")[0] for x in m.group(1).strip("()").split(",") if x.strip()]
+            assert not [x for x in names if x.startswith("_")], f"{n} imports {names} from .cost_volume"
 
 
 def test_loading_the_library_brings_torch_in_first():
