@@ -10,10 +10,7 @@
 //              Wigner-D blocks, one d_sh x d_sh matrix per view, come from k_sh_rotation_blocks below or from the caller)
 // instead of ~20 torch launches with their [G,3,3] intermediates.  grid.y = view, so everything that depends on the
 // view only (pose, SH rotation blocks) is wave-uniform.  Streaming: 336 B read, 352 B (cov6: 340 B) written per Gaussian.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/s360.h"
+#include "s360_launch.h"
 #include "s360_shrot_tables.h"
 #include "s360_adapter_math.h"
 
@@ -602,7 +599,7 @@ extern "C" int s360_adapter_forward(const float* extrinsics, const float* depths
     } else
     hipLaunchKernelGGL(k_adapter_fwd, dim3((per_view + 255) / 256, n_views), dim3(256), 0, (hipStream_t)stream, ap, extrinsics,
                        depths, raw_gaussians, sh_rotation, means, covariances, harmonics, scales_out, rotations_out);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_adapter_backward(const float* extrinsics, const float* depths, const float* raw_gaussians,
@@ -627,7 +624,7 @@ extern "C" int s360_adapter_backward(const float* extrinsics, const float* depth
     } else
     hipLaunchKernelGGL(k_adapter_bwd, dim3((per_view + 255) / 256, n_views), dim3(256), 0, (hipStream_t)stream, ap, extrinsics,
                        depths, raw_gaussians, sh_rotation, d_means, d_covariances, d_harmonics, d_depths, d_raw_gaussians);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_sh_rotation_blocks(const float* rotations, int32_t row_major_stride, int32_t n_views, int32_t d_sh,
@@ -639,5 +636,5 @@ extern "C" int s360_sh_rotation_blocks(const float* rotations, int32_t row_major
     const int threads = n_views * 5;
     hipLaunchKernelGGL(k_sh_rotation_blocks, dim3((threads + 63) / 64), dim3(64), 0, (hipStream_t)stream, rotations,
                        row_major_stride, n_views, d_sh, deg, sh_rotation_out);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

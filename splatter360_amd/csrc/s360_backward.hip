@@ -852,20 +852,6 @@ __global__ __launch_bounds__(192) void k_raw_bwd(KParams kp, const S360View* __r
 
 using namespace s360;
 
-#ifdef S360_DEBUG_LAUNCH  /* compile-time diagnostic (-DS360_DEBUG_LAUNCH): no environment reads in the host path */
-#define S360_LAUNCH_DIAG(e) fprintf(stderr, "s360: %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__)
-#else
-#define S360_LAUNCH_DIAG(e) ((void)0)
-#endif
-#define S360_CHECK_LAUNCH()                                                                          \
-    do {                                                                                             \
-        hipError_t e_ = hipGetLastError();                                                           \
-        if (e_ != hipSuccess) {                                                                      \
-            S360_LAUNCH_DIAG(e_);                                                                    \
-            return S360_E_LAUNCH;                                                                    \
-        }                                                                                            \
-    } while (0)
-
 // Slab passes of k_gaussians_bwd_sh (1 or 2: see the kernel).  -DS360_FUSED_SH_PASSES=1 builds the other schedule of the same
 // sources for a measurement.
 #ifndef S360_FUSED_SH_PASSES

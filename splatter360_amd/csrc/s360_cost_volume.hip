@@ -390,8 +390,8 @@ int cv_setup(int32_t n, int32_t m, int32_t pairs, int32_t C, int32_t h, int32_t 
     if (n < 1 || m < 1 || pairs < 1 || C < 1 || h < 1 || w < 1 || D < 1 || convention != S360_CV_HM3D) return S360_E_BADARG;
     if (h > CV_MAX_SIDE || w > CV_MAX_SIDE || (long long)h * w > 0x3fffffffLL) return S360_E_BADARG;
     const long long HW = (long long)h * w, bpn = (HW + CV_PX - 1) / CV_PX;
-    if (bpn * n > 0x7fffffffLL / S360_BLOCK || (long long)n * D * HW > 0x7fffffffLL * (long long)S360_BLOCK) return S360_E_BADARG;
-    if ((HW + 63) / 64 > 0x7fffffffLL || (C + 31) / 32 > 65535 || n > 65535 || m > 65535) return S360_E_BADARG;
+    if (!s360_grid_fits(bpn * n) || (long long)n * D * HW > (long long)INT32_MAX * S360_BLOCK) return S360_E_BADARG;
+    if ((HW + 63) / 64 > INT32_MAX || (C + 31) / 32 > 65535 || n > 65535 || m > 65535) return S360_E_BADARG;
     pl->CP = (C + 3) & ~3;
     pl->own_bytes = (size_t)n * HW * pl->CP * sizeof(float);
     pl->partner_bytes = (size_t)m * HW * pl->CP * sizeof(float);
@@ -417,24 +417,19 @@ extern "C" int s360_cost_volume_forward(const float* f_own, const float* f_partn
     CVPlan pl;
     const int rc = cv_setup(n, m, pairs, C, h, w, D, convention, &pl);
     if (rc != S360_OK) return rc;
-    const size_t need = pl.own_bytes + pl.partner_bytes;
-    if (!workspace) {
-        *workspace_bytes = need;
-        return S360_OK;
-    }
-    if (!f_own || !f_partner || !poses || !depths || !out || ((uintptr_t)workspace & 15u)) return S360_E_BADARG;
-    if (!partner_slot && m != n) return S360_E_BADARG;
-    if (*workspace_bytes < need) return S360_E_WORKSPACE;
+    const int ws = s360_workspace(workspace, workspace_bytes, pl.own_bytes + pl.partner_bytes, 16,
+                                  f_own && f_partner && poses && depths && out && (partner_slot || m == n));
+    if (ws != S360_WS_READY) return ws;
     const hipStream_t st = (hipStream_t)stream;
     const int HW = h * w;
     float* own_cl = (float*)workspace;
     float* partner_cl = (f_partner == f_own && m == n) ? own_cl : (float*)((char*)workspace + pl.own_bytes);
     cv_to_cl(f_own, own_cl, n, C, pl.CP, HW, st);
     if (partner_cl != own_cl) cv_to_cl(f_partner, partner_cl, m, C, pl.CP, HW, st);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     const CVArgs a{own_cl, partner_cl, partner_slot, poses, depths, n, m, pairs, C, pl.CP, h, w, D, scale};
     hipLaunchKernelGGL(k_cv_forward, dim3(pl.blocks), dim3(S360_BLOCK), 0, st, a, out);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_cost_volume_backward(const float* f_own, const float* f_partner, const int32_t* partner_slot, const float* poses,
@@ -445,15 +440,9 @@ extern "C" int s360_cost_volume_backward(const float* f_own, const float* f_part
     CVPlan pl;
     const int rc = cv_setup(n, m, pairs, C, h, w, D, convention, &pl);
     if (rc != S360_OK) return rc;
-    const size_t need = 2 * (pl.own_bytes + pl.partner_bytes);
-    if (!workspace) {
-        *workspace_bytes = need;
-        return S360_OK;
-    }
-    if (!f_own || !f_partner || !poses || !depths || !grad_out || !grad_own || !grad_partner || ((uintptr_t)workspace & 15u))
-        return S360_E_BADARG;
-    if (!partner_slot && m != n) return S360_E_BADARG;
-    if (*workspace_bytes < need) return S360_E_WORKSPACE;
+    const int wsr = s360_workspace(workspace, workspace_bytes, 2 * (pl.own_bytes + pl.partner_bytes), 16,
+                                   f_own && f_partner && poses && depths && grad_out && grad_own && grad_partner && (partner_slot || m == n));
+    if (wsr != S360_WS_READY) return wsr;
     const hipStream_t st = (hipStream_t)stream;
     const int HW = h * w;
     char* ws = (char*)workspace;
@@ -464,14 +453,14 @@ extern "C" int s360_cost_volume_backward(const float* f_own, const float* f_part
     cv_to_cl(f_own, own_cl, n, C, pl.CP, HW, st);
     if (partner_cl != own_cl) cv_to_cl(f_partner, partner_cl, m, C, pl.CP, HW, st);
     if (hipMemsetAsync(g_partner_cl, 0, pl.partner_bytes, st) != hipSuccess) return S360_E_LAUNCH;
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     const CVArgs a{own_cl, partner_cl, partner_slot, poses, depths, n, m, pairs, C, pl.CP, h, w, D, scale};
     hipLaunchKernelGGL(k_cv_backward_own, dim3(pl.blocks), dim3(S360_BLOCK), 0, st, a, grad_out, g_own_cl);
     hipLaunchKernelGGL(k_cv_backward_partner, dim3(pl.blocks), dim3(S360_BLOCK), 0, st, a, grad_out, g_partner_cl);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     cv_from_cl(g_own_cl, grad_own, n, C, pl.CP, HW, st);
     cv_from_cl(g_partner_cl, grad_partner, m, C, pl.CP, HW, st);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_cost_volume_warp(const float* f_partner, const int32_t* partner_slot, const float* poses, const float* depths,
@@ -484,5 +473,5 @@ extern "C" int s360_cost_volume_warp(const float* f_partner, const int32_t* part
     const long long total = (long long)n * D * h * w;
     hipLaunchKernelGGL(k_cv_warp, dim3((unsigned)((total + S360_BLOCK - 1) / S360_BLOCK)), dim3(S360_BLOCK), 0, (hipStream_t)stream, f_partner,
                        partner_slot, poses, depths, (int)n, (int)m, (int)C, (int)h, (int)w, (int)D, warped);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

@@ -236,8 +236,6 @@ bool dh_sizes_ok(int32_t n, int32_t d, int32_t h, int32_t w) {
     return n >= 1 && d >= 1 && h >= 1 && w >= 1 && n <= 65535 && (long long)h * w <= 0x3fffffffLL;
 }
 
-bool dh_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace
 
 extern "C" int s360_depth_head_forward(const float* logits, const float* candidates, int32_t n, int32_t d, int32_t h, int32_t w,
@@ -246,7 +244,7 @@ extern "C" int s360_depth_head_forward(const float* logits, const float* candida
     const int P = h * w;
     hipLaunchKernelGGL(k_dh_forward, dim3((unsigned)((P + 63) / 64), (unsigned)n), dim3(S360_BLOCK), 0, (hipStream_t)stream, logits,
                        candidates, (int)d, P, depth, pmax, lse, argmax);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_depth_head_backward(const float* logits, const float* candidates, const float* lse, const float* depth,
@@ -255,13 +253,13 @@ extern "C" int s360_depth_head_backward(const float* logits, const float* candid
     if (!logits || !candidates || !lse || !depth || !argmax || !g_logits || !dh_sizes_ok(n, d, h, w)) return S360_E_BADARG;
     const int P = h * w;
     const hipStream_t st = (hipStream_t)stream;
-    const bool vec = P % 4 == 0 && dh_aligned16(logits) && dh_aligned16(lse) && dh_aligned16(depth) && dh_aligned16(g_depth) &&
-                     dh_aligned16(g_pmax) && dh_aligned16(g_logits);
+    const bool vec = P % 4 == 0 && s360_aligned(logits, 16) && s360_aligned(lse, 16) && s360_aligned(depth, 16) && s360_aligned(g_depth, 16) &&
+                     s360_aligned(g_pmax, 16) && s360_aligned(g_logits, 16);
     if (vec)
         hipLaunchKernelGGL(k_dh_backward<4>, dim3((unsigned)((P + 255) / 256), (unsigned)n), dim3(S360_BLOCK), 0, st, logits, candidates, lse,
                            depth, argmax, g_depth, g_pmax, (int)d, P, g_logits);
     else
         hipLaunchKernelGGL(k_dh_backward<1>, dim3((unsigned)((P + 63) / 64), (unsigned)n), dim3(S360_BLOCK), 0, st, logits, candidates, lse,
                            depth, argmax, g_depth, g_pmax, (int)d, P, g_logits);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

@@ -18,8 +18,8 @@
 //                 clamped denominator den' the forward wrote.  The fused backward recomputes the eroded mask from the halo.
 //
 // Determinism: every 32 x 256 tile writes its (num, den) double pair to its own workspace slot (fixed lane / wave order);
-// k_l1_finish sums the slots of a batch element (or all of them) in a fixed order.  No atomics, no memset, no host
-// synchronisation; far is read on the device.
+// k_l1_finish sums the slots of a batch element (or all of them) in a fixed order (block_tree_sum).  No atomics, no memset,
+// no host synchronisation; far is read on the device.
 #include "s360_device.h"
 
 namespace s360 {
@@ -211,6 +211,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_l1_sphere(const float* __restric
         }
     }
     if constexpr (!BWD) {
+        // block_sum's order, written out: through block_sum the mask-mode kernel's register count moved (30 to 29)
 #pragma unroll
         for (int off = S360_WAVE / 2; off > 0; off >>= 1) {
             num += __shfl_down(num, off, S360_WAVE);
@@ -238,27 +239,18 @@ __global__ __launch_bounds__(S360_BLOCK) void k_l1_sphere(const float* __restric
 // clamp_away_from does (>= 0: max(den, 1e-10); else min(den, -1e-10); NaN stays NaN), and the quotient is taken in float32.
 __global__ __launch_bounds__(S360_BLOCK) void k_l1_finish(const double2* __restrict__ partials, int slots_per_out, float* __restrict__ loss,
                                                           float* __restrict__ den_out) {
-    __shared__ double rn[S360_BLOCK], rd[S360_BLOCK];
+    __shared__ double red[2][S360_BLOCK];                     // num, den
     const int tid = threadIdx.x, o = blockIdx.x;
     const double2* p = partials + (size_t)o * slots_per_out;
-    double a = 0.0, b = 0.0;
+    double s[2] = {0.0, 0.0};
     for (int j = tid; j < slots_per_out; j += S360_BLOCK) {
         const double2 v = p[j];
-        a += v.x;
-        b += v.y;
+        s[0] += v.x;
+        s[1] += v.y;
     }
-    rn[tid] = a;
-    rd[tid] = b;
-    __syncthreads();
-    for (int s = S360_BLOCK / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            rn[tid] += rn[tid + s];
-            rd[tid] += rd[tid + s];
-        }
-        __syncthreads();
-    }
+    block_tree_sum(s, red);
     if (tid == 0) {
-        const float nf = (float)rn[0], df = (float)rd[0];
+        const float nf = (float)red[0][0], df = (float)red[1][0];
         float dc;
         if (df >= 0.f) dc = df > 1e-10f ? df : 1e-10f;
         else dc = (df < -1e-10f || df != df) ? df : -1e-10f;
@@ -279,15 +271,15 @@ extern "C" int s360_erode(const float* x, float* out, int32_t n_planes, int32_t 
     if (pad <= ER_MAXPAD) {
         const int tiles_x = (width + ER_TW - 1) / ER_TW, tiles_y = (height + ER_TH - 1) / ER_TH;
         const long long tiles_per_plane = (long long)tiles_x * tiles_y, blocks = tiles_per_plane * n_planes;
-        if (blocks > 0x7fffffffLL / S360_BLOCK) return S360_E_BADARG;
+        if (!s360_grid_fits(blocks)) return S360_E_BADARG;
         hipLaunchKernelGGL(k_erode, dim3((unsigned)blocks), dim3(S360_BLOCK), 0, st, x, out, (int)height, (int)width, tiles_x,
                            (int)tiles_per_plane, pad);
     } else {
         const long long n = (long long)n_planes * height * width, blocks = (n + S360_BLOCK - 1) / S360_BLOCK;
-        if (blocks > 0x7fffffffLL / S360_BLOCK) return S360_E_BADARG;
+        if (!s360_grid_fits(blocks)) return S360_E_BADARG;
         hipLaunchKernelGGL(k_erode_direct, dim3((unsigned)blocks), dim3(S360_BLOCK), 0, st, x, out, n, (int)height, (int)width, pad);
     }
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 namespace {
@@ -308,12 +300,10 @@ int dl_setup(const float* mask, int32_t batch, int32_t views, int32_t height, in
     g->tiles_x = (width + DL_TW - 1) / DL_TW;
     const long long tiles_per_plane = (long long)g->tiles_x * ((height + DL_TH - 1) / DL_TH);
     g->blocks = tiles_per_plane * batch * views;
-    if (g->blocks > 0x7fffffffLL / S360_BLOCK) return S360_E_BADARG;
+    if (!s360_grid_fits(g->blocks)) return S360_E_BADARG;
     g->tiles_per_plane = (int)tiles_per_plane;
     return S360_OK;
 }
-
-bool aligned16(const void* p) { return !p || ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
 
@@ -325,14 +315,10 @@ extern "C" int s360_l1_sphere_forward(const float* pred, const float* target, co
     DLGrid g;
     const int rc = dl_setup(mask, batch, views, height, width, ksize, far, &g);
     if (rc != S360_OK) return rc;
-    const size_t need = (size_t)g.blocks * sizeof(double2);
-    if (!workspace) {
-        *workspace_bytes = need;
-        return S360_OK;
-    }
-    if (!pred || !target || !row_weights || !loss_out || !den_out || ((uintptr_t)workspace & 15u)) return S360_E_BADARG;
-    if (*workspace_bytes < need) return S360_E_WORKSPACE;
-    const int vec = (width % 4 == 0) && aligned16(pred) && aligned16(target) && aligned16(mask);
+    const int ws = s360_workspace(workspace, workspace_bytes, (size_t)g.blocks * sizeof(double2), 16,
+                                  pred && target && row_weights && loss_out && den_out);
+    if (ws != S360_WS_READY) return ws;
+    const int vec = (width % 4 == 0) && s360_aligned(pred, 16) && s360_aligned(target, 16) && (!mask || s360_aligned(mask, 16));
     const DLFused fz{far, near_threshold, fill_below, mask ? 0 : (ksize - 1) / 2};
     double2* partials = (double2*)workspace;
     const hipStream_t st = (hipStream_t)stream;
@@ -344,11 +330,11 @@ extern "C" int s360_l1_sphere_forward(const float* pred, const float* target, co
         hipLaunchKernelGGL((k_l1_sphere<true, false>), dim3((unsigned)g.blocks), dim3(S360_BLOCK), 0, st, pred, target, mask, row_weights,
                            (int)height, (int)width, g.tiles_x, g.tiles_per_plane, (int)views, 0, vec, fz, partials, nullptr, nullptr,
                            nullptr, nullptr);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     const int outs = keep_batch ? batch : 1;
     const long long slots = g.blocks / outs;
     hipLaunchKernelGGL(k_l1_finish, dim3((unsigned)outs), dim3(S360_BLOCK), 0, st, (const double2*)partials, (int)slots, loss_out, den_out);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_l1_sphere_backward(const float* pred, const float* target, const float* mask, const float* row_weights,
@@ -359,8 +345,8 @@ extern "C" int s360_l1_sphere_backward(const float* pred, const float* target, c
     const int rc = dl_setup(mask, batch, views, height, width, ksize, far, &g);
     if (rc != S360_OK) return rc;
     if (!pred || !target || !row_weights || !grad_loss || !den || !grad_pred) return S360_E_BADARG;
-    const int vec = (width % 4 == 0) && aligned16(pred) && aligned16(target) && aligned16(mask) && aligned16(grad_pred) &&
-                    aligned16(grad_target);
+    const int vec = (width % 4 == 0) && s360_aligned(pred, 16) && s360_aligned(target, 16) && (!mask || s360_aligned(mask, 16)) && s360_aligned(grad_pred, 16) &&
+                    (!grad_target || s360_aligned(grad_target, 16));
     const DLFused fz{far, near_threshold, fill_below, mask ? 0 : (ksize - 1) / 2};
     const hipStream_t st = (hipStream_t)stream;
     if (mask)
@@ -371,5 +357,5 @@ extern "C" int s360_l1_sphere_backward(const float* pred, const float* target, c
         hipLaunchKernelGGL((k_l1_sphere<true, true>), dim3((unsigned)g.blocks), dim3(S360_BLOCK), 0, st, pred, target, mask, row_weights,
                            (int)height, (int)width, g.tiles_x, g.tiles_per_plane, (int)views, keep_batch ? 1 : 0, vec, fz, nullptr,
                            grad_loss, den, grad_pred, grad_target);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

@@ -13,8 +13,8 @@
 // gradient are rounded to float32 once.
 //
 // Forward: one workgroup per 32 x 64 tile of one [H, W] plane; the thread of pixel (y, x) forms the x-term that starts at x and
-// the y-term that starts at y.  Sums: lanes by a fixed shuffle tree, the four waves through LDS in wave order, one double pair
-// per tile in its own workspace slot; k_ds_finish adds the slots in index order.  No atomics, no memset, no host read.
+// the y-term that starts at y.  Sums: block_sum (lanes by a fixed shuffle tree, the four waves through LDS in wave order), one
+// double pair per tile in its own workspace slot; k_ds_finish adds the slots in index order.  No atomics, no memset, no host read.
 // Backward: a gather, one thread per pixel, lanes along W; a pixel recomputes the n and e of its own plus-shaped stencil from
 // plain loads (its x-neighbours lie in the cache lines the wave's own row load fetched; the y-neighbours need loads anyway,
 // and a lane exchange would leave the lanes at the wave's edges with a special case for no saved HBM traffic).
@@ -93,25 +93,9 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ds_forward(DSArgs a, double2* __
             if (y + ORD < H) sy += fabs(ds_term<SECOND, BILATERAL>(dplane + o, iplane + o, (size_t)W, hw, a.C, ln, lf, span, sigma));
         }
     }
-#pragma unroll
-    for (int off = S360_WAVE / 2; off > 0; off >>= 1) {
-        sx += __shfl_down(sx, off, S360_WAVE);
-        sy += __shfl_down(sy, off, S360_WAVE);
-    }
-    if (lane == 0) {
-        wsum[0][wave] = sx;
-        wsum[1][wave] = sy;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double p = 0.0, q = 0.0;
-#pragma unroll
-        for (int w = 0; w < DS_WAVES; ++w) {
-            p += wsum[0][w];
-            q += wsum[1][w];
-        }
-        partials[blockIdx.x] = make_double2(p, q);
-    }
+    double s[2] = {sx, sy};
+    block_sum<false>(s, wsum);
+    if (tid == 0) partials[blockIdx.x] = make_double2(s[0], s[1]);
 }
 
 // One workgroup: the slots are staged through LDS 256 at a time and thread 0 adds them in index order.
@@ -223,7 +207,7 @@ int ds_setup(const float* depth, const float* log_near, const float* log_far, co
     const int tiles_x = (W + DS_TW - 1) / DS_TW;
     const long long tiles_per_plane = (long long)tiles_x * ((H + DS_TH - 1) / DS_TH);
     g->blocks = tiles_per_plane * B * V;
-    if (g->blocks > 0x7fffffffLL / S360_BLOCK) return S360_E_BADARG;
+    if (!s360_grid_fits(g->blocks)) return S360_E_BADARG;
     const long long planes = (long long)B * V;                // the element counts, in 64-bit
     g->nx = (double)(planes * H * (long long)(W - ord));
     g->ny = (double)(planes * (long long)(H - ord) * W);
@@ -242,12 +226,9 @@ extern "C" int s360_depth_smooth_forward(const float* depth, const float* log_ne
     const int rc = ds_setup(depth, log_near, log_far, image, batch, views, bound_views, channels, height, width, sigma_image, flags, &g);
     if (rc != S360_OK) return rc;
     const size_t need = (size_t)g.blocks * sizeof(double2);
-    if (!workspace) {
-        *workspace_bytes = need;
-        return S360_OK;
-    }
-    if (!depth || !log_near || !log_far || !loss || ((flags & S360_DS_BILATERAL) && !image) || ((uintptr_t)workspace & 15u)) return S360_E_BADARG;
-    if (*workspace_bytes < need) return S360_E_WORKSPACE;
+    const int ws = s360_workspace(workspace, workspace_bytes, need, 16,
+                                  depth && log_near && log_far && loss && (!(flags & S360_DS_BILATERAL) || image));
+    if (ws != S360_WS_READY) return ws;
     double2* partials = (double2*)workspace;
     const hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)g.blocks), block(S360_BLOCK);
@@ -257,9 +238,9 @@ extern "C" int s360_depth_smooth_forward(const float* depth, const float* log_ne
         case S360_DS_BILATERAL: hipLaunchKernelGGL((k_ds_forward<false, true>), grid, block, 0, st, g.args, partials); break;
         default: hipLaunchKernelGGL((k_ds_forward<true, true>), grid, block, 0, st, g.args, partials); break;
     }
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_ds_finish, dim3(1), block, 0, st, (const double2*)partials, g.blocks, g.nx, g.ny, loss);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_depth_smooth_backward(const float* depth, const float* log_near, const float* log_far, const float* image, int32_t batch,
@@ -277,5 +258,5 @@ extern "C" int s360_depth_smooth_backward(const float* depth, const float* log_n
         case S360_DS_BILATERAL: hipLaunchKernelGGL((k_ds_backward<false, true>), grid, block, 0, st, g.args, g.nx, g.ny, grad_loss, grad_depth); break;
         default: hipLaunchKernelGGL((k_ds_backward<true, true>), grid, block, 0, st, g.args, g.nx, g.ny, grad_loss, grad_depth); break;
     }
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

@@ -44,7 +44,7 @@ __device__ __forceinline__ void up_tap(int mode, int Y, int h, int H, int s, int
     const long long t = (long long)Y * (h - 1);
     const int d = H - 1;
     int r;
-    if (t <= 0x7fffffffLL) {                                  // the usual case: one 32-bit division
+    if (t <= INT32_MAX) {                                     // the usual case: one 32-bit division
         y0 = (int)t / d;
         r = (int)t % d;
     } else {
@@ -320,8 +320,6 @@ using namespace s360;
 
 namespace {
 
-bool dt_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 bool dt_exponent_ok(float e) { return isfinite(e) && e > 0.f; }
 
 bool up_sizes_ok(int32_t n, int32_t h, int32_t w, int32_t s, int32_t mode) {
@@ -342,13 +340,13 @@ extern "C" int s360_upsample_forward(const float* src, float* dst, int32_t n, in
     if (!src || !dst || !up_sizes_ok(n, h, w, s, mode)) return S360_E_BADARG;
     const long long H = (long long)h * s, W = (long long)w * s;
     const hipStream_t st = (hipStream_t)stream;
-    if (W % 4 == 0 && dt_aligned16(dst))                      // H W % 4 == 0 then: every image's rows stay aligned
+    if (W % 4 == 0 && s360_aligned(dst, 16))                  // H W % 4 == 0 then: every image's rows stay aligned
         hipLaunchKernelGGL(k_up_forward<4>, dim3(dt_blocks(H * (W / 4)), (unsigned)n), dim3(S360_BLOCK), 0, st, src, dst, (int)h, (int)w,
                            (int)s, (int)mode, (int)(reciprocal != 0));
     else
         hipLaunchKernelGGL(k_up_forward<1>, dim3(dt_blocks(H * W), (unsigned)n), dim3(S360_BLOCK), 0, st, src, dst, (int)h, (int)w, (int)s,
                            (int)mode, (int)(reciprocal != 0));
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_upsample_backward(const float* g_dst, const float* src, float* g_src, int32_t n, int32_t h, int32_t w, int32_t s,
@@ -356,7 +354,7 @@ extern "C" int s360_upsample_backward(const float* g_dst, const float* src, floa
     if (!g_dst || !g_src || (reciprocal && !src) || !up_sizes_ok(n, h, w, s, mode)) return S360_E_BADARG;
     hipLaunchKernelGGL(k_up_backward, dim3(dt_blocks((long long)h * w), (unsigned)n), dim3(S360_BLOCK), 0, (hipStream_t)stream, g_dst, src,
                        g_src, (int)h, (int)w, (int)s, (int)mode, (int)(reciprocal != 0));
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_depth_tail_forward(const float* fullres_disps, const float* delta_density, const float* lo, const float* hi,
@@ -367,15 +365,15 @@ extern "C" int s360_depth_tail_forward(const float* fullres_disps, const float* 
         return S360_E_BADARG;
     const int P = H * W, b = n / v;
     const hipStream_t st = (hipStream_t)stream;
-    const bool vec = P % 4 == 0 && dt_aligned16(fullres_disps) && dt_aligned16(delta_density) && dt_aligned16(depths_out) &&
-                     dt_aligned16(opacities_out) && dt_aligned16(densities_out);
+    const bool vec = P % 4 == 0 && s360_aligned(fullres_disps, 16) && s360_aligned(delta_density, 16) && s360_aligned(depths_out, 16) &&
+                     s360_aligned(opacities_out, 16) && s360_aligned(densities_out, 16);
     if (vec)
         hipLaunchKernelGGL(k_dt_forward<4>, dim3(dt_blocks(P / 4), (unsigned)n), dim3(S360_BLOCK), 0, st, fullres_disps, delta_density, lo, hi,
                            (double)exponent, (int)gpp, (int)v, b, P, depths_out, opacities_out, densities_out);
     else
         hipLaunchKernelGGL(k_dt_forward<1>, dim3(dt_blocks(P), (unsigned)n), dim3(S360_BLOCK), 0, st, fullres_disps, delta_density, lo, hi,
                            (double)exponent, (int)gpp, (int)v, b, P, depths_out, opacities_out, densities_out);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_depth_tail_backward(const float* g_depths, const float* g_opacities, const float* g_densities,
@@ -387,27 +385,27 @@ extern "C" int s360_depth_tail_backward(const float* g_depths, const float* g_op
         return S360_E_BADARG;
     const int P = H * W, b = n / v;
     const hipStream_t st = (hipStream_t)stream;
-    const bool vec = P % 4 == 0 && dt_aligned16(fullres_disps) && dt_aligned16(delta_density) && dt_aligned16(g_depths) &&
-                     dt_aligned16(g_opacities) && dt_aligned16(g_densities) && dt_aligned16(g_fullres_disps) && dt_aligned16(g_delta_density);
+    const bool vec = P % 4 == 0 && s360_aligned(fullres_disps, 16) && s360_aligned(delta_density, 16) && s360_aligned(g_depths, 16) &&
+                     s360_aligned(g_opacities, 16) && s360_aligned(g_densities, 16) && s360_aligned(g_fullres_disps, 16) && s360_aligned(g_delta_density, 16);
     if (vec)
         hipLaunchKernelGGL(k_dt_backward<4>, dim3(dt_blocks(P / 4), (unsigned)n), dim3(S360_BLOCK), 0, st, g_depths, g_opacities, g_densities,
                            fullres_disps, delta_density, lo, hi, (double)exponent, (int)gpp, (int)v, b, P, g_fullres_disps, g_delta_density);
     else
         hipLaunchKernelGGL(k_dt_backward<1>, dim3(dt_blocks(P), (unsigned)n), dim3(S360_BLOCK), 0, st, g_depths, g_opacities, g_densities,
                            fullres_disps, delta_density, lo, hi, (double)exponent, (int)gpp, (int)v, b, P, g_fullres_disps, g_delta_density);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_opacity_map_forward(const float* pdf, float* out, size_t count, float exponent, void* stream) {
     if (!pdf || !out || count < 1 || count > (size_t)0x3fffffffffLL || !dt_exponent_ok(exponent)) return S360_E_BADARG;
     hipLaunchKernelGGL(k_opacity_map<false>, dim3(dt_blocks((count + 3) / 4)), dim3(S360_BLOCK), 0, (hipStream_t)stream, pdf,
-                       (const float*)nullptr, out, (long long)count, (double)exponent, (int)(dt_aligned16(pdf) && dt_aligned16(out)));
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+                       (const float*)nullptr, out, (long long)count, (double)exponent, (int)(s360_aligned(pdf, 16) && s360_aligned(out, 16)));
+    return s360_launch_status();
 }
 
 extern "C" int s360_opacity_map_backward(const float* pdf, const float* g_out, float* g_pdf, size_t count, float exponent, void* stream) {
     if (!pdf || !g_out || !g_pdf || count < 1 || count > (size_t)0x3fffffffffLL || !dt_exponent_ok(exponent)) return S360_E_BADARG;
     hipLaunchKernelGGL(k_opacity_map<true>, dim3(dt_blocks((count + 3) / 4)), dim3(S360_BLOCK), 0, (hipStream_t)stream, pdf, g_out, g_pdf,
-                       (long long)count, (double)exponent, (int)(dt_aligned16(pdf) && dt_aligned16(g_out) && dt_aligned16(g_pdf)));
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+                       (long long)count, (double)exponent, (int)(s360_aligned(pdf, 16) && s360_aligned(g_out, 16) && s360_aligned(g_pdf, 16)));
+    return s360_launch_status();
 }

@@ -8,10 +8,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/s360.h"
+#include "s360_launch.h"  // the host-side rules (launch check, grid bound, alignment, workspace protocol) and S360_BLOCK
 
 #define S360_WAVE 64
-#define S360_BLOCK 256
+// S360_BLOCK, the 256 threads of a workgroup, is defined in s360_launch.h (the grid bound needs it)
 
 // Pixel footprint of one wave inside a 16x16 tile: SUB_W x (64 / SUB_W) pixels, four of them per tile.
 // 16 -> four 16x4 strips stacked vertically; 8 -> four 8x8 quadrants (fewer (splat, wave) overlaps for the
@@ -528,6 +528,77 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 }
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+
+// ---- sums over a workgroup of S360_BLOCK threads ------------------------------------------
+// The order of every such sum is fixed here, so a result is the same bits from run to run: lanes by a __shfl_down tree
+// (offsets 32 .. 1), lane 0 of each wave into the caller's LDS scratch sh[k][wave], one barrier, then the waves in index order,
+// starting from wave 0's value.  (Starting from 0.0 instead would differ only for a total of -0.0, which no caller can produce:
+// every thread's accumulator starts at +0.0, and a sum is -0.0 only when both terms are.)
+constexpr int BLOCK_WAVES = S360_BLOCK / S360_WAVE;
+
+// v[0..N) summed over the workgroup.  ALL = false: thread 0 alone returns with the totals, one barrier (a kernel that writes
+// one partial per workgroup).  ALL = true: every thread does, and a second barrier frees sh for the next call.
+template <bool ALL, int N, typename T>
+__device__ __forceinline__ void block_sum(T (&v)[N], T (*sh)[BLOCK_WAVES]) {
+#pragma unroll
+    for (int off = S360_WAVE / 2; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] += __shfl_down(v[k], off, S360_WAVE);
+    }
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) sh[k][threadIdx.x / S360_WAVE] = v[k];
+    }
+    __syncthreads();
+    if (ALL || threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            v[k] = sh[k][0];
+#pragma unroll
+            for (int w = 1; w < BLOCK_WAVES; ++w) v[k] += sh[k][w];
+        }
+    }
+    if (ALL) __syncthreads();
+}
+
+// The finishing sum over a row of partials: thread t brings v = slots t, t + S360_BLOCK, ... added in order; an LDS halving tree
+// over the S360_BLOCK entries of sh[k] leaves total k in sh[k][0], visible to every thread.  A caller that goes round again
+// puts a barrier between its read of sh[k][0] and the next call.
+template <int N, typename T>
+__device__ __forceinline__ void block_tree_step(T (*sh)[S360_BLOCK], int s) {
+    if ((int)threadIdx.x < s) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + s];
+    }
+}
+template <int N, typename T>
+__device__ __forceinline__ void block_tree_sum(const T (&v)[N], T (*sh)[S360_BLOCK]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) sh[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int s = S360_BLOCK / 2; s > 0; s >>= 1) {
+        block_tree_step<N>(sh, s);
+        __syncthreads();
+    }
+}
+template <int NA, typename TA, int NB, typename TB>
+__device__ __forceinline__ void block_tree_sum(const TA (&a)[NA], TA (*sa)[S360_BLOCK], const TB (&b)[NB], TB (*sb)[S360_BLOCK]) {
+#pragma unroll
+    for (int k = 0; k < NA; ++k) sa[k][threadIdx.x] = a[k];
+#pragma unroll
+    for (int k = 0; k < NB; ++k) sb[k][threadIdx.x] = b[k];
+    __syncthreads();
+    for (int s = S360_BLOCK / 2; s > 0; s >>= 1) {
+        block_tree_step<NA>(sa, s);
+        block_tree_step<NB>(sb, s);
+        __syncthreads();
+    }
+}
+
+// ---- MFMA 32x32 accumulator tiles ----------------------------------------------------------
+typedef float f32x16 __attribute__((ext_vector_type(16)));  // the 16 accumulator registers of a lane
+// row of the 32 x 32 accumulator tile that register r of a lane in half hf (= lane / 32) holds; the column is lane % 32
+__device__ __forceinline__ int mfma_acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
 
 // Single workgroup: order[] = work-unit ids in descending order of their work estimate (backward: unit =
 // tile*4 + quadrant, weight = the forward's replay length; forward: unit = tile, weight = list length)

@@ -230,7 +230,7 @@ extern "C" int s360_erp2cube_forward(const void* erp, const float* coor, const f
     else
         hipLaunchKernelGGL(k_erp2cube_fwd<uint8_t>, dim3(blocks), dim3(S360_BLOCK), 0, (hipStream_t)stream, (const uint8_t*)erp, coor,
                            scale, (uint8_t*)cube, batch, channels, equ_h, equ_w, face_w, mode, boundary, cm);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_erp2cube_backward(const float* d_cube, const float* coor, const float* scale, const int32_t* plan_offsets,
@@ -248,5 +248,5 @@ extern "C" int s360_erp2cube_backward(const float* d_cube, const float* coor, co
     const unsigned blocks = (unsigned)(((long long)equ_h * equ_w + S360_BLOCK - 1) / S360_BLOCK);
     hipLaunchKernelGGL(k_erp2cube_bwd, dim3(blocks, (unsigned)groups), dim3(S360_BLOCK), 0, (hipStream_t)stream, d_cube, coor, scale,
                        plan_offsets, plan_entries, d_erp, batch, channels, equ_h, equ_w, face_w, mode, boundary, cm);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

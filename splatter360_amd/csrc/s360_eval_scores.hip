@@ -16,9 +16,9 @@
 //
 // Determinism: thread t of a workgroup handles the quads (i * 256 + t) * 4 .. + 3 of the workgroup's 4096 elements, i = 0..3, in
 // that order, whether they are fetched as one 16-byte load or (unaligned / strided rows, the nearest lookup, the row's tail)
-// one by one; wave and workgroup sums run in a fixed order into the workgroup's own workspace slot, and the second stage sums
-// a row's slots in a fixed order.  No atomics: results are bit-identical from call to call, independent of the other rows of
-// the call and of the alignment of the inputs.
+// one by one; wave and workgroup sums run in a fixed order (block_sum's) into the workgroup's own workspace slot, and the
+// second stage sums a row's slots in a fixed order (block_tree_sum).  No atomics: results are bit-identical from call to call,
+// independent of the other rows of the call and of the alignment of the inputs.
 #include "s360_device.h"
 
 namespace s360 {
@@ -135,6 +135,8 @@ __global__ __launch_bounds__(S360_BLOCK) void k_depth_metrics_partials(DmArgs A,
         }
     }
 
+    // block_sum's order, written out: the per-wave scratch is one DmAcc per wave (sums and counts behind the one barrier);
+    // as two block_sum arrays the kernel's registers and LDS moved
 #pragma unroll
     for (int off = S360_WAVE / 2; off > 0; off >>= 1) {
 #pragma unroll
@@ -184,20 +186,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_depth_metrics_rows(const DmParti
 #pragma unroll
         for (int k = 0; k < DM_COUNTS; ++k) c[k] += p[j].cnt[k];
     }
-#pragma unroll
-    for (int k = 0; k < DM_TERMS; ++k) rsum[k][tid] = s[k];
-#pragma unroll
-    for (int k = 0; k < DM_COUNTS; ++k) rcnt[k][tid] = c[k];
-    __syncthreads();
-    for (int st = S360_BLOCK / 2; st > 0; st >>= 1) {
-        if (tid < st) {
-#pragma unroll
-            for (int k = 0; k < DM_TERMS; ++k) rsum[k][tid] += rsum[k][tid + st];
-#pragma unroll
-            for (int k = 0; k < DM_COUNTS; ++k) rcnt[k][tid] += rcnt[k][tid + st];
-        }
-        __syncthreads();
-    }
+    block_tree_sum(s, rsum, c, rcnt);
     if (tid == 0) {
         const unsigned long long nv = rcnt[DM_TERMS + DM_THRESH][0];
         for (int k = 0; k < DM_TERMS; ++k) {
@@ -238,7 +227,7 @@ __device__ __forceinline__ float clip01(float x) {           // NaN stays NaN (t
 template <bool VEC>
 __global__ __launch_bounds__(S360_BLOCK) void k_psnr_partials(const float* __restrict__ pred, const float* __restrict__ gt, long long m,
                                                               int blocks_per_image, double* __restrict__ partials) {
-    __shared__ double wsum[S360_BLOCK / S360_WAVE];
+    __shared__ double wsum[1][BLOCK_WAVES];
     const int tid = threadIdx.x;
     const int img = blockIdx.x / blocks_per_image, blk = blockIdx.x - img * blocks_per_image;
     const float* a = pred + (size_t)img * m;
@@ -268,41 +257,25 @@ __global__ __launch_bounds__(S360_BLOCK) void k_psnr_partials(const float* __res
             acc += (double)(d * d);
         }
     }
-#pragma unroll
-    for (int off = S360_WAVE / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, S360_WAVE);
-    if ((tid & (S360_WAVE - 1)) == 0) wsum[tid / S360_WAVE] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < S360_BLOCK / S360_WAVE; ++w) t += wsum[w];
-        partials[blockIdx.x] = t;
-    }
+    double s[1] = {acc};
+    block_sum<false>(s, wsum);
+    if (tid == 0) partials[blockIdx.x] = s[0];
 }
 
 // One workgroup per image: the mean (float64 -> float32), 0 -> 1e-10, -10 log10.
 __global__ __launch_bounds__(S360_BLOCK) void k_psnr_reduce(const double* __restrict__ partials, int blocks_per_image, double count,
                                                             float* __restrict__ out) {
-    __shared__ double red[S360_BLOCK];
+    __shared__ double red[1][S360_BLOCK];
     const int tid = threadIdx.x, img = blockIdx.x;
     const double* p = partials + (size_t)img * blocks_per_image;
-    double t = 0.0;
-    for (int j = tid; j < blocks_per_image; j += S360_BLOCK) t += p[j];
-    red[tid] = t;
-    __syncthreads();
-    for (int s = S360_BLOCK / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
+    double t[1] = {0.0};
+    for (int j = tid; j < blocks_per_image; j += S360_BLOCK) t[0] += p[j];
+    block_tree_sum(t, red);
     if (tid == 0) {
-        float mse = (float)(red[0] / count);
+        float mse = (float)(red[0][0] / count);
         if (mse == 0.0f) mse = 1e-10f;
         out[img] = (float)(-10.0 * log10((double)mse));
     }
-}
-
-static bool aligned(const void* p, size_t a) {
-    return ((uintptr_t)p & (a - 1)) == 0;
 }
 
 }  // namespace s360
@@ -320,14 +293,9 @@ extern "C" int s360_depth_metrics(const float* gt, const float* pred, const uint
         return S360_E_BADARG;
     const long long bpr = ((long long)n + ES_CHUNK - 1) / ES_CHUNK;
     const long long blocks = bpr * n_rows;
-    if (blocks > 0x7fffffffLL / S360_BLOCK) return S360_E_BADARG;   // grid of at most 2^31 work-items
-    const size_t need = (size_t)blocks * sizeof(DmPartial);
-    if (!workspace) {
-        *workspace_bytes = need;
-        return S360_OK;
-    }
-    if (!gt || !pred || !metrics_out || !valid_count || !aligned(workspace, 8)) return S360_E_BADARG;
-    if (*workspace_bytes < need) return S360_E_WORKSPACE;
+    if (!s360_grid_fits(blocks)) return S360_E_BADARG;
+    const int ws = s360_workspace(workspace, workspace_bytes, (size_t)blocks * sizeof(DmPartial), 8, gt && pred && metrics_out && valid_count);
+    if (ws != S360_WS_READY) return ws;
     DmArgs A;
     A.gt = gt, A.pred = pred, A.valid = valid;
     A.n = n, A.blocks_per_row = (int)bpr, A.rows_per_group = rows_per_group;
@@ -338,9 +306,9 @@ extern "C" int s360_depth_metrics(const float* gt, const float* pred, const uint
     A.scale_h = lookup ? (float)pred_height / (float)gt_height : 1.f;
     A.scale_w = lookup ? (float)pred_width / (float)gt_width : 1.f;
     // 16-byte loads need every row to start on a 16-byte boundary (4-byte for the validity plane)
-    bool vec = aligned(gt, 16) && gt_row_stride % 4 == 0 && gt_group_stride % 4 == 0;
-    if (!lookup) vec = vec && aligned(pred, 16) && pred_row_stride % 4 == 0 && pred_group_stride % 4 == 0;
-    if (valid) vec = vec && aligned(valid, 4) && valid_row_stride % 4 == 0;
+    bool vec = s360_aligned(gt, 16) && gt_row_stride % 4 == 0 && gt_group_stride % 4 == 0;
+    if (!lookup) vec = vec && s360_aligned(pred, 16) && pred_row_stride % 4 == 0 && pred_group_stride % 4 == 0;
+    if (valid) vec = vec && s360_aligned(valid, 4) && valid_row_stride % 4 == 0;
     DmPartial* partials = (DmPartial*)workspace;
     const hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)blocks), block(S360_BLOCK);
@@ -351,14 +319,14 @@ extern "C" int s360_depth_metrics(const float* gt, const float* pred, const uint
         if (vec) hipLaunchKernelGGL((k_depth_metrics_partials<true, false>), grid, block, 0, st, A, partials);
         else hipLaunchKernelGGL((k_depth_metrics_partials<false, false>), grid, block, 0, st, A, partials);
     }
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_depth_metrics_rows, dim3((unsigned)n_rows), block, 0, st, (const DmPartial*)partials, (int)bpr, (int)n_rows,
                        mult_a ? 100.0f : 1.0f, metrics_out, valid_count);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     if (scores_out) {
         hipLaunchKernelGGL(k_depth_metrics_scores, dim3(1), dim3(S360_WAVE), 0, st, (const float*)metrics_out, (const int*)valid_count,
                            (int)n_rows, scores_out);
-        if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+        S360_CHECK_LAUNCH();
     }
     return S360_OK;
 }
@@ -369,22 +337,17 @@ extern "C" int s360_psnr(const float* pred, const float* gt, int32_t n_images, i
     const long long m = (long long)channels * height * width;
     const long long bpi = (m + ES_CHUNK - 1) / ES_CHUNK;
     const long long blocks = bpi * n_images;
-    if (blocks > 0x7fffffffLL / S360_BLOCK) return S360_E_BADARG;
-    const size_t need = (size_t)blocks * sizeof(double);
-    if (!workspace) {
-        *workspace_bytes = need;
-        return S360_OK;
-    }
-    if (!pred || !gt || !psnr_out || !aligned(workspace, 8)) return S360_E_BADARG;
-    if (*workspace_bytes < need) return S360_E_WORKSPACE;
+    if (!s360_grid_fits(blocks)) return S360_E_BADARG;
+    const int ws = s360_workspace(workspace, workspace_bytes, (size_t)blocks * sizeof(double), 8, pred && gt && psnr_out);
+    if (ws != S360_WS_READY) return ws;
     double* partials = (double*)workspace;
     const hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)blocks), block(S360_BLOCK);
-    if (aligned(pred, 16) && aligned(gt, 16) && m % 4 == 0)
+    if (s360_aligned(pred, 16) && s360_aligned(gt, 16) && m % 4 == 0)
         hipLaunchKernelGGL((k_psnr_partials<true>), grid, block, 0, st, pred, gt, m, (int)bpi, partials);
     else
         hipLaunchKernelGGL((k_psnr_partials<false>), grid, block, 0, st, pred, gt, m, (int)bpi, partials);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_psnr_reduce, dim3((unsigned)n_images), block, 0, st, (const double*)partials, (int)bpi, (double)m, psnr_out);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

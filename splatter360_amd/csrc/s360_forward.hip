@@ -2747,20 +2747,6 @@ extern "C" int s360_layout(const S360Params* prm, S360Layout* out) {
     return S360_OK;
 }
 
-#ifdef S360_DEBUG_LAUNCH  /* compile-time diagnostic (-DS360_DEBUG_LAUNCH): no environment reads in the host path */
-#define S360_LAUNCH_DIAG(e) fprintf(stderr, "s360: %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__)
-#else
-#define S360_LAUNCH_DIAG(e) ((void)0)
-#endif
-#define S360_CHECK_LAUNCH()                                                                          \
-    do {                                                                                             \
-        hipError_t e_ = hipGetLastError();                                                           \
-        if (e_ != hipSuccess) {                                                                      \
-            S360_LAUNCH_DIAG(e_);                                                                    \
-            return S360_E_LAUNCH;                                                                    \
-        }                                                                                            \
-    } while (0)
-
 static int forward_impl(const S360Params* prm, const S360View* views, const float* means3D, const float* cov6,
                         const float* opacities, const float* shs, const float* colors_precomp, float* images,
                         float* depth_maps, int depth_mode, int32_t* radii, void* workspace, size_t workspace_bytes,

@@ -11,10 +11,10 @@
 // float64 library functions; none and ReLU evaluate no transcendental.
 //
 // Work split: a workgroup takes one chunk of GN_ROW_CHUNK floats of one (n, c) row — fixed, whatever the device — so the 16 slabs
-// of the depth U-Net's top level become 8192 workgroups.  Sums: a thread's own elements in index order, lanes by a fixed shuffle
-// tree, the four waves through LDS in wave order, one pair of doubles per chunk in the caller's scratch; the launch that needs a
-// slab's (or a channel's) total adds the pairs thread-strided in index order and reduces by the same tree.  No atomics, no
-// memset, no host read: bit-identical from run to run and across streams.
+// of the depth U-Net's top level become 8192 workgroups.  Sums: a thread's own elements in index order, then block_sum (lanes by
+// a fixed shuffle tree, the four waves through LDS in wave order), one pair of doubles per chunk in the caller's scratch; the
+// launch that needs a slab's (or a channel's) total adds the pairs thread-strided in index order and reduces by the same tree.
+// No atomics, no memset, no host read: bit-identical from run to run and across streams.
 //   forward   k_gn_stats: per chunk (mean, M2) from sums shifted by the chunk's first element (exact for a constant chunk, and a
 //             large mean over a small spread costs nothing).  k_gn_apply: mu = sum n_i mean_i / M, var = sum (M2_i + n_i (mean_i
 //             - mu)^2) / M (Chan's merge for all chunks at once: only non-negative terms), stats (mu, r) written by the slab's
@@ -69,29 +69,6 @@ __device__ __forceinline__ GNChunk gn_chunk(const GNArgs& a) {
     return c;
 }
 
-// a and b summed over the workgroup in a fixed order; every thread returns with the totals
-__device__ __forceinline__ void gn_block_sum2(double& a, double& b, double (*sh)[GN_WAVES]) {
-    const int lane = threadIdx.x & (S360_WAVE - 1), wave = threadIdx.x / S360_WAVE;
-#pragma unroll
-    for (int off = S360_WAVE / 2; off > 0; off >>= 1) {
-        a += __shfl_down(a, off, S360_WAVE);
-        b += __shfl_down(b, off, S360_WAVE);
-    }
-    if (lane == 0) {
-        sh[0][wave] = a;
-        sh[1][wave] = b;
-    }
-    __syncthreads();
-    a = sh[0][0];
-    b = sh[1][0];
-#pragma unroll
-    for (int w = 1; w < GN_WAVES; ++w) {
-        a += sh[0][w];
-        b += sh[1][w];
-    }
-    __syncthreads();
-}
-
 template <int ACT>
 __device__ __forceinline__ double gn_act(double z) {
     if constexpr (ACT == S360_GN_ACT_RELU) return z > 0.0 ? z : 0.0;
@@ -134,10 +111,11 @@ __global__ __launch_bounds__(S360_BLOCK) void k_gn_stats(GNArgs a, double* __res
         add(v.w);
     }
     if (tid < c.tail) add(p[c.head + 4 * c.nvec + tid]);
-    gn_block_sum2(s1, s2, sh);
+    double v[2] = {s1, s2};
+    block_sum<true>(v, sh);
     if (tid == 0) {
-        const double n = (double)c.len, m2 = s2 - s1 * (s1 / n);
-        partials[2 * (size_t)blockIdx.x] = shift + s1 / n;
+        const double n = (double)c.len, m2 = v[1] - v[0] * (v[0] / n);
+        partials[2 * (size_t)blockIdx.x] = shift + v[0] / n;
         partials[2 * (size_t)blockIdx.x + 1] = m2 > 0.0 ? m2 : 0.0;
     }
 }
@@ -153,17 +131,19 @@ __global__ __launch_bounds__(S360_BLOCK) void k_gn_apply(GNArgs a, const double*
     const double* __restrict__ slab = partials + 2 * (size_t)(n * a.C + (long long)g * a.cpg) * a.chunks;
     const int entries = a.cpg * a.chunks;
     const double M = (double)a.cpg * (double)a.S;
-    double ws = 0.0, unused = 0.0;
+    double ws = 0.0;
     for (int e = tid; e < entries; e += S360_BLOCK) ws += (double)gn_chunk_len(a, e % a.chunks) * slab[2 * (size_t)e];
-    gn_block_sum2(ws, unused, sh);
-    const double mu = ws / M;
+    double v[1] = {ws};
+    block_sum<true>(v, sh);
+    const double mu = v[0] / M;
     double m2 = 0.0;
     for (int e = tid; e < entries; e += S360_BLOCK) {
         const double d = slab[2 * (size_t)e] - mu;
         m2 += slab[2 * (size_t)e + 1] + (double)gn_chunk_len(a, e % a.chunks) * (d * d);
     }
-    gn_block_sum2(m2, unused, sh);
-    const double r = 1.0 / sqrt(m2 / M + a.eps);
+    v[0] = m2;
+    block_sum<true>(v, sh);
+    const double r = 1.0 / sqrt(v[0] / M + a.eps);
     if (tid == 0 && c.k == 0 && ch == g * a.cpg) {
         stats[2 * (size_t)(n * groups + g)] = mu;
         stats[2 * (size_t)(n * groups + g) + 1] = r;
@@ -225,10 +205,11 @@ __global__ __launch_bounds__(S360_BLOCK) void k_gn_bwd_sums(GNArgs a, const doub
         const int i = c.head + 4 * c.nvec + tid;
         add(p[i], q[i]);
     }
-    gn_block_sum2(sa, sb, sh);
+    double v[2] = {sa, sb};
+    block_sum<true>(v, sh);
     if (tid == 0) {
-        partials[2 * (size_t)blockIdx.x] = sa;
-        partials[2 * (size_t)blockIdx.x + 1] = sb;
+        partials[2 * (size_t)blockIdx.x] = v[0];
+        partials[2 * (size_t)blockIdx.x + 1] = v[1];
     }
 }
 
@@ -250,9 +231,10 @@ __global__ __launch_bounds__(S360_BLOCK) void k_gn_bwd_apply(GNArgs a, const dou
         m1 += ge * slab[2 * (size_t)e];
         m2 += ge * slab[2 * (size_t)e + 1];
     }
-    gn_block_sum2(m1, m2, sh);
-    m1 = m1 / M;
-    m2 = m2 / M;
+    double v[2] = {m1, m2};
+    block_sum<true>(v, sh);
+    m1 = v[0] / M;
+    m2 = v[1] / M;
     const double gam = a.weight ? (double)a.weight[ch] : 1.0, bet = a.bias ? (double)a.bias[ch] : 0.0;
     const float* __restrict__ p = a.x + c.off;
     const float* __restrict__ q = g_out + c.off;
@@ -288,10 +270,11 @@ __global__ __launch_bounds__(S360_BLOCK) void k_gn_bwd_params(const double* __re
         sa += partials[idx];
         sb += partials[idx + 1];
     }
-    gn_block_sum2(sa, sb, sh);
+    double v[2] = {sa, sb};
+    block_sum<true>(v, sh);
     if (tid == 0) {
-        if (g_bias) g_bias[ch] = (float)sa;
-        if (g_weight) g_weight[ch] = (float)sb;
+        if (g_bias) g_bias[ch] = (float)v[0];
+        if (g_weight) g_weight[ch] = (float)v[1];
     }
 }
 
@@ -308,7 +291,7 @@ bool gn_overlap(const float* a, const float* b, size_t count) {
 
 bool gn_aligned(std::initializer_list<const void*> ptrs) {
     for (const void* p : ptrs)
-        if (p && ((uintptr_t)p & 15u)) return false;
+        if (p && !s360_aligned(p, 16)) return false;
     return true;
 }
 
@@ -321,7 +304,7 @@ int gn_setup(const float* x, const float* weight, const float* bias, int32_t n, 
     if (!eps || !(*eps > 0.0) || activation < S360_GN_ACT_NONE || activation > S360_GN_ACT_GELU) return S360_E_BADARG;
     const long long chunks = (long long)((spatial + GN_ROW_CHUNK - 1) / GN_ROW_CHUNK);
     const long long rows = (long long)n * channels;
-    if (rows > 0x7fffffffLL || chunks > 0x7fffffffLL / rows) return S360_E_BADARG;       // 2^31 or more workgroups
+    if (rows > INT32_MAX || chunks > INT32_MAX / rows) return S360_E_BADARG;             // 2^31 or more workgroups
     *blocks = chunks * rows;
     *a = GNArgs{x, weight, bias, (long long)spatial, channels, channels / groups, (int)chunks, 0, *eps};
     return S360_OK;
@@ -354,7 +337,7 @@ extern "C" int s360_group_norm_forward(const float* x, const float* weight, cons
     const dim3 grid((unsigned)blocks), block(S360_BLOCK);
     a.vec = gn_aligned({x});
     hipLaunchKernelGGL(k_gn_stats, grid, block, 0, st, a, scratch);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     a.vec = gn_aligned({x, residual, out});
     if (residual) {
         switch (activation) {
@@ -371,7 +354,7 @@ extern "C" int s360_group_norm_forward(const float* x, const float* weight, cons
             default: hipLaunchKernelGGL((k_gn_apply<S360_GN_ACT_GELU, false>), grid, block, 0, st, a, (const double*)scratch, residual, stats, out); break;
         }
     }
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_group_norm_backward(const float* x, const float* weight, const float* bias, const double* stats, const float* g_out,
@@ -389,16 +372,16 @@ extern "C" int s360_group_norm_backward(const float* x, const float* weight, con
     const dim3 block(S360_BLOCK);
     a.vec = gn_aligned({x, g_out});
     GN_LAUNCH_ACT(k_gn_bwd_sums, a, stats, g_out, scratch)
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     if (g_x) {
         a.vec = gn_aligned({x, g_out, g_x});
         GN_LAUNCH_ACT(k_gn_bwd_apply, a, stats, g_out, (const double*)scratch, g_x)
-        if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+        S360_CHECK_LAUNCH();
     }
     if (g_weight || g_bias) {
         grid = dim3((unsigned)channels);
         hipLaunchKernelGGL(k_gn_bwd_params, grid, block, 0, st, (const double*)scratch, n, channels, a.chunks, g_weight, g_bias);
-        if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+        S360_CHECK_LAUNCH();
     }
     return S360_OK;
 }

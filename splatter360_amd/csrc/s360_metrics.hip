@@ -15,9 +15,9 @@
 // algorithm; the shift removes the cancellation of <x^2> - mx^2 on near-flat images (against C2 = 9e-4), which unshifted
 // float32 leaves at a few 1e-7 of the float64 score.
 //
-// Determinism: each workgroup writes the double sum of S over its tile (fixed lane / wave order) to its own workspace slot;
-// k_ssim_reduce sums the slots of an image in a fixed order.  No atomics: the result is bit-identical from call to call and
-// independent of the other images of the batch.
+// Determinism: each workgroup writes the double sum of S over its tile (block_sum: fixed lane / wave order) to its own
+// workspace slot; k_ssim_reduce sums the slots of an image in a fixed order (block_tree_sum).  No atomics: the result is
+// bit-identical from call to call and independent of the other images of the batch.
 #include "s360_device.h"
 
 namespace s360 {
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ssim_tiles(const float* __restri
                                                            int tiles_x, int tiles_per_plane, SsimWeights wt, double* __restrict__ partials) {
     __shared__ float sx[SS_HH * SS_HW], sy[SS_HH * SS_HW];
     __shared__ float hq[SS_NQ][SS_HH * SS_TW];
-    __shared__ double wsum[S360_BLOCK / S360_WAVE];
+    __shared__ double wsum[1][BLOCK_WAVES];
 
     const int tid = threadIdx.x;
     const int plane = blockIdx.x / tiles_per_plane, tile = blockIdx.x - plane * tiles_per_plane;
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ssim_tiles(const float* __restri
     __syncthreads();
 
     const float cov_norm = 121.0f / 120.0f, C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-    double acc = 0.0;
+    double acc[1] = {0.0};
     for (int i = tid; i < SS_TH * SS_TW; i += S360_BLOCK) {
         const int r = i / SS_TW, c = i - r * SS_TW;
         if (hy0 + SS_R + r >= H - SS_R || hx0 + SS_R + c >= W - SS_R) continue;
@@ -107,39 +107,26 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ssim_tiles(const float* __restri
         const float b1 = mx * mx + my * my + C1;
         const float a1 = b1 - d * d;                         // == 2 mx my + C1
         const float s = (a1 * (2.0f * vxy + C2)) / (b1 * (vx + vy + C2));
-        acc += (double)s;
+        acc[0] += (double)s;
     }
-#pragma unroll
-    for (int off = S360_WAVE / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, S360_WAVE);
-    if ((tid & (S360_WAVE - 1)) == 0) wsum[tid / S360_WAVE] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < S360_BLOCK / S360_WAVE; ++w) t += wsum[w];
-        partials[blockIdx.x] = t;
-    }
+    block_sum<false>(acc, wsum);
+    if (tid == 0) partials[blockIdx.x] = acc[0];
 }
 
 // One workgroup per image: per channel, thread t sums slots t, t + 256, ... in order, then a fixed tree; the channel mean
 // (float64, as skimage's crop(S).mean(dtype=float64)) and the mean over channels.
 __global__ __launch_bounds__(S360_BLOCK) void k_ssim_reduce(const double* __restrict__ partials, int channels, int tiles_per_plane,
                                                             double count, float* __restrict__ out) {
-    __shared__ double red[S360_BLOCK];
+    __shared__ double red[1][S360_BLOCK];
     const int tid = threadIdx.x, img = blockIdx.x;
     double total = 0.0;
     for (int c = 0; c < channels; ++c) {
         const double* p = partials + ((size_t)img * channels + c) * tiles_per_plane;
-        double t = 0.0;
-        for (int j = tid; j < tiles_per_plane; j += S360_BLOCK) t += p[j];
-        red[tid] = t;
-        __syncthreads();
-        for (int s = S360_BLOCK / 2; s > 0; s >>= 1) {
-            if (tid < s) red[tid] += red[tid + s];
-            __syncthreads();
-        }
-        total += red[0] / count;
-        __syncthreads();                                     // red[0] read by every thread before the next channel overwrites it
+        double t[1] = {0.0};
+        for (int j = tid; j < tiles_per_plane; j += S360_BLOCK) t[0] += p[j];
+        block_tree_sum(t, red);
+        total += red[0][0] / count;
+        __syncthreads();                                     // red[0][0] read by every thread before the next channel overwrites it
     }
     if (tid == 0) out[img] = (float)(total / channels);
 }
@@ -167,21 +154,16 @@ extern "C" int s360_ssim(const float* pred, const float* gt, int32_t n_images, i
     const int tiles_x = (width - 2 * SS_R + SS_TW - 1) / SS_TW, tiles_y = (height - 2 * SS_R + SS_TH - 1) / SS_TH;
     const long long tiles_per_plane = (long long)tiles_x * tiles_y;
     const long long blocks = (long long)n_images * channels * tiles_per_plane;
-    if (blocks > 0x7fffffffLL / S360_BLOCK) return S360_E_BADARG;   // grid of at most 2^31 work-items
-    const size_t need = (size_t)blocks * sizeof(double);
-    if (!workspace) {
-        *workspace_bytes = need;
-        return S360_OK;
-    }
-    if (!pred || !gt || !ssim_out || ((uintptr_t)workspace & 7u)) return S360_E_BADARG;
-    if (*workspace_bytes < need) return S360_E_WORKSPACE;
+    if (!s360_grid_fits(blocks)) return S360_E_BADARG;
+    const int ws = s360_workspace(workspace, workspace_bytes, (size_t)blocks * sizeof(double), 8, pred && gt && ssim_out);
+    if (ws != S360_WS_READY) return ws;
     double* partials = (double*)workspace;
     const hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_ssim_tiles, dim3((unsigned)blocks), dim3(S360_BLOCK), 0, st, pred, gt, (int)height, (int)width, tiles_x,
                        (int)tiles_per_plane, ssim_weights(), partials);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     const double count = (double)(height - 2 * SS_R) * (double)(width - 2 * SS_R);
     hipLaunchKernelGGL(k_ssim_reduce, dim3((unsigned)n_images), dim3(S360_BLOCK), 0, st, (const double*)partials, (int)channels,
                        (int)tiles_per_plane, count, ssim_out);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

@@ -35,8 +35,6 @@
 
 namespace s360 {
 
-typedef float qa_f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int QA_CH = 32;                                     // channels per head
 constexpr int QA_T = 32;                                      // rows of an MFMA tile
 constexpr int QA_WAVES = S360_BLOCK / S360_WAVE;              // waves that share the walk of one owner tile
@@ -65,9 +63,6 @@ __device__ __forceinline__ void qa_head(const QAArgs& a, int hd, int& qo, int& k
     if (a.order == 0) { qo = hd * 3 * QA_CH; ko = qo + QA_CH; vo = ko + QA_CH; }
     else { qo = hd * QA_CH; ko = a.heads * QA_CH + qo; vo = 2 * a.heads * QA_CH + qo; }
 }
-
-// row of the accumulator tile that register r of a lane of half hf holds
-__device__ __forceinline__ int qa_acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
 
 // channel rows hf, hf + 2, ... of one token (p: its channel row 0; null: zeros): the owner's row — channel 2 j + hf is the lane's
 // operand of MFMA step j — and a lane's share of a staged tile, whose token l31 it reads: a wave's load is two coalesced
@@ -109,14 +104,14 @@ __device__ __forceinline__ void qa_wave_sync() {
 // float64 adds of chunk c - 1 run under the MFMAs of chunk c.
 __device__ __forceinline__ void qa_dot(const float* tile, const float* b, double mul, double* out) {
     double sum[16];
-    qa_f32x16 prev;
+    f32x16 prev;
 #pragma unroll
     for (int r = 0; r < 16; ++r) sum[r] = 0.0, prev[r] = 0.f;
 #pragma unroll
     for (int c = 0; c < QA_CH / 8; ++c) {
         float z = 0.f;
         asm volatile("" : "+v"(z) : "v"(sum[15]));
-        qa_f32x16 t;
+        f32x16 t;
 #pragma unroll
         for (int r = 0; r < 16; ++r) t[r] = z;
 #pragma unroll
@@ -136,7 +131,7 @@ __device__ __forceinline__ void qa_dot(const float* tile, const float* b, double
 // one float32 fma chain from zero; the tiles are added in FLOAT64 (a float32 chain over all L tokens rounds at the size of the
 // running sum at every step: at L = 640 it missed the accuracy rule of the tests in out).
 __device__ __forceinline__ void qa_accumulate(const float* tile, const float* w, double* acc) {
-    qa_f32x16 t;
+    f32x16 t;
 #pragma unroll
     for (int r = 0; r < 16; ++r) t[r] = 0.f;
 #pragma unroll
@@ -205,14 +200,14 @@ __global__ __launch_bounds__(S360_BLOCK) void k_qa_forward(QAArgs a, float* __re
         float tmax = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            if (t * QA_T + qa_acc_row(r, hf) < a.L) tmax = fmaxf(tmax, (float)s[r]);
+            if (t * QA_T + mfma_acc_row(r, hf) < a.L) tmax = fmaxf(tmax, (float)s[r]);
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
         const float mnew = fmaxf(m, tmax);                    // finite: key 0 of every tile exists
         const float alpha = expf(m - mnew);                   // 0 at the wave's first tile
         float rs = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            p[r] = t * QA_T + qa_acc_row(r, hf) < a.L ? expf((float)(s[r] - (double)mnew)) : 0.f;
+            p[r] = t * QA_T + mfma_acc_row(r, hf) < a.L ? expf((float)(s[r] - (double)mnew)) : 0.f;
             rs += p[r];
         }
         rs += __shfl_xor(rs, 32);
@@ -241,7 +236,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_qa_forward(QAArgs a, float* __re
     }
     float* po = out + qa_token(a, w.bi, sq, a.heads * QA_CH) + (size_t)(w.hd * QA_CH) * a.T;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) po[(size_t)qa_acc_row(r, hf) * a.T] = (float)(o[r] / o[16]);
+    for (int r = 0; r < 16; ++r) po[(size_t)mfma_acc_row(r, hf) * a.T] = (float)(o[r] / o[16]);
     if (hf == 0) lse[((size_t)w.bi * a.heads + w.hd) * a.L + sq] = (double)mall + log(o[16]);
 }
 
@@ -297,7 +292,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_qa_backward_q(QAArgs a, const do
             qa_dot(ks + hf * QA_LD + l31, qB, a.inv_scale, s);                           // S^T / sqrt(ch)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const bool kvalid = t * QA_T + qa_acc_row(r, hf) < a.L;
+                const bool kvalid = t * QA_T + mfma_acc_row(r, hf) < a.L;
                 ds[r] = (kvalid && qvalid) ? expf((float)(s[r] - lq)) : 0.f;             // P^T
             }
             qa_dot(vs + hf * QA_LD + l31, gB, 1.0, dp);                                  // dP^T = V^T dO
@@ -332,7 +327,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_qa_backward_q(QAArgs a, const do
         double x = 0.0;
 #pragma unroll
         for (int u = 0; u < QA_WAVES; ++u) x += qa_handed(s_raw, u, lane, r);
-        pg[(size_t)qa_acc_row(r, hf) * a.T] = (float)(x * a.inv_scale);
+        pg[(size_t)mfma_acc_row(r, hf) * a.T] = (float)(x * a.inv_scale);
     }
 }
 
@@ -387,13 +382,13 @@ __global__ __launch_bounds__(S360_BLOCK) void k_qa_backward_kv(QAArgs a, const d
         qa_dot(qs + hf * QA_LD + l31, kB, a.inv_scale, s);    // S / sqrt(ch): rows = queries, lane = key; the forward's chain, bit for bit
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int qq = qa_acc_row(r, hf);
+            const int qq = mfma_acc_row(r, hf);
             p[r] = (kvalid && t * QA_T + qq < a.L) ? expf((float)(s[r] - sl[qq])) : 0.f;
         }
         qa_accumulate(gs + l31 * QA_LD + 4 * hf, p, dv);      // g_v^T += dO P
         qa_dot(gs + hf * QA_LD + l31, vB, 1.0, s);            // dP = dO^T V
 #pragma unroll
-        for (int r = 0; r < 16; ++r) p[r] *= (float)(s[r] - sd[qa_acc_row(r, hf)]);      // dS = P (dP - Delta)
+        for (int r = 0; r < 16; ++r) p[r] *= (float)(s[r] - sd[mfma_acc_row(r, hf)]);      // dS = P (dP - Delta)
         qa_accumulate(qs + l31 * QA_LD + 4 * hf, p, dk);      // g_k^T += Q dS
         qa_wave_sync();
     }
@@ -410,7 +405,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_qa_backward_kv(QAArgs a, const d
                 double x = 0.0;
 #pragma unroll
                 for (int u = 0; u < QA_WAVES; ++u) x += qa_handed(s_raw, u, lane, r);
-                const size_t c = (size_t)qa_acc_row(r, hf) * a.T;
+                const size_t c = (size_t)mfma_acc_row(r, hf) * a.T;
                 if (part == 0) pv[c] = (float)x;
                 else pk[c] = (float)(x * a.inv_scale);
             }
@@ -446,7 +441,7 @@ extern "C" int s360_qkv_attention_forward(const float* qkv, int32_t rows, int32_
     if (rc != S360_OK) return rc;
     if (!out || !lse) return S360_E_BADARG;
     hipLaunchKernelGGL(k_qa_forward, dim3(qa_grid(a)), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, out, lse);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_qkv_attention_backward(const float* qkv, const double* lse, const float* g_out, int32_t rows, int32_t views,
@@ -460,7 +455,7 @@ extern "C" int s360_qkv_attention_backward(const float* qkv, const double* lse, 
     const dim3 grid(qa_grid(a)), block(S360_BLOCK);
     // the query-owned pass first: it writes Delta for the key-owned one
     hipLaunchKernelGGL(k_qa_backward_q, grid, block, 0, st, a, lse, g_out, delta, g_qkv);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_qa_backward_kv, grid, block, 0, st, a, lse, delta, g_out, g_qkv);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

@@ -340,7 +340,7 @@ extern "C" int s360_cube2erp_forward(const float* faces, const float* grid, floa
     ProfScope ps(PS_STITCH, (hipStream_t)stream);
     hipLaunchKernelGGL(k_cube2erp_fwd, dim3((unsigned)((n + S360_BLOCK - 1) / S360_BLOCK)), dim3(S360_BLOCK), 0,
                        (hipStream_t)stream, faces, grid, erp, channels, face_w, equ_h, equ_w, fm);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_cube2erp_backward(const float* d_erp, const float* grid, const int32_t* plan_offsets,
@@ -359,7 +359,7 @@ extern "C" int s360_cube2erp_backward(const float* d_erp, const float* grid, con
     ProfScope ps(PS_STITCH_BWD, (hipStream_t)stream);
     hipLaunchKernelGGL(k_cube2erp_bwd, dim3((unsigned)((texels + S360_BLOCK - 1) / S360_BLOCK), (unsigned)channels), dim3(S360_BLOCK),
                        0, (hipStream_t)stream, d_erp, grid, plan_offsets, plan_entries, d_faces, channels, face_w, equ_h, equ_w, fm);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_depth_to_distance_forward(const float* depth, const float* fxfycxcy, float* distance, int32_t n, int32_t height,
@@ -375,7 +375,7 @@ extern "C" int s360_depth_to_distance_forward(const float* depth, const float* f
     else
         hipLaunchKernelGGL(k_depth2dist_fwd<S360_D2D_PIXEL>, dim3((unsigned)blocks), dim3(S360_BLOCK), 0, (hipStream_t)stream, depth,
                            fxfycxcy, distance, total, height, width);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_depth_to_distance_backward(const float* d_distance, const float* depth, const float* fxfycxcy, float* d_depth,
@@ -391,7 +391,7 @@ extern "C" int s360_depth_to_distance_backward(const float* d_distance, const fl
     else
         hipLaunchKernelGGL(k_depth2dist_bwd<S360_D2D_PIXEL>, dim3((unsigned)blocks), dim3(S360_BLOCK), 0, (hipStream_t)stream,
                            d_distance, depth, fxfycxcy, d_depth, total, height, width);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 // sizes, convention and the int32 limits shared by the fused stitch's two entry points (panoramas go in gridDim.y)
@@ -421,7 +421,7 @@ extern "C" int s360_cube2erp_distance_forward(const float* depth_faces, const fl
     else
         hipLaunchKernelGGL(k_cube2erp_dist_fwd<S360_D2D_PIXEL>, blocks, dim3(S360_BLOCK), 0, (hipStream_t)stream, depth_faces, fxfycxcy,
                            grid, erp, face_w, equ_h, equ_w, fm, ns);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_cube2erp_distance_backward(const float* d_erp, const float* depth_faces, const float* fxfycxcy, const float* grid,
@@ -442,7 +442,7 @@ extern "C" int s360_cube2erp_distance_backward(const float* d_erp, const float* 
     else
         hipLaunchKernelGGL(k_cube2erp_dist_bwd<S360_D2D_PIXEL>, blocks, dim3(S360_BLOCK), 0, (hipStream_t)stream, d_erp, depth_faces,
                            fxfycxcy, grid, plan_offsets, plan_entries, d_depth_faces, face_w, equ_h, equ_w, fm);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 // ---------------------------------------------------------------------------- profiler

@@ -32,8 +32,6 @@
 
 namespace s360 {
 
-typedef float ff_f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int FF_C = 128;                                     // d_model
 constexpr int FF_H = 1024;                                    // hidden width
 constexpr int FF_X = 2 * FF_C;                                // width of the concatenation
@@ -62,9 +60,6 @@ struct FFArgs {
     double eps;
 };
 
-// row of the accumulator tile that register r of a lane of half hf holds
-__device__ __forceinline__ int ff_acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
-
 __device__ __forceinline__ float ff_gelu(float v) { return 0.5f * v * erfcf(-v * 0.70710678118654752440f); }
 __device__ __forceinline__ float ff_gelu_grad(float v) {
     return 0.5f * erfcf(-v * 0.70710678118654752440f) + v * 0.39894228040143267794f * expf(-0.5f * v * v);
@@ -86,14 +81,14 @@ __device__ __forceinline__ double ff_sum32(double v) {        // over the 32 lan
 template <int STEPS, int CHAIN, class B>
 __device__ __forceinline__ void ff_dot(const float* a, int ks, B b, float* out) {
     double sum[16];
-    ff_f32x16 prev;
+    f32x16 prev;
 #pragma unroll
     for (int r = 0; r < 16; ++r) sum[r] = 0.0, prev[r] = 0.f;
 #pragma unroll
     for (int c = 0; c < STEPS / CHAIN; ++c) {
         float zero = 0.f;
         asm volatile("" : "+v"(zero) : "v"(sum[15]));
-        ff_f32x16 t;
+        f32x16 t;
 #pragma unroll
         for (int r = 0; r < 16; ++r) t[r] = zero;
 #pragma unroll
@@ -119,7 +114,7 @@ __device__ __forceinline__ void ff_dot_lds(const float* a, int ks, const float* 
     for (int r = 0; r < 16; ++r) sum[r] = 0.0;
 #pragma unroll 1
     for (int c = 0; c < STEPS / FF_LDS_CHAIN; ++c) {
-        ff_f32x16 t;
+        f32x16 t;
 #pragma unroll
         for (int r = 0; r < 16; ++r) t[r] = 0.f;
 #pragma unroll
@@ -136,7 +131,7 @@ __device__ __forceinline__ void ff_dot_lds(const float* a, int ks, const float* 
 
 // t[row][lane] += sum over the 32 rows k of a tile w held register by register of A[row][k] w[k][lane]; a points at (k = 4 hf,
 // row l31) of an LDS image with k-stride ld
-__device__ __forceinline__ ff_f32x16 ff_fold(const float* a, int ld, const float* w, ff_f32x16 t) {
+__device__ __forceinline__ f32x16 ff_fold(const float* a, int ld, const float* w, f32x16 t) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) t = __builtin_amdgcn_mfma_f32_32x32x2f32(a[((r & 3) + 8 * (r >> 2)) * ld], w[r], t, 0, 0, 0);
     return t;
@@ -204,7 +199,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ff_forward(FFArgs a, float* __re
         for (int r = 0; r < 16; ++r) h[r] = ff_gelu(h[r]);
 #pragma unroll
         for (int ct = 0; ct < FF_C / FF_T; ++ct) {            // z^T += W2c h^T, two hidden units (one per lane half) a step
-            ff_f32x16 t;
+            f32x16 t;
 #pragma unroll
             for (int r = 0; r < 16; ++r) t[r] = 0.f;
             t = ff_fold(s_w2 + (ct * FF_T + l31) * FF_LD2 + 4 * hf, 1, h, t);
@@ -212,7 +207,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ff_forward(FFArgs a, float* __re
             for (int r = 0; r < 16; ++r) zacc[ct][r] += (double)t[r];
         }
     }
-    // norm2 over the float32 z, the residual, the writes: register r of tile ct is channel 32 ct + ff_acc_row(r, hf)
+    // norm2 over the float32 z, the residual, the writes: register r of tile ct is channel 32 ct + mfma_acc_row(r, hf)
     float zf[FF_C / FF_T][16];
     double sum = 0.0, sq = 0.0;
 #pragma unroll
@@ -297,7 +292,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ff_backward_tokens(FFArgs a, con
                 if (l31 == 0) s_wave[wave][2 * FF_C + c] = pw, s_wave[wave][3 * FF_C + c] = pb;
             }
         }
-        ff_f32x16 dx[FF_X / FF_T];                            // dX^T: tile ct, register r is channel 32 ct + ff_acc_row(r, hf) of the lane's token
+        f32x16 dx[FF_X / FF_T];                            // dX^T: tile ct, register r is channel 32 ct + mfma_acc_row(r, hf) of the lane's token
 #pragma unroll
         for (int ct = 0; ct < FF_X / FF_T; ++ct)
 #pragma unroll
@@ -313,7 +308,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ff_backward_tokens(FFArgs a, con
             for (int r = 0; r < 16; ++r) dh[r] *= ff_gelu_grad(pre[r]);
 #pragma unroll
             for (int ct = 0; ct < FF_X / FF_T; ++ct) {        // one chain per chunk from zero, the chunks added in float32 (see the header)
-                ff_f32x16 t;
+                f32x16 t;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) t[r] = 0.f;
                 dx[ct] += ff_fold(s_w1 + 4 * hf * FF_LD1 + ct * FF_T + l31, FF_LD1, dh, t);
@@ -337,7 +332,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ff_backward_tokens(FFArgs a, con
             for (int ct = 0; ct < FF_C / FF_T; ++ct)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int c = ct * FF_T + ff_acc_row(r, hf);
+                    const int c = ct * FF_T + mfma_acc_row(r, hf);
                     const double gy = (double)dx[FF_C / FF_T + ct][r] * (double)a.n1w[c];
                     const double xh = valid ? ((double)a.m[row + c] - mean1) * rstd1 : 0.0;
                     s1 += gy, s2 += gy * xh;
@@ -348,7 +343,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ff_backward_tokens(FFArgs a, con
             for (int ct = 0; ct < FF_C / FF_T; ++ct)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int c = ct * FF_T + ff_acc_row(r, hf);
+                    const int c = ct * FF_T + mfma_acc_row(r, hf);
                     const double g = (double)dx[FF_C / FF_T + ct][r];
                     const double xh = valid ? ((double)a.m[row + c] - mean1) * rstd1 : 0.0;
                     if (valid) g_m[row + c] = (float)(rstd1 * (g * (double)a.n1w[c] - s1 - xh * s2));
@@ -410,7 +405,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ff_backward_weights(FFArgs a, co
     float w1r[FF_X / 2];
 #pragma unroll
     for (int s = 0; s < FF_X / 2; ++s) w1r[s] = a.w1[(size_t)(j0 + l31) * FF_X + 2 * s + hf];
-    ff_f32x16 gw1[FF_X / FF_T], gw2[FF_C / FF_T];             // g_W1^T, g_W2: rows = channels, lane = hidden unit
+    f32x16 gw1[FF_X / FF_T], gw2[FF_C / FF_T];             // g_W1^T, g_W2: rows = channels, lane = hidden unit
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
 #pragma unroll
@@ -460,9 +455,9 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ff_backward_weights(FFArgs a, co
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
 #pragma unroll
-        for (int ct = 0; ct < FF_X / FF_T; ++ct) q1[ct * FF_T + ff_acc_row(r, hf)] = gw1[ct][r];
+        for (int ct = 0; ct < FF_X / FF_T; ++ct) q1[ct * FF_T + mfma_acc_row(r, hf)] = gw1[ct][r];
 #pragma unroll
-        for (int ct = 0; ct < FF_C / FF_T; ++ct) q2[(size_t)(ct * FF_T + ff_acc_row(r, hf)) * FF_H] = gw2[ct][r];
+        for (int ct = 0; ct < FF_C / FF_T; ++ct) q2[(size_t)(ct * FF_T + mfma_acc_row(r, hf)) * FF_H] = gw2[ct][r];
     }
 }
 
@@ -548,8 +543,6 @@ static int ff_token_wgs(int64_t T) { return (int)min((int64_t)FF_TOKEN_WGS, (T +
 static int ff_row_wgs(int64_t T) { return (int)min((int64_t)FF_ROW_WGS, (T + FF_ROWS - 1) / FF_ROWS); }
 static size_t ff_partial_floats(int64_t T) { return (size_t)ff_chunks(T) * (FF_H * FF_X + FF_C * FF_H); }
 
-static bool ff_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 static int ff_sizes(int32_t tokens, int32_t channels, int32_t hidden) {
     if (tokens < 1 || channels < 1 || hidden < 1) return S360_E_BADARG;
     if (channels != FF_C || hidden != FF_H) return S360_E_UNSUPPORTED;
@@ -573,13 +566,13 @@ extern "C" int s360_ffn_tail_forward(const float* source, const float* m, const 
                                      int32_t channels, int32_t hidden, const double* eps, float* out, float* z, double* stats, void* stream) {
     const void* in[] = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias};
     for (const void* p : in)
-        if (!p || !ff_aligned(p) || p == out || p == z || p == stats) return S360_E_BADARG;
-    if (!eps || !(*eps > 0.0) || !out || !z || !stats || out == z || !ff_aligned(out) || !ff_aligned(z)) return S360_E_BADARG;
+        if (!p || !s360_aligned(p, 16) || p == out || p == z || p == stats) return S360_E_BADARG;
+    if (!eps || !(*eps > 0.0) || !out || !z || !stats || out == z || !s360_aligned(out, 16) || !s360_aligned(z, 16)) return S360_E_BADARG;
     const int rc = ff_sizes(tokens, channels, hidden);
     if (rc != S360_OK) return rc;
     const FFArgs a = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, tokens, *eps};
     hipLaunchKernelGGL(k_ff_forward, dim3((tokens + FF_TM - 1) / FF_TM), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, out, z, stats);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_ffn_tail_backward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias,
@@ -591,12 +584,12 @@ extern "C" int s360_ffn_tail_backward(const float* source, const float* m, const
     const void* in[] = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, z, stats, g_out};
     void* outs[] = {g_source, g_m, g_w1, g_w2, g_norm1_weight, g_norm1_bias, g_norm2_weight, g_norm2_bias, scratch};
     for (const void* o : outs) {
-        if (!o || !ff_aligned(o)) return S360_E_BADARG;
+        if (!o || !s360_aligned(o, 16)) return S360_E_BADARG;
         for (const void* p : in)
             if (p == o) return S360_E_BADARG;
     }
     for (const void* p : in)
-        if (!p || !ff_aligned(p)) return S360_E_BADARG;
+        if (!p || !s360_aligned(p, 16)) return S360_E_BADARG;
     for (int i = 0; i < 9; ++i)
         for (int j = i + 1; j < 9; ++j)
             if (outs[i] == outs[j]) return S360_E_BADARG;
@@ -611,28 +604,28 @@ extern "C" int s360_ffn_tail_backward(const float* source, const float* m, const
     float* p_w2 = p_w1 + (size_t)chunks * FF_H * FF_X;
     double* ln_part = reinterpret_cast<double*>(p_w2 + (size_t)chunks * FF_C * FF_H);
     hipLaunchKernelGGL(k_ff_backward_tokens, dim3(wgs), dim3(S360_BLOCK), 0, st, a, z, stats, g_out, g_source, g_m, ln_part);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_ff_backward_weights, dim3(FF_H / (FF_T * FF_WAVES), chunks), dim3(S360_BLOCK), 0, st, a, z, stats, g_out,
                        ff_chunk_tokens(tokens), p_w1, p_w2);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     const int nw1 = FF_H * FF_X, nw2 = FF_C * FF_H, nln = 4 * FF_C;
     const FFLnOut lo = {{g_norm1_weight, g_norm1_bias, g_norm2_weight, g_norm2_bias}};
     hipLaunchKernelGGL(k_ff_reduce, dim3((nw1 + nw2 + nln + S360_BLOCK - 1) / S360_BLOCK), dim3(S360_BLOCK), 0, st, p_w1, p_w2, chunks, nw1,
                        nw2, g_w1, g_w2, ln_part, wgs, nln, lo);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_layer_norm_residual_forward(const float* x, const float* weight, const float* bias, const float* residual, int32_t tokens,
                                                 int32_t channels, const double* eps, float* out, double* stats, void* stream) {
     const void* in[] = {x, weight, bias, residual};
     for (const void* p : in)
-        if (!p || !ff_aligned(p) || p == out || p == stats) return S360_E_BADARG;
-    if (!eps || !(*eps > 0.0) || !out || !stats || !ff_aligned(out)) return S360_E_BADARG;
+        if (!p || !s360_aligned(p, 16) || p == out || p == stats) return S360_E_BADARG;
+    if (!eps || !(*eps > 0.0) || !out || !stats || !s360_aligned(out, 16)) return S360_E_BADARG;
     const int rc = ff_sizes(tokens, channels, FF_H);
     if (rc != S360_OK) return rc;
     hipLaunchKernelGGL(k_ff_norm_residual_forward, dim3((tokens + FF_ROWS - 1) / FF_ROWS), dim3(S360_BLOCK), 0, (hipStream_t)stream, x, weight,
                        bias, residual, tokens, *eps, out, stats);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_layer_norm_residual_backward(const float* x, const float* weight, const double* stats, const float* g_out, int32_t tokens,
@@ -641,9 +634,9 @@ extern "C" int s360_layer_norm_residual_backward(const float* x, const float* we
     const void* in[] = {x, weight, stats, g_out};
     void* outs[] = {g_x, g_residual, g_weight, g_bias, scratch};
     for (const void* o : outs) {
-        if (!o || !ff_aligned(o)) return S360_E_BADARG;
+        if (!o || !s360_aligned(o, 16)) return S360_E_BADARG;
         for (const void* p : in)
-            if (!p || !ff_aligned(p) || p == o) return S360_E_BADARG;
+            if (!p || !s360_aligned(p, 16) || p == o) return S360_E_BADARG;
     }
     for (int i = 0; i < 5; ++i)
         for (int j = i + 1; j < 5; ++j)
@@ -655,10 +648,10 @@ extern "C" int s360_layer_norm_residual_backward(const float* x, const float* we
     const int wgs = ff_row_wgs(tokens);
     double* ln_part = static_cast<double*>(scratch);
     hipLaunchKernelGGL(k_ff_norm_residual_backward, dim3(wgs), dim3(S360_BLOCK), 0, st, x, weight, stats, g_out, tokens, g_x, g_residual, ln_part);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     const int nln = 2 * FF_C;
     const FFLnOut lo = {{g_weight, g_bias, nullptr, nullptr}};
     hipLaunchKernelGGL(k_ff_reduce, dim3((nln + S360_BLOCK - 1) / S360_BLOCK), dim3(S360_BLOCK), 0, st, nullptr, nullptr, 0, 0, 0, nullptr,
                        nullptr, ln_part, wgs, nln, lo);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

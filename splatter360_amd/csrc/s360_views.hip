@@ -7,10 +7,7 @@
 // The arithmetic follows the reference's formulas in the reference's order; the two inverses are Gauss-Jordan
 // eliminations with partial pivoting instead of LAPACK's LU, so results agree with the torch glue to a few
 // ulp (pinned by tests/test_gpu_views.py), not bit for bit — the drop-in render_cuda keeps the torch glue.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/s360.h"
+#include "s360_launch.h"
 
 namespace s360 {
 
@@ -158,5 +155,5 @@ extern "C" int s360_pack_views(const float* extrinsics, const float* intrinsics,
     if (n_views == 0) return S360_OK;
     hipLaunchKernelGGL(s360::k_pack_views, dim3((n_views + 63) / 64), dim3(64), 0, (hipStream_t)stream, extrinsics, intrinsics,
                        near_planes, far_planes, background, background_per_view ? 3 : 0, n_views, scale_invariant, views_out);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

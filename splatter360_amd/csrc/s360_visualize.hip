@@ -510,7 +510,7 @@ static size_t vs_align(size_t x) {
 
 static bool vs_grid(long long total, unsigned& blocks) {     // a thread per 4 elements
     const long long b = (total + 4LL * S360_BLOCK - 1) / (4LL * S360_BLOCK);
-    if (b < 1 || b > 0x7fffffffLL / S360_BLOCK) return false;
+    if (b < 1 || !s360_grid_fits(b)) return false;
     blocks = (unsigned)b;
     return true;
 }
@@ -532,7 +532,7 @@ extern "C" int s360_depth_colormap(const float* depth, int32_t n_maps, int32_t h
     wgs = wgs > VS_MAX_WGS ? VS_MAX_WGS : wgs;
     const long long per = (hw + wgs - 1) / wgs;
     const long long blocks = wgs * n_maps;
-    if (blocks > 0x7fffffffLL / S360_BLOCK) return S360_E_BADARG;
+    if (!s360_grid_fits(blocks)) return S360_E_BADARG;
     // workspace: counts | state after digit 1 | state after digit 2 | records | partials of digit 1 | digit 2 | digit 3
     const size_t o_counts = 0;
     const size_t o_state1 = o_counts + vs_align((size_t)blocks * sizeof(VsCounts));
@@ -542,12 +542,8 @@ extern "C" int s360_depth_colormap(const float* depth, int32_t n_maps, int32_t h
     const size_t o_part2 = o_part1 + vs_align((size_t)blocks * VS_BINS * sizeof(unsigned));
     const size_t o_part3 = o_part2 + vs_align((size_t)blocks * VS_RANKS * VS_BINS * sizeof(unsigned));
     const size_t need = o_part3 + vs_align((size_t)blocks * VS_RANKS * (VS_BINS / 2) * sizeof(unsigned));
-    if (!workspace) {
-        *workspace_bytes = need;
-        return S360_OK;
-    }
-    if (!depth || (!rgb_out && !bytes_out && !range_out) || ((uintptr_t)workspace & 15) != 0) return S360_E_BADARG;
-    if (*workspace_bytes < need) return S360_E_WORKSPACE;
+    const int wsr = s360_workspace(workspace, workspace_bytes, need, 16, depth && (rgb_out || bytes_out || range_out));
+    if (wsr != S360_WS_READY) return wsr;
     char* ws = (char*)workspace;
     VsCounts* counts = (VsCounts*)(ws + o_counts);
     VsState* state1 = (VsState*)(ws + o_state1);
@@ -561,19 +557,19 @@ extern "C" int s360_depth_colormap(const float* depth, int32_t n_maps, int32_t h
     const hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)blocks), block(S360_BLOCK);
     hipLaunchKernelGGL(k_vs_digit1, grid, block, 0, st, A, counts, part1);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     hipLaunchKernelGGL((k_vs_digit<2>), grid, block, 0, st, A, (const VsCounts*)counts, (const VsState*)nullptr, (const unsigned*)part1, state1, part2);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     hipLaunchKernelGGL((k_vs_digit<3>), grid, block, 0, st, A, (const VsCounts*)counts, (const VsState*)state1, (const unsigned*)part2, state2, part3);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_vs_record, dim3((unsigned)n_maps), block, 0, st, (int)wgs, (unsigned)hw, (const VsState*)state2, (const unsigned*)part3,
                        records, range_out);
-    if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+    S360_CHECK_LAUNCH();
     if (rgb_out || bytes_out) {
         VsOut o;
         o.f32 = rgb_out, o.u8 = bytes_out, o.map_id = 0, o.byte_rule = 0, o.f32_first = 1, o.u8_first = 0, o.plane = hw;
         hipLaunchKernelGGL(k_vs_depth_colour, dim3(colour_blocks), block, 0, st, depth, map_stride, hw, total, (const VsRecord*)records, o);
-        if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+        S360_CHECK_LAUNCH();
     }
     return S360_OK;
 }
@@ -588,7 +584,7 @@ extern "C" int s360_colorize(const float* x, size_t count, size_t plane, int32_t
     o.f32 = rgb_out, o.u8 = bytes_out, o.map_id = color_map, o.byte_rule = 0;
     o.f32_first = o.u8_first = channels_first ? 1 : 0, o.plane = channels_first ? (long long)plane : 1;
     hipLaunchKernelGGL(k_vs_colorize, dim3(blocks), dim3(S360_BLOCK), 0, (hipStream_t)stream, x, (long long)count, o);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_prep_image(const float* image, int32_t batch, int32_t channels, int32_t height, int32_t width, uint8_t* bytes_out,
@@ -602,7 +598,7 @@ extern "C" int s360_prep_image(const float* image, int32_t batch, int32_t channe
         hipLaunchKernelGGL((k_vs_prep_image<4>), dim3(blocks), dim3(S360_BLOCK), 0, st, image, (int)batch, (int)channels, (int)height, (int)width, bytes_out);
     else
         hipLaunchKernelGGL((k_vs_prep_image<3>), dim3(blocks), dim3(S360_BLOCK), 0, st, image, (int)batch, (int)channels, (int)height, (int)width, bytes_out);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 extern "C" int s360_error_map(const float* a, const float* b, int32_t height, int32_t width, uint8_t* bytes_out, void* stream) {
@@ -613,5 +609,5 @@ extern "C" int s360_error_map(const float* a, const float* b, int32_t height, in
     VsOut o;
     o.f32 = nullptr, o.u8 = bytes_out, o.map_id = 1, o.byte_rule = 1, o.f32_first = 0, o.u8_first = 0, o.plane = 1;
     hipLaunchKernelGGL(k_vs_error_map, dim3(blocks), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, b, hw, o);
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }

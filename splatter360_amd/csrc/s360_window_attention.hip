@@ -31,8 +31,6 @@
 
 namespace s360 {
 
-typedef float wa_f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int WA_T = 32;                                      // rows of an MFMA tile
 constexpr int WA_WAVES = S360_BLOCK / S360_WAVE;              // owner tiles of a workgroup
 constexpr int WA_ROWS = WA_T * WA_WAVES;
@@ -110,9 +108,6 @@ __device__ __forceinline__ void wa_store_c(float* p, const float* x) {
     }
 }
 
-// row of the accumulator tile that register r of a lane of half hf holds
-__device__ __forceinline__ int wa_acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
-
 // tile = float32(mul * sum over the lane's HC channels of A-row x B-row) (the two halves of a wave cover all C channels).  The
 // sum runs in chunks of WA_CHUNK MFMA steps (2 WA_CHUNK channels): a chunk is one float32 fma chain from zero, whose partial
 // sums stay small, and the chunks are added in FLOAT64; the result is rounded once.  One chain over all C channels rounds at
@@ -124,15 +119,15 @@ __device__ __forceinline__ float4 wa_ld4(const float* p, int chunk) {
     return p ? reinterpret_cast<const float4*>(p)[chunk] : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-__device__ __forceinline__ wa_f32x16 wa_round(const double* sum, double mul) {
-    wa_f32x16 out;
+__device__ __forceinline__ f32x16 wa_round(const double* sum, double mul) {
+    f32x16 out;
 #pragma unroll
     for (int r = 0; r < 16; ++r) out[r] = (float)(sum[r] * mul);
     return out;
 }
 
-__device__ __forceinline__ wa_f32x16 wa_chunk(const float4& x, const float4& y, float z) {
-    wa_f32x16 t;
+__device__ __forceinline__ f32x16 wa_chunk(const float4& x, const float4& y, float z) {
+    f32x16 t;
 #pragma unroll
     for (int r = 0; r < 16; ++r) t[r] = z;
     t = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x, y.x, t, 0, 0, 0);
@@ -148,17 +143,17 @@ __device__ __forceinline__ wa_f32x16 wa_chunk(const float4& x, const float4& y, 
 // they stand (chunks up to c - 2 added): at most three tiles are live, and the float64 adds of chunk c - 1 run under the
 // MFMAs of chunk c.
 template <int HC>
-__device__ __forceinline__ wa_f32x16 wa_dot(const float* arow, const float* b, double mul) {
+__device__ __forceinline__ f32x16 wa_dot(const float* arow, const float* b, double mul) {
     static_assert(WA_CHUNK == 4 && HC % WA_CHUNK == 0, "a chunk is one dwordx4 of a row");
     double sum[16];
-    wa_f32x16 prev;
+    f32x16 prev;
 #pragma unroll
     for (int r = 0; r < 16; ++r) sum[r] = 0.0, prev[r] = 0.f;
 #pragma unroll
     for (int c = 0; c < HC / WA_CHUNK; ++c) {
         float z = 0.f;
         asm volatile("" : "+v"(z) : "v"(sum[15]));
-        const wa_f32x16 t = wa_chunk(wa_ld4(arow, c), make_float4(b[4 * c], b[4 * c + 1], b[4 * c + 2], b[4 * c + 3]), z);
+        const f32x16 t = wa_chunk(wa_ld4(arow, c), make_float4(b[4 * c], b[4 * c + 1], b[4 * c + 2], b[4 * c + 3]), z);
         if (c > 0) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) sum[r] += (double)prev[r];
@@ -175,11 +170,11 @@ __device__ __forceinline__ wa_f32x16 wa_dot(const float* arow, const float* b, d
 // (measured: 0.8 to 1.5 KB of scratch per lane); the owner's rows are the same every tile and stay in cache.  A real loop,
 // not an unrolled one, with the loads three chunks (768 MFMA cycles) in front of their use in rotating registers.
 template <int HC>
-__device__ __forceinline__ wa_f32x16 wa_dot_mem(const float* arow, const float* brow, double mul) {
+__device__ __forceinline__ f32x16 wa_dot_mem(const float* arow, const float* brow, double mul) {
     constexpr int NCH = HC / WA_CHUNK;
     static_assert(WA_CHUNK == 4 && HC % WA_CHUNK == 0 && NCH >= 3, "a chunk is one dwordx4 of a row");
     double sum[16];
-    wa_f32x16 prev;
+    f32x16 prev;
 #pragma unroll
     for (int r = 0; r < 16; ++r) sum[r] = 0.0, prev[r] = 0.f;
     float4 a0 = wa_ld4(arow, 0), b0 = wa_ld4(brow, 0), a1 = wa_ld4(arow, 1), b1 = wa_ld4(brow, 1), a2 = wa_ld4(arow, 2), b2 = wa_ld4(brow, 2);
@@ -187,7 +182,7 @@ __device__ __forceinline__ wa_f32x16 wa_dot_mem(const float* arow, const float* 
     for (int c = 0; c < NCH; ++c) {
         const bool more = c + 3 < NCH;
         const float4 a3 = wa_ld4(more ? arow : nullptr, c + 3), b3 = wa_ld4(more ? brow : nullptr, c + 3);
-        const wa_f32x16 t = wa_chunk(a0, b0, 0.f);
+        const f32x16 t = wa_chunk(a0, b0, 0.f);
 #pragma unroll
         for (int r = 0; r < 16; ++r) sum[r] += (double)prev[r];      // chunk c - 1 (zeros at c = 0), under the MFMAs of chunk c
         prev = t;
@@ -226,7 +221,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_forward(WAArgs a, float* __re
     const size_t qrow = (size_t)w.b * a.L + qtok;
     float qB[HC];
     wa_load<HC / 4>(qvalid ? a.q + qrow * a.C + hf * HC : nullptr, qB);
-    wa_f32x16 o[NCB];
+    f32x16 o[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -246,12 +241,12 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_forward(WAArgs a, float* __re
         const int* srow = s_row[t & 1];
         const int* sreg = s_reg[t & 1];
         const int kr31 = srow[l31];
-        const wa_f32x16 s = wa_dot<HC>(kr31 >= 0 ? a.k + (size_t)kr31 * a.C + hf * HC : nullptr, qB, a.inv_scale);  // S^T / sqrt(C): rows = keys, lane = query
+        const f32x16 s = wa_dot<HC>(kr31 >= 0 ? a.k + (size_t)kr31 * a.C + hf * HC : nullptr, qB, a.inv_scale);  // S^T / sqrt(C): rows = keys, lane = query
         float p[16];
         float tmax = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int kk = wa_acc_row(r, hf);
+            const int kk = mfma_acc_row(r, hf);
             float x = s[r];
             if (a.shift && sreg[kk] != qreg) x += -100.0f;
             if (srow[kk] < 0) x = -INFINITY;
@@ -276,7 +271,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_forward(WAArgs a, float* __re
             for (int r = 0; r < 16; ++r) o[cb][r] *= alpha;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {                        // O^T += V^T P^T, two keys (one per lane half) a step
-            const int kr = srow[wa_acc_row(r, hf)];
+            const int kr = srow[mfma_acc_row(r, hf)];
             float vv[NCB];
             wa_load_c<NCB>(kr >= 0 ? a.v + (size_t)kr * a.C + NCB * l31 : nullptr, vv);
 #pragma unroll
@@ -289,7 +284,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_forward(WAArgs a, float* __re
         float x[NCB];
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) x[cb] = (float)((double)o[cb][r] / lsum);
-        wa_store_c<NCB>(out + qrow * a.C + NCB * wa_acc_row(r, hf), x);
+        wa_store_c<NCB>(out + qrow * a.C + NCB * mfma_acc_row(r, hf), x);
     }
     if (hf == 0) lse[qrow] = (double)m + log(lsum);
 }
@@ -315,7 +310,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_q(WAArgs a, const do
     const float* gB = qvalid ? g_out + qrow * a.C + hf * HC : nullptr;
     const double lq = qvalid ? lse[qrow] : 0.0;
     double dsum = 0.0;
-    wa_f32x16 acc[NCB];
+    f32x16 acc[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -340,7 +335,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_q(WAArgs a, const do
             __syncthreads();
             const int* srow = s_row[it & 1];
             const int* sreg = s_reg[it & 1];
-            wa_f32x16 s, dp;
+            f32x16 s, dp;
             {
                 const int kr = srow[l31];
                 s = wa_dot_mem<HC>(kr >= 0 ? a.k + (size_t)kr * a.C + hf * HC : nullptr, qB, a.inv_scale);      // S^T / sqrt(C)
@@ -348,7 +343,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_q(WAArgs a, const do
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int kk = wa_acc_row(r, hf);
+                const int kk = mfma_acc_row(r, hf);
                 const int kr = srow[kk];
                 float x = s[r];
                 if (a.shift && sreg[kk] != qreg) x += -100.0f;
@@ -375,7 +370,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_q(WAArgs a, const do
         float x[NCB];
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) x[cb] = acc[cb][r] / a.scale;
-        wa_store_c<NCB>(g_q + qrow * a.C + NCB * wa_acc_row(r, hf), x);
+        wa_store_c<NCB>(g_q + qrow * a.C + NCB * mfma_acc_row(r, hf), x);
     }
 }
 
@@ -396,7 +391,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_kv(WAArgs a, const d
     const size_t krow = (size_t)krow_i;
     const float* kB = kvalid ? a.k + krow * a.C + hf * HC : nullptr;             // the owner's two rows (read per chunk by wa_dot_mem)
     const float* vB = kvalid ? a.v + krow * a.C + hf * HC : nullptr;
-    wa_f32x16 dk[NCB], dv[NCB];
+    f32x16 dk[NCB], dv[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -417,7 +412,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_kv(WAArgs a, const d
         __syncthreads();
         const int* srow = s_row[t & 1];
         const int* sreg = s_reg[t & 1];
-        wa_f32x16 s, dp;
+        f32x16 s, dp;
         {
             const int qr = srow[l31];
             s = wa_dot_mem<HC>(qr >= 0 ? a.q + (size_t)qr * a.C + hf * HC : nullptr, kB, a.inv_scale);              // S / sqrt(C): rows = queries, lane = key; the forward's chain, bit for bit
@@ -427,7 +422,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_kv(WAArgs a, const d
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int qq = wa_acc_row(r, hf);
+            const int qq = mfma_acc_row(r, hf);
             const int qr = srow[qq];
             float x = s[r];
             if (a.shift && sreg[qq] != kreg) x += -100.0f;
@@ -455,17 +450,15 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_kv(WAArgs a, const d
         if constexpr (WANT_V) {
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) x[cb] = dv[cb][r];
-            wa_store_c<NCB>(g_v + krow * a.C + NCB * wa_acc_row(r, hf), x);
+            wa_store_c<NCB>(g_v + krow * a.C + NCB * mfma_acc_row(r, hf), x);
         }
         if constexpr (WANT_K) {
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) x[cb] = dk[cb][r] / a.scale;
-            wa_store_c<NCB>(g_k + krow * a.C + NCB * wa_acc_row(r, hf), x);
+            wa_store_c<NCB>(g_k + krow * a.C + NCB * mfma_acc_row(r, hf), x);
         }
     }
 }
-
-static bool wa_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // shared argument check; fills the kernel arguments
 static int wa_setup(const float* q, const float* k, const float* v, int32_t batch, int32_t partners, int32_t height, int32_t width,
@@ -473,7 +466,7 @@ static int wa_setup(const float* q, const float* k, const float* v, int32_t batc
     if (!q || !k || !v || batch < 1 || partners < 0 || height < 1 || width < 1 || num_splits < 1) return S360_E_BADARG;
     if (channels < 32 || channels > 128 || channels % 32 != 0) return S360_E_UNSUPPORTED;
     if (height % num_splits != 0 || width % num_splits != 0 || (mask_rule != 0 && mask_rule != 1)) return S360_E_BADARG;
-    if (!wa_aligned16(q) || !wa_aligned16(k) || !wa_aligned16(v)) return S360_E_BADARG;
+    if (!s360_aligned(q, 16) || !s360_aligned(k, 16) || !s360_aligned(v, 16)) return S360_E_BADARG;
     const int64_t M = partners > 0 ? partners : 1, L = (int64_t)height * width;
     const int64_t Lw = L / ((int64_t)num_splits * num_splits);
     if (batch * M * L >= (int64_t)1 << 31 || Lw * M >= (int64_t)1 << 31) return S360_E_BADARG;
@@ -514,7 +507,7 @@ extern "C" int s360_window_attention_forward(const float* q, const float* k, con
     WAArgs a;
     const int rc = wa_setup(q, k, v, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, a);
     if (rc != S360_OK) return rc;
-    if (!out || !lse || !wa_aligned16(out)) return S360_E_BADARG;
+    if (!out || !lse || !s360_aligned(out, 16)) return S360_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
     switch (channels / 32) {
@@ -523,7 +516,7 @@ extern "C" int s360_window_attention_forward(const float* q, const float* k, con
         case 3: hipLaunchKernelGGL((k_wa_forward<3>), grid, block, 0, st, a, out, lse); break;
         default: hipLaunchKernelGGL((k_wa_forward<4>), grid, block, 0, st, a, out, lse); break;
     }
-    return hipGetLastError() == hipSuccess ? S360_OK : S360_E_LAUNCH;
+    return s360_launch_status();
 }
 
 template <int NCB>
@@ -540,8 +533,8 @@ extern "C" int s360_window_attention_backward(const float* q, const float* k, co
     WAArgs a;
     const int rc = wa_setup(q, k, v, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, a);
     if (rc != S360_OK) return rc;
-    if (!lse || !g_out || !delta || !wa_aligned16(g_out)) return S360_E_BADARG;
-    if ((g_q && !wa_aligned16(g_q)) || (g_k && !wa_aligned16(g_k)) || (g_v && !wa_aligned16(g_v))) return S360_E_BADARG;
+    if (!lse || !g_out || !delta || !s360_aligned(g_out, 16)) return S360_E_BADARG;
+    if ((g_q && !s360_aligned(g_q, 16)) || (g_k && !s360_aligned(g_k, 16)) || (g_v && !s360_aligned(g_v, 16))) return S360_E_BADARG;
     if (!g_q && !g_k && !g_v) return S360_OK;
     hipStream_t st = (hipStream_t)stream;
     if (g_q || g_k) {                                         // the query-owned pass first: it writes Delta for the key-owned one
@@ -551,7 +544,7 @@ extern "C" int s360_window_attention_backward(const float* q, const float* k, co
             case 3: wa_launch_q<3>(a, lse, g_out, delta, g_q, st); break;
             default: wa_launch_q<4>(a, lse, g_out, delta, g_q, st); break;
         }
-        if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+        S360_CHECK_LAUNCH();
     }
     if (g_k || g_v) {
         switch (channels / 32) {
@@ -560,7 +553,7 @@ extern "C" int s360_window_attention_backward(const float* q, const float* k, co
             case 3: wa_launch_kv<3>(a, lse, delta, g_out, g_k, g_v, st); break;
             default: wa_launch_kv<4>(a, lse, delta, g_out, g_k, g_v, st); break;
         }
-        if (hipGetLastError() != hipSuccess) return S360_E_LAUNCH;
+        S360_CHECK_LAUNCH();
     }
     return S360_OK;
 }

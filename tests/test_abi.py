@@ -196,6 +196,26 @@ def test_native_calls_go_through_the_one_helper():
             assert not [x for x in names if x.startswith("_")], f"{n} imports {names} from .cost_volume"
 
 
+def test_native_sources_share_the_host_rules_and_the_tile_bookkeeping():
+    """csrc/*.hip and csrc/*.h: the launch check and the grid bound live in s360_launch.h alone (besides it, hipGetLastError only
+    clears the error of a failed attribute / occupancy query, in the three places named here), no translation unit keeps an
+    alignment helper of its own, and the MFMA accumulator's vector type and row rule are defined once."""
+    csrc = ROOT / "splatter360_amd" / "csrc"
+    sources = {f.name: f.read_text() for f in sorted(list(csrc.glob("*.hip")) + list(csrc.glob("*.h")))}
+    assert "s360_launch.h" in sources and len(sources) >= 25
+    uses = {n: [ln.strip() for ln in s.splitlines() if "hipGetLastError" in ln] for n, s in sources.items() if n != "s360_launch.h"}
+    uses = {n: u for n, u in uses.items() if u}
+    assert {n: len(u) for n, u in uses.items()} == {"s360_device.h": 2, "s360_backward.hip": 1}, uses
+    assert all("(void)hipGetLastError();" in ln for u in uses.values() for ln in u), uses
+    assert [n for n, s in sources.items() if "0x7fffffffLL" in s] == ["s360_launch.h"]
+    helpers = {n: re.findall(r"\w*aligned\w*\(const void", s) for n, s in sources.items() if n.endswith(".hip")}
+    assert not {n: h for n, h in helpers.items() if h}, helpers
+    typedefs = {n: len(re.findall(r"typedef\s+float\s+\w+\s+__attribute__\(\(ext_vector_type\(16\)\)\)", s)) for n, s in sources.items()}
+    assert {n: c for n, c in typedefs.items() if c} == {"s360_device.h": 1}, typedefs
+    rows = {n: s.count("(r & 3) + 8 * (r >> 2) + 4 * hf") for n, s in sources.items()}
+    assert {n: c for n, c in rows.items() if c} == {"s360_device.h": 1}, rows
+
+
 def test_loading_the_library_brings_torch_in_first():
     """libs360.so links the system libamdhip64; torch's wheel bundles its own.  Loaded before torch, the library would start
     a second HIP runtime in the process and every later launch on torch's streams fails (build() + smoke() in one process
