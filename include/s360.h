@@ -976,6 +976,36 @@ int s360_window_attention_backward(const float* q, const float* k, const float* 
                                    float* g_v, void* stream);
 
 /*
+ * The "high" precision mode of the window attention above: the same function, arguments and outputs, with each of the six
+ * products (S = Q K^T and O = P V; dP = G V^T, g_v = P^T G, g_q = dS K, g_k = dS^T Q) as a bf16x3 product on
+ * v_mfma_f32_32x32x16_bf16 — what torch.set_float32_matmul_precision('high') asks for.  split(x) = (hi, lo): hi = bf16(x),
+ * round to nearest even, lo = bf16(x - float32(hi)) (the difference is exact); A B = Ah Bh + Ah Bl + Al Bh, accumulated in float32
+ * by the MFMA over all channels (keys, queries); Al Bl is dropped.  Both operands of every product are split, P, dS and g_out from
+ * their float32 values.  Roll, split and merge, the finite -100 mask and both mask rules, the 1 / sqrt(channels) scaling (one
+ * rounding of the float32 sum times the float64 factor), the softmax with its float32 running maximum and float64 running sum,
+ * lse, Delta = sum_k P dP (float64) and the token order of every output are those of s360_window_attention_*; the backward
+ * recomputes every score and dP tile from the forward's split operands with the terms in the forward's order.
+ * A pre-pass splits q, k, v (and g_out) once per call into bf16 planes in window order in `scratch`: rows [batch K^2 Lw or Lk,
+ * channels] for the first products and, for the second ones, transposed planes [batch K^2, channels, Lw or Lk rounded up to a
+ * multiple of 4].  s360_window_attention_high_scratch_bytes returns the size for a forward (backward == 0: rows of q and k,
+ * transposed v) or a backward (rows of q, k, v and g_out, transposed q, k and g_out), 0 for arguments the calls refuse: at most
+ * 2 x the bytes of (q, k, v) and, for Lw >= 6, of (q, k, v, g_out).  The contents need no initialisation and nothing in it
+ * is read by a later call: the backward splits again.
+ * No atomics, no host synchronisation, no allocation; bit-identical from run to run and across streams.  Refusals as for
+ * s360_window_attention_*; a null scratch or one not 16-byte aligned: S360_E_BADARG, scratch_bytes smaller than reported:
+ * S360_E_WORKSPACE, both before any GPU work.
+ */
+size_t s360_window_attention_high_scratch_bytes(int32_t batch, int32_t partners, int32_t height, int32_t width, int32_t channels,
+                                                int32_t num_splits, int32_t backward);
+int s360_window_attention_high_forward(const float* q, const float* k, const float* v, int32_t batch, int32_t partners,
+                                       int32_t height, int32_t width, int32_t channels, int32_t num_splits, int32_t with_shift,
+                                       int32_t mask_rule, float* out, double* lse, void* scratch, size_t scratch_bytes, void* stream);
+int s360_window_attention_high_backward(const float* q, const float* k, const float* v, const double* lse, const float* g_out,
+                                        int32_t batch, int32_t partners, int32_t height, int32_t width, int32_t channels,
+                                        int32_t num_splits, int32_t with_shift, int32_t mask_rule, double* delta, float* g_q,
+                                        float* g_k, float* g_v, void* scratch, size_t scratch_bytes, void* stream);
+
+/*
  * The U-Nets' multi-head QKV attention, forward and backward (the reference's QKVAttentionLegacy and QKVAttention,
  * src/model/encoder/costvolume/ldm_unet/unet.py:527-599), on the channel-major qkv tensor where it lies: no [b heads, L, L]
  * weight tensor, no softmax of it and no permuted copy of q, k, v or the output is formed, forward or backward.

@@ -9,7 +9,8 @@ def install(**opts):
     map_pdf_to_opacity, splatter360_amd.depth_tail, whose fine_depth_tail is the direct API for the rest of that stretch),
     erp_distance, visualization (the evaluation step's depth_map, prep_image and apply_color_map, splatter360_amd.visualize),
     depth_smoothness (the training step's LossDepth.forward, splatter360_amd.depth_smooth), window_attention (the multi-view
-    transformer's attention, splatter360_amd.window_attention), group_norm (the encoder's norm + activation + residual sites,
+    transformer's attention, splatter360_amd.window_attention; window_attention_precision = "highest", "high" for its bf16x3
+    products, or "torch" to follow torch.get_float32_matmul_precision() at every call), group_norm (the encoder's norm + activation + residual sites,
     splatter360_amd.group_norm), unet_attention (the two U-Nets' multi-head QKV attention, splatter360_amd.qkv_attention) and
     transformer_ffn (the multi-view transformer layers' norm / mlp / norm tail, splatter360_amd.transformer_ffn)."""
     from .plugin import install as _install

@@ -123,6 +123,9 @@ SIGNATURES = {
     "s360_depth_smooth_backward": (_int, [_vp] * 4 + [_i32] * 6 + [_f32, _i32, _vp, _vp, _vp]),
     "s360_window_attention_forward": (_int, [_vp] * 3 + [_i32] * 8 + [_vp] * 3),
     "s360_window_attention_backward": (_int, [_vp] * 5 + [_i32] * 8 + [_vp] * 5),
+    "s360_window_attention_high_scratch_bytes": (_sz, [_i32] * 7),
+    "s360_window_attention_high_forward": (_int, [_vp] * 3 + [_i32] * 8 + [_vp] * 3 + [_sz, _vp]),
+    "s360_window_attention_high_backward": (_int, [_vp] * 5 + [_i32] * 8 + [_vp] * 5 + [_sz, _vp]),
     "s360_group_norm_scratch_doubles": (_sz, [_i32, _i32, _i64]),
     "s360_group_norm_forward": (_int, [_vp] * 4 + [_i32, _i32, _sz, _i32, _pf64, _i32] + [_vp] * 4),
     "s360_group_norm_backward": (_int, [_vp] * 5 + [_i32, _i32, _sz, _i32, _pf64, _i32] + [_vp] * 5),

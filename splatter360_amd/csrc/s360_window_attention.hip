@@ -557,3 +557,541 @@ extern "C" int s360_window_attention_backward(const float* q, const float* k, co
     }
     return S360_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- the "high" mode (bf16 x 3)
+// The same function with every product as a bf16x3 product on v_mfma_f32_32x32x16_bf16: split(x) = (hi, lo), hi = bf16(x)
+// round-to-nearest-even, lo = bf16(x - float32(hi)); A B = Ah Bh + Ah Bl + Al Bh, accumulated in float32 by the MFMA over all
+// channels (no float64 chunk sums: the split's error is far above the float32 chain's).  Roll, split and merge, the mask, the
+// scaling, the softmax with its running maximum, lse and Delta are those of the kernels above, and so is the orientation: the
+// walked index on the accumulator's rows, the owner on the lanes, so the P or dS tile is the B operand of the second product
+// register by register (registers 8 s .. 8 s + 7 are k-step s; element j of lane half h is tile row 16 s + 8 (j / 4) + 4 h + j % 4,
+// and the A operand's elements are read in that order).
+// A pre-pass (k_wah_split, one launch per operand) splits once per call and writes bf16 planes IN WINDOW ORDER into the caller's
+// scratch: "rows" [B K^2 rows, C] for the first products (a lane reads 8 consecutive channels of its row, 16 bytes), and
+// "transposed" [B K^2, C, pad4(rows)] for the second products (a lane reads 2 x 4 consecutive walked indices of its channel;
+// rows are padded to a multiple of 4 with zeros so that these 8-byte reads are aligned and a group is inside or outside).
+// The loops then have no gathered addressing and no split of an input.  Output channel of accumulator block cb, row r is
+// 32 cb + r: registers 4 g .. 4 g + 3 of a lane are channels 32 cb + 8 g + 4 hf + (0 .. 3), one 16-byte store.
+// The three terms of a score are issued in one order of (q, k) terms — (qh, kh), (ql, kh), (qh, kl) — whichever side is walked
+// (SWAP), and dP likewise in (g, v), so the backward's recomputed tiles are the forward's bit for bit.
+namespace s360 {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+struct WAHPlanes {                                            // hi and lo planes of the operands; null where a call has none
+    __bf16 *q_rh, *q_rl, *q_th, *q_tl;
+    __bf16 *k_rh, *k_rl, *k_th, *k_tl;
+    __bf16 *v_rh, *v_rl, *v_th, *v_tl;
+    __bf16 *g_rh, *g_rl, *g_th, *g_tl;
+};
+
+__host__ __device__ __forceinline__ int wah_pad4(int n) { return (n + 3) & ~3; }
+
+__device__ __forceinline__ void wah_split(float x, __bf16& hi, __bf16& lo) {
+    hi = (__bf16)x;
+    lo = (__bf16)(x - (float)hi);
+}
+
+// 8 consecutive bf16 (p 16-byte aligned), or zeros for p == null
+__device__ __forceinline__ bf16x8 wah_ld8(const __bf16* p) {
+    uint4 u = make_uint4(0u, 0u, 0u, 0u);
+    if (p) u = *reinterpret_cast<const uint4*>(p);
+    return __builtin_bit_cast(bf16x8, u);
+}
+
+// the A fragment of one k-step of a second product: walked indices g .. g + 3 and g + 8 .. g + 11 of one channel row of a
+// transposed plane (g a multiple of 4), zeros from lpad on
+__device__ __forceinline__ bf16x8 wah_ld44(const __bf16* row, int g, int lpad) {
+    uint2 u0 = make_uint2(0u, 0u), u1 = make_uint2(0u, 0u);
+    if (g < lpad) u0 = *reinterpret_cast<const uint2*>(row + g);
+    if (g + 8 < lpad) u1 = *reinterpret_cast<const uint2*>(row + g + 8);
+    return __builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y));
+}
+
+__device__ __forceinline__ f32x16 wah_mfma(bf16x8 x, bf16x8 y, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, c, 0, 0, 0);
+}
+
+// one k-step of a first product: walked fragments (wh, wl) as A, owner fragments (oh, ol) as B
+template <bool SWAP>
+__device__ __forceinline__ f32x16 wah_step(bf16x8 wh, bf16x8 wl, bf16x8 oh, bf16x8 ol, f32x16 acc) {
+    acc = wah_mfma(wh, oh, acc);
+    if constexpr (SWAP) {
+        acc = wah_mfma(wl, oh, acc);
+        acc = wah_mfma(wh, ol, acc);
+    } else {
+        acc = wah_mfma(wh, ol, acc);
+        acc = wah_mfma(wl, oh, acc);
+    }
+    return acc;
+}
+
+// tile = sum over all C channels of walked row x owner row, NS = C / 16 k-steps; the pointers are the lane's row at channel
+// 8 hf (null: zeros).  wah_dot: the owner's fragments are held in registers (the forward); wah_dot_mem: read per step (the
+// backward passes, whose two owners and two or more output tiles would not fit beside them; the reads stay in cache).
+template <int NS, bool SWAP>
+__device__ __forceinline__ f32x16 wah_dot(const __bf16* wh, const __bf16* wl, const bf16x8* oh, const bf16x8* ol) {
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        acc = wah_step<SWAP>(wah_ld8(wh ? wh + 16 * s : nullptr), wah_ld8(wl ? wl + 16 * s : nullptr), oh[s], ol[s], acc);
+    return acc;
+}
+
+template <int NS, bool SWAP>
+__device__ __forceinline__ f32x16 wah_dot_mem(const __bf16* wh, const __bf16* wl, const __bf16* oh, const __bf16* ol) {
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        acc = wah_step<SWAP>(wah_ld8(wh ? wh + 16 * s : nullptr), wah_ld8(wl ? wl + 16 * s : nullptr),
+                             wah_ld8(oh ? oh + 16 * s : nullptr), wah_ld8(ol ? ol + 16 * s : nullptr), acc);
+    return acc;
+}
+
+// acc[cb]^T += T^T x for the NCB channel blocks: x[16] is the lane's column of a 32 x 32 tile whose rows are the walked indices
+// first - 4 hf .. + 31 (split here, register by register); th / tl: the lane's channel row (channel l31 of block 0) of the
+// window's transposed planes, block cb another 32 lpad elements on; `first` = the tile's first walked index + 4 hf.
+template <int NCB>
+__device__ __forceinline__ void wah_accumulate(f32x16* acc, const __bf16* th, const __bf16* tl, int first, int lpad, const float* x) {
+    bf16x8 xh[2], xl[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            __bf16 hi, lo;
+            wah_split(x[8 * s + j], hi, lo);
+            xh[s][j] = hi;
+            xl[s][j] = lo;
+        }
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const size_t off = (size_t)cb * 32 * lpad;
+            const bf16x8 ah = wah_ld44(th + off, first + 16 * s, lpad), al = wah_ld44(tl + off, first + 16 * s, lpad);
+            acc[cb] = wah_mfma(ah, xh[s], acc[cb]);
+            acc[cb] = wah_mfma(ah, xl[s], acc[cb]);
+            acc[cb] = wah_mfma(al, xh[s], acc[cb]);
+        }
+}
+
+// registers 4 g .. 4 g + 3 of the NCB tiles, times mul, to channels 32 cb + 8 g + 4 hf + (0 .. 3) of row p
+template <int NCB, typename F>
+__device__ __forceinline__ void wah_store(float* p, const f32x16* acc, int hf, F f) {
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<float4*>(p + 32 * cb + 8 * g + 4 * hf) =
+                make_float4(f(acc[cb][4 * g]), f(acc[cb][4 * g + 1]), f(acc[cb][4 * g + 2]), f(acc[cb][4 * g + 3]));
+}
+
+// The pre-pass: one operand (queries' side: q, g_out; keys' side: k, v) into its planes.  Thread i takes 8 channels of one
+// window row, the row index fastest (the transposed plane's 2-byte stores of a wave are then consecutive); rows from `rows` to
+// pad4(rows) exist in the transposed plane only and are zeros.  rh / rl or th / tl may be null.
+__global__ __launch_bounds__(S360_BLOCK) void k_wah_split(WAArgs a, const float* __restrict__ src, int keys, __bf16* __restrict__ rh,
+                                                          __bf16* __restrict__ rl, __bf16* __restrict__ th, __bf16* __restrict__ tl) {
+    const int rows = keys ? a.Lk : a.Lw, lpad = wah_pad4(rows), cgs = a.C / 8;
+    const size_t i = (size_t)blockIdx.x * S360_BLOCK + threadIdx.x;
+    const size_t per_win = (size_t)lpad * cgs, nwin = (size_t)a.B * a.K * a.K;
+    if (i >= nwin * per_win) return;
+    const size_t win = i / per_win;
+    const int rem = (int)(i - win * per_win), cg = rem / lpad, p = rem - cg * lpad;
+    const int b = (int)(win / (a.K * a.K)), wi = (int)(win - (size_t)b * a.K * a.K), wy = wi / a.K, wx = wi - wy * a.K;
+    float x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = 0.f;
+    if (p < rows) {
+        int row, reg;
+        if (keys) {
+            wa_key(a, b, wy, wx, p, row, reg);
+        } else {
+            wa_token(a, wy, wx, p, row, reg);
+            row += b * a.L;
+        }
+        wa_load<2>(src + (size_t)row * a.C + 8 * cg, x);
+    }
+    bf16x8 hi, lo;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        __bf16 h, l;
+        wah_split(x[j], h, l);
+        hi[j] = h;
+        lo[j] = l;
+    }
+    if (rh && p < rows) {
+        const size_t o = (win * rows + p) * a.C + 8 * cg;
+        *reinterpret_cast<uint4*>(rh + o) = __builtin_bit_cast(uint4, hi);
+        *reinterpret_cast<uint4*>(rl + o) = __builtin_bit_cast(uint4, lo);
+    }
+    if (th) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const size_t o = (win * a.C + 8 * cg + j) * lpad + p;
+            th[o] = hi[j];
+            tl[o] = lo[j];
+        }
+    }
+}
+
+// Forward.  Owner: queries, their split rows in registers; as k_wa_forward otherwise.
+template <int NCB>
+__global__ __launch_bounds__(S360_BLOCK) void k_wah_forward(WAArgs a, WAHPlanes pl, float* __restrict__ out, double* __restrict__ lse) {
+    constexpr int NS = 2 * NCB;
+    __shared__ int s_reg[2][WA_T];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const WABlock w = wa_block(a, a.Lw);
+    const size_t win = ((size_t)w.b * a.K + w.wy) * a.K + w.wx;
+    const int qp = w.ob * WA_ROWS + wave * WA_T + l31;
+    const bool qvalid = qp < a.Lw;
+    int qtok = 0, qreg = 0;
+    if (qvalid) wa_token(a, w.wy, w.wx, qp, qtok, qreg);
+    const size_t qrow = (size_t)w.b * a.L + qtok;
+    bf16x8 qh[NS], ql[NS];
+    {
+        const size_t o = (win * a.Lw + qp) * a.C + 8 * hf;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            qh[s] = wah_ld8(qvalid ? pl.q_rh + o + 16 * s : nullptr);
+            ql[s] = wah_ld8(qvalid ? pl.q_rl + o + 16 * s : nullptr);
+        }
+    }
+    const int lkpad = wah_pad4(a.Lk);
+    const __bf16* vth = pl.v_th + (win * a.C + l31) * lkpad;
+    const __bf16* vtl = pl.v_tl + (win * a.C + l31) * lkpad;
+    f32x16 o[NCB];
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[cb][r] = 0.f;
+    float m = -INFINITY;
+    double lsum = 0.0;
+    const int ntiles = (a.Lk + WA_T - 1) / WA_T;
+    for (int t = 0; t < ntiles; ++t) {
+        if (tid < WA_T) {
+            const int j = t * WA_T + tid;
+            int row = -1, reg = 0;
+            if (j < a.Lk) wa_key(a, w.b, w.wy, w.wx, j, row, reg);
+            s_reg[t & 1][tid] = reg;
+        }
+        __syncthreads();                                      // one barrier per tile: the table is double-buffered
+        const int* sreg = s_reg[t & 1];
+        const int j31 = t * WA_T + l31;
+        const size_t ko = (win * a.Lk + j31) * a.C + 8 * hf;
+        const f32x16 s = wah_dot<NS, false>(j31 < a.Lk ? pl.k_rh + ko : nullptr, j31 < a.Lk ? pl.k_rl + ko : nullptr, qh, ql);  // S^T: rows = keys, lane = query
+        float p[16];
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int kk = mfma_acc_row(r, hf);
+            float x = (float)((double)s[r] * a.inv_scale);
+            if (a.shift && sreg[kk] != qreg) x += -100.0f;
+            if (t * WA_T + kk >= a.Lk) x = -INFINITY;
+            p[r] = x;
+            tmax = fmaxf(tmax, x);
+        }
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+        const float mnew = fmaxf(m, tmax);                    // finite: key 0 of every tile exists
+        const float alpha = expf(m - mnew);                   // 0 at the first tile
+        float rs = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            p[r] = expf(p[r] - mnew);
+            rs += p[r];
+        }
+        rs += __shfl_xor(rs, 32);
+        lsum = lsum * (double)alpha + (double)rs;
+        m = mnew;
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[cb][r] *= alpha;
+        wah_accumulate<NCB>(o, vth, vtl, t * WA_T + 4 * hf, lkpad, p);                      // O^T += V^T P^T
+    }
+    if (!qvalid) return;
+    wah_store<NCB>(out + qrow * a.C, o, hf, [lsum](float x) { return (float)((double)x / lsum); });
+    if (hf == 0) lse[qrow] = (double)m + log(lsum);
+}
+
+// Backward, Delta and g_q.  Owner: queries; two sweeps, as k_wa_backward_q.
+template <int NCB, bool WANT_Q>
+__global__ __launch_bounds__(S360_BLOCK) void k_wah_backward_q(WAArgs a, WAHPlanes pl, const double* __restrict__ lse,
+                                                               double* __restrict__ delta, float* __restrict__ g_q) {
+    constexpr int NS = 2 * NCB;
+    __shared__ int s_reg[2][WA_T];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const WABlock w = wa_block(a, a.Lw);
+    const size_t win = ((size_t)w.b * a.K + w.wy) * a.K + w.wx;
+    const int qp = w.ob * WA_ROWS + wave * WA_T + l31;
+    const bool qvalid = qp < a.Lw;
+    int qtok = 0, qreg = 0;
+    if (qvalid) wa_token(a, w.wy, w.wx, qp, qtok, qreg);
+    const size_t qrow = (size_t)w.b * a.L + qtok;
+    const size_t oo = (win * a.Lw + qp) * a.C + 8 * hf;
+    const __bf16* oqh = qvalid ? pl.q_rh + oo : nullptr;                        // the owner's rows (read per step by wah_dot_mem)
+    const __bf16* oql = qvalid ? pl.q_rl + oo : nullptr;
+    const __bf16* ogh = qvalid ? pl.g_rh + oo : nullptr;
+    const __bf16* ogl = qvalid ? pl.g_rl + oo : nullptr;
+    const int lkpad = wah_pad4(a.Lk);
+    const __bf16* kth = WANT_Q ? pl.k_th + (win * a.C + l31) * lkpad : nullptr;
+    const __bf16* ktl = WANT_Q ? pl.k_tl + (win * a.C + l31) * lkpad : nullptr;
+    const double lq = qvalid ? lse[qrow] : 0.0;
+    double dsum = 0.0;
+    f32x16 acc[NCB];
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[cb][r] = 0.f;
+    const int ntiles = (a.Lk + WA_T - 1) / WA_T;
+    int it = 0;                                               // parity of the double-buffered table, across both sweeps
+#pragma unroll
+    for (int sweep = 0; sweep < (WANT_Q ? 2 : 1); ++sweep) {  // two loops in the code, as in k_wa_backward_q
+        for (int t = 0; t < ntiles; ++t, ++it) {
+            if (tid < WA_T) {
+                const int j = t * WA_T + tid;
+                int row = -1, reg = 0;
+                if (j < a.Lk) wa_key(a, w.b, w.wy, w.wx, j, row, reg);
+                s_reg[it & 1][tid] = reg;
+            }
+            __syncthreads();
+            const int* sreg = s_reg[it & 1];
+            const int j31 = t * WA_T + l31;
+            const bool jv = j31 < a.Lk;
+            const size_t ko = (win * a.Lk + j31) * a.C + 8 * hf;
+            const f32x16 s = wah_dot_mem<NS, false>(jv ? pl.k_rh + ko : nullptr, jv ? pl.k_rl + ko : nullptr, oqh, oql);   // S^T
+            const f32x16 dp = wah_dot_mem<NS, false>(jv ? pl.v_rh + ko : nullptr, jv ? pl.v_rl + ko : nullptr, ogh, ogl);  // dP^T = V dO^T
+            float ds[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int kk = mfma_acc_row(r, hf);
+                float x = (float)((double)s[r] * a.inv_scale);
+                if (a.shift && sreg[kk] != qreg) x += -100.0f;
+                const float p = (t * WA_T + kk < a.Lk && qvalid) ? expf((float)((double)x - lq)) : 0.f;
+                if (sweep == 0) dsum += (double)p * (double)dp[r];
+                else ds[r] = p * (float)((double)dp[r] - dsum);
+            }
+            if (sweep == 1) wah_accumulate<NCB>(acc, kth, ktl, t * WA_T + 4 * hf, lkpad, ds);      // g_q^T += K^T dS^T
+        }
+        if (sweep == 0) {
+            dsum += __shfl_xor(dsum, 32);
+            if (qvalid && hf == 0) delta[qrow] = dsum;
+        }
+    }
+    if (!qvalid || !WANT_Q) return;
+    const float scale = a.scale;
+    wah_store<NCB>(g_q + qrow * a.C, acc, hf, [scale](float x) { return x / scale; });
+}
+
+// Backward, g_k and / or g_v.  Owner: keys; walks the window's query tiles, as k_wa_backward_kv.
+template <int NCB, bool WANT_K, bool WANT_V>
+__global__ __launch_bounds__(S360_BLOCK) void k_wah_backward_kv(WAArgs a, WAHPlanes pl, const double* __restrict__ lse,
+                                                                const double* __restrict__ delta, float* __restrict__ g_k,
+                                                                float* __restrict__ g_v) {
+    constexpr int NS = 2 * NCB;
+    __shared__ int s_row[2][WA_T], s_reg[2][WA_T];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const WABlock w = wa_block(a, a.Lk);
+    const size_t win = ((size_t)w.b * a.K + w.wy) * a.K + w.wx;
+    const int kj = w.ob * WA_ROWS + wave * WA_T + l31;
+    const bool kvalid = kj < a.Lk;
+    int krow_i = 0, kreg = 0;
+    if (kvalid) wa_key(a, w.b, w.wy, w.wx, kj, krow_i, kreg);
+    const size_t krow = (size_t)krow_i;
+    const size_t oo = (win * a.Lk + kj) * a.C + 8 * hf;
+    const __bf16* okh = kvalid ? pl.k_rh + oo : nullptr;                        // the owner's rows (read per step by wah_dot_mem)
+    const __bf16* okl = kvalid ? pl.k_rl + oo : nullptr;
+    const __bf16* ovh = kvalid ? pl.v_rh + oo : nullptr;
+    const __bf16* ovl = kvalid ? pl.v_rl + oo : nullptr;
+    const int lwpad = wah_pad4(a.Lw);
+    const size_t to = (win * a.C + l31) * lwpad;
+    f32x16 dk[NCB], dv[NCB];
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dk[cb][r] = dv[cb][r] = 0.f;
+    const int ntiles = (a.Lw + WA_T - 1) / WA_T;
+    for (int t = 0; t < ntiles; ++t) {
+        if (tid < WA_T) {
+            const int p = t * WA_T + tid;
+            int row = -1, reg = 0;
+            if (p < a.Lw) {
+                int tok;
+                wa_token(a, w.wy, w.wx, p, tok, reg);
+                row = w.b * a.L + tok;
+            }
+            s_row[t & 1][tid] = row;
+            s_reg[t & 1][tid] = reg;
+        }
+        __syncthreads();
+        const int* srow = s_row[t & 1];
+        const int* sreg = s_reg[t & 1];
+        const int p31 = t * WA_T + l31;
+        const bool pv = p31 < a.Lw;
+        const size_t qo = (win * a.Lw + p31) * a.C + 8 * hf;
+        const f32x16 s = wah_dot_mem<NS, true>(pv ? pl.q_rh + qo : nullptr, pv ? pl.q_rl + qo : nullptr, okh, okl);   // S: rows = queries, lane = key
+        f32x16 dp;
+        if constexpr (WANT_K) dp = wah_dot_mem<NS, true>(pv ? pl.g_rh + qo : nullptr, pv ? pl.g_rl + qo : nullptr, ovh, ovl);  // dP = dO V^T
+        float pp[16], ds[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int qq = mfma_acc_row(r, hf);
+            const int qr = srow[qq];
+            float x = (float)((double)s[r] * a.inv_scale);
+            if (a.shift && sreg[qq] != kreg) x += -100.0f;
+            float p = 0.f;
+            if (qr >= 0 && kvalid) p = expf((float)((double)x - lse[qr]));
+            pp[r] = p;
+            if constexpr (WANT_K) ds[r] = p * (float)((double)dp[r] - (qr >= 0 ? delta[qr] : 0.0));
+        }
+        if constexpr (WANT_V) wah_accumulate<NCB>(dv, pl.g_th + to, pl.g_tl + to, t * WA_T + 4 * hf, lwpad, pp);  // g_v^T += dO^T P
+        if constexpr (WANT_K) wah_accumulate<NCB>(dk, pl.q_th + to, pl.q_tl + to, t * WA_T + 4 * hf, lwpad, ds);  // g_k^T += Q^T dS
+    }
+    if (!kvalid) return;
+    if constexpr (WANT_V) wah_store<NCB>(g_v + krow * a.C, dv, hf, [](float x) { return x; });
+    if constexpr (WANT_K) {
+        const float scale = a.scale;
+        wah_store<NCB>(g_k + krow * a.C, dk, hf, [scale](float x) { return x / scale; });
+    }
+}
+
+// The scratch of a call: the planes in the order q, k, v, g (rows, then transposed; hi, then lo), each a multiple of 64 bytes.
+// Forward: rows of q and k, transposed v.  Backward: rows of all four, transposed q, k and g.
+static size_t wah_layout(const WAArgs& a, bool backward, char* base, WAHPlanes* pl) {
+    const size_t nwin = (size_t)a.B * a.K * a.K;
+    const size_t nq = nwin * a.Lw * a.C, nk = nwin * a.Lk * a.C;
+    const size_t tq = nwin * a.C * wah_pad4(a.Lw), tk = nwin * a.C * wah_pad4(a.Lk);
+    size_t off = 0;
+    auto take = [&](size_t n, __bf16** hi, __bf16** lo) {
+        if (pl) {
+            *hi = reinterpret_cast<__bf16*>(base + off);
+            *lo = reinterpret_cast<__bf16*>(base + off + 2 * n);
+        }
+        off += 4 * n;
+    };
+    WAHPlanes none = {};
+    if (pl) *pl = none;
+    WAHPlanes* p = pl ? pl : &none;
+    take(nq, &p->q_rh, &p->q_rl);
+    take(nk, &p->k_rh, &p->k_rl);
+    if (!backward) {
+        take(tk, &p->v_th, &p->v_tl);
+        return off;
+    }
+    take(nk, &p->v_rh, &p->v_rl);
+    take(nq, &p->g_rh, &p->g_rl);
+    take(tq, &p->q_th, &p->q_tl);
+    take(tk, &p->k_th, &p->k_tl);
+    take(tq, &p->g_th, &p->g_tl);
+    return off;
+}
+
+// launches k_wah_split for one operand; false if the grid does not fit
+static bool wah_split_launch(const WAArgs& a, const float* src, int keys, __bf16* rh, __bf16* rl, __bf16* th, __bf16* tl, hipStream_t st) {
+    const size_t n = (size_t)a.B * a.K * a.K * wah_pad4(keys ? a.Lk : a.Lw) * (a.C / 8);
+    const size_t blocks = (n + S360_BLOCK - 1) / S360_BLOCK;
+    if (!s360_grid_fits((long long)blocks)) return false;
+    hipLaunchKernelGGL(k_wah_split, dim3((unsigned)blocks), dim3(S360_BLOCK), 0, st, a, src, keys, rh, rl, th, tl);
+    return true;
+}
+
+static bool wah_split_fits(const WAArgs& a) {
+    return s360_grid_fits((long long)(((size_t)a.B * a.K * a.K * wah_pad4(a.Lk) * (a.C / 8) + S360_BLOCK - 1) / S360_BLOCK));
+}
+
+template <int NCB>
+static void wah_launch_q(const WAArgs& a, const WAHPlanes& pl, const double* lse, double* delta, float* g_q, hipStream_t st) {
+    const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
+    if (g_q) hipLaunchKernelGGL((k_wah_backward_q<NCB, true>), grid, block, 0, st, a, pl, lse, delta, g_q);
+    else hipLaunchKernelGGL((k_wah_backward_q<NCB, false>), grid, block, 0, st, a, pl, lse, delta, g_q);
+}
+
+template <int NCB>
+static void wah_launch_kv(const WAArgs& a, const WAHPlanes& pl, const double* lse, const double* delta, float* g_k, float* g_v,
+                          hipStream_t st) {
+    const dim3 grid(wa_grid(a, a.Lk)), block(S360_BLOCK);
+    if (g_k && g_v) hipLaunchKernelGGL((k_wah_backward_kv<NCB, true, true>), grid, block, 0, st, a, pl, lse, delta, g_k, g_v);
+    else if (g_k) hipLaunchKernelGGL((k_wah_backward_kv<NCB, true, false>), grid, block, 0, st, a, pl, lse, delta, g_k, g_v);
+    else hipLaunchKernelGGL((k_wah_backward_kv<NCB, false, true>), grid, block, 0, st, a, pl, lse, delta, g_k, g_v);
+}
+
+}  // namespace s360
+
+extern "C" size_t s360_window_attention_high_scratch_bytes(int32_t batch, int32_t partners, int32_t height, int32_t width,
+                                                           int32_t channels, int32_t num_splits, int32_t backward) {
+    WAArgs a;
+    const float* any = reinterpret_cast<const float*>((uintptr_t)16);           // wa_setup checks the pointers it is given; none is read
+    if (wa_setup(any, any, any, batch, partners, height, width, channels, num_splits, 0, 0, a) != S360_OK) return 0;
+    return wah_layout(a, backward != 0, nullptr, nullptr);
+}
+
+extern "C" int s360_window_attention_high_forward(const float* q, const float* k, const float* v, int32_t batch, int32_t partners,
+                                                  int32_t height, int32_t width, int32_t channels, int32_t num_splits,
+                                                  int32_t with_shift, int32_t mask_rule, float* out, double* lse, void* scratch,
+                                                  size_t scratch_bytes, void* stream) {
+    WAArgs a;
+    const int rc = wa_setup(q, k, v, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, a);
+    if (rc != S360_OK) return rc;
+    if (!out || !lse || !s360_aligned(out, 16) || !scratch || !s360_aligned(scratch, 16) || !wah_split_fits(a)) return S360_E_BADARG;
+    if (scratch_bytes < wah_layout(a, false, nullptr, nullptr)) return S360_E_WORKSPACE;
+    WAHPlanes pl;
+    wah_layout(a, false, static_cast<char*>(scratch), &pl);
+    hipStream_t st = (hipStream_t)stream;
+    wah_split_launch(a, q, 0, pl.q_rh, pl.q_rl, nullptr, nullptr, st);
+    wah_split_launch(a, k, 1, pl.k_rh, pl.k_rl, nullptr, nullptr, st);
+    wah_split_launch(a, v, 1, nullptr, nullptr, pl.v_th, pl.v_tl, st);
+    S360_CHECK_LAUNCH();
+    const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
+    switch (channels / 32) {
+        case 1: hipLaunchKernelGGL((k_wah_forward<1>), grid, block, 0, st, a, pl, out, lse); break;
+        case 2: hipLaunchKernelGGL((k_wah_forward<2>), grid, block, 0, st, a, pl, out, lse); break;
+        case 3: hipLaunchKernelGGL((k_wah_forward<3>), grid, block, 0, st, a, pl, out, lse); break;
+        default: hipLaunchKernelGGL((k_wah_forward<4>), grid, block, 0, st, a, pl, out, lse); break;
+    }
+    return s360_launch_status();
+}
+
+extern "C" int s360_window_attention_high_backward(const float* q, const float* k, const float* v, const double* lse,
+                                                   const float* g_out, int32_t batch, int32_t partners, int32_t height, int32_t width,
+                                                   int32_t channels, int32_t num_splits, int32_t with_shift, int32_t mask_rule,
+                                                   double* delta, float* g_q, float* g_k, float* g_v, void* scratch,
+                                                   size_t scratch_bytes, void* stream) {
+    WAArgs a;
+    const int rc = wa_setup(q, k, v, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, a);
+    if (rc != S360_OK) return rc;
+    if (!lse || !g_out || !delta || !s360_aligned(g_out, 16)) return S360_E_BADARG;
+    if ((g_q && !s360_aligned(g_q, 16)) || (g_k && !s360_aligned(g_k, 16)) || (g_v && !s360_aligned(g_v, 16))) return S360_E_BADARG;
+    if (!scratch || !s360_aligned(scratch, 16) || !wah_split_fits(a)) return S360_E_BADARG;
+    if (scratch_bytes < wah_layout(a, true, nullptr, nullptr)) return S360_E_WORKSPACE;
+    if (!g_q && !g_k && !g_v) return S360_OK;
+    WAHPlanes pl;
+    wah_layout(a, true, static_cast<char*>(scratch), &pl);
+    hipStream_t st = (hipStream_t)stream;
+    wah_split_launch(a, q, 0, pl.q_rh, pl.q_rl, pl.q_th, pl.q_tl, st);
+    wah_split_launch(a, k, 1, pl.k_rh, pl.k_rl, pl.k_th, pl.k_tl, st);
+    wah_split_launch(a, v, 1, pl.v_rh, pl.v_rl, nullptr, nullptr, st);
+    wah_split_launch(a, g_out, 0, pl.g_rh, pl.g_rl, pl.g_th, pl.g_tl, st);
+    S360_CHECK_LAUNCH();
+    if (g_q || g_k) {                                         // the query-owned pass first: it writes Delta for the key-owned one
+        switch (channels / 32) {
+            case 1: wah_launch_q<1>(a, pl, lse, delta, g_q, st); break;
+            case 2: wah_launch_q<2>(a, pl, lse, delta, g_q, st); break;
+            case 3: wah_launch_q<3>(a, pl, lse, delta, g_q, st); break;
+            default: wah_launch_q<4>(a, pl, lse, delta, g_q, st); break;
+        }
+        S360_CHECK_LAUNCH();
+    }
+    if (g_k || g_v) {
+        switch (channels / 32) {
+            case 1: wah_launch_kv<1>(a, pl, lse, delta, g_k, g_v, st); break;
+            case 2: wah_launch_kv<2>(a, pl, lse, delta, g_k, g_v, st); break;
+            case 3: wah_launch_kv<3>(a, pl, lse, delta, g_k, g_v, st); break;
+            default: wah_launch_kv<4>(a, pl, lse, delta, g_k, g_v, st); break;
+        }
+        S360_CHECK_LAUNCH();
+    }
+    return S360_OK;
+}

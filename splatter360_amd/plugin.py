@@ -47,6 +47,9 @@ everything behind the layer's attention — norm1, the concatenation, the two-Li
 kernels of transformer_ffn.py; the projections and merge stay the layer's own nn.Linears and the attention is called through the
 module's globals, so window_attention=True composes in either order; every form the wrapper does not recognise reaches the
 replaced method.
+install(window_attention=True) rebinds that module's single_head_split_window_attention and single_head_full_attention to the fused
+kernels of window_attention.py; window_attention_precision="high" runs their bf16x3 products, "torch" whatever
+torch.get_float32_matmul_precision() asks for at the call (the reference's main sets 'high').
 
 Without install() the reference still runs on this library through the drop-in module `diff_gaussian_rasterization`
  — per face, per pass, with upstream's host synchronisations; bench.py prints both step times.
@@ -711,40 +714,55 @@ def _dense_mask(attn_mask):
     return attn_mask.dense() if isinstance(attn_mask, _wa.ShiftMask) else attn_mask
 
 
-def _native_split_window_attention(replaced):
+def _window_attention_precision(precision) -> str:
+    """The `precision` option of the window-attention seam, checked when the seam is installed: "highest", "high", or "torch"
+    (window_attention.resolve_precision reads torch's float32 matmul precision at every call)."""
+    from . import window_attention as _wa
+    if precision != "torch" and precision not in _wa.PRECISIONS:
+        raise ValueError(f"window_attention_precision is one of {[*_wa.PRECISIONS, 'torch']}, got {precision!r}")
+    return precision
+
+
+def _native_split_window_attention(replaced, mod=None, precision="highest"):
     """single_head_split_window_attention with the reference's signature: the fused kernels for float32 GPU q, k, v of agreeing
     shapes and a supported C — with_shift only with the ShiftMask handle of this grid and split (or without a mask argument the
-    reference would refuse anyway); the replaced function otherwise, with a handle made dense first."""
+    reference would refuse anyway); the replaced function otherwise, with a handle made dense first.  precision: the seam's
+    option, "torch" resolved per call."""
     from . import window_attention as _wa
+    _window_attention_precision(precision)
 
     def single_head_split_window_attention(q, k, v, num_splits=1, with_shift=False, h=None, w=None, attn_mask=None):
         if _window_attention_call(q, k, v, h, w, num_splits) and (
                 not with_shift or (isinstance(attn_mask, _wa.ShiftMask) and attn_mask.matches(h, w, num_splits))):
-            return _wa.window_attention(q, k, v, height=h, width=w, num_splits=num_splits, with_shift=bool(with_shift))
+            return _wa.window_attention(q, k, v, height=h, width=w, num_splits=num_splits, with_shift=bool(with_shift),
+                                        precision=_wa.resolve_precision(precision))
         return replaced(q, k, v, num_splits=num_splits, with_shift=with_shift, h=h, w=w, attn_mask=_dense_mask(attn_mask))
 
     single_head_split_window_attention.replaced = replaced
+    single_head_split_window_attention.precision = precision
     single_head_split_window_attention.__doc__ = _wa.window_attention.__doc__
     return single_head_split_window_attention
 
 
-def _native_full_attention(replaced):
+def _native_full_attention(replaced, mod=None, precision="highest"):
     """single_head_full_attention with the reference's signature: the fused kernels (one window, no shift) for float32 GPU
-    q, k, v [B, L, C] of one shape and a supported C; the replaced function otherwise."""
+    q, k, v [B, L, C] of one shape and a supported C; the replaced function otherwise.  precision: as above."""
     from . import window_attention as _wa
+    _window_attention_precision(precision)
 
     def single_head_full_attention(q, k, v):
         if (all(_is_cuda_f32(t) for t in (q, k, v)) and q.dim() == 3 and tuple(q.shape) == tuple(k.shape)
                 and _window_attention_call(q, k, v, 1, int(q.shape[1]), 1)):
-            return _wa.full_attention(q, k, v)
+            return _wa.full_attention(q, k, v, precision=_wa.resolve_precision(precision))
         return replaced(q, k, v)
 
     single_head_full_attention.replaced = replaced
+    single_head_full_attention.precision = precision
     single_head_full_attention.__doc__ = _wa.full_attention.__doc__
     return single_head_full_attention
 
 
-def _native_shift_mask(replaced):
+def _native_shift_mask(replaced, mod=None, **_):
     """generate_shift_window_attn_mask with the reference's signature: returns a window_attention.ShiftMask — the arguments and
     no [K^2, Lw, Lw] tensor; its dense() calls the replaced generator, for the torch paths only."""
     from . import window_attention as _wa
@@ -761,7 +779,7 @@ def _native_shift_mask(replaced):
     return generate_shift_window_attn_mask
 
 
-def _native_multi_head_attention(replaced):
+def _native_multi_head_attention(replaced, mod=None, **_):
     """multi_head_split_window_attention stays the reference's torch code; the wrapper only makes a ShiftMask handle dense, so
     that a handle never reaches torch."""
     import functools
@@ -777,7 +795,8 @@ def _native_multi_head_attention(replaced):
 
 WINDOW_ATTENTION_SEAM = _Seam("window_attention", WINDOW_ATTENTION_MODULE, WINDOW_ATTENTION_NAMES, (),
                               {WINDOW_ATTENTION_SPLIT: _native_split_window_attention, WINDOW_ATTENTION_FULL: _native_full_attention,
-                               WINDOW_ATTENTION_MASK: _native_shift_mask, WINDOW_ATTENTION_MULTI: _native_multi_head_attention})
+                               WINDOW_ATTENTION_MASK: _native_shift_mask, WINDOW_ATTENTION_MULTI: _native_multi_head_attention},
+                              context=True)
 
 
 GROUP_NORM_UNET_MODULE = "src.model.encoder.costvolume.ldm_unet.unet"   # defines ResBlock (:176-307) and AttentionBlock (:310-380)
@@ -1079,11 +1098,13 @@ def install_depth_loss():
     return DEPTH_LOSS_SEAM.install()
 
 
-def install_window_attention():
+def install_window_attention(precision: str = "highest"):
     """The half of install(window_attention=True): rebind the backbone module's single_head_split_window_attention,
     single_head_full_attention, generate_shift_window_attn_mask and multi_head_split_window_attention now if the module is
-    imported, else as soon as it is (import hook).  Returns {name: patched function} or None."""
-    return WINDOW_ATTENTION_SEAM.install()
+    imported, else as soon as it is (import hook).  Returns {name: patched function} or None.  precision: "highest" (exact
+    float32 products), "high" (bf16x3 products, window_attention.py) or "torch" (torch.get_float32_matmul_precision() at every
+    call: 'highest' is "highest", 'high' and 'medium' are "high")."""
+    return WINDOW_ATTENTION_SEAM.install(precision=_window_attention_precision(precision))
 
 
 def install_group_norm():
@@ -1197,7 +1218,9 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     window_attention=True: ALSO rebind the multi-view transformer's single_head_split_window_attention and
     single_head_full_attention (src/model/encoder/backbone/multiview_transformer.py:8-16, :60-210) to the fused window-attention
     kernels of splatter360_amd.window_attention, and generate_shift_window_attn_mask to return a ShiftMask handle in place of
-    the [K^2, Lw, Lw] tensor (install_window_attention; off by default).
+    the [K^2, Lw, Lw] tensor (install_window_attention; off by default).  window_attention_precision: "highest" (the default:
+    exact float32 products), "high" (bf16x3 products on the bf16 MFMA) or "torch" (what torch.get_float32_matmul_precision() says
+    at every call — the reference's main sets 'high', so with "torch" the unchanged reference runs the "high" kernels).
     group_norm=True: ALSO rebind the two U-Nets' ResBlock._forward and AttentionBlock._forward (ldm_unet/unet.py), the CNN
     backbones' ResidualBlock.forward and DepthPredictorMultiView360.__init__ so that every conv -> GroupNorm / InstanceNorm2d ->
     SiLU / GELU / ReLU (-> + skip) of the encoder runs the fused kernels of splatter360_amd.group_norm (install_group_norm; off
@@ -1215,8 +1238,10 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
     the fused decoder.  lazy=True: only installs an import hook that patches the registry when the reference itself first imports
     the package (for a sitecustomize that runs before sys.path is set up).  Idempotent.
-    opts: views_per_group (6), shared_campos (None = checked per group with one small read per forward), check ("sync"), glue."""
+    opts: window_attention_precision (above); for the decoder views_per_group (6), shared_campos (None = checked per group with one small read per forward), check ("sync"), glue."""
     given = locals()
+    # an option of a seam, not a seam: taken out of opts (the decoder's options) before they reach the decoder
+    given["window_attention_options"] = {"precision": _window_attention_precision(opts.pop("window_attention_precision", "highest"))}
     for keyword, seams in OPTION_SEAMS.items():
         if given[keyword]:
             for seam in seams:

@@ -10,6 +10,12 @@ autograd node saves q, k, v and one float64 log-sum-exp per query.  `full_attent
 `ShiftMask` is what plugin.install(window_attention=True) lets generate_shift_window_attn_mask return in place of the
 [K^2, Lw, Lw] tensor.  Float32 GPU tensors with 32 | C, 32 <= C <= 128; there is no CPU path (the installed seam keeps the
 replaced functions for everything else).  Forward and backward are bit-identical from run to run: fixed order, no atomics.
+
+precision="highest" (the default) forms every product from exact float32 products; precision="high" is what
+torch.set_float32_matmul_precision('high') asks for: each float32 number as the sum of two bfloat16 numbers and each product
+A B as Ah Bh + Ah Bl + Al Bh on the bf16 MFMA, accumulated in float32 (csrc: the k_wah_* kernels).  Its planes live in a scratch
+tensor of `scratch_bytes(...)` bytes that a call allocates and drops; the autograd node keeps q, k, v and lse in either mode.
+`resolve_precision("torch")` reads torch's setting at call time.
 """
 from __future__ import annotations
 
@@ -17,10 +23,13 @@ import torch
 from torch import Tensor
 from torch.autograd.function import once_differentiable
 
+from . import _lib
 from ._call import _check_cuda_f32, call, ptr
 
 MASK_RULES = {"reference": 0, "aligned": 1}
 MIN_CHANNELS, MAX_CHANNELS, CHANNEL_STEP = 32, 128, 32
+PRECISIONS = ("highest", "high")
+_TORCH_PRECISIONS = {"highest": "highest", "high": "high", "medium": "high"}    # never less accurate than asked
 
 
 def supported_channels(c: int) -> bool:
@@ -31,6 +40,31 @@ def _rule(mask_rule: str) -> int:
     if mask_rule not in MASK_RULES:
         raise ValueError(f"window_attention knows the mask rules {sorted(MASK_RULES)}, got mask_rule={mask_rule!r}")
     return MASK_RULES[mask_rule]
+
+
+def _precision(precision: str) -> str:
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"window_attention knows the precisions {list(PRECISIONS)}, got precision={precision!r}")
+    return precision
+
+
+def resolve_precision(name: str) -> str:
+    """"highest" or "high" as they are; "torch": what torch.get_float32_matmul_precision() says now — 'highest' is "highest",
+    'high' and 'medium' are "high" (there is no single-bf16 mode: the result is never less accurate than asked)."""
+    if name == "torch":
+        return _TORCH_PRECISIONS[torch.get_float32_matmul_precision()]
+    return _precision(name)
+
+
+def scratch_bytes(batch: int, partners: int, height: int, width: int, channels: int, num_splits: int, backward: bool) -> int:
+    """s360_window_attention_high_scratch_bytes: the bytes of bf16 planes a "high" forward (backward) call needs."""
+    return int(_lib.lib().s360_window_attention_high_scratch_bytes(int(batch), int(partners), int(height), int(width), int(channels),
+                                                                   int(num_splits), int(bool(backward))))
+
+
+def _scratch(q: Tensor, partners: int, height: int, width: int, num_splits: int, backward: bool) -> Tensor:
+    n = scratch_bytes(int(q.shape[0]), partners, height, width, int(q.shape[2]), num_splits, backward)
+    return torch.empty(n, dtype=torch.uint8, device=q.device)
 
 
 def _checked(what: str, q: Tensor, k: Tensor, v: Tensor, height: int, width: int, num_splits: int) -> int:
@@ -60,23 +94,30 @@ def _checked(what: str, q: Tensor, k: Tensor, v: Tensor, height: int, width: int
 
 
 def attention_forward(q: Tensor, k: Tensor, v: Tensor, *, height: int, width: int, num_splits: int, with_shift: bool = False,
-                      mask_rule: str = "reference") -> tuple:
-    """s360_window_attention_forward on contiguous float32 GPU tensors -> (out [B, L, C] float32, lse [B, L] float64)."""
-    rule = _rule(mask_rule)
+                      mask_rule: str = "reference", precision: str = "highest") -> tuple:
+    """s360_window_attention_forward (precision "high": s360_window_attention_high_forward) on contiguous float32 GPU tensors ->
+    (out [B, L, C] float32, lse [B, L] float64)."""
+    rule, precision = _rule(mask_rule), _precision(precision)
     partners = _checked("attention_forward", q, k, v, height, width, num_splits)
     q, k, v = (t.detach().contiguous() for t in (q, k, v))
     b, l, c = (int(s) for s in q.shape)
     out = torch.empty_like(q)
     lse = torch.empty(b, l, dtype=torch.float64, device=q.device)
-    call("s360_window_attention_forward", q.device, ptr(q), ptr(k), ptr(v), b, partners, int(height), int(width), c, int(num_splits),
-         int(bool(with_shift)), rule, ptr(out), ptr(lse))
+    args = (ptr(q), ptr(k), ptr(v), b, partners, int(height), int(width), c, int(num_splits), int(bool(with_shift)), rule, ptr(out), ptr(lse))
+    if precision == "high":
+        scratch = _scratch(q, partners, height, width, num_splits, False)
+        call("s360_window_attention_high_forward", q.device, *args, ptr(scratch), scratch.numel())
+    else:
+        call("s360_window_attention_forward", q.device, *args)
     return out, lse
 
 
 def attention_backward(q: Tensor, k: Tensor, v: Tensor, lse: Tensor, g_out: Tensor, *, height: int, width: int, num_splits: int,
-                       with_shift: bool = False, mask_rule: str = "reference", needs=(True, True, True)) -> tuple:
-    """s360_window_attention_backward -> (g_q, g_k, g_v) in the inputs' shapes, None where `needs` is False."""
-    rule = _rule(mask_rule)
+                       with_shift: bool = False, mask_rule: str = "reference", needs=(True, True, True),
+                       precision: str = "highest") -> tuple:
+    """s360_window_attention_backward (precision "high": s360_window_attention_high_backward, with the lse of a "high" forward)
+    -> (g_q, g_k, g_v) in the inputs' shapes, None where `needs` is False."""
+    rule, precision = _rule(mask_rule), _precision(precision)
     partners = _checked("attention_backward", q, k, v, height, width, num_splits)
     _check_cuda_f32("attention_backward", q, g_out)
     if tuple(g_out.shape) != tuple(q.shape):
@@ -89,20 +130,24 @@ def attention_backward(q: Tensor, k: Tensor, v: Tensor, lse: Tensor, g_out: Tens
     if g_q is None and g_k is None and g_v is None:
         return None, None, None
     delta = torch.empty(b, l, dtype=torch.float64, device=q.device)
-    call("s360_window_attention_backward", q.device, ptr(q), ptr(k), ptr(v), ptr(lse), ptr(g_out), b, partners,
-         int(height), int(width), c, int(num_splits), int(bool(with_shift)), rule,
-         ptr(delta), ptr(g_q), ptr(g_k), ptr(g_v))
+    args = (ptr(q), ptr(k), ptr(v), ptr(lse), ptr(g_out), b, partners, int(height), int(width), c, int(num_splits),
+            int(bool(with_shift)), rule, ptr(delta), ptr(g_q), ptr(g_k), ptr(g_v))
+    if precision == "high":
+        scratch = _scratch(q, partners, height, width, num_splits, True)
+        call("s360_window_attention_high_backward", q.device, *args, ptr(scratch), scratch.numel())
+    else:
+        call("s360_window_attention_backward", q.device, *args)
     return g_q, g_k, g_v
 
 
 class _WindowAttention(torch.autograd.Function):
     """out of (q, k, v); saves q, k, v and lse, nothing score-sized (the backward forms Delta from the recomputed probabilities,
-    so not even out is kept)."""
+    so not even out is kept) and, in the "high" mode, none of the bf16 planes (the backward splits again)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, height, width, num_splits, with_shift, mask_rule):
+    def forward(ctx, q, k, v, height, width, num_splits, with_shift, mask_rule, precision):
         q, k, v = (t.detach().contiguous() for t in (q, k, v))
-        opts = dict(height=height, width=width, num_splits=num_splits, with_shift=with_shift, mask_rule=mask_rule)
+        opts = dict(height=height, width=width, num_splits=num_splits, with_shift=with_shift, mask_rule=mask_rule, precision=precision)
         out, lse = attention_forward(q, k, v, **opts)
         ctx.save_for_backward(q, k, v, lse)
         ctx.opts = opts
@@ -113,11 +158,11 @@ class _WindowAttention(torch.autograd.Function):
     def backward(ctx, g_out):
         q, k, v, lse = ctx.saved_tensors
         grads = attention_backward(q, k, v, lse, g_out.to(torch.float32), needs=tuple(ctx.needs_input_grad[:3]), **ctx.opts)
-        return (*grads, None, None, None, None, None)
+        return (*grads, None, None, None, None, None, None)
 
 
 def window_attention(q: Tensor, k: Tensor, v: Tensor, *, height: int, width: int, num_splits: int, with_shift: bool = False,
-                     mask_rule: str = "reference") -> Tensor:
+                     mask_rule: str = "reference", precision: str = "highest") -> Tensor:
     """The reference's single_head_split_window_attention (multiview_transformer.py:60-210) without its temporaries.
 
     q [B, L, C] with L = height * width tokens in (y, x) order; k, v [B, L, C] (the same-shape branch) or [B, m, L, C] (the
@@ -125,22 +170,25 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, *, height: int, width: int
     (width / num_splits); with_shift rolls the grid by half a window first and masks pairs from different regions with the
     reference's FINITE -100.0.  mask_rule "reference" reproduces the reference's `attn_mask.repeat(b, 1, m)`, which gives key
     column j the region of window token j mod Lw; "aligned" gives it the region of its own token j // m.  The two coincide at
-    m <= 1 and without shift.  Returns out [B, L, C] in the original token order.  Differentiable (once) in q, k and v.
-    Float32 GPU tensors, C a multiple of 32 in [32, 128]; no CPU path; non-contiguous inputs are copied once."""
+    m <= 1 and without shift.  precision "highest": exact float32 products; "high": bf16x3 products on the bf16 MFMA, forward
+    and backward (the module's docstring).  Returns out [B, L, C] in the original token order.  Differentiable (once) in q, k
+    and v.  Float32 GPU tensors, C a multiple of 32 in [32, 128]; no CPU path; non-contiguous inputs are copied once."""
+    _precision(precision)
     _rule(mask_rule)
     _checked("window_attention", q, k, v, height, width, num_splits)
-    return _WindowAttention.apply(q, k, v, int(height), int(width), int(num_splits), bool(with_shift), mask_rule)
+    return _WindowAttention.apply(q, k, v, int(height), int(width), int(num_splits), bool(with_shift), mask_rule, precision)
 
 
-def full_attention(q: Tensor, k: Tensor, v: Tensor) -> Tensor:
+def full_attention(q: Tensor, k: Tensor, v: Tensor, precision: str = "highest") -> Tensor:
     """The reference's single_head_full_attention (multiview_transformer.py:8-16) for Lq == Lk: softmax(q k^T / sqrt(C)) v over all
     tokens of a batch element, as one window without shift."""
+    _precision(precision)
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, Tensor) or t.dim() != 3:
             raise ValueError(f"full_attention expects {name} [B, L, C]")
     if tuple(k.shape) != tuple(q.shape):
         raise ValueError(f"full_attention needs Lq == Lk: q {tuple(q.shape)}, k {tuple(k.shape)}")
-    return window_attention(q, k, v, height=1, width=int(q.shape[1]), num_splits=1)
+    return window_attention(q, k, v, height=1, width=int(q.shape[1]), num_splits=1, precision=precision)
 
 
 class ShiftMask:

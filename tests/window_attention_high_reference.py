@@ -1,0 +1,80 @@
+"""The yardstick of the window attention's "high" precision mode (splatter360_amd/window_attention.py, precision="high"): the
+function of tests/window_attention_reference.py with each of its six products as a bf16x3 product of split operands, every sum
+in float64.  What the kernels and this file share is the specification:
+
+  split(x)   hi = bf16(x), round to nearest even; lo = bf16(x - float32(hi)); the difference is exact in float32
+  product    A B = Ah Bh + Ah Bl + Al Bh (terms=3); Al Bl is dropped.  terms=1 keeps Ah Bh alone: a single-bf16 product, the
+             arithmetic a kernel that lost its lo planes would compute — tests/test_window_attention_high_spec.py shows that
+             the accuracy bound of the GPU test tells the two apart.
+
+Both operands of every product are split from their float32 values: q, k, v, g_out, and P, dS as the float64 softmax and its
+backward leave them.
+"""
+import torch
+
+import window_attention_reference as R
+
+
+def split(x):
+    """(hi, lo) of a float32 tensor, both bfloat16."""
+    assert x.dtype == torch.float32
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.to(torch.float32)).to(torch.bfloat16)
+    return hi, lo
+
+
+def _product(a, b, terms):
+    """a [..., n, k] times b [..., k, m], float64 in and out: the operands rounded to float32, split, the terms summed in float64."""
+    (ah, al), (bh, bl) = (tuple(t.double() for t in split(x.to(torch.float32))) for x in (a, b))
+    out = ah @ bh
+    if terms == 3:
+        out = out + ah @ bl + al @ bh
+    return out
+
+
+class HighProduct(torch.autograd.Function):
+    """a @ b as a high product, and both backward products (g b^T, a^T g) as high products of their own split operands."""
+
+    @staticmethod
+    def forward(ctx, a, b, terms):
+        assert terms in (1, 3)
+        ctx.save_for_backward(a, b)
+        ctx.terms = terms
+        return _product(a, b, terms)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        return _product(g, b.transpose(-1, -2), ctx.terms), _product(a.transpose(-1, -2), g, ctx.terms), None
+
+
+def split_statement(q, k, v, num_splits, shift, h, w, rule="reference", terms=3):
+    """R.statement with high products: q [B, L, C], k / v [B, L, C] or [B, m, L, C] float32 -> out [B, L, C] float64;
+    differentiable (g_q = dS K, g_k = dS^T Q, g_v = P^T G and dP = G V^T are high products too)."""
+    assert rule in ("reference", "aligned")
+    q, k, v = (t.double() for t in (q, k, v))
+    if k.dim() == 3:
+        k, v = k.unsqueeze(1), v.unsqueeze(1)
+    b, l, c = q.shape
+    m = k.shape[1]
+    assert l == h * w and h % num_splits == 0 and w % num_splits == 0
+    tok, region = R.window_index(h, w, num_splits, shift, q.device)
+    nw, lw = tok.shape
+    qw = q[:, tok]                                              # [B, K^2, Lw, C]
+    kw, vw = (t[:, :, tok].permute(0, 2, 3, 1, 4).reshape(b, nw, lw * m, c) for t in (k, v))      # key j = p m + u
+    scores = HighProduct.apply(qw, kw.transpose(-1, -2), terms) / (c ** 0.5)
+    if shift:
+        j = torch.arange(lw * m, device=q.device)
+        key_region = region[:, j % lw] if rule == "reference" else region[:, j // m]
+        differ = region.unsqueeze(2) != key_region.unsqueeze(1)
+        scores = scores + torch.where(differ, R.MASK_VALUE, 0.0).to(scores.dtype)
+    ow = HighProduct.apply(torch.softmax(scores, dim=-1), vw, terms)                              # [B, K^2, Lw, C]
+    back = torch.empty(l, dtype=torch.long, device=q.device)
+    back[tok.reshape(-1)] = torch.arange(l, device=q.device)
+    return ow.reshape(b, l, c)[:, back]
+
+
+def errors(x, want):
+    """(max, mean) absolute error of x against the float64 `want`."""
+    e = (x.double() - want).abs()
+    return e.max().item(), e.mean().item()
