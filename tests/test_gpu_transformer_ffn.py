@@ -19,6 +19,9 @@ chunks added), dz W2c in chains of 64 values, and X W1c^T in chains of 64 values
 the rounding of a pre-activation that is a small difference of large terms (inputs of scale 6) into an error of dH: g_w1 of `tiny`
 at scale 6 stood at 1.67 x, of `constant_row` at 1.52 x; with chains of 32 values they are 0.66 x and 0.71 x.
 Memory at T = 32 768: forward + backward rise 108.5 MiB (0.85 of one hidden tensor); the float32 lines 464.8 MiB (3.63).
+Every accuracy case here is one workgroup of the token-owned kernels and one tile per weight chunk, pooled into one maximum and one
+mean per tensor: tests/test_gpu_transformer_ffn_float64.py holds the same kernels per row at the sizes past that (a second and
+third workgroup, two and three tiles per chunk, both grid strides), with sentinels around every buffer.
 """
 import functools
 import sys

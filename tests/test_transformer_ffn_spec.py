@@ -167,7 +167,9 @@ def test_the_header_declares_the_entries_and_the_library_exports_them():
 
 def test_the_host_only_entries_and_the_argument_checks_need_no_gpu():
     """The scratch size is fixed beyond sixteen chunks; unsupported widths, null pointers and sizes < 1 are refused before any GPU
-    work (the refusals below would otherwise fail on a machine without one)."""
+    work (the refusals below would otherwise fail on a machine without one).  The two backward entries likewise: an output that
+    aliases an input, another output or the scratch, a pointer that is not 16-byte aligned, a null pointer, a scratch one byte
+    short (S360_E_WORKSPACE) and unsupported widths, every one with nothing else wrong in the call."""
     import ctypes as C
     lib = _lib.lib()
     assert lib.s360_ffn_tail_scratch_bytes(0) == 0 and lib.s360_ffn_tail_scratch_bytes(-3) == 0
@@ -183,3 +185,48 @@ def test_the_host_only_entries_and_the_argument_checks_need_no_gpu():
     assert fwd(1 << 24, 128, 1024, *[p] * 8) == -1                                  # 2^31 elements
     assert lib.s360_layer_norm_residual_forward(p, p, p, p, 4, 96, eps, C.c_void_p(8192), C.c_void_p(16384), None) == -4
     assert lib.s360_layer_norm_residual_forward(p, p, p, p, 4, 128, None, C.c_void_p(8192), C.c_void_p(16384), None) == -1
+    # the backward entries: eleven inputs, the scratch and eight outputs (the no_ffn tail: four, the scratch and four), every one
+    # at an address of its own, then one thing wrong per call
+    tokens = 545
+    need = lib.s360_ffn_tail_scratch_bytes(tokens)
+    at = lambda i: 4096 * (i + 1)                                                   # noqa: E731
+    ins, scratch, outs = [at(i) for i in range(11)], at(11), [at(12 + i) for i in range(8)]
+
+    def bwd(ins=ins, scratch=scratch, outs=outs, tokens=tokens, c=128, h=1024, eps=eps, scratch_bytes=need):
+        v = lambda a: None if a is None else C.c_void_p(a)                          # noqa: E731
+        return lib.s360_ffn_tail_backward(*map(v, ins), tokens, c, h, eps, v(scratch), scratch_bytes, *map(v, outs), None)
+
+    swap = lambda xs, i, a: [*xs[:i], a, *xs[i + 1:]]                                # noqa: E731
+    assert bwd(scratch_bytes=need - 1) == -2 and bwd(scratch_bytes=0) == -2        # S360_E_WORKSPACE
+    assert bwd(tokens=0) == -1 and bwd(tokens=1 << 24) == -1 and bwd(eps=None) == -1
+    assert bwd(c=64, h=512) == -4 and bwd(h=512) == -4 and bwd(c=96) == -4          # unsupported widths
+    for i in range(8):
+        assert bwd(outs=swap(outs, i, None)) == -1, i                               # a null gradient pointer
+        assert bwd(outs=swap(outs, i, outs[i] + 8)) == -1, i                        # 8-byte aligned only
+        assert bwd(outs=swap(outs, i, scratch)) == -1, i                            # a gradient in the scratch
+        for j in range(11):
+            assert bwd(outs=swap(outs, i, ins[j])) == -1, (i, j)                    # an output that aliases an input
+        for j in range(i + 1, 8):
+            assert bwd(outs=swap(outs, i, outs[j])) == -1, (i, j)                   # two outputs that alias each other
+    for j in range(11):
+        assert bwd(ins=swap(ins, j, None)) == -1 and bwd(ins=swap(ins, j, ins[j] + 4)) == -1, j
+        assert bwd(scratch=ins[j]) == -1, j
+    assert bwd(scratch=None) == -1 and bwd(scratch=scratch + 8) == -1
+    nins, nouts = ins[:4], outs[:4]
+
+    def nbwd(ins=nins, scratch=scratch, outs=nouts, tokens=tokens, c=128, scratch_bytes=need):
+        v = lambda a: None if a is None else C.c_void_p(a)                          # noqa: E731
+        return lib.s360_layer_norm_residual_backward(*map(v, ins), tokens, c, v(scratch), scratch_bytes, *map(v, outs), None)
+
+    assert nbwd(scratch_bytes=need - 1) == -2 and nbwd(tokens=0) == -1 and nbwd(tokens=1 << 24) == -1
+    assert nbwd(c=96) == -4 and nbwd(c=64) == -4
+    for i in range(4):
+        assert nbwd(outs=swap(nouts, i, None)) == -1 and nbwd(outs=swap(nouts, i, nouts[i] + 8)) == -1, i
+        assert nbwd(outs=swap(nouts, i, scratch)) == -1, i
+        for j in range(4):
+            assert nbwd(outs=swap(nouts, i, nins[j])) == -1, (i, j)
+        for j in range(i + 1, 4):
+            assert nbwd(outs=swap(nouts, i, nouts[j])) == -1, (i, j)
+    for j in range(4):
+        assert nbwd(ins=swap(nins, j, None)) == -1 and nbwd(ins=swap(nins, j, nins[j] + 4)) == -1 and nbwd(scratch=nins[j]) == -1, j
+    assert nbwd(scratch=None) == -1 and nbwd(scratch=scratch + 8) == -1
