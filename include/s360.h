@@ -1126,6 +1126,31 @@ int s360_ffn_tail_backward(const float* source, const float* m, const float* nor
                            const float* g_out, int32_t tokens, int32_t channels, int32_t hidden, const double* eps, void* scratch,
                            size_t scratch_bytes, float* g_source, float* g_m, float* g_w1, float* g_w2, float* g_norm1_weight,
                            float* g_norm1_bias, float* g_norm2_weight, float* g_norm2_bias, void* stream);
+/*
+ * The "high" precision mode of the FFN tail: the same function and the same tensors with the two products of the forward and the
+ * four of the backward as bf16x3 products on v_mfma_f32_32x32x16_bf16 — each float32 operand the sum of two bfloat16 numbers
+ * (hi = bf16(x) round to nearest even, lo = bf16(x - hi)), A B = Ah Bh + Ah Bl + Al Bh accumulated in float32 by the MFMA — which
+ * is what torch.set_float32_matmul_precision('high') asks for.  The LayerNorm rows, statistics and parameter gradients stay
+ * float64, h, z, dz and dpre are rounded to float32 as above, the launch geometry, the partials and the last launch are those
+ * above.  A pre-pass (one launch per call) splits w1 and w2 into bf16 planes at the start of `scratch`, each in the two layouts
+ * its two uses need: 3 MiB whatever tokens.  The token-side operands are split in registers and LDS: no plane grows with tokens.
+ * s360_ffn_tail_high_scratch_bytes(tokens, backward): the planes (backward == 0) or the planes and s360_ffn_tail_scratch_bytes
+ * (backward != 0); 0 for tokens < 1.  The contents need no initialisation and nothing in it is read by a later call: the backward
+ * splits again.  z and stats of a "high" forward go to the "high" backward.
+ * Refusals as s360_ffn_tail_*, and for the forward's scratch as for the backward's: null or not 16-byte aligned S360_E_BADARG,
+ * smaller than reported S360_E_WORKSPACE, both before any GPU work.  No atomics, no host synchronisation, bit-identical from run
+ * to run and across streams.
+ */
+size_t s360_ffn_tail_high_scratch_bytes(int32_t tokens, int32_t backward);
+int s360_ffn_tail_high_forward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias, const float* w1,
+                               const float* w2, const float* norm2_weight, const float* norm2_bias, int32_t tokens, int32_t channels,
+                               int32_t hidden, const double* eps, float* out, float* z, double* stats, void* scratch,
+                               size_t scratch_bytes, void* stream);
+int s360_ffn_tail_high_backward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias, const float* w1,
+                                const float* w2, const float* norm2_weight, const float* norm2_bias, const float* z, const double* stats,
+                                const float* g_out, int32_t tokens, int32_t channels, int32_t hidden, const double* eps, void* scratch,
+                                size_t scratch_bytes, float* g_source, float* g_m, float* g_w1, float* g_w2, float* g_norm1_weight,
+                                float* g_norm1_bias, float* g_norm2_weight, float* g_norm2_bias, void* stream);
 int s360_layer_norm_residual_forward(const float* x, const float* weight, const float* bias, const float* residual, int32_t tokens,
                                      int32_t channels, const double* eps, float* out, double* stats, void* stream);
 int s360_layer_norm_residual_backward(const float* x, const float* weight, const double* stats, const float* g_out, int32_t tokens,

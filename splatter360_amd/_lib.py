@@ -135,6 +135,9 @@ SIGNATURES = {
     "s360_ffn_tail_weight_chunks": (_int, [_i32]),
     "s360_ffn_tail_forward": (_int, [_vp] * 8 + [_i32] * 3 + [_pf64] + [_vp] * 4),
     "s360_ffn_tail_backward": (_int, [_vp] * 11 + [_i32] * 3 + [_pf64, _vp, _sz] + [_vp] * 9),
+    "s360_ffn_tail_high_scratch_bytes": (_sz, [_i32, _i32]),
+    "s360_ffn_tail_high_forward": (_int, [_vp] * 8 + [_i32] * 3 + [_pf64] + [_vp] * 4 + [_sz, _vp]),
+    "s360_ffn_tail_high_backward": (_int, [_vp] * 11 + [_i32] * 3 + [_pf64, _vp, _sz] + [_vp] * 9),
     "s360_layer_norm_residual_forward": (_int, [_vp] * 4 + [_i32, _i32, _pf64] + [_vp] * 3),
     "s360_layer_norm_residual_backward": (_int, [_vp] * 4 + [_i32, _i32, _vp, _sz] + [_vp] * 5),
     "s360_count_backward_slots": (_int, [_prm, _vp, _sz, _vp, _vp]),

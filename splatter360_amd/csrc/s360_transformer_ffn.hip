@@ -655,3 +655,541 @@ extern "C" int s360_layer_norm_residual_backward(const float* x, const float* we
                        nullptr, ln_part, wgs, nln, lo);
     return s360_launch_status();
 }
+
+// ---------------------------------------------------------------------------------------------- the "high" mode (bf16 x 3)
+// The same function with its two products, and the four of the backward, as bf16x3 products on v_mfma_f32_32x32x16_bf16:
+// split(x) = (hi, lo), hi = bf16(x) round-to-nearest-even, lo = bf16(x - float32(hi)); A B = Ah Bh + Ah Bl + Al Bh, both operands
+// split from their float32 values, accumulated in float32 by the MFMA over the whole k range (no float64 chain sums: the split's
+// error is far above the float32 chain's).  The LayerNorm rows, their statistics and the parameter gradients' partial sums are
+// float64 as above; h, z, dz and dpre are rounded to float32 where the kernels above round them.
+// A pre-pass (k_ffh_split, one launch) splits W1 and W2 once per call into bf16 planes in the caller's scratch, each in the two
+// layouts its two uses need (3 MiB, whatever T): w1_r [8C][2C] for X W1^T (a lane reads 8 consecutive channels of a unit's row),
+// w1_t [2C][8C] for dpre W1 (2 x 4 consecutive units of a channel's row: the k permutation of an accumulator tile used as the
+// B operand, s360_window_attention.hip), w2_r [C][8C] for h W2^T and w2_t [8C][C] for dz W2.  The kernels read the planes from
+// global memory (L1 / L2: 3 MiB shared by every workgroup), so the token-owned kernels have no staging and no barrier in the walk
+// over the hidden width.  The token side is split where it is produced: X and dz in registers / the lane's own LDS slots, h and
+// dpre register by register from the accumulator tile, the weight-owned pass's X and dz tiles as they are staged in LDS (rows
+// and transposed).  No plane that grows with T exists.  Orientation, launch geometry, partials and k_ff_reduce are those above.
+// A product's three terms are issued in one order of (weight, token-side) terms — (wh, th), (wh, tl), (wl, th) — whichever side
+// is the A operand (SWAP).
+namespace s360 {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr size_t FFH_W1 = (size_t)FF_H * FF_X, FFH_W2 = (size_t)FF_C * FF_H;
+constexpr size_t FFH_PLANE_BYTES = 2 * 2 * (FFH_W1 + FFH_W2) * sizeof(__bf16);   // two layouts x (hi, lo) of both weights
+constexpr int FFH_LDR = FF_X + 8;                             // row stride of the staged X tile [32][2C] (bf16; rows 16-byte aligned)
+constexpr int FFH_LDD = FF_C + 8;                             // of the staged dz tile [32][C]
+constexpr int FFH_LDT = FF_T + 4;                             // of the transposed tiles [2C][32], [C][32] (rows 8-byte aligned)
+
+struct FFHPlanes {
+    __bf16 *w1_rh, *w1_rl, *w1_th, *w1_tl, *w2_rh, *w2_rl, *w2_th, *w2_tl;
+};
+
+__device__ __forceinline__ void ffh_split(float x, __bf16& hi, __bf16& lo) {
+    hi = (__bf16)x;
+    lo = (__bf16)(x - (float)hi);
+}
+__device__ __forceinline__ void ffh_split8(const float* x, bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        __bf16 h, l;
+        ffh_split(x[j], h, l);
+        hi[j] = h;
+        lo[j] = l;
+    }
+}
+
+// 8 consecutive bf16 (p 16-byte aligned)
+__device__ __forceinline__ bf16x8 ffh_ld8(const __bf16* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p)); }
+// p[0 .. 3] and p[8 .. 11] (p 8-byte aligned): the A fragment that goes with registers 8 s .. 8 s + 7 of an accumulator tile as
+// the B operand, p at tile row 16 s + 4 hf
+__device__ __forceinline__ bf16x8 ffh_ld44(const __bf16* p) {
+    const uint2 u0 = *reinterpret_cast<const uint2*>(p), u1 = *reinterpret_cast<const uint2*>(p + 8);
+    return __builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y));
+}
+// 8 consecutive floats (p 16-byte aligned), zeros unless valid
+__device__ __forceinline__ void ffh_load8(const float* p, bool valid, float* x) {
+    float4 u = make_float4(0.f, 0.f, 0.f, 0.f), v = u;
+    if (valid) u = *reinterpret_cast<const float4*>(p), v = *reinterpret_cast<const float4*>(p + 4);
+    x[0] = u.x, x[1] = u.y, x[2] = u.z, x[3] = u.w, x[4] = v.x, x[5] = v.y, x[6] = v.z, x[7] = v.w;
+}
+
+// one k-step of 16: acc += A B in three terms.  SWAP = false: A is the weight; true: B is
+template <bool SWAP>
+__device__ __forceinline__ f32x16 ffh_mfma3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x16 acc) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+    if constexpr (SWAP) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+    } else {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+__device__ __forceinline__ f32x16 ffh_zero() {
+    f32x16 t;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t[r] = 0.f;
+    return t;
+}
+
+// the lane's column of a 32 x 32 accumulator tile as the B operand of the next product: two k-steps of 16, split here
+__device__ __forceinline__ void ffh_split_tile(const float* t, bf16x8* hi, bf16x8* lo) {
+    ffh_split8(t, hi[0], lo[0]);
+    ffh_split8(t + 8, hi[1], lo[1]);
+}
+
+// The pre-pass: element i of W1 (then of W2) into its four planes.
+__global__ __launch_bounds__(S360_BLOCK) void k_ffh_split(const float* __restrict__ w1, const float* __restrict__ w2, FFHPlanes pl) {
+    const size_t i = (size_t)blockIdx.x * S360_BLOCK + threadIdx.x;
+    __bf16 h, l;
+    if (i < FFH_W1) {
+        const size_t unit = i / FF_X, c = i % FF_X;
+        ffh_split(w1[i], h, l);
+        pl.w1_rh[i] = h, pl.w1_rl[i] = l;
+        pl.w1_th[c * FF_H + unit] = h, pl.w1_tl[c * FF_H + unit] = l;
+    } else if (i < FFH_W1 + FFH_W2) {
+        const size_t k = i - FFH_W1, c = k / FF_H, unit = k % FF_H;
+        ffh_split(w2[k], h, l);
+        pl.w2_rh[k] = h, pl.w2_rl[k] = l;
+        pl.w2_th[unit * FF_C + c] = h, pl.w2_tl[unit * FF_C + c] = l;
+    }
+}
+
+// the lane's float64 (mean, rstd) of its token's m row: lane half hf sums channels 16 s + 8 hf + j, the halves are added
+__device__ __forceinline__ void ffh_row_stats(const float* m_row, bool valid, int hf, double eps, double& mean, double& rstd) {
+    float v[FF_C / 2];
+#pragma unroll
+    for (int s = 0; s < FF_C / 16; ++s) ffh_load8(m_row + 16 * s + 8 * hf, valid, v + 8 * s);
+    double sum = 0.0, sq = 0.0;
+#pragma unroll
+    for (int i = 0; i < FF_C / 2; ++i) sum += (double)v[i];
+    sum += __shfl_xor(sum, 32);
+    mean = sum * FF_INV_C;
+#pragma unroll
+    for (int i = 0; i < FF_C / 2; ++i) {
+        const double d = valid ? (double)v[i] - mean : 0.0;
+        sq += d * d;
+    }
+    sq += __shfl_xor(sq, 32);
+    rstd = 1.0 / sqrt(sq * FF_INV_C + eps);
+}
+
+// the token's row of X = [source, LN1(m)] as the B fragments of 16 k-steps: element j of step s is channel 16 s + 8 hf + j
+__device__ __forceinline__ void ffh_load_x(const FFArgs& a, int token, bool valid, int hf, double mean, double rstd, bf16x8* xh, bf16x8* xl) {
+    const size_t row = (size_t)token * FF_C;
+#pragma unroll
+    for (int s = 0; s < FF_C / 16; ++s) {
+        float v[8];
+        ffh_load8(a.source + row + 16 * s + 8 * hf, valid, v);
+        ffh_split8(v, xh[s], xl[s]);
+        ffh_load8(a.m + row + 16 * s + 8 * hf, valid, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = 16 * s + 8 * hf + j;
+            v[j] = valid ? ff_norm(v[j], mean, rstd, a.n1w[c], a.n1b[c]) : 0.f;
+        }
+        ffh_split8(v, xh[FF_C / 16 + s], xl[FF_C / 16 + s]);
+    }
+}
+
+// (X W1c^T)^T for the 32 units from j0: rows = hidden units, lane = token; w1h / w1l: the lane's row l31 of w1_r at channel 8 hf
+__device__ __forceinline__ f32x16 ffh_pre(const __bf16* w1h, const __bf16* w1l, int j0, const bf16x8* xh, const bf16x8* xl) {
+    f32x16 t = ffh_zero();
+#pragma unroll
+    for (int s = 0; s < FF_X / 16; ++s)
+        t = ffh_mfma3<false>(ffh_ld8(w1h + (size_t)j0 * FF_X + 16 * s), ffh_ld8(w1l + (size_t)j0 * FF_X + 16 * s), xh[s], xl[s], t);
+    return t;
+}
+
+// Forward, as k_ff_forward: 32 tokens per wave on the lanes, the hidden width in 32 chunks of 32 units.  Held to 256 registers (two
+// waves per SIMD: one wave's erfc runs under the other's MFMAs and loads; 0.66 -> 0.54 ms at 65 536 tokens) at the price of 6
+// spilled registers, outside the loop over the chunks.
+__global__ __launch_bounds__(S360_BLOCK, 2) void k_ffh_forward(FFArgs a, FFHPlanes pl, float* __restrict__ out, float* __restrict__ z,
+                                                               double* __restrict__ stats) {
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const int token = blockIdx.x * FF_TM + wave * FF_T + l31;
+    const bool valid = token < a.T;
+    double mean1, rstd1;
+    ffh_row_stats(a.m + (size_t)token * FF_C, valid, hf, a.eps, mean1, rstd1);
+    bf16x8 xh[FF_X / 16], xl[FF_X / 16];
+    ffh_load_x(a, token, valid, hf, mean1, rstd1, xh, xl);
+    f32x16 zt[FF_C / FF_T];
+#pragma unroll
+    for (int ct = 0; ct < FF_C / FF_T; ++ct) zt[ct] = ffh_zero();
+    const __bf16* w1h = pl.w1_rh + l31 * FF_X + 8 * hf;
+    const __bf16* w1l = pl.w1_rl + l31 * FF_X + 8 * hf;
+    const __bf16* w2h = pl.w2_rh + l31 * FF_H + 4 * hf;
+    const __bf16* w2l = pl.w2_rl + l31 * FF_H + 4 * hf;
+    for (int j0 = 0; j0 < FF_H; j0 += FF_T) {
+        const f32x16 pre = ffh_pre(w1h, w1l, j0, xh, xl);
+        float h[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) h[r] = ff_gelu(pre[r]);
+        bf16x8 hh[2], hl[2];
+        ffh_split_tile(h, hh, hl);
+#pragma unroll
+        for (int ct = 0; ct < FF_C / FF_T; ++ct)              // z^T += W2c h^T
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                zt[ct] = ffh_mfma3<false>(ffh_ld44(w2h + ct * FF_T * FF_H + j0 + 16 * s), ffh_ld44(w2l + ct * FF_T * FF_H + j0 + 16 * s),
+                                          hh[s], hl[s], zt[ct]);
+    }
+    // norm2 over the float32 z, the residual, the writes: as k_ff_forward
+    double sum = 0.0, sq = 0.0;
+#pragma unroll
+    for (int ct = 0; ct < FF_C / FF_T; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sum += (double)zt[ct][r];
+    sum += __shfl_xor(sum, 32);
+    const double mean2 = sum * FF_INV_C;
+#pragma unroll
+    for (int ct = 0; ct < FF_C / FF_T; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const double d = (double)zt[ct][r] - mean2;
+            sq += d * d;
+        }
+    sq += __shfl_xor(sq, 32);
+    const double rstd2 = 1.0 / sqrt(sq * FF_INV_C + a.eps);
+    if (!valid) return;
+#pragma unroll
+    for (int ct = 0; ct < FF_C / FF_T; ++ct)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int c0 = ct * FF_T + 8 * q + 4 * hf;
+            const size_t at = (size_t)token * FF_C + c0;
+            const float4 sv = *reinterpret_cast<const float4*>(a.source + at);
+            const float4 wv = *reinterpret_cast<const float4*>(a.n2w + c0);
+            const float4 bv = *reinterpret_cast<const float4*>(a.n2b + c0);
+            const float zr[4] = {zt[ct][4 * q], zt[ct][4 * q + 1], zt[ct][4 * q + 2], zt[ct][4 * q + 3]};
+            float4 o;
+            o.x = sv.x + ff_norm(zr[0], mean2, rstd2, wv.x, bv.x);
+            o.y = sv.y + ff_norm(zr[1], mean2, rstd2, wv.y, bv.y);
+            o.z = sv.z + ff_norm(zr[2], mean2, rstd2, wv.z, bv.z);
+            o.w = sv.w + ff_norm(zr[3], mean2, rstd2, wv.w, bv.w);
+            *reinterpret_cast<float4*>(out + at) = o;
+            *reinterpret_cast<float4*>(z + at) = make_float4(zr[0], zr[1], zr[2], zr[3]);
+        }
+    if (hf == 0) {
+        stats[(size_t)token * 2] = mean1, stats[(size_t)token * 2 + 1] = rstd1;
+        stats[((size_t)a.T + token) * 2] = mean2, stats[((size_t)a.T + token) * 2 + 1] = rstd2;
+    }
+}
+
+// Backward, the pass owned by token tiles, as k_ff_backward_tokens; dX is one float32 MFMA accumulation over the hidden width.
+__global__ __launch_bounds__(S360_BLOCK) void k_ffh_backward_tokens(FFArgs a, FFHPlanes pl, const float* __restrict__ z,
+                                                                    const double* __restrict__ stats, const float* __restrict__ g_out,
+                                                                    float* __restrict__ g_source, float* __restrict__ g_m,
+                                                                    double* __restrict__ ln_part) {
+    __shared__ double s_wave[FF_WAVES][4 * FF_C];
+    __shared__ double s_ln[4 * FF_C];
+    __shared__ uint4 s_dz[FF_WAVES][2][FF_C / 16][S360_WAVE];  // dz's (hi, lo) fragments, each lane's 8 k-steps: written and read by that lane alone
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    for (int i = tid; i < 4 * FF_C; i += S360_BLOCK) s_ln[i] = 0.0;
+    const __bf16* w1h = pl.w1_rh + l31 * FF_X + 8 * hf;
+    const __bf16* w1l = pl.w1_rl + l31 * FF_X + 8 * hf;
+    const __bf16* w2th = pl.w2_th + l31 * FF_C + 8 * hf;
+    const __bf16* w2tl = pl.w2_tl + l31 * FF_C + 8 * hf;
+    const __bf16* w1th = pl.w1_th + l31 * FF_H + 4 * hf;
+    const __bf16* w1tl = pl.w1_tl + l31 * FF_H + 4 * hf;
+    const int ntiles = (a.T + FF_TM - 1) / FF_TM;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int token = tile * FF_TM + wave * FF_T + l31;
+        const bool valid = token < a.T;
+        const size_t row = (size_t)token * FF_C;
+        const double mean1 = valid ? stats[(size_t)token * 2] : 0.0, rstd1 = valid ? stats[(size_t)token * 2 + 1] : 0.0;
+        const double mean2 = valid ? stats[((size_t)a.T + token) * 2] : 0.0, rstd2 = valid ? stats[((size_t)a.T + token) * 2 + 1] : 0.0;
+        bf16x8 xh[FF_X / 16], xl[FF_X / 16];
+        ffh_load_x(a, token, valid, hf, mean1, rstd1, xh, xl);
+        {   // norm2's backward: element j of k-step s is channel 16 s + 8 hf + j
+            double s1 = 0.0, s2 = 0.0;
+            for (int s = 0; s < FF_C / 16; ++s) {
+                float g[8], zz[8];
+                ffh_load8(g_out + row + 16 * s + 8 * hf, valid, g);
+                ffh_load8(z + row + 16 * s + 8 * hf, valid, zz);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const double gy = (double)g[j] * (double)a.n2w[16 * s + 8 * hf + j];
+                    const double xn = valid ? ((double)zz[j] - mean2) * rstd2 : 0.0;
+                    s1 += gy, s2 += gy * xn;
+                }
+            }
+            s1 += __shfl_xor(s1, 32), s2 += __shfl_xor(s2, 32);
+            s1 *= FF_INV_C, s2 *= FF_INV_C;
+            for (int s = 0; s < FF_C / 16; ++s) {
+                float g[8], zz[8], d[8];
+                ffh_load8(g_out + row + 16 * s + 8 * hf, valid, g);
+                ffh_load8(z + row + 16 * s + 8 * hf, valid, zz);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int c = 16 * s + 8 * hf + j;
+                    const double gd = (double)g[j];
+                    const double xn = valid ? ((double)zz[j] - mean2) * rstd2 : 0.0;
+                    d[j] = (float)(rstd2 * (gd * (double)a.n2w[c] - s1 - xn * s2));
+                    const double pw = ff_sum32(gd * xn), pb = ff_sum32(gd);
+                    if (l31 == 0) s_wave[wave][2 * FF_C + c] = pw, s_wave[wave][3 * FF_C + c] = pb;
+                }
+                bf16x8 dh, dl;
+                ffh_split8(d, dh, dl);
+                s_dz[wave][0][s][lane] = __builtin_bit_cast(uint4, dh);
+                s_dz[wave][1][s][lane] = __builtin_bit_cast(uint4, dl);
+            }
+        }
+        f32x16 dx[FF_X / FF_T];                            // dX^T: tile ct, register r is channel 32 ct + mfma_acc_row(r, hf) of the lane's token
+#pragma unroll
+        for (int ct = 0; ct < FF_X / FF_T; ++ct) dx[ct] = ffh_zero();
+        for (int j0 = 0; j0 < FF_H; j0 += FF_T) {
+            const f32x16 pre = ffh_pre(w1h, w1l, j0, xh, xl);                   // X W1c^T again
+            f32x16 dh = ffh_zero();                                             // (dz W2c)^T
+#pragma unroll
+            for (int s = 0; s < FF_C / 16; ++s)
+                dh = ffh_mfma3<false>(ffh_ld8(w2th + (size_t)j0 * FF_C + 16 * s), ffh_ld8(w2tl + (size_t)j0 * FF_C + 16 * s),
+                                      __builtin_bit_cast(bf16x8, s_dz[wave][0][s][lane]), __builtin_bit_cast(bf16x8, s_dz[wave][1][s][lane]), dh);
+            float dp[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dp[r] = dh[r] * ff_gelu_grad(pre[r]);
+            bf16x8 ph[2], pw[2];
+            ffh_split_tile(dp, ph, pw);
+#pragma unroll
+            for (int ct = 0; ct < FF_X / FF_T; ++ct)          // dX^T += W1c^T dpre^T
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+                    dx[ct] = ffh_mfma3<false>(ffh_ld44(w1th + ct * FF_T * FF_H + j0 + 16 * s), ffh_ld44(w1tl + ct * FF_T * FF_H + j0 + 16 * s),
+                                              ph[s], pw[s], dx[ct]);
+        }
+        // g_source = g_out + dX[:, :C]
+        if (valid) {
+#pragma unroll
+            for (int ct = 0; ct < FF_C / FF_T; ++ct)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const size_t at = row + ct * FF_T + 8 * q + 4 * hf;
+                    const float4 g = *reinterpret_cast<const float4*>(g_out + at);
+                    *reinterpret_cast<float4*>(g_source + at) =
+                        make_float4(g.x + dx[ct][4 * q], g.y + dx[ct][4 * q + 1], g.z + dx[ct][4 * q + 2], g.w + dx[ct][4 * q + 3]);
+                }
+        }
+        {   // norm1's backward on dX[:, C:]
+            double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+            for (int ct = 0; ct < FF_C / FF_T; ++ct)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int c = ct * FF_T + mfma_acc_row(r, hf);
+                    const double gy = (double)dx[FF_C / FF_T + ct][r] * (double)a.n1w[c];
+                    const double xn = valid ? ((double)a.m[row + c] - mean1) * rstd1 : 0.0;
+                    s1 += gy, s2 += gy * xn;
+                }
+            s1 += __shfl_xor(s1, 32), s2 += __shfl_xor(s2, 32);
+            s1 *= FF_INV_C, s2 *= FF_INV_C;
+#pragma unroll
+            for (int ct = 0; ct < FF_C / FF_T; ++ct)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int c = ct * FF_T + mfma_acc_row(r, hf);
+                    const double g = (double)dx[FF_C / FF_T + ct][r];
+                    const double xn = valid ? ((double)a.m[row + c] - mean1) * rstd1 : 0.0;
+                    if (valid) g_m[row + c] = (float)(rstd1 * (g * (double)a.n1w[c] - s1 - xn * s2));
+                    const double pw = ff_sum32(g * xn), pb = ff_sum32(g);
+                    if (l31 == 0) s_wave[wave][c] = pw, s_wave[wave][FF_C + c] = pb;
+                }
+        }
+        __syncthreads();
+        for (int i = tid; i < 4 * FF_C; i += S360_BLOCK) {
+            double v = s_ln[i];
+#pragma unroll
+            for (int w = 0; w < FF_WAVES; ++w) v += s_wave[w][i];
+            s_ln[i] = v;
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    for (int i = tid; i < 4 * FF_C; i += S360_BLOCK) ln_part[(size_t)blockIdx.x * 4 * FF_C + i] = s_ln[i];
+}
+
+// Backward, the pass owned by (hidden group of 128 units, token chunk), as k_ff_backward_weights: a tile of 32 tokens is staged
+// in LDS as split bf16 — X [32][2C] and dz [32][C] by rows (the A operand of X W1c^T and dz W2c) and transposed (the A operand of
+// dpre^T X and dz^T h, whose B operand is the accumulator tile) — and the unit's W1 row and W2 column are read from the planes.
+__global__ __launch_bounds__(S360_BLOCK) void k_ffh_backward_weights(FFArgs a, FFHPlanes pl, const float* __restrict__ z,
+                                                                     const double* __restrict__ stats, const float* __restrict__ g_out,
+                                                                     int chunk_tokens, float* __restrict__ p_w1, float* __restrict__ p_w2) {
+    __shared__ __attribute__((aligned(16))) __bf16 s_xr[2][FF_T * FFH_LDR];
+    __shared__ __attribute__((aligned(16))) __bf16 s_dr[2][FF_T * FFH_LDD];
+    __shared__ __attribute__((aligned(16))) __bf16 s_xt[2][FF_X * FFH_LDT];
+    __shared__ __attribute__((aligned(16))) __bf16 s_dt[2][FF_C * FFH_LDT];
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const int j0 = (blockIdx.x * FF_WAVES + wave) * FF_T, chunk = blockIdx.y;
+    const int first = chunk * chunk_tokens, last = min(a.T, first + chunk_tokens);
+    const __bf16* w1h = pl.w1_rh + (size_t)(j0 + l31) * FF_X + 8 * hf;
+    const __bf16* w1l = pl.w1_rl + (size_t)(j0 + l31) * FF_X + 8 * hf;
+    const __bf16* w2th = pl.w2_th + (size_t)(j0 + l31) * FF_C + 8 * hf;
+    const __bf16* w2tl = pl.w2_tl + (size_t)(j0 + l31) * FF_C + 8 * hf;
+    f32x16 gw1[FF_X / FF_T], gw2[FF_C / FF_T];             // g_W1^T, g_W2: rows = channels, lane = hidden unit
+#pragma unroll
+    for (int ct = 0; ct < FF_X / FF_T; ++ct) gw1[ct] = ffh_zero();
+#pragma unroll
+    for (int ct = 0; ct < FF_C / FF_T; ++ct) gw2[ct] = ffh_zero();
+    const int slot = tid >> 5, l = tid & 31;
+    const float4 n1w = *reinterpret_cast<const float4*>(a.n1w + 4 * l), n1b = *reinterpret_cast<const float4*>(a.n1b + 4 * l);
+    const float4 n2w = *reinterpret_cast<const float4*>(a.n2w + 4 * l);
+    for (int t0 = first; t0 < last; t0 += FF_T) {
+        __syncthreads();                                      // the previous tile has been read
+#pragma unroll
+        for (int it = 0; it < FF_T / FF_ROWS; ++it) {
+            const int tl = it * FF_ROWS + slot, token = t0 + tl;
+            float4 sv = make_float4(0.f, 0.f, 0.f, 0.f), xv = sv, dv = sv;
+            if (token < last) {                               // uniform over the 32 lanes of a row
+                const size_t at = (size_t)token * FF_C + 4 * l;
+                sv = *reinterpret_cast<const float4*>(a.source + at);
+                xv = ff_norm4(*reinterpret_cast<const float4*>(a.m + at), stats[(size_t)token * 2], stats[(size_t)token * 2 + 1], n1w, n1b);
+                double xn[4];
+                dv = ff_row_backward(*reinterpret_cast<const float4*>(z + at), *reinterpret_cast<const float4*>(g_out + at), n2w,
+                                     stats[((size_t)a.T + token) * 2], stats[((size_t)a.T + token) * 2 + 1], xn);
+            }
+            const float xs[8] = {sv.x, sv.y, sv.z, sv.w, xv.x, xv.y, xv.z, xv.w}, ds[4] = {dv.x, dv.y, dv.z, dv.w};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int c = (i < 4 ? 0 : FF_C - 4) + 4 * l + i;
+                __bf16 h, lo;
+                ffh_split(xs[i], h, lo);
+                s_xr[0][tl * FFH_LDR + c] = h, s_xr[1][tl * FFH_LDR + c] = lo;
+                s_xt[0][c * FFH_LDT + tl] = h, s_xt[1][c * FFH_LDT + tl] = lo;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = 4 * l + i;
+                __bf16 h, lo;
+                ffh_split(ds[i], h, lo);
+                s_dr[0][tl * FFH_LDD + c] = h, s_dr[1][tl * FFH_LDD + c] = lo;
+                s_dt[0][c * FFH_LDT + tl] = h, s_dt[1][c * FFH_LDT + tl] = lo;
+            }
+        }
+        __syncthreads();
+        f32x16 pre = ffh_zero(), dh = ffh_zero();             // X W1c^T, dz W2c: rows = tokens, lane = hidden unit
+#pragma unroll
+        for (int s = 0; s < FF_X / 16; ++s)
+            pre = ffh_mfma3<true>(ffh_ld8(s_xr[0] + l31 * FFH_LDR + 16 * s + 8 * hf), ffh_ld8(s_xr[1] + l31 * FFH_LDR + 16 * s + 8 * hf),
+                                  ffh_ld8(w1h + 16 * s), ffh_ld8(w1l + 16 * s), pre);
+#pragma unroll
+        for (int s = 0; s < FF_C / 16; ++s)
+            dh = ffh_mfma3<true>(ffh_ld8(s_dr[0] + l31 * FFH_LDD + 16 * s + 8 * hf), ffh_ld8(s_dr[1] + l31 * FFH_LDD + 16 * s + 8 * hf),
+                                 ffh_ld8(w2th + 16 * s), ffh_ld8(w2tl + 16 * s), dh);
+        float dp[16], h[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            dp[r] = dh[r] * ff_gelu_grad(pre[r]);
+            h[r] = ff_gelu(pre[r]);
+        }
+        bf16x8 ph[2], pw[2], hh[2], hl[2];
+        ffh_split_tile(dp, ph, pw);
+        ffh_split_tile(h, hh, hl);
+#pragma unroll
+        for (int ct = 0; ct < FF_X / FF_T; ++ct)              // g_W1^T += X^T dpre
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                gw1[ct] = ffh_mfma3<true>(ffh_ld44(s_xt[0] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf),
+                                          ffh_ld44(s_xt[1] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf), ph[s], pw[s], gw1[ct]);
+#pragma unroll
+        for (int ct = 0; ct < FF_C / FF_T; ++ct)              // g_W2 += dz^T h
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                gw2[ct] = ffh_mfma3<true>(ffh_ld44(s_dt[0] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf),
+                                          ffh_ld44(s_dt[1] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf), hh[s], hl[s], gw2[ct]);
+    }
+    float* q1 = p_w1 + ((size_t)chunk * FF_H + j0 + l31) * FF_X;
+    float* q2 = p_w2 + (size_t)chunk * FF_C * FF_H + j0 + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+#pragma unroll
+        for (int ct = 0; ct < FF_X / FF_T; ++ct) q1[ct * FF_T + mfma_acc_row(r, hf)] = gw1[ct][r];
+#pragma unroll
+        for (int ct = 0; ct < FF_C / FF_T; ++ct) q2[(size_t)(ct * FF_T + mfma_acc_row(r, hf)) * FF_H] = gw2[ct][r];
+    }
+}
+
+// the planes in the first FFH_PLANE_BYTES of a scratch, and the pre-pass
+static FFHPlanes ffh_planes(void* scratch) {
+    __bf16* p = static_cast<__bf16*>(scratch);
+    FFHPlanes pl;
+    pl.w1_rh = p, pl.w1_rl = p + FFH_W1, pl.w1_th = p + 2 * FFH_W1, pl.w1_tl = p + 3 * FFH_W1;
+    p += 4 * FFH_W1;
+    pl.w2_rh = p, pl.w2_rl = p + FFH_W2, pl.w2_th = p + 2 * FFH_W2, pl.w2_tl = p + 3 * FFH_W2;
+    return pl;
+}
+static void ffh_split_launch(const float* w1, const float* w2, const FFHPlanes& pl, hipStream_t st) {
+    hipLaunchKernelGGL(k_ffh_split, dim3((unsigned)((FFH_W1 + FFH_W2 + S360_BLOCK - 1) / S360_BLOCK)), dim3(S360_BLOCK), 0, st, w1, w2, pl);
+}
+
+}  // namespace s360
+
+extern "C" size_t s360_ffn_tail_high_scratch_bytes(int32_t tokens, int32_t backward) {
+    if (tokens < 1) return 0;
+    return FFH_PLANE_BYTES + (backward ? s360_ffn_tail_scratch_bytes(tokens) : 0);
+}
+
+extern "C" int s360_ffn_tail_high_forward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias,
+                                          const float* w1, const float* w2, const float* norm2_weight, const float* norm2_bias,
+                                          int32_t tokens, int32_t channels, int32_t hidden, const double* eps, float* out, float* z,
+                                          double* stats, void* scratch, size_t scratch_bytes, void* stream) {
+    const void* in[] = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias};
+    for (const void* p : in)
+        if (!p || !s360_aligned(p, 16) || p == out || p == z || p == stats || p == scratch) return S360_E_BADARG;
+    if (!eps || !(*eps > 0.0) || !out || !z || !stats || out == z || !s360_aligned(out, 16) || !s360_aligned(z, 16)) return S360_E_BADARG;
+    if (!scratch || !s360_aligned(scratch, 16) || scratch == out || scratch == z || scratch == stats) return S360_E_BADARG;
+    const int rc = ff_sizes(tokens, channels, hidden);
+    if (rc != S360_OK) return rc;
+    if (scratch_bytes < s360_ffn_tail_high_scratch_bytes(tokens, 0)) return S360_E_WORKSPACE;
+    const FFArgs a = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, tokens, *eps};
+    const FFHPlanes pl = ffh_planes(scratch);
+    ffh_split_launch(w1, w2, pl, (hipStream_t)stream);
+    S360_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ffh_forward, dim3((tokens + FF_TM - 1) / FF_TM), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, pl, out, z, stats);
+    return s360_launch_status();
+}
+
+extern "C" int s360_ffn_tail_high_backward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias,
+                                           const float* w1, const float* w2, const float* norm2_weight, const float* norm2_bias,
+                                           const float* z, const double* stats, const float* g_out, int32_t tokens, int32_t channels,
+                                           int32_t hidden, const double* eps, void* scratch, size_t scratch_bytes, float* g_source,
+                                           float* g_m, float* g_w1, float* g_w2, float* g_norm1_weight, float* g_norm1_bias,
+                                           float* g_norm2_weight, float* g_norm2_bias, void* stream) {
+    const void* in[] = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, z, stats, g_out};
+    void* outs[] = {g_source, g_m, g_w1, g_w2, g_norm1_weight, g_norm1_bias, g_norm2_weight, g_norm2_bias, scratch};
+    for (const void* o : outs) {
+        if (!o || !s360_aligned(o, 16)) return S360_E_BADARG;
+        for (const void* p : in)
+            if (p == o) return S360_E_BADARG;
+    }
+    for (const void* p : in)
+        if (!p || !s360_aligned(p, 16)) return S360_E_BADARG;
+    for (int i = 0; i < 9; ++i)
+        for (int j = i + 1; j < 9; ++j)
+            if (outs[i] == outs[j]) return S360_E_BADARG;
+    if (!eps || !(*eps > 0.0)) return S360_E_BADARG;
+    const int rc = ff_sizes(tokens, channels, hidden);
+    if (rc != S360_OK) return rc;
+    if (scratch_bytes < s360_ffn_tail_high_scratch_bytes(tokens, 1)) return S360_E_WORKSPACE;
+    const FFArgs a = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, tokens, *eps};
+    hipStream_t st = (hipStream_t)stream;
+    const int chunks = ff_chunks(tokens), wgs = ff_token_wgs(tokens);
+    const FFHPlanes pl = ffh_planes(scratch);
+    float* p_w1 = reinterpret_cast<float*>(static_cast<char*>(scratch) + FFH_PLANE_BYTES);
+    float* p_w2 = p_w1 + (size_t)chunks * FF_H * FF_X;
+    double* ln_part = reinterpret_cast<double*>(p_w2 + (size_t)chunks * FF_C * FF_H);
+    ffh_split_launch(w1, w2, pl, st);
+    S360_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ffh_backward_tokens, dim3(wgs), dim3(S360_BLOCK), 0, st, a, pl, z, stats, g_out, g_source, g_m, ln_part);
+    S360_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ffh_backward_weights, dim3(FF_H / (FF_T * FF_WAVES), chunks), dim3(S360_BLOCK), 0, st, a, pl, z, stats, g_out,
+                       ff_chunk_tokens(tokens), p_w1, p_w2);
+    S360_CHECK_LAUNCH();
+    const int nw1 = FF_H * FF_X, nw2 = FF_C * FF_H, nln = 4 * FF_C;
+    const FFLnOut lo = {{g_norm1_weight, g_norm1_bias, g_norm2_weight, g_norm2_bias}};
+    hipLaunchKernelGGL(k_ff_reduce, dim3((nw1 + nw2 + nln + S360_BLOCK - 1) / S360_BLOCK), dim3(S360_BLOCK), 0, st, p_w1, p_w2, chunks, nw1,
+                       nw2, g_w1, g_w2, ln_part, wgs, nln, lo);
+    return s360_launch_status();
+}

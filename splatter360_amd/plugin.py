@@ -150,9 +150,12 @@ class _Seam:
 
     def install(self, **options):
         """Patch now if the module is imported, else put a _SeamPatcher on sys.meta_path.  Returns {name: function} or None.
-        A pending hook keeps the options of the call that placed it."""
+        A pending hook keeps the options of the call that placed it.  A wrapper that an earlier call built with other options
+        is taken out first and built again (patch() keeps a wrapper it finds), so `options` is what the bound wrapper runs with."""
         mod = sys.modules.get(self.module)
         if self.ready(mod):
+            if self.context and options != self.options:
+                self.restore()
             self.options = options
             return self.patch(mod)
         if not any(isinstance(f, _SeamPatcher) and f.seam is self for f in sys.meta_path):
@@ -599,10 +602,11 @@ def _native_map_pdf_to_opacity(replaced):
 
 
 class _MethodSeam(_Seam):
-    """A seam on a method: `names` are attributes of the class `cls_name` that `module` defines."""
+    """A seam on a method: `names` are attributes of the class `cls_name` that `module` defines.  context=True: as in _Seam, the
+    wrapper takes the defining module and the seam's options."""
 
-    def __init__(self, keyword, module, cls_name, names, wrappers):
-        super().__init__(keyword, module, names, (), wrappers)
+    def __init__(self, keyword, module, cls_name, names, wrappers, context=False):
+        super().__init__(keyword, module, names, (), wrappers, context)
         self.cls_name = cls_name
 
     def ready(self, mod) -> bool:
@@ -613,7 +617,10 @@ class _MethodSeam(_Seam):
         cls, out = getattr(mod, self.cls_name), {}
         for name in self.names:
             cur = cls.__dict__.get(name, getattr(cls, name))
-            out[name] = cur if getattr(cur, "replaced", None) is not None else self.wrappers[name](cur)
+            if getattr(cur, "replaced", None) is not None:
+                out[name] = cur
+            else:
+                out[name] = self.wrappers[name](cur, mod, **self.options) if self.context else self.wrappers[name](cur)
             setattr(cls, name, out[name])
         return out
 
@@ -1011,14 +1018,26 @@ def _transformer_ffn_call(layer, source, target, kwargs) -> bool:
     return _affine_norm(getattr(layer, "norm2", None), c) and layer.norm2.eps == layer.norm1.eps
 
 
-def _native_transformer_layer_forward(replaced):
+def _transformer_ffn_precision(precision) -> str:
+    """The `precision` option of the transformer-FFN seam, checked when the seam is installed: "highest", "high", or "torch"
+    (window_attention.resolve_precision reads torch's float32 matmul precision at every call)."""
+    from . import transformer_ffn as _tf
+    if precision != "torch" and precision not in _tf.PRECISIONS:
+        raise ValueError(f"transformer_ffn_precision is one of {[*_tf.PRECISIONS, 'torch']}, got {precision!r}")
+    return precision
+
+
+def _native_transformer_layer_forward(replaced, mod=None, precision="highest"):
     """TransformerLayer.forward with the reference's signature: for the calls _transformer_ffn_call accepts, the layer's own
     q_proj / k_proj / v_proj, the attention function the replaced method would call — looked up in the module's globals at call
     time, so the window-attention seam composes in either installation order — the layer's own merge, and then
     transformer_ffn.ffn_tail (layer_norm_residual with no_ffn) in place of :408-414.  The replaced method otherwise (several
     heads, per-view attention, the epipolar path's attn_type, CPU or half precision, another width or mlp).
-    `forward.native_calls` counts the calls the kernels took."""
+    `forward.native_calls` counts the calls the kernels took.  precision: the seam's option for ffn_tail's products, resolved
+    at every call (layer_norm_residual has no product); `forward.precision` holds it."""
     from . import transformer_ffn as _tf
+    from . import window_attention as _wa
+    _transformer_ffn_precision(precision)
 
     def forward(self, source, target, height=None, width=None, shifted_window_attn_mask=None, attn_num_splits=None, **kwargs):
         if not _transformer_ffn_call(self, source, target, kwargs):
@@ -1037,16 +1056,17 @@ def _native_transformer_layer_forward(replaced):
         if self.no_ffn:
             return _tf.layer_norm_residual(message, n1.weight, n1.bias, source, n1.eps)
         return _tf.ffn_tail(source, message, n1.weight, n1.bias, self.mlp[0].weight, self.mlp[2].weight, self.norm2.weight,
-                            self.norm2.bias, n1.eps)
+                            self.norm2.bias, n1.eps, precision=_wa.resolve_precision(precision))
 
     forward.replaced = replaced
+    forward.precision = precision
     forward.native_calls = 0
     forward.__doc__ = _tf.ffn_tail.__doc__
     return forward
 
 
 TRANSFORMER_FFN_SEAM = _MethodSeam("transformer_ffn", TRANSFORMER_FFN_MODULE, TRANSFORMER_FFN_CLASS, (TRANSFORMER_FFN_METHOD,),
-                                   {TRANSFORMER_FFN_METHOD: _native_transformer_layer_forward})
+                                   {TRANSFORMER_FFN_METHOD: _native_transformer_layer_forward}, context=True)
 
 
 # install()'s option keywords -> their seams, in installation order; the decoder registry (DECODER_SEAM) comes after them.
@@ -1123,11 +1143,12 @@ def install_unet_attention():
     return dict(zip((f"{seam.cls_name}.{seam.names[0]}" for seam in UNET_ATTENTION_SEAMS), _installed("unet_attention")))
 
 
-def install_transformer_ffn():
+def install_transformer_ffn(precision: str = "highest"):
     """The half of install(transformer_ffn=True): rebind TransformerLayer.forward (multiview_transformer.py:334-414) to the wrapper
     around the fused kernels of transformer_ffn.py now if the module is imported, else as soon as it is (import hook).  Returns the
-    patched method or None."""
-    return _installed("transformer_ffn")[0]
+    patched method or None.  precision: "highest" (exact float32 products), "high" (bf16x3 products, transformer_ffn.py) or
+    "torch" (torch.get_float32_matmul_precision() at every call: 'highest' is "highest", 'high' and 'medium' are "high")."""
+    return _installed("transformer_ffn", precision=_transformer_ffn_precision(precision))[0]
 
 
 def install_depth_smoothness():
@@ -1232,16 +1253,19 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     transformer_ffn=True: ALSO rebind the multi-view transformer's TransformerLayer.forward (multiview_transformer.py:334-414) so
     that norm1, cat([source, message]), the mlp, norm2 and the residual behind the layer's attention run the fused kernels of
     splatter360_amd.transformer_ffn, which form no [T, 2C] or [T, 8C] tensor (install_transformer_ffn; off by default; composes
-    with window_attention in either order; state_dict keys are unchanged).
+    with window_attention in either order; state_dict keys are unchanged).  transformer_ffn_precision: "highest" (the default),
+    "high" (bf16x3 products on the bf16 MFMA in ffn_tail, forward and backward) or "torch" (torch's setting at every call);
+    independent of window_attention_precision.
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
     the fused decoder.  lazy=True: only installs an import hook that patches the registry when the reference itself first imports
     the package (for a sitecustomize that runs before sys.path is set up).  Idempotent.
-    opts: window_attention_precision (above); for the decoder views_per_group (6), shared_campos (None = checked per group with one small read per forward), check ("sync"), glue."""
+    opts: window_attention_precision, transformer_ffn_precision (above); for the decoder views_per_group (6), shared_campos (None = checked per group with one small read per forward), check ("sync"), glue."""
     given = locals()
     # an option of a seam, not a seam: taken out of opts (the decoder's options) before they reach the decoder
     given["window_attention_options"] = {"precision": _window_attention_precision(opts.pop("window_attention_precision", "highest"))}
+    given["transformer_ffn_options"] = {"precision": _transformer_ffn_precision(opts.pop("transformer_ffn_precision", "highest"))}
     for keyword, seams in OPTION_SEAMS.items():
         if given[keyword]:
             for seam in seams:

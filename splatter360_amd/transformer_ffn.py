@@ -14,6 +14,13 @@ a three-launch backward that recompute the hidden activations: the autograd node
 gain is memory; speed against torch's rocBLAS path is what profiles/transformer_ffn_timing.json says it is.  Float32 GPU tensors,
 C = 128 and hidden width 1024 (what both backbones use); there is no CPU path (the installed seam keeps the replaced method for
 everything else).  Forward and backward are bit-identical from run to run: fixed order, no atomics.
+
+precision="highest" (the default) forms every product from exact float32 products; precision="high" is what
+torch.set_float32_matmul_precision('high') asks for: each float32 number as the sum of two bfloat16 numbers and each product of the
+forward and the backward as Ah Bh + Ah Bl + Al Bh on the bf16 MFMA, float32 accumulation (the LayerNorm rows stay float64).  The
+weights are split once per call into 3 MiB of bf16 planes in a scratch buffer; the token side is split inside the kernels, so the
+"high" mode saves what "highest" saves.  A forward run in one precision takes its backward in the same one.
+`window_attention.resolve_precision("torch")` reads torch's setting at call time.
 """
 from __future__ import annotations
 
@@ -31,6 +38,24 @@ CHANNELS = 128
 HIDDEN = 1024
 FFN_GRADIENTS = ("g_source", "g_m", "g_norm1_weight", "g_norm1_bias", "g_w1", "g_w2", "g_norm2_weight", "g_norm2_bias")
 NORM_GRADIENTS = ("g_x", "g_weight", "g_bias", "g_residual")
+PRECISIONS = ("highest", "high")
+
+
+def _precision(precision: str) -> str:
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"ffn_tail knows the precisions {list(PRECISIONS)}, got precision={precision!r}")
+    return precision
+
+
+def scratch_bytes(tokens: int, backward: bool, precision: str = "highest") -> int:
+    """The bytes of scratch a forward (backward) call of ffn_tail allocates for `tokens` tokens: "highest" none for the forward
+    and s360_ffn_tail_scratch_bytes for the backward; "high" s360_ffn_tail_high_scratch_bytes, the same plus the weights' bf16
+    planes, whose size does not depend on tokens.  0 for tokens < 1."""
+    _precision(precision)
+    tokens = int(tokens)
+    if precision == "high":
+        return int(_lib.lib().s360_ffn_tail_high_scratch_bytes(tokens, int(bool(backward))))
+    return int(_lib.lib().s360_ffn_tail_scratch_bytes(tokens)) if backward else 0
 
 
 def supported_widths(channels: int, hidden: int = HIDDEN) -> bool:
@@ -127,24 +152,53 @@ def _scratch(tokens: int, device) -> Tensor:
     return torch.empty(int(_lib.lib().s360_ffn_tail_scratch_bytes(tokens)), dtype=torch.uint8, device=device)
 
 
+def _no_scratch(what: str, precision: str, given) -> None:
+    """Only the "high" call takes the caller's scratch: one handed to a "highest" call would go unused, so it is refused."""
+    if given is not None and precision != "high":
+        raise ValueError(f"{what}: scratch is the buffer of a precision=\"high\" call, got one with precision={precision!r}")
+
+
+def _high_scratch(what: str, tokens: int, backward: bool, device, given: Optional[Tensor]) -> Tensor:
+    """The scratch of a "high" call: allocated, or the caller's uint8 buffer (the library checks its size and alignment)."""
+    if given is None:
+        return torch.empty(scratch_bytes(tokens, backward, "high"), dtype=torch.uint8, device=device)
+    _tensor(what, "scratch", given, dtype=torch.uint8, device=device)
+    if given.dim() != 1 or not given.is_contiguous():
+        raise ValueError(f"{what}: scratch must be a contiguous 1-D uint8 buffer")
+    return given
+
+
 def ffn_tail_forward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bias: Tensor, w1: Tensor, w2: Tensor, norm2_weight: Tensor,
-                     norm2_bias: Tensor, eps: float = 1e-5) -> tuple:
-    """s360_ffn_tail_forward -> (out in source's shape, z [T, C] float32, stats [2, T, 2] float64)."""
+                     norm2_bias: Tensor, eps: float = 1e-5, *, precision: str = "highest", scratch: Optional[Tensor] = None) -> tuple:
+    """s360_ffn_tail_forward (precision "high": s360_ffn_tail_high_forward) -> (out in source's shape, z [T, C] float32, stats
+    [2, T, 2] float64).  `scratch`: a uint8 buffer of scratch_bytes(T, False, "high") bytes for the "high" call to use in place
+    of one it allocates; refused (ValueError) with any other precision, whose forward has no scratch."""
+    _precision(precision)
+    _no_scratch("ffn_tail_forward", precision, scratch)
     tokens = _checked_ffn("ffn_tail_forward", source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps)
     args = [_flat(t) for t in (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias)]
     out = torch.empty(source.shape, dtype=torch.float32, device=source.device)
     z = torch.empty(tokens, CHANNELS, dtype=torch.float32, device=source.device)
     stats = torch.empty(2, tokens, 2, dtype=torch.float64, device=source.device)
-    call("s360_ffn_tail_forward", source.device, *(ptr(t) for t in args), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))),
-         ptr(out), ptr(z), ptr(stats))
+    common = (*(ptr(t) for t in args), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))), ptr(out), ptr(z), ptr(stats))
+    if precision == "high":
+        scratch = _high_scratch("ffn_tail_forward", tokens, False, source.device, scratch)
+        call("s360_ffn_tail_high_forward", source.device, *common, ptr(scratch), scratch.numel())
+    else:
+        call("s360_ffn_tail_forward", source.device, *common)
     return out, z, stats
 
 
 def ffn_tail_backward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bias: Tensor, w1: Tensor, w2: Tensor, norm2_weight: Tensor,
-                      norm2_bias: Tensor, z: Tensor, stats: Tensor, g_out: Tensor, eps: float = 1e-5, *, buffers: Optional[dict] = None) -> tuple:
-    """s360_ffn_tail_backward -> the gradients in FFN_GRADIENTS' order (the order of ffn_tail's arguments).  `buffers`: {name:
-    contiguous float32 buffer} for any of them to write into; the others are allocated."""
+                      norm2_bias: Tensor, z: Tensor, stats: Tensor, g_out: Tensor, eps: float = 1e-5, *, buffers: Optional[dict] = None,
+                      precision: str = "highest", scratch: Optional[Tensor] = None) -> tuple:
+    """s360_ffn_tail_backward (precision "high": s360_ffn_tail_high_backward, with z and stats of a "high" forward) -> the
+    gradients in FFN_GRADIENTS' order (the order of ffn_tail's arguments).  `buffers`: {name: contiguous float32 buffer} for any of
+    them to write into; the others are allocated.  `scratch`: as in ffn_tail_forward, scratch_bytes(T, True, "high") bytes, refused with
+    any other precision (the "highest" backward allocates its own)."""
     what = "ffn_tail_backward"
+    _precision(precision)
+    _no_scratch(what, precision, scratch)
     tokens = _checked_ffn(what, source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps)
     _tensor(what, "g_out", g_out, source.shape, device=source.device)
     _tensor(what, "z", z, (tokens, CHANNELS), device=source.device)
@@ -152,9 +206,9 @@ def ffn_tail_backward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bia
     ins = [_flat(t) for t in (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, z, stats, g_out)]
     outs = dict(zip(FFN_GRADIENTS, _buffers(what, FFN_GRADIENTS, (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias),
                                             buffers)))
-    scratch = _scratch(tokens, source.device)
+    scratch = _high_scratch(what, tokens, True, source.device, scratch) if precision == "high" else _scratch(tokens, source.device)
     order = ("g_source", "g_m", "g_w1", "g_w2", "g_norm1_weight", "g_norm1_bias", "g_norm2_weight", "g_norm2_bias")
-    call("s360_ffn_tail_backward", source.device, *(ptr(t) for t in ins), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))),
+    call("s360_ffn_tail_high_backward" if precision == "high" else "s360_ffn_tail_backward", source.device, *(ptr(t) for t in ins), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))),
          ptr(scratch), scratch.numel(), *(ptr(outs[n]) for n in order))
     return tuple(outs[n] for n in FFN_GRADIENTS)
 
@@ -186,21 +240,22 @@ def layer_norm_residual_backward(x: Tensor, weight: Tensor, stats: Tensor, g_out
 
 
 class _FFNTail(torch.autograd.Function):
-    """Saves source, m, z [T, C], the statistics and the parameters: nothing of size [T, 2C] or [T, 8C]."""
+    """Saves source, m, z [T, C], the statistics and the parameters: nothing of size [T, 2C] or [T, 8C] and, in the "high" mode,
+    none of the bf16 planes (the backward splits the weights again)."""
 
     @staticmethod
-    def forward(ctx, source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps):
+    def forward(ctx, source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps, precision):
         args = [_flat(t) for t in (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias)]
-        out, z, stats = ffn_tail_forward(*args, eps)
+        out, z, stats = ffn_tail_forward(*args, eps, precision=precision)
         ctx.save_for_backward(*args, z, stats)
-        ctx.eps = eps
+        ctx.eps, ctx.precision = eps, precision
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_out):
         *args, z, stats = ctx.saved_tensors
-        return (*ffn_tail_backward(*args, z, stats, g_out.to(torch.float32), ctx.eps), None)
+        return (*ffn_tail_backward(*args, z, stats, g_out.to(torch.float32), ctx.eps, precision=ctx.precision), None, None)
 
 
 class _LayerNormResidual(torch.autograd.Function):
@@ -221,16 +276,18 @@ class _LayerNormResidual(torch.autograd.Function):
 
 
 def ffn_tail(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bias: Tensor, w1: Tensor, w2: Tensor, norm2_weight: Tensor,
-             norm2_bias: Tensor, eps: float = 1e-5) -> Tensor:
+             norm2_bias: Tensor, eps: float = 1e-5, precision: str = "highest") -> Tensor:
     """source + LN2(gelu(cat([source, LN1(m)], -1) w1^T) w2^T): the reference's TransformerLayer.forward :408-414 behind
     `message = self.merge(message)`, m being that message.
 
     source, m [..., C] with any leading dimensions; norm1 / norm2 weight and bias [C] (nn.LayerNorm's affine parameters, biased
     variance, eps); w1 [8C, 2C] and w2 [C, 8C] (nn.Linear's layout, no biases); GELU in the erf form.  Returns a tensor of
     source's shape.  Differentiable (once) in all eight tensors.  Float32 GPU tensors, C = 128 and 8C = 1024; no CPU path; a
-    non-contiguous input is copied once."""
+    non-contiguous input is copied once.  precision "highest": exact float32 products; "high": bf16x3 products on the bf16 MFMA,
+    forward and backward (the module's docstring)."""
+    _precision(precision)
     _checked_ffn("ffn_tail", source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps)
-    return _FFNTail.apply(source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, float(eps))
+    return _FFNTail.apply(source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, float(eps), precision)
 
 
 def layer_norm_residual(x: Tensor, weight: Tensor, bias: Tensor, residual: Tensor, eps: float = 1e-5) -> Tensor:

@@ -1,0 +1,354 @@
+"""The FFN tail's "high" precision mode on the GPU (the k_ffh_* kernels of csrc/s360_transformer_ffn.hip through
+splatter360_amd/transformer_ffn.py, precision="high") against the float64 statement of tests/transformer_ffn_reference.py.
+
+Accuracy rule: for out and the eight gradients, over all elements, the kernel's max and mean absolute error against
+statement(float64) are <= max(1.5 x (e3 + e32), 2^-24 max|want|), e3 the error of
+transformer_ffn_high_reference.split_statement(terms=3) — the specification's own distance from float64 — and e32 the error of the
+reference's float32 lines on the same GPU (the kernels round h, z, dz and dpre to float32 and accumulate in float32); 1.5 is the
+project's factor.  tests/test_transformer_ffn_high_spec.py shows that a single-bf16 product (terms=1) is >= 50 x e3 away.
+Cases: the pooled file's eight at scales 1 and 6, and the smallest T that reaches each path of the kernels' launch geometry (a
+second and a third workgroup, two and three tiles per weight chunk, the token pass's grid stride at scale 1 only), derived from
+the kernel file's constants (transformer_ffn_high_reference.geometry_cases; the spec test pins them).
+
+Measured on one MI355X over the 25 runs (zero_norm's exact zeros left out), kernel / bound, maxima and means: out 0.57 to 0.72
+and 0.61 to 0.64; g_source 0.55 to 0.69 and 0.62 to 0.65; g_m 0.53 to 0.76 and 0.62 to 0.64; norm1's weight and bias gradients
+0.48 to 0.80 and 0.59 to 0.88; g_w1 0.39 to 0.72 and 0.51 to 0.66; g_w2 0.36 to 0.68 and 0.49 to 0.65; g_norm2_weight 0.55 to 0.69
+and 0.59 to 0.64; g_norm2_bias (no product: e3 = 0) at most 0.45 and 0.12.  The kernels sit on the specification: kernel / e3 is
+0.73 to 1.32 (max) and 0.94 to 1.05 (mean; g_norm1_bias of the grid-stride case 1.45), and e3 is 1.4 to 60 x (max) and 2.7 to 36 x
+(mean) e32.  The layer through both seams at "high" (13 tensors): 0.08 to 0.76 and 0.07 to 0.69.
+Memory at T = 32 768: forward + backward rise 110.6 MiB (0.86 of one hidden tensor); "highest" 107.6 MiB (0.84).
+"""
+import ctypes
+import functools
+import sys
+
+import pytest
+import torch
+
+import transformer_ffn_high_reference as HR
+import transformer_ffn_reference as R
+from splatter360_amd import _lib, plugin, transformer_ffn as tf
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+C = 128
+# the pooled file's cases (tests/test_gpu_transformer_ffn.py): leading dimensions, None: the `chunks` case
+POOLED = {"one": (1,), "tiny": (5,), "tile": (32,), "ragged": (33,), "lead": (2, 3, 20), "chunks": None, "constant_row": (40,),
+          "zero_norm": (37,)}
+GEOMETRY = HR.geometry_cases()
+SCALES = (1.0, 6.0)
+RUNS = ([(n, s) for n in sorted(POOLED) for s in SCALES] + [(n, s) for n in GEOMETRY if n != "stride" for s in SCALES]
+        + [("stride", 1.0)])
+FFN_OUT = HR.OUT_NAMES
+
+
+def _chunks_tokens():
+    t = 1
+    while not (tf.weight_chunks(t) >= 3 and t % 32 != 0):
+        t += 1
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(name, scale):
+    if name in GEOMETRY:                                         # T from the kernel file's constants; row_inputs' seed
+        return R.random_case(GEOMETRY[name], scale=scale, seed=5000 + 7 * sorted(R.ROW_CASES).index(name), device=DEV)
+    lead = POOLED[name] or (_chunks_tokens(),)
+    tokens = 1
+    for n in lead:
+        tokens *= n
+    tensors, g = R.random_case(tokens, scale=scale, seed=3000 + 7 * sorted(POOLED).index(name), device=DEV, lead=lead)
+    source, m, n1w, n1b, w1, w2, n2w, n2b = tensors
+    if name == "constant_row":
+        m = m.clone()
+        m.view(-1, C)[tokens // 2] = 0.75 * scale
+    if name == "zero_norm":
+        n2w, n2b = torch.zeros_like(n2w), torch.zeros_like(n2b)
+    return (source, m, n1w, n1b, w1, w2, n2w, n2b), g
+
+
+def _native(tensors, g, precision="high"):
+    xs = [t.detach().clone().requires_grad_(True) for t in tensors]
+    out = tf.ffn_tail(*xs, precision=precision)
+    out.backward(g)
+    return (out.detach(), *(x.grad for x in xs))
+
+
+@functools.lru_cache(maxsize=None)
+def _run(name, scale):
+    """Inputs, the float64 statement, the three-term statement, the float32 lines and the kernels' results of one case: computed
+    once, shared, never modified."""
+    tensors, g = _inputs(name, scale)
+    assert torch.get_float32_matmul_precision() == "highest"
+    want = R.gradients(lambda *t: R.statement(*t), tensors, g, torch.float64)
+    three = R.gradients(lambda *t: HR.split_statement(*t), tensors, g, torch.float64)
+    lines = R.gradients(lambda *t: R.reference_lines(*t), tensors, g)
+    got = _native(tensors, g)
+    return (tensors, g), want, three, lines, got
+
+
+def _check_rule(tag, names, want, three, lines, got):
+    failures = []
+    for n, w64, t3, l32, x in zip(names, want, three, lines, got):
+        assert x.dtype == torch.float32 and x.shape == w64.shape, (tag, n)
+        assert torch.isfinite(x).all(), (tag, n)
+        (kmax, kmean), (e3max, e3mean), (lmax, lmean) = HR.errors(x, w64), HR.errors(t3, w64), HR.errors(l32, w64)
+        floor = 2.0 ** -24 * w64.abs().max().item()
+        bmax, bmean = max(1.5 * (e3max + lmax), floor), max(1.5 * (e3mean + lmean), floor)
+        print(f"{tag} {n}: kernel max {kmax:.3e} mean {kmean:.3e} | e3 max {e3max:.3e} mean {e3mean:.3e} | e32 max {lmax:.3e} mean "
+              f"{lmean:.3e} | floor {floor:.3e} | kernel / bound {kmax / bmax if bmax else 0:.2f} {kmean / bmean if bmean else 0:.2f}")
+        if not (kmax <= bmax and kmean <= bmean):
+            failures.append((n, kmax, kmean, bmax, bmean))
+    assert not failures, (tag, failures)
+
+
+@pytest.mark.parametrize("name,scale", RUNS)
+def test_ffn_tail_high_accuracy_against_the_float64_statement(name, scale):
+    _, want, three, lines, got = _run(name, scale)
+    _check_rule(f"ffn high {name} scale={scale:g}", FFN_OUT, want, three, lines, got)
+
+
+@pytest.mark.parametrize("scale", SCALES)
+def test_zero_norm_is_the_identity_bit_for_bit(scale):
+    (tensors, g), _, _, _, got = _run("zero_norm", scale)
+    named = dict(zip(FFN_OUT, got))
+    assert torch.equal(named["out"], tensors[0]) and torch.equal(named["g_source"], g)
+    for n in ("g_m", "g_w1", "g_w2", "g_norm1_weight", "g_norm1_bias"):
+        assert not named[n].any(), n
+    assert named["g_norm2_weight"].abs().max().item() > 0 and named["g_norm2_bias"].abs().max().item() > 0
+
+
+@pytest.mark.parametrize("name", ["ragged", "wg2"])
+def test_the_default_is_highest_and_high_is_another_function(name):
+    (tensors, g), _, _, _, high = _run(name, 1.0)
+    plain = _native_default(tensors, g)
+    highest = _native(tensors, g, "highest")
+    assert all(torch.equal(x, y) for x, y in zip(plain, highest))
+    for n, x, y in zip(FFN_OUT, high, highest):
+        assert torch.equal(x, y) == (n in HR.EXACT), n            # g_norm2_bias holds no product
+
+
+def _native_default(tensors, g):
+    xs = [t.detach().clone().requires_grad_(True) for t in tensors]
+    out = tf.ffn_tail(*xs)
+    out.backward(g)
+    return (out.detach(), *(x.grad for x in xs))
+
+
+def _direct(tensors, g, buffers=None, scratch=(None, None)):
+    out, z, stats = tf.ffn_tail_forward(*tensors, precision="high", scratch=scratch[0])
+    return (out, z, stats, *tf.ffn_tail_backward(*tensors, z, stats, g, buffers=buffers, precision="high", scratch=scratch[1]))
+
+
+@pytest.mark.parametrize("name", ["lead", "chunks", "wg3"])
+def test_forward_and_backward_are_deterministic(name):
+    (tensors, g), _, _, _, got = _run(name, 1.0)
+    first = _direct(tensors, g)
+    assert torch.equal(first[0], got[0]) and all(torch.equal(x, y) for x, y in zip(first[3:], got[1:]))   # the autograd node runs the same calls
+    again = _direct(tensors, g)
+    assert all(torch.equal(x, y) for x, y in zip(first, again))
+    side = torch.cuda.Stream(device=DEV)
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(side):
+        again = _direct(tensors, g)
+    side.synchronize()
+    assert all(torch.equal(x, y) for x, y in zip(first, again))
+    tokens = g.numel() // C
+    assert first[1].shape == (tokens, C) and first[1].dtype == torch.float32
+    assert first[2].shape == (2, tokens, 2) and first[2].dtype == torch.float64
+
+
+@pytest.mark.parametrize("name", ["ragged", "chunks"])
+def test_every_element_of_every_gradient_is_written(name):
+    (tensors, g), _, _, _, got = _run(name, 1.0)
+    buffers = {n: torch.full_like(t, float("nan")) for n, t in zip(tf.FFN_GRADIENTS, tensors)}
+    res = _direct(tensors, g, buffers=buffers)[3:]
+    for n, x, ref in zip(tf.FFN_GRADIENTS, res, got[1:]):
+        assert x is buffers[n] and torch.isfinite(x).all() and torch.equal(x, ref), n
+
+
+@pytest.mark.parametrize("name", ["ragged", "tiles2"])
+def test_nothing_is_written_behind_the_reported_scratch(name):
+    (tensors, g), _, _, _, got = _run(name, 1.0)
+    tokens, extra = g.numel() // C, 4096
+    need = [tf.scratch_bytes(tokens, back, "high") for back in (False, True)]
+    scratch = [torch.full((n + extra,), 0xA5, dtype=torch.uint8, device=DEV) for n in need]
+    res = _direct(tensors, g, scratch=scratch)
+    assert torch.equal(res[0], got[0]) and all(torch.equal(x, y) for x, y in zip(res[3:], got[1:]))
+    for buf, n in zip(scratch, need):
+        assert (buf[n:] == 0xA5).all() and (buf[:n] != 0xA5).any()
+
+
+def test_no_host_synchronisation():
+    (tensors, g), _, _, _, got = _run("lead", 1.0)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        again = _native(tensors, g)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert all(torch.equal(x, y) for x, y in zip(again, got))
+
+
+def test_inputs_at_scale_30_stay_finite():
+    tensors, g = R.random_case(33, scale=30.0, seed=77, device=DEV)
+    for x in _native(tensors, g):
+        assert torch.isfinite(x).all()
+
+
+def test_memory_stays_under_one_hidden_tensor():
+    """T = 32 768: one [T, 8C] hidden tensor is 128 MiB, the bound of tests/test_gpu_transformer_ffn.py; the "high" mode adds the
+    3 MiB of weight planes to each of the forward's and the backward's scratch and nothing that grows with T."""
+    tokens = 32768
+    hidden = tokens * 1024 * 4
+    tensors, _ = R.random_case(tokens, seed=3, device=DEV)
+    tensors = [t.requires_grad_(True) for t in tensors]
+
+    def rise(precision):
+        def step():
+            out = tf.ffn_tail(*tensors, precision=precision)
+            out.backward(torch.ones_like(out))
+        step()                                                                      # warm-up
+        for t in tensors:
+            t.grad = None
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(DEV)
+        base = torch.cuda.memory_allocated(DEV)
+        step()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated(DEV) - base
+        assert all(torch.isfinite(t.grad).all() and t.grad.abs().max().item() > 0 for t in tensors)
+        for t in tensors:
+            t.grad = None
+        return peak
+
+    high, highest = rise("high"), rise("highest")
+    print(f"forward + backward peak rise: high {high / 2 ** 20:.1f} MiB ({high / hidden:.2f} hidden tensors), "
+          f"highest {highest / 2 ** 20:.1f} MiB ({highest / hidden:.2f} hidden tensors)")
+    assert high <= hidden
+
+
+def test_scratch_refusals_write_nothing():
+    (tensors, g), _, _, _, _ = _run("tiny", 1.0)
+    tokens = g.numel() // C
+    lib, p = _lib.lib(), lambda t: ctypes.c_void_p(t.data_ptr())
+    eps = ctypes.byref(ctypes.c_double(1e-5))
+    stream = ctypes.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
+    seven = lambda *shape, dtype=torch.float32: torch.full(shape, 7.0, dtype=dtype, device=DEV)          # noqa: E731
+    out, z, stats = seven(tokens, C), seven(tokens, C), seven(2, tokens, 2, dtype=torch.float64)
+    grads = [seven(*t.shape) for t in tensors]
+    need = [tf.scratch_bytes(tokens, back, "high") for back in (False, True)]
+    big = torch.empty(need[1] + 64, dtype=torch.uint8, device=DEV)
+    assert big.data_ptr() % 16 == 0
+    ins = [p(t) for t in tensors]
+    order = [grads[i] for i in (0, 1, 4, 5, 2, 3, 6, 7)]                            # the ABI's order: g_source, g_m, g_w1, g_w2, norms
+
+    def forward(scratch, nbytes):
+        return lib.s360_ffn_tail_high_forward(*ins, tokens, C, 1024, eps, p(out), p(z), p(stats), scratch, nbytes, stream)
+
+    def backward(scratch, nbytes):
+        return lib.s360_ffn_tail_high_backward(*ins, p(z), p(stats), p(g), tokens, C, 1024, eps, scratch, nbytes, *(p(t) for t in order), stream)
+
+    for call, n in ((forward, need[0]), (backward, need[1])):
+        assert call(None, n) == -1                                                  # null
+        assert call(p(big), n - 1) == -2                                            # short
+        assert call(p(big[8:]), n) == -1                                            # misaligned
+    refused = lib.s360_ffn_tail_forward(*ins, tokens, 96, 768, eps, p(out), p(z), p(stats), stream)
+    assert refused < 0 and lib.s360_ffn_tail_high_forward(*ins, tokens, 96, 768, eps, p(out), p(z), p(stats), p(big), need[0], stream) == refused
+    torch.cuda.synchronize()
+    for t in (out, z, stats, *grads):
+        assert (t == 7.0).all()
+
+
+# ---- the seam on the GPU -------------------------------------------------------------------------------------------------------
+
+MODULE = plugin.TRANSFORMER_FFN_MODULE
+
+
+@pytest.fixture
+def standin():
+    assert MODULE not in sys.modules
+    mod = R.standin_module(MODULE)
+    sys.modules[MODULE] = mod
+    try:
+        yield mod
+    finally:
+        plugin.uninstall()
+        del sys.modules[MODULE]
+
+
+def _layer_inputs():
+    gen = torch.Generator().manual_seed(22)
+    return tuple(torch.randn(3, 24, 128, generator=gen).to(DEV) for _ in range(3))
+
+
+def test_the_torch_option_follows_torch_s_setting_at_every_call(standin, monkeypatch):
+    layer = R.randomise(standin.TransformerLayer(d_model=128), 21).to(DEV)
+    source, target, _ = _layer_inputs()
+    plugin.install(lazy=True, transformer_ffn=True, transformer_ffn_precision="torch")
+    wrapper = standin.TransformerLayer.forward
+    launched, merged = [], []
+    real = tf.ffn_tail_forward
+    monkeypatch.setattr(tf, "ffn_tail_forward", lambda *a, **k: (launched.append(k.get("precision")), real(*a, **k))[1])
+    layer.merge.register_forward_hook(lambda mod, args, out: merged.append(out.detach()))
+    before = torch.get_float32_matmul_precision()
+    try:
+        for setting, want in (("high", "high"), ("highest", "highest"), ("medium", "high")):
+            torch.set_float32_matmul_precision(setting)
+            with torch.no_grad():
+                out = layer(source, target, height=4, width=6, attn_num_splits=1)
+                direct = tf.ffn_tail(source, merged[-1], layer.norm1.weight, layer.norm1.bias, layer.mlp[0].weight, layer.mlp[2].weight,
+                                     layer.norm2.weight, layer.norm2.bias, layer.norm1.eps, precision=want)
+            assert launched[-2:] == [want, want] and torch.equal(out, direct), setting
+    finally:
+        torch.set_float32_matmul_precision(before)
+    assert wrapper.native_calls == 3 and layer.calls == 0      # the kernels; the replaced method, never
+
+
+def test_no_ffn_layers_run_layer_norm_residual_whatever_the_precision(standin):
+    layer = R.randomise(standin.TransformerLayer(d_model=128, no_ffn=True), 21).to(DEV)
+    source, target, _ = _layer_inputs()
+    outs = []
+    for precision in ("highest", "high"):
+        plugin.install(lazy=True, transformer_ffn=True, transformer_ffn_precision=precision)
+        assert standin.TransformerLayer.forward.precision == precision
+        with torch.no_grad():
+            outs.append(layer(source, target, height=4, width=6, attn_num_splits=1))
+        assert standin.TransformerLayer.forward.native_calls == 1
+        plugin.uninstall()
+    assert torch.equal(outs[0], outs[1]) and layer.calls == 0
+
+
+def _layer_gradients(fn, layer, source, target, g):
+    keys = R.layer_params(layer.no_ffn)
+    named = dict(layer.named_parameters())
+    return R.gradients(lambda s, t, *p: fn(dict(zip(keys, p)), s, t), [source, target, *(named[k] for k in keys)], g, torch.float64)
+
+
+def _layer32(layer, source, target, g):
+    layer.zero_grad(set_to_none=True)
+    s, t = (x.detach().clone().requires_grad_(True) for x in (source, target))
+    out = layer(s, t, height=4, width=6, attn_num_splits=1)
+    out.backward(g)
+    named = dict(layer.named_parameters())
+    return (out.detach(), s.grad, t.grad, *(named[k].grad.clone() for k in R.layer_params(layer.no_ffn)))
+
+
+def test_the_layer_holds_the_rule_with_both_seams_at_high(standin):
+    """The stand-in TransformerLayer (d_model 128, 3 x 24 tokens, full attention) with install(transformer_ffn=True,
+    window_attention=True), both at "high": output, input gradients and every parameter gradient against the layer in float64;
+    e3 is the layer with the tail's and the attention's products as three-term products, e32 the uninstalled float32 layer."""
+    layer = R.randomise(standin.TransformerLayer(d_model=128), 21).to(DEV)
+    source, target, g = _layer_inputs()
+    names = ("out", "g_source", "g_target", *("g_" + k for k in R.layer_params(False)))
+    want = _layer_gradients(lambda p, s, t: R.layer_statement(p, s, t), layer, source, target, g)
+    three = _layer_gradients(lambda p, s, t: HR.layer_split_statement(p, s, t, attention_terms=3), layer, source, target, g)
+    lines = _layer32(layer, source, target, g)
+    assert layer.calls == 1
+    plugin.install(lazy=True, transformer_ffn=True, transformer_ffn_precision="high", window_attention=True,
+                   window_attention_precision="high")
+    wrapper = standin.TransformerLayer.forward
+    standin.calls.clear()
+    got = _layer32(layer, source, target, g)
+    assert wrapper.native_calls == 1 and layer.calls == 1 and standin.calls == []
+    _check_rule("layer high", names, want, three, lines, got)
