@@ -18,16 +18,38 @@ _HERE = Path(__file__).resolve().parent
 _LIBS: dict = {}
 
 
-def build(force: bool = False) -> None:
-    """Compile liboracle_f32.so / liboracle_f64.so with gcc (oracle/Makefile)."""
-    need = force or not all((_HERE / n).exists() for n in ("liboracle_f32.so", "liboracle_f64.so"))
+_NAMES = ("liboracle_f32.so", "liboracle_f64.so")
+
+
+def _stale() -> bool:
     src_m = (_HERE / "s360_oracle.c").stat().st_mtime
-    for n in ("liboracle_f32.so", "liboracle_f64.so"):
-        f = _HERE / n
-        if f.exists() and f.stat().st_mtime < src_m:
-            need = True
-    if need:
-        subprocess.run(["make", "-C", str(_HERE), "-B"], check=True, capture_output=True)
+    return not all((_HERE / n).exists() and (_HERE / n).stat().st_mtime >= src_m for n in _NAMES)
+
+
+def build(force: bool = False) -> None:
+    """Compile liboracle_f32.so / liboracle_f64.so with gcc (oracle/Makefile).  Safe when several processes call it at once (the
+    spawned ranks of tests/test_dist_cpu.py all do, and all find the libraries stale after a fresh checkout): the compile runs in a
+    temporary directory beside the targets and each finished library is renamed into place, so no process can ever load a
+    half-written file; a lock on the directory lets the others wait and find the work done instead of repeating it."""
+    if not (force or _stale()):
+        return
+    import fcntl
+    import shutil
+    import tempfile
+    fd = os.open(str(_HERE), os.O_RDONLY)
+    try:
+        fcntl.flock(fd, fcntl.LOCK_EX)
+        if not (force or _stale()):
+            return
+        tmp = Path(tempfile.mkdtemp(prefix=".build-", dir=str(_HERE)))
+        try:
+            subprocess.run(["make", "-B", "-C", str(tmp), "-f", str(_HERE / "Makefile"), f"VPATH={_HERE}"], check=True, capture_output=True)
+            for n in _NAMES:
+                os.replace(tmp / n, _HERE / n)
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
+    finally:
+        os.close(fd)                                            # releases the lock
 
 
 def _lib(dtype):

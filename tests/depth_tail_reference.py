@@ -8,6 +8,8 @@ import torch
 import torch.nn.functional as F
 from einops import rearrange, repeat
 
+from depth_head_reference import COND, TINY, UNIT, bound, worst  # noqa: F401  (the measure, shared)
+
 
 def upsample(x, s, mode, reciprocal=False, dtype=torch.float64):
     """F.interpolate itself on x [n, 1, h, w] (of 1 / x with reciprocal), in `dtype`."""
@@ -108,6 +110,180 @@ def random_maps(n, h, w, s, seed, device="cpu"):
     pmax = 1.0 - torch.rand(n, 1, h, w, generator=gen)
     grads = [torch.randn(n, 1, h * s, w * s, generator=gen) for _ in range(2)]
     return tuple(t.to(device) for t in (depth, pmax, *grads))
+
+
+# ------------------------------------------------------------------------------------------------ the per-element measure
+# bound = 2^-24 |want| + 2^-40 A + 2^-149, as in tests/depth_head_reference.py: one float32 rounding, 2^13 float64 ulps of the
+# element's condition A (the sum of the magnitudes of its terms), half the smallest float32 subnormal.
+PLANTED_LOGITS = (17.5, -17.5, 20.0, -20.0, 40.0, -40.0, 88.0, -88.0, 100.0, -100.0)
+
+
+def sigmoid_parts(x):
+    """(log p, log(1 - p), p, 1 - p) of p = sigmoid(x) in float64, each to a few ulps of ITSELF for every finite x, from
+    t = exp(-|x|) alone: no difference of near-equal numbers is formed.  (torch's 1 - sigmoid(x) keeps no digit from x = 37 on.)"""
+    x = x.double()
+    t = (-x.abs()).exp()
+    lt = torch.log1p(t)
+    big, small = 1.0 / (1.0 + t), t / (1.0 + t)
+    pos = x >= 0
+    return torch.where(pos, -lt, x - lt), torch.where(pos, -x - lt, -lt), torch.where(pos, big, small), torch.where(pos, small, big)
+
+
+def opacity_elements(x, exponent, gpp=1):
+    """The float64 `want` of the tail's opacity, its slope in the logit x, p and p (1 - p), in a form without cancellation:
+    1 - (1 - p)^e = -expm1(e log(1 - p)), and every other factor is a product of positive numbers.  Pinned against 200-bit
+    arithmetic by tests/test_depth_tail_elements.py.  Returns a dict of opacity, slope, p, pq."""
+    lp, lq, p, q = sigmoid_parts(x)
+    e = float(exponent)
+    root = (lp / e).exp()
+    return dict(opacity=(root - torch.special.expm1(e * lq)) * (0.5 / gpp), slope=(e * (e * lq).exp() * p + root * q / e) * (0.5 / gpp), p=p, pq=p * q)
+
+
+def _taps(n_in, s, mode):
+    """The [n_in s, n_in] float64 matrix of one axis of the upsampling, from exact integer taps: nearest takes Y // s; bilinear
+    with align_corners=True has the source coordinate Y (h - 1) / (H - 1), so the upper tap's weight is the rational
+    (Y (h - 1) mod (H - 1)) / (H - 1)."""
+    import numpy as np
+    n_out = n_in * s
+    m = np.zeros((n_out, n_in))
+    for Y in range(n_out):
+        if mode == "nearest":
+            m[Y, Y // s] = 1.0
+        elif n_out == 1:
+            m[Y, 0] = 1.0
+        else:
+            y0, r = divmod(Y * (n_in - 1), n_out - 1)
+            m[Y, y0] += (n_out - 1 - r) / (n_out - 1)
+            m[Y, min(y0 + 1, n_in - 1)] += r / (n_out - 1)
+    return m
+
+
+def upsample_elements(x, s, mode, reciprocal=False):
+    """The project's own numpy statement of the upsampling of x [n, 1, h, w]: (want, A), float64 [n, 1, h s, w s], with
+    A = sum_i |w_i v_i| over the taps (v = 1 / x with reciprocal)."""
+    import numpy as np
+    v = x.detach().cpu().double().numpy()[:, 0]
+    if reciprocal:
+        v = 1.0 / v
+    wy, wx = _taps(v.shape[1], s, mode), _taps(v.shape[2], s, mode)
+    want = np.einsum("Yy,nyx,Xx->nYX", wy, v, wx)
+    cond = np.einsum("Yy,nyx,Xx->nYX", wy, np.abs(v), wx)
+    return torch.from_numpy(want)[:, None], torch.from_numpy(cond)[:, None]
+
+
+def upsample_backward_elements(g, x, s, mode, reciprocal=False):
+    """The adjoint: (want, A) [n, 1, h, w] for g [n, 1, h s, w s]; A = sum |w g|, and both times 1 / x^2 (want: -1 / x^2) with
+    reciprocal."""
+    import numpy as np
+    gg = g.detach().cpu().double().numpy()[:, 0]
+    v = x.detach().cpu().double().numpy()[:, 0]
+    wy, wx = _taps(v.shape[1], s, mode), _taps(v.shape[2], s, mode)
+    want = np.einsum("Yy,nYX,Xx->nyx", wy, gg, wx)
+    cond = np.einsum("Yy,nYX,Xx->nyx", wy, np.abs(gg), wx)
+    if reciprocal:
+        want, cond = -want / (v * v), cond / (v * v)
+    return torch.from_numpy(want)[:, None], torch.from_numpy(cond)[:, None]
+
+
+def clamp_pattern(fullres, delta, lo, hi):
+    """Where the tail's backward passes the disparity gradient — its stated contract: lo <= float32(f) + float32(d) <= hi on the
+    FLOAT32 sum, bounds included — computed in numpy.  fullres [n, 1, H, W], delta [n, gpp, H, W], lo / hi [n] -> bool tensor."""
+    import numpy as np
+    f, d = (t.detach().cpu().numpy().astype(np.float32) for t in (fullres, delta))
+    l, u = (t.detach().cpu().numpy().astype(np.float32).reshape(-1, 1, 1, 1) for t in (lo, hi))
+    total = f + d
+    assert total.dtype == np.float32
+    return torch.from_numpy((total >= l) & (total <= u))
+
+
+def tail_elements(fullres, delta_density, lo, hi, gpp, exponent, grads):
+    """The float64 `want` and the condition A of everything the tail computes, in plane layout ([(v b), gpp, H, W]; g_fullres
+    [(v b), 1, H, W]) — depths, opacities, densities, g_fullres, g_delta (disparity half), g_logit (density half).  lo / hi are the
+    float32 bounds [(v b)]; grads are (g_depths, g_opacities, g_densities) in [b, v, H W, 1, gpp], any may be None."""
+    n, _, h, w = fullres.shape
+    f, dd = fullres.detach().cpu().double(), delta_density.detach().cpu().double()
+    l, u = (t.detach().cpu().double().reshape(-1, 1, 1, 1) for t in (lo, hi))
+    total = f + dd[:, :gpp]
+    fine = torch.minimum(torch.maximum(total, l), u)
+    o = opacity_elements(dd[:, gpp:], exponent, gpp)
+    zero = torch.zeros(n, gpp, h, w, dtype=torch.float64)
+    g_dep, g_opa, g_den = (zero if g is None else planes(g.detach().cpu().double(), h, w) for g in grads)
+    inside = clamp_pattern(fullres, delta_density[:, :gpp], lo, hi)
+    g_delta = torch.where(inside, -g_dep / (fine * fine), zero)
+    t_o, t_s = g_opa * o["slope"], g_den * o["pq"]
+    want = dict(depths=1.0 / fine, opacities=o["opacity"], densities=o["p"], g_fullres=g_delta.sum(dim=1, keepdim=True), g_delta=g_delta,
+                g_logit=t_o + t_s)
+    cond = {k: want[k].abs() for k in ("depths", "opacities", "densities", "g_delta")}
+    cond.update(g_fullres=g_delta.abs().sum(dim=1, keepdim=True), g_logit=t_o.abs() + t_s.abs())
+    return want, cond
+
+
+TAIL_QUANTITIES = ("depths", "opacities", "densities", "g_fullres", "g_delta", "g_logit")
+
+
+def tail_model(fullres, delta_density, lo, hi, gpp, exponent, grads, opacity="stable", slope_q="stable", float64_clamp=False):
+    """A float64 model of the tail kernels' formulas (log p = -softplus(-x), log(1 - p) = -softplus(x), expm1), each output rounded
+    once to float32; plane layout as tail_elements.  Planted defects: opacity="pow" forms 1 - (1 - p)^e from p = sigmoid(x) in
+    float64; slope_q="one_minus_p" takes q = 1 - p; float64_clamp decides the clamp on the float64 sum."""
+    n, _, h, w = fullres.shape
+    f, dd = fullres.detach().cpu().double(), delta_density.detach().cpu().double()
+    l, u = (t.detach().cpu().double().reshape(-1, 1, 1, 1) for t in (lo, hi))
+    total = f + dd[:, :gpp]
+    fine = torch.minimum(torch.maximum(total, l), u)
+    x, e = dd[:, gpp:], float(exponent)
+    softplus = lambda t: torch.where(t > 0, t + torch.log1p((-t).exp()), torch.log1p(t.exp()))
+    lp, lq = -softplus(-x), -softplus(x)
+    p, q = lp.exp(), lq.exp()
+    root = (lp / e).exp()
+    op = (root - torch.special.expm1(e * lq)) * (0.5 / gpp)
+    if opacity == "pow":
+        op = (1.0 - (1.0 - torch.sigmoid(x)) ** e + torch.sigmoid(x) ** (1.0 / e)) * (0.5 / gpp)
+    if slope_q == "one_minus_p":
+        q = 1.0 - p
+    slope = (e * (e * lq).exp() * p + root * q / e) * (0.5 / gpp)
+    zero = torch.zeros(n, gpp, h, w, dtype=torch.float64)
+    g_dep, g_opa, g_den = (zero if g is None else planes(g.detach().cpu().double(), h, w) for g in grads)
+    inside = ((total >= l) & (total <= u)) if float64_clamp else clamp_pattern(fullres, delta_density[:, :gpp], lo, hi)
+    g_delta = torch.where(inside, -g_dep / (fine * fine), zero)
+    return dict(depths=(1.0 / fine).float(), opacities=op.float(), densities=p.float(), g_fullres=g_delta.sum(dim=1, keepdim=True).float(),
+                g_delta=g_delta.float(), g_logit=(g_opa * slope + g_den * (p * q)).float())
+
+
+def opacity_map_elements(pdf, exponent, g=None):
+    """map_pdf_to_opacity on probabilities, as the reference states it (with pow, which the kernel deliberately uses too):
+    (want, A) of the value, A = 0.5 (1 + (1 - p)^e + p^(1 / e)); with g, of the gradient in p, g 0.5 (e (1 - p)^(e - 1) +
+    p^(1 / e - 1) / e), whose two terms have one sign: A = |want| (infinite where the statement is)."""
+    p, e = pdf.detach().cpu().double(), float(exponent)
+    if g is None:
+        a, b = (1.0 - p) ** e, p ** (1.0 / e)
+        return 0.5 * (1.0 - a + b), 0.5 * (1.0 + a + b)
+    want = g.detach().cpu().double() * (0.5 * (e * (1.0 - p) ** (e - 1.0) + p ** (1.0 / e - 1.0) / e))
+    return want, want.abs()
+
+
+def plant(fullres, delta_density, lo, hi, gpp):
+    """Copies of a random case's fullres and delta / logits with the edges planted: the first density logits of every image become
+    PLANTED_LOGITS (as many as fit), and the first pixels of every image get fullres + delta exactly on lo, on hi, one float32 ulp
+    on either side of each, and lo and hi with a delta of a quarter ulp either way — the float64 sum is off the bound, the float32
+    sum is on it.  Image ni starts the list at entry ni, so that an image of one pixel still meets another entry."""
+    fullres, dd = fullres.clone(), delta_density.clone()
+    n, _, h, w = fullres.shape
+    inf = torch.tensor(float("inf"), device=fullres.device)
+    f_flat, d_flat, x_flat = fullres.view(n, h * w), dd[:, :gpp].reshape(n, gpp, h * w).clone(), dd[:, gpp:].reshape(n, gpp * h * w).clone()
+    values = torch.tensor(PLANTED_LOGITS, device=fullres.device)
+    for ni in range(n):
+        l, u = lo[ni], hi[ni]
+        sums = [(l, 0.0), (u, 0.0), (torch.nextafter(l, -inf), 0.0), (torch.nextafter(l, inf), 0.0), (torch.nextafter(u, -inf), 0.0),
+                (torch.nextafter(u, inf), 0.0), (l, l * 2.0 ** -26), (l, -l * 2.0 ** -26), (u, u * 2.0 ** -26), (u, -u * 2.0 ** -26)]
+        for i in range(min(len(sums), h * w)):
+            base, delta = sums[(i + ni) % len(sums)]
+            f_flat[ni, i] = base
+            d_flat[ni, :, i] = delta
+        k = min(len(values), x_flat.shape[1])
+        x_flat[ni, :k] = values.roll(-ni)[:k]
+    dd[:, :gpp] = d_flat.view(n, gpp, h, w)
+    dd[:, gpp:] = x_flat.view(n, gpp, h, w)
+    return fullres, dd
 
 
 PREDICTOR_SOURCE = """
