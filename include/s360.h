@@ -1038,6 +1038,34 @@ int s360_qkv_attention_backward(const float* qkv, const double* lse, const float
                                 int32_t ch, int32_t tokens, int32_t order, double* delta, float* g_qkv, void* stream);
 
 /*
+ * The "high" precision mode of the QKV attention: the function of s360_qkv_attention_* with each of its six products (scores
+ * Q^T K and O = V P^T in the forward; dP = dO^T V, g_q = K dS^T, g_k = Q dS and g_v = dO P in the backward) as a bf16x3 product on
+ * v_mfma_f32_32x32x16_bf16 — the specification of s360_window_attention_high_* above: split(x) = (hi, lo), hi = bf16(x) round to
+ * nearest even, lo = bf16(x - float32(hi)); A B = Ah Bh + Ah Bl + Al Bh accumulated in float32 by the MFMA, Al Bl dropped.  Both
+ * operands of every product are split from their float32 values: q and k UNSCALED (1 / sqrt(ch) multiplies the summed score and
+ * g_q, g_k once), P and dS as the softmax and its backward leave them.  The softmax with its float32 running maximum and float64
+ * running sum, lse[B, heads, L] FLOAT64, Delta = sum_s P dP / sum_s P, the layout rules (both orders, the (v b) rows of the joint
+ * sequence, in-place writes of out and g_qkv), the four waves on one owner tile and their fixed-order combine are those of
+ * s360_qkv_attention_*; the backward recomputes every score and dP from the forward's split operands with the terms in the
+ * forward's order and takes the lse of a "high" forward.
+ * A pre-pass splits q, k, v (and g_out) once per call into bf16 planes in joint-sequence order per (batch element, head) in
+ * `scratch`, L rounded up to a multiple of 32 (Lpad) and the padding written as zeros: rows [B, heads, Lpad, 32] for the products
+ * over the channels, transposed [B, heads, 32, Lpad] for those over the walked tokens.  s360_qkv_attention_high_scratch_bytes
+ * returns the size for a forward (backward == 0: rows of q and k, transposed v — the bytes of qkv at Lpad tokens) or a backward
+ * (rows of q, k, v and g_out, transposed q, k and g_out — 1.75 x the bytes of qkv and g_out at Lpad tokens), 0 for arguments the
+ * calls refuse.  The contents need no initialisation and nothing in it is read by a later call: the backward splits again.
+ * No atomics, no host synchronisation, no allocation; bit-identical from run to run and across streams.  Refusals as for
+ * s360_qkv_attention_*; a null scratch or one not 16-byte aligned: S360_E_BADARG, scratch_bytes smaller than reported:
+ * S360_E_WORKSPACE, both before any GPU work.
+ */
+size_t s360_qkv_attention_high_scratch_bytes(int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens, int32_t backward);
+int s360_qkv_attention_high_forward(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens,
+                                    int32_t order, float* out, double* lse, void* scratch, size_t scratch_bytes, void* stream);
+int s360_qkv_attention_high_backward(const float* qkv, const double* lse, const float* g_out, int32_t rows, int32_t views,
+                                     int32_t heads, int32_t ch, int32_t tokens, int32_t order, double* delta, float* g_qkv,
+                                     void* scratch, size_t scratch_bytes, void* stream);
+
+/*
  * The encoder's normalise-then-activate pair, forward and backward: GroupNorm (the reference's GroupNorm8 / GroupNorm4,
  * src/model/encoder/costvolume/ldm_unet/util.py:199-238, and nn.GroupNorm at depth_predictor_multiview_360.py:425-427, :480-482)
  * or InstanceNorm2d without affine (groups == channels; backbone/unimatch/backbone.py:28-36), the activation that follows it

@@ -19,7 +19,19 @@ The driver starts no GPU work itself: every step (one case, one path) is a child
 one after the other, and the first one that fails, is killed or times out ends the run (what was measured until then is
 written, with the failed step's name).  Each time is the median of `calls` calls (HIP events around one call, launch overhead
 included) after 3 warm-up calls.  forward_tflops is 4 B heads L^2 ch floating-point operations (the two products) over the
-forward's median time."""
+forward's median time.
+
+    python scripts/qkv_attention_timing.py --high [--out profiles/qkv_attention_high_timing.json] [--collections 3]
+
+times the "high" precision mode (bf16x3 products) against the default one -> profiles/qkv_attention_high_timing.json.  Paths:
+  highest     qkv_attention(..., precision="highest"), the `native` path above
+  high        qkv_attention(..., precision="high")
+  torch       the float32 torch lines under torch.set_float32_matmul_precision('highest')
+  torch_high  the same lines under 'high', the setting held over the backward too
+One child process per case runs the four paths ALTERNATED: `collections` rounds, in each round every path in turn, `calls` calls
+of the forward and `calls` of forward + backward.  A figure is the median of the rounds' medians, and `spread` the distance between
+the largest and the smallest round median — what a difference between two paths has to exceed to mean anything.  Peaks are
+bytes REQUESTED from the allocator (requested_bytes of torch.cuda.memory_stats)."""
 import argparse
 import json
 import statistics
@@ -79,6 +91,99 @@ def path_function(path, n, views, heads):
     return window
 
 
+HIGH_PATHS = ("highest", "high", "torch", "torch_high")
+
+
+def peak_requested(fn):
+    import torch
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_stats()["requested_bytes.all.current"]
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.memory_stats()["requested_bytes.all.peak"] - base
+
+
+def high_step(case, calls, collections):
+    """One child's work in the --high mode: the four paths of one case, alternated."""
+    import torch
+
+    import qkv_attention_reference as R
+    from splatter360_amd import qkv_attention as qa
+
+    n, views, heads, t = CASES[case]
+    qkv, g = R.random_case(n, heads, t, ch=CH, seed=11, device="cuda:0")
+
+    def under(setting, fn):
+        def run(*a):
+            before = torch.get_float32_matmul_precision()
+            torch.set_float32_matmul_precision(setting)
+            try:
+                return fn(*a)
+            finally:
+                torch.set_float32_matmul_precision(before)
+        return run
+
+    lines = lambda x: R.reference_lines(x, heads, views, True, "legacy")
+    fns = {"highest": lambda x: qa.qkv_attention(x, heads, n_frames=views, cross_view=True, precision="highest"),
+           "high": lambda x: qa.qkv_attention(x, heads, n_frames=views, cross_view=True, precision="high"),
+           "torch": lines, "torch_high": lines}
+    setting = {"highest": "highest", "high": "highest", "torch": "highest", "torch_high": "high"}
+
+    def legs(path):
+        def forward():
+            with torch.no_grad():
+                return fns[path](qkv)
+        return under(setting[path], forward), under(setting[path], lambda: R.gradients(fns[path], qkv, g))
+
+    rounds = {path: {"fwd_ms": [], "fwd_bwd_ms": []} for path in HIGH_PATHS}
+    for _ in range(collections):
+        for path in HIGH_PATHS:
+            forward, forward_backward = legs(path)
+            rounds[path]["fwd_ms"].append(timed(forward, calls)["median"])
+            rounds[path]["fwd_bwd_ms"].append(timed(forward_backward, calls)["median"])
+    res = {}
+    for path in HIGH_PATHS:
+        forward, forward_backward = legs(path)
+        res[path] = {key: {"median": statistics.median(ms), "spread": max(ms) - min(ms), "rounds": ms} for key, ms in rounds[path].items()}
+        res[path]["fwd_peak_requested_bytes"], res[path]["fwd_bwd_peak_requested_bytes"] = peak_requested(forward), peak_requested(forward_backward)
+    length = views * t
+    for path in ("highest", "high"):
+        res[path]["forward_tflops"] = 4.0 * (n // views) * heads * length * length * CH / (res[path]["fwd_ms"]["median"] * 1e-3) / 1e12
+    for key in ("fwd_ms", "fwd_bwd_ms"):
+        for other in ("highest", "torch", "torch_high"):
+            res[f"high_speedup_over_{other}_{key[:-3]}"] = res[other][key]["median"] / res["high"][key]["median"]
+    res["qkv_bytes"] = qkv.numel() * 4
+    res["high_scratch_bytes"] = {"forward": qa.scratch_bytes(n, views, heads, t, False), "backward": qa.scratch_bytes(n, views, heads, t, True)}
+    return res
+
+
+def high_main(args):
+    out_path = Path(args.out if args.out else ROOT / "profiles" / "qkv_attention_high_timing.json")
+    res = {"calls": args.calls, "collections": args.collections, "head_channels": CH, "failed_step": None, "cases": {}}
+    rc = 0
+    for case in args.cases:
+        cmd = ["timeout", "-k", "10", str(STEP_LIMIT), sys.executable, __file__, "--calls", str(args.calls), "--collections",
+               str(args.collections), "--high-step", case]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("STEP_RESULT ")]
+        if r.returncode != 0 or not lines:
+            res["failed_step"] = {"case": case, "returncode": r.returncode, "stderr": r.stderr[-1500:]}
+            print("FAILED", res["failed_step"], flush=True)
+            rc = 1
+            break                                               # nothing is started on the GPU after a failed step
+        res["cases"][case] = {"shape": dict(zip(("N", "views", "heads", "T"), CASES[case])), **json.loads(lines[0][len("STEP_RESULT "):])}
+        print(case, json.dumps(res["cases"][case]), flush=True)
+    if rc == 0:
+        import torch
+
+        from splatter360_amd import _lib
+        res["device"], res["source_hash"] = torch.cuda.get_device_name(0), _lib.source_hash()
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    out_path.write_text(json.dumps(res, indent=1) + "\n")
+    return rc
+
+
 def step(case, path, calls):
     """One child's work: returns the figures of (case, path)."""
     import torch
@@ -107,12 +212,22 @@ def step(case, path, calls):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "qkv_attention_timing.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/qkv_attention_timing.json (--high: profiles/qkv_attention_high_timing.json)")
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--cases", nargs="*", default=list(CASES))
     ap.add_argument("--paths", nargs="*", default=list(PATHS))
     ap.add_argument("--step", nargs=2, metavar=("CASE", "PATH"), help="run one step in this process and print its JSON")
+    ap.add_argument("--high", action="store_true", help='time the "high" precision mode (the docstring)')
+    ap.add_argument("--collections", type=int, default=3)
+    ap.add_argument("--high-step", metavar="CASE", help="run one case of the --high mode in this process and print its JSON")
     args = ap.parse_args()
+    if args.high_step:
+        print("STEP_RESULT " + json.dumps(high_step(args.high_step, args.calls, args.collections)))
+        return 0
+    if args.high:
+        return high_main(args)
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / "qkv_attention_timing.json")
     if args.step:
         print("STEP_RESULT " + json.dumps(step(args.step[0], args.step[1], args.calls)))
         return 0

@@ -131,6 +131,9 @@ SIGNATURES = {
     "s360_group_norm_backward": (_int, [_vp] * 5 + [_i32, _i32, _sz, _i32, _pf64, _i32] + [_vp] * 5),
     "s360_qkv_attention_forward": (_int, [_vp] + [_i32] * 6 + [_vp] * 3),
     "s360_qkv_attention_backward": (_int, [_vp] * 3 + [_i32] * 6 + [_vp] * 3),
+    "s360_qkv_attention_high_scratch_bytes": (_sz, [_i32] * 6),
+    "s360_qkv_attention_high_forward": (_int, [_vp] + [_i32] * 6 + [_vp] * 3 + [_sz, _vp]),
+    "s360_qkv_attention_high_backward": (_int, [_vp] * 3 + [_i32] * 6 + [_vp] * 3 + [_sz, _vp]),
     "s360_ffn_tail_scratch_bytes": (_sz, [_i32]),
     "s360_ffn_tail_weight_chunks": (_int, [_i32]),
     "s360_ffn_tail_forward": (_int, [_vp] * 8 + [_i32] * 3 + [_pf64] + [_vp] * 4),

@@ -459,3 +459,518 @@ extern "C" int s360_qkv_attention_backward(const float* qkv, const double* lse, 
     hipLaunchKernelGGL(k_qa_backward_kv, grid, block, 0, st, a, lse, delta, g_out, g_qkv);
     return s360_launch_status();
 }
+
+// ---------------------------------------------------------------------------------------------- the "high" mode (bf16 x 3)
+// The same function with every product as a bf16x3 product on v_mfma_f32_32x32x16_bf16 — the window attention's specification
+// (s360_window_attention.hip, "the high mode"): split(x) = (hi, lo), hi = bf16(x) round-to-nearest-even, lo = bf16(x - float32(hi));
+// A B = Ah Bh + Ah Bl + Al Bh, accumulated in float32 by the MFMA; q and k are split unscaled and 1 / sqrt(ch) multiplies the
+// summed score (and g_q, g_k) once.  Orientation, decomposition and combine are those of the kernels above: the owner on the
+// lanes, the walked tile on the accumulator's rows, four waves on one owner tile, their partial results combined through LDS in
+// the order w = 0..3.  No float64 chunk sums: the split's own error (2^-16 of a product) is far above a float32 chain's, so a
+// score is the MFMA's float32 sum, and tiles are accumulated in float32 in the MFMA's accumulator, rescaled by the running
+// maximum's factor in the forward.  The forward's softmax is float32 (score x float32(1 / sqrt(ch)), minus the running maximum);
+// the backward's P = exp(float32(sum / sqrt(ch) - lse)) and dS = P float32(dP - Delta) take their differences in float64, as the
+// kernels above do: P is then the float32 number next to the exact softmax of the summed scores, which is what its split depends on
+// (a P a few float32 steps off rounds its lo part the other way now and then, 2^-17 P each time; qah_exp).
+// A pre-pass (k_qah_split, one launch per operand) resolves the (v b) row gather, the head interleave and the channel order
+// once per call and writes bf16 planes in joint-sequence order per (batch element, head) into the caller's scratch, L padded
+// to a multiple of 32 (Lpad) with zeros — every byte the main kernels read is written, so the scratch needs no initialisation:
+//   rows       [B, heads, Lpad, 32]: a lane reads 8 consecutive channels of its token, 16 bytes (scores, dP)
+//   transposed [B, heads, 32, Lpad]: the walked token is the k-dimension (O, g_q, g_k, g_v).  Within a tile of 32 tokens the
+//              order is the one the B operand imposes: registers 8 s .. 8 s + 7 of a score-shaped tile are k-step s, element j of
+//              lane half h is tile row 16 s + 8 (j / 4) + 4 h + j % 4 (mfma_acc_row), so token u of a tile is stored at
+//              qah_tpos(u) = 16 h + 8 s + j and a lane reads its 8 tokens of a step as 16 consecutive bytes.
+// The three terms of a score are issued in one order of (q, k) terms — (qh, kh), (ql, kh), (qh, kl) — whichever side is walked
+// (SWAP), and dP likewise in (g, v): the P recomputed in both backward passes is formed from the forward's sums bit for bit.
+// Walked fragments are read straight from the planes (they stay in L2: 256 KB per plane and head at L = 4096), the next tile's
+// loads issued before the current tile's products.
+namespace s360 {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+struct QAHPlanes {                                            // hi and lo planes of the operands; null where a call has none
+    __bf16 *q_rh, *q_rl, *q_th, *q_tl;
+    __bf16 *k_rh, *k_rl, *k_th, *k_tl;
+    __bf16 *v_rh, *v_rl, *v_th, *v_tl;
+    __bf16 *g_rh, *g_rl, *g_th, *g_tl;
+};
+
+__host__ __device__ __forceinline__ int qah_pad(int n) { return (n + QA_T - 1) & ~(QA_T - 1); }
+
+// position of token u (< 32) of a tile in a transposed plane (above)
+__device__ __forceinline__ int qah_tpos(int u) { return 16 * ((u >> 2) & 1) + 8 * (u >> 4) + 4 * ((u >> 3) & 1) + (u & 3); }
+
+__device__ __forceinline__ void qah_split(float x, __bf16& hi, __bf16& lo) {
+    hi = (__bf16)x;
+    lo = (__bf16)(x - (float)hi);
+}
+
+// exp(x) of a float64 x as a float32 number: expf of x's leading float32 part e, times 1 + the rest.  The backward's P through
+// this is within a float32 step or two of the exact exp(x); expf((float)x) alone is off by the rounding of x, up to 2^-24 |x| of P.
+__device__ __forceinline__ float qah_exp(double x) {
+    const float h = (float)x, e = expf(h);
+    return fmaf(e, (float)(x - (double)h), e);
+}
+
+__device__ __forceinline__ bf16x8 qah_ld8(const __bf16* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p)); }
+
+__device__ __forceinline__ f32x16 qah_mfma(bf16x8 x, bf16x8 y, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, c, 0, 0, 0); }
+
+// the two k-steps of one operand tile, hi and lo: of a rows plane channels 8 hf + 16 s .. + 7 of the lane's token, of a
+// transposed plane the lane's channel at the 8 tokens of step s
+struct QAHFrag { bf16x8 h[2], l[2]; };
+
+// p: element offset of the lane's first 8 values; step: elements between the k-steps (16 in a rows plane, 8 in a transposed one)
+__device__ __forceinline__ QAHFrag qah_load(const __bf16* hi, const __bf16* lo, size_t p, int step) {
+    QAHFrag f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) f.h[s] = qah_ld8(hi + p + s * step), f.l[s] = qah_ld8(lo + p + s * step);
+    return f;
+}
+
+// tile[walked][owner] = sum over the 32 channels of walked row x owner row: walked fragments as A, the owner's as B
+template <bool SWAP>
+__device__ __forceinline__ f32x16 qah_dot(const QAHFrag& w, const QAHFrag& o) {
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        acc = qah_mfma(w.h[s], o.h[s], acc);
+        if constexpr (SWAP) {
+            acc = qah_mfma(w.l[s], o.h[s], acc);
+            acc = qah_mfma(w.h[s], o.l[s], acc);
+        } else {
+            acc = qah_mfma(w.h[s], o.l[s], acc);
+            acc = qah_mfma(w.l[s], o.h[s], acc);
+        }
+    }
+    return acc;
+}
+
+// acc^T[channel][owner] += sum over the tile's 32 walked tokens of t[channel][token] x[token][owner]: x[16] is the lane's column
+// of a score-shaped tile, split here register by register
+__device__ __forceinline__ f32x16 qah_accumulate(f32x16 acc, const QAHFrag& t, const float* x) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        bf16x8 xh, xl;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            __bf16 hi, lo;
+            qah_split(x[8 * s + j], hi, lo);
+            xh[j] = hi;
+            xl[j] = lo;
+        }
+        acc = qah_mfma(t.h[s], xh, acc);
+        acc = qah_mfma(t.h[s], xl, acc);
+        acc = qah_mfma(t.l[s], xh, acc);
+    }
+    return acc;
+}
+
+// The pre-pass: one operand (which: 0 q, 1 k, 2 v of qkv; 3 g_out) into its planes.  Thread i takes 8 channels of one joint
+// token of one (batch element, head), the token fastest: a wave's reads are 8 coalesced rows along t and its 2-byte stores into
+// the transposed plane fill whole 64-byte tiles.  Tokens from L to Lpad are written as zeros.  rh / rl or th / tl may be null.
+__global__ __launch_bounds__(S360_BLOCK) void k_qah_split(QAArgs a, const float* __restrict__ src, int which, __bf16* __restrict__ rh,
+                                                          __bf16* __restrict__ rl, __bf16* __restrict__ th, __bf16* __restrict__ tl) {
+    const int lpad = qah_pad(a.L);
+    const size_t i = (size_t)blockIdx.x * S360_BLOCK + threadIdx.x;
+    const size_t per = (size_t)lpad * (QA_CH / 8), nbh = (size_t)a.B * a.heads;
+    if (i >= nbh * per) return;
+    const size_t bh = i / per;
+    const int rem = (int)(i - bh * per), cg = rem / lpad, s = rem - cg * lpad;
+    const int bi = (int)(bh / a.heads), hd = (int)(bh - (size_t)bi * a.heads);
+    int width = a.heads * QA_CH, coff = hd * QA_CH;
+    if (which != 3) {
+        int qo, ko, vo;
+        qa_head(a, hd, qo, ko, vo);
+        width = a.W;
+        coff = which == 0 ? qo : which == 1 ? ko : vo;
+    }
+    float x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = 0.f;
+    if (s < a.L) {
+        const float* p = src + qa_token(a, bi, s, width) + (size_t)(coff + 8 * cg) * a.T;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = p[(size_t)j * a.T];
+    }
+    bf16x8 hi, lo;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        __bf16 h, l;
+        qah_split(x[j], h, l);
+        hi[j] = h;
+        lo[j] = l;
+    }
+    if (rh) {
+        const size_t o = (bh * lpad + s) * QA_CH + 8 * cg;
+        *reinterpret_cast<uint4*>(rh + o) = __builtin_bit_cast(uint4, hi);
+        *reinterpret_cast<uint4*>(rl + o) = __builtin_bit_cast(uint4, lo);
+    }
+    if (th) {
+        const int pos = (s & ~(QA_T - 1)) + qah_tpos(s & (QA_T - 1));
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const size_t o = (bh * QA_CH + 8 * cg + j) * lpad + pos;
+            th[o] = hi[j];
+            tl[o] = lo[j];
+        }
+    }
+}
+
+// what the three main kernels share: the lane's offsets into the planes of its (batch element, head)
+struct QAHLane {
+    size_t rows;                                              // rows plane: (token l31 of tile 0, channel 8 hf); a tile is QA_T QA_CH further
+    size_t cols;                                              // transposed plane: (channel l31, position 16 hf of tile 0); a tile is QA_T further
+    size_t own;                                               // rows plane: (the lane's owner token, channel 8 hf)
+};
+__device__ __forceinline__ QAHLane qah_lane(const QAArgs& a, const QABlock& w, int l31, int hf) {
+    const size_t lpad = qah_pad(a.L), bh = (size_t)w.bi * a.heads + w.hd;
+    QAHLane o;
+    o.rows = (bh * lpad + l31) * QA_CH + 8 * hf;
+    o.cols = (bh * QA_CH + l31) * lpad + 16 * hf;
+    o.own = o.rows + (size_t)w.ot * QA_T * QA_CH;
+    return o;
+}
+constexpr int QAH_ROWS_TILE = QA_T * QA_CH;
+
+// Forward.  Owner: 32 queries, their split rows in registers.  Each wave walks its key tiles with a float32 running maximum, a
+// float64 running sum and O^T in the MFMA's accumulator; wave 0 merges the four (m, sum, O) in the order w = 0..3 and writes.
+__global__ __launch_bounds__(S360_BLOCK) void k_qah_forward(QAArgs a, QAHPlanes pl, float* __restrict__ out, double* __restrict__ lse) {
+    __shared__ float s_o[QA_WAVES][16][S360_WAVE];
+    __shared__ double s_l[QA_WAVES][S360_WAVE];
+    __shared__ float s_m[QA_WAVES][S360_WAVE];
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const QABlock w = qa_block(a);
+    const QAHLane at = qah_lane(a, w, l31, hf);
+    const int sq = w.ot * QA_T + l31;
+    const bool qvalid = sq < a.L;
+    const float sc = (float)a.inv_scale;
+    const QAHFrag q = qah_load(pl.q_rh, pl.q_rl, at.own, 16);
+    f32x16 o;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[r] = 0.f;
+    float m = -INFINITY;
+    double lsum = 0.0;
+    const int ntiles = (a.L + QA_T - 1) / QA_T;
+    QAHFrag k = q, v = q;                                     // a wave without tiles never uses them
+    if (wave < ntiles) {
+        k = qah_load(pl.k_rh, pl.k_rl, at.rows + (size_t)wave * QAH_ROWS_TILE, 16);
+        v = qah_load(pl.v_th, pl.v_tl, at.cols + (size_t)wave * QA_T, 8);
+    }
+    for (int t = wave; t < ntiles; t += QA_WAVES) {
+        QAHFrag kn = k, vn = v;
+        if (t + QA_WAVES < ntiles) {
+            kn = qah_load(pl.k_rh, pl.k_rl, at.rows + (size_t)(t + QA_WAVES) * QAH_ROWS_TILE, 16);
+            vn = qah_load(pl.v_th, pl.v_tl, at.cols + (size_t)(t + QA_WAVES) * QA_T, 8);
+        }
+        const f32x16 s = qah_dot<false>(k, q);                // S^T: rows = keys, lane = query
+        float p[16];
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            p[r] = t * QA_T + mfma_acc_row(r, hf) < a.L ? s[r] * sc : -INFINITY;
+            tmax = fmaxf(tmax, p[r]);
+        }
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+        const float mnew = fmaxf(m, tmax);                    // finite: key 0 of every tile exists
+        const float alpha = expf(m - mnew);                   // 0 at the wave's first tile
+        float rs = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            p[r] = expf(p[r] - mnew);
+            rs += p[r];
+        }
+        rs += __shfl_xor(rs, 32);
+        lsum = lsum * (double)alpha + (double)rs;
+        m = mnew;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[r] *= alpha;
+        o = qah_accumulate(o, v, p);                          // O^T += V P^T
+        k = kn;
+        v = vn;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s_o[wave][r][lane] = o[r];
+    s_l[wave][lane] = lsum;
+    s_m[wave][lane] = m;
+    __syncthreads();
+    if (wave != 0 || !qvalid) return;
+    float mall = m;                                           // wave 0 has tile 0: finite
+#pragma unroll
+    for (int u = 1; u < QA_WAVES; ++u) mall = fmaxf(mall, s_m[u][lane]);
+    double x[16], l = 0.0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) x[r] = 0.0;
+#pragma unroll
+    for (int u = 0; u < QA_WAVES; ++u) {
+        const double f = (double)expf(s_m[u][lane] - mall);   // 0 for a wave without tiles (its maximum is -inf)
+        l += s_l[u][lane] * f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) x[r] += (double)s_o[u][r][lane] * f;
+    }
+    float* po = out + qa_token(a, w.bi, sq, a.heads * QA_CH) + (size_t)(w.hd * QA_CH) * a.T;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) po[(size_t)mfma_acc_row(r, hf) * a.T] = (float)(x[r] / l);
+    if (hf == 0) lse[((size_t)w.bi * a.heads + w.hd) * a.L + sq] = (double)mall + log(l);
+}
+
+// Backward, Delta and the q rows of g_qkv.  Owner: 32 queries; two sweeps, as k_qa_backward_q: Delta = sum P dP / sum P from the
+// first, every term and the waves' partial sums (w = 0..3) in float64 — a tile's terms summed in float32 first missed the
+// accuracy rule at the 5-token shape at logits of +-100 (4.1e-6 on gradients of 2.9e-6: dS of a one-hot row is P (dP - Delta),
+// a small difference of numbers of 30) —, dS^T = P (dP - Delta) and g_q^T += K dS^T in the second.
+__global__ __launch_bounds__(S360_BLOCK) void k_qah_backward_q(QAArgs a, QAHPlanes pl, const double* __restrict__ lse,
+                                                               double* __restrict__ delta, float* __restrict__ g_qkv) {
+    __shared__ float s_acc[QA_WAVES][16][S360_WAVE];
+    __shared__ double s_sum[2][QA_WAVES][S360_WAVE];
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const QABlock w = qa_block(a);
+    const QAHLane at = qah_lane(a, w, l31, hf);
+    int qo, ko, vo;
+    qa_head(a, w.hd, qo, ko, vo);
+    const int sq = w.ot * QA_T + l31;
+    const bool qvalid = sq < a.L;
+    const size_t stat = ((size_t)w.bi * a.heads + w.hd) * a.L + sq;
+    const QAHFrag q = qah_load(pl.q_rh, pl.q_rl, at.own, 16), g = qah_load(pl.g_rh, pl.g_rl, at.own, 16);
+    const double lq = qvalid ? lse[stat] : 0.0;
+    double dsum = 0.0, psum = 0.0;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const int ntiles = (a.L + QA_T - 1) / QA_T;
+#pragma unroll
+    for (int sweep = 0; sweep < 2; ++sweep) {
+        QAHFrag k = q, v = q, kt = q;
+        if (wave < ntiles) {
+            k = qah_load(pl.k_rh, pl.k_rl, at.rows + (size_t)wave * QAH_ROWS_TILE, 16);
+            v = qah_load(pl.v_rh, pl.v_rl, at.rows + (size_t)wave * QAH_ROWS_TILE, 16);
+            if (sweep == 1) kt = qah_load(pl.k_th, pl.k_tl, at.cols + (size_t)wave * QA_T, 8);
+        }
+        for (int t = wave; t < ntiles; t += QA_WAVES) {
+            QAHFrag kn = k, vn = v, ktn = kt;
+            if (t + QA_WAVES < ntiles) {
+                kn = qah_load(pl.k_rh, pl.k_rl, at.rows + (size_t)(t + QA_WAVES) * QAH_ROWS_TILE, 16);
+                vn = qah_load(pl.v_rh, pl.v_rl, at.rows + (size_t)(t + QA_WAVES) * QAH_ROWS_TILE, 16);
+                if (sweep == 1) ktn = qah_load(pl.k_th, pl.k_tl, at.cols + (size_t)(t + QA_WAVES) * QA_T, 8);
+            }
+            const f32x16 s = qah_dot<false>(k, q);            // S^T
+            const f32x16 dp = qah_dot<false>(v, g);           // dP^T = V^T dO
+            float ds[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const bool kvalid = t * QA_T + mfma_acc_row(r, hf) < a.L;
+                const float p = (kvalid && qvalid) ? qah_exp((double)s[r] * a.inv_scale - lq) : 0.f;     // P^T
+                if (sweep == 0) dsum += (double)p * (double)dp[r], psum += (double)p;
+                else ds[r] = p * (float)((double)dp[r] - dsum);
+            }
+            if (sweep == 1) acc = qah_accumulate(acc, kt, ds);           // g_q^T += K dS^T
+            k = kn;
+            v = vn;
+            kt = ktn;
+        }
+        if (sweep == 0) {
+            dsum += __shfl_xor(dsum, 32);
+            psum += __shfl_xor(psum, 32);
+            s_sum[0][wave][lane] = dsum;
+            s_sum[1][wave][lane] = psum;
+            __syncthreads();
+            dsum = psum = 0.0;
+#pragma unroll
+            for (int u = 0; u < QA_WAVES; ++u) dsum += s_sum[0][u][lane], psum += s_sum[1][u][lane];
+            dsum = psum > 0.0 ? dsum / psum : 0.0;            // the same Delta in every wave; a query past L has no P
+            if (wave == 0 && qvalid && hf == 0) delta[stat] = dsum;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s_acc[wave][r][lane] = acc[r];
+    __syncthreads();
+    if (wave != 0 || !qvalid) return;
+    float* pg = g_qkv + qa_token(a, w.bi, sq, a.W) + (size_t)qo * a.T;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        double x = 0.0;
+#pragma unroll
+        for (int u = 0; u < QA_WAVES; ++u) x += (double)s_acc[u][r][lane];
+        pg[(size_t)mfma_acc_row(r, hf) * a.T] = (float)(x * a.inv_scale);
+    }
+}
+
+// Backward, the k and v rows of g_qkv.  Owner: 32 keys; the waves walk the query tiles, whose lse and Delta a wave stages in LDS.  S = Q^T K (rows = queries, lane = key), g_v^T += dO P, g_k^T += Q dS; the waves' partial tiles are
+// added in the order w = 0..3, g_v first, then g_k through the same area.
+__global__ __launch_bounds__(S360_BLOCK) void k_qah_backward_kv(QAArgs a, QAHPlanes pl, const double* __restrict__ lse,
+                                                                const double* __restrict__ delta, float* __restrict__ g_qkv) {
+    __shared__ float s_acc[QA_WAVES][16][S360_WAVE];
+    __shared__ double s_stat[QA_WAVES][S360_WAVE];            // per wave: lse of the tile's 32 queries, then their Delta
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
+    const QABlock w = qa_block(a);
+    const QAHLane at = qah_lane(a, w, l31, hf);
+    int qo, ko, vo;
+    qa_head(a, w.hd, qo, ko, vo);
+    const int sk = w.ot * QA_T + l31;
+    const bool kvalid = sk < a.L;
+    const size_t stat = ((size_t)w.bi * a.heads + w.hd) * a.L;
+    const double* stats = hf ? delta : lse;
+    const QAHFrag k = qah_load(pl.k_rh, pl.k_rl, at.own, 16), v = qah_load(pl.v_rh, pl.v_rl, at.own, 16);
+    f32x16 dk, dv;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dk[r] = dv[r] = 0.f;
+    const int ntiles = (a.L + QA_T - 1) / QA_T;
+    QAHFrag q = k, g = k, qt = k, gt = k;
+    const double* sl = s_stat[wave];
+    const double* sd = s_stat[wave] + QA_T;
+    double rs = 0.0;                                          // lse (lanes 0..31) or Delta (32..63) of query l31 of the tile
+    if (wave < ntiles) {
+        q = qah_load(pl.q_rh, pl.q_rl, at.rows + (size_t)wave * QAH_ROWS_TILE, 16);
+        g = qah_load(pl.g_rh, pl.g_rl, at.rows + (size_t)wave * QAH_ROWS_TILE, 16);
+        qt = qah_load(pl.q_th, pl.q_tl, at.cols + (size_t)wave * QA_T, 8);
+        gt = qah_load(pl.g_th, pl.g_tl, at.cols + (size_t)wave * QA_T, 8);
+        if (wave * QA_T + l31 < a.L) rs = stats[stat + wave * QA_T + l31];
+    }
+    for (int t = wave; t < ntiles; t += QA_WAVES) {
+        s_stat[wave][lane] = rs;
+        qa_wave_sync();
+        QAHFrag qn = q, gn = g, qtn = qt, gtn = gt;
+        if (t + QA_WAVES < ntiles) {
+            const int tn = t + QA_WAVES;
+            qn = qah_load(pl.q_rh, pl.q_rl, at.rows + (size_t)tn * QAH_ROWS_TILE, 16);
+            gn = qah_load(pl.g_rh, pl.g_rl, at.rows + (size_t)tn * QAH_ROWS_TILE, 16);
+            qtn = qah_load(pl.q_th, pl.q_tl, at.cols + (size_t)tn * QA_T, 8);
+            gtn = qah_load(pl.g_th, pl.g_tl, at.cols + (size_t)tn * QA_T, 8);
+            rs = tn * QA_T + l31 < a.L ? stats[stat + tn * QA_T + l31] : 0.0;
+        }
+        const f32x16 s = qah_dot<true>(q, k);                 // S: rows = queries, lane = key; the forward's sums, bit for bit
+        const f32x16 dp = qah_dot<true>(g, v);                // dP = dO^T V
+        float p[16], ds[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int qq = mfma_acc_row(r, hf);
+            p[r] = (kvalid && t * QA_T + qq < a.L) ? qah_exp((double)s[r] * a.inv_scale - sl[qq]) : 0.f;
+            ds[r] = p[r] * (float)((double)dp[r] - sd[qq]);   // dS = P (dP - Delta)
+        }
+        dv = qah_accumulate(dv, gt, p);                       // g_v^T += dO P
+        dk = qah_accumulate(dk, qt, ds);                      // g_k^T += Q dS
+        qa_wave_sync();
+        q = qn;
+        g = gn;
+        qt = qtn;
+        gt = gtn;
+    }
+    const size_t ktok = kvalid ? qa_token(a, w.bi, sk, a.W) : 0;
+    float* pk = g_qkv + ktok + (size_t)ko * a.T;
+    float* pv = g_qkv + ktok + (size_t)vo * a.T;
+#pragma unroll
+    for (int part = 0; part < 2; ++part) {
+        if (part == 1) __syncthreads();                       // wave 0 has read part 0
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s_acc[wave][r][lane] = part == 0 ? dv[r] : dk[r];
+        __syncthreads();
+        if (wave == 0 && kvalid) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                double x = 0.0;
+#pragma unroll
+                for (int u = 0; u < QA_WAVES; ++u) x += (double)s_acc[u][r][lane];
+                const size_t c = (size_t)mfma_acc_row(r, hf) * a.T;
+                if (part == 0) pv[c] = (float)x;
+                else pk[c] = (float)(x * a.inv_scale);
+            }
+        }
+    }
+}
+
+// The scratch of a call: the planes in the order q, k, v, g (rows, then transposed; hi, then lo), n = B heads Lpad 32 elements
+// each.  Forward: rows of q and k, transposed v (12 n bytes: the padded qkv's).  Backward: rows of all four, transposed q, k
+// and g (28 n bytes: 1.75 x the padded qkv and g_out).
+static size_t qah_layout(const QAArgs& a, bool backward, char* base, QAHPlanes* pl) {
+    const size_t n = (size_t)a.B * a.heads * qah_pad(a.L) * QA_CH;
+    size_t off = 0;
+    auto take = [&](__bf16** hi, __bf16** lo) {
+        if (pl) {
+            *hi = reinterpret_cast<__bf16*>(base + off);
+            *lo = reinterpret_cast<__bf16*>(base + off + 2 * n);
+        }
+        off += 4 * n;
+    };
+    QAHPlanes none = {};
+    if (pl) *pl = none;
+    QAHPlanes* p = pl ? pl : &none;
+    take(&p->q_rh, &p->q_rl);
+    take(&p->k_rh, &p->k_rl);
+    if (!backward) {
+        take(&p->v_th, &p->v_tl);
+        return off;
+    }
+    take(&p->v_rh, &p->v_rl);
+    take(&p->g_rh, &p->g_rl);
+    take(&p->q_th, &p->q_tl);
+    take(&p->k_th, &p->k_tl);
+    take(&p->g_th, &p->g_tl);
+    return off;
+}
+
+// qa_setup and what the "high" calls ask beyond it: Lpad is an int, both grids fit
+static int qah_setup(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens, int32_t order, QAArgs& a) {
+    const int rc = qa_setup(qkv, rows, views, heads, ch, tokens, order, a);
+    if (rc != S360_OK) return rc;
+    if (a.L > INT32_MAX - QA_T || !s360_grid_fits((long long)qa_grid(a))) return S360_E_BADARG;
+    return S360_OK;
+}
+
+static void qah_split_launch(const QAArgs& a, const float* src, int which, __bf16* rh, __bf16* rl, __bf16* th, __bf16* tl, hipStream_t st) {
+    const size_t n = (size_t)a.B * a.heads * qah_pad(a.L) * (QA_CH / 8);        // qa_grid(a) / 2 workgroups
+    hipLaunchKernelGGL(k_qah_split, dim3((unsigned)((n + S360_BLOCK - 1) / S360_BLOCK)), dim3(S360_BLOCK), 0, st, a, src, which, rh, rl, th, tl);
+}
+
+}  // namespace s360
+
+extern "C" size_t s360_qkv_attention_high_scratch_bytes(int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens,
+                                                        int32_t backward) {
+    QAArgs a;
+    const float* any = reinterpret_cast<const float*>((uintptr_t)16);           // qa_setup checks the pointer it is given; it is not read
+    if (qah_setup(any, rows, views, heads, ch, tokens, 0, a) != S360_OK) return 0;
+    return qah_layout(a, backward != 0, nullptr, nullptr);
+}
+
+extern "C" int s360_qkv_attention_high_forward(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens,
+                                               int32_t order, float* out, double* lse, void* scratch, size_t scratch_bytes,
+                                               void* stream) {
+    QAArgs a;
+    const int rc = qah_setup(qkv, rows, views, heads, ch, tokens, order, a);
+    if (rc != S360_OK) return rc;
+    if (!out || !lse || !scratch || !s360_aligned(scratch, 16)) return S360_E_BADARG;
+    if (scratch_bytes < qah_layout(a, false, nullptr, nullptr)) return S360_E_WORKSPACE;
+    QAHPlanes pl;
+    qah_layout(a, false, static_cast<char*>(scratch), &pl);
+    hipStream_t st = (hipStream_t)stream;
+    qah_split_launch(a, qkv, 0, pl.q_rh, pl.q_rl, nullptr, nullptr, st);
+    qah_split_launch(a, qkv, 1, pl.k_rh, pl.k_rl, nullptr, nullptr, st);
+    qah_split_launch(a, qkv, 2, nullptr, nullptr, pl.v_th, pl.v_tl, st);
+    S360_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_qah_forward, dim3(qa_grid(a)), dim3(S360_BLOCK), 0, st, a, pl, out, lse);
+    return s360_launch_status();
+}
+
+extern "C" int s360_qkv_attention_high_backward(const float* qkv, const double* lse, const float* g_out, int32_t rows, int32_t views,
+                                                int32_t heads, int32_t ch, int32_t tokens, int32_t order, double* delta, float* g_qkv,
+                                                void* scratch, size_t scratch_bytes, void* stream) {
+    QAArgs a;
+    const int rc = qah_setup(qkv, rows, views, heads, ch, tokens, order, a);
+    if (rc != S360_OK) return rc;
+    if (!lse || !g_out || !delta || !g_qkv || g_qkv == qkv || !scratch || !s360_aligned(scratch, 16)) return S360_E_BADARG;
+    if (scratch_bytes < qah_layout(a, true, nullptr, nullptr)) return S360_E_WORKSPACE;
+    QAHPlanes pl;
+    qah_layout(a, true, static_cast<char*>(scratch), &pl);
+    hipStream_t st = (hipStream_t)stream;
+    qah_split_launch(a, qkv, 0, pl.q_rh, pl.q_rl, pl.q_th, pl.q_tl, st);
+    qah_split_launch(a, qkv, 1, pl.k_rh, pl.k_rl, pl.k_th, pl.k_tl, st);
+    qah_split_launch(a, qkv, 2, pl.v_rh, pl.v_rl, nullptr, nullptr, st);
+    qah_split_launch(a, g_out, 3, pl.g_rh, pl.g_rl, pl.g_th, pl.g_tl, st);
+    S360_CHECK_LAUNCH();
+    const dim3 grid(qa_grid(a)), block(S360_BLOCK);
+    // the query-owned pass first: it writes Delta for the key-owned one
+    hipLaunchKernelGGL(k_qah_backward_q, grid, block, 0, st, a, pl, lse, delta, g_qkv);
+    S360_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_qah_backward_kv, grid, block, 0, st, a, pl, lse, delta, g_qkv);
+    return s360_launch_status();
+}

@@ -945,13 +945,25 @@ def _unet_attention_call(qkv, n_heads, views) -> bool:
     return width % (3 * n_heads) == 0 and _qa.supported_head_channels(width // (3 * n_heads)) and qkv.shape[0] % views == 0
 
 
+def _unet_attention_precision(precision) -> str:
+    """The `precision` option of the U-Net attention seam, checked when the seam is installed: "highest", "high", or "torch"
+    (window_attention.resolve_precision reads torch's float32 matmul precision at every call)."""
+    from . import qkv_attention as _qa
+    if precision != "torch" and precision not in _qa.PRECISIONS:
+        raise ValueError(f"unet_attention_precision is one of {[*_qa.PRECISIONS, 'torch']}, got {precision!r}")
+    return precision
+
+
 def _native_qkv_attention_forward(order):
     """QKVAttentionLegacy.forward (order "legacy": n_heads, n_frames, use_cross_view_self_attn of the module) or
     QKVAttention.forward (order "new": n_heads) with the reference's signature: the fused kernels of qkv_attention.py for the calls
     _unet_attention_call accepts, the replaced method otherwise (half precision, autocast, CPU, other ch — and every error the
-    reference raises).  `forward.native_calls` counts the calls the kernels took."""
-    def wrapper(replaced):
+    reference raises).  `forward.native_calls` counts the calls the kernels took.  precision: the seam's option, resolved at every
+    call — the recomputation under the reference's checkpoint included; `forward.precision` holds it."""
+    def wrapper(replaced, mod=None, precision="highest"):
         from . import qkv_attention as _qa
+        from . import window_attention as _wa
+        _unet_attention_precision(precision)
 
         def forward(self, qkv):
             heads = getattr(self, "n_heads", None)
@@ -959,10 +971,12 @@ def _native_qkv_attention_forward(order):
             frames = getattr(self, "n_frames", 1) if cross else 1
             if _unet_attention_call(qkv, heads, frames):
                 forward.native_calls += 1
-                return _qa.qkv_attention(qkv, heads, n_frames=frames, cross_view=cross, order=order)
+                return _qa.qkv_attention(qkv, heads, n_frames=frames, cross_view=cross, order=order,
+                                         precision=_wa.resolve_precision(precision))
             return replaced(self, qkv)
 
         forward.replaced = replaced
+        forward.precision = precision
         forward.native_calls = 0
         forward.__doc__ = _qa.qkv_attention.__doc__
         return forward
@@ -971,9 +985,9 @@ def _native_qkv_attention_forward(order):
 
 
 UNET_ATTENTION_LEGACY_SEAM = _MethodSeam("unet_attention", UNET_ATTENTION_MODULE, UNET_ATTENTION_LEGACY, (UNET_ATTENTION_METHOD,),
-                                         {UNET_ATTENTION_METHOD: _native_qkv_attention_forward("legacy")})
+                                         {UNET_ATTENTION_METHOD: _native_qkv_attention_forward("legacy")}, context=True)
 UNET_ATTENTION_NEW_SEAM = _MethodSeam("unet_attention", UNET_ATTENTION_MODULE, UNET_ATTENTION_NEW, (UNET_ATTENTION_METHOD,),
-                                      {UNET_ATTENTION_METHOD: _native_qkv_attention_forward("new")})
+                                      {UNET_ATTENTION_METHOD: _native_qkv_attention_forward("new")}, context=True)
 UNET_ATTENTION_SEAMS = (UNET_ATTENTION_LEGACY_SEAM, UNET_ATTENTION_NEW_SEAM)
 
 
@@ -1136,11 +1150,14 @@ def install_group_norm():
     return dict(zip((f"{seam.cls_name}.{seam.names[0]}" for seam in GROUP_NORM_SEAMS), _installed("group_norm")))
 
 
-def install_unet_attention():
+def install_unet_attention(precision: str = "highest"):
     """The half of install(unet_attention=True): rebind QKVAttentionLegacy.forward and QKVAttention.forward (ldm_unet/unet.py:527-599)
     to the wrappers around the fused QKV-attention kernels of qkv_attention.py now if the module is imported, else as soon as it
-    is (import hook).  Returns {"Class.forward": patched method or None}."""
-    return dict(zip((f"{seam.cls_name}.{seam.names[0]}" for seam in UNET_ATTENTION_SEAMS), _installed("unet_attention")))
+    is (import hook).  Returns {"Class.forward": patched method or None}.  precision: "highest" (exact float32 products), "high"
+    (bf16x3 products, qkv_attention.py) or "torch" (torch.get_float32_matmul_precision() at every call: 'highest' is "highest",
+    'high' and 'medium' are "high")."""
+    return dict(zip((f"{seam.cls_name}.{seam.names[0]}" for seam in UNET_ATTENTION_SEAMS),
+                    _installed("unet_attention", precision=_unet_attention_precision(precision))))
 
 
 def install_transformer_ffn(precision: str = "highest"):
@@ -1249,7 +1266,9 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     unet_attention=True: ALSO rebind the two U-Nets' QKVAttentionLegacy.forward and QKVAttention.forward (ldm_unet/unet.py:527-599)
     to the fused QKV-attention kernels of splatter360_amd.qkv_attention, which read the channel-major qkv tensor in place and form
     no [b heads, L, L] weight tensor (install_unet_attention; off by default; composes with group_norm, whose AttentionBlock._forward
-    calls self.attention, and with the reference's checkpoint).
+    calls self.attention, and with the reference's checkpoint).  unet_attention_precision: "highest" (the default), "high" (bf16x3
+    products on the bf16 MFMA, forward and backward) or "torch" (torch's setting at every call, the checkpoint's recomputation
+    included); independent of the other two precisions.
     transformer_ffn=True: ALSO rebind the multi-view transformer's TransformerLayer.forward (multiview_transformer.py:334-414) so
     that norm1, cat([source, message]), the mlp, norm2 and the residual behind the layer's attention run the fused kernels of
     splatter360_amd.transformer_ffn, which form no [T, 2C] or [T, 8C] tensor (install_transformer_ffn; off by default; composes
@@ -1261,10 +1280,11 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
     the fused decoder.  lazy=True: only installs an import hook that patches the registry when the reference itself first imports
     the package (for a sitecustomize that runs before sys.path is set up).  Idempotent.
-    opts: window_attention_precision, transformer_ffn_precision (above); for the decoder views_per_group (6), shared_campos (None = checked per group with one small read per forward), check ("sync"), glue."""
+    opts: window_attention_precision, unet_attention_precision, transformer_ffn_precision (above); for the decoder views_per_group (6), shared_campos (None = checked per group with one small read per forward), check ("sync"), glue."""
     given = locals()
     # an option of a seam, not a seam: taken out of opts (the decoder's options) before they reach the decoder
     given["window_attention_options"] = {"precision": _window_attention_precision(opts.pop("window_attention_precision", "highest"))}
+    given["unet_attention_options"] = {"precision": _unet_attention_precision(opts.pop("unet_attention_precision", "highest"))}
     given["transformer_ffn_options"] = {"precision": _transformer_ffn_precision(opts.pop("transformer_ffn_precision", "highest"))}
     for keyword, seams in OPTION_SEAMS.items():
         if given[keyword]:

@@ -11,6 +11,12 @@ and the autograd node saves qkv and one float64 log-sum-exp per (batch element, 
 speed against torch's rocBLAS path is what profiles/qkv_attention_timing.json says it is.  Float32 GPU tensors with ch = 32
 (what both U-Nets use); there is no CPU path (the installed seam keeps the replaced methods for everything else).  Forward and backward are
 bit-identical from run to run: fixed order, no atomics.
+
+precision="highest" (the default) forms every product from exact float32 products; precision="high" is what
+torch.set_float32_matmul_precision('high') asks for, as in window_attention.py: each float32 number as the sum of two bfloat16
+numbers and each product A B as Ah Bh + Ah Bl + Al Bh on the bf16 MFMA, accumulated in float32 (csrc: the k_qah_* kernels).  Its
+planes live in a scratch tensor of `scratch_bytes(...)` bytes that a call allocates and drops; the autograd node keeps qkv and lse
+in either mode.  `window_attention.resolve_precision("torch")` reads torch's setting at call time.
 """
 from __future__ import annotations
 
@@ -22,6 +28,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._call import call, ptr
+from .window_attention import PRECISIONS
 
 ORDERS = {"legacy": _lib.QKV_LEGACY, "new": _lib.QKV_NEW}
 HEAD_CHANNELS = (32,)
@@ -29,6 +36,22 @@ HEAD_CHANNELS = (32,)
 
 def supported_head_channels(ch: int) -> bool:
     return ch in HEAD_CHANNELS
+
+
+def _precision(precision: str) -> str:
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"qkv_attention knows the precisions {list(PRECISIONS)}, got precision={precision!r}")
+    return precision
+
+
+def scratch_bytes(rows: int, views: int, heads: int, tokens: int, backward: bool) -> int:
+    """s360_qkv_attention_high_scratch_bytes: the bytes of bf16 planes a "high" forward (backward) call needs."""
+    return int(_lib.lib().s360_qkv_attention_high_scratch_bytes(int(rows), int(views), int(heads), HEAD_CHANNELS[0], int(tokens),
+                                                                int(bool(backward))))
+
+
+def _scratch(qkv: Tensor, views: int, heads: int, backward: bool) -> Tensor:
+    return torch.empty(scratch_bytes(int(qkv.shape[0]), views, heads, int(qkv.shape[2]), backward), dtype=torch.uint8, device=qkv.device)
 
 
 def _checked(what: str, qkv, n_heads, n_frames, cross_view, order) -> tuple:
@@ -61,20 +84,30 @@ def _checked(what: str, qkv, n_heads, n_frames, cross_view, order) -> tuple:
     return rows, views, n_heads, ch, tokens, ORDERS[order]
 
 
-def attention_forward(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: bool = False, order: str = "legacy") -> tuple:
-    """s360_qkv_attention_forward -> (out [N, heads ch, T] float32, lse [N / views, heads, views T] float64)."""
+def attention_forward(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: bool = False, order: str = "legacy",
+                      precision: str = "highest") -> tuple:
+    """s360_qkv_attention_forward (precision "high": s360_qkv_attention_high_forward) -> (out [N, heads ch, T] float32,
+    lse [N / views, heads, views T] float64)."""
+    precision = _precision(precision)
     rows, views, heads, ch, tokens, code = _checked("attention_forward", qkv, n_heads, n_frames, cross_view, order)
     qkv = qkv.detach().contiguous()
     out = torch.empty(rows, heads * ch, tokens, dtype=torch.float32, device=qkv.device)
     lse = torch.empty(rows // views, heads, views * tokens, dtype=torch.float64, device=qkv.device)
-    call("s360_qkv_attention_forward", qkv.device, ptr(qkv), rows, views, heads, ch, tokens, code, ptr(out), ptr(lse))
+    args = (ptr(qkv), rows, views, heads, ch, tokens, code, ptr(out), ptr(lse))
+    if precision == "high":
+        scratch = _scratch(qkv, views, heads, False)
+        call("s360_qkv_attention_high_forward", qkv.device, *args, ptr(scratch), scratch.numel())
+    else:
+        call("s360_qkv_attention_forward", qkv.device, *args)
     return out, lse
 
 
 def attention_backward(qkv: Tensor, lse: Tensor, g_out: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: bool = False,
-                       order: str = "legacy", g_qkv: Optional[Tensor] = None) -> Tensor:
-    """s360_qkv_attention_backward -> g_qkv in qkv's shape and layout.  `g_qkv`: a contiguous float32 buffer of qkv's shape on its
-    device to write into (every element is written); allocated when None."""
+                       order: str = "legacy", g_qkv: Optional[Tensor] = None, precision: str = "highest") -> Tensor:
+    """s360_qkv_attention_backward (precision "high": s360_qkv_attention_high_backward, with the lse of a "high" forward) -> g_qkv
+    in qkv's shape and layout.  `g_qkv`: a contiguous float32 buffer of qkv's shape on its device to write into (every element is
+    written); allocated when None."""
+    precision = _precision(precision)
     rows, views, heads, ch, tokens, code = _checked("attention_backward", qkv, n_heads, n_frames, cross_view, order)
     if not isinstance(g_out, Tensor) or not g_out.is_cuda or g_out.dtype != torch.float32 or g_out.device != qkv.device \
             or tuple(g_out.shape) != (rows, heads * ch, tokens):
@@ -89,19 +122,23 @@ def attention_backward(qkv: Tensor, lse: Tensor, g_out: Tensor, n_heads: int, *,
             or tuple(g_qkv.shape) != tuple(qkv.shape) or not g_qkv.is_contiguous() or g_qkv.data_ptr() == qkv.data_ptr():
         raise ValueError("attention_backward: g_qkv must be a contiguous float32 buffer of qkv's shape on its device, not qkv itself")
     delta = torch.empty_like(lse)
-    call("s360_qkv_attention_backward", qkv.device, ptr(qkv), ptr(lse), ptr(g_out), rows, views, heads, ch, tokens, code,
-         ptr(delta), ptr(g_qkv))
+    args = (ptr(qkv), ptr(lse), ptr(g_out), rows, views, heads, ch, tokens, code, ptr(delta), ptr(g_qkv))
+    if precision == "high":
+        scratch = _scratch(qkv, views, heads, True)
+        call("s360_qkv_attention_high_backward", qkv.device, *args, ptr(scratch), scratch.numel())
+    else:
+        call("s360_qkv_attention_backward", qkv.device, *args)
     return g_qkv
 
 
 class _QKVAttention(torch.autograd.Function):
     """a of qkv; saves qkv and lse, nothing score-sized (the backward forms Delta from the recomputed probabilities, so not even
-    the output is kept)."""
+    the output is kept) and, in the "high" mode, none of the bf16 planes (the backward splits again)."""
 
     @staticmethod
-    def forward(ctx, qkv, n_heads, n_frames, cross_view, order):
+    def forward(ctx, qkv, n_heads, n_frames, cross_view, order, precision):
         qkv = qkv.detach().contiguous()
-        opts = dict(n_frames=n_frames, cross_view=cross_view, order=order)
+        opts = dict(n_frames=n_frames, cross_view=cross_view, order=order, precision=precision)
         out, lse = attention_forward(qkv, n_heads, **opts)
         ctx.save_for_backward(qkv, lse)
         ctx.n_heads, ctx.opts = n_heads, opts
@@ -111,10 +148,11 @@ class _QKVAttention(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_out):
         qkv, lse = ctx.saved_tensors
-        return attention_backward(qkv, lse, g_out.to(torch.float32), ctx.n_heads, **ctx.opts), None, None, None, None
+        return attention_backward(qkv, lse, g_out.to(torch.float32), ctx.n_heads, **ctx.opts), None, None, None, None, None
 
 
-def qkv_attention(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: bool = False, order: str = "legacy") -> Tensor:
+def qkv_attention(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: bool = False, order: str = "legacy",
+                  precision: str = "highest") -> Tensor:
     """The reference's QKVAttentionLegacy(n_heads, n_frames, use_cross_view_self_attn).forward (order "legacy", unet.py:527-565)
     or QKVAttention(n_heads).forward (order "new", :572-599) without its temporaries.
 
@@ -122,7 +160,9 @@ def qkv_attention(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: b
     heads ch rows, head hd owns [hd ch, (hd + 1) ch) of each.  With cross_view the n_frames views of a batch element, which lie
     in rows u N / n_frames + bi (the reference's (v b) order), form one joint sequence of n_frames T tokens; without it n_frames
     is not used and every row attends within itself.  weight = softmax((q ch^-1/4) . (k ch^-1/4)) over the keys,
-    a[c, t] = sum_s weight[t, s] v[c, s].  Returns a [N, heads ch, T] in qkv's row order.  Differentiable (once) in qkv.  Float32
-    GPU tensors, ch = 32; no CPU path; a non-contiguous qkv is copied once."""
+    a[c, t] = sum_s weight[t, s] v[c, s].  precision "highest": exact float32 products; "high": bf16x3 products on the bf16 MFMA,
+    forward and backward (the module's docstring).  Returns a [N, heads ch, T] in qkv's row order.  Differentiable (once) in qkv.
+    Float32 GPU tensors, ch = 32; no CPU path; a non-contiguous qkv is copied once."""
+    _precision(precision)
     _checked("qkv_attention", qkv, n_heads, n_frames, cross_view, order)
-    return _QKVAttention.apply(qkv, int(n_heads), int(n_frames), bool(cross_view), order)
+    return _QKVAttention.apply(qkv, int(n_heads), int(n_frames), bool(cross_view), order, precision)
