@@ -1,5 +1,5 @@
 // s360_launch.h — host-side rules every entry point of the library shares: the check after a launch, the bound on a grid,
-// pointer alignment and the workspace-size protocol of include/s360.h.
+// pointer alignment, the workspace-size protocol of include/s360.h and the check of a "high" call's scratch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,4 +47,11 @@ static inline int s360_workspace(const void* workspace, size_t* bytes, size_t ne
     }
     if (!args_ok || !s360_aligned(workspace, align)) return S360_E_BADARG;
     return *bytes < need ? S360_E_WORKSPACE : S360_WS_READY;
+}
+
+// The caller's scratch of a "high" call (its size comes from the operator's *_scratch_bytes): S360_E_BADARG for a null or
+// misaligned one, then S360_E_WORKSPACE for a short one, S360_OK otherwise.
+static inline int s360_scratch(const void* scratch, size_t bytes, size_t need) {
+    if (!scratch || !s360_aligned(scratch, 16)) return S360_E_BADARG;
+    return bytes < need ? S360_E_WORKSPACE : S360_OK;
 }

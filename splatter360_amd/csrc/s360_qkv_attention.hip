@@ -32,6 +32,7 @@
 // bit the forward's), dS = P (dP - Delta), Delta = sum_s P dP / sum_s P (float64) from a first sweep of the query-owned pass
 // over the very dP values dS subtracts it from.
 #include "s360_device.h"
+#include "s360_bf16x3.h"
 
 namespace s360 {
 
@@ -461,12 +462,10 @@ extern "C" int s360_qkv_attention_backward(const float* qkv, const double* lse, 
 }
 
 // ---------------------------------------------------------------------------------------------- the "high" mode (bf16 x 3)
-// The same function with every product as a bf16x3 product on v_mfma_f32_32x32x16_bf16 — the window attention's specification
-// (s360_window_attention.hip, "the high mode"): split(x) = (hi, lo), hi = bf16(x) round-to-nearest-even, lo = bf16(x - float32(hi));
-// A B = Ah Bh + Ah Bl + Al Bh, accumulated in float32 by the MFMA; q and k are split unscaled and 1 / sqrt(ch) multiplies the
-// summed score (and g_q, g_k) once.  Orientation, decomposition and combine are those of the kernels above: the owner on the
-// lanes, the walked tile on the accumulator's rows, four waves on one owner tile, their partial results combined through LDS in
-// the order w = 0..3.  No float64 chunk sums: the split's own error (2^-16 of a product) is far above a float32 chain's, so a
+// The same function with every product as a bf16x3 product (s360_bf16x3.h: the split, the three terms and their order, the
+// B-operand register rule); q and k are split unscaled and 1 / sqrt(ch) multiplies the summed score (and g_q, g_k) once.
+// Orientation, decomposition and combine are those of the kernels above: the owner on the lanes, the walked tile on the
+// accumulator's rows, four waves on one owner tile, their partial results combined through LDS in the order w = 0..3.  A
 // score is the MFMA's float32 sum, and tiles are accumulated in float32 in the MFMA's accumulator, rescaled by the running
 // maximum's factor in the forward.  The forward's softmax is float32 (score x float32(1 / sqrt(ch)), minus the running maximum);
 // the backward's P = exp(float32(sum / sqrt(ch) - lse)) and dS = P float32(dP - Delta) take their differences in float64, as the
@@ -477,16 +476,13 @@ extern "C" int s360_qkv_attention_backward(const float* qkv, const double* lse, 
 // to a multiple of 32 (Lpad) with zeros — every byte the main kernels read is written, so the scratch needs no initialisation:
 //   rows       [B, heads, Lpad, 32]: a lane reads 8 consecutive channels of its token, 16 bytes (scores, dP)
 //   transposed [B, heads, 32, Lpad]: the walked token is the k-dimension (O, g_q, g_k, g_v).  Within a tile of 32 tokens the
-//              order is the one the B operand imposes: registers 8 s .. 8 s + 7 of a score-shaped tile are k-step s, element j of
-//              lane half h is tile row 16 s + 8 (j / 4) + 4 h + j % 4 (mfma_acc_row), so token u of a tile is stored at
-//              qah_tpos(u) = 16 h + 8 s + j and a lane reads its 8 tokens of a step as 16 consecutive bytes.
-// The three terms of a score are issued in one order of (q, k) terms — (qh, kh), (ql, kh), (qh, kl) — whichever side is walked
-// (SWAP), and dP likewise in (g, v): the P recomputed in both backward passes is formed from the forward's sums bit for bit.
+//              order is the one the B-operand register rule imposes: token u = 16 s + 8 (j / 4) + 4 h + j % 4 of a tile is
+//              stored at qah_tpos(u) = 16 h + 8 s + j, and a lane reads its 8 tokens of a step as 16 consecutive bytes.
+// The terms of a score are in (q, k) order — (qh, kh), (ql, kh), (qh, kl) — and those of dP in (g, v) order, whichever side is
+// walked: the P recomputed in both backward passes is formed from the forward's sums bit for bit.
 // Walked fragments are read straight from the planes (they stay in L2: 256 KB per plane and head at L = 4096), the next tile's
 // loads issued before the current tile's products.
 namespace s360 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct QAHPlanes {                                            // hi and lo planes of the operands; null where a call has none
     __bf16 *q_rh, *q_rl, *q_th, *q_tl;
@@ -500,21 +496,12 @@ __host__ __device__ __forceinline__ int qah_pad(int n) { return (n + QA_T - 1) &
 // position of token u (< 32) of a tile in a transposed plane (above)
 __device__ __forceinline__ int qah_tpos(int u) { return 16 * ((u >> 2) & 1) + 8 * (u >> 4) + 4 * ((u >> 3) & 1) + (u & 3); }
 
-__device__ __forceinline__ void qah_split(float x, __bf16& hi, __bf16& lo) {
-    hi = (__bf16)x;
-    lo = (__bf16)(x - (float)hi);
-}
-
 // exp(x) of a float64 x as a float32 number: expf of x's leading float32 part e, times 1 + the rest.  The backward's P through
 // this is within a float32 step or two of the exact exp(x); expf((float)x) alone is off by the rounding of x, up to 2^-24 |x| of P.
 __device__ __forceinline__ float qah_exp(double x) {
     const float h = (float)x, e = expf(h);
     return fmaf(e, (float)(x - (double)h), e);
 }
-
-__device__ __forceinline__ bf16x8 qah_ld8(const __bf16* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p)); }
-
-__device__ __forceinline__ f32x16 qah_mfma(bf16x8 x, bf16x8 y, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, c, 0, 0, 0); }
 
 // the two k-steps of one operand tile, hi and lo: of a rows plane channels 8 hf + 16 s .. + 7 of the lane's token, of a
 // transposed plane the lane's channel at the 8 tokens of step s
@@ -524,27 +511,16 @@ struct QAHFrag { bf16x8 h[2], l[2]; };
 __device__ __forceinline__ QAHFrag qah_load(const __bf16* hi, const __bf16* lo, size_t p, int step) {
     QAHFrag f;
 #pragma unroll
-    for (int s = 0; s < 2; ++s) f.h[s] = qah_ld8(hi + p + s * step), f.l[s] = qah_ld8(lo + p + s * step);
+    for (int s = 0; s < 2; ++s) f.h[s] = bx3_ld8(hi + p + s * step), f.l[s] = bx3_ld8(lo + p + s * step);
     return f;
 }
 
 // tile[walked][owner] = sum over the 32 channels of walked row x owner row: walked fragments as A, the owner's as B
 template <bool SWAP>
 __device__ __forceinline__ f32x16 qah_dot(const QAHFrag& w, const QAHFrag& o) {
-    f32x16 acc;
+    f32x16 acc = bx3_zero();
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        acc = qah_mfma(w.h[s], o.h[s], acc);
-        if constexpr (SWAP) {
-            acc = qah_mfma(w.l[s], o.h[s], acc);
-            acc = qah_mfma(w.h[s], o.l[s], acc);
-        } else {
-            acc = qah_mfma(w.h[s], o.l[s], acc);
-            acc = qah_mfma(w.l[s], o.h[s], acc);
-        }
-    }
+    for (int s = 0; s < 2; ++s) acc = bx3_mfma3<SWAP>(w.h[s], w.l[s], o.h[s], o.l[s], acc);
     return acc;
 }
 
@@ -554,16 +530,8 @@ __device__ __forceinline__ f32x16 qah_accumulate(f32x16 acc, const QAHFrag& t, c
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         bf16x8 xh, xl;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            __bf16 hi, lo;
-            qah_split(x[8 * s + j], hi, lo);
-            xh[j] = hi;
-            xl[j] = lo;
-        }
-        acc = qah_mfma(t.h[s], xh, acc);
-        acc = qah_mfma(t.h[s], xl, acc);
-        acc = qah_mfma(t.l[s], xh, acc);
+        bx3_split8(x + 8 * s, xh, xl);
+        acc = bx3_mfma3<false>(t.h[s], t.l[s], xh, xl, acc);
     }
     return acc;
 }
@@ -596,18 +564,8 @@ __global__ __launch_bounds__(S360_BLOCK) void k_qah_split(QAArgs a, const float*
         for (int j = 0; j < 8; ++j) x[j] = p[(size_t)j * a.T];
     }
     bf16x8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        __bf16 h, l;
-        qah_split(x[j], h, l);
-        hi[j] = h;
-        lo[j] = l;
-    }
-    if (rh) {
-        const size_t o = (bh * lpad + s) * QA_CH + 8 * cg;
-        *reinterpret_cast<uint4*>(rh + o) = __builtin_bit_cast(uint4, hi);
-        *reinterpret_cast<uint4*>(rl + o) = __builtin_bit_cast(uint4, lo);
-    }
+    bx3_split8(x, hi, lo);
+    if (rh) bx3_st8(rh, rl, (bh * lpad + s) * QA_CH + 8 * cg, hi, lo);
     if (th) {
         const int pos = (s & ~(QA_T - 1)) + qah_tpos(s & (QA_T - 1));
 #pragma unroll
@@ -884,29 +842,22 @@ __global__ __launch_bounds__(S360_BLOCK) void k_qah_backward_kv(QAArgs a, QAHPla
 // and g (28 n bytes: 1.75 x the padded qkv and g_out).
 static size_t qah_layout(const QAArgs& a, bool backward, char* base, QAHPlanes* pl) {
     const size_t n = (size_t)a.B * a.heads * qah_pad(a.L) * QA_CH;
-    size_t off = 0;
-    auto take = [&](__bf16** hi, __bf16** lo) {
-        if (pl) {
-            *hi = reinterpret_cast<__bf16*>(base + off);
-            *lo = reinterpret_cast<__bf16*>(base + off + 2 * n);
-        }
-        off += 4 * n;
-    };
+    Bx3Carver c{base};
     QAHPlanes none = {};
     if (pl) *pl = none;
     QAHPlanes* p = pl ? pl : &none;
-    take(&p->q_rh, &p->q_rl);
-    take(&p->k_rh, &p->k_rl);
+    c.take(n, &p->q_rh, &p->q_rl);
+    c.take(n, &p->k_rh, &p->k_rl);
     if (!backward) {
-        take(&p->v_th, &p->v_tl);
-        return off;
+        c.take(n, &p->v_th, &p->v_tl);
+        return c.off;
     }
-    take(&p->v_rh, &p->v_rl);
-    take(&p->g_rh, &p->g_rl);
-    take(&p->q_th, &p->q_tl);
-    take(&p->k_th, &p->k_tl);
-    take(&p->g_th, &p->g_tl);
-    return off;
+    c.take(n, &p->v_rh, &p->v_rl);
+    c.take(n, &p->g_rh, &p->g_rl);
+    c.take(n, &p->q_th, &p->q_tl);
+    c.take(n, &p->k_th, &p->k_tl);
+    c.take(n, &p->g_th, &p->g_tl);
+    return c.off;
 }
 
 // qa_setup and what the "high" calls ask beyond it: Lpad is an int, both grids fit
@@ -938,8 +889,9 @@ extern "C" int s360_qkv_attention_high_forward(const float* qkv, int32_t rows, i
     QAArgs a;
     const int rc = qah_setup(qkv, rows, views, heads, ch, tokens, order, a);
     if (rc != S360_OK) return rc;
-    if (!out || !lse || !scratch || !s360_aligned(scratch, 16)) return S360_E_BADARG;
-    if (scratch_bytes < qah_layout(a, false, nullptr, nullptr)) return S360_E_WORKSPACE;
+    if (!out || !lse) return S360_E_BADARG;
+    const int rs = s360_scratch(scratch, scratch_bytes, qah_layout(a, false, nullptr, nullptr));
+    if (rs != S360_OK) return rs;
     QAHPlanes pl;
     qah_layout(a, false, static_cast<char*>(scratch), &pl);
     hipStream_t st = (hipStream_t)stream;
@@ -957,8 +909,9 @@ extern "C" int s360_qkv_attention_high_backward(const float* qkv, const double* 
     QAArgs a;
     const int rc = qah_setup(qkv, rows, views, heads, ch, tokens, order, a);
     if (rc != S360_OK) return rc;
-    if (!lse || !g_out || !delta || !g_qkv || g_qkv == qkv || !scratch || !s360_aligned(scratch, 16)) return S360_E_BADARG;
-    if (scratch_bytes < qah_layout(a, true, nullptr, nullptr)) return S360_E_WORKSPACE;
+    if (!lse || !g_out || !delta || !g_qkv || g_qkv == qkv) return S360_E_BADARG;
+    const int rs = s360_scratch(scratch, scratch_bytes, qah_layout(a, true, nullptr, nullptr));
+    if (rs != S360_OK) return rs;
     QAHPlanes pl;
     qah_layout(a, true, static_cast<char*>(scratch), &pl);
     hipStream_t st = (hipStream_t)stream;

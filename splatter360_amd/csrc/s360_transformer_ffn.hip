@@ -29,6 +29,7 @@
 // LayerNorm rows: float64 mean, two-pass biased variance and rstd per token, saved as (mean, rstd) pairs; the backward reads them.
 // No atomics; every sum has a fixed order: bit-identical from run to run and across streams.
 #include "s360_device.h"
+#include "s360_bf16x3.h"
 
 namespace s360 {
 
@@ -657,24 +658,21 @@ extern "C" int s360_layer_norm_residual_backward(const float* x, const float* we
 }
 
 // ---------------------------------------------------------------------------------------------- the "high" mode (bf16 x 3)
-// The same function with its two products, and the four of the backward, as bf16x3 products on v_mfma_f32_32x32x16_bf16:
-// split(x) = (hi, lo), hi = bf16(x) round-to-nearest-even, lo = bf16(x - float32(hi)); A B = Ah Bh + Ah Bl + Al Bh, both operands
-// split from their float32 values, accumulated in float32 by the MFMA over the whole k range (no float64 chain sums: the split's
-// error is far above the float32 chain's).  The LayerNorm rows, their statistics and the parameter gradients' partial sums are
-// float64 as above; h, z, dz and dpre are rounded to float32 where the kernels above round them.
+// The same function with its two products, and the four of the backward, as bf16x3 products (s360_bf16x3.h: the split, the
+// three terms and their order, the B-operand register rule), both operands split from their float32 values.  The LayerNorm
+// rows, their statistics and the parameter gradients' partial sums are float64 as above; h, z, dz and dpre are rounded to
+// float32 where the kernels above round them.
 // A pre-pass (k_ffh_split, one launch) splits W1 and W2 once per call into bf16 planes in the caller's scratch, each in the two
 // layouts its two uses need (3 MiB, whatever T): w1_r [8C][2C] for X W1^T (a lane reads 8 consecutive channels of a unit's row),
-// w1_t [2C][8C] for dpre W1 (2 x 4 consecutive units of a channel's row: the k permutation of an accumulator tile used as the
-// B operand, s360_window_attention.hip), w2_r [C][8C] for h W2^T and w2_t [8C][C] for dz W2.  The kernels read the planes from
+// w1_t [2C][8C] for dpre W1 (2 x 4 consecutive units of a channel's row: bx3_ld44, the k permutation of an accumulator tile used
+// as the B operand), w2_r [C][8C] for h W2^T and w2_t [8C][C] for dz W2.  The kernels read the planes from
 // global memory (L1 / L2: 3 MiB shared by every workgroup), so the token-owned kernels have no staging and no barrier in the walk
 // over the hidden width.  The token side is split where it is produced: X and dz in registers / the lane's own LDS slots, h and
 // dpre register by register from the accumulator tile, the weight-owned pass's X and dz tiles as they are staged in LDS (rows
 // and transposed).  No plane that grows with T exists.  Orientation, launch geometry, partials and k_ff_reduce are those above.
-// A product's three terms are issued in one order of (weight, token-side) terms — (wh, th), (wh, tl), (wl, th) — whichever side
-// is the A operand (SWAP).
+// A product's terms are in (weight, token side) order — (wh, th), (wh, tl), (wl, th) — whichever side is the A operand: SWAP =
+// false where A is the weight, true where B is.
 namespace s360 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr size_t FFH_W1 = (size_t)FF_H * FF_X, FFH_W2 = (size_t)FF_C * FF_H;
 constexpr size_t FFH_PLANE_BYTES = 2 * 2 * (FFH_W1 + FFH_W2) * sizeof(__bf16);   // two layouts x (hi, lo) of both weights
@@ -686,60 +684,11 @@ struct FFHPlanes {
     __bf16 *w1_rh, *w1_rl, *w1_th, *w1_tl, *w2_rh, *w2_rl, *w2_th, *w2_tl;
 };
 
-__device__ __forceinline__ void ffh_split(float x, __bf16& hi, __bf16& lo) {
-    hi = (__bf16)x;
-    lo = (__bf16)(x - (float)hi);
-}
-__device__ __forceinline__ void ffh_split8(const float* x, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        __bf16 h, l;
-        ffh_split(x[j], h, l);
-        hi[j] = h;
-        lo[j] = l;
-    }
-}
-
-// 8 consecutive bf16 (p 16-byte aligned)
-__device__ __forceinline__ bf16x8 ffh_ld8(const __bf16* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p)); }
-// p[0 .. 3] and p[8 .. 11] (p 8-byte aligned): the A fragment that goes with registers 8 s .. 8 s + 7 of an accumulator tile as
-// the B operand, p at tile row 16 s + 4 hf
-__device__ __forceinline__ bf16x8 ffh_ld44(const __bf16* p) {
-    const uint2 u0 = *reinterpret_cast<const uint2*>(p), u1 = *reinterpret_cast<const uint2*>(p + 8);
-    return __builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y));
-}
 // 8 consecutive floats (p 16-byte aligned), zeros unless valid
 __device__ __forceinline__ void ffh_load8(const float* p, bool valid, float* x) {
     float4 u = make_float4(0.f, 0.f, 0.f, 0.f), v = u;
     if (valid) u = *reinterpret_cast<const float4*>(p), v = *reinterpret_cast<const float4*>(p + 4);
     x[0] = u.x, x[1] = u.y, x[2] = u.z, x[3] = u.w, x[4] = v.x, x[5] = v.y, x[6] = v.z, x[7] = v.w;
-}
-
-// one k-step of 16: acc += A B in three terms.  SWAP = false: A is the weight; true: B is
-template <bool SWAP>
-__device__ __forceinline__ f32x16 ffh_mfma3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x16 acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-    if constexpr (SWAP) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-    } else {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-    }
-    return acc;
-}
-
-__device__ __forceinline__ f32x16 ffh_zero() {
-    f32x16 t;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t[r] = 0.f;
-    return t;
-}
-
-// the lane's column of a 32 x 32 accumulator tile as the B operand of the next product: two k-steps of 16, split here
-__device__ __forceinline__ void ffh_split_tile(const float* t, bf16x8* hi, bf16x8* lo) {
-    ffh_split8(t, hi[0], lo[0]);
-    ffh_split8(t + 8, hi[1], lo[1]);
 }
 
 // The pre-pass: element i of W1 (then of W2) into its four planes.
@@ -748,12 +697,12 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ffh_split(const float* __restric
     __bf16 h, l;
     if (i < FFH_W1) {
         const size_t unit = i / FF_X, c = i % FF_X;
-        ffh_split(w1[i], h, l);
+        bx3_split(w1[i], h, l);
         pl.w1_rh[i] = h, pl.w1_rl[i] = l;
         pl.w1_th[c * FF_H + unit] = h, pl.w1_tl[c * FF_H + unit] = l;
     } else if (i < FFH_W1 + FFH_W2) {
         const size_t k = i - FFH_W1, c = k / FF_H, unit = k % FF_H;
-        ffh_split(w2[k], h, l);
+        bx3_split(w2[k], h, l);
         pl.w2_rh[k] = h, pl.w2_rl[k] = l;
         pl.w2_th[unit * FF_C + c] = h, pl.w2_tl[unit * FF_C + c] = l;
     }
@@ -785,23 +734,23 @@ __device__ __forceinline__ void ffh_load_x(const FFArgs& a, int token, bool vali
     for (int s = 0; s < FF_C / 16; ++s) {
         float v[8];
         ffh_load8(a.source + row + 16 * s + 8 * hf, valid, v);
-        ffh_split8(v, xh[s], xl[s]);
+        bx3_split8(v, xh[s], xl[s]);
         ffh_load8(a.m + row + 16 * s + 8 * hf, valid, v);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int c = 16 * s + 8 * hf + j;
             v[j] = valid ? ff_norm(v[j], mean, rstd, a.n1w[c], a.n1b[c]) : 0.f;
         }
-        ffh_split8(v, xh[FF_C / 16 + s], xl[FF_C / 16 + s]);
+        bx3_split8(v, xh[FF_C / 16 + s], xl[FF_C / 16 + s]);
     }
 }
 
 // (X W1c^T)^T for the 32 units from j0: rows = hidden units, lane = token; w1h / w1l: the lane's row l31 of w1_r at channel 8 hf
 __device__ __forceinline__ f32x16 ffh_pre(const __bf16* w1h, const __bf16* w1l, int j0, const bf16x8* xh, const bf16x8* xl) {
-    f32x16 t = ffh_zero();
+    f32x16 t = bx3_zero();
 #pragma unroll
     for (int s = 0; s < FF_X / 16; ++s)
-        t = ffh_mfma3<false>(ffh_ld8(w1h + (size_t)j0 * FF_X + 16 * s), ffh_ld8(w1l + (size_t)j0 * FF_X + 16 * s), xh[s], xl[s], t);
+        t = bx3_mfma3<false>(bx3_ld8(w1h + (size_t)j0 * FF_X + 16 * s), bx3_ld8(w1l + (size_t)j0 * FF_X + 16 * s), xh[s], xl[s], t);
     return t;
 }
 
@@ -819,7 +768,7 @@ __global__ __launch_bounds__(S360_BLOCK, 2) void k_ffh_forward(FFArgs a, FFHPlan
     ffh_load_x(a, token, valid, hf, mean1, rstd1, xh, xl);
     f32x16 zt[FF_C / FF_T];
 #pragma unroll
-    for (int ct = 0; ct < FF_C / FF_T; ++ct) zt[ct] = ffh_zero();
+    for (int ct = 0; ct < FF_C / FF_T; ++ct) zt[ct] = bx3_zero();
     const __bf16* w1h = pl.w1_rh + l31 * FF_X + 8 * hf;
     const __bf16* w1l = pl.w1_rl + l31 * FF_X + 8 * hf;
     const __bf16* w2h = pl.w2_rh + l31 * FF_H + 4 * hf;
@@ -830,12 +779,12 @@ __global__ __launch_bounds__(S360_BLOCK, 2) void k_ffh_forward(FFArgs a, FFHPlan
 #pragma unroll
         for (int r = 0; r < 16; ++r) h[r] = ff_gelu(pre[r]);
         bf16x8 hh[2], hl[2];
-        ffh_split_tile(h, hh, hl);
+        bx3_split_tile(h, hh, hl);
 #pragma unroll
         for (int ct = 0; ct < FF_C / FF_T; ++ct)              // z^T += W2c h^T
 #pragma unroll
             for (int s = 0; s < 2; ++s)
-                zt[ct] = ffh_mfma3<false>(ffh_ld44(w2h + ct * FF_T * FF_H + j0 + 16 * s), ffh_ld44(w2l + ct * FF_T * FF_H + j0 + 16 * s),
+                zt[ct] = bx3_mfma3<false>(bx3_ld44(w2h + ct * FF_T * FF_H + j0 + 16 * s), bx3_ld44(w2l + ct * FF_T * FF_H + j0 + 16 * s),
                                           hh[s], hl[s], zt[ct]);
     }
     // norm2 over the float32 z, the residual, the writes: as k_ff_forward
@@ -934,31 +883,31 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ffh_backward_tokens(FFArgs a, FF
                     if (l31 == 0) s_wave[wave][2 * FF_C + c] = pw, s_wave[wave][3 * FF_C + c] = pb;
                 }
                 bf16x8 dh, dl;
-                ffh_split8(d, dh, dl);
+                bx3_split8(d, dh, dl);
                 s_dz[wave][0][s][lane] = __builtin_bit_cast(uint4, dh);
                 s_dz[wave][1][s][lane] = __builtin_bit_cast(uint4, dl);
             }
         }
         f32x16 dx[FF_X / FF_T];                            // dX^T: tile ct, register r is channel 32 ct + mfma_acc_row(r, hf) of the lane's token
 #pragma unroll
-        for (int ct = 0; ct < FF_X / FF_T; ++ct) dx[ct] = ffh_zero();
+        for (int ct = 0; ct < FF_X / FF_T; ++ct) dx[ct] = bx3_zero();
         for (int j0 = 0; j0 < FF_H; j0 += FF_T) {
             const f32x16 pre = ffh_pre(w1h, w1l, j0, xh, xl);                   // X W1c^T again
-            f32x16 dh = ffh_zero();                                             // (dz W2c)^T
+            f32x16 dh = bx3_zero();                                             // (dz W2c)^T
 #pragma unroll
             for (int s = 0; s < FF_C / 16; ++s)
-                dh = ffh_mfma3<false>(ffh_ld8(w2th + (size_t)j0 * FF_C + 16 * s), ffh_ld8(w2tl + (size_t)j0 * FF_C + 16 * s),
+                dh = bx3_mfma3<false>(bx3_ld8(w2th + (size_t)j0 * FF_C + 16 * s), bx3_ld8(w2tl + (size_t)j0 * FF_C + 16 * s),
                                       __builtin_bit_cast(bf16x8, s_dz[wave][0][s][lane]), __builtin_bit_cast(bf16x8, s_dz[wave][1][s][lane]), dh);
             float dp[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) dp[r] = dh[r] * ff_gelu_grad(pre[r]);
             bf16x8 ph[2], pw[2];
-            ffh_split_tile(dp, ph, pw);
+            bx3_split_tile(dp, ph, pw);
 #pragma unroll
             for (int ct = 0; ct < FF_X / FF_T; ++ct)          // dX^T += W1c^T dpre^T
 #pragma unroll
                 for (int s = 0; s < 2; ++s)
-                    dx[ct] = ffh_mfma3<false>(ffh_ld44(w1th + ct * FF_T * FF_H + j0 + 16 * s), ffh_ld44(w1tl + ct * FF_T * FF_H + j0 + 16 * s),
+                    dx[ct] = bx3_mfma3<false>(bx3_ld44(w1th + ct * FF_T * FF_H + j0 + 16 * s), bx3_ld44(w1tl + ct * FF_T * FF_H + j0 + 16 * s),
                                               ph[s], pw[s], dx[ct]);
         }
         // g_source = g_out + dX[:, :C]
@@ -1030,9 +979,9 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ffh_backward_weights(FFArgs a, F
     const __bf16* w2tl = pl.w2_tl + (size_t)(j0 + l31) * FF_C + 8 * hf;
     f32x16 gw1[FF_X / FF_T], gw2[FF_C / FF_T];             // g_W1^T, g_W2: rows = channels, lane = hidden unit
 #pragma unroll
-    for (int ct = 0; ct < FF_X / FF_T; ++ct) gw1[ct] = ffh_zero();
+    for (int ct = 0; ct < FF_X / FF_T; ++ct) gw1[ct] = bx3_zero();
 #pragma unroll
-    for (int ct = 0; ct < FF_C / FF_T; ++ct) gw2[ct] = ffh_zero();
+    for (int ct = 0; ct < FF_C / FF_T; ++ct) gw2[ct] = bx3_zero();
     const int slot = tid >> 5, l = tid & 31;
     const float4 n1w = *reinterpret_cast<const float4*>(a.n1w + 4 * l), n1b = *reinterpret_cast<const float4*>(a.n1b + 4 * l);
     const float4 n2w = *reinterpret_cast<const float4*>(a.n2w + 4 * l);
@@ -1055,7 +1004,7 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ffh_backward_weights(FFArgs a, F
             for (int i = 0; i < 8; ++i) {
                 const int c = (i < 4 ? 0 : FF_C - 4) + 4 * l + i;
                 __bf16 h, lo;
-                ffh_split(xs[i], h, lo);
+                bx3_split(xs[i], h, lo);
                 s_xr[0][tl * FFH_LDR + c] = h, s_xr[1][tl * FFH_LDR + c] = lo;
                 s_xt[0][c * FFH_LDT + tl] = h, s_xt[1][c * FFH_LDT + tl] = lo;
             }
@@ -1063,21 +1012,21 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ffh_backward_weights(FFArgs a, F
             for (int i = 0; i < 4; ++i) {
                 const int c = 4 * l + i;
                 __bf16 h, lo;
-                ffh_split(ds[i], h, lo);
+                bx3_split(ds[i], h, lo);
                 s_dr[0][tl * FFH_LDD + c] = h, s_dr[1][tl * FFH_LDD + c] = lo;
                 s_dt[0][c * FFH_LDT + tl] = h, s_dt[1][c * FFH_LDT + tl] = lo;
             }
         }
         __syncthreads();
-        f32x16 pre = ffh_zero(), dh = ffh_zero();             // X W1c^T, dz W2c: rows = tokens, lane = hidden unit
+        f32x16 pre = bx3_zero(), dh = bx3_zero();             // X W1c^T, dz W2c: rows = tokens, lane = hidden unit
 #pragma unroll
         for (int s = 0; s < FF_X / 16; ++s)
-            pre = ffh_mfma3<true>(ffh_ld8(s_xr[0] + l31 * FFH_LDR + 16 * s + 8 * hf), ffh_ld8(s_xr[1] + l31 * FFH_LDR + 16 * s + 8 * hf),
-                                  ffh_ld8(w1h + 16 * s), ffh_ld8(w1l + 16 * s), pre);
+            pre = bx3_mfma3<true>(bx3_ld8(s_xr[0] + l31 * FFH_LDR + 16 * s + 8 * hf), bx3_ld8(s_xr[1] + l31 * FFH_LDR + 16 * s + 8 * hf),
+                                  bx3_ld8(w1h + 16 * s), bx3_ld8(w1l + 16 * s), pre);
 #pragma unroll
         for (int s = 0; s < FF_C / 16; ++s)
-            dh = ffh_mfma3<true>(ffh_ld8(s_dr[0] + l31 * FFH_LDD + 16 * s + 8 * hf), ffh_ld8(s_dr[1] + l31 * FFH_LDD + 16 * s + 8 * hf),
-                                 ffh_ld8(w2th + 16 * s), ffh_ld8(w2tl + 16 * s), dh);
+            dh = bx3_mfma3<true>(bx3_ld8(s_dr[0] + l31 * FFH_LDD + 16 * s + 8 * hf), bx3_ld8(s_dr[1] + l31 * FFH_LDD + 16 * s + 8 * hf),
+                                 bx3_ld8(w2th + 16 * s), bx3_ld8(w2tl + 16 * s), dh);
         float dp[16], h[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -1085,20 +1034,20 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ffh_backward_weights(FFArgs a, F
             h[r] = ff_gelu(pre[r]);
         }
         bf16x8 ph[2], pw[2], hh[2], hl[2];
-        ffh_split_tile(dp, ph, pw);
-        ffh_split_tile(h, hh, hl);
+        bx3_split_tile(dp, ph, pw);
+        bx3_split_tile(h, hh, hl);
 #pragma unroll
         for (int ct = 0; ct < FF_X / FF_T; ++ct)              // g_W1^T += X^T dpre
 #pragma unroll
             for (int s = 0; s < 2; ++s)
-                gw1[ct] = ffh_mfma3<true>(ffh_ld44(s_xt[0] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf),
-                                          ffh_ld44(s_xt[1] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf), ph[s], pw[s], gw1[ct]);
+                gw1[ct] = bx3_mfma3<true>(bx3_ld44(s_xt[0] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf),
+                                          bx3_ld44(s_xt[1] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf), ph[s], pw[s], gw1[ct]);
 #pragma unroll
         for (int ct = 0; ct < FF_C / FF_T; ++ct)              // g_W2 += dz^T h
 #pragma unroll
             for (int s = 0; s < 2; ++s)
-                gw2[ct] = ffh_mfma3<true>(ffh_ld44(s_dt[0] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf),
-                                          ffh_ld44(s_dt[1] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf), hh[s], hl[s], gw2[ct]);
+                gw2[ct] = bx3_mfma3<true>(bx3_ld44(s_dt[0] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf),
+                                          bx3_ld44(s_dt[1] + (ct * FF_T + l31) * FFH_LDT + 16 * s + 4 * hf), hh[s], hl[s], gw2[ct]);
     }
     float* q1 = p_w1 + ((size_t)chunk * FF_H + j0 + l31) * FF_X;
     float* q2 = p_w2 + (size_t)chunk * FF_C * FF_H + j0 + l31;
@@ -1113,11 +1062,12 @@ __global__ __launch_bounds__(S360_BLOCK) void k_ffh_backward_weights(FFArgs a, F
 
 // the planes in the first FFH_PLANE_BYTES of a scratch, and the pre-pass
 static FFHPlanes ffh_planes(void* scratch) {
-    __bf16* p = static_cast<__bf16*>(scratch);
+    Bx3Carver c{static_cast<char*>(scratch)};
     FFHPlanes pl;
-    pl.w1_rh = p, pl.w1_rl = p + FFH_W1, pl.w1_th = p + 2 * FFH_W1, pl.w1_tl = p + 3 * FFH_W1;
-    p += 4 * FFH_W1;
-    pl.w2_rh = p, pl.w2_rl = p + FFH_W2, pl.w2_th = p + 2 * FFH_W2, pl.w2_tl = p + 3 * FFH_W2;
+    c.take(FFH_W1, &pl.w1_rh, &pl.w1_rl);
+    c.take(FFH_W1, &pl.w1_th, &pl.w1_tl);
+    c.take(FFH_W2, &pl.w2_rh, &pl.w2_rl);
+    c.take(FFH_W2, &pl.w2_th, &pl.w2_tl);
     return pl;
 }
 static void ffh_split_launch(const float* w1, const float* w2, const FFHPlanes& pl, hipStream_t st) {
@@ -1139,10 +1089,11 @@ extern "C" int s360_ffn_tail_high_forward(const float* source, const float* m, c
     for (const void* p : in)
         if (!p || !s360_aligned(p, 16) || p == out || p == z || p == stats || p == scratch) return S360_E_BADARG;
     if (!eps || !(*eps > 0.0) || !out || !z || !stats || out == z || !s360_aligned(out, 16) || !s360_aligned(z, 16)) return S360_E_BADARG;
-    if (!scratch || !s360_aligned(scratch, 16) || scratch == out || scratch == z || scratch == stats) return S360_E_BADARG;
+    const int rs = s360_scratch(scratch, scratch_bytes, s360_ffn_tail_high_scratch_bytes(tokens, 0));
+    if (rs == S360_E_BADARG || scratch == out || scratch == z || scratch == stats) return S360_E_BADARG;
     const int rc = ff_sizes(tokens, channels, hidden);
     if (rc != S360_OK) return rc;
-    if (scratch_bytes < s360_ffn_tail_high_scratch_bytes(tokens, 0)) return S360_E_WORKSPACE;
+    if (rs != S360_OK) return rs;                             // short: after the sizes, as the size depends on them
     const FFArgs a = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, tokens, *eps};
     const FFHPlanes pl = ffh_planes(scratch);
     ffh_split_launch(w1, w2, pl, (hipStream_t)stream);
@@ -1172,7 +1123,8 @@ extern "C" int s360_ffn_tail_high_backward(const float* source, const float* m, 
     if (!eps || !(*eps > 0.0)) return S360_E_BADARG;
     const int rc = ff_sizes(tokens, channels, hidden);
     if (rc != S360_OK) return rc;
-    if (scratch_bytes < s360_ffn_tail_high_scratch_bytes(tokens, 1)) return S360_E_WORKSPACE;
+    const int rs = s360_scratch(scratch, scratch_bytes, s360_ffn_tail_high_scratch_bytes(tokens, 1));     // scratch is one of outs: not null, aligned
+    if (rs != S360_OK) return rs;
     const FFArgs a = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, tokens, *eps};
     hipStream_t st = (hipStream_t)stream;
     const int chunks = ff_chunks(tokens), wgs = ff_token_wgs(tokens);

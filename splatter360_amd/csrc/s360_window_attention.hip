@@ -28,6 +28,9 @@
 // No atomics: each output row is written by one wave.  Backward: P = exp(score - lse) recomputed (float64 difference, float32
 // exp), dS = P (dP - Delta), Delta = sum_k P dP (float64 sum) from a first sweep of the query-owned pass.
 #include "s360_device.h"
+#include "s360_bf16x3.h"
+
+#include <type_traits>
 
 namespace s360 {
 
@@ -497,6 +500,18 @@ static void wa_launch_kv(const WAArgs& a, const double* lse, const double* delta
     else hipLaunchKernelGGL((k_wa_backward_kv<NCB, false, true>), grid, block, 0, st, a, lse, delta, g_out, g_k, g_v);
 }
 
+// f(std::integral_constant<int, NCB>()) with NCB = channels / 32 channel blocks (1 .. 4: wa_setup has checked the channels):
+// the one place where a call's channel count becomes the kernels' template argument, in both modes
+template <typename F>
+static void wa_with_ncb(int channels, F f) {
+    switch (channels / 32) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        default: f(std::integral_constant<int, 4>()); break;
+    }
+}
+
 }  // namespace s360
 
 using namespace s360;
@@ -510,12 +525,7 @@ extern "C" int s360_window_attention_forward(const float* q, const float* k, con
     if (!out || !lse || !s360_aligned(out, 16)) return S360_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
-    switch (channels / 32) {
-        case 1: hipLaunchKernelGGL((k_wa_forward<1>), grid, block, 0, st, a, out, lse); break;
-        case 2: hipLaunchKernelGGL((k_wa_forward<2>), grid, block, 0, st, a, out, lse); break;
-        case 3: hipLaunchKernelGGL((k_wa_forward<3>), grid, block, 0, st, a, out, lse); break;
-        default: hipLaunchKernelGGL((k_wa_forward<4>), grid, block, 0, st, a, out, lse); break;
-    }
+    wa_with_ncb(channels, [&](auto ncb) { hipLaunchKernelGGL((k_wa_forward<decltype(ncb)::value>), grid, block, 0, st, a, out, lse); });
     return s360_launch_status();
 }
 
@@ -538,45 +548,31 @@ extern "C" int s360_window_attention_backward(const float* q, const float* k, co
     if (!g_q && !g_k && !g_v) return S360_OK;
     hipStream_t st = (hipStream_t)stream;
     if (g_q || g_k) {                                         // the query-owned pass first: it writes Delta for the key-owned one
-        switch (channels / 32) {
-            case 1: wa_launch_q<1>(a, lse, g_out, delta, g_q, st); break;
-            case 2: wa_launch_q<2>(a, lse, g_out, delta, g_q, st); break;
-            case 3: wa_launch_q<3>(a, lse, g_out, delta, g_q, st); break;
-            default: wa_launch_q<4>(a, lse, g_out, delta, g_q, st); break;
-        }
+        wa_with_ncb(channels, [&](auto ncb) { wa_launch_q<decltype(ncb)::value>(a, lse, g_out, delta, g_q, st); });
         S360_CHECK_LAUNCH();
     }
     if (g_k || g_v) {
-        switch (channels / 32) {
-            case 1: wa_launch_kv<1>(a, lse, delta, g_out, g_k, g_v, st); break;
-            case 2: wa_launch_kv<2>(a, lse, delta, g_out, g_k, g_v, st); break;
-            case 3: wa_launch_kv<3>(a, lse, delta, g_out, g_k, g_v, st); break;
-            default: wa_launch_kv<4>(a, lse, delta, g_out, g_k, g_v, st); break;
-        }
+        wa_with_ncb(channels, [&](auto ncb) { wa_launch_kv<decltype(ncb)::value>(a, lse, delta, g_out, g_k, g_v, st); });
         S360_CHECK_LAUNCH();
     }
     return S360_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- the "high" mode (bf16 x 3)
-// The same function with every product as a bf16x3 product on v_mfma_f32_32x32x16_bf16: split(x) = (hi, lo), hi = bf16(x)
-// round-to-nearest-even, lo = bf16(x - float32(hi)); A B = Ah Bh + Ah Bl + Al Bh, accumulated in float32 by the MFMA over all
-// channels (no float64 chunk sums: the split's error is far above the float32 chain's).  Roll, split and merge, the mask, the
-// scaling, the softmax with its running maximum, lse and Delta are those of the kernels above, and so is the orientation: the
-// walked index on the accumulator's rows, the owner on the lanes, so the P or dS tile is the B operand of the second product
-// register by register (registers 8 s .. 8 s + 7 are k-step s; element j of lane half h is tile row 16 s + 8 (j / 4) + 4 h + j % 4,
-// and the A operand's elements are read in that order).
+// The same function with every product as a bf16x3 product (s360_bf16x3.h: the split, the three terms and their order, the
+// B-operand register rule), accumulated by the MFMA over all channels.  Roll, split and merge, the mask, the scaling, the
+// softmax with its running maximum, lse and Delta are those of the kernels above, and so is the orientation: the walked index
+// on the accumulator's rows, the owner on the lanes, so the P or dS tile is the B operand of the second product register by
+// register.
 // A pre-pass (k_wah_split, one launch per operand) splits once per call and writes bf16 planes IN WINDOW ORDER into the caller's
 // scratch: "rows" [B K^2 rows, C] for the first products (a lane reads 8 consecutive channels of its row, 16 bytes), and
 // "transposed" [B K^2, C, pad4(rows)] for the second products (a lane reads 2 x 4 consecutive walked indices of its channel;
 // rows are padded to a multiple of 4 with zeros so that these 8-byte reads are aligned and a group is inside or outside).
 // The loops then have no gathered addressing and no split of an input.  Output channel of accumulator block cb, row r is
 // 32 cb + r: registers 4 g .. 4 g + 3 of a lane are channels 32 cb + 8 g + 4 hf + (0 .. 3), one 16-byte store.
-// The three terms of a score are issued in one order of (q, k) terms — (qh, kh), (ql, kh), (qh, kl) — whichever side is walked
-// (SWAP), and dP likewise in (g, v), so the backward's recomputed tiles are the forward's bit for bit.
+// The terms of a score are in (q, k) order — (qh, kh), (ql, kh), (qh, kl) — and those of dP in (g, v) order, whichever side is
+// walked, so the backward's recomputed tiles are the forward's bit for bit.
 namespace s360 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct WAHPlanes {                                            // hi and lo planes of the operands; null where a call has none
     __bf16 *q_rh, *q_rl, *q_th, *q_tl;
@@ -587,68 +583,26 @@ struct WAHPlanes {                                            // hi and lo plane
 
 __host__ __device__ __forceinline__ int wah_pad4(int n) { return (n + 3) & ~3; }
 
-__device__ __forceinline__ void wah_split(float x, __bf16& hi, __bf16& lo) {
-    hi = (__bf16)x;
-    lo = (__bf16)(x - (float)hi);
-}
+// the lane's 8 channels of k-step s of a row (p: the row at channel 8 hf; null: zeros)
+__device__ __forceinline__ bf16x8 wah_frag(const __bf16* p, int s) { return bx3_ld8_or_zero(p ? p + 16 * s : nullptr); }
 
-// 8 consecutive bf16 (p 16-byte aligned), or zeros for p == null
-__device__ __forceinline__ bf16x8 wah_ld8(const __bf16* p) {
-    uint4 u = make_uint4(0u, 0u, 0u, 0u);
-    if (p) u = *reinterpret_cast<const uint4*>(p);
-    return __builtin_bit_cast(bf16x8, u);
-}
-
-// the A fragment of one k-step of a second product: walked indices g .. g + 3 and g + 8 .. g + 11 of one channel row of a
-// transposed plane (g a multiple of 4), zeros from lpad on
-__device__ __forceinline__ bf16x8 wah_ld44(const __bf16* row, int g, int lpad) {
-    uint2 u0 = make_uint2(0u, 0u), u1 = make_uint2(0u, 0u);
-    if (g < lpad) u0 = *reinterpret_cast<const uint2*>(row + g);
-    if (g + 8 < lpad) u1 = *reinterpret_cast<const uint2*>(row + g + 8);
-    return __builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y));
-}
-
-__device__ __forceinline__ f32x16 wah_mfma(bf16x8 x, bf16x8 y, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, c, 0, 0, 0);
-}
-
-// one k-step of a first product: walked fragments (wh, wl) as A, owner fragments (oh, ol) as B
-template <bool SWAP>
-__device__ __forceinline__ f32x16 wah_step(bf16x8 wh, bf16x8 wl, bf16x8 oh, bf16x8 ol, f32x16 acc) {
-    acc = wah_mfma(wh, oh, acc);
-    if constexpr (SWAP) {
-        acc = wah_mfma(wl, oh, acc);
-        acc = wah_mfma(wh, ol, acc);
-    } else {
-        acc = wah_mfma(wh, ol, acc);
-        acc = wah_mfma(wl, oh, acc);
-    }
-    return acc;
-}
-
-// tile = sum over all C channels of walked row x owner row, NS = C / 16 k-steps; the pointers are the lane's row at channel
-// 8 hf (null: zeros).  wah_dot: the owner's fragments are held in registers (the forward); wah_dot_mem: read per step (the
-// backward passes, whose two owners and two or more output tiles would not fit beside them; the reads stay in cache).
+// tile = sum over all C channels of walked row x owner row, NS = C / 16 k-steps, the walked fragments as A, the owner's as B;
+// the pointers are the lane's row at channel 8 hf (null: zeros).  wah_dot: the owner's fragments are held in registers (the
+// forward); wah_dot_mem: read per step (the backward passes, whose two owners and two or more output tiles would not fit
+// beside them; the reads stay in cache).
 template <int NS, bool SWAP>
 __device__ __forceinline__ f32x16 wah_dot(const __bf16* wh, const __bf16* wl, const bf16x8* oh, const bf16x8* ol) {
-    f32x16 acc;
+    f32x16 acc = bx3_zero();
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-        acc = wah_step<SWAP>(wah_ld8(wh ? wh + 16 * s : nullptr), wah_ld8(wl ? wl + 16 * s : nullptr), oh[s], ol[s], acc);
+    for (int s = 0; s < NS; ++s) acc = bx3_mfma3<SWAP>(wah_frag(wh, s), wah_frag(wl, s), oh[s], ol[s], acc);
     return acc;
 }
 
 template <int NS, bool SWAP>
 __device__ __forceinline__ f32x16 wah_dot_mem(const __bf16* wh, const __bf16* wl, const __bf16* oh, const __bf16* ol) {
-    f32x16 acc;
+    f32x16 acc = bx3_zero();
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-        acc = wah_step<SWAP>(wah_ld8(wh ? wh + 16 * s : nullptr), wah_ld8(wl ? wl + 16 * s : nullptr),
-                             wah_ld8(oh ? oh + 16 * s : nullptr), wah_ld8(ol ? ol + 16 * s : nullptr), acc);
+    for (int s = 0; s < NS; ++s) acc = bx3_mfma3<SWAP>(wah_frag(wh, s), wah_frag(wl, s), wah_frag(oh, s), wah_frag(ol, s), acc);
     return acc;
 }
 
@@ -658,24 +612,18 @@ __device__ __forceinline__ f32x16 wah_dot_mem(const __bf16* wh, const __bf16* wl
 template <int NCB>
 __device__ __forceinline__ void wah_accumulate(f32x16* acc, const __bf16* th, const __bf16* tl, int first, int lpad, const float* x) {
     bf16x8 xh[2], xl[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            __bf16 hi, lo;
-            wah_split(x[8 * s + j], hi, lo);
-            xh[s][j] = hi;
-            xl[s][j] = lo;
-        }
+    bx3_split_tile(x, xh, xl);
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const size_t off = (size_t)cb * 32 * lpad;
-            const bf16x8 ah = wah_ld44(th + off, first + 16 * s, lpad), al = wah_ld44(tl + off, first + 16 * s, lpad);
-            acc[cb] = wah_mfma(ah, xh[s], acc[cb]);
-            acc[cb] = wah_mfma(ah, xl[s], acc[cb]);
-            acc[cb] = wah_mfma(al, xh[s], acc[cb]);
+            const bf16x8 ah = bx3_ld44(th + off, first + 16 * s, lpad), al = bx3_ld44(tl + off, first + 16 * s, lpad);
+            // bx3_mfma3<false>(ah, al, xh[s], xl[s], acc[cb]), written out: behind any function boundary the register
+            // allocation of k_wah_forward<1> exchanges two VGPRs (nothing else moves), and its code is held as it was
+            acc[cb] = bx3_mfma(ah, xh[s], acc[cb]);
+            acc[cb] = bx3_mfma(ah, xl[s], acc[cb]);
+            acc[cb] = bx3_mfma(al, xh[s], acc[cb]);
         }
 }
 
@@ -716,18 +664,8 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wah_split(WAArgs a, const float*
         wa_load<2>(src + (size_t)row * a.C + 8 * cg, x);
     }
     bf16x8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        __bf16 h, l;
-        wah_split(x[j], h, l);
-        hi[j] = h;
-        lo[j] = l;
-    }
-    if (rh && p < rows) {
-        const size_t o = (win * rows + p) * a.C + 8 * cg;
-        *reinterpret_cast<uint4*>(rh + o) = __builtin_bit_cast(uint4, hi);
-        *reinterpret_cast<uint4*>(rl + o) = __builtin_bit_cast(uint4, lo);
-    }
+    bx3_split8(x, hi, lo);
+    if (rh && p < rows) bx3_st8(rh, rl, (win * rows + p) * a.C + 8 * cg, hi, lo);
     if (th) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -756,8 +694,8 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wah_forward(WAArgs a, WAHPlanes 
         const size_t o = (win * a.Lw + qp) * a.C + 8 * hf;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            qh[s] = wah_ld8(qvalid ? pl.q_rh + o + 16 * s : nullptr);
-            ql[s] = wah_ld8(qvalid ? pl.q_rl + o + 16 * s : nullptr);
+            qh[s] = bx3_ld8_or_zero(qvalid ? pl.q_rh + o + 16 * s : nullptr);
+            ql[s] = bx3_ld8_or_zero(qvalid ? pl.q_rl + o + 16 * s : nullptr);
         }
     }
     const int lkpad = wah_pad4(a.Lk);
@@ -964,29 +902,22 @@ static size_t wah_layout(const WAArgs& a, bool backward, char* base, WAHPlanes* 
     const size_t nwin = (size_t)a.B * a.K * a.K;
     const size_t nq = nwin * a.Lw * a.C, nk = nwin * a.Lk * a.C;
     const size_t tq = nwin * a.C * wah_pad4(a.Lw), tk = nwin * a.C * wah_pad4(a.Lk);
-    size_t off = 0;
-    auto take = [&](size_t n, __bf16** hi, __bf16** lo) {
-        if (pl) {
-            *hi = reinterpret_cast<__bf16*>(base + off);
-            *lo = reinterpret_cast<__bf16*>(base + off + 2 * n);
-        }
-        off += 4 * n;
-    };
+    Bx3Carver c{base};
     WAHPlanes none = {};
     if (pl) *pl = none;
     WAHPlanes* p = pl ? pl : &none;
-    take(nq, &p->q_rh, &p->q_rl);
-    take(nk, &p->k_rh, &p->k_rl);
+    c.take(nq, &p->q_rh, &p->q_rl);
+    c.take(nk, &p->k_rh, &p->k_rl);
     if (!backward) {
-        take(tk, &p->v_th, &p->v_tl);
-        return off;
+        c.take(tk, &p->v_th, &p->v_tl);
+        return c.off;
     }
-    take(nk, &p->v_rh, &p->v_rl);
-    take(nq, &p->g_rh, &p->g_rl);
-    take(tq, &p->q_th, &p->q_tl);
-    take(tk, &p->k_th, &p->k_tl);
-    take(tq, &p->g_th, &p->g_tl);
-    return off;
+    c.take(nk, &p->v_rh, &p->v_rl);
+    c.take(nq, &p->g_rh, &p->g_rl);
+    c.take(tq, &p->q_th, &p->q_tl);
+    c.take(tk, &p->k_th, &p->k_tl);
+    c.take(tq, &p->g_th, &p->g_tl);
+    return c.off;
 }
 
 // launches k_wah_split for one operand; false if the grid does not fit
@@ -1035,8 +966,9 @@ extern "C" int s360_window_attention_high_forward(const float* q, const float* k
     WAArgs a;
     const int rc = wa_setup(q, k, v, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, a);
     if (rc != S360_OK) return rc;
-    if (!out || !lse || !s360_aligned(out, 16) || !scratch || !s360_aligned(scratch, 16) || !wah_split_fits(a)) return S360_E_BADARG;
-    if (scratch_bytes < wah_layout(a, false, nullptr, nullptr)) return S360_E_WORKSPACE;
+    if (!out || !lse || !s360_aligned(out, 16) || !wah_split_fits(a)) return S360_E_BADARG;
+    const int rs = s360_scratch(scratch, scratch_bytes, wah_layout(a, false, nullptr, nullptr));
+    if (rs != S360_OK) return rs;
     WAHPlanes pl;
     wah_layout(a, false, static_cast<char*>(scratch), &pl);
     hipStream_t st = (hipStream_t)stream;
@@ -1045,12 +977,7 @@ extern "C" int s360_window_attention_high_forward(const float* q, const float* k
     wah_split_launch(a, v, 1, nullptr, nullptr, pl.v_th, pl.v_tl, st);
     S360_CHECK_LAUNCH();
     const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
-    switch (channels / 32) {
-        case 1: hipLaunchKernelGGL((k_wah_forward<1>), grid, block, 0, st, a, pl, out, lse); break;
-        case 2: hipLaunchKernelGGL((k_wah_forward<2>), grid, block, 0, st, a, pl, out, lse); break;
-        case 3: hipLaunchKernelGGL((k_wah_forward<3>), grid, block, 0, st, a, pl, out, lse); break;
-        default: hipLaunchKernelGGL((k_wah_forward<4>), grid, block, 0, st, a, pl, out, lse); break;
-    }
+    wa_with_ncb(channels, [&](auto ncb) { hipLaunchKernelGGL((k_wah_forward<decltype(ncb)::value>), grid, block, 0, st, a, pl, out, lse); });
     return s360_launch_status();
 }
 
@@ -1064,8 +991,9 @@ extern "C" int s360_window_attention_high_backward(const float* q, const float* 
     if (rc != S360_OK) return rc;
     if (!lse || !g_out || !delta || !s360_aligned(g_out, 16)) return S360_E_BADARG;
     if ((g_q && !s360_aligned(g_q, 16)) || (g_k && !s360_aligned(g_k, 16)) || (g_v && !s360_aligned(g_v, 16))) return S360_E_BADARG;
-    if (!scratch || !s360_aligned(scratch, 16) || !wah_split_fits(a)) return S360_E_BADARG;
-    if (scratch_bytes < wah_layout(a, true, nullptr, nullptr)) return S360_E_WORKSPACE;
+    if (!wah_split_fits(a)) return S360_E_BADARG;
+    const int rs = s360_scratch(scratch, scratch_bytes, wah_layout(a, true, nullptr, nullptr));
+    if (rs != S360_OK) return rs;
     if (!g_q && !g_k && !g_v) return S360_OK;
     WAHPlanes pl;
     wah_layout(a, true, static_cast<char*>(scratch), &pl);
@@ -1076,21 +1004,11 @@ extern "C" int s360_window_attention_high_backward(const float* q, const float* 
     wah_split_launch(a, g_out, 0, pl.g_rh, pl.g_rl, pl.g_th, pl.g_tl, st);
     S360_CHECK_LAUNCH();
     if (g_q || g_k) {                                         // the query-owned pass first: it writes Delta for the key-owned one
-        switch (channels / 32) {
-            case 1: wah_launch_q<1>(a, pl, lse, delta, g_q, st); break;
-            case 2: wah_launch_q<2>(a, pl, lse, delta, g_q, st); break;
-            case 3: wah_launch_q<3>(a, pl, lse, delta, g_q, st); break;
-            default: wah_launch_q<4>(a, pl, lse, delta, g_q, st); break;
-        }
+        wa_with_ncb(channels, [&](auto ncb) { wah_launch_q<decltype(ncb)::value>(a, pl, lse, delta, g_q, st); });
         S360_CHECK_LAUNCH();
     }
     if (g_k || g_v) {
-        switch (channels / 32) {
-            case 1: wah_launch_kv<1>(a, pl, lse, delta, g_k, g_v, st); break;
-            case 2: wah_launch_kv<2>(a, pl, lse, delta, g_k, g_v, st); break;
-            case 3: wah_launch_kv<3>(a, pl, lse, delta, g_k, g_v, st); break;
-            default: wah_launch_kv<4>(a, pl, lse, delta, g_k, g_v, st); break;
-        }
+        wa_with_ncb(channels, [&](auto ncb) { wah_launch_kv<decltype(ncb)::value>(a, pl, lse, delta, g_k, g_v, st); });
         S360_CHECK_LAUNCH();
     }
     return S360_OK;

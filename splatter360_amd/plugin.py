@@ -64,6 +64,8 @@ from typing import Optional
 
 import torch
 
+from . import precision as _precision
+
 REGISTRY_MODULE = "src.model.decoder"
 REGISTRY_KEY = "splatting_cuda"
 ADAPTER_MODULE = "src.model.encoder.common.gaussian_adapter_erp"      # defines GaussianAdapterERP (:33-119)
@@ -721,28 +723,19 @@ def _dense_mask(attn_mask):
     return attn_mask.dense() if isinstance(attn_mask, _wa.ShiftMask) else attn_mask
 
 
-def _window_attention_precision(precision) -> str:
-    """The `precision` option of the window-attention seam, checked when the seam is installed: "highest", "high", or "torch"
-    (window_attention.resolve_precision reads torch's float32 matmul precision at every call)."""
-    from . import window_attention as _wa
-    if precision != "torch" and precision not in _wa.PRECISIONS:
-        raise ValueError(f"window_attention_precision is one of {[*_wa.PRECISIONS, 'torch']}, got {precision!r}")
-    return precision
-
-
 def _native_split_window_attention(replaced, mod=None, precision="highest"):
     """single_head_split_window_attention with the reference's signature: the fused kernels for float32 GPU q, k, v of agreeing
     shapes and a supported C — with_shift only with the ShiftMask handle of this grid and split (or without a mask argument the
     reference would refuse anyway); the replaced function otherwise, with a handle made dense first.  precision: the seam's
     option, "torch" resolved per call."""
     from . import window_attention as _wa
-    _window_attention_precision(precision)
+    _precision.seam_option("window_attention_precision", precision)
 
     def single_head_split_window_attention(q, k, v, num_splits=1, with_shift=False, h=None, w=None, attn_mask=None):
         if _window_attention_call(q, k, v, h, w, num_splits) and (
                 not with_shift or (isinstance(attn_mask, _wa.ShiftMask) and attn_mask.matches(h, w, num_splits))):
             return _wa.window_attention(q, k, v, height=h, width=w, num_splits=num_splits, with_shift=bool(with_shift),
-                                        precision=_wa.resolve_precision(precision))
+                                        precision=_precision.resolve(precision))
         return replaced(q, k, v, num_splits=num_splits, with_shift=with_shift, h=h, w=w, attn_mask=_dense_mask(attn_mask))
 
     single_head_split_window_attention.replaced = replaced
@@ -755,12 +748,12 @@ def _native_full_attention(replaced, mod=None, precision="highest"):
     """single_head_full_attention with the reference's signature: the fused kernels (one window, no shift) for float32 GPU
     q, k, v [B, L, C] of one shape and a supported C; the replaced function otherwise.  precision: as above."""
     from . import window_attention as _wa
-    _window_attention_precision(precision)
+    _precision.seam_option("window_attention_precision", precision)
 
     def single_head_full_attention(q, k, v):
         if (all(_is_cuda_f32(t) for t in (q, k, v)) and q.dim() == 3 and tuple(q.shape) == tuple(k.shape)
                 and _window_attention_call(q, k, v, 1, int(q.shape[1]), 1)):
-            return _wa.full_attention(q, k, v, precision=_wa.resolve_precision(precision))
+            return _wa.full_attention(q, k, v, precision=_precision.resolve(precision))
         return replaced(q, k, v)
 
     single_head_full_attention.replaced = replaced
@@ -945,15 +938,6 @@ def _unet_attention_call(qkv, n_heads, views) -> bool:
     return width % (3 * n_heads) == 0 and _qa.supported_head_channels(width // (3 * n_heads)) and qkv.shape[0] % views == 0
 
 
-def _unet_attention_precision(precision) -> str:
-    """The `precision` option of the U-Net attention seam, checked when the seam is installed: "highest", "high", or "torch"
-    (window_attention.resolve_precision reads torch's float32 matmul precision at every call)."""
-    from . import qkv_attention as _qa
-    if precision != "torch" and precision not in _qa.PRECISIONS:
-        raise ValueError(f"unet_attention_precision is one of {[*_qa.PRECISIONS, 'torch']}, got {precision!r}")
-    return precision
-
-
 def _native_qkv_attention_forward(order):
     """QKVAttentionLegacy.forward (order "legacy": n_heads, n_frames, use_cross_view_self_attn of the module) or
     QKVAttention.forward (order "new": n_heads) with the reference's signature: the fused kernels of qkv_attention.py for the calls
@@ -962,8 +946,7 @@ def _native_qkv_attention_forward(order):
     call — the recomputation under the reference's checkpoint included; `forward.precision` holds it."""
     def wrapper(replaced, mod=None, precision="highest"):
         from . import qkv_attention as _qa
-        from . import window_attention as _wa
-        _unet_attention_precision(precision)
+        _precision.seam_option("unet_attention_precision", precision)
 
         def forward(self, qkv):
             heads = getattr(self, "n_heads", None)
@@ -972,7 +955,7 @@ def _native_qkv_attention_forward(order):
             if _unet_attention_call(qkv, heads, frames):
                 forward.native_calls += 1
                 return _qa.qkv_attention(qkv, heads, n_frames=frames, cross_view=cross, order=order,
-                                         precision=_wa.resolve_precision(precision))
+                                         precision=_precision.resolve(precision))
             return replaced(self, qkv)
 
         forward.replaced = replaced
@@ -1032,15 +1015,6 @@ def _transformer_ffn_call(layer, source, target, kwargs) -> bool:
     return _affine_norm(getattr(layer, "norm2", None), c) and layer.norm2.eps == layer.norm1.eps
 
 
-def _transformer_ffn_precision(precision) -> str:
-    """The `precision` option of the transformer-FFN seam, checked when the seam is installed: "highest", "high", or "torch"
-    (window_attention.resolve_precision reads torch's float32 matmul precision at every call)."""
-    from . import transformer_ffn as _tf
-    if precision != "torch" and precision not in _tf.PRECISIONS:
-        raise ValueError(f"transformer_ffn_precision is one of {[*_tf.PRECISIONS, 'torch']}, got {precision!r}")
-    return precision
-
-
 def _native_transformer_layer_forward(replaced, mod=None, precision="highest"):
     """TransformerLayer.forward with the reference's signature: for the calls _transformer_ffn_call accepts, the layer's own
     q_proj / k_proj / v_proj, the attention function the replaced method would call — looked up in the module's globals at call
@@ -1050,8 +1024,7 @@ def _native_transformer_layer_forward(replaced, mod=None, precision="highest"):
     `forward.native_calls` counts the calls the kernels took.  precision: the seam's option for ffn_tail's products, resolved
     at every call (layer_norm_residual has no product); `forward.precision` holds it."""
     from . import transformer_ffn as _tf
-    from . import window_attention as _wa
-    _transformer_ffn_precision(precision)
+    _precision.seam_option("transformer_ffn_precision", precision)
 
     def forward(self, source, target, height=None, width=None, shifted_window_attn_mask=None, attn_num_splits=None, **kwargs):
         if not _transformer_ffn_call(self, source, target, kwargs):
@@ -1070,7 +1043,7 @@ def _native_transformer_layer_forward(replaced, mod=None, precision="highest"):
         if self.no_ffn:
             return _tf.layer_norm_residual(message, n1.weight, n1.bias, source, n1.eps)
         return _tf.ffn_tail(source, message, n1.weight, n1.bias, self.mlp[0].weight, self.mlp[2].weight, self.norm2.weight,
-                            self.norm2.bias, n1.eps, precision=_wa.resolve_precision(precision))
+                            self.norm2.bias, n1.eps, precision=_precision.resolve(precision))
 
     forward.replaced = replaced
     forward.precision = precision
@@ -1138,7 +1111,7 @@ def install_window_attention(precision: str = "highest"):
     imported, else as soon as it is (import hook).  Returns {name: patched function} or None.  precision: "highest" (exact
     float32 products), "high" (bf16x3 products, window_attention.py) or "torch" (torch.get_float32_matmul_precision() at every
     call: 'highest' is "highest", 'high' and 'medium' are "high")."""
-    return WINDOW_ATTENTION_SEAM.install(precision=_window_attention_precision(precision))
+    return WINDOW_ATTENTION_SEAM.install(precision=_precision.seam_option("window_attention_precision", precision))
 
 
 def install_group_norm():
@@ -1157,7 +1130,7 @@ def install_unet_attention(precision: str = "highest"):
     (bf16x3 products, qkv_attention.py) or "torch" (torch.get_float32_matmul_precision() at every call: 'highest' is "highest",
     'high' and 'medium' are "high")."""
     return dict(zip((f"{seam.cls_name}.{seam.names[0]}" for seam in UNET_ATTENTION_SEAMS),
-                    _installed("unet_attention", precision=_unet_attention_precision(precision))))
+                    _installed("unet_attention", precision=_precision.seam_option("unet_attention_precision", precision))))
 
 
 def install_transformer_ffn(precision: str = "highest"):
@@ -1165,7 +1138,7 @@ def install_transformer_ffn(precision: str = "highest"):
     around the fused kernels of transformer_ffn.py now if the module is imported, else as soon as it is (import hook).  Returns the
     patched method or None.  precision: "highest" (exact float32 products), "high" (bf16x3 products, transformer_ffn.py) or
     "torch" (torch.get_float32_matmul_precision() at every call: 'highest' is "highest", 'high' and 'medium' are "high")."""
-    return _installed("transformer_ffn", precision=_transformer_ffn_precision(precision))[0]
+    return _installed("transformer_ffn", precision=_precision.seam_option("transformer_ffn_precision", precision))[0]
 
 
 def install_depth_smoothness():
@@ -1283,9 +1256,9 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     opts: window_attention_precision, unet_attention_precision, transformer_ffn_precision (above); for the decoder views_per_group (6), shared_campos (None = checked per group with one small read per forward), check ("sync"), glue."""
     given = locals()
     # an option of a seam, not a seam: taken out of opts (the decoder's options) before they reach the decoder
-    given["window_attention_options"] = {"precision": _window_attention_precision(opts.pop("window_attention_precision", "highest"))}
-    given["unet_attention_options"] = {"precision": _unet_attention_precision(opts.pop("unet_attention_precision", "highest"))}
-    given["transformer_ffn_options"] = {"precision": _transformer_ffn_precision(opts.pop("transformer_ffn_precision", "highest"))}
+    for seam in ("window_attention", "unet_attention", "transformer_ffn"):
+        option = seam + "_precision"
+        given[seam + "_options"] = {"precision": _precision.seam_option(option, opts.pop(option, "highest"))}
     for keyword, seams in OPTION_SEAMS.items():
         if given[keyword]:
             for seam in seams:

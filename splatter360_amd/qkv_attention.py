@@ -16,7 +16,7 @@ precision="highest" (the default) forms every product from exact float32 product
 torch.set_float32_matmul_precision('high') asks for, as in window_attention.py: each float32 number as the sum of two bfloat16
 numbers and each product A B as Ah Bh + Ah Bl + Al Bh on the bf16 MFMA, accumulated in float32 (csrc: the k_qah_* kernels).  Its
 planes live in a scratch tensor of `scratch_bytes(...)` bytes that a call allocates and drops; the autograd node keeps qkv and lse
-in either mode.  `window_attention.resolve_precision("torch")` reads torch's setting at call time.
+in either mode.  `precision.resolve("torch")` reads torch's setting at call time.
 """
 from __future__ import annotations
 
@@ -27,8 +27,9 @@ from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from . import precision as _prec
 from ._call import call, ptr
-from .window_attention import PRECISIONS
+from .precision import PRECISIONS  # noqa: F401  (the name callers of this module use)
 
 ORDERS = {"legacy": _lib.QKV_LEGACY, "new": _lib.QKV_NEW}
 HEAD_CHANNELS = (32,)
@@ -38,12 +39,6 @@ def supported_head_channels(ch: int) -> bool:
     return ch in HEAD_CHANNELS
 
 
-def _precision(precision: str) -> str:
-    if not isinstance(precision, str) or precision not in PRECISIONS:
-        raise ValueError(f"qkv_attention knows the precisions {list(PRECISIONS)}, got precision={precision!r}")
-    return precision
-
-
 def scratch_bytes(rows: int, views: int, heads: int, tokens: int, backward: bool) -> int:
     """s360_qkv_attention_high_scratch_bytes: the bytes of bf16 planes a "high" forward (backward) call needs."""
     return int(_lib.lib().s360_qkv_attention_high_scratch_bytes(int(rows), int(views), int(heads), HEAD_CHANNELS[0], int(tokens),
@@ -51,7 +46,7 @@ def scratch_bytes(rows: int, views: int, heads: int, tokens: int, backward: bool
 
 
 def _scratch(qkv: Tensor, views: int, heads: int, backward: bool) -> Tensor:
-    return torch.empty(scratch_bytes(int(qkv.shape[0]), views, heads, int(qkv.shape[2]), backward), dtype=torch.uint8, device=qkv.device)
+    return _prec.scratch(scratch_bytes(int(qkv.shape[0]), views, heads, int(qkv.shape[2]), backward), qkv.device)
 
 
 def _checked(what: str, qkv, n_heads, n_frames, cross_view, order) -> tuple:
@@ -88,7 +83,7 @@ def attention_forward(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_vie
                       precision: str = "highest") -> tuple:
     """s360_qkv_attention_forward (precision "high": s360_qkv_attention_high_forward) -> (out [N, heads ch, T] float32,
     lse [N / views, heads, views T] float64)."""
-    precision = _precision(precision)
+    precision = _prec.check("qkv_attention", precision)
     rows, views, heads, ch, tokens, code = _checked("attention_forward", qkv, n_heads, n_frames, cross_view, order)
     qkv = qkv.detach().contiguous()
     out = torch.empty(rows, heads * ch, tokens, dtype=torch.float32, device=qkv.device)
@@ -107,7 +102,7 @@ def attention_backward(qkv: Tensor, lse: Tensor, g_out: Tensor, n_heads: int, *,
     """s360_qkv_attention_backward (precision "high": s360_qkv_attention_high_backward, with the lse of a "high" forward) -> g_qkv
     in qkv's shape and layout.  `g_qkv`: a contiguous float32 buffer of qkv's shape on its device to write into (every element is
     written); allocated when None."""
-    precision = _precision(precision)
+    precision = _prec.check("qkv_attention", precision)
     rows, views, heads, ch, tokens, code = _checked("attention_backward", qkv, n_heads, n_frames, cross_view, order)
     if not isinstance(g_out, Tensor) or not g_out.is_cuda or g_out.dtype != torch.float32 or g_out.device != qkv.device \
             or tuple(g_out.shape) != (rows, heads * ch, tokens):
@@ -163,6 +158,6 @@ def qkv_attention(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: b
     a[c, t] = sum_s weight[t, s] v[c, s].  precision "highest": exact float32 products; "high": bf16x3 products on the bf16 MFMA,
     forward and backward (the module's docstring).  Returns a [N, heads ch, T] in qkv's row order.  Differentiable (once) in qkv.
     Float32 GPU tensors, ch = 32; no CPU path; a non-contiguous qkv is copied once."""
-    _precision(precision)
+    _prec.check("qkv_attention", precision)
     _checked("qkv_attention", qkv, n_heads, n_frames, cross_view, order)
     return _QKVAttention.apply(qkv, int(n_heads), int(n_frames), bool(cross_view), order, precision)

@@ -20,7 +20,7 @@ torch.set_float32_matmul_precision('high') asks for: each float32 number as the 
 forward and the backward as Ah Bh + Ah Bl + Al Bh on the bf16 MFMA, float32 accumulation (the LayerNorm rows stay float64).  The
 weights are split once per call into 3 MiB of bf16 planes in a scratch buffer; the token side is split inside the kernels, so the
 "high" mode saves what "highest" saves.  A forward run in one precision takes its backward in the same one.
-`window_attention.resolve_precision("torch")` reads torch's setting at call time.
+`precision.resolve("torch")` reads torch's setting at call time.
 """
 from __future__ import annotations
 
@@ -32,26 +32,21 @@ from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from . import precision as _prec
 from ._call import call, ptr
+from .precision import PRECISIONS  # noqa: F401  (the name callers of this module use)
 
 CHANNELS = 128
 HIDDEN = 1024
 FFN_GRADIENTS = ("g_source", "g_m", "g_norm1_weight", "g_norm1_bias", "g_w1", "g_w2", "g_norm2_weight", "g_norm2_bias")
 NORM_GRADIENTS = ("g_x", "g_weight", "g_bias", "g_residual")
-PRECISIONS = ("highest", "high")
-
-
-def _precision(precision: str) -> str:
-    if not isinstance(precision, str) or precision not in PRECISIONS:
-        raise ValueError(f"ffn_tail knows the precisions {list(PRECISIONS)}, got precision={precision!r}")
-    return precision
 
 
 def scratch_bytes(tokens: int, backward: bool, precision: str = "highest") -> int:
     """The bytes of scratch a forward (backward) call of ffn_tail allocates for `tokens` tokens: "highest" none for the forward
     and s360_ffn_tail_scratch_bytes for the backward; "high" s360_ffn_tail_high_scratch_bytes, the same plus the weights' bf16
     planes, whose size does not depend on tokens.  0 for tokens < 1."""
-    _precision(precision)
+    _prec.check("ffn_tail", precision)
     tokens = int(tokens)
     if precision == "high":
         return int(_lib.lib().s360_ffn_tail_high_scratch_bytes(tokens, int(bool(backward))))
@@ -149,7 +144,7 @@ def _buffers(what: str, names: Sequence[str], like: Sequence[Tensor], given: Opt
 
 
 def _scratch(tokens: int, device) -> Tensor:
-    return torch.empty(int(_lib.lib().s360_ffn_tail_scratch_bytes(tokens)), dtype=torch.uint8, device=device)
+    return _prec.scratch(_lib.lib().s360_ffn_tail_scratch_bytes(tokens), device)
 
 
 def _no_scratch(what: str, precision: str, given) -> None:
@@ -161,7 +156,7 @@ def _no_scratch(what: str, precision: str, given) -> None:
 def _high_scratch(what: str, tokens: int, backward: bool, device, given: Optional[Tensor]) -> Tensor:
     """The scratch of a "high" call: allocated, or the caller's uint8 buffer (the library checks its size and alignment)."""
     if given is None:
-        return torch.empty(scratch_bytes(tokens, backward, "high"), dtype=torch.uint8, device=device)
+        return _prec.scratch(scratch_bytes(tokens, backward, "high"), device)
     _tensor(what, "scratch", given, dtype=torch.uint8, device=device)
     if given.dim() != 1 or not given.is_contiguous():
         raise ValueError(f"{what}: scratch must be a contiguous 1-D uint8 buffer")
@@ -173,7 +168,7 @@ def ffn_tail_forward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bias
     """s360_ffn_tail_forward (precision "high": s360_ffn_tail_high_forward) -> (out in source's shape, z [T, C] float32, stats
     [2, T, 2] float64).  `scratch`: a uint8 buffer of scratch_bytes(T, False, "high") bytes for the "high" call to use in place
     of one it allocates; refused (ValueError) with any other precision, whose forward has no scratch."""
-    _precision(precision)
+    _prec.check("ffn_tail", precision)
     _no_scratch("ffn_tail_forward", precision, scratch)
     tokens = _checked_ffn("ffn_tail_forward", source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps)
     args = [_flat(t) for t in (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias)]
@@ -197,7 +192,7 @@ def ffn_tail_backward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bia
     them to write into; the others are allocated.  `scratch`: as in ffn_tail_forward, scratch_bytes(T, True, "high") bytes, refused with
     any other precision (the "highest" backward allocates its own)."""
     what = "ffn_tail_backward"
-    _precision(precision)
+    _prec.check("ffn_tail", precision)
     _no_scratch(what, precision, scratch)
     tokens = _checked_ffn(what, source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps)
     _tensor(what, "g_out", g_out, source.shape, device=source.device)
@@ -285,7 +280,7 @@ def ffn_tail(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bias: Tensor
     source's shape.  Differentiable (once) in all eight tensors.  Float32 GPU tensors, C = 128 and 8C = 1024; no CPU path; a
     non-contiguous input is copied once.  precision "highest": exact float32 products; "high": bf16x3 products on the bf16 MFMA,
     forward and backward (the module's docstring)."""
-    _precision(precision)
+    _prec.check("ffn_tail", precision)
     _checked_ffn("ffn_tail", source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, eps)
     return _FFNTail.apply(source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, float(eps), precision)
 

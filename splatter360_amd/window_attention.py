@@ -13,9 +13,9 @@ replaced functions for everything else).  Forward and backward are bit-identical
 
 precision="highest" (the default) forms every product from exact float32 products; precision="high" is what
 torch.set_float32_matmul_precision('high') asks for: each float32 number as the sum of two bfloat16 numbers and each product
-A B as Ah Bh + Ah Bl + Al Bh on the bf16 MFMA, accumulated in float32 (csrc: the k_wah_* kernels).  Its planes live in a scratch
-tensor of `scratch_bytes(...)` bytes that a call allocates and drops; the autograd node keeps q, k, v and lse in either mode.
-`resolve_precision("torch")` reads torch's setting at call time.
+A B as Ah Bh + Ah Bl + Al Bh on the bf16 MFMA, accumulated in float32 (precision.py; csrc: the k_wah_* kernels).  Its planes live
+in a scratch tensor of `scratch_bytes(...)` bytes that a call allocates and drops; the autograd node keeps q, k, v and lse in either
+mode.  `resolve_precision("torch")` (precision.resolve) reads torch's setting at call time.
 """
 from __future__ import annotations
 
@@ -24,12 +24,12 @@ from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from . import precision as _prec
 from ._call import _check_cuda_f32, call, ptr
+from .precision import PRECISIONS, resolve as resolve_precision  # noqa: F401  (the names callers of this module use)
 
 MASK_RULES = {"reference": 0, "aligned": 1}
 MIN_CHANNELS, MAX_CHANNELS, CHANNEL_STEP = 32, 128, 32
-PRECISIONS = ("highest", "high")
-_TORCH_PRECISIONS = {"highest": "highest", "high": "high", "medium": "high"}    # never less accurate than asked
 
 
 def supported_channels(c: int) -> bool:
@@ -42,20 +42,6 @@ def _rule(mask_rule: str) -> int:
     return MASK_RULES[mask_rule]
 
 
-def _precision(precision: str) -> str:
-    if not isinstance(precision, str) or precision not in PRECISIONS:
-        raise ValueError(f"window_attention knows the precisions {list(PRECISIONS)}, got precision={precision!r}")
-    return precision
-
-
-def resolve_precision(name: str) -> str:
-    """"highest" or "high" as they are; "torch": what torch.get_float32_matmul_precision() says now — 'highest' is "highest",
-    'high' and 'medium' are "high" (there is no single-bf16 mode: the result is never less accurate than asked)."""
-    if name == "torch":
-        return _TORCH_PRECISIONS[torch.get_float32_matmul_precision()]
-    return _precision(name)
-
-
 def scratch_bytes(batch: int, partners: int, height: int, width: int, channels: int, num_splits: int, backward: bool) -> int:
     """s360_window_attention_high_scratch_bytes: the bytes of bf16 planes a "high" forward (backward) call needs."""
     return int(_lib.lib().s360_window_attention_high_scratch_bytes(int(batch), int(partners), int(height), int(width), int(channels),
@@ -63,8 +49,7 @@ def scratch_bytes(batch: int, partners: int, height: int, width: int, channels: 
 
 
 def _scratch(q: Tensor, partners: int, height: int, width: int, num_splits: int, backward: bool) -> Tensor:
-    n = scratch_bytes(int(q.shape[0]), partners, height, width, int(q.shape[2]), num_splits, backward)
-    return torch.empty(n, dtype=torch.uint8, device=q.device)
+    return _prec.scratch(scratch_bytes(int(q.shape[0]), partners, height, width, int(q.shape[2]), num_splits, backward), q.device)
 
 
 def _checked(what: str, q: Tensor, k: Tensor, v: Tensor, height: int, width: int, num_splits: int) -> int:
@@ -97,7 +82,7 @@ def attention_forward(q: Tensor, k: Tensor, v: Tensor, *, height: int, width: in
                       mask_rule: str = "reference", precision: str = "highest") -> tuple:
     """s360_window_attention_forward (precision "high": s360_window_attention_high_forward) on contiguous float32 GPU tensors ->
     (out [B, L, C] float32, lse [B, L] float64)."""
-    rule, precision = _rule(mask_rule), _precision(precision)
+    rule, precision = _rule(mask_rule), _prec.check("window_attention", precision)
     partners = _checked("attention_forward", q, k, v, height, width, num_splits)
     q, k, v = (t.detach().contiguous() for t in (q, k, v))
     b, l, c = (int(s) for s in q.shape)
@@ -117,7 +102,7 @@ def attention_backward(q: Tensor, k: Tensor, v: Tensor, lse: Tensor, g_out: Tens
                        precision: str = "highest") -> tuple:
     """s360_window_attention_backward (precision "high": s360_window_attention_high_backward, with the lse of a "high" forward)
     -> (g_q, g_k, g_v) in the inputs' shapes, None where `needs` is False."""
-    rule, precision = _rule(mask_rule), _precision(precision)
+    rule, precision = _rule(mask_rule), _prec.check("window_attention", precision)
     partners = _checked("attention_backward", q, k, v, height, width, num_splits)
     _check_cuda_f32("attention_backward", q, g_out)
     if tuple(g_out.shape) != tuple(q.shape):
@@ -173,7 +158,7 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, *, height: int, width: int
     m <= 1 and without shift.  precision "highest": exact float32 products; "high": bf16x3 products on the bf16 MFMA, forward
     and backward (the module's docstring).  Returns out [B, L, C] in the original token order.  Differentiable (once) in q, k
     and v.  Float32 GPU tensors, C a multiple of 32 in [32, 128]; no CPU path; non-contiguous inputs are copied once."""
-    _precision(precision)
+    _prec.check("window_attention", precision)
     _rule(mask_rule)
     _checked("window_attention", q, k, v, height, width, num_splits)
     return _WindowAttention.apply(q, k, v, int(height), int(width), int(num_splits), bool(with_shift), mask_rule, precision)
@@ -182,7 +167,7 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, *, height: int, width: int
 def full_attention(q: Tensor, k: Tensor, v: Tensor, precision: str = "highest") -> Tensor:
     """The reference's single_head_full_attention (multiview_transformer.py:8-16) for Lq == Lk: softmax(q k^T / sqrt(C)) v over all
     tokens of a batch element, as one window without shift."""
-    _precision(precision)
+    _prec.check("window_attention", precision)
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, Tensor) or t.dim() != 3:
             raise ValueError(f"full_attention expects {name} [B, L, C]")
