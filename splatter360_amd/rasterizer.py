@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import NamedTuple, Optional
 
 import torch
@@ -409,123 +410,238 @@ def _f32c(t: Tensor, name: str) -> Tensor:
     return t.detach().float().contiguous()
 
 
-def _forward_call(prm, views, means3D, cov6, opac, shs, colors, want_radii: bool, depth_mode=None, mse=None):
-    lay = _lib.layout(prm)
-    dev = means3D.device
-    ws = torch.empty(lay.total_bytes, dtype=torch.uint8, device=dev)
-    n_img = prm.V // 2 if (prm.flags & _lib.FLAG_SPHERICAL) else prm.V     # spherical: views = (camera, seam ghost) pairs
-    images = torch.empty((n_img, 3, prm.H, prm.W), dtype=torch.float32, device=dev)
-    radii = torch.empty((prm.V, prm.P), dtype=torch.int32, device=dev) if want_radii else None
-    stream = _call.stream(dev)
-    depth = None
-    if mse is not None:     # (target[V,3,H,W], grad_scale): loss epilogue fused into the composite store
-        target, grad_scale = mse
-        if depth_mode is not None:
-            depth = torch.empty((prm.V, prm.H, prm.W), dtype=torch.float32, device=dev)
-        d_images = torch.empty_like(images)
-        nquads = prm.V * ((prm.H + 15) // 16) * ((prm.W + 15) // 16) * 4   # one partial per wave footprint (8x8 px)
-        partials = torch.empty((nquads, 2), dtype=torch.float32, device=dev)
-        loss_out = torch.empty((1 + prm.V,), dtype=torch.float32, device=dev)   # loss, clipped MSE per view (same call)
-        invoke("s360_forward_mse", C.byref(prm), ptr(views), ptr(means3D), ptr(cov6), ptr(opac), ptr(shs),
-               ptr(colors), ptr(images), ptr(depth), DEPTH_MODES.get(depth_mode, 0), ptr(radii),
-               ptr(target), C.c_float(grad_scale), ptr(d_images), ptr(partials), ptr(loss_out),
-               ptr(ws), lay.total_bytes, stream)
-        st = RasterState(prm, lay, ws)
-        st.d_images, st.mse_partials, st.mse_out = d_images, partials, loss_out
-        return images, radii, st, depth
-    if depth_mode is None:
-        invoke("s360_forward", C.byref(prm), ptr(views), ptr(means3D), ptr(cov6), ptr(opac), ptr(shs),
-               ptr(colors), ptr(images), ptr(radii), ptr(ws), lay.total_bytes, stream)
+class _Options(NamedTuple):
+    """The non-tensor arguments of one rasteriser call, as Function.apply carries them: one tuple, read by name.  The fields from
+    `shared_campos` to `atomic_grads` are rasterize_views' own and off in rasterize_raw; `differentiable_means` is rasterize_raw's."""
+    h: int
+    w: int
+    lean: bool
+    split_lists: object                 # True / False / "auto"
+    max_instances: Optional[int] = None
+    check: str = "sync"
+    depth_mode: Optional[str] = None
+    mse_weight: float = 1.0
+    mse_count: Optional[int] = None
+    mse_defer: bool = False
+    exchange: object = None
+    sh_degree: int = 0
+    shared_campos: bool = False
+    want_radii: bool = False
+    cov9: bool = False
+    sh_channel_major: bool = False
+    keep_slots: bool = False
+    defer_sh: bool = False
+    spherical: bool = False
+    atomic_grads: bool = False
+    differentiable_means: bool = False
+
+
+_NO_LOSS = SimpleNamespace(target=None, grad_scale=0.0, d_images=None, partials=None, out=None)
+_last = SimpleNamespace(state=None, deferred=None, holder=None)     # of the most recent call: last_state(), last_deferred(), deferred_of()
+
+
+def _params(dev, p: int, v: int, opt: _Options, needs_bwd: bool, has_target: bool, fixed_flags: int = 0, sh=None) -> _lib.S360Params:
+    """The S360Params of one call, from plain values (no GPU work).  `sh`: the shape of the harmonics, the raw node's coefficient
+    count, or None for precomputed colours; `fixed_flags`: what the node sets whatever its options say.  Each stateful policy runs
+    once, in this order: _mirror, split_decision, coop_decision, default_capacity, default_segments."""
+    if v > _lib.S360_MAX_VIEWS:
+        raise RuntimeError(f"at most {_lib.S360_MAX_VIEWS} views per call")
+    h, w = int(opt.h), int(opt.w)
+    prm = _lib.S360Params()
+    prm.P, prm.V, prm.H, prm.W, prm.sh_degree = p, v, h, w, int(opt.sh_degree)
+    if sh is None:
+        prm.M = 0
     else:
-        depth = torch.empty((n_img, prm.H, prm.W), dtype=torch.float32, device=dev)
-        invoke("s360_forward_depth", C.byref(prm), ptr(views), ptr(means3D), ptr(cov6), ptr(opac), ptr(shs),
-               ptr(colors), ptr(images), ptr(depth), DEPTH_MODES[depth_mode], ptr(radii),
-               ptr(ws), lay.total_bytes, stream)
-    return images, radii, RasterState(prm, lay, ws), depth
+        m = sh if isinstance(sh, int) else int(sh[2] if opt.sh_channel_major else sh[1])
+        prm.M = max(m, (int(opt.sh_degree) + 1) ** 2) if p == 0 else m
+    key = _hint_key(dev, p, v, h, w, opt.lean)
+    mirror = _mirror(key)
+    # (spherical mode never splits, but the adaptive decision still consumes the mirror's report and ages)
+    split = split_decision(key, opt.split_lists, v * ((h + 15) // 16) * ((w + 15) // 16) * 4) and not opt.spherical
+    atomic = opt.atomic_grads and needs_bwd
+    flags = fixed_flags
+    for flag, on in (
+            (_lib.FLAG_SHARED_CAMPOS, opt.shared_campos or v == 1),
+            (_lib.FLAG_COV9, opt.cov9),
+            (_lib.FLAG_SH_CHANNEL_MAJOR, opt.sh_channel_major),
+            (_lib.FLAG_FORWARD_ONLY, not (needs_bwd or opt.keep_slots)),
+            (_lib.FLAG_SH_DEG4_IGNORED, SH_DEG4_IGNORED and not fixed_flags & _lib.FLAG_RAW_INPUTS),   # (the raw entry never took the switch)
+            (_lib.FLAG_SPHERICAL, opt.spherical),
+            (_lib.FLAG_LEAN_LISTS, opt.lean),
+            (_lib.FLAG_DEFER_LOSS, opt.mse_defer and has_target and needs_bwd),
+            (_lib.FLAG_ATOMIC_GRADS, atomic),
+            (_lib.FLAG_SPLIT_LISTS, split and not atomic),
+            (_lib.FLAG_COOP_WALK, coop_decision(key))):
+        if on:
+            flags |= flag
+    prm.flags = flags
+    prm.max_instances = int(opt.max_instances) if opt.max_instances else default_capacity(
+        p, v, h, w, device=dev, lean=opt.lean, lazy=(opt.check != "sync"))
+    # every forward reports (instance count, overflow flag, long-list chunks) into pinned host memory: how check="lazy" callers
+    # size the next call
+    prm.header_mirror = mirror.data_ptr()
+    prm.max_segments = default_segments(key) if split else 0        # (from the decision itself, atomic_grads or not)
+    return prm
+
+
+def _loss_setup(mse_target: Optional[Tensor], v: int, opt: _Options) -> SimpleNamespace:
+    """The loss epilogue of one forward (a re-render writes the same buffers): the target, grad_scale = 2 w / n, d_images[V,3,H,W] =
+    grad_scale (image - target), one partial sum per wave footprint (8x8 px) and out[1 + V] = loss, clipped MSE per view."""
+    if mse_target is None:
+        return _NO_LOSS
+    h, w = int(opt.h), int(opt.w)
+    tgt = _f32c(mse_target, "mse_target")
+    if tuple(tgt.shape) != (v, 3, h, w):
+        raise RuntimeError(f"mse_target must be [{v},3,{opt.h},{opt.w}], got {tuple(tgt.shape)}")
+    n_mean = int(opt.mse_count) if opt.mse_count else v * 3 * h * w
+    nquads = v * ((h + 15) // 16) * ((w + 15) // 16) * 4
+    return SimpleNamespace(target=tgt, grad_scale=2.0 * float(opt.mse_weight) / n_mean, d_images=torch.empty_like(tgt),
+                           partials=torch.empty((nquads, 2), dtype=torch.float32, device=tgt.device),
+                           out=torch.empty((1 + v,), dtype=torch.float32, device=tgt.device))
+
+
+def _forward_call(prm, views: Tensor, head: tuple, opt: _Options, loss):
+    """Run the forward entry point of `prm` (`head`: its arguments between the views and the images) -> images, radii, depth,
+    RasterState.  check="sync": an overflowing call is rendered again at the exact size."""
+    dev = views.device
+    stream = _call.stream(dev)
+    n_img = prm.V // 2 if (prm.flags & _lib.FLAG_SPHERICAL) else prm.V     # spherical: views = (camera, seam ghost) pairs
+    dm = DEPTH_MODES.get(opt.depth_mode, 0)
+    raw = bool(prm.flags & _lib.FLAG_RAW_INPUTS)
+
+    def launch():
+        lay = _lib.layout(prm)
+        ws = torch.empty(lay.total_bytes, dtype=torch.uint8, device=dev)
+        images = torch.empty((n_img, 3, prm.H, prm.W), dtype=torch.float32, device=dev)
+        radii = torch.empty((prm.V, prm.P), dtype=torch.int32, device=dev) if opt.want_radii else None
+        depth = torch.empty((n_img, prm.H, prm.W), dtype=torch.float32, device=dev) if opt.depth_mode is not None else None
+        if raw or loss.target is not None:      # loss epilogue fused into the composite store
+            entry = "s360_forward_raw" if raw else "s360_forward_mse"
+            out = (ptr(images), ptr(depth), dm, ptr(radii), ptr(loss.target), C.c_float(loss.grad_scale), ptr(loss.d_images),
+                   ptr(loss.partials), ptr(loss.out))
+        elif depth is not None:
+            entry, out = "s360_forward_depth", (ptr(images), ptr(depth), dm, ptr(radii))
+        else:
+            entry, out = "s360_forward", (ptr(images), ptr(radii))
+        invoke(entry, C.byref(prm), ptr(views), *head, *out, ptr(ws), lay.total_bytes, stream)
+        st = RasterState(prm, lay, ws)
+        if loss.target is not None:
+            st.d_images, st.mse_partials, st.mse_out = loss.d_images, loss.partials, loss.out
+        return images, radii, depth, st
+
+    res = launch()
+    if opt.check == "sync" and res[3].overflowed():
+        prm.max_instances = res[3].num_rendered()
+        res = launch()
+    return res
+
+
+def _finish_forward(ctx, state: RasterState, depth: Optional[Tensor], not_differentiable: tuple):
+    """What both nodes do after the launch: keep the state, fill in the placeholders of results the call did not produce and mark
+    what autograd must not follow -> depth, loss, clipped MSE as the node returns them."""
+    dev = state.workspace.device
+    ctx.set_materialize_grads(False)
+    ctx.state = _last.state = state
+    if getattr(state, "mse_out", None) is not None:
+        loss = state.mse_out[0]             # reduced by the call itself (k_mse_finish: fixed order, deterministic)
+        clipped = state.mse_out[1:]
+    else:
+        loss = clipped = torch.empty(0, dtype=torch.float32, device=dev)
+    if depth is None:
+        depth = torch.empty(0, dtype=torch.float32, device=dev)
+        ctx.mark_non_differentiable(depth, clipped, *not_differentiable)
+    else:   # the fused depth map is differentiable (LossDepth back-propagates through it, loss_depth.py:37-60)
+        ctx.mark_non_differentiable(clipped, *not_differentiable)
+    return depth, loss, clipped
+
+
+def _upstream_grads(ctx, grad_images, grad_depth, grad_loss):
+    """What autograd hands a node's backward -> (dL/dimages, its device scalar factor or None, dL/ddepth or None, depth mode)."""
+    state: RasterState = ctx.state
+    prm = state.prm
+    g = None if grad_images is None else grad_images.detach().float()
+    g_scale = None
+    if grad_loss is not None and getattr(state, "d_images", None) is not None:
+        # d_images = 2w/N (image - target) from the epilogue; the scalar autograd hands back multiplies it inside
+        # the composite's pixel load (dL_dimages_scale) unless an image gradient has to be added as well
+        if g is None:
+            g, g_scale = state.d_images, grad_loss.detach().float().reshape(1).contiguous()
+        else:
+            g = g + state.d_images * grad_loss.detach().float()
+    if g is None:
+        n_img = prm.V // 2 if (prm.flags & _lib.FLAG_SPHERICAL) else prm.V
+        g = torch.zeros((n_img, 3, prm.H, prm.W), dtype=torch.float32, device=state.workspace.device)
+    gd, dm = None, 0
+    if grad_depth is not None and ctx.depth_mode is not None:
+        gd, dm = grad_depth.detach().float().contiguous(), DEPTH_MODES[ctx.depth_mode]
+    return g.contiguous(), g_scale, gd, dm
+
+
+def _exchange_gradients(ex, state: RasterState, views: Tensor, upstream, geometry, cov9: int, d_m2, on_range, d_m3, d_c6, d_op, bws):
+    """The multi-GPU backward up to the summed dL/dmean, dL/dcov, dL/dopacity: composite once, then the per-Gaussian tail range by
+    range with every range's collectives in flight behind the next one (distributed.exchange_chunked).  `geometry`: the means, the
+    covariances and the harmonics or raw records s360_backward_gaussians reads; `on_range(lo, hi, rgb_all, rep_all)`: what the
+    node does with a range's gathered dL/dRGB factors (None: they are not gathered)."""
+    from . import distributed
+    prm, lay, ws = state.prm, state.layout, state.workspace
+    dev = views.device
+    stream = _call.stream(dev)
+    g, g_scale, gd, dm = upstream
+    p = prm.P
+    invoke("s360_backward_composite", C.byref(prm), ptr(views), ptr(ws), lay.total_bytes, ptr(g), ptr(g_scale),
+           ptr(gd), dm, ptr(bws), lay.backward_bytes, stream)
+    packed = torch.empty((p, 10), dtype=torch.float32, device=dev)      # dL/dmean | dL/dcov6 | dL/dopacity
+    rgb = torch.empty((p, 4), dtype=torch.float32, device=dev)          # the clamp-masked dL/dRGB sums
+    rank = ex.rank()
+    means, cov, colours = geometry
+
+    def produce(lo, hi):
+        invoke("s360_backward_gaussians", C.byref(prm), ptr(views), ptr(means), ptr(cov), ptr(colours), ptr(ws),
+               lay.total_bytes, int(gd is not None), dm, lo, hi - lo, rank, ptr(packed),
+               ptr(d_m2), ptr(rgb), ptr(bws), lay.backward_bytes, stream)
+
+    def reduce_rows(lo, hi, rows):      # "gather" form: sum the ranks' rows + unpack, one pass
+        invoke("s360_reduce_unpack_gradients", ptr(rows), int(rows.shape[0]), lo, hi - lo, cov9, ptr(d_m3), ptr(d_c6),
+               ptr(d_op), _call.stream(dev))
+
+    form = distributed.exchange_chunked(p, packed, rgb, views[0], produce, on_range,
+                                        n_chunks=ex.n_chunks, group=ex.group, group_gather=ex.group_gather,
+                                        force_collectives=getattr(ex, "force_collectives", False), mode=getattr(ex, "mode", None),
+                                        reduce_rows=reduce_rows)
+    if form != "gather":
+        invoke("s360_unpack_gradients", ptr(packed), p, cov9, ptr(d_m3), ptr(d_c6), ptr(d_op), stream)
 
 
 class _RasterizeViews(torch.autograd.Function):
     """autograd node of one multi-view rasterisation (forward saves inputs + workspace)."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, shs, colors_precomp, opacities, cov6, views, cfg, mse_target=None):
-        (h, w, sh_degree, shared_campos, max_instances, check, want_radii, cov9, sh_channel_major, keep_slots, depth_mode,
-         defer_sh, mse_weight, mse_count, spherical, exchange, lean, mse_defer, atomic_grads, split_lists) = cfg
-        if exchange is not None and (shs is None or not (shared_campos or int(views.shape[0]) == 1) or defer_sh):
+    def forward(ctx, means3D, means2D, shs, colors_precomp, opacities, cov6, views, opt: _Options, mse_target=None):
+        if opt.exchange is not None and (shs is None or not (opt.shared_campos or int(views.shape[0]) == 1) or opt.defer_sh):
             raise RuntimeError("exchange=: the chunked gradient exchange needs SH colours and views sharing one camera centre "
                                "(and replaces defer_sh)")
-        ctx.exchange = exchange
-        if spherical and (mse_target is not None or int(views.shape[0]) % 2):
+        ctx.exchange = opt.exchange
+        if opt.spherical and (mse_target is not None or int(views.shape[0]) % 2):
             raise RuntimeError("spherical mode: views come in (camera, seam ghost) pairs; the fused loss epilogue is cube-face only")
-        if not means3D.is_cuda:
-            raise RuntimeError("means3D must live on the GPU (hip device); the rasteriser has no CPU path")
-        with torch.cuda.device(means3D.device):
-            m3 = _f32c(means3D, "means3D")
+        m3 = _f32c(means3D, "means3D")
+        with torch.cuda.device(m3.device):
             c6 = _f32c(cov6, "cov3D_precomp")
             op = _f32c(opacities, "opacities").reshape(-1)
             sh = None if shs is None else _f32c(shs, "shs")
             col = None if colors_precomp is None else _f32c(colors_precomp, "colors_precomp")
             vw = _f32c(views, "views")
             p, v = int(m3.shape[0]), int(vw.shape[0])
-            if v > _lib.S360_MAX_VIEWS:
-                raise RuntimeError(f"at most {_lib.S360_MAX_VIEWS} views per call")
-            prm = _lib.S360Params()
-            prm.P, prm.V, prm.H, prm.W = p, v, int(h), int(w)
-            prm.sh_degree = int(sh_degree)
-            prm.M = 0 if sh is None else int(sh.shape[2] if sh_channel_major else sh.shape[1])
-            if sh is not None and p == 0:
-                prm.M = max(prm.M, (int(sh_degree) + 1) ** 2)
             needs_bwd = any(ctx.needs_input_grad[:6])  # (grad mode is off inside Function.forward; this reflects apply-time)
-            hkey = _hint_key(m3.device, p, v, int(h), int(w), lean)
-            _mirror(hkey)
-            split_lists = split_decision(hkey, split_lists, v * ((int(h) + 15) // 16) * ((int(w) + 15) // 16) * 4) and not spherical
-            prm.flags = (_lib.FLAG_SHARED_CAMPOS if (shared_campos or v == 1) else 0) | (
-                _lib.FLAG_COV9 if cov9 else 0) | (_lib.FLAG_SH_CHANNEL_MAJOR if sh_channel_major else 0) | (
-                0 if (needs_bwd or keep_slots) else _lib.FLAG_FORWARD_ONLY) | (
-                _lib.FLAG_SH_DEG4_IGNORED if SH_DEG4_IGNORED else 0) | (_lib.FLAG_SPHERICAL if spherical else 0) | (
-                _lib.FLAG_LEAN_LISTS if lean else 0) | (
-                _lib.FLAG_DEFER_LOSS if (mse_defer and mse_target is not None and needs_bwd) else 0) | (
-                _lib.FLAG_ATOMIC_GRADS if (atomic_grads and needs_bwd) else 0) | (
-                _lib.FLAG_SPLIT_LISTS if (split_lists and not (atomic_grads and needs_bwd)) else 0) | (
-                _lib.FLAG_COOP_WALK if coop_decision(hkey) else 0)
-            prm.max_instances = int(max_instances) if max_instances else default_capacity(
-                p, v, int(h), int(w), device=m3.device, lean=lean, lazy=(check != "sync"))
-            # every forward reports (instance count, overflow flag, long-list chunks) into pinned host memory: how check="lazy" callers
-            # size the next call
-            prm.header_mirror = _mirror(hkey).data_ptr()
-            prm.max_segments = default_segments(hkey) if split_lists else 0
-            mse = None
-            if mse_target is not None:
-                tgt = _f32c(mse_target, "mse_target")
-                if tuple(tgt.shape) != (v, 3, int(h), int(w)):
-                    raise RuntimeError(f"mse_target must be [{v},3,{h},{w}], got {tuple(tgt.shape)}")
-                n_mean = int(mse_count) if mse_count else v * 3 * int(h) * int(w)
-                mse = (tgt, 2.0 * float(mse_weight) / n_mean)
-            images, radii, state, depth = _forward_call(prm, vw, m3, c6, op, sh, col, want_radii, depth_mode, mse)
-            if check == "sync" and state.overflowed():
-                prm.max_instances = state.num_rendered()
-                images, radii, state, depth = _forward_call(prm, vw, m3, c6, op, sh, col, want_radii, depth_mode, mse)
-            if mse is not None:
-                loss = state.mse_out[0]             # reduced by the call itself (k_mse_finish: fixed order, deterministic)
-                clipped_mse = state.mse_out[1:]
-            else:
-                loss = torch.empty(0, dtype=torch.float32, device=images.device)
-                clipped_mse = loss
-        ctx.set_materialize_grads(False)
-        ctx.state = state
-        ctx.holder = {}                       # filled by a deferred-SH backward; reachable from the output (deferred_of)
-        _RasterizeViews.last_holder = ctx.holder
-        ctx.defer_sh = bool(defer_sh) and sh is not None
+            prm = _params(m3.device, p, v, opt, needs_bwd, mse_target is not None, sh=None if sh is None else tuple(sh.shape))
+            loss = _loss_setup(mse_target, v, opt)
+            images, radii, depth, state = _forward_call(prm, vw, (ptr(m3), ptr(c6), ptr(op), ptr(sh), ptr(col)), opt, loss)
+        ctx.holder = _last.holder = {}        # filled by a deferred-SH backward; reachable from the output (deferred_of)
+        ctx.defer_sh = bool(opt.defer_sh) and sh is not None
         ctx.has_means2D = means2D is not None
-        ctx.depth_mode = depth_mode if depth is not None else None
-        _RasterizeViews.last_state = state
+        ctx.depth_mode = opt.depth_mode if depth is not None else None
         if radii is None:
             radii = torch.empty(0, dtype=torch.int32, device=images.device)
-        if depth is None:
-            depth = torch.empty(0, dtype=torch.float32, device=images.device)
-            ctx.mark_non_differentiable(radii, depth, clipped_mse)
-        else:   # the fused depth map is differentiable (LossDepth back-propagates through it, loss_depth.py:37-60)
-            ctx.mark_non_differentiable(radii, clipped_mse)
+        depth, loss, clipped_mse = _finish_forward(ctx, state, depth, (radii,))
         ctx.save_for_backward(m3, c6, op, sh, col, vw)
         return images, radii, depth, loss, clipped_mse
 
@@ -536,22 +652,7 @@ class _RasterizeViews(torch.autograd.Function):
         prm, lay = state.prm, state.layout
         dev = m3.device
         with torch.cuda.device(dev):
-            g = None if grad_images is None else grad_images.detach().float()
-            g_scale = None
-            if grad_loss is not None and getattr(state, "d_images", None) is not None:
-                # d_images = 2w/N (image - target) from the epilogue; the scalar autograd hands back multiplies it inside
-                # the composite's pixel load (dL_dimages_scale) unless an image gradient has to be added as well
-                if g is None:
-                    g, g_scale = state.d_images, grad_loss.detach().float().reshape(1).contiguous()
-                else:
-                    g = g + state.d_images * grad_loss.detach().float()
-            if g is None:
-                n_img = prm.V // 2 if (prm.flags & _lib.FLAG_SPHERICAL) else prm.V
-                g = torch.zeros((n_img, 3, prm.H, prm.W), dtype=torch.float32, device=dev)
-            g = g.contiguous()
-            gd, dm = None, 0
-            if grad_depth is not None and ctx.depth_mode is not None:
-                gd, dm = grad_depth.detach().float().contiguous(), DEPTH_MODES[ctx.depth_mode]
+            upstream = g, g_scale, gd, dm = _upstream_grads(ctx, grad_images, grad_depth, grad_loss)
             p, v = prm.P, prm.V
             d_m3 = torch.empty((p, 3), dtype=torch.float32, device=dev)
             d_c6 = torch.empty_like(c6)
@@ -563,21 +664,7 @@ class _RasterizeViews(torch.autograd.Function):
             bws = torch.empty(lay.backward_bytes, dtype=torch.uint8, device=dev)
             stream = _call.stream(dev)
             if ctx.exchange is not None:
-                # multi-GPU: the per-Gaussian gradients leave this node already SUMMED over the ranks — composite once, then
-                # the per-Gaussian tail range by range with every range's collectives in flight behind the next one
-                from . import distributed
-                ex = ctx.exchange
-                invoke("s360_backward_composite", C.byref(prm), ptr(vw), ptr(state.workspace), lay.total_bytes, ptr(g), ptr(g_scale),
-                       ptr(gd), dm, ptr(bws), lay.backward_bytes, stream)
-                packed = torch.empty((p, 10), dtype=torch.float32, device=dev)
-                rgb = torch.empty((p, 4), dtype=torch.float32, device=dev)
-                rank = ex.rank()
-
-                def produce(lo, hi):
-                    invoke("s360_backward_gaussians", C.byref(prm), ptr(vw), ptr(m3), ptr(c6), ptr(sh), ptr(state.workspace),
-                           lay.total_bytes, int(gd is not None), dm, lo, hi - lo, rank, ptr(packed),
-                           ptr(d_m2), ptr(rgb), ptr(bws), lay.backward_bytes, stream)
-
+                # multi-GPU: the per-Gaussian gradients leave this node already SUMMED over the ranks
                 slab = sh.shape[1] * sh.shape[2]
 
                 def rebuild_sh(lo, hi, rgb_all, rep_all):
@@ -588,21 +675,10 @@ class _RasterizeViews(torch.autograd.Function):
                            C.c_void_p(m3.data_ptr() + 12 * lo), ptr(rgb_all.contiguous()),
                            C.c_void_p(d_sh.data_ptr() + 4 * slab * lo), _call.stream(dev))
 
-                def reduce_rows(lo, hi, rows):      # "gather" form: sum the ranks' rows + unpack, one pass
-                    invoke("s360_reduce_unpack_gradients", ptr(rows), int(rows.shape[0]), lo, hi - lo, int(c6.dim() == 3), ptr(d_m3), ptr(d_c6),
-                           ptr(d_op), _call.stream(dev))
-
                 # harmonics frozen (need[2] False — on every rank, it is the same model): no dL/dRGB gathers, no dL/dSH rebuild
-                form = distributed.exchange_chunked(p, packed, rgb, vw[0], produce, rebuild_sh if d_sh is not None else None,
-                                                    n_chunks=ex.n_chunks, group=ex.group, group_gather=ex.group_gather,
-                                                    force_collectives=getattr(ex, "force_collectives", False), mode=getattr(ex, "mode", None),
-                                                    reduce_rows=reduce_rows)
-                if form != "gather":
-                    invoke("s360_unpack_gradients", ptr(packed), p, int(c6.dim() == 3), ptr(d_m3), ptr(d_c6), ptr(d_op), stream)
-                if d_m2 is not None:
-                    d_m2 = d_m2.sum(0) if v > 1 else d_m2[0]
-                return d_m3, d_m2, d_sh, None, d_op.view(-1, 1), d_c6, None, None, None
-            if ctx.defer_sh:
+                _exchange_gradients(ctx.exchange, state, vw, upstream, (m3, c6, sh), int(c6.dim() == 3), d_m2,
+                                    rebuild_sh if d_sh is not None else None, d_m3, d_c6, d_op, bws)
+            elif ctx.defer_sh:
                 # multi-GPU factored form: no SH pass here; the caller exchanges d_rgb_sum and finishes with
                 # finish_deferred_sh() (see distributed.sync_gradients_factored)
                 d_rgb = torch.empty((p, 4), dtype=torch.float32, device=dev)
@@ -610,14 +686,13 @@ class _RasterizeViews(torch.autograd.Function):
                        C.byref(prm), ptr(vw), ptr(m3), ptr(c6), ptr(op), ptr(sh), ptr(state.workspace), lay.total_bytes,
                        ptr(g), ptr(g_scale), ptr(gd), dm, ptr(d_m3), ptr(d_m2), ptr(d_c6), ptr(d_op), ptr(d_rgb),
                        ptr(bws), lay.backward_bytes, stream)
-                ctx.holder["deferred"] = _RasterizeViews.last_deferred = DeferredSH(prm, vw, m3, sh, d_rgb)
-                if d_m2 is not None:
-                    d_m2 = d_m2.sum(0) if v > 1 else d_m2[0]
-                return d_m3, d_m2, None, None, d_op.view(-1, 1), d_c6, None, None, None
-            invoke("s360_backward",
-                   C.byref(prm), ptr(vw), ptr(m3), ptr(c6), ptr(op), ptr(sh), ptr(col), ptr(state.workspace),
-                   lay.total_bytes, ptr(g), ptr(g_scale), ptr(gd), dm, ptr(d_m3), ptr(d_m2), ptr(d_c6),
-                   ptr(d_op), ptr(d_sh), ptr(d_col), ptr(bws), lay.backward_bytes, stream)
+                ctx.holder["deferred"] = _last.deferred = DeferredSH(prm, vw, m3, sh, d_rgb)
+                d_sh = None
+            else:
+                invoke("s360_backward",
+                       C.byref(prm), ptr(vw), ptr(m3), ptr(c6), ptr(op), ptr(sh), ptr(col), ptr(state.workspace),
+                       lay.total_bytes, ptr(g), ptr(g_scale), ptr(gd), dm, ptr(d_m3), ptr(d_m2), ptr(d_c6),
+                       ptr(d_op), ptr(d_sh), ptr(d_col), ptr(bws), lay.backward_bytes, stream)
         if d_m2 is not None:
             d_m2 = d_m2.sum(0) if v > 1 else d_m2[0]
         return d_m3, d_m2, d_sh, d_col, d_op.view(-1, 1), d_c6, None, None, None
@@ -630,15 +705,11 @@ class _RasterizeRaw(torch.autograd.Function):
     back, and without the [G,3,25] dL/dSH round trip in the backward.  Differentiable w.r.t. depths, opacities, raw_gaussians."""
 
     @staticmethod
-    def forward(ctx, depths, opacities, raw, ctx_extrinsics, sh_rot, views, cfg, mse_target=None):
-        (h, w, ch, cw, per_ray, smin, smax, eps, conv, diff_means, max_instances, check, depth_mode, mse_weight, mse_count, lean, mse_defer,
-         split_lists, exchange) = cfg
-        ctx.exchange = exchange
-        if not depths.is_cuda:
-            raise RuntimeError("depths must live on the GPU (hip device); the rasteriser has no CPU path")
-        dev = depths.device
+    def forward(ctx, depths, opacities, raw, ctx_extrinsics, sh_rot, views, opt: _Options, rin: _lib.S360RawInputs, mse_target=None):
+        ctx.exchange = opt.exchange
+        dep = _f32c(depths, "depths").reshape(-1)
+        dev = dep.device
         with torch.cuda.device(dev):
-            dep = _f32c(depths, "depths").reshape(-1)
             op = _f32c(opacities, "opacities").reshape(-1)
             rw = _f32c(raw, "raw_gaussians")
             ext = _f32c(ctx_extrinsics, "extrinsics").reshape(-1, 4, 4)
@@ -646,66 +717,21 @@ class _RasterizeRaw(torch.autograd.Function):
             vw = _f32c(views, "views")
             nv = int(ext.shape[0])
             p, v = int(dep.shape[0]), int(vw.shape[0])
-            if rw.shape[-1] != 82 or rw.numel() != p * 82 or p % max(nv, 1) or (p // max(nv, 1)) != ch * cw * per_ray:
+            if rw.shape[-1] != 82 or rw.numel() != p * 82 or p % max(nv, 1) or (p // max(nv, 1)) != rin.H * rin.W * rin.per_ray:
                 raise RuntimeError("rasterize_raw: raw_gaussians must be [views * h * w * per_ray, 82] (degree-4 harmonics) matching depths / extrinsics")
-            if v > _lib.S360_MAX_VIEWS:
-                raise RuntimeError(f"at most {_lib.S360_MAX_VIEWS} views per call")
-            needs_bwd = any(ctx.needs_input_grad[:3])
-            hkey = _hint_key(dev, p, v, int(h), int(w), lean)
-            _mirror(hkey)
-            split_lists = split_decision(hkey, split_lists, v * ((int(h) + 15) // 16) * ((int(w) + 15) // 16) * 4)
-            prm = _lib.S360Params()
-            prm.P, prm.V, prm.H, prm.W, prm.sh_degree, prm.M = p, v, int(h), int(w), 4, 25
-            prm.flags = _lib.FLAG_SHARED_CAMPOS | _lib.FLAG_RAW_INPUTS | (0 if needs_bwd else _lib.FLAG_FORWARD_ONLY) | (
-                _lib.FLAG_LEAN_LISTS if lean else 0) | (_lib.FLAG_SPLIT_LISTS if split_lists else 0) | (
-                _lib.FLAG_DEFER_LOSS if (mse_defer and mse_target is not None and needs_bwd) else 0) | (
-                _lib.FLAG_COOP_WALK if coop_decision(hkey) else 0)
-            prm.max_instances = int(max_instances) if max_instances else default_capacity(p, v, int(h), int(w), device=dev, lean=lean,
-                                                                                          lazy=(check != "sync"))
-            prm.header_mirror = _mirror(hkey).data_ptr()
-            prm.max_segments = default_segments(hkey) if split_lists else 0
-            rin = _lib.S360RawInputs(ext.data_ptr(), dep.data_ptr(), rw.data_ptr(), None if rot is None else rot.data_ptr(), nv, p // max(nv, 1),
-                                     int(ch), int(cw), int(per_ray), int(conv), float(smin), float(smax), float(eps))
+            prm = _params(dev, p, v, opt, any(ctx.needs_input_grad[:3]), mse_target is not None,
+                          _lib.FLAG_SHARED_CAMPOS | _lib.FLAG_RAW_INPUTS, sh=25)
+            loss = _loss_setup(mse_target, v, opt)
+            # (rasterize_raw filled in the geometry; the tensors are saved below, so the record still holds in the backward)
+            rin.extrinsics, rin.depths, rin.raw_gaussians = ext.data_ptr(), dep.data_ptr(), rw.data_ptr()
+            rin.sh_rotation = None if rot is None else rot.data_ptr()
+            rin.n_views, rin.per_view = nv, p // max(nv, 1)
             means = torch.empty((p, 3), dtype=torch.float32, device=dev)
             cov6 = torch.empty((p, 6), dtype=torch.float32, device=dev)
-            stream = _call.stream(dev)
-
-            def launch():
-                lay = _lib.layout(prm)
-                ws = torch.empty(lay.total_bytes, dtype=torch.uint8, device=dev)
-                images = torch.empty((v, 3, prm.H, prm.W), dtype=torch.float32, device=dev)
-                depth = torch.empty((v, prm.H, prm.W), dtype=torch.float32, device=dev) if depth_mode is not None else None
-                st = RasterState(prm, lay, ws)
-                tgt = d_images = partials = loss_out = None
-                gs = 0.0
-                if mse_target is not None:
-                    tgt = _f32c(mse_target, "mse_target")
-                    n_mean = int(mse_count) if mse_count else v * 3 * int(h) * int(w)
-                    gs = 2.0 * float(mse_weight) / n_mean
-                    d_images = torch.empty_like(images)
-                    partials = torch.empty((v * ((prm.H + 15) // 16) * ((prm.W + 15) // 16) * 4, 2), dtype=torch.float32, device=dev)
-                    loss_out = torch.empty((1 + v,), dtype=torch.float32, device=dev)
-                    st.d_images, st.mse_partials, st.mse_out = d_images, partials, loss_out
-                invoke("s360_forward_raw", C.byref(prm), ptr(vw), C.byref(rin), ptr(op), ptr(means), ptr(cov6), ptr(images), ptr(depth),
-                       DEPTH_MODES.get(depth_mode, 0), None, ptr(tgt), C.c_float(gs), ptr(d_images), ptr(partials),
-                       ptr(loss_out), ptr(ws), lay.total_bytes, stream)
-                return images, depth, st
-
-            images, depth, state = launch()
-            if check == "sync" and state.overflowed():
-                prm.max_instances = state.num_rendered()
-                images, depth, state = launch()
-        ctx.set_materialize_grads(False)
-        ctx.state, ctx.rin_cfg, ctx.depth_mode, ctx.diff_means = state, (nv, ch, cw, per_ray, conv, smin, smax, eps), depth_mode, bool(diff_means)
+            images, _, depth, state = _forward_call(prm, vw, (C.byref(rin), ptr(op), ptr(means), ptr(cov6)), opt, loss)
+        ctx.rin, ctx.depth_mode, ctx.diff_means = rin, opt.depth_mode, bool(opt.differentiable_means)
         ctx.in_shapes = (tuple(depths.shape), tuple(opacities.shape), tuple(raw.shape))   # gradients go back in the callers' shapes
-        _RasterizeViews.last_state = state
-        loss = state.mse_out[0] if mse_target is not None else torch.empty(0, dtype=torch.float32, device=dev)
-        clipped = state.mse_out[1:] if mse_target is not None else loss
-        if depth is None:
-            depth = torch.empty(0, dtype=torch.float32, device=dev)
-            ctx.mark_non_differentiable(depth, clipped, means, cov6)
-        else:
-            ctx.mark_non_differentiable(clipped, means, cov6)
+        depth, loss, clipped = _finish_forward(ctx, state, depth, (means, cov6))
         ctx.save_for_backward(dep, op, rw, ext, rot, vw, means, cov6)
         return images, depth, loss, clipped, means, cov6
 
@@ -713,26 +739,11 @@ class _RasterizeRaw(torch.autograd.Function):
     def backward(ctx, grad_images, grad_depth, grad_loss, _gc, _gm, _gv):
         dep, op, rw, ext, rot, vw, means, cov6 = ctx.saved_tensors
         state: RasterState = ctx.state
-        prm, lay = state.prm, state.layout
-        nv, ch, cw, per_ray, conv, smin, smax, eps = ctx.rin_cfg
+        prm, lay, rin, diff_means = state.prm, state.layout, ctx.rin, ctx.diff_means
         dev = dep.device
         p = prm.P
         with torch.cuda.device(dev):
-            g = None if grad_images is None else grad_images.detach().float()
-            g_scale = None
-            if grad_loss is not None and getattr(state, "d_images", None) is not None:
-                if g is None:
-                    g, g_scale = state.d_images, grad_loss.detach().float().reshape(1).contiguous()
-                else:
-                    g = g + state.d_images * grad_loss.detach().float()
-            if g is None:
-                g = torch.zeros((prm.V, 3, prm.H, prm.W), dtype=torch.float32, device=dev)
-            g = g.contiguous()
-            gd, dm = None, 0
-            if grad_depth is not None and ctx.depth_mode is not None:
-                gd, dm = grad_depth.detach().float().contiguous(), DEPTH_MODES[ctx.depth_mode]
-            rin = _lib.S360RawInputs(ext.data_ptr(), dep.data_ptr(), rw.data_ptr(), None if rot is None else rot.data_ptr(), nv, p // max(nv, 1),
-                                     int(ch), int(cw), int(per_ray), int(conv), float(smin), float(smax), float(eps))
+            upstream = g, g_scale, gd, dm = _upstream_grads(ctx, grad_images, grad_depth, grad_loss)
             d_m3 = torch.empty((p, 3), dtype=torch.float32, device=dev)
             d_c6 = torch.empty((p, 6), dtype=torch.float32, device=dev)
             d_op = torch.empty((p,), dtype=torch.float32, device=dev)
@@ -743,33 +754,15 @@ class _RasterizeRaw(torch.autograd.Function):
             stream = _call.stream(dev)
             if ctx.exchange is not None:
                 # multi-GPU (one target panorama per rank, the same raw cloud on every rank): the rows the exchange moves — packed
-                # [P,10] (dL/dmean | dL/dcov6 | dL/dopacity) and the clamp-masked dL/dRGB sums [P,4] — are exactly what k_raw_bwd takes,
-                # so after the exchange ONE launch forms dL/d(raw record) from the summed rows and the N ranks' dL/dRGB factors
-                from . import distributed
-                ex = ctx.exchange
-                invoke("s360_backward_composite", C.byref(prm), ptr(vw), ptr(state.workspace), lay.total_bytes, ptr(g), ptr(g_scale),
-                       ptr(gd), dm, ptr(bws), lay.backward_bytes, stream)
-                packed = torch.empty((p, 10), dtype=torch.float32, device=dev)
-                rgb = torch.empty((p, 4), dtype=torch.float32, device=dev)
-                rank = ex.rank()
+                # [P,10] and the dL/dRGB sums [P,4] — are exactly what k_raw_bwd takes, so after the exchange ONE launch forms
+                # dL/d(raw record) from the summed rows and the N ranks' dL/dRGB factors
                 gathered = {}
-
-                def produce(lo, hi):
-                    invoke("s360_backward_gaussians", C.byref(prm), ptr(vw), ptr(means), ptr(cov6), ptr(rw), ptr(state.workspace),
-                           lay.total_bytes, int(gd is not None), dm, lo, hi - lo, rank, ptr(packed),
-                           None, ptr(rgb), ptr(bws), lay.backward_bytes, stream)
 
                 def collect(lo, hi, rgb_all, rep_all):      # keep every range's gathered factors: k_raw_bwd runs once, over all of them
                     gathered[(lo, hi)] = rgb_all
                     gathered["rep"] = rep_all
 
-                def reduce_rows(lo, hi, rows):      # "gather" form: sum the ranks' rows + unpack, one pass
-                    invoke("s360_reduce_unpack_gradients", ptr(rows), int(rows.shape[0]), lo, hi - lo, 0, ptr(d_m3), ptr(d_c6), ptr(d_op),
-                           _call.stream(dev))
-
-                form = distributed.exchange_chunked(p, packed, rgb, vw[0], produce, collect, n_chunks=ex.n_chunks, group=ex.group,
-                                                    group_gather=ex.group_gather, force_collectives=getattr(ex, "force_collectives", False),
-                                                    mode=getattr(ex, "mode", None), reduce_rows=reduce_rows)
+                _exchange_gradients(ctx.exchange, state, vw, upstream, (means, cov6, rw), 0, None, collect, d_m3, d_c6, d_op, bws)
                 rep_all = gathered.pop("rep").contiguous()
                 world = int(rep_all.shape[0])
                 if len(gathered) == 1:
@@ -778,23 +771,15 @@ class _RasterizeRaw(torch.autograd.Function):
                     rgb_all = torch.empty((world, p, 4), dtype=torch.float32, device=dev)
                     for (lo, hi), t in gathered.items():
                         rgb_all[:, lo:hi] = t
-                if form != "gather":
-                    invoke("s360_unpack_gradients", ptr(packed), p, 0, ptr(d_m3), ptr(d_c6), ptr(d_op), stream)
                 invoke("s360_backward_raw_tail", C.byref(prm), ptr(rep_all), world, C.byref(rin), ptr(means), ptr(state.workspace),
-                       lay.total_bytes, ptr(d_m3) if ctx.diff_means else None, ptr(d_c6), ptr(rgb_all),
+                       lay.total_bytes, ptr(d_m3) if diff_means else None, ptr(d_c6), ptr(rgb_all),
                        ptr(d_dep), ptr(d_raw), stream)
-                sd, so, sr = ctx.in_shapes
-                return d_dep.view(sd), d_op.view(so), d_raw.view(sr), None, None, None, None, None
-            invoke("s360_backward_raw", C.byref(prm), ptr(vw), C.byref(rin), ptr(means), ptr(cov6), ptr(op), ptr(state.workspace),
-                   lay.total_bytes, ptr(g), ptr(g_scale), ptr(gd), dm, int(ctx.diff_means), ptr(d_m3), ptr(d_c6),
-                   ptr(d_op), ptr(d_rgb), ptr(d_dep), ptr(d_raw), ptr(bws), lay.backward_bytes, stream)
+            else:
+                invoke("s360_backward_raw", C.byref(prm), ptr(vw), C.byref(rin), ptr(means), ptr(cov6), ptr(op), ptr(state.workspace),
+                       lay.total_bytes, ptr(g), ptr(g_scale), ptr(gd), dm, int(diff_means), ptr(d_m3), ptr(d_c6),
+                       ptr(d_op), ptr(d_rgb), ptr(d_dep), ptr(d_raw), ptr(bws), lay.backward_bytes, stream)
         sd, so, sr = ctx.in_shapes
-        return d_dep.view(sd), d_op.view(so), d_raw.view(sr), None, None, None, None, None
-
-
-_RasterizeViews.last_state = None
-_RasterizeViews.last_deferred = None
-_RasterizeViews.last_holder = None
+        return d_dep.view(sd), d_op.view(so), d_raw.view(sr), None, None, None, None, None, None
 
 
 class FusedMse(NamedTuple):
@@ -820,7 +805,7 @@ class DeferredSH:
 def last_deferred() -> Optional[DeferredSH]:
     """DeferredSH of the most recent deferred-SH backward in this process (prefer deferred_of(images): it is tied to one
     rasteriser call and therefore safe with several defer_sh calls per step)."""
-    return _RasterizeViews.last_deferred
+    return _last.deferred
 
 
 def deferred_of(images: Tensor) -> Optional[DeferredSH]:
@@ -884,13 +869,15 @@ def rasterize_views(means3D: Tensor, cov6: Tensor, opacities: Tensor, shs: Optio
     op2 = opacities.reshape(-1, 1)
     if depth_mode is not None and depth_mode not in DEPTH_MODES:
         raise ValueError(f"depth_mode must be one of {sorted(DEPTH_MODES)}")
-    cfg = (image_height, image_width, sh_degree, shared_campos, max_instances, check, want_radii, cov9,
-           sh_channel_major, keep_slots, depth_mode, defer_sh, mse_weight, mse_count, bool(spherical), exchange,
-           LEAN_LISTS if lean is None else bool(lean), bool(mse_defer), ATOMIC_GRADS if atomic_grads is None else bool(atomic_grads),
-           SPLIT_LONG_LISTS if split_lists is None else (split_lists if split_lists == "auto" else bool(split_lists)))
+    opt = _Options(h=image_height, w=image_width, lean=LEAN_LISTS if lean is None else bool(lean),
+                   split_lists=SPLIT_LONG_LISTS if split_lists is None else (split_lists if split_lists == "auto" else bool(split_lists)),
+                   max_instances=max_instances, check=check, depth_mode=depth_mode, mse_weight=mse_weight, mse_count=mse_count,
+                   mse_defer=bool(mse_defer), exchange=exchange, sh_degree=sh_degree, shared_campos=shared_campos, want_radii=want_radii,
+                   cov9=cov9, sh_channel_major=sh_channel_major, keep_slots=keep_slots, defer_sh=defer_sh, spherical=bool(spherical),
+                   atomic_grads=ATOMIC_GRADS if atomic_grads is None else bool(atomic_grads))
     images, radii, depth, loss, clipped = _RasterizeViews.apply(means3D, means2D, shs, colors_precomp, op2, cov6, views,
-                                                                cfg, mse_target)
-    images.s360_deferred = _RasterizeViews.last_holder      # see deferred_of()
+                                                                opt, mse_target)
+    images.s360_deferred = _last.holder      # see deferred_of()
     out = (images, radii) if depth_mode is None else (images, radii, depth)
     return out if mse_target is None else out + (FusedMse(loss, clipped),)
 
@@ -912,18 +899,21 @@ def rasterize_raw(depths: Tensor, opacities: Tensor, raw_gaussians: Tensor, cont
     if depth_mode is not None and depth_mode not in DEPTH_MODES:
         raise ValueError(f"depth_mode must be one of {sorted(DEPTH_MODES)}")
     ch, cw = context_shape
-    cfg = (image_height, image_width, int(ch), int(cw), int(per_ray), float(scale_min), float(scale_max), float(eps), int(erp_convention),
-           bool(differentiable_means), max_instances, check, depth_mode, mse_weight, mse_count, LEAN_LISTS if lean is None else bool(lean),
-           bool(mse_defer), SPLIT_LONG_LISTS if split_lists is None else (split_lists if split_lists == "auto" else bool(split_lists)), exchange)
-    images, depth, loss, clipped, means, cov6 = _RasterizeRaw.apply(depths, opacities, raw_gaussians, context_extrinsics, sh_rotation, views, cfg,
-                                                                    mse_target)
+    opt = _Options(h=image_height, w=image_width, lean=LEAN_LISTS if lean is None else bool(lean),
+                   split_lists=SPLIT_LONG_LISTS if split_lists is None else (split_lists if split_lists == "auto" else bool(split_lists)),
+                   max_instances=max_instances, check=check, depth_mode=depth_mode, mse_weight=mse_weight, mse_count=mse_count,
+                   mse_defer=bool(mse_defer), exchange=exchange, sh_degree=4, differentiable_means=bool(differentiable_means))
+    rin = _lib.S360RawInputs(H=int(ch), W=int(cw), per_ray=int(per_ray), erp_convention=int(erp_convention), scale_min=float(scale_min),
+                             scale_max=float(scale_max), eps=float(eps))      # (the node adds the tensors' addresses and counts)
+    images, depth, loss, clipped, means, cov6 = _RasterizeRaw.apply(depths, opacities, raw_gaussians, context_extrinsics, sh_rotation, views, opt,
+                                                                    rin, mse_target)
     out = (images, means, cov6) if depth_mode is None else (images, means, cov6, depth)
     return out if mse_target is None else out + (FusedMse(loss, clipped),)
 
 
 def last_state() -> Optional[RasterState]:
     """Workspace of the most recent forward (tests / lazy overflow validation)."""
-    return _RasterizeViews.last_state
+    return _last.state
 
 
 def _cov6_from_scale_rotation(scales: Tensor, rotations: Tensor, scale_modifier: float) -> Tensor:

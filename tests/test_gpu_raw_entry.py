@@ -105,6 +105,25 @@ def test_raw_entry_inference_call_and_plain_images(gpu):
                                  context_shape=hw, scale_min=0.5, scale_max=15.0)
 
 
+def test_raw_entry_rejects_a_mis_shaped_loss_target(gpu):
+    """s360_forward_raw cannot know the target's extent (the composite's epilogue would read past its end), so the node checks it like
+    rasterize_views does — before any launch; the next call of the shape is the usual one."""
+    hw, nv, fw = (9, 14), 3, 64
+    depths, opac, raw, ext = _inputs(gpu, nv, *hw, seed=5 + nv)
+    rot = adapter.sh_rotation_blocks(ext, 25)
+    cams = decoder.cube_cameras(torch.eye(4, device=gpu), 0.1, 10.0)
+    views = decoder.pack_camera_views(*cams, torch.zeros(3, device=gpu))
+    before = rasterizer.last_state()
+    with pytest.raises(RuntimeError, match="mse_target must be"):
+        rasterizer.rasterize_raw(depths.reshape(-1), opac.reshape(-1), raw.reshape(-1, 82), ext, views=views, image_height=fw, image_width=fw,
+                                 context_shape=hw, scale_min=0.5, scale_max=15.0, sh_rotation=rot, mse_target=torch.zeros(6, 3, fw, fw + 1, device=gpu))
+    assert rasterizer.last_state() is before                  # nothing was rendered
+    target = torch.rand((6, 3, fw, fw), generator=torch.Generator().manual_seed(1)).to(gpu)
+    (img_a, fm_a), _, _ = _two_step(depths, opac, raw, ext, rot, cams, fw, hw, False, None, target)
+    (img_b, _, _, fm_b), _ = _raw(depths, opac, raw, ext, rot, cams, fw, hw, False, None, target)
+    assert torch.equal(img_a.detach(), img_b.detach()) and float(fm_a.loss.detach()) == float(fm_b.loss.detach())
+
+
 _MFMA_CHILD = r"""
 import sys, numpy as np, torch
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
