@@ -252,8 +252,9 @@ typedef struct S360Layout {
 typedef struct S360RawInputs {
     const float* extrinsics;    /* [n_views,4,4] context-panorama camera-to-world (row-major) */
     const float* depths;        /* [n_views*per_view] */
-    const float* raw_gaussians; /* [n_views*per_view, 82]: 3 scale logits, quaternion (x,y,z,w), 3 x 25 SH coefficients channel-major */
-    const float* sh_rotation;   /* [n_views,25,25] block-diagonal Wigner-D matrices of rotate_sh (s360_sh_rotation_blocks) or NULL = identity */
+    const float* raw_gaussians; /* raw_gaussians [P, 7 + 3*M]: 3 scale logits, quaternion (x,y,z,w), 3 x M SH coefficients channel-major,
+                                   M = prm->M = (prm->sh_degree + 1)^2 (record widths 10, 19, 34, 55, 82 at degrees 0..4) */
+    const float* sh_rotation;   /* sh_rotation [n_views, M, M]: block-diagonal Wigner-D matrices of rotate_sh (s360_sh_rotation_blocks) or NULL = identity */
     int32_t n_views, per_view;  /* P = n_views * per_view Gaussians, view-major */
     int32_t H, W, per_ray;      /* context panorama size; per_view = H*W*per_ray, ray-major */
     int32_t erp_convention;     /* as s360_adapter_forward */
@@ -447,14 +448,17 @@ int s360_pack_views(const float* extrinsics, const float* intrinsics, const floa
 /*
  * The adapter tail FUSED into the rasteriser: replaces GaussianAdapterERP.forward
  * (gaussian_adapter_erp.py:63-119) + the decoder's rasteriser call on its output (cuda_splatting.py:99-124) for views sharing one
- * camera centre, at the reference's configuration (degree-4 harmonics).  The call's first kernel reads the raw records once
- * (328 B/Gaussian), writes means_out[P,3] and cov6_out[P,6] (the adapter's values: what the geometry pass then reads, and what a
- * caller may keep) and evaluates the view-dependent colour with the SH basis carried through sh_mask and the per-view rotation —
- * the [P,3,25] harmonics and [P,3,3] covariances are never materialised (340 B/Gaussian written + 340 read by the two-step path).
- * prm: P = raw->n_views * raw->per_view, M = 25, sh_degree = 4, flags must hold S360_FLAG_RAW_INPUTS | S360_FLAG_SHARED_CAMPOS and not
- * S360_FLAG_COV9.  target == NULL: no loss epilogue (d_images / partials / loss_out ignored); depth_maps == NULL: no depth channel.
- * s360_backward_raw: the backward of that call down to the encoder's outputs — d_depths[P], d_raw_gaussians[P,82] (dL/d(SH
- * coefficient) formed as (mask . D^T Y) (x) dL/dRGB: the [P,3,25] dL/dSH round trip of the two-step path does not exist),
+ * camera centre, at SH degrees 0..4 (the reference's configuration is degree 4).  The call's first kernel reads the raw records once
+ * (40 / 76 / 136 / 220 / 328 B per Gaussian at degrees 0..4), writes means_out[P,3] and cov6_out[P,6] (the adapter's values: what the
+ * geometry pass then reads, and what a caller may keep) and evaluates the view-dependent colour with the SH basis carried through
+ * sh_mask and the per-view rotation — the [P,3,M] harmonics and [P,3,3] covariances are never materialised (340 B/Gaussian written +
+ * 340 read by the two-step path at degree 4).
+ * prm: P = raw->n_views * raw->per_view, sh_degree in 0..4, M = (sh_degree + 1)^2 exactly (the record holds that many coefficients per
+ * channel), flags must hold S360_FLAG_RAW_INPUTS | S360_FLAG_SHARED_CAMPOS and not S360_FLAG_COV9.  All three raw entry points answer
+ * a degree outside 0..4 or M > (sh_degree + 1)^2 with S360_E_UNSUPPORTED, and M < (sh_degree + 1)^2 with S360_E_BADARG (as s360_forward).
+ * target == NULL: no loss epilogue (d_images / partials / loss_out ignored); depth_maps == NULL: no depth channel.
+ * s360_backward_raw: the backward of that call down to the encoder's outputs — d_depths[P], d_raw_gaussians [P, 7 + 3*M] (dL/d(SH
+ * coefficient) formed as (mask . D^T Y) (x) dL/dRGB: the [P,3,M] dL/dSH round trip of the two-step path does not exist),
  * d_opacities[P]; d_means3D[P,3], d_cov6[P,6], d_rgb_sum[P,4] are caller-provided intermediates (valid results themselves).
  * differentiable_means = 0: the reference's detached means (sphere_projection.py:14-86 runs under torch.no_grad()); 1 adds the
  * un-projection's own depth term.  means / cov6: what s360_forward_raw wrote.

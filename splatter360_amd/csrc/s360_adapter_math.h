@@ -139,6 +139,70 @@ __device__ __forceinline__ void sh_rotate_basis25(const float* Dg, const float* 
     }
 }
 
+// ---- the same two transforms at a compile-time degree DEG in 0..4 (d_sh = (DEG + 1)^2 coefficients, matrix [d_sh, d_sh]) -------------
+// DEG = 4 is the code above, untouched.  Below it the COEFFICIENT transform restates the generic adapter kernel's expression
+// (k_adapter_fwd: acc = 0; acc += D * (c * mask), unfused, ascending b), because at those degrees that kernel is the two-step path
+// whose bits the raw forward reproduces; the matrix is still wave-uniform and read through the constant address space.
+template <int DEG, bool ROT>
+__device__ __forceinline__ void sh_rotate_coefs(const float* Dg, const float* c, float* out) {
+    static_assert(DEG >= 0 && DEG <= 4, "SH degree 0..4");
+    if constexpr (DEG == 4) {
+        sh_rotate_coefs25<ROT>(Dg, c, out);
+    } else {
+        constexpr int N = (DEG + 1) * (DEG + 1);
+        const sh_rot_ptr D = sh_rot_const(Dg);
+#pragma unroll
+        for (int l = 0; l <= DEG; ++l) {
+            const int o = l * l, nl = 2 * l + 1;
+#pragma unroll
+            for (int a = 0; a < nl; ++a) {
+                float acc;
+                if (ROT) {
+                    acc = 0.f;
+#pragma unroll
+                    for (int b = 0; b < nl; ++b) acc += D[(o + a) * N + o + b] * (c[o + b] * kShMask[l]);
+                } else {
+                    acc = c[o + a] * kShMask[l];
+                }
+                out[o + a] = acc;
+            }
+        }
+    }
+}
+
+// The basis transform of the raw backward.  Its multiply-adds are shared by waves 1 and 2 of k_raw_bwd: wave 1 owns the top band
+// (outputs k >= sh_split(DEG): (2 DEG + 1)^2 multiply-adds), wave 2 the bands below it (81 | 84 at degree 4, 49 | 35 at 3, 25 | 10
+// at 2); at degrees 0 and 1 the whole vector is 1 or 10 multiply-adds and wave 1 does it alone (sh_split = 0).
+__device__ constexpr int sh_split(int deg) { return deg >= 2 ? deg * deg : 0; }
+template <int DEG, bool ROT, int W>
+__device__ __forceinline__ void sh_rotate_basis(const float* Dg, const float* y, float* out) {
+    static_assert(DEG >= 0 && DEG <= 4, "SH degree 0..4");
+    static_assert(sh_split(4) == 16 && sh_half_owner(15) == 2 && sh_half_owner(16) == 1, "degree 4 keeps sh_half_owner's split");
+    if constexpr (DEG == 4) {
+        sh_rotate_basis25<ROT, W>(Dg, y, out);
+    } else {
+        constexpr int N = (DEG + 1) * (DEG + 1);
+        const sh_rot_ptr D = sh_rot_const(Dg);
+#pragma unroll
+        for (int l = 0; l <= DEG; ++l) {
+            const int o = l * l, nl = 2 * l + 1;
+#pragma unroll
+            for (int b = 0; b < nl; ++b) {
+                if (W >= 0 && (o + b >= sh_split(DEG) ? 1 : 2) != W) continue;
+                float acc;
+                if (ROT) {
+                    acc = D[o * N + o + b] * y[o];
+#pragma unroll
+                    for (int a = 1; a < nl; ++a) acc = __builtin_fmaf(D[(o + a) * N + o + b], y[o + a], acc);
+                } else {
+                    acc = y[o + b];
+                }
+                out[o + b] = acc * kShMask[l];
+            }
+        }
+    }
+}
+
 // ---- the same coefficient rotation on the matrix cores (round 6; north_star's MFMA clause, VERDICT r05 missing #7) ---------------------
 // For the 64 Gaussians of a workgroup and one colour channel, harmonics[64 x 25] = (mask . raw)[64 x 25] . D^T is a small dense
 // product with ONE shared operand (the view's matrix).  v_mfma_f32_16x16x4_f32, two block-diagonal tiles: degrees 3 + 4 are 7 + 9 = 16

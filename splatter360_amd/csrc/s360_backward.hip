@@ -682,25 +682,28 @@ struct RawBwd {
     const float* d_cov6;       // [P,6]
     const float4* d_rgb;       // [n_groups][P] (.w = index of the group's camera record, int32 bits, or -1)
     float* d_depths;           // [P]
-    float* d_raw;              // [P,82]
+    float* d_raw;              // [P, 7 + 3 M], M = (sh_degree + 1)^2
     int Gv, H, W, per_ray, conv, n_groups;
     float smin, smax, eps;
 };
-constexpr int RAWB_C = 82;
 
 // Round 6: workgroups dealt per context view (the view's Wigner-D matrix is wave-uniform: scalar loads, SGPR operands — round 5 read it
 // from LDS, one ds_read per multiply-add, on all three waves redundantly); the rotated masked basis is computed ONCE per Gaussian, its
 // 165 multiply-adds shared by waves 1 and 2 (degree 4 | degrees 0..3) through LDS, while wave 0 runs the geometry chain.
-template <bool ROT>
+// DEG (compile time, 0..4): the gradient record is 7 + 3 (DEG + 1)^2 floats; wave 1 rotates the basis entries k >= sh_split(DEG) and
+// wave 2 those below (s360_adapter_math.h: the top band against the rest at degrees 2..4, everything on wave 1 at degrees 0 and 1).
+// Every sum keeps its fixed order at every degree: ascending groups, no atomics.
+template <bool ROT, int DEG = 4>
 __global__ __launch_bounds__(192) void k_raw_bwd(KParams kp, const S360View* __restrict__ views, RawBwd rb) {
+    constexpr int N = (DEG + 1) * (DEG + 1), RAWB_C = 7 + 3 * N, SPLIT = sh_split(DEG);
     __shared__ __attribute__((aligned(16))) float s_out[64 * RAWB_C];
-    __shared__ float s_yp[25 * 64];      // (mask . D^T Y)[k] of lane l at [k * 64 + l]
+    __shared__ float s_yp[N * 64];       // (mask . D^T Y)[k] of lane l at [k * 64 + l]
     __shared__ float4 s_w[64];           // the group's dL/dRGB (0 where the Gaussian is invisible in the group's views)
     const int tid = threadIdx.x, d = tid >> 6, l = tid & 63;
     const int v = blockIdx.y, gi0 = blockIdx.x * 64;
     const int nb = min(64, rb.Gv - gi0), g0 = v * rb.Gv + gi0, g = g0 + l;
     const bool live = l < nb;
-    const float* D = ROT ? rb.sh_rot + (size_t)v * 625 : nullptr;   // wave-uniform
+    const float* D = ROT ? rb.sh_rot + (size_t)v * (N * N) : nullptr;   // wave-uniform
     if (d == 0 && live) {
         // ---- geometry: k_adapter_bwd's chain (scale map, quaternion, covariance), 6-entry covariance gradient — wave 0, while waves 1
         // and 2 rotate the basis
@@ -791,14 +794,15 @@ __global__ __launch_bounds__(192) void k_raw_bwd(KParams kp, const S360View* __r
     {
         // ---- colour channel d: sum over the camera groups of (mask . D^T Y(dir_j)) * dL/dRGB_j[d]
         float m0 = 0.f, m1 = 0.f, m2 = 1.f;
-        if (live && d >= 1) { m0 = rb.means[3 * (size_t)g]; m1 = rb.means[3 * (size_t)g + 1]; m2 = rb.means[3 * (size_t)g + 2]; }
-        float acc[25];
+        const bool rotates = SPLIT > 0 ? d >= 1 : d == 1;   // the waves that share the basis transform
+        if (live && rotates) { m0 = rb.means[3 * (size_t)g]; m1 = rb.means[3 * (size_t)g + 1]; m2 = rb.means[3 * (size_t)g + 2]; }
+        float acc[N];
 #pragma unroll
-        for (int k = 0; k < 25; ++k) acc[k] = 0.f;
+        for (int k = 0; k < N; ++k) acc[k] = 0.f;
 #pragma unroll 1
         for (int j = 0; j < rb.n_groups; ++j) {
             if (j > 0) __syncthreads();   // the previous group's s_yp / s_w were read
-            if (d >= 1) {
+            if (rotates) {
                 float4 dr = make_float4(0.f, 0.f, 0.f, 0.f);
                 int fv = 0;
                 if (live) {
@@ -811,28 +815,28 @@ __global__ __launch_bounds__(192) void k_raw_bwd(KParams kp, const S360View* __r
                 const float dx = m0 * sc - vw.campos[0], dy = m1 * sc - vw.campos[1], dz = m2 * sc - vw.campos[2];
                 const float inv = 1.f / sqrtf(dx * dx + dy * dy + dz * dz);
                 float Y[25], Yp[25];
-                sh_basis(4, dx * inv, dy * inv, dz * inv, Y);
+                sh_basis(DEG, dx * inv, dy * inv, dz * inv, Y);
                 if (d == 1) {
-                    sh_rotate_basis25<ROT, 1>(D, Y, Yp);
+                    sh_rotate_basis<DEG, ROT, 1>(D, Y, Yp);
 #pragma unroll
-                    for (int k = 16; k < 25; ++k) s_yp[k * 64 + l] = Yp[k];
+                    for (int k = SPLIT; k < N; ++k) s_yp[k * 64 + l] = Yp[k];
                     s_w[l] = dr;
                 } else {
-                    sh_rotate_basis25<ROT, 2>(D, Y, Yp);
+                    sh_rotate_basis<DEG, ROT, 2>(D, Y, Yp);
 #pragma unroll
-                    for (int k = 0; k < 16; ++k) s_yp[k * 64 + l] = Yp[k];
+                    for (int k = 0; k < SPLIT; ++k) s_yp[k * 64 + l] = Yp[k];
                 }
             }
             __syncthreads();
             const float4 dr = s_w[l];
             const float w = d == 0 ? dr.x : (d == 1 ? dr.y : dr.z);
 #pragma unroll
-            for (int k = 0; k < 25; ++k) acc[k] = __builtin_fmaf(s_yp[k * 64 + l], w, acc[k]);
+            for (int k = 0; k < N; ++k) acc[k] = __builtin_fmaf(s_yp[k * 64 + l], w, acc[k]);
         }
         if (live) {
-            float* orec = s_out + l * RAWB_C + 7 + 25 * d;
+            float* orec = s_out + l * RAWB_C + 7 + N * d;
 #pragma unroll
-            for (int k = 0; k < 25; ++k) orec[k] = acc[k];
+            for (int k = 0; k < N; ++k) orec[k] = acc[k];
         }
     }
     __syncthreads();
@@ -1417,7 +1421,7 @@ static int raw_tail(const S360Params* prm, const S360View* views, int n_groups, 
     const int rc = s360_layout(prm, &L);
     if (rc) return rc;
     KParams kp;
-    kp.P = prm->P; kp.V = prm->V; kp.H = prm->H; kp.W = prm->W; kp.deg = 4; kp.M = 25;
+    kp.P = prm->P; kp.V = prm->V; kp.H = prm->H; kp.W = prm->W; kp.deg = prm->sh_degree; kp.M = prm->M;   // (s360_raw_degree_check passed)
     kp.gx = (prm->W + 15) / 16; kp.gy = (prm->H + 15) / 16; kp.T = kp.gx * kp.gy;
     kp.flags = prm->flags; kp.cap = prm->max_instances;
     RawBwd rb{raw->extrinsics, raw->depths, (const float*)((const char*)workspace + L.geo7), raw->sh_rotation, means,
@@ -1426,8 +1430,16 @@ static int raw_tail(const S360Params* prm, const S360View* views, int n_groups, 
     {
         ProfScope ps(PS_SH_BWD, (hipStream_t)stream_);
         const dim3 bgrid((rb.Gv + 63) / 64, (unsigned)(prm->P / rb.Gv));   // per context view: its rotation matrix is wave-uniform
-        if (rb.sh_rot) hipLaunchKernelGGL(k_raw_bwd<true>, bgrid, dim3(192), 0, (hipStream_t)stream_, kp, views, rb);
-        else hipLaunchKernelGGL(k_raw_bwd<false>, bgrid, dim3(192), 0, (hipStream_t)stream_, kp, views, rb);
+#define S360_RAWB(DG) do { if (rb.sh_rot) hipLaunchKernelGGL((k_raw_bwd<true, DG>), bgrid, dim3(192), 0, (hipStream_t)stream_, kp, views, rb); \
+                           else hipLaunchKernelGGL((k_raw_bwd<false, DG>), bgrid, dim3(192), 0, (hipStream_t)stream_, kp, views, rb); } while (0)
+        switch (prm->sh_degree) {
+            case 0: S360_RAWB(0); break;
+            case 1: S360_RAWB(1); break;
+            case 2: S360_RAWB(2); break;
+            case 3: S360_RAWB(3); break;
+            default: S360_RAWB(4);
+        }
+#undef S360_RAWB
     }
     S360_CHECK_LAUNCH();
     return S360_OK;
@@ -1442,7 +1454,7 @@ extern "C" int s360_backward_raw(const S360Params* prm, const S360View* views, c
         return S360_E_BADARG;
     if (!(prm->flags & S360_FLAG_RAW_INPUTS) || !(prm->flags & S360_FLAG_SHARED_CAMPOS) || (prm->flags & (S360_FLAG_COV9 | S360_FLAG_SPHERICAL)))
         return S360_E_BADARG;
-    if (prm->M != 25 || prm->sh_degree != 4) return S360_E_UNSUPPORTED;
+    if (const int rc = s360_raw_degree_check(prm)) return rc;
     if ((long long)raw->n_views * raw->per_view != (long long)prm->P) return S360_E_BADARG;
     // the rasteriser's own backward without its dL/dSH pass (the s360_backward_split form: per-Gaussian dL/dmean, dL/dcov6, dL/dopacity
     // and the clamp-masked sum of dL/dRGB) ...
@@ -1484,7 +1496,7 @@ extern "C" int s360_backward_raw_tail(const S360Params* prm, const S360View* gro
     if (!prm || !group_views || !raw || !means || !workspace || !d_cov6 || !d_rgb_sums || !d_depths || !d_raw_gaussians || n_groups < 1)
         return S360_E_BADARG;
     if (!(prm->flags & S360_FLAG_RAW_INPUTS) || (prm->flags & (S360_FLAG_COV9 | S360_FLAG_SPHERICAL | S360_FLAG_FORWARD_ONLY))) return S360_E_BADARG;
-    if (prm->M != 25 || prm->sh_degree != 4) return S360_E_UNSUPPORTED;
+    if (const int rc = s360_raw_degree_check(prm)) return rc;
     if ((long long)raw->n_views * raw->per_view != (long long)prm->P) return S360_E_BADARG;
     S360Layout L;
     const int rc = s360_layout(prm, &L);

@@ -26,6 +26,16 @@ static inline int s360_effective_degree(const S360Params* prm) {
     return (prm->sh_degree > 3 && (prm->flags & S360_FLAG_SH_DEG4_IGNORED)) ? 3 : prm->sh_degree;
 }
 
+// The raw-input entry points (s360_forward_raw, s360_backward_raw, s360_backward_raw_tail) run at SH degrees 0..4 and read records of
+// exactly (sh_degree + 1)^2 coefficients per channel.  A degree outside 0..4, or more stored coefficients than the degree uses (an
+// active degree below the stored one: the general path's feature), is a configuration they do not have: S360_E_UNSUPPORTED.  Fewer
+// stored coefficients than the degree needs is a contradiction in the arguments, S360_E_BADARG, as in s360_forward / s360_backward.
+static inline int s360_raw_degree_check(const S360Params* prm) {
+    if (prm->sh_degree < 0 || prm->sh_degree > 4) return S360_E_UNSUPPORTED;
+    const int n = (prm->sh_degree + 1) * (prm->sh_degree + 1);
+    return prm->M < n ? S360_E_BADARG : (prm->M > n ? S360_E_UNSUPPORTED : S360_OK);
+}
+
 // float4s per (instance, quadrant) partial raster-gradient record of the backward: 3 = packed 48-byte records, 4 = 64-byte aligned
 // slots (a record never straddles a 128-byte line or a 32-byte write granule)
 #ifndef S360_PREC_F4

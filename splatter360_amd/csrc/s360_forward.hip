@@ -180,18 +180,21 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_sh_eval3(KParams kp, const S360V
 // previous step's k_sh_bwd, whose 315 MB of dL/dSH are still being written back from the L2 / Infinity Cache while it reads
 // (ablations: without the jacobian stores 96 us, without the gradient evaluation 99 us — neither is the cost).
 constexpr uint32_t SHG_NZ_X = 0x1E7FFD8u, SHG_NZ_Y = 0x1CFFF72u, SHG_NZ_Z = 0x0FE7CE4u;  // non-zero entries of sh_basis_grad's dx / dy / dz at degree 4
-template <int D>
+// DEG: the slab's degree ([3][(DEG + 1)^2] channel-major).  The non-zero masks are prefixes of the degree-4 ones: the basis is the same
+// polynomial table cut at (DEG + 1)^2 entries, and the sums are k_sh_eval's fmaf chains from 0 in ascending k at every degree.
+template <int D, int DEG = 4>
 __device__ __forceinline__ void sh_jac_component(float x, float y, float z, const float* __restrict__ slab, float* G) {
+    constexpr int N = (DEG + 1) * (DEG + 1);
     float b0[25], b1[25], b2[25];
-    sh_basis_grad(4, x, y, z, b0, b1, b2);
+    sh_basis_grad(DEG, x, y, z, b0, b1, b2);
     const float* b = D == 0 ? b0 : (D == 1 ? b1 : b2);
     constexpr uint32_t NZ = D == 0 ? SHG_NZ_X : (D == 1 ? SHG_NZ_Y : SHG_NZ_Z);
     G[0] = G[1] = G[2] = 0.f;
 #pragma unroll
-    for (int k = 0; k < 25; ++k) {
+    for (int k = 0; k < N; ++k) {
         if (!((NZ >> k) & 1u)) continue;  // fma(0, c, G) == G
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) G[ch] = __builtin_fmaf(b[k], slab[25 * ch + k], G[ch]);
+        for (int ch = 0; ch < 3; ++ch) G[ch] = __builtin_fmaf(b[k], slab[N * ch + k], G[ch]);
     }
 }
 
@@ -289,15 +292,18 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_sh_eval3_jac(KParams kp, const S
 struct RawIn {
     const float* extrinsics;   // [n_views,4,4] context-panorama camera-to-world
     const float* depths;       // [P]
-    const float* raw;          // [P, 82]
-    const float* sh_rot;       // [n_views,25,25] or null (identity)
+    const float* raw;          // [P, 7 + 3 M], M = (sh_degree + 1)^2
+    const float* sh_rot;       // [n_views,M,M] or null (identity)
     float* means_out;          // [P,3]
     float* cov6_out;           // [P,6]
     float* geo7;               // [P,7] (workspace): the raw geometry words, for the backward
     int Gv, H, W, per_ray, conv;
     float smin, smax, eps;
 };
-constexpr int RAW_C = 82;   // 7 + 3 * 25 floats per raw record
+constexpr int raw_record_floats(int deg) { return 7 + 3 * (deg + 1) * (deg + 1); }   // 10, 19, 34, 55, 82 floats per raw record
+// 16-byte staging rounds of the workgroup's 64 records (192 float4 per round): 1, 2, 3, 5, 7
+constexpr int raw_stage_rounds(int deg) { return (SHE3_G * raw_record_floats(deg) / 4 + SHE3_G * 3 - 1) / (SHE3_G * 3); }
+static_assert(raw_stage_rounds(4) == 7 && raw_stage_rounds(0) == 1 && (SHE3_G * raw_record_floats(1)) % 4 == 0, "64 records are whole float4s at every degree");
 
 // Round 6: the transform is applied to the COEFFICIENTS, once per (Gaussian, channel), with the view's matrix in SGPRs
 // (sh_rotate_coefs25: 165 multiply-adds on wave ch, scalar loads of D — the kernel's workgroups are dealt per context view, so D is
@@ -306,10 +312,20 @@ constexpr int RAW_C = 82;   // 7 + 3 * 25 floats per raw record
 // multiply-adds per lane on every one of the three waves, 145 us); rotating three coefficient vectors is less work than rotating
 // four basis vectors, and the harmonics — hence colours, sh_jac, images — are now bit-identical to the two-step path's
 // (adapter kernel, then k_sh_eval3_jac).
-template <bool JAC, bool ROT, bool MFMA = false>
+//
+// DEG (compile time, 0..4): the records hold (DEG + 1)^2 coefficients per channel; record stride, staging rounds, slab offsets and the
+// matrix stride derive from it.  Degree 4 is the code as it was.  Below it the two-step path whose bits this kernel reproduces is the
+// GENERIC pair (k_adapter_fwd, then k_sh_eval<true, JAC>): sh_rotate_coefs<DEG> restates the former's rotation, the colour sum and the
+// jacobian chains are the latter's, and so is its last rounding — sh_jac = scale * ((G - dir (dir . G)) * inv) there, against
+// (G - dir (dir . G)) * (scale * inv) in k_sh_eval3_jac — so s_dir.w carries inv alone below degree 4.  Lanes read their record at a
+// stride of 10 / 19 / 34 / 55 / 82 words: the even strides are two-way bank conflicts on the 64 banks, as degree 4 always had; the
+// records are not padded (the staging rounds stay plain 16-byte copies).  MFMA exists at degree 4 only.
+template <bool JAC, bool ROT, bool MFMA = false, int DEG = 4>
 __global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360View* __restrict__ views, RawIn rin, float4* __restrict__ rgbc,
                                                         float* __restrict__ sh_jac, uint32_t* __restrict__ zero_ptr, int zero_words) {
-    __shared__ __attribute__((aligned(16))) float s_raw[7 * SHE3_G * 3 * 4];   // 64 records x 82 floats = 5 248 floats (+ pad to 7 rounds of 192 float4)
+    static_assert(!MFMA || DEG == 4, "the matrix-core rotation is a degree-4 experiment");
+    constexpr int N = (DEG + 1) * (DEG + 1), RAW_C = raw_record_floats(DEG), ROUNDS = raw_stage_rounds(DEG);
+    __shared__ __attribute__((aligned(16))) float s_raw[ROUNDS * SHE3_G * 3 * 4];   // 64 records x RAW_C floats (degree 4: 5 248) + pad to whole rounds of 192 float4
     __shared__ float s_rgb[SHE3_G * 3];
     __shared__ float s_G[9 * SHE3_G];
     __shared__ float4 s_dir[SHE3_G];
@@ -327,14 +343,14 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360V
         const int nfl = nb * RAW_C;
         if ((((uintptr_t)src) & 15) == 0 && nb == SHE3_G) {
             float4* d4 = reinterpret_cast<float4*>(s_raw);
-            float4 q[7];
+            float4 q[ROUNDS];
 #pragma unroll
-            for (int r = 0; r < 7; ++r) {
+            for (int r = 0; r < ROUNDS; ++r) {
                 const f4v t = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(src) + min(tid + r * (SHE3_G * 3), SHE3_G * RAW_C / 4 - 1));
                 q[r] = make_float4(t.x, t.y, t.z, t.w);
             }
 #pragma unroll
-            for (int r = 0; r < 7; ++r) d4[tid + r * (SHE3_G * 3)] = q[r];
+            for (int r = 0; r < ROUNDS; ++r) d4[tid + r * (SHE3_G * 3)] = q[r];
         } else {
             for (int i = tid; i < nfl; i += SHE3_G * 3) s_raw[i] = src[i];
         }
@@ -362,19 +378,19 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360V
         rin.means_out[3 * (size_t)g] = mn[0]; rin.means_out[3 * (size_t)g + 1] = mn[1]; rin.means_out[3 * (size_t)g + 2] = mn[2];
         const float dx = mn[0] * sc - vw.campos[0], dy = mn[1] * sc - vw.campos[1], dz = mn[2] * sc - vw.campos[2];
         const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-        s_dir[l] = make_float4(dx * inv, dy * inv, dz * inv, sc * inv);
+        s_dir[l] = make_float4(dx * inv, dy * inv, dz * inv, DEG == 4 ? sc * inv : inv);
     }
     // (Measured and dropped: wave 1's covariance chain in front of the barrier too, its seven geometry words loaded straight from
     // global memory — the non-temporal staging lines are not retained, FETCH_SIZE +113 MB, 98 us instead of 92.)
     float depth = 0.f;
     if (d == 1 && live) depth = rin.depths[g];
     __syncthreads();      // the staged records, the view directions
-    float* slab = s_raw + l * RAW_C + 7;     // [3][25] channel-major coefficients of this lane's Gaussian
+    float* slab = s_raw + l * RAW_C + 7;     // [3][N] channel-major coefficients of this lane's Gaussian
     float x = 0.f, y = 0.f, z = 1.f;
     if (MFMA) {
         // MFMA form (ROT only): the wave rotates its channel of all 64 records on the matrix cores, in place (every lane takes part:
         // rows of a partial block compute on stale LDS words and are never read); the colour sum then reads the harmonics back
-        sh_rotate_coefs25_mfma(rin.sh_rot + (size_t)v * 625, s_raw, d, l);
+        sh_rotate_coefs25_mfma(rin.sh_rot + (size_t)v * (N * N), s_raw, d, l);
         __syncthreads();  // the three channels' harmonics (also orders this wave's own LDS writes before its reads below)
         if (live) {
             const float4 dr = s_dir[l];
@@ -391,29 +407,29 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360V
         const float4 dr = s_dir[l];
         x = dr.x; y = dr.y; z = dr.z;
         // channel d: harmonics = D (mask . raw), the adapter kernel's own expression
-        const float* D = ROT ? rin.sh_rot + (size_t)v * 625 : nullptr;
-        float c[25], h[25];
+        const float* D = ROT ? rin.sh_rot + (size_t)v * (N * N) : nullptr;
+        float c[N], h[N];
 #pragma unroll
-        for (int k = 0; k < 25; ++k) c[k] = slab[25 * d + k];
-        sh_rotate_coefs25<ROT>(D, c, h);
+        for (int k = 0; k < N; ++k) c[k] = slab[N * d + k];
+        sh_rotate_coefs<DEG, ROT>(D, c, h);
         float Y[25];
-        sh_basis(4, x, y, z, Y);
+        sh_basis(DEG, x, y, z, Y);
         float acc = 0.f;
 #pragma unroll
-        for (int k = 0; k < 25; ++k) acc += Y[k] * h[k];     // k_sh_eval3_jac's sum, term for term
+        for (int k = 0; k < N; ++k) acc += Y[k] * h[k];     // k_sh_eval3_jac's sum (below degree 4: k_sh_eval's), term for term
         s_rgb[3 * l + d] = acc + 0.5f;
         if (JAC) {
 #pragma unroll
-            for (int k = 0; k < 25; ++k) slab[25 * d + k] = h[k];   // in place: only wave d ever touched these 25 words
+            for (int k = 0; k < N; ++k) slab[N * d + k] = h[k];   // in place: only wave d ever touched these N words
         }
     }
     if (JAC) {
         if (!MFMA) __syncthreads();  // the three channels' harmonics
         if (live) {
             float G[3];
-            if (d == 0) sh_jac_component<0>(x, y, z, slab, G);     // wave-uniform: each wave compiles ONE derivative component
-            else if (d == 1) sh_jac_component<1>(x, y, z, slab, G);
-            else sh_jac_component<2>(x, y, z, slab, G);
+            if (d == 0) sh_jac_component<0, DEG>(x, y, z, slab, G);     // wave-uniform: each wave compiles ONE derivative component
+            else if (d == 1) sh_jac_component<1, DEG>(x, y, z, slab, G);
+            else sh_jac_component<2, DEG>(x, y, z, slab, G);
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) s_G[(3 * ch + d) * SHE3_G + l] = G[ch];
         }
@@ -456,9 +472,15 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360V
             const float4 dr = s_dir[gl];
             const float dot = dr.x * G0 + dr.y * G1 + dr.z * G2;
             float* o = sh_jac + 3 * ((size_t)g0 * 3 + tid);
-            o[0] = (G0 - dr.x * dot) * dr.w;
-            o[1] = (G1 - dr.y * dot) * dr.w;
-            o[2] = (G2 - dr.z * dot) * dr.w;
+            if (DEG == 4) {
+                o[0] = (G0 - dr.x * dot) * dr.w;
+                o[1] = (G1 - dr.y * dot) * dr.w;
+                o[2] = (G2 - dr.z * dot) * dr.w;
+            } else {   // k_sh_eval's rounding: dr.w = inv
+                o[0] = sc * ((G0 - dr.x * dot) * dr.w);
+                o[1] = sc * ((G1 - dr.y * dot) * dr.w);
+                o[2] = sc * ((G2 - dr.z * dot) * dr.w);
+            }
         }
     }
     if (tid < nb) {
@@ -2829,13 +2851,23 @@ static int forward_impl(const S360Params* prm, const S360View* views, const floa
                 // workgroups are dealt per context view (grid.y): pose and SH rotation matrix are wave-uniform
                 const dim3 rgrid((rin.Gv + SHE3_G - 1) / SHE3_G, (unsigned)(kp.P / rin.Gv));
                 const bool rot = rin.sh_rot != nullptr;
-#define S360_RAWE(J, R, M) hipLaunchKernelGGL((k_raw_eval<J, R, M>), rgrid, dim3(SHE3_G * 3), 0, st, kp, views, rin, rgbc, sh_jac, zero_ptr, zero_words)
+#define S360_RAWE(J, R, M, DG) hipLaunchKernelGGL((k_raw_eval<J, R, M, DG>), rgrid, dim3(SHE3_G * 3), 0, st, kp, views, rin, rgbc, sh_jac, zero_ptr, zero_words)
+#define S360_RAWE_DEG(DG) do { if (jac) { if (rot) S360_RAWE(true, true, false, DG); else S360_RAWE(true, false, false, DG); } \
+                               else { if (rot) S360_RAWE(false, true, false, DG); else S360_RAWE(false, false, false, DG); } } while (0)
                 // S360_RAW_MFMA=1: the coefficient rotation on the matrix cores (v_mfma_f32_16x16x4_f32) instead of SGPR-operand
-                // multiply-adds — same bits; measured side by side in DESIGN.md section 6
+                // multiply-adds — same bits; measured side by side in DESIGN.md section 6.  A degree-4 experiment: at degrees 0..3 the
+                // switch is ignored and the SGPR form runs.
                 static const bool raw_mfma = [] { const char* e = getenv("S360_RAW_MFMA"); return e && e[0] == '1'; }();
-                if (rot && raw_mfma) { if (jac) S360_RAWE(true, true, true); else S360_RAWE(false, true, true); }
-                else if (jac) { if (rot) S360_RAWE(true, true, false); else S360_RAWE(true, false, false); }
-                else { if (rot) S360_RAWE(false, true, false); else S360_RAWE(false, false, false); }
+                switch (prm->sh_degree) {   // s360_forward_raw admitted 0..4 with M == (degree + 1)^2
+                    case 0: S360_RAWE_DEG(0); break;
+                    case 1: S360_RAWE_DEG(1); break;
+                    case 2: S360_RAWE_DEG(2); break;
+                    case 3: S360_RAWE_DEG(3); break;
+                    default:
+                        if (rot && raw_mfma) { if (jac) S360_RAWE(true, true, true, 4); else S360_RAWE(false, true, true, 4); }
+                        else S360_RAWE_DEG(4);
+                }
+#undef S360_RAWE_DEG
 #undef S360_RAWE
             } else if (chm && kp.M == 25 && kp.deg == 4) {  // the reference's harmonics: one lane per (Gaussian, channel)
                 const int nb3 = (kp.P + SHE3_G - 1) / SHE3_G;
@@ -3005,7 +3037,7 @@ extern "C" int s360_forward_raw(const S360Params* prm, const S360View* views, co
     if (!prm || !raw || !means_out || !cov6_out) return S360_E_BADARG;
     if (!(prm->flags & S360_FLAG_RAW_INPUTS) || !(prm->flags & S360_FLAG_SHARED_CAMPOS) || (prm->flags & (S360_FLAG_COV9 | S360_FLAG_SPHERICAL)))
         return S360_E_BADARG;   // one camera centre per call; the geometry pass reads the 6-entry covariances this call writes
-    if (prm->M != 25 || prm->sh_degree != 4) return S360_E_UNSUPPORTED;   // the reference's configuration (costvolume.yaml:16)
+    if (const int rc = s360_raw_degree_check(prm)) return rc;   // degrees 0..4 with M == (sh_degree + 1)^2 (the reference: 4, costvolume.yaml:16)
     if (prm->P > 0 && (!raw->extrinsics || !raw->depths || !raw->raw_gaussians)) return S360_E_BADARG;
     if (raw->n_views < 0 || raw->per_view < 0 || raw->H < 1 || raw->W < 1 || raw->per_ray < 1 ||
         (long long)raw->n_views * raw->per_view != (long long)prm->P || (long long)raw->H * raw->W * raw->per_ray != (long long)raw->per_view)

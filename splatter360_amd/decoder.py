@@ -319,7 +319,8 @@ class DecoderSplattingFused(torch.nn.Module):
         packed = {(i, e.start): allv[i, e] for i, e in groups}
         # Gaussians whose means / covariances / harmonics are still lazy.LazyFields of one adapter call (splatter360_amd.install(adapter=True)
         # replaced the reference's GaussianAdapterERP): groups of views sharing a camera centre are rendered straight from the encoder's
-        # raw outputs (s360_forward_raw / s360_backward_raw) — the [G,3,25] harmonics and [G,3,3] covariances are never materialised.
+        # raw outputs (s360_forward_raw / s360_backward_raw) — the [G,3,d_sh] harmonics and [G,3,3] covariances are never materialised
+        # (bundle_of reads d_sh from the bundle's records: every SH degree the adapter class hands out lazy fields for).
         # Any other group indexes the fields, which materialises them once with the stand-alone adapter kernels.
         from . import lazy as _lazy
         bundle = _lazy.bundle_of(gaussians)

@@ -14,7 +14,9 @@ stays lazy; ANY other operation first materialises the field with the stand-alon
 cached in the bundle, autograd-connected to the encoder's outputs) and then runs on the real tensor — every other consumer of the
 Gaussians (ply export, visualisation, a different decoder) sees ordinary tensors with the reference's values.  The fused decoder
 (decoder.DecoderSplattingFused, registered by install()) recognises untouched LazyFields (`bundle_of`) and calls
-rasterizer.rasterize_raw on the bundle's raw tensors instead: neither harmonics nor covariances ever exist.
+rasterizer.rasterize_raw on the bundle's raw tensors instead: neither harmonics nor covariances ever exist.  This holds at every
+SH degree of RAW_SEAM_DEGREES (d_sh = (sh_degree + 1)^2 coefficients per channel, raw records of 7 + 3 d_sh floats; the reference's
+configuration is degree 4: [.,3,25] harmonics, 82-float records).
 """
 from __future__ import annotations
 
@@ -26,11 +28,17 @@ from torch import Tensor
 
 from . import adapter as _adapter
 
+# The seam table: the SH degrees at which the adapter class hands out lazy fields, so that the fused decoder renders from the raw
+# records (rasterizer.rasterize_raw).  A degree is listed when the raw path is not slower than the two-step path (adapter kernels,
+# then render) beyond the run-to-run spread of scripts/raw_degrees_timing.py (profiles/raw_degrees_timing.json); at any other degree
+# the class keeps the eager adapter, and rasterize_raw stays available to a caller who asks for it directly.
+RAW_SEAM_DEGREES = (0, 1, 2, 3, 4)
+
 _FIELDS = {"means": (3,), "covariances": (3, 3), "scales": (3,), "rotations": (4,), "harmonics": None}
 
 
 class RawBundle:
-    """The adapter's inputs, kept instead of its outputs.  depths / opacities [b, v, r, srf, spp]; raw [b, v, r, srf, spp or 1, 82];
+    """The adapter's inputs, kept instead of its outputs.  depths / opacities [b, v, r, srf, spp]; raw [b, v, r, srf, spp or 1, 7 + 3 d_sh];
     extrinsics [b, v, 4, 4] (context panoramas, camera-to-world)."""
 
     def __init__(self, module, dataset_name, extrinsics, depths, opacities, raw, image_shape, eps):
@@ -49,8 +57,13 @@ class RawBundle:
     def per_ray(self) -> int:
         return self.shape5[3] * self.shape5[4]
 
+    @property
+    def d_sh(self) -> int:
+        """Coefficients per colour channel of the raw records (7 + 3 * d_sh floats each): 1, 4, 9, 16 or 25."""
+        return (int(self.raw.shape[-1]) - 7) // 3
+
     def sh_rotation(self) -> Optional[Tensor]:
-        """[b * v, 25, 25] matrices of rotate_sh for the context views (None: identity), built once per bundle."""
+        """[b * v, d_sh, d_sh] matrices of rotate_sh for the context views (None: identity), built once per bundle."""
         if self._rot is None:
             b, v = self.shape5[:2]
             self._rot = (self.module.rotation_blocks(self.extrinsics.reshape(b * v, 4, 4)),)
@@ -137,9 +150,10 @@ def _identity_permutation(name, args, kwargs, nd) -> bool:
         return False
 
 
-def bundle_of(gaussians, d_sh: int = 25) -> Optional[RawBundle]:
+def bundle_of(gaussians, d_sh: Optional[int] = None) -> Optional[RawBundle]:
     """The RawBundle behind a Gaussians container whose means / covariances / harmonics are UNTOUCHED LazyFields of one adapter call
-    in the reference's flat layout ([b, G, 3], [b, G, 3, 3], [b, G, 3, 25]: src/model/types.py:7-12), else None."""
+    in the reference's flat layout ([b, G, 3], [b, G, 3, 3], [b, G, 3, d_sh]: src/model/types.py:7-12), else None.  d_sh is read from
+    the bundle's own raw records (7 + 3 * d_sh floats each) unless the caller names one."""
     try:
         m, c, h = gaussians.means, gaussians.covariances, gaussians.harmonics
     except AttributeError:
@@ -151,6 +165,8 @@ def bundle_of(gaussians, d_sh: int = 25) -> Optional[RawBundle]:
         return None
     b = bd.shape5[0]
     g = math.prod(bd.shape5[1:])
+    if d_sh is None:
+        d_sh = bd.d_sh
     if tuple(m.shape) != (b, g, 3) or tuple(c.shape) != (b, g, 3, 3) or tuple(h.shape) != (b, g, 3, d_sh):
         return None
     op = gaussians.opacities
@@ -203,7 +219,7 @@ def make_adapter_class(base_cls=None, container_cls=None, *, sh_rotation="native
             if dataset_name not in _adapter.ERP_CONVENTIONS:
                 raise Exception(f"no ERP convention for dataset {dataset_name!r} (src/geometry/utils360.py raises for it too)")
             d_sh = (int(self.cfg.sh_degree) + 1) ** 2
-            if not self.s360_lazy or d_sh != 25 or depths.dim() != 5:
+            if not self.s360_lazy or int(self.cfg.sh_degree) not in RAW_SEAM_DEGREES or depths.dim() != 5:
                 g = self.forward_eager(dataset_name, extrinsics, depths, opacities, raw_gaussians, image_shape, eps)
                 return container(means=g.means, covariances=g.covariances, scales=g.scales, rotations=g.rotations, harmonics=g.harmonics,
                                  opacities=g.opacities)

@@ -436,6 +436,8 @@ class _Options(NamedTuple):
     differentiable_means: bool = False
 
 
+RAW_D_SH = (1, 4, 9, 16, 25)    # coefficients per channel of a raw record at SH degrees 0..4 (index = degree): records of 7 + 3 * d_sh floats
+
 _NO_LOSS = SimpleNamespace(target=None, grad_scale=0.0, d_images=None, partials=None, out=None)
 _last = SimpleNamespace(state=None, deferred=None, holder=None)     # of the most recent call: last_state(), last_deferred(), deferred_of()
 
@@ -698,11 +700,26 @@ class _RasterizeViews(torch.autograd.Function):
         return d_m3, d_m2, d_sh, d_col, d_op.view(-1, 1), d_c6, None, None, None
 
 
+def _raw_record_d_sh(raw: Tensor, sh_rot: Optional[Tensor], n_views: int) -> int:
+    """d_sh of raw records [..., 7 + 3 d_sh] (shapes only: no device work); RuntimeError for a width no SH degree 0..4 has, or an
+    sh_rotation that is not [n_views, d_sh, d_sh]."""
+    width = int(raw.shape[-1]) if raw.dim() else 0
+    d_sh = (width - 7) // 3
+    if d_sh not in RAW_D_SH or width != 7 + 3 * d_sh:
+        raise RuntimeError(f"rasterize_raw: raw_gaussians has {width} floats per record; the allowed widths are "
+                           f"{', '.join(str(7 + 3 * n) for n in RAW_D_SH)} (7 + 3 * d_sh, d_sh = (sh_degree + 1)^2 for SH degrees 0..4)")
+    if sh_rot is not None and tuple(sh_rot.shape) != (n_views, d_sh, d_sh):
+        raise RuntimeError(f"rasterize_raw: sh_rotation must be [{n_views}, {d_sh}, {d_sh}] for {width}-float records "
+                           f"(d_sh = {d_sh}), got {list(sh_rot.shape)}")
+    return d_sh
+
+
 class _RasterizeRaw(torch.autograd.Function):
     """The adapter tail fused into the rasteriser (s360_forward_raw / s360_backward_raw): from the encoder's raw
     outputs (depths, opacities, raw_gaussians of the context panoramas) to the rendered views of ONE target camera centre, without
-    the [G,3,25] harmonics / [G,3,3] covariances the two-step path (adapter.adapter_tail, then rasterize_views) writes and reads
-    back, and without the [G,3,25] dL/dSH round trip in the backward.  Differentiable w.r.t. depths, opacities, raw_gaussians."""
+    the [G,3,d_sh] harmonics / [G,3,3] covariances the two-step path (adapter.adapter_tail, then rasterize_views) writes and reads
+    back, and without the [G,3,d_sh] dL/dSH round trip in the backward, at SH degrees 0..4 (d_sh = 1, 4, 9, 16, 25: the raw records
+    are 7 + 3 d_sh floats wide).  Differentiable w.r.t. depths, opacities, raw_gaussians."""
 
     @staticmethod
     def forward(ctx, depths, opacities, raw, ctx_extrinsics, sh_rot, views, opt: _Options, rin: _lib.S360RawInputs, mse_target=None):
@@ -717,10 +734,13 @@ class _RasterizeRaw(torch.autograd.Function):
             vw = _f32c(views, "views")
             nv = int(ext.shape[0])
             p, v = int(dep.shape[0]), int(vw.shape[0])
-            if rw.shape[-1] != 82 or rw.numel() != p * 82 or p % max(nv, 1) or (p // max(nv, 1)) != rin.H * rin.W * rin.per_ray:
-                raise RuntimeError("rasterize_raw: raw_gaussians must be [views * h * w * per_ray, 82] (degree-4 harmonics) matching depths / extrinsics")
+            d_sh = _raw_record_d_sh(rw, rot, nv)
+            width = 7 + 3 * d_sh
+            if rw.numel() != p * width or p % max(nv, 1) or (p // max(nv, 1)) != rin.H * rin.W * rin.per_ray:
+                raise RuntimeError(f"rasterize_raw: raw_gaussians must be [views * h * w * per_ray, {width}] matching depths / extrinsics")
+            opt = opt._replace(sh_degree=RAW_D_SH.index(d_sh))      # the record's width decides the degree: M == (sh_degree + 1)^2
             prm = _params(dev, p, v, opt, any(ctx.needs_input_grad[:3]), mse_target is not None,
-                          _lib.FLAG_SHARED_CAMPOS | _lib.FLAG_RAW_INPUTS, sh=25)
+                          _lib.FLAG_SHARED_CAMPOS | _lib.FLAG_RAW_INPUTS, sh=d_sh)
             loss = _loss_setup(mse_target, v, opt)
             # (rasterize_raw filled in the geometry; the tensors are saved below, so the record still holds in the backward)
             rin.extrinsics, rin.depths, rin.raw_gaussians = ext.data_ptr(), dep.data_ptr(), rw.data_ptr()
@@ -749,7 +769,7 @@ class _RasterizeRaw(torch.autograd.Function):
             d_op = torch.empty((p,), dtype=torch.float32, device=dev)
             d_rgb = torch.empty((p, 4), dtype=torch.float32, device=dev)
             d_dep = torch.empty((p,), dtype=torch.float32, device=dev)
-            d_raw = torch.empty((p, 82), dtype=torch.float32, device=dev)
+            d_raw = torch.empty((p, 7 + 3 * prm.M), dtype=torch.float32, device=dev)
             bws = torch.empty(lay.backward_bytes, dtype=torch.uint8, device=dev)
             stream = _call.stream(dev)
             if ctx.exchange is not None:
@@ -889,8 +909,9 @@ def rasterize_raw(depths: Tensor, opacities: Tensor, raw_gaussians: Tensor, cont
                   mse_target: Optional[Tensor] = None, mse_weight: float = 1.0, mse_count: Optional[int] = None, lean: Optional[bool] = None,
                   mse_defer: bool = False, split_lists: Optional[bool] = None, exchange=None):
     """Render V views sharing one camera centre ([V,44] packed) straight from the encoder's raw outputs: depths / opacities [n*h*w*per_ray]
-    (view-major, ray-major), raw_gaussians [same, 82] (3 scale logits, quaternion xyzw, 3 x 25 SH coefficients), context_extrinsics
-    [n,4,4], sh_rotation [n,25,25] (adapter.sh_rotation_blocks) or None.  = adapter.adapter_tail(...) followed by rasterize_views(...)
+    (view-major, ray-major), raw_gaussians [same, 7 + 3 d_sh] (3 scale logits, quaternion xyzw, 3 x d_sh SH coefficients; d_sh = 1, 4, 9,
+    16 or 25 = SH degree 0..4, read off the record's width: 10, 19, 34, 55 or 82 floats), context_extrinsics [n,4,4], sh_rotation
+    [n,d_sh,d_sh] (adapter.sh_rotation_blocks) or None.  = adapter.adapter_tail(...) followed by rasterize_views(...)
     on its result, in fewer bytes: see _RasterizeRaw.  Returns (images[V,3,H,W], means[P,3], cov6[P,6]) (+ depth maps, + FusedMse as
     in rasterize_views).  Gradients flow to depths, opacities and raw_gaussians; the means are detached like the reference's unless
     differentiable_means.  exchange=distributed.ExchangeConfig(...): multi-GPU — every rank renders its own target panorama of the same
@@ -898,6 +919,7 @@ def rasterize_raw(depths: Tensor, opacities: Tensor, raw_gaussians: Tensor, cont
     rasterize_views, with k_raw_bwd fed the N ranks' dL/dRGB factors)."""
     if depth_mode is not None and depth_mode not in DEPTH_MODES:
         raise ValueError(f"depth_mode must be one of {sorted(DEPTH_MODES)}")
+    _raw_record_d_sh(raw_gaussians, sh_rotation, int(context_extrinsics.numel()) // 16)   # shape errors first, whatever the device
     ch, cw = context_shape
     opt = _Options(h=image_height, w=image_width, lean=LEAN_LISTS if lean is None else bool(lean),
                    split_lists=SPLIT_LONG_LISTS if split_lists is None else (split_lists if split_lists == "auto" else bool(split_lists)),
