@@ -261,6 +261,19 @@ typedef struct S360RawInputs {
     float scale_min, scale_max, eps;
 } S360RawInputs;
 
+/*
+ * Where the raw words lie when the encoder's last convolution output is read in place (the *_planes entry points): channel planes
+ * [n_views, C_total, H, W] instead of records.  Strides in FLOATS; word c of Gaussian gi (gi = ray * per_ray + surface) of view v is at
+ *     raw_gaussians + v * view_stride + (gi % per_ray) * surface_stride + c * channel_stride + gi / per_ray
+ * (ray stride 1); raw_gaussians / d_raw_gaussians point at word 0 of view 0, surface 0, ray 0 — channels in front of the record (the
+ * reference's two offset_xy channels) are skipped by the caller's pointer, never by the kernels.
+ */
+typedef struct S360RawPlanes {
+    int64_t view_stride;        /* >= (per_ray - 1) * surface_stride + (7 + 3*M - 1) * channel_stride + H*W */
+    int64_t surface_stride;     /* >= (7 + 3*M) * channel_stride when per_ray > 1 (ignored when per_ray == 1) */
+    int64_t channel_stride;     /* >= H*W */
+} S360RawPlanes;
+
 /* ABI version of the loaded library (== S360_ABI_VERSION). */
 int s360_abi_version(void);
 const char* s360_error_string(int code);
@@ -483,6 +496,30 @@ int s360_backward_raw(const S360Params* prm, const S360View* views, const S360Ra
 int s360_backward_raw_tail(const S360Params* prm, const S360View* group_views, int32_t n_groups, const S360RawInputs* raw,
                            const float* means, const void* workspace, size_t workspace_bytes, const float* d_means3D,
                            const float* d_cov6, const float* d_rgb_sums, float* d_depths, float* d_raw_gaussians, void* stream);
+/*
+ * The three raw entry points with the raw words read, and their gradient written, as CHANNEL PLANES (S360RawPlanes above) — the
+ * layout the reference's encoder leaves them in ("(v b) c h w" out of its last convolution, depth_predictor_multiview_360.py:672-674):
+ * raw->raw_gaussians and d_raw_gaussians are addressed through `planes`, everything else is the record entry's argument, rule and
+ * result, bit for bit (the kernels differ in their staging loads and their last stores only).  d_raw_gaussians: the kernel writes the
+ * 7 + 3*M gradient words of every one of the P records at the addresses above and nothing else — channels the records do not cover,
+ * and padding between views, belong to the caller (zero them, or not).  S360_E_BADARG before any GPU work for planes == NULL,
+ * channel_stride < H*W, surface_stride < (7 + 3*M) * channel_stride with per_ray > 1, or a view_stride below the extent of one view's
+ * per_ray surfaces; otherwise the record entries' own answers.  The S360_RAW_MFMA=1 experiment rotates records and has no plane form:
+ * s360_forward_raw_planes answers S360_E_UNSUPPORTED under it.
+ */
+int s360_forward_raw_planes(const S360Params* prm, const S360View* views, const S360RawInputs* raw, const S360RawPlanes* planes,
+                            const float* opacities, float* means_out, float* cov6_out, float* images, float* depth_maps,
+                            int32_t depth_mode, int32_t* radii, const float* target, float grad_scale, float* d_images, float* partials,
+                            float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
+int s360_backward_raw_planes(const S360Params* prm, const S360View* views, const S360RawInputs* raw, const S360RawPlanes* planes,
+                             const float* means, const float* cov6, const float* opacities, const void* workspace, size_t workspace_bytes,
+                             const float* dL_dimages, const float* dL_dimages_scale, const float* dL_ddepth, int32_t depth_mode,
+                             int32_t differentiable_means, float* d_means3D, float* d_cov6, float* d_opacities, float* d_rgb_sum,
+                             float* d_depths, float* d_raw_gaussians, void* bwd_workspace, size_t bwd_workspace_bytes, void* stream);
+int s360_backward_raw_tail_planes(const S360Params* prm, const S360View* group_views, int32_t n_groups, const S360RawInputs* raw,
+                                  const S360RawPlanes* planes, const float* means, const void* workspace, size_t workspace_bytes,
+                                  const float* d_means3D, const float* d_cov6, const float* d_rgb_sums, float* d_depths,
+                                  float* d_raw_gaussians, void* stream);
 int s360_sh_rotation_blocks(const float* rotations, int32_t row_major_stride, int32_t n_views, int32_t d_sh,
                             float* sh_rotation_out, void* stream);
 int s360_adapter_forward(const float* extrinsics, const float* depths, const float* raw_gaussians,

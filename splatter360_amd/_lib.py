@@ -63,8 +63,13 @@ class S360RawInputs(C.Structure):
                 ("erp_convention", C.c_int32), ("scale_min", C.c_float), ("scale_max", C.c_float), ("eps", C.c_float)]
 
 
+class S360RawPlanes(C.Structure):
+    """include/s360.h S360RawPlanes: where the raw words lie as channel planes (strides in floats)."""
+    _fields_ = [("view_stride", C.c_int64), ("surface_stride", C.c_int64), ("channel_stride", C.c_int64)]
+
+
 _int, _i32, _i64, _sz, _f32, _vp = C.c_int, C.c_int32, C.c_int64, C.c_size_t, C.c_float, C.c_void_p
-_prm, _raw = C.POINTER(S360Params), C.POINTER(S360RawInputs)
+_prm, _raw, _pln = C.POINTER(S360Params), C.POINTER(S360RawInputs), C.POINTER(S360RawPlanes)
 _p32, _p64, _psz, _pf64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_size_t), C.POINTER(C.c_double)
 
 # Every function include/s360.h declares: name -> (restype, argtypes).  lib() applies it; tests/test_abi.py holds it to the header.
@@ -86,6 +91,9 @@ SIGNATURES = {
     "s360_forward_raw": (_int, [_prm, _vp, _raw] + [_vp] * 5 + [_i32, _vp, _vp, _f32] + [_vp] * 4 + [_sz, _vp]),
     "s360_backward_raw_tail": (_int, [_prm, _vp, _i32, _raw, _vp, _vp, _sz] + [_vp] * 6),
     "s360_backward_raw": (_int, [_prm, _vp, _raw] + [_vp] * 4 + [_sz] + [_vp] * 3 + [_i32, _i32] + [_vp] * 7 + [_sz, _vp]),
+    "s360_forward_raw_planes": (_int, [_prm, _vp, _raw, _pln] + [_vp] * 5 + [_i32, _vp, _vp, _f32] + [_vp] * 4 + [_sz, _vp]),
+    "s360_backward_raw_planes": (_int, [_prm, _vp, _raw, _pln] + [_vp] * 4 + [_sz] + [_vp] * 3 + [_i32, _i32] + [_vp] * 7 + [_sz, _vp]),
+    "s360_backward_raw_tail_planes": (_int, [_prm, _vp, _i32, _raw, _pln, _vp, _vp, _sz] + [_vp] * 6),
     "s360_pack_views": (_int, [_vp] * 5 + [_i32, _i32, _i32, _vp, _vp]),
     "s360_adapter_forward": (_int, [_vp] * 4 + [_i32] * 6 + [_f32] * 3 + [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "s360_adapter_backward": (_int, [_vp] * 4 + [_i32] * 6 + [_f32] * 3 + [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),

@@ -22,6 +22,7 @@
 #include "s360_adapter_math.h"
 
 #include <cstdio>
+#include <type_traits>
 #include <cstdlib>
 
 namespace s360 {
@@ -686,6 +687,11 @@ struct RawBwd {
     int Gv, H, W, per_ray, conv, n_groups;
     float smin, smax, eps;
 };
+// PLANES form (s360_backward_raw_planes / _tail_planes): d_raw is addressed as channel planes (S360RawPlanes: strides in floats).  The
+// record instantiations keep RawBwd itself as their argument.
+struct RawBwdPlanes : RawBwd {
+    long long view_stride, surface_stride, channel_stride;
+};
 
 // Round 6: workgroups dealt per context view (the view's Wigner-D matrix is wave-uniform: scalar loads, SGPR operands — round 5 read it
 // from LDS, one ds_read per multiply-add, on all three waves redundantly); the rotated masked basis is computed ONCE per Gaussian, its
@@ -693,9 +699,14 @@ struct RawBwd {
 // DEG (compile time, 0..4): the gradient record is 7 + 3 (DEG + 1)^2 floats; wave 1 rotates the basis entries k >= sh_split(DEG) and
 // wave 2 those below (s360_adapter_math.h: the top band against the rest at degrees 2..4, everything on wave 1 at degrees 0 and 1).
 // Every sum keeps its fixed order at every degree: ascending groups, no atomics.
-template <bool ROT, int DEG = 4>
-__global__ __launch_bounds__(192) void k_raw_bwd(KParams kp, const S360View* __restrict__ views, RawBwd rb) {
+// PLANES (compile time): the gradient record is assembled as s_out[c][lane] (word stride LS = 64: the lanes' writes fall on 64 different
+// banks) and stored channel by channel at d_raw + v view_stride + (gi % per_ray) surface_stride + c channel_stride + gi / per_ray — 256 B
+// per wave and channel, 16 bytes per lane where that address is 16-byte aligned (per_ray = 1, a full block), word by word otherwise.
+// Only the record's 7 + 3 N words of live Gaussians are written.  Everything in front of the store is the record form's code.
+template <bool ROT, int DEG = 4, bool PLANES = false>
+__global__ __launch_bounds__(192) void k_raw_bwd(KParams kp, const S360View* __restrict__ views, std::conditional_t<PLANES, RawBwdPlanes, RawBwd> rb) {
     constexpr int N = (DEG + 1) * (DEG + 1), RAWB_C = 7 + 3 * N, SPLIT = sh_split(DEG);
+    constexpr int LS = PLANES ? 64 : 1;      // LDS words between consecutive words of one Gaussian's gradient record
     __shared__ __attribute__((aligned(16))) float s_out[64 * RAWB_C];
     __shared__ float s_yp[N * 64];       // (mask . D^T Y)[k] of lane l at [k * 64 + l]
     __shared__ float4 s_w[64];           // the group's dL/dRGB (0 where the Gaussian is invisible in the group's views)
@@ -773,13 +784,13 @@ __global__ __launch_bounds__(192) void k_raw_bwd(KParams kp, const S360View* __r
         for (int k = 0; k < 4; ++k) dq[k] += da * qg.q[k];
         const float dot = qr[0] * dq[0] + qr[1] * dq[1] + qr[2] * dq[2] + qr[3] * dq[3];
         const float f = qg.n > 0.f ? dot / (qg.n * qg.m * qg.m) : 0.f;
-        float* orec = s_out + l * RAWB_C;
+        float* orec = PLANES ? s_out + l : s_out + l * RAWB_C;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) orec[3 + k] = dq[k] / qg.m - qr[k] * f;
+        for (int k = 0; k < 4; ++k) orec[(3 + k) * LS] = dq[k] / qg.m - qr[k] * f;
         float dd = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            orec[k] = ds[k] * depth * px * (rb.smax - rb.smin) * sig[k] * (1.0f - sig[k]);
+            orec[k * LS] = ds[k] * depth * px * (rb.smax - rb.smin) * sig[k] * (1.0f - sig[k]);
             dd += ds[k] * base[k] * px;
         }
         if (rb.d_means) {   // opt-in: the reference's means are detached (sphere_projection.py:14-86)
@@ -834,12 +845,32 @@ __global__ __launch_bounds__(192) void k_raw_bwd(KParams kp, const S360View* __r
             for (int k = 0; k < N; ++k) acc[k] = __builtin_fmaf(s_yp[k * 64 + l], w, acc[k]);
         }
         if (live) {
-            float* orec = s_out + l * RAWB_C + 7 + N * d;
+            float* orec = PLANES ? s_out + (7 + N * d) * 64 + l : s_out + l * RAWB_C + 7 + N * d;
 #pragma unroll
-            for (int k = 0; k < N; ++k) orec[k] = acc[k];
+            for (int k = 0; k < N; ++k) orec[k * LS] = acc[k];
         }
     }
     __syncthreads();
+    if constexpr (PLANES) {
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        float* vbase = rb.d_raw + (size_t)v * rb.view_stride;
+        if (rb.per_ray == 1 && nb == 64) {
+            // item = (channel c, quad qd): Gaussians gi0 + 4 qd .. + 3 of channel c; 16 consecutive lanes store one channel's 256 bytes
+            for (int it = tid; it < RAWB_C * 16; it += 192) {
+                float* p = vbase + (size_t)(it >> 4) * rb.channel_stride + gi0 + 4 * (it & 15);
+                const f4v t = reinterpret_cast<const f4v*>(s_out)[it];      // words c * 64 + 4 qd .. + 3
+                if ((((uintptr_t)p) & 15) == 0) __builtin_nontemporal_store(t, reinterpret_cast<f4v*>(p));
+                else { p[0] = t.x; p[1] = t.y; p[2] = t.z; p[3] = t.w; }
+            }
+        } else {
+            for (int i = tid; i < RAWB_C * 64; i += 192) {
+                const int c = i >> 6, gi = gi0 + (i & 63);
+                if ((i & 63) < nb)
+                    vbase[(size_t)(gi % rb.per_ray) * rb.surface_stride + (size_t)c * rb.channel_stride + gi / rb.per_ray] = s_out[i];
+            }
+        }
+        return;
+    }
     const int nfl = nb * RAWB_C;
     float* dst = rb.d_raw + (size_t)g0 * RAWB_C;
     if ((((uintptr_t)dst) & 15) == 0) {
@@ -1416,7 +1447,7 @@ extern "C" int s360_count_contributions(const S360Params* prm, const void* works
 // centre: one for a single-GPU call, one per rank after the multi-GPU exchange) -> dL/d(raw record), dL/ddepth
 static int raw_tail(const S360Params* prm, const S360View* views, int n_groups, const S360RawInputs* raw, const float* means, const void* workspace,
                     const float* d_means_or_null, const float* d_cov6, const float* d_rgb_sums, float* d_depths, float* d_raw_gaussians,
-                    void* stream_) {
+                    void* stream_, const S360RawPlanes* planes = nullptr) {
     S360Layout L;
     const int rc = s360_layout(prm, &L);
     if (rc) return rc;
@@ -1432,6 +1463,21 @@ static int raw_tail(const S360Params* prm, const S360View* views, int n_groups, 
         const dim3 bgrid((rb.Gv + 63) / 64, (unsigned)(prm->P / rb.Gv));   // per context view: its rotation matrix is wave-uniform
 #define S360_RAWB(DG) do { if (rb.sh_rot) hipLaunchKernelGGL((k_raw_bwd<true, DG>), bgrid, dim3(192), 0, (hipStream_t)stream_, kp, views, rb); \
                            else hipLaunchKernelGGL((k_raw_bwd<false, DG>), bgrid, dim3(192), 0, (hipStream_t)stream_, kp, views, rb); } while (0)
+        if (planes) {   // the *_planes entries: the same kernel with the plane store
+            RawBwdPlanes rpl;
+            static_cast<RawBwd&>(rpl) = rb;
+            rpl.view_stride = planes->view_stride; rpl.surface_stride = planes->surface_stride; rpl.channel_stride = planes->channel_stride;
+#define S360_RAWBP(DG) do { if (rb.sh_rot) hipLaunchKernelGGL((k_raw_bwd<true, DG, true>), bgrid, dim3(192), 0, (hipStream_t)stream_, kp, views, rpl); \
+                            else hipLaunchKernelGGL((k_raw_bwd<false, DG, true>), bgrid, dim3(192), 0, (hipStream_t)stream_, kp, views, rpl); } while (0)
+            switch (prm->sh_degree) {
+                case 0: S360_RAWBP(0); break;
+                case 1: S360_RAWBP(1); break;
+                case 2: S360_RAWBP(2); break;
+                case 3: S360_RAWBP(3); break;
+                default: S360_RAWBP(4);
+            }
+#undef S360_RAWBP
+        } else
         switch (prm->sh_degree) {
             case 0: S360_RAWB(0); break;
             case 1: S360_RAWB(1); break;
@@ -1445,17 +1491,23 @@ static int raw_tail(const S360Params* prm, const S360View* views, int n_groups, 
     return S360_OK;
 }
 
-extern "C" int s360_backward_raw(const S360Params* prm, const S360View* views, const S360RawInputs* raw, const float* means, const float* cov6,
-                                 const float* opacities, const void* workspace, size_t workspace_bytes, const float* dL_dimages,
-                                 const float* dL_dimages_scale, const float* dL_ddepth, int32_t depth_mode, int32_t differentiable_means,
-                                 float* d_means3D, float* d_cov6, float* d_opacities, float* d_rgb_sum, float* d_depths,
-                                 float* d_raw_gaussians, void* bwd_workspace, size_t bwd_workspace_bytes, void* stream_) {
+// s360_backward_raw and its plane form: `as_planes` decides how d_raw_gaussians is addressed (and that `planes` is checked), nothing else
+static int backward_raw(const S360Params* prm, const S360View* views, const S360RawInputs* raw, const S360RawPlanes* planes, bool as_planes,
+                        const float* means, const float* cov6,
+                        const float* opacities, const void* workspace, size_t workspace_bytes, const float* dL_dimages,
+                        const float* dL_dimages_scale, const float* dL_ddepth, int32_t depth_mode, int32_t differentiable_means,
+                        float* d_means3D, float* d_cov6, float* d_opacities, float* d_rgb_sum, float* d_depths,
+                        float* d_raw_gaussians, void* bwd_workspace, size_t bwd_workspace_bytes, void* stream_) {
     if (!prm || !raw || !means || !cov6 || !d_means3D || !d_cov6 || !d_opacities || !d_rgb_sum || !d_depths || !d_raw_gaussians)
         return S360_E_BADARG;
     if (!(prm->flags & S360_FLAG_RAW_INPUTS) || !(prm->flags & S360_FLAG_SHARED_CAMPOS) || (prm->flags & (S360_FLAG_COV9 | S360_FLAG_SPHERICAL)))
         return S360_E_BADARG;
     if (const int rc = s360_raw_degree_check(prm)) return rc;
     if ((long long)raw->n_views * raw->per_view != (long long)prm->P) return S360_E_BADARG;
+    if (as_planes) {
+        if ((long long)raw->H * raw->W * raw->per_ray != (long long)raw->per_view) return S360_E_BADARG;
+        if (const int rc = s360_raw_planes_check(prm, raw, planes)) return rc;
+    }
     // the rasteriser's own backward without its dL/dSH pass (the s360_backward_split form: per-Gaussian dL/dmean, dL/dcov6, dL/dopacity
     // and the clamp-masked sum of dL/dRGB) ...
     const float* dummy_sh = raw->raw_gaussians;   // never read: views sharing a camera centre take the colour terms from sh_jac
@@ -1465,7 +1517,28 @@ extern "C" int s360_backward_raw(const S360Params* prm, const S360View* views, c
     if (rc || prm->P == 0) return rc;
     // ... then ONE kernel down to the encoder's outputs
     return raw_tail(prm, views, 1, raw, means, workspace, differentiable_means ? d_means3D : (const float*)nullptr, d_cov6, d_rgb_sum, d_depths,
-                    d_raw_gaussians, stream_);
+                    d_raw_gaussians, stream_, as_planes ? planes : nullptr);
+}
+
+extern "C" int s360_backward_raw(const S360Params* prm, const S360View* views, const S360RawInputs* raw, const float* means, const float* cov6,
+                                 const float* opacities, const void* workspace, size_t workspace_bytes, const float* dL_dimages,
+                                 const float* dL_dimages_scale, const float* dL_ddepth, int32_t depth_mode, int32_t differentiable_means,
+                                 float* d_means3D, float* d_cov6, float* d_opacities, float* d_rgb_sum, float* d_depths,
+                                 float* d_raw_gaussians, void* bwd_workspace, size_t bwd_workspace_bytes, void* stream_) {
+    return backward_raw(prm, views, raw, nullptr, false, means, cov6, opacities, workspace, workspace_bytes, dL_dimages, dL_dimages_scale,
+                        dL_ddepth, depth_mode, differentiable_means, d_means3D, d_cov6, d_opacities, d_rgb_sum, d_depths, d_raw_gaussians,
+                        bwd_workspace, bwd_workspace_bytes, stream_);
+}
+
+extern "C" int s360_backward_raw_planes(const S360Params* prm, const S360View* views, const S360RawInputs* raw, const S360RawPlanes* planes,
+                                        const float* means, const float* cov6, const float* opacities, const void* workspace,
+                                        size_t workspace_bytes, const float* dL_dimages, const float* dL_dimages_scale, const float* dL_ddepth,
+                                        int32_t depth_mode, int32_t differentiable_means, float* d_means3D, float* d_cov6, float* d_opacities,
+                                        float* d_rgb_sum, float* d_depths, float* d_raw_gaussians, void* bwd_workspace,
+                                        size_t bwd_workspace_bytes, void* stream_) {
+    return backward_raw(prm, views, raw, planes, true, means, cov6, opacities, workspace, workspace_bytes, dL_dimages, dL_dimages_scale,
+                        dL_ddepth, depth_mode, differentiable_means, d_means3D, d_cov6, d_opacities, d_rgb_sum, d_depths, d_raw_gaussians,
+                        bwd_workspace, bwd_workspace_bytes, stream_);
 }
 
 extern "C" int s360_count_backward_slots(const S360Params* prm, const void* workspace, size_t workspace_bytes, uint64_t* counts, void* stream_) {
@@ -1490,18 +1563,39 @@ extern "C" int s360_count_backward_slots(const S360Params* prm, const void* work
     return S360_OK;
 }
 
-extern "C" int s360_backward_raw_tail(const S360Params* prm, const S360View* group_views, int32_t n_groups, const S360RawInputs* raw,
-                                      const float* means, const void* workspace, size_t workspace_bytes, const float* d_means3D,
-                                      const float* d_cov6, const float* d_rgb_sums, float* d_depths, float* d_raw_gaussians, void* stream_) {
+static int backward_raw_tail(const S360Params* prm, const S360View* group_views, int32_t n_groups, const S360RawInputs* raw,
+                             const S360RawPlanes* planes, bool as_planes,
+                             const float* means, const void* workspace, size_t workspace_bytes, const float* d_means3D,
+                             const float* d_cov6, const float* d_rgb_sums, float* d_depths, float* d_raw_gaussians, void* stream_) {
     if (!prm || !group_views || !raw || !means || !workspace || !d_cov6 || !d_rgb_sums || !d_depths || !d_raw_gaussians || n_groups < 1)
         return S360_E_BADARG;
     if (!(prm->flags & S360_FLAG_RAW_INPUTS) || (prm->flags & (S360_FLAG_COV9 | S360_FLAG_SPHERICAL | S360_FLAG_FORWARD_ONLY))) return S360_E_BADARG;
     if (const int rc = s360_raw_degree_check(prm)) return rc;
     if ((long long)raw->n_views * raw->per_view != (long long)prm->P) return S360_E_BADARG;
+    if (as_planes) {
+        if ((long long)raw->H * raw->W * raw->per_ray != (long long)raw->per_view) return S360_E_BADARG;
+        if (const int rc = s360_raw_planes_check(prm, raw, planes)) return rc;
+    }
     S360Layout L;
     const int rc = s360_layout(prm, &L);
     if (rc) return rc;
     if (workspace_bytes < L.total_bytes) return S360_E_WORKSPACE;
     if (prm->P == 0) return S360_OK;
-    return raw_tail(prm, group_views, n_groups, raw, means, workspace, d_means3D, d_cov6, d_rgb_sums, d_depths, d_raw_gaussians, stream_);
+    return raw_tail(prm, group_views, n_groups, raw, means, workspace, d_means3D, d_cov6, d_rgb_sums, d_depths, d_raw_gaussians, stream_,
+                    as_planes ? planes : nullptr);
+}
+
+extern "C" int s360_backward_raw_tail(const S360Params* prm, const S360View* group_views, int32_t n_groups, const S360RawInputs* raw,
+                                      const float* means, const void* workspace, size_t workspace_bytes, const float* d_means3D,
+                                      const float* d_cov6, const float* d_rgb_sums, float* d_depths, float* d_raw_gaussians, void* stream_) {
+    return backward_raw_tail(prm, group_views, n_groups, raw, nullptr, false, means, workspace, workspace_bytes, d_means3D, d_cov6, d_rgb_sums,
+                             d_depths, d_raw_gaussians, stream_);
+}
+
+extern "C" int s360_backward_raw_tail_planes(const S360Params* prm, const S360View* group_views, int32_t n_groups, const S360RawInputs* raw,
+                                             const S360RawPlanes* planes, const float* means, const void* workspace, size_t workspace_bytes,
+                                             const float* d_means3D, const float* d_cov6, const float* d_rgb_sums, float* d_depths,
+                                             float* d_raw_gaussians, void* stream_) {
+    return backward_raw_tail(prm, group_views, n_groups, raw, planes, true, means, workspace, workspace_bytes, d_means3D, d_cov6, d_rgb_sums,
+                             d_depths, d_raw_gaussians, stream_);
 }

@@ -36,6 +36,19 @@ static inline int s360_raw_degree_check(const S360Params* prm) {
     return prm->M < n ? S360_E_BADARG : (prm->M > n ? S360_E_UNSUPPORTED : S360_OK);
 }
 
+// The *_planes forms of those entry points: the strides must keep the words of one view, one surface and one channel apart (planes of
+// at least H*W floats, a surface's 7 + 3 M planes inside its surface stride, a view's per_ray surfaces inside its view stride).  Host
+// arithmetic, before any GPU work; called after s360_raw_degree_check (M is the record's coefficient count).
+static inline int s360_raw_planes_check(const S360Params* prm, const S360RawInputs* raw, const S360RawPlanes* pl) {
+    if (!pl || raw->H < 1 || raw->W < 1 || raw->per_ray < 1) return S360_E_BADARG;
+    const long long hw = (long long)raw->H * raw->W, width = 7 + 3 * (long long)prm->M;
+    if (pl->channel_stride < hw) return S360_E_BADARG;
+    if (raw->per_ray > 1 && pl->surface_stride < width * pl->channel_stride) return S360_E_BADARG;
+    const long long surfaces = raw->per_ray > 1 ? (raw->per_ray - 1) * (long long)pl->surface_stride : 0;
+    if (pl->view_stride < surfaces + (width - 1) * pl->channel_stride + hw) return S360_E_BADARG;
+    return S360_OK;
+}
+
 // float4s per (instance, quadrant) partial raster-gradient record of the backward: 3 = packed 48-byte records, 4 = 64-byte aligned
 // slots (a record never straddles a 128-byte line or a 32-byte write granule)
 #ifndef S360_PREC_F4

@@ -17,6 +17,7 @@
 #include "s360_adapter_math.h"
 
 #include <cstdio>
+#include <type_traits>
 #include <cstdlib>
 
 namespace s360 {
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_sh_eval3(KParams kp, const S360V
 constexpr uint32_t SHG_NZ_X = 0x1E7FFD8u, SHG_NZ_Y = 0x1CFFF72u, SHG_NZ_Z = 0x0FE7CE4u;  // non-zero entries of sh_basis_grad's dx / dy / dz at degree 4
 // DEG: the slab's degree ([3][(DEG + 1)^2] channel-major).  The non-zero masks are prefixes of the degree-4 ones: the basis is the same
 // polynomial table cut at (DEG + 1)^2 entries, and the sums are k_sh_eval's fmaf chains from 0 in ascending k at every degree.
-template <int D, int DEG = 4>
+template <int D, int DEG = 4, int LS = 1>   // LS: words between consecutive slab entries (k_raw_eval's plane form: 64)
 __device__ __forceinline__ void sh_jac_component(float x, float y, float z, const float* __restrict__ slab, float* G) {
     constexpr int N = (DEG + 1) * (DEG + 1);
     float b0[25], b1[25], b2[25];
@@ -194,7 +195,7 @@ __device__ __forceinline__ void sh_jac_component(float x, float y, float z, cons
     for (int k = 0; k < N; ++k) {
         if (!((NZ >> k) & 1u)) continue;  // fma(0, c, G) == G
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) G[ch] = __builtin_fmaf(b[k], slab[N * ch + k], G[ch]);
+        for (int ch = 0; ch < 3; ++ch) G[ch] = __builtin_fmaf(b[k], slab[(N * ch + k) * LS], G[ch]);
     }
 }
 
@@ -300,6 +301,11 @@ struct RawIn {
     int Gv, H, W, per_ray, conv;
     float smin, smax, eps;
 };
+// PLANES form of the kernel below (s360_forward_raw_planes): `raw` is addressed as channel planes (S360RawPlanes: strides in floats).
+// The record instantiations keep RawIn itself as their argument, byte for byte.
+struct RawInPlanes : RawIn {
+    long long view_stride, surface_stride, channel_stride;
+};
 constexpr int raw_record_floats(int deg) { return 7 + 3 * (deg + 1) * (deg + 1); }   // 10, 19, 34, 55, 82 floats per raw record
 // 16-byte staging rounds of the workgroup's 64 records (192 float4 per round): 1, 2, 3, 5, 7
 constexpr int raw_stage_rounds(int deg) { return (SHE3_G * raw_record_floats(deg) / 4 + SHE3_G * 3 - 1) / (SHE3_G * 3); }
@@ -320,11 +326,24 @@ static_assert(raw_stage_rounds(4) == 7 && raw_stage_rounds(0) == 1 && (SHE3_G * 
 // (G - dir (dir . G)) * (scale * inv) in k_sh_eval3_jac — so s_dir.w carries inv alone below degree 4.  Lanes read their record at a
 // stride of 10 / 19 / 34 / 55 / 82 words: the even strides are two-way bank conflicts on the 64 banks, as degree 4 always had; the
 // records are not padded (the staging rounds stay plain 16-byte copies).  MFMA exists at degree 4 only.
-template <bool JAC, bool ROT, bool MFMA = false, int DEG = 4>
-__global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360View* __restrict__ views, RawIn rin, float4* __restrict__ rgbc,
-                                                        float* __restrict__ sh_jac, uint32_t* __restrict__ zero_ptr, int zero_words) {
+//
+// PLANES (compile time): the raw words lie as channel planes (RawInPlanes; word c of Gaussian gi of view v at raw + v view_stride +
+// (gi % per_ray) surface_stride + c channel_stride + gi / per_ray) and are staged as s_raw[c][lane]: 64 Gaussians of one channel are one
+// 256-byte run in memory (per_ray = 1) and one conflict-free row of the 64 LDS banks, so every later per-lane read — slab word
+// N d + k, geometry word k — is the record form's own expression at a stride of LS = 64 words instead of 1, free of the two-way
+// conflicts of the even record strides.  A thread stages four Gaussians of one channel per round with one 16-byte load where that
+// address is 16-byte aligned (per_ray = 1, a full block), word by word where it is not (planes of H W floats with H W % 4 != 0 leave
+// three channels in four unaligned) — RAW_C 16 quads over 192 threads: the record form's 1 / 2 / 3 / 5 / 7 rounds.  Partial blocks and
+// per_ray > 1 (a Gaussian's ray is gi / per_ray: the run is per_ray interleaved runs) load word by word.  Everything after the staging
+// barrier is the record form's code.
+template <bool JAC, bool ROT, bool MFMA = false, int DEG = 4, bool PLANES = false>
+__global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360View* __restrict__ views, std::conditional_t<PLANES, RawInPlanes, RawIn> rin,
+                                                        float4* __restrict__ rgbc, float* __restrict__ sh_jac, uint32_t* __restrict__ zero_ptr, int zero_words) {
     static_assert(!MFMA || DEG == 4, "the matrix-core rotation is a degree-4 experiment");
+    static_assert(!MFMA || !PLANES, "the matrix-core rotation reads records");
     constexpr int N = (DEG + 1) * (DEG + 1), RAW_C = raw_record_floats(DEG), ROUNDS = raw_stage_rounds(DEG);
+    constexpr int LS = PLANES ? SHE3_G : 1;      // LDS words between consecutive words of one Gaussian
+    static_assert(ROUNDS * SHE3_G * 3 * 4 >= SHE3_G * RAW_C && ROUNDS * SHE3_G * 3 >= RAW_C * (SHE3_G / 4), "the plane form's quads fit the same rounds and the same LDS");
     __shared__ __attribute__((aligned(16))) float s_raw[ROUNDS * SHE3_G * 3 * 4];   // 64 records x RAW_C floats (degree 4: 5 248) + pad to whole rounds of 192 float4
     __shared__ float s_rgb[SHE3_G * 3];
     __shared__ float s_G[9 * SHE3_G];
@@ -338,7 +357,37 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360V
     const int gi0 = blockIdx.x * SHE3_G;                        // first Gaussian of the block inside its view
     const int nb = min(SHE3_G, rin.Gv - gi0);
     const int g0 = v * rin.Gv + gi0;
-    {
+    if constexpr (PLANES) {
+        const float* vbase = rin.raw + (size_t)v * rin.view_stride;
+        static_assert(SHE3_G == 64, "quads and lanes are cut with shifts");
+        if (rin.per_ray == 1 && nb == SHE3_G) {
+            // item = (channel c, quad qd): Gaussians gi0 + 4 qd .. + 3 of channel c; 16 consecutive lanes cover one channel's 256 bytes
+            float4 q[ROUNDS];
+#pragma unroll
+            for (int r = 0; r < ROUNDS; ++r) {
+                const int it = min(tid + r * (SHE3_G * 3), RAW_C * (SHE3_G / 4) - 1);
+                const float* p = vbase + (size_t)(it >> 4) * rin.channel_stride + gi0 + 4 * (it & 15);
+                if ((((uintptr_t)p) & 15) == 0) {
+                    const f4v t = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p));
+                    q[r] = make_float4(t.x, t.y, t.z, t.w);
+                } else {
+                    q[r] = make_float4(__builtin_nontemporal_load(p), __builtin_nontemporal_load(p + 1), __builtin_nontemporal_load(p + 2),
+                                       __builtin_nontemporal_load(p + 3));
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < ROUNDS; ++r) {
+                const int it = tid + r * (SHE3_G * 3);
+                if (it < RAW_C * (SHE3_G / 4)) reinterpret_cast<float4*>(s_raw)[it] = q[r];    // word c * 64 + 4 qd
+            }
+        } else {
+            for (int i = tid; i < RAW_C * SHE3_G; i += SHE3_G * 3) {
+                const int c = i >> 6, gi = gi0 + (i & 63);
+                if ((i & 63) < nb)
+                    s_raw[i] = vbase[(size_t)(gi % rin.per_ray) * rin.surface_stride + (size_t)c * rin.channel_stride + gi / rin.per_ray];
+            }
+        }
+    } else {
         const float* src = rin.raw + (size_t)g0 * RAW_C;
         const int nfl = nb * RAW_C;
         if ((((uintptr_t)src) & 15) == 0 && nb == SHE3_G) {
@@ -385,7 +434,7 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360V
     float depth = 0.f;
     if (d == 1 && live) depth = rin.depths[g];
     __syncthreads();      // the staged records, the view directions
-    float* slab = s_raw + l * RAW_C + 7;     // [3][N] channel-major coefficients of this lane's Gaussian
+    float* slab = PLANES ? s_raw + 7 * SHE3_G + l : s_raw + l * RAW_C + 7;     // [3][N] channel-major coefficients of this lane's Gaussian (word stride LS)
     float x = 0.f, y = 0.f, z = 1.f;
     if (MFMA) {
         // MFMA form (ROT only): the wave rotates its channel of all 64 records on the matrix cores, in place (every lane takes part:
@@ -410,7 +459,7 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360V
         const float* D = ROT ? rin.sh_rot + (size_t)v * (N * N) : nullptr;
         float c[N], h[N];
 #pragma unroll
-        for (int k = 0; k < N; ++k) c[k] = slab[N * d + k];
+        for (int k = 0; k < N; ++k) c[k] = slab[(N * d + k) * LS];
         sh_rotate_coefs<DEG, ROT>(D, c, h);
         float Y[25];
         sh_basis(DEG, x, y, z, Y);
@@ -420,29 +469,29 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360V
         s_rgb[3 * l + d] = acc + 0.5f;
         if (JAC) {
 #pragma unroll
-            for (int k = 0; k < N; ++k) slab[N * d + k] = h[k];   // in place: only wave d ever touched these N words
+            for (int k = 0; k < N; ++k) slab[(N * d + k) * LS] = h[k];   // in place: only wave d ever touched these N words
         }
     }
     if (JAC) {
         if (!MFMA) __syncthreads();  // the three channels' harmonics
         if (live) {
             float G[3];
-            if (d == 0) sh_jac_component<0, DEG>(x, y, z, slab, G);     // wave-uniform: each wave compiles ONE derivative component
-            else if (d == 1) sh_jac_component<1, DEG>(x, y, z, slab, G);
-            else sh_jac_component<2, DEG>(x, y, z, slab, G);
+            if (d == 0) sh_jac_component<0, DEG, LS>(x, y, z, slab, G);     // wave-uniform: each wave compiles ONE derivative component
+            else if (d == 1) sh_jac_component<1, DEG, LS>(x, y, z, slab, G);
+            else sh_jac_component<2, DEG, LS>(x, y, z, slab, G);
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) s_G[(3 * ch + d) * SHE3_G + l] = G[ch];
         }
     }
     if (d == 1 && live) {
         // ---- covariance: the adapter tail's own expressions (k_adapter_fwd)
-        const float* rw = s_raw + l * RAW_C;
+        const float* rw = PLANES ? s_raw + l : s_raw + l * RAW_C;
         const float px = 1.0f / (float)max(rin.W, rin.H);
         float sc3[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) sc3[k] = ((rin.smin + (rin.smax - rin.smin) * sigmoidf(rw[k])) * depth) * px;
+        for (int k = 0; k < 3; ++k) sc3[k] = ((rin.smin + (rin.smax - rin.smin) * sigmoidf(rw[k * LS])) * depth) * px;
         QuatGeom qg;
-        const float qr[4] = {rw[3], rw[4], rw[5], rw[6]};
+        const float qr[4] = {rw[3 * LS], rw[4 * LS], rw[5 * LS], rw[6 * LS]};
         quat_geom(qr, rin.eps, qg);
         float M[3][3];
 #pragma unroll
@@ -459,10 +508,10 @@ __global__ __launch_bounds__(SHE3_G * 3) void k_raw_eval(KParams kp, const S360V
         oc[0] = S[0][0]; oc[1] = S[0][1]; oc[2] = S[0][2]; oc[3] = S[1][1]; oc[4] = S[1][2]; oc[5] = S[2][2];
     }
     if (d == 2 && live && rin.geo7) {
-        const float* rw = s_raw + l * RAW_C;
+        const float* rw = PLANES ? s_raw + l : s_raw + l * RAW_C;
         float* o7 = rin.geo7 + 7 * (size_t)g;
 #pragma unroll
-        for (int k = 0; k < 7; ++k) o7[k] = rw[k];
+        for (int k = 0; k < 7; ++k) o7[k] = rw[k * LS];
     }
     __syncthreads();
     if (JAC) {
@@ -2772,7 +2821,8 @@ extern "C" int s360_layout(const S360Params* prm, S360Layout* out) {
 static int forward_impl(const S360Params* prm, const S360View* views, const float* means3D, const float* cov6,
                         const float* opacities, const float* shs, const float* colors_precomp, float* images,
                         float* depth_maps, int depth_mode, int32_t* radii, void* workspace, size_t workspace_bytes,
-                        void* stream_, MseEp ep = MseEp{nullptr, nullptr, nullptr, 0.f, nullptr}, const RawIn* rawin = nullptr) {
+                        void* stream_, MseEp ep = MseEp{nullptr, nullptr, nullptr, 0.f, nullptr}, const RawIn* rawin = nullptr,
+                        const S360RawPlanes* planes = nullptr) {
     if (!prm || !views || !images || !workspace) return S360_E_BADARG;
     if (prm->P > 0 && (shs == nullptr) == (colors_precomp == nullptr)) return S360_E_BADARG;
     if (((prm->flags & S360_FLAG_RAW_INPUTS) != 0) != (rawin != nullptr)) return S360_E_BADARG;   // the flag sizes the workspace for this entry point
@@ -2858,6 +2908,23 @@ static int forward_impl(const S360Params* prm, const S360View* views, const floa
                 // multiply-adds — same bits; measured side by side in DESIGN.md section 6.  A degree-4 experiment: at degrees 0..3 the
                 // switch is ignored and the SGPR form runs.
                 static const bool raw_mfma = [] { const char* e = getenv("S360_RAW_MFMA"); return e && e[0] == '1'; }();
+                if (planes) {   // s360_forward_raw_planes: the same kernel with the plane staging (no matrix-core form: rejected by the entry)
+                    RawInPlanes rpl;
+                    static_cast<RawIn&>(rpl) = rin;
+                    rpl.view_stride = planes->view_stride; rpl.surface_stride = planes->surface_stride; rpl.channel_stride = planes->channel_stride;
+#define S360_RAWP(J, R, DG) hipLaunchKernelGGL((k_raw_eval<J, R, false, DG, true>), rgrid, dim3(SHE3_G * 3), 0, st, kp, views, rpl, rgbc, sh_jac, zero_ptr, zero_words)
+#define S360_RAWP_DEG(DG) do { if (jac) { if (rot) S360_RAWP(true, true, DG); else S360_RAWP(true, false, DG); } \
+                               else { if (rot) S360_RAWP(false, true, DG); else S360_RAWP(false, false, DG); } } while (0)
+                    switch (prm->sh_degree) {
+                        case 0: S360_RAWP_DEG(0); break;
+                        case 1: S360_RAWP_DEG(1); break;
+                        case 2: S360_RAWP_DEG(2); break;
+                        case 3: S360_RAWP_DEG(3); break;
+                        default: S360_RAWP_DEG(4);
+                    }
+#undef S360_RAWP_DEG
+#undef S360_RAWP
+                } else
                 switch (prm->sh_degree) {   // s360_forward_raw admitted 0..4 with M == (degree + 1)^2
                     case 0: S360_RAWE_DEG(0); break;
                     case 1: S360_RAWE_DEG(1); break;
@@ -3030,10 +3097,10 @@ extern "C" int s360_forward_mse(const S360Params* prm, const S360View* views, co
                         workspace, workspace_bytes, stream_, s360::MseEp{target, d_images, partials, grad_scale, loss_out});
 }
 
-extern "C" int s360_forward_raw(const S360Params* prm, const S360View* views, const S360RawInputs* raw, const float* opacities,
+static int forward_raw(const S360Params* prm, const S360View* views, const S360RawInputs* raw, const S360RawPlanes* planes, const float* opacities,
                                 float* means_out, float* cov6_out, float* images, float* depth_maps, int32_t depth_mode, int32_t* radii,
                                 const float* target, float grad_scale, float* d_images, float* partials, float* loss_out, void* workspace,
-                                size_t workspace_bytes, void* stream_) {
+                                size_t workspace_bytes, void* stream_, bool as_planes) {
     if (!prm || !raw || !means_out || !cov6_out) return S360_E_BADARG;
     if (!(prm->flags & S360_FLAG_RAW_INPUTS) || !(prm->flags & S360_FLAG_SHARED_CAMPOS) || (prm->flags & (S360_FLAG_COV9 | S360_FLAG_SPHERICAL)))
         return S360_E_BADARG;   // one camera centre per call; the geometry pass reads the 6-entry covariances this call writes
@@ -3043,6 +3110,11 @@ extern "C" int s360_forward_raw(const S360Params* prm, const S360View* views, co
         (long long)raw->n_views * raw->per_view != (long long)prm->P || (long long)raw->H * raw->W * raw->per_ray != (long long)raw->per_view)
         return S360_E_BADARG;
     if (raw->erp_convention < 0 || raw->erp_convention > 3 || (raw->erp_convention != 0 && (raw->H < 2 || raw->W < 2))) return S360_E_BADARG;
+    if (as_planes) {
+        if (const int rc = s360_raw_planes_check(prm, raw, planes)) return rc;
+        static const bool raw_mfma = [] { const char* e = getenv("S360_RAW_MFMA"); return e && e[0] == '1'; }();
+        if (raw_mfma) return S360_E_UNSUPPORTED;   // the matrix-core experiment rotates records in LDS: it has no plane form
+    }
     if (depth_maps && (depth_mode < 0 || depth_mode > 3)) return S360_E_BADARG;
     if (target && (!d_images || !partials)) return S360_E_BADARG;
     s360::RawIn rin{raw->extrinsics, raw->depths, raw->raw_gaussians, raw->sh_rotation, means_out, cov6_out, nullptr,
@@ -3050,5 +3122,21 @@ extern "C" int s360_forward_raw(const S360Params* prm, const S360View* views, co
     const float* dummy_sh = reinterpret_cast<const float*>(raw->raw_gaussians ? raw->raw_gaussians : (const float*)workspace);   // never read: the colours come from k_raw_eval
     return forward_impl(prm, views, means_out, cov6_out, opacities, dummy_sh, nullptr, images, depth_maps, depth_mode, radii, workspace,
                         workspace_bytes, stream_, target ? s360::MseEp{target, d_images, partials, grad_scale, loss_out}
-                                                         : s360::MseEp{nullptr, nullptr, nullptr, 0.f, nullptr}, &rin);
+                                                         : s360::MseEp{nullptr, nullptr, nullptr, 0.f, nullptr}, &rin, as_planes ? planes : nullptr);
+}
+
+extern "C" int s360_forward_raw(const S360Params* prm, const S360View* views, const S360RawInputs* raw, const float* opacities,
+                                float* means_out, float* cov6_out, float* images, float* depth_maps, int32_t depth_mode, int32_t* radii,
+                                const float* target, float grad_scale, float* d_images, float* partials, float* loss_out, void* workspace,
+                                size_t workspace_bytes, void* stream_) {
+    return forward_raw(prm, views, raw, nullptr, opacities, means_out, cov6_out, images, depth_maps, depth_mode, radii, target, grad_scale,
+                       d_images, partials, loss_out, workspace, workspace_bytes, stream_, false);
+}
+
+extern "C" int s360_forward_raw_planes(const S360Params* prm, const S360View* views, const S360RawInputs* raw, const S360RawPlanes* planes,
+                                       const float* opacities, float* means_out, float* cov6_out, float* images, float* depth_maps,
+                                       int32_t depth_mode, int32_t* radii, const float* target, float grad_scale, float* d_images,
+                                       float* partials, float* loss_out, void* workspace, size_t workspace_bytes, void* stream_) {
+    return forward_raw(prm, views, raw, planes, opacities, means_out, cov6_out, images, depth_maps, depth_mode, radii, target, grad_scale,
+                       d_images, partials, loss_out, workspace, workspace_bytes, stream_, true);
 }

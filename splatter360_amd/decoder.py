@@ -324,6 +324,15 @@ class DecoderSplattingFused(torch.nn.Module):
         # Any other group indexes the fields, which materialises them once with the stand-alone adapter kernels.
         from . import lazy as _lazy
         bundle = _lazy.bundle_of(gaussians)
+        # ... and where the bundle's raw words still lie as the encoder's last convolution left them (lazy.raw_planes_of: the reference's
+        # own view chain over [(v b), C, h, w]) they are read there, batch element i at a view stride of b C h w, and their gradient is
+        # written in the convolution output's own layout: no transposing copy in front of the forward, no reshape / slice / permute
+        # nodes behind the backward.  Anything else — and any degree outside lazy.RAW_PLANE_SEAM_DEGREES — takes the records.
+        planes = None
+        if bundle is not None and bundle.shape5[4] == 1 and isqrt(bundle.d_sh) - 1 in _lazy.RAW_PLANE_SEAM_DEGREES:
+            planes = _lazy.raw_planes_of(bundle.raw)
+            if planes is not None and (tuple(planes.base.shape[2:]) != bundle.image_shape or planes.base.device != bundle.device):
+                planes = None
         for i in range(b):
             cs, ds = [], []
             for s in range(0, v, self.views_per_group):
@@ -332,13 +341,17 @@ class DecoderSplattingFused(torch.nn.Module):
                     m = bundle.module
                     nvc = bundle.shape5[1]
                     rot = bundle.sh_rotation()
+                    if planes is not None:
+                        raw_i, layout = planes.element(i, b), dict(raw_layout="planes", raw_channel_offset=planes.channel_offset)
+                    else:
+                        raw_i, layout = bundle.raw[i].reshape(-1, bundle.raw.shape[-1]), {}
                     out = rasterizer.rasterize_raw(
-                        bundle.depths[i].reshape(-1), gaussians.opacities[i].reshape(-1), bundle.raw[i].reshape(-1, bundle.raw.shape[-1]),
+                        bundle.depths[i].reshape(-1), gaussians.opacities[i].reshape(-1), raw_i,
                         bundle.extrinsics[i], views=packed[(i, s)], image_height=int(image_shape[0]), image_width=int(image_shape[1]),
                         context_shape=bundle.image_shape, scale_min=float(m.cfg.gaussian_scale_min), scale_max=float(m.cfg.gaussian_scale_max),
                         sh_rotation=None if rot is None else rot[i * nvc:(i + 1) * nvc], per_ray=bundle.per_ray, eps=bundle.eps,
                         erp_convention=_lazy._adapter.ERP_CONVENTIONS[bundle.dataset_name], differentiable_means=m._s360.differentiable_means,
-                        check=self.check, depth_mode=depth_mode)
+                        check=self.check, depth_mode=depth_mode, **layout)
                     cs.append(out[0])
                     if depth_mode is not None:
                         ds.append(out[3])

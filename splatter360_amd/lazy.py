@@ -21,7 +21,7 @@ configuration is degree 4: [.,3,25] harmonics, 82-float records).
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor
@@ -33,6 +33,11 @@ from . import adapter as _adapter
 # then render) beyond the run-to-run spread of scripts/raw_degrees_timing.py (profiles/raw_degrees_timing.json); at any other degree
 # the class keeps the eager adapter, and rasterize_raw stays available to a caller who asks for it directly.
 RAW_SEAM_DEGREES = (0, 1, 2, 3, 4)
+# ... and the degrees at which the fused decoder reads the raw words where the encoder's last convolution left them (raw_planes_of
+# below, rasterize_raw(raw_layout="planes")) instead of transposing them into records first.  The same rule: a degree is listed where
+# the plane route is not slower than the record route from the same convolution output beyond the run-to-run spread of
+# scripts/raw_planes_timing.py (profiles/raw_planes_timing.json, legs B against A).  rasterize_raw takes planes at every degree.
+RAW_PLANE_SEAM_DEGREES = (0, 1, 2, 3, 4)
 
 _FIELDS = {"means": (3,), "covariances": (3, 3), "scales": (3,), "rotations": (4,), "harmonics": None}
 
@@ -148,6 +153,50 @@ def _identity_permutation(name, args, kwargs, nd) -> bool:
         return len(args) == 3 and int(args[1]) % nd == int(args[2]) % nd
     except Exception:
         return False
+
+
+class RawPlanes(NamedTuple):
+    """What raw_planes_of found: the adapter's raw_gaussians is a view of `base` [(v b), C, h, w] (contiguous float32); per surface
+    `surface_channels` = C / srf channels, of which the first `channel_offset` precede the record; context view j of batch element i is
+    base[j * b + i], `view_stride` = b C h w floats after view j - 1."""
+    base: Tensor
+    channel_offset: int
+    surface_channels: int
+    view_stride: int
+
+    def element(self, i: int, b: int) -> Tensor:
+        """[v, C, h, w]: the planes of batch element i of b, in place (view stride b C h w)."""
+        base = self.base
+        if b == 1:
+            return base
+        return base.view(base.shape[0] // b, b, *base.shape[1:])[:, i]
+
+
+def raw_planes_of(raw) -> Optional[RawPlanes]:
+    """Is the adapter's raw_gaussians [b, v, r, srf, 1, 7 + 3 d_sh] what the reference's encoder hands over — the last convolution's
+    output [(v b), C, h, w] under "(v b) c h w -> b v (h w) c", "... (srf c) -> ... srf c" and the [..., k:] slice that drops the
+    offset_xy channels, three views and not one byte moved?  Decided from shape, strides, storage offset and `_base` alone (no device
+    work, no data read); None for anything else — a copy, channels-last memory, another dtype, a base that is itself strided, an
+    expanded samples-per-pixel dimension, a slice that does not run to the surface's last channel — and the caller keeps the record
+    route.  Strides of size-1 dimensions carry no information and are ignored."""
+    if not isinstance(raw, Tensor) or isinstance(raw, LazyField) or raw.dim() != 6 or raw.dtype != torch.float32:
+        return None
+    base = getattr(raw, "_base", None)
+    if base is None or base.dim() != 4 or base.dtype != torch.float32 or not base.is_contiguous():
+        return None
+    b, v, r, srf, spp, width = (int(x) for x in raw.shape)
+    n, c_total, h, w = (int(x) for x in base.shape)
+    hw = h * w
+    if spp != 1 or n != v * b or r != hw or srf < 1 or c_total % srf or min(b, v, r, width) < 1:
+        return None
+    cs = c_total // srf
+    off = int(raw.storage_offset()) - int(base.storage_offset())
+    if off < 0 or off % hw or off // hw + width != cs:
+        return None
+    want = (c_total * hw, b * c_total * hw, 1, cs * hw, 0, hw)       # "(v b)": the batch index is the fast one
+    if any(size > 1 and int(st) != exp for size, st, exp in zip(raw.shape, raw.stride(), want)):
+        return None
+    return RawPlanes(base, off // hw, cs, b * c_total * hw)
 
 
 def bundle_of(gaussians, d_sh: Optional[int] = None) -> Optional[RawBundle]:

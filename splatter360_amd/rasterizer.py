@@ -412,7 +412,7 @@ def _f32c(t: Tensor, name: str) -> Tensor:
 
 class _Options(NamedTuple):
     """The non-tensor arguments of one rasteriser call, as Function.apply carries them: one tuple, read by name.  The fields from
-    `shared_campos` to `atomic_grads` are rasterize_views' own and off in rasterize_raw; `differentiable_means` is rasterize_raw's."""
+    `shared_campos` to `atomic_grads` are rasterize_views' own and off in rasterize_raw; `differentiable_means` and `raw_planes` are rasterize_raw's."""
     h: int
     w: int
     lean: bool
@@ -434,6 +434,7 @@ class _Options(NamedTuple):
     spherical: bool = False
     atomic_grads: bool = False
     differentiable_means: bool = False
+    raw_planes: Optional[int] = None    # None: raw records; else the raw words lie as channel planes and this many channels precede each record
 
 
 RAW_D_SH = (1, 4, 9, 16, 25)    # coefficients per channel of a raw record at SH degrees 0..4 (index = degree): records of 7 + 3 * d_sh floats
@@ -518,7 +519,7 @@ def _forward_call(prm, views: Tensor, head: tuple, opt: _Options, loss):
         radii = torch.empty((prm.V, prm.P), dtype=torch.int32, device=dev) if opt.want_radii else None
         depth = torch.empty((n_img, prm.H, prm.W), dtype=torch.float32, device=dev) if opt.depth_mode is not None else None
         if raw or loss.target is not None:      # loss epilogue fused into the composite store
-            entry = "s360_forward_raw" if raw else "s360_forward_mse"
+            entry = ("s360_forward_raw" if opt.raw_planes is None else "s360_forward_raw_planes") if raw else "s360_forward_mse"
             out = (ptr(images), ptr(depth), dm, ptr(radii), ptr(loss.target), C.c_float(loss.grad_scale), ptr(loss.d_images),
                    ptr(loss.partials), ptr(loss.out))
         elif depth is not None:
@@ -714,6 +715,36 @@ def _raw_record_d_sh(raw: Tensor, sh_rot: Optional[Tensor], n_views: int) -> int
     return d_sh
 
 
+def _raw_planes_d_sh(raw: Tensor, sh_rot: Optional[Tensor], n_views: int, context_shape: tuple, per_ray: int, offset: int) -> int:
+    """d_sh of raw channel planes [n_views, per_ray * (offset + 7 + 3 d_sh), h, w] (shape, strides and dtype only: no device work);
+    RuntimeError for anything the plane kernels cannot read where it lies."""
+    ch, cw = int(context_shape[0]), int(context_shape[1])
+    if offset < 0 or per_ray < 1:
+        raise RuntimeError(f"rasterize_raw: raw_channel_offset must be >= 0 and per_ray >= 1, got {offset} and {per_ray}")
+    if raw.dim() != 4 or tuple(raw.shape[2:]) != (ch, cw) or int(raw.shape[0]) != n_views:
+        raise RuntimeError(f"rasterize_raw: raw_layout='planes' takes raw_gaussians [{n_views}, C, {ch}, {cw}] (context views, channels, "
+                           f"context_shape), got {list(raw.shape)}")
+    c_total = int(raw.shape[1])
+    width = c_total // per_ray - offset
+    d_sh = (width - 7) // 3
+    if c_total % per_ray or d_sh not in RAW_D_SH or width != 7 + 3 * d_sh:
+        raise RuntimeError(f"rasterize_raw: raw_gaussians has {c_total} channels; with per_ray = {per_ray} and raw_channel_offset = {offset} "
+                           f"the allowed counts are {', '.join(str(per_ray * (offset + 7 + 3 * n)) for n in RAW_D_SH)} "
+                           f"(per_ray * (offset + 7 + 3 * d_sh), d_sh = (sh_degree + 1)^2 for SH degrees 0..4)")
+    if raw.dtype != torch.float32:
+        raise RuntimeError(f"rasterize_raw: raw_layout='planes' reads raw_gaussians in place and needs float32, got {raw.dtype}")
+    st = raw.stride()
+    inner = tuple(s for n, s in zip(raw.shape[1:], st[1:]) if n > 1)
+    want = tuple(s for n, s in zip(raw.shape[1:], (ch * cw, cw, 1)) if n > 1)
+    if inner != want or (n_views > 1 and st[0] < c_total * ch * cw):
+        raise RuntimeError(f"rasterize_raw: raw_layout='planes' reads raw_gaussians in place: its channel, row and column strides must be "
+                           f"({ch * cw}, {cw}, 1) and its view stride >= {c_total * ch * cw}, got strides {tuple(st)}")
+    if sh_rot is not None and tuple(sh_rot.shape) != (n_views, d_sh, d_sh):
+        raise RuntimeError(f"rasterize_raw: sh_rotation must be [{n_views}, {d_sh}, {d_sh}] for {width}-word records "
+                           f"(d_sh = {d_sh}), got {list(sh_rot.shape)}")
+    return d_sh
+
+
 class _RasterizeRaw(torch.autograd.Function):
     """The adapter tail fused into the rasteriser (s360_forward_raw / s360_backward_raw): from the encoder's raw
     outputs (depths, opacities, raw_gaussians of the context panoramas) to the rendered views of ONE target camera centre, without
@@ -728,28 +759,45 @@ class _RasterizeRaw(torch.autograd.Function):
         dev = dep.device
         with torch.cuda.device(dev):
             op = _f32c(opacities, "opacities").reshape(-1)
-            rw = _f32c(raw, "raw_gaussians")
+            planes = opt.raw_planes is not None
+            if planes and not raw.is_cuda:
+                raise RuntimeError("raw_gaussians must live on the GPU (hip device); the rasteriser has no CPU path")
+            rw = raw.detach() if planes else _f32c(raw, "raw_gaussians")       # planes: read where they lie (rasterize_raw checked the layout)
             ext = _f32c(ctx_extrinsics, "extrinsics").reshape(-1, 4, 4)
             rot = None if sh_rot is None else _f32c(sh_rot, "sh_rotation")
             vw = _f32c(views, "views")
             nv = int(ext.shape[0])
             p, v = int(dep.shape[0]), int(vw.shape[0])
-            d_sh = _raw_record_d_sh(rw, rot, nv)
-            width = 7 + 3 * d_sh
-            if rw.numel() != p * width or p % max(nv, 1) or (p // max(nv, 1)) != rin.H * rin.W * rin.per_ray:
-                raise RuntimeError(f"rasterize_raw: raw_gaussians must be [views * h * w * per_ray, {width}] matching depths / extrinsics")
+            pln = None
+            if planes:
+                d_sh = _raw_planes_d_sh(rw, rot, nv, (rin.H, rin.W), rin.per_ray, opt.raw_planes)
+                width = 7 + 3 * d_sh
+                if p != nv * rin.H * rin.W * rin.per_ray:
+                    raise RuntimeError(f"rasterize_raw: depths must hold views * h * w * per_ray = {nv * rin.H * rin.W * rin.per_ray} values, got {p}")
+                hw = rin.H * rin.W
+                # (a view stride of a one-view tensor carries no information: the kernels never multiply it by anything but 0)
+                pln = _lib.S360RawPlanes(view_stride=int(rw.stride(0)) if nv > 1 else int(rw.shape[1]) * hw,
+                                         surface_stride=(opt.raw_planes + width) * hw, channel_stride=hw)
+            else:
+                d_sh = _raw_record_d_sh(rw, rot, nv)
+                width = 7 + 3 * d_sh
+                if rw.numel() != p * width or p % max(nv, 1) or (p // max(nv, 1)) != rin.H * rin.W * rin.per_ray:
+                    raise RuntimeError(f"rasterize_raw: raw_gaussians must be [views * h * w * per_ray, {width}] matching depths / extrinsics")
             opt = opt._replace(sh_degree=RAW_D_SH.index(d_sh))      # the record's width decides the degree: M == (sh_degree + 1)^2
             prm = _params(dev, p, v, opt, any(ctx.needs_input_grad[:3]), mse_target is not None,
                           _lib.FLAG_SHARED_CAMPOS | _lib.FLAG_RAW_INPUTS, sh=d_sh)
             loss = _loss_setup(mse_target, v, opt)
             # (rasterize_raw filled in the geometry; the tensors are saved below, so the record still holds in the backward)
-            rin.extrinsics, rin.depths, rin.raw_gaussians = ext.data_ptr(), dep.data_ptr(), rw.data_ptr()
+            rin.extrinsics, rin.depths = ext.data_ptr(), dep.data_ptr()
+            rin.raw_gaussians = rw.data_ptr() + 4 * opt.raw_planes * rin.H * rin.W if planes else rw.data_ptr()    # word 0 of view 0, surface 0
             rin.sh_rotation = None if rot is None else rot.data_ptr()
             rin.n_views, rin.per_view = nv, p // max(nv, 1)
             means = torch.empty((p, 3), dtype=torch.float32, device=dev)
             cov6 = torch.empty((p, 6), dtype=torch.float32, device=dev)
-            images, _, depth, state = _forward_call(prm, vw, (C.byref(rin), ptr(op), ptr(means), ptr(cov6)), opt, loss)
+            head = (C.byref(rin), C.byref(pln)) if planes else (C.byref(rin),)
+            images, _, depth, state = _forward_call(prm, vw, head + (ptr(op), ptr(means), ptr(cov6)), opt, loss)
         ctx.rin, ctx.depth_mode, ctx.diff_means = rin, opt.depth_mode, bool(opt.differentiable_means)
+        ctx.planes, ctx.plane_offset = pln, opt.raw_planes
         ctx.in_shapes = (tuple(depths.shape), tuple(opacities.shape), tuple(raw.shape))   # gradients go back in the callers' shapes
         depth, loss, clipped = _finish_forward(ctx, state, depth, (means, cov6))
         ctx.save_for_backward(dep, op, rw, ext, rot, vw, means, cov6)
@@ -769,7 +817,21 @@ class _RasterizeRaw(torch.autograd.Function):
             d_op = torch.empty((p,), dtype=torch.float32, device=dev)
             d_rgb = torch.empty((p, 4), dtype=torch.float32, device=dev)
             d_dep = torch.empty((p,), dtype=torch.float32, device=dev)
-            d_raw = torch.empty((p, 7 + 3 * prm.M), dtype=torch.float32, device=dev)
+            pln = ctx.planes
+            if pln is None:
+                d_raw = torch.empty((p, 7 + 3 * prm.M), dtype=torch.float32, device=dev)
+                praw = (ptr(d_raw),)
+                tail = ("", (C.byref(rin),))
+            else:
+                # contiguous, shaped like raw_gaussians: the kernel writes every record word where the convolution's backward reads it;
+                # the channels in front of each record are nobody's output: zeroed here (offset / (offset + width) of the tensor)
+                hw, nv, off = rin.H * rin.W, rin.n_views, ctx.plane_offset
+                d_raw = torch.empty(ctx.in_shapes[2], dtype=torch.float32, device=dev)
+                if off:
+                    d_raw.view(nv, rin.per_ray, -1, hw)[:, :, :off].zero_()
+                gpl = _lib.S360RawPlanes(view_stride=int(d_raw.shape[1]) * hw, surface_stride=pln.surface_stride, channel_stride=hw)
+                praw = (C.c_void_p(d_raw.data_ptr() + 4 * off * hw),)
+                tail = ("_planes", (C.byref(rin), C.byref(gpl)))
             bws = torch.empty(lay.backward_bytes, dtype=torch.uint8, device=dev)
             stream = _call.stream(dev)
             if ctx.exchange is not None:
@@ -791,13 +853,13 @@ class _RasterizeRaw(torch.autograd.Function):
                     rgb_all = torch.empty((world, p, 4), dtype=torch.float32, device=dev)
                     for (lo, hi), t in gathered.items():
                         rgb_all[:, lo:hi] = t
-                invoke("s360_backward_raw_tail", C.byref(prm), ptr(rep_all), world, C.byref(rin), ptr(means), ptr(state.workspace),
+                invoke("s360_backward_raw_tail" + tail[0], C.byref(prm), ptr(rep_all), world, *tail[1], ptr(means), ptr(state.workspace),
                        lay.total_bytes, ptr(d_m3) if diff_means else None, ptr(d_c6), ptr(rgb_all),
-                       ptr(d_dep), ptr(d_raw), stream)
+                       ptr(d_dep), *praw, stream)
             else:
-                invoke("s360_backward_raw", C.byref(prm), ptr(vw), C.byref(rin), ptr(means), ptr(cov6), ptr(op), ptr(state.workspace),
+                invoke("s360_backward_raw" + tail[0], C.byref(prm), ptr(vw), *tail[1], ptr(means), ptr(cov6), ptr(op), ptr(state.workspace),
                        lay.total_bytes, ptr(g), ptr(g_scale), ptr(gd), dm, int(diff_means), ptr(d_m3), ptr(d_c6),
-                       ptr(d_op), ptr(d_rgb), ptr(d_dep), ptr(d_raw), ptr(bws), lay.backward_bytes, stream)
+                       ptr(d_op), ptr(d_rgb), ptr(d_dep), *praw, ptr(bws), lay.backward_bytes, stream)
         sd, so, sr = ctx.in_shapes
         return d_dep.view(sd), d_op.view(so), d_raw.view(sr), None, None, None, None, None, None
 
@@ -907,7 +969,8 @@ def rasterize_raw(depths: Tensor, opacities: Tensor, raw_gaussians: Tensor, cont
                   per_ray: int = 1, eps: float = 1e-8, erp_convention: int = 0, differentiable_means: bool = False,
                   max_instances: Optional[int] = None, check: str = "sync", depth_mode: Optional[str] = None,
                   mse_target: Optional[Tensor] = None, mse_weight: float = 1.0, mse_count: Optional[int] = None, lean: Optional[bool] = None,
-                  mse_defer: bool = False, split_lists: Optional[bool] = None, exchange=None):
+                  mse_defer: bool = False, split_lists: Optional[bool] = None, exchange=None, raw_layout: str = "records",
+                  raw_channel_offset: int = 0):
     """Render V views sharing one camera centre ([V,44] packed) straight from the encoder's raw outputs: depths / opacities [n*h*w*per_ray]
     (view-major, ray-major), raw_gaussians [same, 7 + 3 d_sh] (3 scale logits, quaternion xyzw, 3 x d_sh SH coefficients; d_sh = 1, 4, 9,
     16 or 25 = SH degree 0..4, read off the record's width: 10, 19, 34, 55 or 82 floats), context_extrinsics [n,4,4], sh_rotation
@@ -916,15 +979,29 @@ def rasterize_raw(depths: Tensor, opacities: Tensor, raw_gaussians: Tensor, cont
     in rasterize_views).  Gradients flow to depths, opacities and raw_gaussians; the means are detached like the reference's unless
     differentiable_means.  exchange=distributed.ExchangeConfig(...): multi-GPU — every rank renders its own target panorama of the same
     raw cloud and the gradients w.r.t. depths / opacities / raw_gaussians come back SUMMED over the ranks (the exchange of
-    rasterize_views, with k_raw_bwd fed the N ranks' dL/dRGB factors)."""
+    rasterize_views, with k_raw_bwd fed the N ranks' dL/dRGB factors).
+    raw_layout="planes": raw_gaussians is the encoder's last convolution output where it lies — [n, C_total, h, w] float32 channel
+    planes, C_total = per_ray * (raw_channel_offset + 7 + 3 d_sh) (per surface: raw_channel_offset channels the records do not cover,
+    the reference's two offset_xy channels, then the record's words), channel / row / column strides (h w, w, 1) and any view stride
+    >= C_total h w (one batch element of a [(v b), C, h, w] tensor).  It is read in place (no .contiguous(), no reshape) and its
+    gradient comes back contiguous in its own shape, the offset channels exactly 0; every value is the record layout's, bit for bit."""
     if depth_mode is not None and depth_mode not in DEPTH_MODES:
         raise ValueError(f"depth_mode must be one of {sorted(DEPTH_MODES)}")
-    _raw_record_d_sh(raw_gaussians, sh_rotation, int(context_extrinsics.numel()) // 16)   # shape errors first, whatever the device
+    if raw_layout not in ("records", "planes"):
+        raise ValueError(f"raw_layout must be 'records' or 'planes', got {raw_layout!r}")
+    n_ctx = int(context_extrinsics.numel()) // 16
+    if raw_layout == "planes":      # shape and layout errors first, whatever the device
+        _raw_planes_d_sh(raw_gaussians, sh_rotation, n_ctx, context_shape, int(per_ray), int(raw_channel_offset))
+    else:
+        if raw_channel_offset:
+            raise ValueError("raw_channel_offset belongs to raw_layout='planes': records start at word 0")
+        _raw_record_d_sh(raw_gaussians, sh_rotation, n_ctx)
     ch, cw = context_shape
     opt = _Options(h=image_height, w=image_width, lean=LEAN_LISTS if lean is None else bool(lean),
                    split_lists=SPLIT_LONG_LISTS if split_lists is None else (split_lists if split_lists == "auto" else bool(split_lists)),
                    max_instances=max_instances, check=check, depth_mode=depth_mode, mse_weight=mse_weight, mse_count=mse_count,
-                   mse_defer=bool(mse_defer), exchange=exchange, sh_degree=4, differentiable_means=bool(differentiable_means))
+                   mse_defer=bool(mse_defer), exchange=exchange, sh_degree=4, differentiable_means=bool(differentiable_means),
+                   raw_planes=int(raw_channel_offset) if raw_layout == "planes" else None)
     rin = _lib.S360RawInputs(H=int(ch), W=int(cw), per_ray=int(per_ray), erp_convention=int(erp_convention), scale_min=float(scale_min),
                              scale_max=float(scale_max), eps=float(eps))      # (the node adds the tensors' addresses and counts)
     images, depth, loss, clipped, means, cov6 = _RasterizeRaw.apply(depths, opacities, raw_gaussians, context_extrinsics, sh_rotation, views, opt,
