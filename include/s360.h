@@ -1227,6 +1227,56 @@ int s360_layer_norm_residual_backward(const float* x, const float* weight, const
                                       float* g_weight, float* g_bias, void* stream);
 
 /*
+ * The mono-feature fusion of the cost-volume encoder (the reference's src/model/encoder/encoder_costvolume.py:297 and :351-354 with
+ * the rgbd_fusion of :119-125: features_mono = c2e(features_mono) under no_grad; cat([trans_features, features_mono], 1); Linear(C + Cm,
+ * C), LayerNorm(C), ReLU, Linear(C, C) over the channel-last tokens), forward and backward, without the stitched [n, Cm, h, w] map,
+ * without the [n, C + Cm, h, w] concatenation and without its channel-last copy.
+ *   erp_feat[n, channels, equ_h, equ_w] float32 contiguous (takes a gradient); mono_cube[n, mono_channels, face_w, 6 face_w] float32
+ *   contiguous, the six faces side by side in slot order F R B L U D, what Cube2Equirec.forward receives (a constant: no gradient);
+ *   grid[equ_h, equ_w, 3] the stitch's sampling grid (s360_cube2erp_forward's); w1[channels, channels + mono_channels] and
+ *   w2[channels, channels] in nn.Linear's layout, no biases; ln_weight, ln_bias[channels]; channels = 128, mono_channels a multiple
+ *   of 64 in 64 .. 1024; eps a HOST pointer to one float64, read before the launch.
+ *   Token t = (panorama, y, x), tokens = n equ_h equ_w.  m[k] = the stitch of mono_cube[panorama, k] at grid[y, x]: the eight taps
+ *   4 dz + 2 dy + dx, the border clamp and the float32 expressions of s360_cube2erp_forward (for finite inputs its float32 value; a
+ *   tap outside the volume has weight 0, is clamped to a valid address and not added), formed once per token for all channels.
+ *   yv = [e, m] w1^T; a = relu(LN(yv)), LN(x) = (x - mean) rstd weight + bias with mean and the BIASED variance in float64 (two
+ *   passes) over the float32 yv, every element formed in float64 and rounded once; out[n, channels, equ_h, equ_w] = a w2^T.  The
+ *   call also writes y[tokens, channels] (yv, float32) and stats[tokens, 2] FLOAT64 (mean, rstd) for the backward.
+ * Products run on v_mfma_f32_32x32x2_f32.  A workgroup owns 128 consecutive tokens (a tile may span two panoramas), 32 per wave, on
+ * the lanes; K = channels + mono_channels is walked in chunks of 64 whose slice of w1 is staged once per workgroup in LDS; each
+ * chunk is one float32 chain per output tile and the chunks are added in float64; a w2^T is float32 chains of 32 added in float64.
+ * s360_mono_fusion_backward takes the forward's inputs, y, stats and g_out[n, channels, equ_h, equ_w]: a pass owned by token tiles
+ * (g_a = g_out w2, ReLU's mask from the forward's own LN value with derivative 0 at exactly 0, LayerNorm's backward -> g_y,
+ * g_erp_feat = g_y w1[:, :channels] written in erp_feat's layout, float64 partial sums of g_ln_weight and g_ln_bias per workgroup,
+ * one per tile; g_y is handed to the next pass through scratch, tokens channels 4 bytes, not recomputed), a
+ * pass owned by (64 columns of g_w1 or g_w2, token chunk) (g_w1 = sum_t g_y[t] (x) [e, m][t] with the taps gathered again,
+ * g_w2 = sum_t g_out[t] (x) a[t]; tiles of 64 tokens, one float32 chain per tile added in float64 over the chunk) that writes
+ * per-chunk float32 partials into scratch, and a last launch that adds the partials in the order 0, 1, ... in float64.  The token
+ * chunks are s360_mono_fusion_weight_chunks(tokens) = min(32, ceil(tokens / 64)) runs of 64-token tiles, as even as integer division
+ * makes them.  Every output element is written exactly once, no atomics; bit-identical from run to run and across streams.
+ * Measured on one MI355X (profiles/mono_fusion_timing.json; N = 2, 128 x 256 tokens a panorama, medians of 50 calls, three collections,
+ * launch overhead included; this / the reference's lines in float32 torch): Cm = 384: forward 0.408 / 1.136 ms, forward + backward 1.190 / 1.999 ms — ahead of torch by 2.79 x and 1.68 x;
+ * Cm = 768: 0.736 / 2.169 ms and 1.802 / 3.174 ms, 2.95 x and 1.76 x.  The forward is 26.3 TFLOP/s (23.3 at Cm = 768), 16.8 % (14.9 %) of the float32 MFMA peak, the stitch's work not counted;
+ * forward + backward peak memory 246 / 553 MiB (324 / 913 MiB).
+ * No host synchronisation, no allocation.  scratch: s360_mono_fusion_scratch_bytes(tokens, mono_channels) bytes of device memory
+ * (16-byte aligned, contents need no initialisation; 0 for tokens < 1 or an unsupported mono_channels): tokens channels 4 +
+ * chunks channels (2 channels + mono_channels) 4 + ceil(tokens / 128) 2 channels 8; smaller: S360_E_WORKSPACE.
+ * channels != 128 or mono_channels not a multiple of 64 in 64 .. 1024: S360_E_UNSUPPORTED.  Null pointers, sizes < 1, eps null or
+ * *eps <= 0, a pointer that is not 16-byte aligned, an output that is an input or another output, 2^31 or more elements or
+ * workgroups, or equ_h equ_w 8 beyond int32: S360_E_BADARG before any GPU work.
+ */
+size_t s360_mono_fusion_scratch_bytes(int32_t tokens, int32_t mono_channels);
+int s360_mono_fusion_weight_chunks(int32_t tokens);
+int s360_mono_fusion_forward(const float* erp_feat, const float* mono_cube, const float* grid, const float* w1, const float* ln_weight,
+                             const float* ln_bias, const float* w2, int32_t n, int32_t channels, int32_t mono_channels, int32_t face_w,
+                             int32_t equ_h, int32_t equ_w, const double* eps, float* out, float* y, double* stats, void* stream);
+int s360_mono_fusion_backward(const float* erp_feat, const float* mono_cube, const float* grid, const float* w1, const float* ln_weight,
+                              const float* ln_bias, const float* w2, const float* y, const double* stats, const float* g_out, int32_t n,
+                              int32_t channels, int32_t mono_channels, int32_t face_w, int32_t equ_h, int32_t equ_w, const double* eps,
+                              void* scratch, size_t scratch_bytes, float* g_erp_feat, float* g_w1, float* g_ln_weight, float* g_ln_bias,
+                              float* g_w2, void* stream);
+
+/*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an
  * un-synchronised wall clock, src/misc/benchmarker.py:15-33).  While enabled, every kernel group
  * is bracketed by HIP events recorded on the launch stream; s360_profile_collect() synchronises

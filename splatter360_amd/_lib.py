@@ -17,7 +17,7 @@ LIB_PATH = _PKG / "libs360.so"
 SOURCES = ("s360_forward.hip", "s360_backward.hip", "s360_backward_em.hip", "s360_stitch.hip", "s360_views.hip", "s360_adapter.hip", "s360_metrics.hip",
            "s360_depth_loss.hip", "s360_eval_scores.hip", "s360_cost_volume.hip", "s360_depth_head.hip", "s360_depth_tail.hip", "s360_equirec2cube.hip", "s360_visualize.hip",
            "s360_depth_smooth.hip", "s360_window_attention.hip", "s360_group_norm.hip", "s360_qkv_attention.hip",
-           "s360_transformer_ffn.hip")
+           "s360_transformer_ffn.hip", "s360_mono_fusion.hip")
 # per-source extra flags (s360_backward_em.hip: see the launcher comment in csrc/s360_bwd_em.h)
 SOURCE_FLAGS = {"s360_backward_em.hip": ("-fno-slp-vectorize",)}
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result")
@@ -151,6 +151,10 @@ SIGNATURES = {
     "s360_ffn_tail_high_backward": (_int, [_vp] * 11 + [_i32] * 3 + [_pf64, _vp, _sz] + [_vp] * 9),
     "s360_layer_norm_residual_forward": (_int, [_vp] * 4 + [_i32, _i32, _pf64] + [_vp] * 3),
     "s360_layer_norm_residual_backward": (_int, [_vp] * 4 + [_i32, _i32, _vp, _sz] + [_vp] * 5),
+    "s360_mono_fusion_scratch_bytes": (_sz, [_i32, _i32]),
+    "s360_mono_fusion_weight_chunks": (_int, [_i32]),
+    "s360_mono_fusion_forward": (_int, [_vp] * 7 + [_i32] * 6 + [_pf64] + [_vp] * 4),
+    "s360_mono_fusion_backward": (_int, [_vp] * 10 + [_i32] * 6 + [_pf64, _vp, _sz] + [_vp] * 6),
     "s360_count_backward_slots": (_int, [_prm, _vp, _sz, _vp, _vp]),
     "s360_count_contributions": (_int, [_prm, _vp, _sz, _vp, _vp]),
     "s360_profile_slots": (_int, []),

@@ -16,6 +16,7 @@
 // and sums in plan order: gradients are bit-reproducible.
 #include "s360_device.h"
 #include "s360_prof.h"
+#include "s360_stitch_taps.h"  // unnorm_clip, StitchFrac, stitch_frac
 
 #include <climits>
 #include <mutex>
@@ -28,34 +29,6 @@ struct FaceMap {
     int flip[6];  // 1: read the face flipped on both image axes
     long long fs, cs, rs;  // element strides between faces / channels / rows of the face tensor
 };
-
-__device__ __forceinline__ float unnorm_clip(float g, int size) {
-    float i = ((g + 1.0f) / 2.0f) * (float)(size - 1);
-    return fminf((float)(size - 1), fmaxf(i, 0.0f));
-}
-
-// Corner (x0, y0, z0) and the per-axis weights of pixel i: shared by both kernels so the adjoint's weights are the forward's bits.
-struct StitchFrac {
-    int x0, y0, z0;
-    float wx[2], wy[2], wz[2];
-};
-
-__device__ __forceinline__ StitchFrac stitch_frac(const float* __restrict__ grid, size_t i, int fw) {
-    const float ix = unnorm_clip(grid[3 * i], fw), iy = unnorm_clip(grid[3 * i + 1], fw), iz = unnorm_clip(grid[3 * i + 2], 6);
-    const float x0f = floorf(ix), y0f = floorf(iy), z0f = floorf(iz);
-    const float fx = ix - x0f, fy = iy - y0f, fz = iz - z0f;
-    StitchFrac f;
-    f.x0 = (int)x0f;
-    f.y0 = (int)y0f;
-    f.z0 = (int)z0f;
-    f.wx[0] = 1.0f - fx;
-    f.wx[1] = fx;
-    f.wy[0] = 1.0f - fy;
-    f.wy[1] = fy;
-    f.wz[0] = 1.0f - fz;
-    f.wz[1] = fz;
-    return f;
-}
 
 __global__ __launch_bounds__(S360_BLOCK) void k_cube2erp_fwd(const float* __restrict__ faces, const float* __restrict__ grid,
                                                             float* __restrict__ erp, int C, int fw, int eh, int ew, FaceMap fm) {

@@ -1056,6 +1056,39 @@ TRANSFORMER_FFN_SEAM = _MethodSeam("transformer_ffn", TRANSFORMER_FFN_MODULE, TR
                                    {TRANSFORMER_FFN_METHOD: _native_transformer_layer_forward}, context=True)
 
 
+MONO_FUSION_MODULE = DEPTH_TAIL_MODULE                                 # defines EncoderCostVolume (:119-125 rgbd_fusion, :297 c2e, :351-354)
+MONO_FUSION_CLASS = DEPTH_TAIL_CLASS
+MONO_FUSION_METHOD = "__init__"
+MONO_FUSION_NETS = ("rgbd_fusion", "c2e")
+
+
+def _native_encoder_init(replaced):
+    """EncoderCostVolume.__init__ with the reference's signature: the replaced constructor, then — only for an instance that has
+    rgbd_fusion (add_mono_feat) — rgbd_fusion becomes a mono_fusion.FusedMonoFusion over the same four child modules (the same
+    Parameter objects at the same indices: state-dict keys and the reference's checkpoints unchanged) and c2e.forward is rebound on
+    the instance (mono_fusion.wrap_stitch; c2e.sample_grid stays where it is) so that the no-grad mono stitch returns a
+    MonoStitchHandle."""
+    import functools
+
+    from . import mono_fusion as _mf
+
+    @functools.wraps(replaced)
+    def __init__(self, *args, **kwargs):
+        replaced(self, *args, **kwargs)
+        fusion, c2e = (getattr(self, name, None) for name in MONO_FUSION_NETS)
+        if isinstance(fusion, torch.nn.Sequential) and isinstance(c2e, torch.nn.Module):
+            if not isinstance(fusion, _mf.FusedMonoFusion):
+                self.rgbd_fusion = _mf.FusedMonoFusion.from_sequential(fusion)
+            _mf.wrap_stitch(c2e, self.rgbd_fusion)
+
+    __init__.replaced = replaced
+    return __init__
+
+
+MONO_FUSION_SEAM = _MethodSeam("mono_fusion", MONO_FUSION_MODULE, MONO_FUSION_CLASS, (MONO_FUSION_METHOD,),
+                               {MONO_FUSION_METHOD: _native_encoder_init})
+
+
 # install()'s option keywords -> their seams, in installation order; the decoder registry (DECODER_SEAM) comes after them.
 # uninstall() restores exactly these, so a new seam is a new entry here and nothing else.
 OPTION_SEAMS = {
@@ -1074,6 +1107,7 @@ OPTION_SEAMS = {
     "group_norm": GROUP_NORM_SEAMS,
     "unet_attention": UNET_ATTENTION_SEAMS,
     "transformer_ffn": (TRANSFORMER_FFN_SEAM,),
+    "mono_fusion": (MONO_FUSION_SEAM,),
 }
 
 
@@ -1141,6 +1175,14 @@ def install_transformer_ffn(precision: str = "highest"):
     return _installed("transformer_ffn", precision=_precision.seam_option("transformer_ffn_precision", precision))[0]
 
 
+def install_mono_fusion():
+    """The half of install(mono_fusion=True): rebind EncoderCostVolume.__init__ (encoder_costvolume.py) to the wrapper that turns a
+    new encoder's rgbd_fusion into a mono_fusion.FusedMonoFusion and wraps its c2e, now if the module is imported, else as soon as
+    it is (import hook).  Returns the patched method or None.  Encoders built before the call keep their modules;
+    mono_fusion.FusedMonoFusion.from_sequential and mono_fusion.wrap_stitch are the direct API for them."""
+    return _installed("mono_fusion")[0]
+
+
 def install_depth_smoothness():
     """The half of install(depth_smoothness=True): rebind LossDepth.forward (src/loss/loss_depth.py:27-60) to the wrapper around
     the depth-smoothness kernels now if the reference's module is imported, else as soon as it is (import hook).  Returns the
@@ -1199,7 +1241,7 @@ def install_psnr():
 def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optional[dict] = None, metrics: bool = False,
             depth_loss: bool = False, depth_metrics: bool = False, psnr: bool = False, cost_volume: bool = False, depth_head: bool = False, depth_tail: bool = False,
             erp_distance: bool = False, visualization: bool = False, depth_smoothness: bool = False, window_attention: bool = False,
-            group_norm: bool = False, unet_attention: bool = False, transformer_ffn: bool = False, **opts):
+            group_norm: bool = False, unet_attention: bool = False, transformer_ffn: bool = False, mono_fusion: bool = False, **opts):
     """Register the fused decoder under the reference's registry key "splatting_cuda".  Returns the class (lazy=False) or None.
     adapter=True: ALSO replace the encoder's GaussianAdapterERP (gaussian_adapter_erp.py:33-119) by the lazy-field adapter of lazy.py,
     so that the registered decoder renders straight from the encoder's raw outputs (no [G,3,25] harmonics / [G,3,3] covariances in
@@ -1248,6 +1290,20 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     with window_attention in either order; state_dict keys are unchanged).  transformer_ffn_precision: "highest" (the default),
     "high" (bf16x3 products on the bf16 MFMA in ffn_tail, forward and backward) or "torch" (torch's setting at every call);
     independent of window_attention_precision.
+    mono_fusion=True: ALSO rebind EncoderCostVolume.__init__ (encoder_costvolume.py) so that an encoder built with add_mono_feat
+    gets a mono_fusion.FusedMonoFusion as rgbd_fusion (the same four children and Parameter objects: state-dict keys 0.weight,
+    1.weight, 1.bias, 3.weight unchanged) and a c2e whose forward, called with grad disabled on a 4-D float32 GPU tensor of
+    rgbd_fusion[0].in_features - out_features channels at widths the kernels take (C = 128, Cm a multiple of 64 in 64 .. 1024),
+    returns a mono_fusion.MonoStitchHandle in place of the stitched [(b v), Cm, h, w] map (:297) — metadata and no data; every other
+    call runs the module's own forward and returns its bits; c2e.sample_grid and its state-dict key are unchanged.  The handle stays
+    lazy through exactly what the reference does next: torch.cat([trans_features, handle], dim=1) (:351), the permute(0, 2, 3, 1)
+    that einops' rearrange issues for "bv c h w -> bv h w c" (:353), same-shape reshapes and metadata queries.  FusedMonoFusion then
+    runs the fused kernels of splatter360_amd.mono_fusion — the stitch, the concatenation, Linear, LayerNorm, ReLU, Linear in one
+    forward kernel and a three-launch backward that form neither the stitched map nor the [(b v), C + Cm, h, w] concatenation — and
+    returns out.permute(0, 2, 3, 1), so the rearrange back (:354) yields a dense NCHW tensor.  Any other operation on a handle
+    first materialises it (the stitch by c2e's own forward under no_grad, then torch's cat and permute) and runs on the real tensor
+    with the reference's values.  install_mono_fusion; off by default; composes with depth_tail, whose method seam sits on the same
+    class, in either order; uninstall() restores the class (encoders built meanwhile keep their modules).
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
@@ -1275,7 +1331,7 @@ def uninstall() -> None:
     compute_l1_sphere_loss, erode, warp_with_pose_depth_candidates, depth_to_distance_map_batch, depth_map, prep_image,
     apply_color_map, EncoderCostVolume.map_pdf_to_opacity, LossDepth.forward, the backbone module's four attention functions,
     ResBlock._forward, AttentionBlock._forward, ResidualBlock.forward, DepthPredictorMultiView360.__init__,
-    QKVAttentionLegacy.forward, QKVAttention.forward, TransformerLayer.forward and the predictor
+    QKVAttentionLegacy.forward, QKVAttention.forward, TransformerLayer.forward, EncoderCostVolume.__init__ and the predictor
     module's `F` (torch.nn.functional itself) back (and drop pending import hooks)."""
     sys.meta_path[:] = [f for f in sys.meta_path if not isinstance(f, _SeamPatcher)]
     for seams in (*OPTION_SEAMS.values(), (DECODER_SEAM,)):
