@@ -1275,6 +1275,35 @@ int s360_mono_fusion_backward(const float* erp_feat, const float* mono_cube, con
                               int32_t channels, int32_t mono_channels, int32_t face_w, int32_t equ_h, int32_t equ_w, const double* eps,
                               void* scratch, size_t scratch_bytes, float* g_erp_feat, float* g_w1, float* g_ln_weight, float* g_ln_bias,
                               float* g_w2, void* stream);
+/*
+ * The "high" precision mode of the mono-feature fusion: the same function and the same tensors with the two products of the
+ * forward ([e, m] w1^T, a w2^T) and the four of the backward (g_out w2, g_y w1[:, :channels], g_y^T [e, m], g_out^T a) as bf16x3
+ * products on v_mfma_f32_32x32x16_bf16 — each float32 operand the sum of two bfloat16 numbers (hi = bf16(x) round to nearest
+ * even, lo = bf16(x - hi)), A B = Ah Bh + Ah Bl + Al Bh accumulated in float32 by the MFMA — which is what
+ * torch.set_float32_matmul_precision('high') asks for.  m is the float32 8-tap stitch as above, taken inside the kernels; the
+ * LayerNorm rows, statistics, the ReLU mask and the parameter gradients' partial sums stay float64; y, a, g_y and the partials are
+ * rounded to float32 as above; the launch geometry, g_y's hand-over through scratch and the last launch are those above.  A
+ * pre-pass (one launch per call) splits w1 and w2 into bf16 planes at the start of `scratch`, in the layouts their uses need:
+ * 4 channels (4 channels + mono_channels) bytes (0.75 MiB at mono_channels = 1024) whatever tokens.  The token-side operands
+ * are split in registers and LDS: no plane grows with tokens, and neither the stitched map nor the concatenation exists.
+ * s360_mono_fusion_high_scratch_bytes(tokens, mono_channels, backward): the planes (backward == 0) or the planes and
+ * s360_mono_fusion_scratch_bytes (backward != 0); a multiple of 16; 0 for tokens < 1 or an unsupported mono_channels.  The
+ * contents need no initialisation and nothing in it is read by a later call: the backward splits again.  y and stats of a "high"
+ * forward go to the "high" backward.
+ * Refusals as s360_mono_fusion_*, and for the forward's scratch as for the backward's: null or not 16-byte aligned S360_E_BADARG,
+ * smaller than reported S360_E_WORKSPACE, unsupported widths S360_E_UNSUPPORTED, all before any GPU work.  No atomics, no host
+ * synchronisation, bit-identical from run to run and across streams.
+ */
+size_t s360_mono_fusion_high_scratch_bytes(int32_t tokens, int32_t mono_channels, int32_t backward);
+int s360_mono_fusion_high_forward(const float* erp_feat, const float* mono_cube, const float* grid, const float* w1, const float* ln_weight,
+                                  const float* ln_bias, const float* w2, int32_t n, int32_t channels, int32_t mono_channels,
+                                  int32_t face_w, int32_t equ_h, int32_t equ_w, const double* eps, float* out, float* y, double* stats,
+                                  void* scratch, size_t scratch_bytes, void* stream);
+int s360_mono_fusion_high_backward(const float* erp_feat, const float* mono_cube, const float* grid, const float* w1,
+                                   const float* ln_weight, const float* ln_bias, const float* w2, const float* y, const double* stats,
+                                   const float* g_out, int32_t n, int32_t channels, int32_t mono_channels, int32_t face_w, int32_t equ_h,
+                                   int32_t equ_w, const double* eps, void* scratch, size_t scratch_bytes, float* g_erp_feat, float* g_w1,
+                                   float* g_ln_weight, float* g_ln_bias, float* g_w2, void* stream);
 
 /*
  * Optional measurement aid (no reference counterpart; the reference's Benchmarker is an

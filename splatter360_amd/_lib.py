@@ -155,6 +155,9 @@ SIGNATURES = {
     "s360_mono_fusion_weight_chunks": (_int, [_i32]),
     "s360_mono_fusion_forward": (_int, [_vp] * 7 + [_i32] * 6 + [_pf64] + [_vp] * 4),
     "s360_mono_fusion_backward": (_int, [_vp] * 10 + [_i32] * 6 + [_pf64, _vp, _sz] + [_vp] * 6),
+    "s360_mono_fusion_high_scratch_bytes": (_sz, [_i32, _i32, _i32]),
+    "s360_mono_fusion_high_forward": (_int, [_vp] * 7 + [_i32] * 6 + [_pf64] + [_vp] * 4 + [_sz, _vp]),
+    "s360_mono_fusion_high_backward": (_int, [_vp] * 10 + [_i32] * 6 + [_pf64, _vp, _sz] + [_vp] * 6),
     "s360_count_backward_slots": (_int, [_prm, _vp, _sz, _vp, _vp]),
     "s360_count_contributions": (_int, [_prm, _vp, _sz, _vp, _vp]),
     "s360_profile_slots": (_int, []),

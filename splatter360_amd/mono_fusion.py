@@ -17,6 +17,14 @@ torch is what profiles/mono_fusion_timing.json says it is.  Float32 GPU tensors,
 three vit_types give 384, 768, 1024); there is no CPU path.  Forward and backward are bit-identical from run to run: fixed order, no
 atomics.
 
+precision="highest" (the default) forms every product from exact float32 products; precision="high" is what
+torch.set_float32_matmul_precision('high') asks for: each float32 number as the sum of two bfloat16 numbers and each of the two
+products of the forward and the four of the backward as Ah Bh + Ah Bl + Al Bh on the bf16 MFMA, float32 accumulation (the stitch
+stays the float32 8-tap stitch, the LayerNorm rows float64).  The two weights are split once per call into bf16 planes in a scratch
+buffer (under 1 MiB, whatever the token count); the token side is split inside the kernels, so the "high" mode saves what
+"highest" saves.  A forward run in one precision takes its backward in the same one.  `precision.resolve("torch")` reads torch's
+setting at call time.
+
 `install(mono_fusion=True)` (plugin.py) reaches these kernels from the unchanged reference: `MonoStitchHandle` is what the wrapped
 `c2e` returns for the no-grad mono stitch — a torch.Tensor wrapper subclass built like lazy.LazyField, metadata and no data — and
 `FusedMonoFusion` is the rgbd_fusion that recognises it.
@@ -32,7 +40,9 @@ from torch import Tensor, nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from . import precision as _prec
 from ._call import call, ptr
+from .precision import PRECISIONS  # noqa: F401  (the name callers of this module use)
 
 CHANNELS = 128
 MONO_STEP, MONO_MAX = 64, 1024
@@ -51,13 +61,17 @@ def _positive(what: str, name: str, v) -> int:
     return v
 
 
-def scratch_bytes(tokens: int, mono_channels: int) -> int:
-    """The bytes of scratch a backward call allocates for `tokens` tokens and `mono_channels` mono channels
-    (s360_mono_fusion_scratch_bytes); the forward has none."""
+def scratch_bytes(tokens: int, mono_channels: int, backward: bool = True, precision: str = "highest") -> int:
+    """The bytes of scratch a backward (forward, with backward=False) call allocates for `tokens` tokens and `mono_channels` mono
+    channels: "highest" s360_mono_fusion_scratch_bytes for the backward and none for the forward; "high"
+    s360_mono_fusion_high_scratch_bytes, the same plus the weights' bf16 planes, whose size does not depend on tokens."""
+    _prec.check("mono_fusion", precision)
     _positive("scratch_bytes", "tokens", tokens)
     if not supported_widths(CHANNELS, mono_channels):
         raise ValueError(f"scratch_bytes: mono_channels must be a multiple of {MONO_STEP} in {MONO_STEP} .. {MONO_MAX}, got {mono_channels!r}")
-    return int(_lib.lib().s360_mono_fusion_scratch_bytes(tokens, int(mono_channels)))
+    if precision == "high":
+        return int(_lib.lib().s360_mono_fusion_high_scratch_bytes(tokens, int(mono_channels), int(bool(backward))))
+    return int(_lib.lib().s360_mono_fusion_scratch_bytes(tokens, int(mono_channels))) if backward else 0
 
 
 def weight_chunks(tokens: int) -> int:
@@ -128,26 +142,56 @@ def _buffers(what: str, names, shapes, dtypes, device, given: Optional[dict]) ->
     return out
 
 
+def _no_scratch(what: str, precision: str, given) -> None:
+    """Only the "high" call takes the caller's scratch: one handed to a "highest" call would go unused, so it is refused."""
+    if given is not None and precision != "high":
+        raise ValueError(f"{what}: scratch is the buffer of a precision=\"high\" call, got one with precision={precision!r}")
+
+
+def _high_scratch(what: str, tokens: int, mono_channels: int, backward: bool, device, given: Optional[Tensor]) -> Tensor:
+    """The scratch of a "high" call: allocated, or the caller's uint8 buffer (the library checks its size and alignment)."""
+    if given is None:
+        return _prec.scratch(scratch_bytes(tokens, mono_channels, backward, "high"), device)
+    _tensor(what, "scratch", given, dtype=torch.uint8, device=device)
+    if given.dim() != 1 or not given.is_contiguous():
+        raise ValueError(f"{what}: scratch must be a contiguous 1-D uint8 buffer")
+    return given
+
+
 def mono_fusion_forward(erp_feat: Tensor, mono_cube: Tensor, grid: Tensor, w1: Tensor, ln_weight: Tensor, ln_bias: Tensor, w2: Tensor,
-                        eps: float = 1e-5, *, buffers: Optional[dict] = None) -> tuple:
-    """s360_mono_fusion_forward -> (out [N, C, H, W], y [T, C] float32, stats [T, 2] float64), T = N H W.  `buffers`: {name: buffer}
-    for any of FORWARD_OUTPUTS to write into; the others are allocated."""
+                        eps: float = 1e-5, *, buffers: Optional[dict] = None, precision: str = "highest",
+                        scratch: Optional[Tensor] = None) -> tuple:
+    """s360_mono_fusion_forward (precision "high": s360_mono_fusion_high_forward) -> (out [N, C, H, W], y [T, C] float32, stats
+    [T, 2] float64), T = N H W.  `buffers`: {name: buffer} for any of FORWARD_OUTPUTS to write into; the others are allocated.
+    `scratch`: a uint8 buffer of scratch_bytes(T, Cm, False, "high") bytes for the "high" call to use in place of one it
+    allocates; refused (ValueError) with any other precision, whose forward has no scratch."""
+    _prec.check("mono_fusion", precision)
+    _no_scratch("mono_fusion_forward", precision, scratch)
     n, cm, fw, h, w = _checked("mono_fusion_forward", erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, eps)
     args = [_flat(t) for t in (erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2)]
     dev, tokens = erp_feat.device, n * h * w
     out, y, stats = _buffers("mono_fusion_forward", FORWARD_OUTPUTS, ((n, CHANNELS, h, w), (tokens, CHANNELS), (tokens, 2)),
                              (torch.float32, torch.float32, torch.float64), dev, buffers)
-    call("s360_mono_fusion_forward", dev, *(ptr(t) for t in args), n, CHANNELS, cm, fw, h, w, C.byref(C.c_double(float(eps))), ptr(out), ptr(y),
-         ptr(stats))
+    common = (*(ptr(t) for t in args), n, CHANNELS, cm, fw, h, w, C.byref(C.c_double(float(eps))), ptr(out), ptr(y), ptr(stats))
+    if precision == "high":
+        scratch = _high_scratch("mono_fusion_forward", tokens, cm, False, dev, scratch)
+        call("s360_mono_fusion_high_forward", dev, *common, ptr(scratch), scratch.numel())
+    else:
+        call("s360_mono_fusion_forward", dev, *common)
     return out, y, stats
 
 
 def mono_fusion_backward(erp_feat: Tensor, mono_cube: Tensor, grid: Tensor, w1: Tensor, ln_weight: Tensor, ln_bias: Tensor, w2: Tensor,
-                         y: Tensor, stats: Tensor, g_out: Tensor, eps: float = 1e-5, *, buffers: Optional[dict] = None) -> tuple:
-    """s360_mono_fusion_backward -> the gradients in GRADIENTS' order (g_erp_feat, g_w1, g_ln_weight, g_ln_bias, g_w2).  `buffers`:
-    {name: contiguous float32 buffer of the right shape} for any of them to write into (every element is written); the others and
-    the scratch (scratch_bytes) are allocated."""
+                         y: Tensor, stats: Tensor, g_out: Tensor, eps: float = 1e-5, *, buffers: Optional[dict] = None,
+                         precision: str = "highest", scratch: Optional[Tensor] = None) -> tuple:
+    """s360_mono_fusion_backward (precision "high": s360_mono_fusion_high_backward, with y and stats of a "high" forward) -> the
+    gradients in GRADIENTS' order (g_erp_feat, g_w1, g_ln_weight, g_ln_bias, g_w2).  `buffers`: {name: contiguous float32 buffer of
+    the right shape} for any of them to write into (every element is written); the others and the scratch (scratch_bytes) are
+    allocated.  `scratch`: as in mono_fusion_forward, scratch_bytes(T, Cm, True, "high") bytes, refused with any other precision
+    (the "highest" backward allocates its own)."""
     what = "mono_fusion_backward"
+    _prec.check("mono_fusion", precision)
+    _no_scratch(what, precision, scratch)
     n, cm, fw, h, w = _checked(what, erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, eps)
     dev, tokens = erp_feat.device, n * h * w
     _tensor(what, "g_out", g_out, erp_feat.shape, device=dev)
@@ -155,33 +199,37 @@ def mono_fusion_backward(erp_feat: Tensor, mono_cube: Tensor, grid: Tensor, w1: 
     _tensor(what, "stats", stats, (tokens, 2), dtype=torch.float64, device=dev)
     ins = [_flat(t) for t in (erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, y, stats, g_out)]
     outs = _buffers(what, GRADIENTS, [t.shape for t in (erp_feat, w1, ln_weight, ln_bias, w2)], [torch.float32] * 5, dev, buffers)
-    scratch = torch.empty(scratch_bytes(tokens, cm), dtype=torch.uint8, device=dev)
-    call("s360_mono_fusion_backward", dev, *(ptr(t) for t in ins), n, CHANNELS, cm, fw, h, w, C.byref(C.c_double(float(eps))), ptr(scratch),
+    if precision == "high":
+        scratch = _high_scratch(what, tokens, cm, True, dev, scratch)
+    else:
+        scratch = torch.empty(scratch_bytes(tokens, cm), dtype=torch.uint8, device=dev)
+    call("s360_mono_fusion_high_backward" if precision == "high" else "s360_mono_fusion_backward", dev, *(ptr(t) for t in ins), n, CHANNELS, cm, fw, h, w, C.byref(C.c_double(float(eps))), ptr(scratch),
          scratch.numel(), *(ptr(t) for t in outs))
     return tuple(outs)
 
 
 class _MonoFusion(torch.autograd.Function):
-    """Saves the inputs, y [T, C] and the statistics: nothing of Cm or C + Cm channels per token."""
+    """Saves the inputs, y [T, C] and the statistics: nothing of Cm or C + Cm channels per token and, in the "high" mode, none of
+    the bf16 planes (the backward splits the weights again)."""
 
     @staticmethod
-    def forward(ctx, erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, eps):
+    def forward(ctx, erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, eps, precision):
         args = [_flat(t) for t in (erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2)]
-        out, y, stats = mono_fusion_forward(*args, eps)
+        out, y, stats = mono_fusion_forward(*args, eps, precision=precision)
         ctx.save_for_backward(*args, y, stats)
-        ctx.eps = eps
+        ctx.eps, ctx.precision = eps, precision
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_out):
         *args, y, stats = ctx.saved_tensors
-        g_erp, g_w1, g_lnw, g_lnb, g_w2 = mono_fusion_backward(*args, y, stats, g_out.to(torch.float32), ctx.eps)
-        return g_erp, None, None, g_w1, g_lnw, g_lnb, g_w2, None
+        g_erp, g_w1, g_lnw, g_lnb, g_w2 = mono_fusion_backward(*args, y, stats, g_out.to(torch.float32), ctx.eps, precision=ctx.precision)
+        return g_erp, None, None, g_w1, g_lnw, g_lnb, g_w2, None, None
 
 
 def mono_fusion(erp_feat: Tensor, mono_cube: Tensor, grid: Tensor, w1: Tensor, ln_weight: Tensor, ln_bias: Tensor, w2: Tensor,
-                eps: float = 1e-5) -> Tensor:
+                eps: float = 1e-5, precision: str = "highest") -> Tensor:
     """relu(LN(cat([erp_feat, Cube2Equirec(mono_cube)], 1) w1^T)) w2^T over the channels -> out [N, C, H, W] (dense NCHW): the
     reference's encoder_costvolume.py:297 and :351-354.
 
@@ -190,12 +238,14 @@ def mono_fusion(erp_feat: Tensor, mono_cube: Tensor, grid: Tensor, w1: Tensor, l
     w2 [C, C] in nn.Linear's layout, no biases; ln_weight, ln_bias [C] (nn.LayerNorm's affine parameters, biased variance, eps).
     Differentiable (once) in erp_feat and the four parameters.  mono_cube is a constant: a mono_cube that requires a gradient is a
     RuntimeError (the reference stitches it under torch.no_grad()).  Float32 GPU tensors, C = 128, Cm a multiple of 64 in
-    64 .. 1024; no CPU path; a non-contiguous input is copied once."""
+    64 .. 1024; no CPU path; a non-contiguous input is copied once.  precision "highest": exact float32 products; "high": bf16x3
+    products on the bf16 MFMA, forward and backward (the module's docstring)."""
+    _prec.check("mono_fusion", precision)
     _checked("mono_fusion", erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, eps)
     if mono_cube.requires_grad:
         raise RuntimeError("mono_fusion: mono_cube requires a gradient, but the mono features are a constant of the fused kernels (the "
                            "reference stitches them under torch.no_grad()): detach it, or use the modules' own forward")
-    return _MonoFusion.apply(erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, float(eps))
+    return _MonoFusion.apply(erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, float(eps), precision)
 
 
 # ------------------------------------------------------------------------------------------------ the seam's two halves
@@ -313,7 +363,11 @@ class FusedMonoFusion(nn.Sequential):
     """The reference's rgbd_fusion with its four children (state-dict keys 0.weight, 1.weight, 1.bias, 3.weight).  Handed the
     channel-last MonoStitchHandle of the installed seam it runs `mono_fusion` on what the handle holds and returns
     out.permute(0, 2, 3, 1), so that the reference's rearrange back to "bv c h w" yields a dense NCHW tensor; any other input runs
-    nn.Sequential.forward on the real tensor."""
+    nn.Sequential.forward on the real tensor.  `precision`: "highest" (the default), "high" or "torch", the precision of
+    mono_fusion's products, resolved by precision.resolve at every call ("torch": torch.get_float32_matmul_precision() then); the
+    installed seam stamps it with its mono_fusion_precision option."""
+
+    precision = "highest"
 
     @classmethod
     def from_sequential(cls, seq: nn.Sequential) -> "FusedMonoFusion":
@@ -327,7 +381,7 @@ class FusedMonoFusion(nn.Sequential):
                     and supported_widths(self[0].out_features, self[0].in_features - self[0].out_features)
                     and int(x._s360_erp.shape[1]) == self[0].out_features and grid.device == x.device):
                 out = mono_fusion(x._s360_erp, x._s360_cube, grid.detach()[0, 0], self[0].weight, self[1].weight, self[1].bias, self[3].weight,
-                                  float(self[1].eps))
+                                  float(self[1].eps), precision=_prec.resolve(self.precision))
                 return out.permute(*_CHANNELS_LAST)
             x = x.materialise()
         return super().forward(x)

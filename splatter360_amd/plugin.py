@@ -1062,15 +1062,17 @@ MONO_FUSION_METHOD = "__init__"
 MONO_FUSION_NETS = ("rgbd_fusion", "c2e")
 
 
-def _native_encoder_init(replaced):
+def _native_encoder_init(replaced, mod=None, precision="highest"):
     """EncoderCostVolume.__init__ with the reference's signature: the replaced constructor, then — only for an instance that has
     rgbd_fusion (add_mono_feat) — rgbd_fusion becomes a mono_fusion.FusedMonoFusion over the same four child modules (the same
     Parameter objects at the same indices: state-dict keys and the reference's checkpoints unchanged) and c2e.forward is rebound on
     the instance (mono_fusion.wrap_stitch; c2e.sample_grid stays where it is) so that the no-grad mono stitch returns a
-    MonoStitchHandle."""
+    MonoStitchHandle.  precision: the seam's option; the encoder's FusedMonoFusion is stamped with it (and resolves "torch" at
+    every call); `__init__.precision` holds it."""
     import functools
 
     from . import mono_fusion as _mf
+    _precision.seam_option("mono_fusion_precision", precision)
 
     @functools.wraps(replaced)
     def __init__(self, *args, **kwargs):
@@ -1079,14 +1081,16 @@ def _native_encoder_init(replaced):
         if isinstance(fusion, torch.nn.Sequential) and isinstance(c2e, torch.nn.Module):
             if not isinstance(fusion, _mf.FusedMonoFusion):
                 self.rgbd_fusion = _mf.FusedMonoFusion.from_sequential(fusion)
+            self.rgbd_fusion.precision = precision
             _mf.wrap_stitch(c2e, self.rgbd_fusion)
 
     __init__.replaced = replaced
+    __init__.precision = precision
     return __init__
 
 
 MONO_FUSION_SEAM = _MethodSeam("mono_fusion", MONO_FUSION_MODULE, MONO_FUSION_CLASS, (MONO_FUSION_METHOD,),
-                               {MONO_FUSION_METHOD: _native_encoder_init})
+                               {MONO_FUSION_METHOD: _native_encoder_init}, context=True)
 
 
 # install()'s option keywords -> their seams, in installation order; the decoder registry (DECODER_SEAM) comes after them.
@@ -1175,12 +1179,14 @@ def install_transformer_ffn(precision: str = "highest"):
     return _installed("transformer_ffn", precision=_precision.seam_option("transformer_ffn_precision", precision))[0]
 
 
-def install_mono_fusion():
+def install_mono_fusion(precision: str = "highest"):
     """The half of install(mono_fusion=True): rebind EncoderCostVolume.__init__ (encoder_costvolume.py) to the wrapper that turns a
     new encoder's rgbd_fusion into a mono_fusion.FusedMonoFusion and wraps its c2e, now if the module is imported, else as soon as
-    it is (import hook).  Returns the patched method or None.  Encoders built before the call keep their modules;
-    mono_fusion.FusedMonoFusion.from_sequential and mono_fusion.wrap_stitch are the direct API for them."""
-    return _installed("mono_fusion")[0]
+    it is (import hook).  Returns the patched method or None.  Encoders built before the call keep their modules (and the
+    precision they were built with); mono_fusion.FusedMonoFusion.from_sequential and mono_fusion.wrap_stitch are the direct API
+    for them.  precision: "highest" (exact float32 products), "high" (bf16x3 products, mono_fusion.py) or "torch"
+    (torch.get_float32_matmul_precision() at every call: 'highest' is "highest", 'high' and 'medium' are "high")."""
+    return _installed("mono_fusion", precision=_precision.seam_option("mono_fusion_precision", precision))[0]
 
 
 def install_depth_smoothness():
@@ -1283,7 +1289,7 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     no [b heads, L, L] weight tensor (install_unet_attention; off by default; composes with group_norm, whose AttentionBlock._forward
     calls self.attention, and with the reference's checkpoint).  unet_attention_precision: "highest" (the default), "high" (bf16x3
     products on the bf16 MFMA, forward and backward) or "torch" (torch's setting at every call, the checkpoint's recomputation
-    included); independent of the other two precisions.
+    included); independent of the other precisions.
     transformer_ffn=True: ALSO rebind the multi-view transformer's TransformerLayer.forward (multiview_transformer.py:334-414) so
     that norm1, cat([source, message]), the mlp, norm2 and the residual behind the layer's attention run the fused kernels of
     splatter360_amd.transformer_ffn, which form no [T, 2C] or [T, 8C] tensor (install_transformer_ffn; off by default; composes
@@ -1304,15 +1310,17 @@ def install(*, lazy: bool = False, adapter: bool = False, adapter_options: Optio
     first materialises it (the stitch by c2e's own forward under no_grad, then torch's cat and permute) and runs on the real tensor
     with the reference's values.  install_mono_fusion; off by default; composes with depth_tail, whose method seam sits on the same
     class, in either order; uninstall() restores the class (encoders built meanwhile keep their modules).
+    mono_fusion_precision: "highest" (the default), "high" (bf16x3 products on the bf16 MFMA, forward and backward) or "torch"
+    (torch's setting at every call); stamped on each new encoder's FusedMonoFusion, independent of the other three precisions.
 
     lazy=False: imports `src.model.decoder` now (the reference must be importable: its repository root on sys.path) and patches
     its DECODERS dict in place — `get_decoder` reads the dict at call time, so every later `get_decoder(cfg, dataset_cfg)` builds
     the fused decoder.  lazy=True: only installs an import hook that patches the registry when the reference itself first imports
     the package (for a sitecustomize that runs before sys.path is set up).  Idempotent.
-    opts: window_attention_precision, unet_attention_precision, transformer_ffn_precision (above); for the decoder views_per_group (6), shared_campos (None = checked per group with one small read per forward), check ("sync"), glue."""
+    opts: window_attention_precision, unet_attention_precision, transformer_ffn_precision, mono_fusion_precision (above); for the decoder views_per_group (6), shared_campos (None = checked per group with one small read per forward), check ("sync"), glue."""
     given = locals()
     # an option of a seam, not a seam: taken out of opts (the decoder's options) before they reach the decoder
-    for seam in ("window_attention", "unet_attention", "transformer_ffn"):
+    for seam in ("window_attention", "unet_attention", "transformer_ffn", "mono_fusion"):
         option = seam + "_precision"
         given[seam + "_options"] = {"precision": _precision.seam_option(option, opts.pop(option, "highest"))}
     for keyword, seams in OPTION_SEAMS.items():

@@ -1,4 +1,5 @@
-"""The one precision rule of the operators that have a "high" mode (window_attention, qkv_attention, transformer_ffn).
+"""The one precision rule of the four operators that have a "high" mode (window_attention, qkv_attention, transformer_ffn,
+mono_fusion): every kernel of the package that uses the matrix unit obeys it.
 
 precision="highest" forms every product from exact float32 products; precision="high" is what
 torch.set_float32_matmul_precision('high') asks for: each float32 number as the sum of two bfloat16 numbers and each product
