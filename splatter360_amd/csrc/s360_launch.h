@@ -1,5 +1,6 @@
 // s360_launch.h — host-side rules every entry point of the library shares: the check after a launch, the bound on a grid,
-// pointer alignment, the workspace-size protocol of include/s360.h and the check of a "high" call's scratch.
+// pointer alignment, the pointer rule of an entry's inputs and outputs, the workspace-size protocol of include/s360.h and the
+// check of a "high" call's scratch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,6 +36,22 @@ static inline bool s360_grid_fits(long long blocks) { return blocks <= 0x7ffffff
 
 // p is a multiple of a (a power of two)
 static inline bool s360_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+// The pointer rule of include/s360.h for one entry point: `in` is what the call reads, `out` what it writes, the caller's
+// scratch among them.  Every pointer is non-null and 16-byte aligned, no output is an input and no two outputs are the same.
+template <size_t NI, size_t NO>
+static inline bool s360_pointers_ok(const void* const (&in)[NI], const void* const (&out)[NO]) {
+    for (const void* p : in)
+        if (!p || !s360_aligned(p, 16)) return false;
+    for (size_t i = 0; i < NO; ++i) {
+        if (!out[i] || !s360_aligned(out[i], 16)) return false;
+        for (const void* p : in)
+            if (p == out[i]) return false;
+        for (size_t j = i + 1; j < NO; ++j)
+            if (out[j] == out[i]) return false;
+    }
+    return true;
+}
 
 // The workspace-size protocol of include/s360.h.  workspace == NULL is the size query: *bytes = need, S360_OK.  Otherwise
 // args_ok (the entry point's own pointer checks) and the alignment of the workspace come first, S360_E_BADARG, then the size,

@@ -530,77 +530,6 @@ static int mf_sizes(int32_t n, int32_t channels, int32_t mono_channels, int32_t 
 
 }  // namespace s360
 
-using namespace s360;
-
-extern "C" size_t s360_mono_fusion_scratch_bytes(int32_t tokens, int32_t mono_channels) {
-    if (tokens < 1 || !mf_widths(MF_C, mono_channels)) return 0;
-    return (size_t)tokens * MF_C * sizeof(float) + (size_t)mf_chunks(tokens) * MF_C * (2 * MF_C + mono_channels) * sizeof(float) +
-           (size_t)mf_token_wgs(tokens) * 2 * MF_C * sizeof(double);
-}
-
-extern "C" int s360_mono_fusion_weight_chunks(int32_t tokens) { return tokens < 1 ? 0 : mf_chunks(tokens); }
-
-extern "C" int s360_mono_fusion_forward(const float* erp_feat, const float* mono_cube, const float* grid, const float* w1, const float* ln_weight,
-                                        const float* ln_bias, const float* w2, int32_t n, int32_t channels, int32_t mono_channels,
-                                        int32_t face_w, int32_t equ_h, int32_t equ_w, const double* eps, float* out, float* y, double* stats,
-                                        void* stream) {
-    const void* in[] = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2};
-    void* outs[] = {out, y, stats};
-    for (const void* o : outs) {
-        if (!o || !s360_aligned(o, 16)) return S360_E_BADARG;
-        for (const void* p : in)
-            if (!p || !s360_aligned(p, 16) || p == o) return S360_E_BADARG;
-    }
-    if (out == y || (void*)out == (void*)stats || (void*)y == (void*)stats) return S360_E_BADARG;
-    if (!eps || !(*eps > 0.0)) return S360_E_BADARG;
-    int64_t tokens = 0;
-    const int rc = mf_sizes(n, channels, mono_channels, face_w, equ_h, equ_w, &tokens);
-    if (rc != S360_OK) return rc;
-    const MFArgs a = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, (int)tokens, equ_h * equ_w, mono_channels, face_w, *eps};
-    hipLaunchKernelGGL(k_mf_forward, dim3((unsigned)((tokens + MF_TM - 1) / MF_TM)), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, out, y, stats);
-    return s360_launch_status();
-}
-
-extern "C" int s360_mono_fusion_backward(const float* erp_feat, const float* mono_cube, const float* grid, const float* w1,
-                                         const float* ln_weight, const float* ln_bias, const float* w2, const float* y, const double* stats,
-                                         const float* g_out, int32_t n, int32_t channels, int32_t mono_channels, int32_t face_w,
-                                         int32_t equ_h, int32_t equ_w, const double* eps, void* scratch, size_t scratch_bytes,
-                                         float* g_erp_feat, float* g_w1, float* g_ln_weight, float* g_ln_bias, float* g_w2, void* stream) {
-    const void* in[] = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, y, stats, g_out};
-    void* outs[] = {g_erp_feat, g_w1, g_ln_weight, g_ln_bias, g_w2, scratch};
-    for (const void* p : in)
-        if (!p || !s360_aligned(p, 16)) return S360_E_BADARG;
-    for (const void* o : outs) {
-        if (!o || !s360_aligned(o, 16)) return S360_E_BADARG;
-        for (const void* p : in)
-            if (p == o) return S360_E_BADARG;
-    }
-    for (int i = 0; i < 6; ++i)
-        for (int j = i + 1; j < 6; ++j)
-            if (outs[i] == outs[j]) return S360_E_BADARG;
-    if (!eps || !(*eps > 0.0)) return S360_E_BADARG;
-    int64_t tokens = 0;
-    const int rc = mf_sizes(n, channels, mono_channels, face_w, equ_h, equ_w, &tokens);
-    if (rc != S360_OK) return rc;
-    if (scratch_bytes < s360_mono_fusion_scratch_bytes((int32_t)tokens, mono_channels)) return S360_E_WORKSPACE;
-    const MFArgs a = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, (int)tokens, equ_h * equ_w, mono_channels, face_w, *eps};
-    hipStream_t st = (hipStream_t)stream;
-    const int K = MF_C + mono_channels, chunks = mf_chunks(tokens), wgs = mf_token_wgs(tokens);
-    float* g_y = static_cast<float*>(scratch);
-    float* p_w1 = g_y + (size_t)tokens * MF_C;
-    float* p_w2 = p_w1 + (size_t)chunks * MF_C * K;
-    double* ln_part = reinterpret_cast<double*>(p_w2 + (size_t)chunks * MF_C * MF_C);
-    hipLaunchKernelGGL(k_mf_backward_tokens, dim3(wgs), dim3(S360_BLOCK), 0, st, a, y, stats, g_out, g_erp_feat, g_y, ln_part);
-    S360_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mf_backward_weights, dim3(K / MF_KC + MF_C / MF_KC, chunks), dim3(S360_BLOCK), 0, st, a, y, stats, g_out, g_y,
-                       mf_tiles(tokens), chunks, p_w1, p_w2);
-    S360_CHECK_LAUNCH();
-    const int nw1 = MF_C * K, nw2 = MF_C * MF_C;
-    hipLaunchKernelGGL(k_mf_reduce, dim3((nw1 + nw2 + 2 * MF_C + S360_BLOCK - 1) / S360_BLOCK), dim3(S360_BLOCK), 0, st, p_w1, p_w2, chunks,
-                       nw1, nw2, g_w1, g_w2, ln_part, wgs, g_ln_weight, g_ln_bias);
-    return s360_launch_status();
-}
-
 // ---------------------------------------------------------------------------------------------- the "high" mode (bf16 x 3)
 // The same function with its two products, and the four of the backward, as bf16x3 products (s360_bf16x3.h: the split, the
 // three terms and their order, the B-operand register rule), both operands split from their float32 values: X = [erp_feat, m]
@@ -1009,39 +938,102 @@ static void mfh_split_launch(const float* w1, const float* w2, int K, const MFHP
     hipLaunchKernelGGL(k_mfh_split, dim3((unsigned)((MF_C * K + MF_C * MF_C + S360_BLOCK - 1) / S360_BLOCK)), dim3(S360_BLOCK), 0, st, w1, w2, K, pl);
 }
 
+// ---------------------------------------------------------------------------------------------- the entry points, both modes
+// The caller's scratch, one order in both modes: in "high" the weights' bf16 planes at the front, then, for a backward, g_y
+// [tokens, C], the per-chunk partials of g_w1, those of g_w2 and the LayerNorm partial sums of the token pass's workgroups.
+// Byte offsets; `bytes` is what the *_scratch_bytes functions report.
+struct MFLayout {
+    size_t g_y, p_w1, p_w2, ln_part, bytes;
+};
+static MFLayout mf_layout(int64_t T, int32_t mono_channels, bool high, bool backward) {
+    const size_t tokens = backward ? T : 0, chunks = backward ? mf_chunks(T) : 0, wgs = backward ? mf_token_wgs(T) : 0;
+    MFLayout l;
+    l.g_y = high ? mfh_plane_bytes(mono_channels) : 0;
+    l.p_w1 = l.g_y + tokens * MF_C * sizeof(float);
+    l.p_w2 = l.p_w1 + chunks * MF_C * (MF_C + mono_channels) * sizeof(float);
+    l.ln_part = l.p_w2 + chunks * MF_C * MF_C * sizeof(float);
+    l.bytes = l.ln_part + wgs * 2 * MF_C * sizeof(double);
+    return l;
+}
+
+// What every launch entry starts with, in the order of include/s360.h's refusals: the pointer rule, eps, the sizes.  Completes
+// `a` (the caller has set its pointers) with the sizes and eps, and gives the token count.
+template <size_t NI, size_t NO>
+static int mf_setup(const void* const (&in)[NI], const void* const (&outs)[NO], const double* eps, int32_t n, int32_t channels,
+                    int32_t mono_channels, int32_t face_w, int32_t equ_h, int32_t equ_w, MFArgs& a, int64_t& tokens) {
+    if (!s360_pointers_ok(in, outs)) return S360_E_BADARG;
+    if (!eps || !(*eps > 0.0)) return S360_E_BADARG;
+    const int rc = mf_sizes(n, channels, mono_channels, face_w, equ_h, equ_w, &tokens);
+    if (rc != S360_OK) return rc;
+    a.T = (int)tokens, a.HW = equ_h * equ_w, a.Cm = mono_channels, a.fw = face_w, a.eps = *eps;
+    return S360_OK;
+}
+
+struct MFGrads {
+    float *erp, *w1, *lnw, *lnb, *w2;
+};
+
+// s360_mono_fusion_backward (HIGH = false) and s360_mono_fusion_high_backward (true).  Only declared here and defined behind
+// the two entries, at the end of the file: tests/test_mono_fusion_high_spec.py reads the backward's launches from the text
+// that follows `extern "C" int s360_mono_fusion_high_backward`, so the body has to stay below that entry.
+template <bool HIGH>
+static int mf_backward(MFArgs a, const float* y, const double* stats, const float* g_out, int32_t n, int32_t channels, int32_t mono_channels,
+                       int32_t face_w, int32_t equ_h, int32_t equ_w, const double* eps, void* scratch, size_t scratch_bytes, const MFGrads& g,
+                       hipStream_t st);
+
 }  // namespace s360
 
+using namespace s360;
+
+extern "C" size_t s360_mono_fusion_scratch_bytes(int32_t tokens, int32_t mono_channels) {
+    return tokens < 1 || !mf_widths(MF_C, mono_channels) ? 0 : mf_layout(tokens, mono_channels, false, true).bytes;
+}
+
 extern "C" size_t s360_mono_fusion_high_scratch_bytes(int32_t tokens, int32_t mono_channels, int32_t backward) {
-    if (tokens < 1 || !mf_widths(MF_C, mono_channels)) return 0;
-    return mfh_plane_bytes(mono_channels) + (backward ? s360_mono_fusion_scratch_bytes(tokens, mono_channels) : 0);
+    return tokens < 1 || !mf_widths(MF_C, mono_channels) ? 0 : mf_layout(tokens, mono_channels, true, backward != 0).bytes;
+}
+
+extern "C" int s360_mono_fusion_weight_chunks(int32_t tokens) { return tokens < 1 ? 0 : mf_chunks(tokens); }
+
+extern "C" int s360_mono_fusion_forward(const float* erp_feat, const float* mono_cube, const float* grid, const float* w1, const float* ln_weight,
+                                        const float* ln_bias, const float* w2, int32_t n, int32_t channels, int32_t mono_channels,
+                                        int32_t face_w, int32_t equ_h, int32_t equ_w, const double* eps, float* out, float* y, double* stats,
+                                        void* stream) {
+    MFArgs a = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2};
+    const void* const in[] = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2};
+    const void* const outs[] = {out, y, stats};
+    int64_t tokens = 0;
+    const int rc = mf_setup(in, outs, eps, n, channels, mono_channels, face_w, equ_h, equ_w, a, tokens);
+    if (rc != S360_OK) return rc;
+    hipLaunchKernelGGL(k_mf_forward, dim3((unsigned)((tokens + MF_TM - 1) / MF_TM)), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, out, y, stats);
+    return s360_launch_status();
 }
 
 extern "C" int s360_mono_fusion_high_forward(const float* erp_feat, const float* mono_cube, const float* grid, const float* w1,
                                              const float* ln_weight, const float* ln_bias, const float* w2, int32_t n, int32_t channels,
                                              int32_t mono_channels, int32_t face_w, int32_t equ_h, int32_t equ_w, const double* eps, float* out,
                                              float* y, double* stats, void* scratch, size_t scratch_bytes, void* stream) {
-    const void* in[] = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2};
-    void* outs[] = {out, y, stats, scratch};
-    for (const void* o : outs) {
-        if (!o || !s360_aligned(o, 16)) return S360_E_BADARG;
-        for (const void* p : in)
-            if (!p || !s360_aligned(p, 16) || p == o) return S360_E_BADARG;
-    }
-    for (int i = 0; i < 4; ++i)
-        for (int j = i + 1; j < 4; ++j)
-            if (outs[i] == outs[j]) return S360_E_BADARG;
-    if (!eps || !(*eps > 0.0)) return S360_E_BADARG;
+    MFArgs a = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2};
+    const void* const in[] = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2};
+    const void* const outs[] = {out, y, stats, scratch};
     int64_t tokens = 0;
-    const int rc = mf_sizes(n, channels, mono_channels, face_w, equ_h, equ_w, &tokens);
+    const int rc = mf_setup(in, outs, eps, n, channels, mono_channels, face_w, equ_h, equ_w, a, tokens);
     if (rc != S360_OK) return rc;
-    const int rs = s360_scratch(scratch, scratch_bytes, s360_mono_fusion_high_scratch_bytes((int32_t)tokens, mono_channels, 0));
-    if (rs != S360_OK) return rs;                             // short: after the sizes, as the size depends on them
-    const MFArgs a = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, (int)tokens, equ_h * equ_w, mono_channels, face_w, *eps};
+    if (scratch_bytes < mf_layout(tokens, mono_channels, true, false).bytes) return S360_E_WORKSPACE;   // after the sizes, as the size depends on them
     const MFHPlanes pl = mfh_planes(scratch, MF_C + mono_channels);
     mfh_split_launch(w1, w2, MF_C + mono_channels, pl, (hipStream_t)stream);
     S360_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_mfh_forward, dim3((unsigned)((tokens + MF_TM - 1) / MF_TM)), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, pl, out, y, stats);
     return s360_launch_status();
+}
+
+extern "C" int s360_mono_fusion_backward(const float* erp_feat, const float* mono_cube, const float* grid, const float* w1,
+                                         const float* ln_weight, const float* ln_bias, const float* w2, const float* y, const double* stats,
+                                         const float* g_out, int32_t n, int32_t channels, int32_t mono_channels, int32_t face_w,
+                                         int32_t equ_h, int32_t equ_w, const double* eps, void* scratch, size_t scratch_bytes,
+                                         float* g_erp_feat, float* g_w1, float* g_ln_weight, float* g_ln_bias, float* g_w2, void* stream) {
+    return mf_backward<false>({erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2}, y, stats, g_out, n, channels, mono_channels, face_w, equ_h,
+                              equ_w, eps, scratch, scratch_bytes, {g_erp_feat, g_w1, g_ln_weight, g_ln_bias, g_w2}, (hipStream_t)stream);
 }
 
 extern "C" int s360_mono_fusion_high_backward(const float* erp_feat, const float* mono_cube, const float* grid, const float* w1,
@@ -1050,41 +1042,49 @@ extern "C" int s360_mono_fusion_high_backward(const float* erp_feat, const float
                                               int32_t face_w, int32_t equ_h, int32_t equ_w, const double* eps, void* scratch,
                                               size_t scratch_bytes, float* g_erp_feat, float* g_w1, float* g_ln_weight, float* g_ln_bias,
                                               float* g_w2, void* stream) {
-    const void* in[] = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, y, stats, g_out};
-    void* outs[] = {g_erp_feat, g_w1, g_ln_weight, g_ln_bias, g_w2, scratch};
-    for (const void* p : in)
-        if (!p || !s360_aligned(p, 16)) return S360_E_BADARG;
-    for (const void* o : outs) {
-        if (!o || !s360_aligned(o, 16)) return S360_E_BADARG;
-        for (const void* p : in)
-            if (p == o) return S360_E_BADARG;
-    }
-    for (int i = 0; i < 6; ++i)
-        for (int j = i + 1; j < 6; ++j)
-            if (outs[i] == outs[j]) return S360_E_BADARG;
-    if (!eps || !(*eps > 0.0)) return S360_E_BADARG;
+    return mf_backward<true>({erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2}, y, stats, g_out, n, channels, mono_channels, face_w, equ_h,
+                             equ_w, eps, scratch, scratch_bytes, {g_erp_feat, g_w1, g_ln_weight, g_ln_bias, g_w2}, (hipStream_t)stream);
+}
+
+// The body of the two backward entries above: the pre-pass and the two kernels differ.  It stays below them (see its
+// declaration).
+namespace s360 {
+
+template <bool HIGH>
+static int mf_backward(MFArgs a, const float* y, const double* stats, const float* g_out, int32_t n, int32_t channels, int32_t mono_channels,
+                       int32_t face_w, int32_t equ_h, int32_t equ_w, const double* eps, void* scratch, size_t scratch_bytes, const MFGrads& g,
+                       hipStream_t st) {
+    const void* const in[] = {a.erp, a.cube, a.grid, a.w1, a.lnw, a.lnb, a.w2, y, stats, g_out};
+    const void* const outs[] = {g.erp, g.w1, g.lnw, g.lnb, g.w2, scratch};
     int64_t tokens = 0;
-    const int rc = mf_sizes(n, channels, mono_channels, face_w, equ_h, equ_w, &tokens);
+    const int rc = mf_setup(in, outs, eps, n, channels, mono_channels, face_w, equ_h, equ_w, a, tokens);
     if (rc != S360_OK) return rc;
-    const int rs = s360_scratch(scratch, scratch_bytes, s360_mono_fusion_high_scratch_bytes((int32_t)tokens, mono_channels, 1));   // scratch is one of outs: not null, aligned
-    if (rs != S360_OK) return rs;
-    const MFArgs a = {erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, (int)tokens, equ_h * equ_w, mono_channels, face_w, *eps};
-    hipStream_t st = (hipStream_t)stream;
+    const MFLayout l = mf_layout(tokens, mono_channels, HIGH, true);
+    if (scratch_bytes < l.bytes) return S360_E_WORKSPACE;
     const int K = MF_C + mono_channels, chunks = mf_chunks(tokens), wgs = mf_token_wgs(tokens);
-    const MFHPlanes pl = mfh_planes(scratch, K);
-    float* g_y = reinterpret_cast<float*>(static_cast<char*>(scratch) + mfh_plane_bytes(mono_channels));
-    float* p_w1 = g_y + (size_t)tokens * MF_C;
-    float* p_w2 = p_w1 + (size_t)chunks * MF_C * K;
-    double* ln_part = reinterpret_cast<double*>(p_w2 + (size_t)chunks * MF_C * MF_C);
-    mfh_split_launch(w1, w2, K, pl, st);
-    S360_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mfh_backward_tokens, dim3(wgs), dim3(S360_BLOCK), 0, st, a, pl, y, stats, g_out, g_erp_feat, g_y, ln_part);
-    S360_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mfh_backward_weights, dim3(K / MF_KC + MF_C / MF_KC, chunks), dim3(S360_BLOCK), 0, st, a, y, stats, g_out, g_y,
-                       mf_tiles(tokens), chunks, p_w1, p_w2);
+    char* base = static_cast<char*>(scratch);
+    float *g_y = reinterpret_cast<float*>(base + l.g_y), *p_w1 = reinterpret_cast<float*>(base + l.p_w1);
+    float* p_w2 = reinterpret_cast<float*>(base + l.p_w2);
+    double* ln_part = reinterpret_cast<double*>(base + l.ln_part);
+    if constexpr (HIGH) {
+        const MFHPlanes pl = mfh_planes(scratch, K);
+        mfh_split_launch(a.w1, a.w2, K, pl, st);
+        S360_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_mfh_backward_tokens, dim3(wgs), dim3(S360_BLOCK), 0, st, a, pl, y, stats, g_out, g.erp, g_y, ln_part);
+        S360_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_mfh_backward_weights, dim3(K / MF_KC + MF_C / MF_KC, chunks), dim3(S360_BLOCK), 0, st, a, y, stats, g_out, g_y,
+                           mf_tiles(tokens), chunks, p_w1, p_w2);
+    } else {
+        hipLaunchKernelGGL(k_mf_backward_tokens, dim3(wgs), dim3(S360_BLOCK), 0, st, a, y, stats, g_out, g.erp, g_y, ln_part);
+        S360_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_mf_backward_weights, dim3(K / MF_KC + MF_C / MF_KC, chunks), dim3(S360_BLOCK), 0, st, a, y, stats, g_out, g_y,
+                           mf_tiles(tokens), chunks, p_w1, p_w2);
+    }
     S360_CHECK_LAUNCH();
     const int nw1 = MF_C * K, nw2 = MF_C * MF_C;
     hipLaunchKernelGGL(k_mf_reduce, dim3((nw1 + nw2 + 2 * MF_C + S360_BLOCK - 1) / S360_BLOCK), dim3(S360_BLOCK), 0, st, p_w1, p_w2, chunks,
-                       nw1, nw2, g_w1, g_w2, ln_part, wgs, g_ln_weight, g_ln_bias);
+                       nw1, nw2, g.w1, g.w2, ln_part, wgs, g.lnw, g.lnb);
     return s360_launch_status();
 }
+
+}  // namespace s360

@@ -542,8 +542,6 @@ static int ff_chunk_tokens(int64_t T) {
 static int ff_chunks(int64_t T) { return (int)((T + ff_chunk_tokens(T) - 1) / ff_chunk_tokens(T)); }
 static int ff_token_wgs(int64_t T) { return (int)min((int64_t)FF_TOKEN_WGS, (T + FF_TM - 1) / FF_TM); }
 static int ff_row_wgs(int64_t T) { return (int)min((int64_t)FF_ROW_WGS, (T + FF_ROWS - 1) / FF_ROWS); }
-static size_t ff_partial_floats(int64_t T) { return (size_t)ff_chunks(T) * (FF_H * FF_X + FF_C * FF_H); }
-
 static int ff_sizes(int32_t tokens, int32_t channels, int32_t hidden) {
     if (tokens < 1 || channels < 1 || hidden < 1) return S360_E_BADARG;
     if (channels != FF_C || hidden != FF_H) return S360_E_UNSUPPORTED;
@@ -552,110 +550,6 @@ static int ff_sizes(int32_t tokens, int32_t channels, int32_t hidden) {
 }
 
 }  // namespace s360
-
-using namespace s360;
-
-extern "C" size_t s360_ffn_tail_scratch_bytes(int32_t tokens) {
-    if (tokens < 1) return 0;
-    return ff_partial_floats(tokens) * sizeof(float) + (size_t)max(ff_token_wgs(tokens), ff_row_wgs(tokens)) * 4 * FF_C * sizeof(double);
-}
-
-extern "C" int s360_ffn_tail_weight_chunks(int32_t tokens) { return tokens < 1 ? 0 : ff_chunks(tokens); }
-
-extern "C" int s360_ffn_tail_forward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias,
-                                     const float* w1, const float* w2, const float* norm2_weight, const float* norm2_bias, int32_t tokens,
-                                     int32_t channels, int32_t hidden, const double* eps, float* out, float* z, double* stats, void* stream) {
-    const void* in[] = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias};
-    for (const void* p : in)
-        if (!p || !s360_aligned(p, 16) || p == out || p == z || p == stats) return S360_E_BADARG;
-    if (!eps || !(*eps > 0.0) || !out || !z || !stats || out == z || !s360_aligned(out, 16) || !s360_aligned(z, 16)) return S360_E_BADARG;
-    const int rc = ff_sizes(tokens, channels, hidden);
-    if (rc != S360_OK) return rc;
-    const FFArgs a = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, tokens, *eps};
-    hipLaunchKernelGGL(k_ff_forward, dim3((tokens + FF_TM - 1) / FF_TM), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, out, z, stats);
-    return s360_launch_status();
-}
-
-extern "C" int s360_ffn_tail_backward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias,
-                                      const float* w1, const float* w2, const float* norm2_weight, const float* norm2_bias, const float* z,
-                                      const double* stats, const float* g_out, int32_t tokens, int32_t channels, int32_t hidden,
-                                      const double* eps, void* scratch, size_t scratch_bytes, float* g_source, float* g_m, float* g_w1,
-                                      float* g_w2, float* g_norm1_weight, float* g_norm1_bias, float* g_norm2_weight, float* g_norm2_bias,
-                                      void* stream) {
-    const void* in[] = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, z, stats, g_out};
-    void* outs[] = {g_source, g_m, g_w1, g_w2, g_norm1_weight, g_norm1_bias, g_norm2_weight, g_norm2_bias, scratch};
-    for (const void* o : outs) {
-        if (!o || !s360_aligned(o, 16)) return S360_E_BADARG;
-        for (const void* p : in)
-            if (p == o) return S360_E_BADARG;
-    }
-    for (const void* p : in)
-        if (!p || !s360_aligned(p, 16)) return S360_E_BADARG;
-    for (int i = 0; i < 9; ++i)
-        for (int j = i + 1; j < 9; ++j)
-            if (outs[i] == outs[j]) return S360_E_BADARG;
-    if (!eps || !(*eps > 0.0)) return S360_E_BADARG;
-    const int rc = ff_sizes(tokens, channels, hidden);
-    if (rc != S360_OK) return rc;
-    if (scratch_bytes < s360_ffn_tail_scratch_bytes(tokens)) return S360_E_WORKSPACE;
-    const FFArgs a = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, tokens, *eps};
-    hipStream_t st = (hipStream_t)stream;
-    const int chunks = ff_chunks(tokens), wgs = ff_token_wgs(tokens);
-    float* p_w1 = static_cast<float*>(scratch);
-    float* p_w2 = p_w1 + (size_t)chunks * FF_H * FF_X;
-    double* ln_part = reinterpret_cast<double*>(p_w2 + (size_t)chunks * FF_C * FF_H);
-    hipLaunchKernelGGL(k_ff_backward_tokens, dim3(wgs), dim3(S360_BLOCK), 0, st, a, z, stats, g_out, g_source, g_m, ln_part);
-    S360_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ff_backward_weights, dim3(FF_H / (FF_T * FF_WAVES), chunks), dim3(S360_BLOCK), 0, st, a, z, stats, g_out,
-                       ff_chunk_tokens(tokens), p_w1, p_w2);
-    S360_CHECK_LAUNCH();
-    const int nw1 = FF_H * FF_X, nw2 = FF_C * FF_H, nln = 4 * FF_C;
-    const FFLnOut lo = {{g_norm1_weight, g_norm1_bias, g_norm2_weight, g_norm2_bias}};
-    hipLaunchKernelGGL(k_ff_reduce, dim3((nw1 + nw2 + nln + S360_BLOCK - 1) / S360_BLOCK), dim3(S360_BLOCK), 0, st, p_w1, p_w2, chunks, nw1,
-                       nw2, g_w1, g_w2, ln_part, wgs, nln, lo);
-    return s360_launch_status();
-}
-
-extern "C" int s360_layer_norm_residual_forward(const float* x, const float* weight, const float* bias, const float* residual, int32_t tokens,
-                                                int32_t channels, const double* eps, float* out, double* stats, void* stream) {
-    const void* in[] = {x, weight, bias, residual};
-    for (const void* p : in)
-        if (!p || !s360_aligned(p, 16) || p == out || p == stats) return S360_E_BADARG;
-    if (!eps || !(*eps > 0.0) || !out || !stats || !s360_aligned(out, 16)) return S360_E_BADARG;
-    const int rc = ff_sizes(tokens, channels, FF_H);
-    if (rc != S360_OK) return rc;
-    hipLaunchKernelGGL(k_ff_norm_residual_forward, dim3((tokens + FF_ROWS - 1) / FF_ROWS), dim3(S360_BLOCK), 0, (hipStream_t)stream, x, weight,
-                       bias, residual, tokens, *eps, out, stats);
-    return s360_launch_status();
-}
-
-extern "C" int s360_layer_norm_residual_backward(const float* x, const float* weight, const double* stats, const float* g_out, int32_t tokens,
-                                                 int32_t channels, void* scratch, size_t scratch_bytes, float* g_x, float* g_residual,
-                                                 float* g_weight, float* g_bias, void* stream) {
-    const void* in[] = {x, weight, stats, g_out};
-    void* outs[] = {g_x, g_residual, g_weight, g_bias, scratch};
-    for (const void* o : outs) {
-        if (!o || !s360_aligned(o, 16)) return S360_E_BADARG;
-        for (const void* p : in)
-            if (!p || !s360_aligned(p, 16) || p == o) return S360_E_BADARG;
-    }
-    for (int i = 0; i < 5; ++i)
-        for (int j = i + 1; j < 5; ++j)
-            if (outs[i] == outs[j]) return S360_E_BADARG;
-    const int rc = ff_sizes(tokens, channels, FF_H);
-    if (rc != S360_OK) return rc;
-    if (scratch_bytes < s360_ffn_tail_scratch_bytes(tokens)) return S360_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int wgs = ff_row_wgs(tokens);
-    double* ln_part = static_cast<double*>(scratch);
-    hipLaunchKernelGGL(k_ff_norm_residual_backward, dim3(wgs), dim3(S360_BLOCK), 0, st, x, weight, stats, g_out, tokens, g_x, g_residual, ln_part);
-    S360_CHECK_LAUNCH();
-    const int nln = 2 * FF_C;
-    const FFLnOut lo = {{g_weight, g_bias, nullptr, nullptr}};
-    hipLaunchKernelGGL(k_ff_reduce, dim3((nln + S360_BLOCK - 1) / S360_BLOCK), dim3(S360_BLOCK), 0, st, nullptr, nullptr, 0, 0, 0, nullptr,
-                       nullptr, ln_part, wgs, nln, lo);
-    return s360_launch_status();
-}
 
 // ---------------------------------------------------------------------------------------------- the "high" mode (bf16 x 3)
 // The same function with its two products, and the four of the backward, as bf16x3 products (s360_bf16x3.h: the split, the
@@ -1074,32 +968,125 @@ static void ffh_split_launch(const float* w1, const float* w2, const FFHPlanes& 
     hipLaunchKernelGGL(k_ffh_split, dim3((unsigned)((FFH_W1 + FFH_W2 + S360_BLOCK - 1) / S360_BLOCK)), dim3(S360_BLOCK), 0, st, w1, w2, pl);
 }
 
+// ---------------------------------------------------------------------------------------------- the entry points, both modes
+// The caller's scratch, one order in both modes: in "high" the weights' bf16 planes at the front, then, for a backward, the
+// per-chunk partials of g_w1, those of g_w2 and the LayerNorm partial sums (of the token pass or the row backward, whichever has
+// more workgroups).  Byte offsets; `bytes` is what the *_scratch_bytes functions report.
+struct FFLayout {
+    size_t p_w1, p_w2, ln_part, bytes;
+};
+static FFLayout ff_layout(int64_t T, bool high, bool backward) {
+    const size_t chunks = backward ? ff_chunks(T) : 0, wgs = backward ? max(ff_token_wgs(T), ff_row_wgs(T)) : 0;
+    FFLayout l;
+    l.p_w1 = high ? FFH_PLANE_BYTES : 0;
+    l.p_w2 = l.p_w1 + chunks * FF_H * FF_X * sizeof(float);
+    l.ln_part = l.p_w2 + chunks * FF_C * FF_H * sizeof(float);
+    l.bytes = l.ln_part + wgs * 4 * FF_C * sizeof(double);
+    return l;
+}
+
+// What every launch entry starts with, in the order of include/s360.h's refusals: the pointer rule, eps (has_eps: every entry
+// but the row backward, which reads rstd from stats), the sizes.  After S360_OK *eps may be read.
+template <size_t NI, size_t NO>
+static int ff_setup(const void* const (&in)[NI], const void* const (&outs)[NO], bool has_eps, const double* eps, int32_t tokens,
+                    int32_t channels, int32_t hidden) {
+    if (!s360_pointers_ok(in, outs)) return S360_E_BADARG;
+    if (has_eps && (!eps || !(*eps > 0.0))) return S360_E_BADARG;
+    return ff_sizes(tokens, channels, hidden);
+}
+
+struct FFGrads {
+    float *source, *m, *w1, *w2, *n1w, *n1b, *n2w, *n2b;
+};
+
+// s360_ffn_tail_backward (HIGH = false) and s360_ffn_tail_high_backward (true): the pre-pass and the two kernels differ.
+// `a` comes with its pointers set.
+template <bool HIGH>
+static int ff_backward(FFArgs a, const float* z, const double* stats, const float* g_out, int32_t tokens, int32_t channels, int32_t hidden,
+                       const double* eps, void* scratch, size_t scratch_bytes, const FFGrads& g, hipStream_t st) {
+    const void* const in[] = {a.source, a.m, a.n1w, a.n1b, a.w1, a.w2, a.n2w, a.n2b, z, stats, g_out};
+    const void* const outs[] = {g.source, g.m, g.w1, g.w2, g.n1w, g.n1b, g.n2w, g.n2b, scratch};
+    const int rc = ff_setup(in, outs, true, eps, tokens, channels, hidden);
+    if (rc != S360_OK) return rc;
+    a.T = tokens, a.eps = *eps;
+    const FFLayout l = ff_layout(tokens, HIGH, true);
+    if (scratch_bytes < l.bytes) return S360_E_WORKSPACE;
+    const int chunks = ff_chunks(tokens), wgs = ff_token_wgs(tokens);
+    char* base = static_cast<char*>(scratch);
+    float *p_w1 = reinterpret_cast<float*>(base + l.p_w1), *p_w2 = reinterpret_cast<float*>(base + l.p_w2);
+    double* ln_part = reinterpret_cast<double*>(base + l.ln_part);
+    if constexpr (HIGH) {
+        const FFHPlanes pl = ffh_planes(scratch);
+        ffh_split_launch(a.w1, a.w2, pl, st);
+        S360_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_ffh_backward_tokens, dim3(wgs), dim3(S360_BLOCK), 0, st, a, pl, z, stats, g_out, g.source, g.m, ln_part);
+        S360_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_ffh_backward_weights, dim3(FF_H / (FF_T * FF_WAVES), chunks), dim3(S360_BLOCK), 0, st, a, pl, z, stats, g_out,
+                           ff_chunk_tokens(tokens), p_w1, p_w2);
+    } else {
+        hipLaunchKernelGGL(k_ff_backward_tokens, dim3(wgs), dim3(S360_BLOCK), 0, st, a, z, stats, g_out, g.source, g.m, ln_part);
+        S360_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_ff_backward_weights, dim3(FF_H / (FF_T * FF_WAVES), chunks), dim3(S360_BLOCK), 0, st, a, z, stats, g_out,
+                           ff_chunk_tokens(tokens), p_w1, p_w2);
+    }
+    S360_CHECK_LAUNCH();
+    const int nw1 = FF_H * FF_X, nw2 = FF_C * FF_H, nln = 4 * FF_C;
+    const FFLnOut lo = {{g.n1w, g.n1b, g.n2w, g.n2b}};
+    hipLaunchKernelGGL(k_ff_reduce, dim3((nw1 + nw2 + nln + S360_BLOCK - 1) / S360_BLOCK), dim3(S360_BLOCK), 0, st, p_w1, p_w2, chunks, nw1,
+                       nw2, g.w1, g.w2, ln_part, wgs, nln, lo);
+    return s360_launch_status();
+}
+
 }  // namespace s360
 
+using namespace s360;
+
+extern "C" size_t s360_ffn_tail_scratch_bytes(int32_t tokens) { return tokens < 1 ? 0 : ff_layout(tokens, false, true).bytes; }
+
 extern "C" size_t s360_ffn_tail_high_scratch_bytes(int32_t tokens, int32_t backward) {
-    if (tokens < 1) return 0;
-    return FFH_PLANE_BYTES + (backward ? s360_ffn_tail_scratch_bytes(tokens) : 0);
+    return tokens < 1 ? 0 : ff_layout(tokens, true, backward != 0).bytes;
+}
+
+extern "C" int s360_ffn_tail_weight_chunks(int32_t tokens) { return tokens < 1 ? 0 : ff_chunks(tokens); }
+
+extern "C" int s360_ffn_tail_forward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias,
+                                     const float* w1, const float* w2, const float* norm2_weight, const float* norm2_bias, int32_t tokens,
+                                     int32_t channels, int32_t hidden, const double* eps, float* out, float* z, double* stats, void* stream) {
+    const void* const in[] = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias};
+    const void* const outs[] = {out, z, stats};
+    const int rc = ff_setup(in, outs, true, eps, tokens, channels, hidden);
+    if (rc != S360_OK) return rc;
+    const FFArgs a = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, tokens, *eps};
+    hipLaunchKernelGGL(k_ff_forward, dim3((tokens + FF_TM - 1) / FF_TM), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, out, z, stats);
+    return s360_launch_status();
 }
 
 extern "C" int s360_ffn_tail_high_forward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias,
                                           const float* w1, const float* w2, const float* norm2_weight, const float* norm2_bias,
                                           int32_t tokens, int32_t channels, int32_t hidden, const double* eps, float* out, float* z,
                                           double* stats, void* scratch, size_t scratch_bytes, void* stream) {
-    const void* in[] = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias};
-    for (const void* p : in)
-        if (!p || !s360_aligned(p, 16) || p == out || p == z || p == stats || p == scratch) return S360_E_BADARG;
-    if (!eps || !(*eps > 0.0) || !out || !z || !stats || out == z || !s360_aligned(out, 16) || !s360_aligned(z, 16)) return S360_E_BADARG;
-    const int rs = s360_scratch(scratch, scratch_bytes, s360_ffn_tail_high_scratch_bytes(tokens, 0));
-    if (rs == S360_E_BADARG || scratch == out || scratch == z || scratch == stats) return S360_E_BADARG;
-    const int rc = ff_sizes(tokens, channels, hidden);
+    const void* const in[] = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias};
+    const void* const outs[] = {out, z, stats, scratch};
+    const int rc = ff_setup(in, outs, true, eps, tokens, channels, hidden);
     if (rc != S360_OK) return rc;
-    if (rs != S360_OK) return rs;                             // short: after the sizes, as the size depends on them
     const FFArgs a = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, tokens, *eps};
+    if (scratch_bytes < ff_layout(tokens, true, false).bytes) return S360_E_WORKSPACE;   // after the sizes, as the size depends on them
     const FFHPlanes pl = ffh_planes(scratch);
     ffh_split_launch(w1, w2, pl, (hipStream_t)stream);
     S360_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_ffh_forward, dim3((tokens + FF_TM - 1) / FF_TM), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, pl, out, z, stats);
     return s360_launch_status();
+}
+
+extern "C" int s360_ffn_tail_backward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias,
+                                      const float* w1, const float* w2, const float* norm2_weight, const float* norm2_bias, const float* z,
+                                      const double* stats, const float* g_out, int32_t tokens, int32_t channels, int32_t hidden,
+                                      const double* eps, void* scratch, size_t scratch_bytes, float* g_source, float* g_m, float* g_w1,
+                                      float* g_w2, float* g_norm1_weight, float* g_norm1_bias, float* g_norm2_weight, float* g_norm2_bias,
+                                      void* stream) {
+    return ff_backward<false>({source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias}, z, stats, g_out, tokens, channels, hidden,
+                              eps, scratch, scratch_bytes,
+                              {g_source, g_m, g_w1, g_w2, g_norm1_weight, g_norm1_bias, g_norm2_weight, g_norm2_bias}, (hipStream_t)stream);
 }
 
 extern "C" int s360_ffn_tail_high_backward(const float* source, const float* m, const float* norm1_weight, const float* norm1_bias,
@@ -1108,40 +1095,38 @@ extern "C" int s360_ffn_tail_high_backward(const float* source, const float* m, 
                                            int32_t hidden, const double* eps, void* scratch, size_t scratch_bytes, float* g_source,
                                            float* g_m, float* g_w1, float* g_w2, float* g_norm1_weight, float* g_norm1_bias,
                                            float* g_norm2_weight, float* g_norm2_bias, void* stream) {
-    const void* in[] = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, z, stats, g_out};
-    void* outs[] = {g_source, g_m, g_w1, g_w2, g_norm1_weight, g_norm1_bias, g_norm2_weight, g_norm2_bias, scratch};
-    for (const void* o : outs) {
-        if (!o || !s360_aligned(o, 16)) return S360_E_BADARG;
-        for (const void* p : in)
-            if (p == o) return S360_E_BADARG;
-    }
-    for (const void* p : in)
-        if (!p || !s360_aligned(p, 16)) return S360_E_BADARG;
-    for (int i = 0; i < 9; ++i)
-        for (int j = i + 1; j < 9; ++j)
-            if (outs[i] == outs[j]) return S360_E_BADARG;
-    if (!eps || !(*eps > 0.0)) return S360_E_BADARG;
-    const int rc = ff_sizes(tokens, channels, hidden);
+    return ff_backward<true>({source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias}, z, stats, g_out, tokens, channels, hidden,
+                             eps, scratch, scratch_bytes,
+                             {g_source, g_m, g_w1, g_w2, g_norm1_weight, g_norm1_bias, g_norm2_weight, g_norm2_bias}, (hipStream_t)stream);
+}
+
+extern "C" int s360_layer_norm_residual_forward(const float* x, const float* weight, const float* bias, const float* residual, int32_t tokens,
+                                                int32_t channels, const double* eps, float* out, double* stats, void* stream) {
+    const void* const in[] = {x, weight, bias, residual};
+    const void* const outs[] = {out, stats};
+    const int rc = ff_setup(in, outs, true, eps, tokens, channels, FF_H);
     if (rc != S360_OK) return rc;
-    const int rs = s360_scratch(scratch, scratch_bytes, s360_ffn_tail_high_scratch_bytes(tokens, 1));     // scratch is one of outs: not null, aligned
-    if (rs != S360_OK) return rs;
-    const FFArgs a = {source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, tokens, *eps};
+    hipLaunchKernelGGL(k_ff_norm_residual_forward, dim3((tokens + FF_ROWS - 1) / FF_ROWS), dim3(S360_BLOCK), 0, (hipStream_t)stream, x, weight,
+                       bias, residual, tokens, *eps, out, stats);
+    return s360_launch_status();
+}
+
+extern "C" int s360_layer_norm_residual_backward(const float* x, const float* weight, const double* stats, const float* g_out, int32_t tokens,
+                                                 int32_t channels, void* scratch, size_t scratch_bytes, float* g_x, float* g_residual,
+                                                 float* g_weight, float* g_bias, void* stream) {
+    const void* const in[] = {x, weight, stats, g_out};
+    const void* const outs[] = {g_x, g_residual, g_weight, g_bias, scratch};
+    const int rc = ff_setup(in, outs, false, nullptr, tokens, channels, FF_H);
+    if (rc != S360_OK) return rc;
+    if (scratch_bytes < ff_layout(tokens, false, true).bytes) return S360_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int chunks = ff_chunks(tokens), wgs = ff_token_wgs(tokens);
-    const FFHPlanes pl = ffh_planes(scratch);
-    float* p_w1 = reinterpret_cast<float*>(static_cast<char*>(scratch) + FFH_PLANE_BYTES);
-    float* p_w2 = p_w1 + (size_t)chunks * FF_H * FF_X;
-    double* ln_part = reinterpret_cast<double*>(p_w2 + (size_t)chunks * FF_C * FF_H);
-    ffh_split_launch(w1, w2, pl, st);
+    const int wgs = ff_row_wgs(tokens);
+    double* ln_part = static_cast<double*>(scratch);                                          // alone in the scratch, at its start
+    hipLaunchKernelGGL(k_ff_norm_residual_backward, dim3(wgs), dim3(S360_BLOCK), 0, st, x, weight, stats, g_out, tokens, g_x, g_residual, ln_part);
     S360_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ffh_backward_tokens, dim3(wgs), dim3(S360_BLOCK), 0, st, a, pl, z, stats, g_out, g_source, g_m, ln_part);
-    S360_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ffh_backward_weights, dim3(FF_H / (FF_T * FF_WAVES), chunks), dim3(S360_BLOCK), 0, st, a, pl, z, stats, g_out,
-                       ff_chunk_tokens(tokens), p_w1, p_w2);
-    S360_CHECK_LAUNCH();
-    const int nw1 = FF_H * FF_X, nw2 = FF_C * FF_H, nln = 4 * FF_C;
-    const FFLnOut lo = {{g_norm1_weight, g_norm1_bias, g_norm2_weight, g_norm2_bias}};
-    hipLaunchKernelGGL(k_ff_reduce, dim3((nw1 + nw2 + nln + S360_BLOCK - 1) / S360_BLOCK), dim3(S360_BLOCK), 0, st, p_w1, p_w2, chunks, nw1,
-                       nw2, g_w1, g_w2, ln_part, wgs, nln, lo);
+    const int nln = 2 * FF_C;
+    const FFLnOut lo = {{g_weight, g_bias, nullptr, nullptr}};
+    hipLaunchKernelGGL(k_ff_reduce, dim3((nln + S360_BLOCK - 1) / S360_BLOCK), dim3(S360_BLOCK), 0, st, nullptr, nullptr, 0, 0, 0, nullptr,
+                       nullptr, ln_part, wgs, nln, lo);
     return s360_launch_status();
 }

@@ -41,6 +41,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import precision as _prec
+from ._args import buffers as _buffers, eps as _eps, flat as _flat, high_scratch as _high_scratch, no_scratch as _no_scratch, \
+    positive_int as _positive, tensor_rule
 from ._call import call, ptr
 from .precision import PRECISIONS  # noqa: F401  (the name callers of this module use)
 
@@ -48,17 +50,12 @@ CHANNELS = 128
 MONO_STEP, MONO_MAX = 64, 1024
 FORWARD_OUTPUTS = ("out", "y", "stats")
 GRADIENTS = ("g_erp_feat", "g_w1", "g_ln_weight", "g_ln_bias", "g_w2")
+_tensor = tensor_rule(RuntimeError, "{what} runs on the GPU only (there is no CPU path): {name} is on {device}")
 
 
 def supported_widths(channels: int, mono_channels: int) -> bool:
     """channels == 128 and mono_channels a multiple of 64 in 64 .. 1024."""
     return int(channels) == CHANNELS and MONO_STEP <= int(mono_channels) <= MONO_MAX and int(mono_channels) % MONO_STEP == 0
-
-
-def _positive(what: str, name: str, v) -> int:
-    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
-        raise ValueError(f"{what}: {name} must be a positive integer, got {v!r}")
-    return v
 
 
 def scratch_bytes(tokens: int, mono_channels: int, backward: bool = True, precision: str = "highest") -> int:
@@ -77,19 +74,6 @@ def scratch_bytes(tokens: int, mono_channels: int, backward: bool = True, precis
 def weight_chunks(tokens: int) -> int:
     """How many token chunks the weight-gradient pass of the backward uses for `tokens` tokens: min(32, ceil(tokens / 64))."""
     return int(_lib.lib().s360_mono_fusion_weight_chunks(_positive("weight_chunks", "tokens", tokens)))
-
-
-def _tensor(what: str, name: str, t, shape=None, dtype=torch.float32, device=None) -> None:
-    if not isinstance(t, Tensor):
-        raise ValueError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} runs on the GPU only (there is no CPU path): {name} is on {t.device}")
-    if t.dtype != dtype:
-        raise ValueError(f"{what}: {name} must be {str(dtype).replace('torch.', '')}, got {t.dtype}")
-    if device is not None and t.device != device:
-        raise ValueError(f"{what}: {name} is on {t.device}, expected {device}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
 
 
 def _checked(what: str, erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, eps) -> tuple:
@@ -111,51 +95,8 @@ def _checked(what: str, erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, e
     _tensor(what, "w2", w2, (c, c), device=dev)
     _tensor(what, "ln_weight", ln_weight, (c,), device=dev)
     _tensor(what, "ln_bias", ln_bias, (c,), device=dev)
-    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps > 0:
-        raise ValueError(f"{what}: eps must be a positive number, got {eps!r}")
+    _eps(what, eps)
     return n, cm, fw, h, w
-
-
-def _flat(t: Tensor) -> Tensor:
-    """Detached, contiguous and 16-byte aligned: a non-contiguous (or misaligned) input is copied once."""
-    t = t.detach().contiguous()
-    return t.clone() if t.data_ptr() % 16 else t
-
-
-def _buffers(what: str, names, shapes, dtypes, device, given: Optional[dict]) -> list:
-    """The output buffers of a call: `given` maps names to contiguous, 16-byte aligned buffers of the right shape and dtype on the
-    device to write into (every element is written); the others are allocated."""
-    given = dict(given or {})
-    unknown = set(given) - set(names)
-    if unknown:
-        raise ValueError(f"{what}: unknown buffers {sorted(unknown)}; the outputs are {list(names)}")
-    out = []
-    for name, shape, dtype in zip(names, shapes, dtypes):
-        buf = given.get(name)
-        if buf is None:
-            buf = torch.empty(tuple(shape), dtype=dtype, device=device)
-        else:
-            _tensor(what, name, buf, shape, dtype=dtype, device=device)
-            if not buf.is_contiguous() or buf.data_ptr() % 16:
-                raise ValueError(f"{what}: the buffer {name} must be contiguous and 16-byte aligned")
-        out.append(buf)
-    return out
-
-
-def _no_scratch(what: str, precision: str, given) -> None:
-    """Only the "high" call takes the caller's scratch: one handed to a "highest" call would go unused, so it is refused."""
-    if given is not None and precision != "high":
-        raise ValueError(f"{what}: scratch is the buffer of a precision=\"high\" call, got one with precision={precision!r}")
-
-
-def _high_scratch(what: str, tokens: int, mono_channels: int, backward: bool, device, given: Optional[Tensor]) -> Tensor:
-    """The scratch of a "high" call: allocated, or the caller's uint8 buffer (the library checks its size and alignment)."""
-    if given is None:
-        return _prec.scratch(scratch_bytes(tokens, mono_channels, backward, "high"), device)
-    _tensor(what, "scratch", given, dtype=torch.uint8, device=device)
-    if given.dim() != 1 or not given.is_contiguous():
-        raise ValueError(f"{what}: scratch must be a contiguous 1-D uint8 buffer")
-    return given
 
 
 def mono_fusion_forward(erp_feat: Tensor, mono_cube: Tensor, grid: Tensor, w1: Tensor, ln_weight: Tensor, ln_bias: Tensor, w2: Tensor,
@@ -171,10 +112,10 @@ def mono_fusion_forward(erp_feat: Tensor, mono_cube: Tensor, grid: Tensor, w1: T
     args = [_flat(t) for t in (erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2)]
     dev, tokens = erp_feat.device, n * h * w
     out, y, stats = _buffers("mono_fusion_forward", FORWARD_OUTPUTS, ((n, CHANNELS, h, w), (tokens, CHANNELS), (tokens, 2)),
-                             (torch.float32, torch.float32, torch.float64), dev, buffers)
+                             (torch.float32, torch.float32, torch.float64), dev, buffers, _tensor)
     common = (*(ptr(t) for t in args), n, CHANNELS, cm, fw, h, w, C.byref(C.c_double(float(eps))), ptr(out), ptr(y), ptr(stats))
     if precision == "high":
-        scratch = _high_scratch("mono_fusion_forward", tokens, cm, False, dev, scratch)
+        scratch = _high_scratch("mono_fusion_forward", scratch_bytes(tokens, cm, False, "high"), dev, scratch, _tensor)
         call("s360_mono_fusion_high_forward", dev, *common, ptr(scratch), scratch.numel())
     else:
         call("s360_mono_fusion_forward", dev, *common)
@@ -198,11 +139,9 @@ def mono_fusion_backward(erp_feat: Tensor, mono_cube: Tensor, grid: Tensor, w1: 
     _tensor(what, "y", y, (tokens, CHANNELS), device=dev)
     _tensor(what, "stats", stats, (tokens, 2), dtype=torch.float64, device=dev)
     ins = [_flat(t) for t in (erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, y, stats, g_out)]
-    outs = _buffers(what, GRADIENTS, [t.shape for t in (erp_feat, w1, ln_weight, ln_bias, w2)], [torch.float32] * 5, dev, buffers)
-    if precision == "high":
-        scratch = _high_scratch(what, tokens, cm, True, dev, scratch)
-    else:
-        scratch = torch.empty(scratch_bytes(tokens, cm), dtype=torch.uint8, device=dev)
+    outs = _buffers(what, GRADIENTS, [t.shape for t in (erp_feat, w1, ln_weight, ln_bias, w2)], [torch.float32] * 5, dev, buffers, _tensor)
+    nbytes = scratch_bytes(tokens, cm, True, precision)
+    scratch = _high_scratch(what, nbytes, dev, scratch, _tensor) if precision == "high" else _prec.scratch(nbytes, dev)
     call("s360_mono_fusion_high_backward" if precision == "high" else "s360_mono_fusion_backward", dev, *(ptr(t) for t in ins), n, CHANNELS, cm, fw, h, w, C.byref(C.c_double(float(eps))), ptr(scratch),
          scratch.numel(), *(ptr(t) for t in outs))
     return tuple(outs)

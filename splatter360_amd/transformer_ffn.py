@@ -25,7 +25,7 @@ weights are split once per call into 3 MiB of bf16 planes in a scratch buffer; t
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import Optional
 
 import torch
 from torch import Tensor
@@ -33,6 +33,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import precision as _prec
+from ._args import buffers as _buffers, eps as _eps, flat as _flat, high_scratch as _high_scratch, no_scratch as _no_scratch, \
+    positive_int as _positive, tensor_rule
 from ._call import call, ptr
 from .precision import PRECISIONS  # noqa: F401  (the name callers of this module use)
 
@@ -40,6 +42,7 @@ CHANNELS = 128
 HIDDEN = 1024
 FFN_GRADIENTS = ("g_source", "g_m", "g_norm1_weight", "g_norm1_bias", "g_w1", "g_w2", "g_norm2_weight", "g_norm2_bias")
 NORM_GRADIENTS = ("g_x", "g_weight", "g_bias", "g_residual")
+_tensor = tensor_rule(ValueError, "{what}: {name} must be a GPU tensor (there is no CPU path), got device {device}")
 
 
 def scratch_bytes(tokens: int, backward: bool, precision: str = "highest") -> int:
@@ -60,28 +63,8 @@ def supported_widths(channels: int, hidden: int = HIDDEN) -> bool:
 def weight_chunks(tokens: int) -> int:
     """How many token chunks the weight-gradient pass of ffn_tail's backward uses for `tokens` tokens (at most 16, each a multiple
     of 32 tokens but for the last)."""
-    if isinstance(tokens, bool) or not isinstance(tokens, int) or tokens < 1:
-        raise ValueError(f"weight_chunks: tokens must be a positive integer, got {tokens!r}")
+    tokens = _positive("weight_chunks", "tokens", tokens)
     return int(_lib.lib().s360_ffn_tail_weight_chunks(tokens))
-
-
-def _tensor(what: str, name: str, t, shape=None, dtype=torch.float32, device=None) -> None:
-    if not isinstance(t, Tensor):
-        raise ValueError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-    if not t.is_cuda:
-        raise ValueError(f"{what}: {name} must be a GPU tensor (there is no CPU path), got device {t.device}")
-    if t.dtype != dtype:
-        raise ValueError(f"{what}: {name} must be {str(dtype).replace('torch.', '')}, got {t.dtype}")
-    if device is not None and t.device != device:
-        raise ValueError(f"{what}: {name} is on {t.device}, expected {device}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{what}: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-
-
-def _eps(what: str, eps) -> float:
-    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps > 0:
-        raise ValueError(f"{what}: eps must be a positive number, got {eps!r}")
-    return float(eps)
 
 
 def _rows(what: str, name: str, t) -> int:
@@ -117,52 +100,6 @@ def _checked_norm(what: str, x, weight, bias, residual, eps) -> int:
     return tokens
 
 
-def _flat(t: Tensor) -> Tensor:
-    """Detached, contiguous and 16-byte aligned: a non-contiguous (or misaligned) input is copied once."""
-    t = t.detach().contiguous()
-    return t.clone() if t.data_ptr() % 16 else t
-
-
-def _buffers(what: str, names: Sequence[str], like: Sequence[Tensor], given: Optional[dict]) -> list:
-    """The output buffers of a backward: `given` maps names to contiguous float32 buffers of the right shape on the device to write
-    into (every element is written); the others are allocated."""
-    given = dict(given or {})
-    unknown = set(given) - set(names)
-    if unknown:
-        raise ValueError(f"{what}: unknown buffers {sorted(unknown)}; the outputs are {list(names)}")
-    out = []
-    for name, ref in zip(names, like):
-        buf = given.get(name)
-        if buf is None:
-            buf = torch.empty(ref.shape, dtype=torch.float32, device=ref.device)
-        else:
-            _tensor(what, name, buf, ref.shape, device=ref.device)
-            if not buf.is_contiguous() or buf.data_ptr() % 16:
-                raise ValueError(f"{what}: the buffer {name} must be contiguous and 16-byte aligned")
-        out.append(buf)
-    return out
-
-
-def _scratch(tokens: int, device) -> Tensor:
-    return _prec.scratch(_lib.lib().s360_ffn_tail_scratch_bytes(tokens), device)
-
-
-def _no_scratch(what: str, precision: str, given) -> None:
-    """Only the "high" call takes the caller's scratch: one handed to a "highest" call would go unused, so it is refused."""
-    if given is not None and precision != "high":
-        raise ValueError(f"{what}: scratch is the buffer of a precision=\"high\" call, got one with precision={precision!r}")
-
-
-def _high_scratch(what: str, tokens: int, backward: bool, device, given: Optional[Tensor]) -> Tensor:
-    """The scratch of a "high" call: allocated, or the caller's uint8 buffer (the library checks its size and alignment)."""
-    if given is None:
-        return _prec.scratch(scratch_bytes(tokens, backward, "high"), device)
-    _tensor(what, "scratch", given, dtype=torch.uint8, device=device)
-    if given.dim() != 1 or not given.is_contiguous():
-        raise ValueError(f"{what}: scratch must be a contiguous 1-D uint8 buffer")
-    return given
-
-
 def ffn_tail_forward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bias: Tensor, w1: Tensor, w2: Tensor, norm2_weight: Tensor,
                      norm2_bias: Tensor, eps: float = 1e-5, *, precision: str = "highest", scratch: Optional[Tensor] = None) -> tuple:
     """s360_ffn_tail_forward (precision "high": s360_ffn_tail_high_forward) -> (out in source's shape, z [T, C] float32, stats
@@ -177,7 +114,7 @@ def ffn_tail_forward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bias
     stats = torch.empty(2, tokens, 2, dtype=torch.float64, device=source.device)
     common = (*(ptr(t) for t in args), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))), ptr(out), ptr(z), ptr(stats))
     if precision == "high":
-        scratch = _high_scratch("ffn_tail_forward", tokens, False, source.device, scratch)
+        scratch = _high_scratch("ffn_tail_forward", scratch_bytes(tokens, False, "high"), source.device, scratch, _tensor)
         call("s360_ffn_tail_high_forward", source.device, *common, ptr(scratch), scratch.numel())
     else:
         call("s360_ffn_tail_forward", source.device, *common)
@@ -199,9 +136,12 @@ def ffn_tail_backward(source: Tensor, m: Tensor, norm1_weight: Tensor, norm1_bia
     _tensor(what, "z", z, (tokens, CHANNELS), device=source.device)
     _tensor(what, "stats", stats, (2, tokens, 2), dtype=torch.float64, device=source.device)
     ins = [_flat(t) for t in (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias, z, stats, g_out)]
-    outs = dict(zip(FFN_GRADIENTS, _buffers(what, FFN_GRADIENTS, (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias),
-                                            buffers)))
-    scratch = _high_scratch(what, tokens, True, source.device, scratch) if precision == "high" else _scratch(tokens, source.device)
+    shapes = [t.shape for t in (source, m, norm1_weight, norm1_bias, w1, w2, norm2_weight, norm2_bias)]
+    outs = dict(zip(FFN_GRADIENTS, _buffers(what, FFN_GRADIENTS, shapes, [torch.float32] * 8, source.device, buffers, _tensor)))
+    if precision == "high":
+        scratch = _high_scratch(what, scratch_bytes(tokens, True, "high"), source.device, scratch, _tensor)
+    else:
+        scratch = _prec.scratch(_lib.lib().s360_ffn_tail_scratch_bytes(tokens), source.device)
     order = ("g_source", "g_m", "g_w1", "g_w2", "g_norm1_weight", "g_norm1_bias", "g_norm2_weight", "g_norm2_bias")
     call("s360_ffn_tail_high_backward" if precision == "high" else "s360_ffn_tail_backward", source.device, *(ptr(t) for t in ins), tokens, CHANNELS, HIDDEN, C.byref(C.c_double(float(eps))),
          ptr(scratch), scratch.numel(), *(ptr(outs[n]) for n in order))
@@ -227,8 +167,9 @@ def layer_norm_residual_backward(x: Tensor, weight: Tensor, stats: Tensor, g_out
     _tensor(what, "g_out", g_out, x.shape, device=x.device)
     _tensor(what, "stats", stats, (tokens, 2), dtype=torch.float64, device=x.device)
     ins = [_flat(t) for t in (x, weight, stats, g_out)]
-    outs = dict(zip(NORM_GRADIENTS, _buffers(what, NORM_GRADIENTS, (x, weight, weight, x), buffers)))
-    scratch = _scratch(tokens, x.device)
+    shapes = [t.shape for t in (x, weight, weight, x)]
+    outs = dict(zip(NORM_GRADIENTS, _buffers(what, NORM_GRADIENTS, shapes, [torch.float32] * 4, x.device, buffers, _tensor)))
+    scratch = _prec.scratch(_lib.lib().s360_ffn_tail_scratch_bytes(tokens), x.device)
     call("s360_layer_norm_residual_backward", x.device, *(ptr(t) for t in ins), tokens, CHANNELS, ptr(scratch), scratch.numel(),
          ptr(outs["g_x"]), ptr(outs["g_residual"]), ptr(outs["g_weight"]), ptr(outs["g_bias"]))
     return tuple(outs[n] for n in NORM_GRADIENTS)

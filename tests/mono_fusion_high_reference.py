@@ -21,7 +21,7 @@ import mono_fusion_reference as R
 import window_attention_high_reference as H
 
 KERNEL_FILE = Path(__file__).resolve().parent.parent / "splatter360_amd" / "csrc" / "s360_mono_fusion.hip"
-errors = H.errors
+errors, check_rule = H.errors, H.check_rule
 
 
 def split_statement(erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, eps=1e-5, terms=3, parts=None, m=None):

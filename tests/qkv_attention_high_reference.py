@@ -13,7 +13,7 @@ and its backward leave, rounded to float32.  Further the cases the CPU and the G
 import torch
 
 import qkv_attention_reference as R
-from window_attention_high_reference import HighProduct, errors, split  # noqa: F401  (errors and split: for the tests)
+from window_attention_high_reference import HighProduct, bound, check_rule, errors, split  # noqa: F401  (all but HighProduct: for the tests)
 
 # name: (N, views, cross_view, heads, T, order); ch = 32: the nine shapes of tests/test_gpu_qkv_attention.py and two more
 SHAPES = {
@@ -67,8 +67,3 @@ def yardsticks(name, scale, device="cpu"):
     return (qkv, g), with_parts(name, want), with_parts(name, three), with_parts(name, lines)
 
 
-def bound(w64, t3, l32):
-    """The accuracy rule's (max, mean) bounds for one tensor: max(1.5 x (e3 + e32), 2^-24 max|want|)."""
-    (smax, smean), (lmax, lmean) = errors(t3, w64), errors(l32, w64)
-    floor = 2.0 ** -24 * w64.abs().max().item()
-    return max(1.5 * (smax + lmax), floor), max(1.5 * (smean + lmean), floor)

@@ -84,22 +84,6 @@ def _run(name, scale):
     return (cpu, g, m, dev), tuple(w.to(DEV) for w in want), tuple(t.to(DEV) for t in three), lines, got
 
 
-def _check_rule(tag, want, three, lines, got):
-    failures = []
-    for n, w64, t3, l32, x in zip(R.RESULTS, want, three, lines, got):
-        assert x.dtype == torch.float32 and x.shape == w64.shape, (tag, n)
-        assert torch.isfinite(x).all(), (tag, n)
-        (kmax, kmean), (e3max, e3mean), (lmax, lmean) = HR.errors(x, w64), HR.errors(t3, w64), HR.errors(l32, w64)
-        floor = 2.0 ** -24 * w64.abs().max().item()
-        bmax, bmean = max(1.5 * (e3max + lmax), floor), max(1.5 * (e3mean + lmean), floor)
-        print(f"{tag} {n}: kernel max {kmax:.3e} mean {kmean:.3e} | e3 max {e3max:.3e} mean {e3mean:.3e} | e32 max {lmax:.3e} mean "
-              f"{lmean:.3e} | floor {floor:.3e} | kernel / bound {kmax / bmax if bmax else 0:.2f} {kmean / bmean if bmean else 0:.2f}"
-              f" | kernel / e3 {kmax / e3max if e3max else 0:.2f} {kmean / e3mean if e3mean else 0:.2f}")
-        if not (kmax <= bmax and kmean <= bmean):
-            failures.append((n, kmax, kmean, bmax, bmean))
-    assert not failures, (tag, failures)
-
-
 @pytest.mark.parametrize("scale", SCALES)
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_accuracy_against_the_float64_statement(name, scale):
@@ -110,7 +94,7 @@ def test_accuracy_against_the_float64_statement(name, scale):
     assert margin >= 8.0 * deviation, (name, scale, margin, deviation)
     assert CASES[name][3] != "decided" or margin >= 0.4
     assert HR.flipped_decisions(cpu, m) == 0
-    _check_rule(f"{name} scale={scale:g}", want, three, lines, got)
+    HR.check_rule(f"{name} scale={scale:g}", R.RESULTS, want, three, lines, got)
 
 
 @pytest.mark.parametrize("name", ["straddle", "edges"])
@@ -354,7 +338,7 @@ def test_the_standin_encoder_holds_the_rule_at_high(standin):
     assert enc.c2e.calls == 0
     direct = _native(tensors, g)
     assert all(torch.equal(a, b) for a, b in zip(got, direct))
-    _check_rule("seam high", want, three, lines, got)
+    HR.check_rule("seam high", R.RESULTS, want, three, lines, got)
     splatter360_amd.uninstall()
     after = run(_encoder(standin, tensors, cm))
     assert all(torch.equal(a, b) for a, b in zip(lines, after))

@@ -70,17 +70,7 @@ def _run(name, scale):
 @pytest.mark.parametrize("name", sorted(SHAPES))
 def test_accuracy_against_the_float64_statement(name, scale):
     _, want, three, lines, got = _run(name, scale)
-    failures = []
-    for n, w64, t3, l32, x in zip(H.NAMES, want, three, lines, got):
-        assert x.dtype == torch.float32 and x.shape == w64.shape, (name, n)
-        assert torch.isfinite(x).all(), (name, n)
-        (kmax, kmean), (bmax, bmean) = H.errors(x, w64), H.bound(w64, t3, l32)
-        (smax, smean), (lmax, lmean) = H.errors(t3, w64), H.errors(l32, w64)
-        print(f"{name} scale={scale:g} {n}: kernel max {kmax:.3e} mean {kmean:.3e} | terms=3 max {smax:.3e} mean {smean:.3e} | float32 lines "
-              f"max {lmax:.3e} mean {lmean:.3e} | bound max {bmax:.3e} mean {bmean:.3e} | ratios {kmax / bmax:.3f} {kmean / bmean:.3f}")
-        if not (kmax <= bmax and kmean <= bmean):
-            failures.append((n, kmax, kmean, bmax, bmean))
-    assert not failures, (name, scale, failures)
+    H.check_rule(f"{name} scale={scale:g}", H.NAMES, want, three, lines, got)
 
 
 @pytest.mark.parametrize("name", ["straddle", "new_order", "long", "uneven"])

@@ -87,25 +87,10 @@ def _run(name, scale):
     return (tensors, g), want, three, lines, got
 
 
-def _check_rule(tag, names, want, three, lines, got):
-    failures = []
-    for n, w64, t3, l32, x in zip(names, want, three, lines, got):
-        assert x.dtype == torch.float32 and x.shape == w64.shape, (tag, n)
-        assert torch.isfinite(x).all(), (tag, n)
-        (kmax, kmean), (e3max, e3mean), (lmax, lmean) = HR.errors(x, w64), HR.errors(t3, w64), HR.errors(l32, w64)
-        floor = 2.0 ** -24 * w64.abs().max().item()
-        bmax, bmean = max(1.5 * (e3max + lmax), floor), max(1.5 * (e3mean + lmean), floor)
-        print(f"{tag} {n}: kernel max {kmax:.3e} mean {kmean:.3e} | e3 max {e3max:.3e} mean {e3mean:.3e} | e32 max {lmax:.3e} mean "
-              f"{lmean:.3e} | floor {floor:.3e} | kernel / bound {kmax / bmax if bmax else 0:.2f} {kmean / bmean if bmean else 0:.2f}")
-        if not (kmax <= bmax and kmean <= bmean):
-            failures.append((n, kmax, kmean, bmax, bmean))
-    assert not failures, (tag, failures)
-
-
 @pytest.mark.parametrize("name,scale", RUNS)
 def test_ffn_tail_high_accuracy_against_the_float64_statement(name, scale):
     _, want, three, lines, got = _run(name, scale)
-    _check_rule(f"ffn high {name} scale={scale:g}", FFN_OUT, want, three, lines, got)
+    HR.check_rule(f"ffn high {name} scale={scale:g}", FFN_OUT, want, three, lines, got)
 
 
 @pytest.mark.parametrize("scale", SCALES)
@@ -351,4 +336,4 @@ def test_the_layer_holds_the_rule_with_both_seams_at_high(standin):
     standin.calls.clear()
     got = _layer32(layer, source, target, g)
     assert wrapper.native_calls == 1 and layer.calls == 1 and standin.calls == []
-    _check_rule("layer high", names, want, three, lines, got)
+    HR.check_rule("layer high", names, want, three, lines, got)

@@ -68,23 +68,10 @@ def _run(name, shift, scale, rule):
     return (q, k, v, g), want, three, lines, got
 
 
-def _check_rule(tag, want, three, lines, got):
-    failures = []
-    for n, w64, t3, l32, x in zip(NAMES, want, three, lines, got):
-        assert x.dtype == torch.float32 and x.shape == w64.shape, (tag, n)
-        (kmax, kmean), (smax, smean), (lmax, lmean) = H.errors(x, w64), H.errors(t3, w64), H.errors(l32, w64)
-        floor = 2.0 ** -24 * w64.abs().max().item()
-        print(f"{tag} {n}: kernel max {kmax:.3e} mean {kmean:.3e} | terms=3 max {smax:.3e} mean {smean:.3e} | float32 lines max {lmax:.3e} "
-              f"mean {lmean:.3e} | floor {floor:.3e}")
-        if not (kmax <= max(1.5 * (smax + lmax), floor) and kmean <= max(1.5 * (smean + lmean), floor)):
-            failures.append((n, kmax, kmean, smax, smean, lmax, lmean, floor))
-    assert not failures, (tag, failures)
-
-
 @pytest.mark.parametrize("name,shift,scale,rule", RUNS)
 def test_accuracy_against_the_float64_statement(name, shift, scale, rule):
     _, want, three, lines, got = _run(name, shift, scale, rule)
-    _check_rule(f"{name} shift={int(shift)} scale={scale:g} {rule}", want, three, lines, got)
+    H.check_rule(f"{name} shift={int(shift)} scale={scale:g} {rule}", NAMES, want, three, lines, got)
 
 
 @pytest.mark.parametrize("name,shift", [("ragged", True), ("multi", True), ("long", False), ("long", True)])

@@ -69,6 +69,77 @@ def test_three_terms_are_fifty_times_closer_than_one(name, shift, scale):
         assert max3 > 0.0 and max1 >= 50.0 * max3 and mean1 >= 50.0 * mean3, (name, shift, scale, n)
 
 
+# ---- H.check_rule, the accuracy rule the four "high" GPU files share, on tensors whose errors are exact powers of two
+def _ruled(e3, e32, kernel, want=None):
+    """check_rule on one tensor "t" of 64 elements: `want` (ones), want + e3 as the terms=3 statement, want + e32 as the float32
+    lines and want + kernel as the kernel's float32 result; each error a number or a tensor of 64."""
+    want = torch.ones(64, dtype=torch.float64) if want is None else want
+    three, lines, got = want + e3, (want + e32).float(), (want + kernel).float()
+    assert torch.equal(got.double(), want + kernel) and torch.equal(lines.double(), want + e32)       # nothing was rounded away
+    H.check_rule("case", ("t",), (want,), (three,), (lines,), (got,))
+
+
+def _only(i, v):
+    x = torch.zeros(64, dtype=torch.float64)
+    x[i] = v
+    return x
+
+
+def test_check_rule_passes_the_statement_itself_and_prints_every_figure(capsys):
+    _ruled(2.0 ** -10, 2.0 ** -12, 2.0 ** -10)
+    line = capsys.readouterr().out
+    for field in ("case t: kernel max 9.766e-04 mean 9.766e-04", "e3 max 9.766e-04", "e32 max 2.441e-04", "floor 5.960e-08",
+                  "kernel / bound 0.533 0.533", "kernel / e3 1.00 1.00"):
+        assert field in line, (field, line)
+
+
+def test_check_rule_fails_on_the_maximum_alone():
+    e3, e32 = 2.0 ** -10, 2.0 ** -12
+    _ruled(e3, e32, e3 + _only(5, 1.5 * (e3 + e32) - e3))                    # 1.5 x (e3 + e32) at one element: the bound itself
+    with pytest.raises(AssertionError) as failed:
+        _ruled(e3, e32, e3 + _only(5, 2.0 ** -9 - e3))                       # 2^-9 = 1.6 x (e3 + e32) there
+    tag, ((name, kmax, kmean, bmax, bmean),) = failed.value.args[0]
+    assert (tag, name, kmax, bmax) == ("case", "t", 2.0 ** -9, 1.5 * (e3 + e32)) and kmean <= bmean
+
+
+def test_check_rule_fails_on_the_mean_alone():
+    e3 = _only(0, 2.0 ** -10)                                                # max 2^-10, mean 2^-16; the float32 lines exact
+    _ruled(e3, 0.0, 2.0 ** -16)
+    with pytest.raises(AssertionError) as failed:
+        _ruled(e3, 0.0, 2.0 ** -12)                                          # below the maximum's bound at every element
+    tag, ((name, kmax, kmean, bmax, bmean),) = failed.value.args[0]
+    assert kmax == 2.0 ** -12 <= bmax == 1.5 * 2.0 ** -10 and kmean == 2.0 ** -12 > bmean == 1.5 * 2.0 ** -16
+
+
+def test_check_rule_fails_on_one_nan_a_wrong_dtype_and_a_wrong_shape():
+    want = torch.ones(64, dtype=torch.float64)
+    good = want.float()
+    bad = good.clone()
+    bad[17] = float("nan")
+    for got in (bad, good.double(), good[:63], good.view(8, 8)):
+        with pytest.raises(AssertionError) as failed:
+            H.check_rule("case", ("t",), (want,), (want,), (good,), (got,))
+        assert failed.value.args[0] == ("case", "t")
+    H.check_rule("case", ("t",), (want,), (want,), (good,), (good,))
+
+
+def test_check_rule_lets_the_floor_decide_where_both_yardsticks_are_exact():
+    want = torch.ones(64, dtype=torch.float64) + _only(0, 2.0 ** 20 - 1.0)   # max|want| = 2^20: the floor is 2^-4
+    _ruled(0.0, 0.0, 2.0 ** -4 * (want == 1.0), want)                        # e3 = e32 = 0: only the floor admits 2^-4
+    with pytest.raises(AssertionError):
+        _ruled(0.0, 0.0, _only(1, 2.0 ** -3), want)
+    with pytest.raises(AssertionError):
+        _ruled(0.0, 0.0, 2.0 ** -4 * (want == 1.0))                          # the same error with max|want| = 1: floor 2^-24
+
+
+def test_check_rule_collects_every_failing_tensor_before_it_asserts():
+    want = torch.ones(64, dtype=torch.float64)
+    exact, off = want.float(), (want + 2.0 ** -10).float()
+    with pytest.raises(AssertionError) as failed:
+        H.check_rule("case", ("a", "b", "c"), (want,) * 3, (want,) * 3, (exact,) * 3, (off, exact, off))
+    assert [f[0] for f in failed.value.args[0][1]] == ["a", "c"]
+
+
 def test_an_unknown_precision_is_refused_before_any_tensor_is_touched():
     q, k, v, g = R.random_case(1, 0, 4, 8, c=32, seed=1)
     opts = dict(height=4, width=8, num_splits=2)

@@ -55,7 +55,7 @@ def layer_split_statement(params, source, target, no_ffn=False, eps=1e-5, terms=
                            p["norm2.bias"], eps, terms)
 
 
-errors = H.errors
+errors, check_rule = H.errors, H.check_rule
 
 
 # ---- the launch geometry of the "high" kernels -------------------------------------------------------------------------------

@@ -78,3 +78,32 @@ def errors(x, want):
     """(max, mean) absolute error of x against the float64 `want`."""
     e = (x.double() - want).abs()
     return e.max().item(), e.mean().item()
+
+
+def bound(w64, t3, l32):
+    """The accuracy rule's (max, mean) bounds for one tensor: max(1.5 x (e3 + e32), 2^-24 max|want|), e3 the error of the terms=3
+    statement `t3` and e32 that of the float32 lines `l32` against the float64 `w64`."""
+    (smax, smean), (lmax, lmean) = errors(t3, w64), errors(l32, w64)
+    floor = 2.0 ** -24 * w64.abs().max().item()
+    return max(1.5 * (smax + lmax), floor), max(1.5 * (smean + lmean), floor)
+
+
+def check_rule(tag, names, want, three, lines, got):
+    """The accuracy rule of the four "high" modes, for the tensors `names` of one case: each of `got` is float32, has the shape
+    of its float64 `want`, is finite, and its max and mean absolute error against `want` are within `bound` of `three` (the
+    terms=3 statement) and `lines` (the float32 lines).  One line of figures per tensor is printed; the failures are collected
+    and asserted once."""
+    ratio = lambda a, b: a / b if b else 0.0
+    failures = []
+    for n, w64, t3, l32, x in zip(names, want, three, lines, got):
+        assert x.dtype == torch.float32 and x.shape == w64.shape, (tag, n)
+        assert torch.isfinite(x).all(), (tag, n)
+        (kmax, kmean), (e3max, e3mean), (lmax, lmean) = errors(x, w64), errors(t3, w64), errors(l32, w64)
+        floor = 2.0 ** -24 * w64.abs().max().item()
+        bmax, bmean = bound(w64, t3, l32)
+        print(f"{tag} {n}: kernel max {kmax:.3e} mean {kmean:.3e} | e3 max {e3max:.3e} mean {e3mean:.3e} | e32 max {lmax:.3e} mean "
+              f"{lmean:.3e} | floor {floor:.3e} | kernel / bound {ratio(kmax, bmax):.3f} {ratio(kmean, bmean):.3f}"
+              f" | kernel / e3 {ratio(kmax, e3max):.2f} {ratio(kmean, e3mean):.2f}")
+        if not (kmax <= bmax and kmean <= bmean):
+            failures.append((n, kmax, kmean, bmax, bmean))
+    assert not failures, (tag, failures)
