@@ -27,18 +27,28 @@ errors, check_rule = H.errors, H.check_rule
 def split_statement(erp_feat, mono_cube, grid, w1, ln_weight, ln_bias, w2, eps=1e-5, terms=3, parts=None, m=None):
     """R.statement with high products: float32 tensors -> out [N, C, H, W], float64; differentiable in erp_feat and the
     parameters (g_a = g_out W2, g_X = g_y W1, g_w1 = g_y^T X and g_w2 = g_out^T a are high products of their own split operands).
-    m: R.stitch32 of the case if at hand.  parts: a dict that receives "ln", LayerNorm's output [N, H, W, C]."""
+    m: R.stitch32 of the case if at hand.  parts: a dict that receives "y", the first high product [T, C], and "ln", LayerNorm's
+    output [N, H, W, C]."""
     if m is None:
         m = R.stitch32(mono_cube, grid)
     m = m.to(device=erp_feat.device, dtype=torch.float64)
     erp_feat, w1, ln_weight, ln_bias, w2 = (t.double() for t in (erp_feat, w1, ln_weight, ln_bias, w2))
     n, c, h, w = erp_feat.shape
     x = torch.cat([erp_feat, m], dim=1).permute(0, 2, 3, 1).reshape(n * h * w, -1)
-    ln = R.layer_norm(H.HighProduct.apply(x, w1.transpose(0, 1), terms), ln_weight, ln_bias, eps)
+    y = H.HighProduct.apply(x, w1.transpose(0, 1), terms)
+    ln = R.layer_norm(y, ln_weight, ln_bias, eps)
     if parts is not None:
+        parts["y"] = y
         parts["ln"] = ln.reshape(n, h, w, c)
     out = H.HighProduct.apply(torch.relu(ln), w2.transpose(0, 1), terms)
     return out.reshape(n, h, w, c).permute(0, 3, 1, 2)
+
+
+def three_rows(tensors, g, eps=1e-5, terms=3):
+    """split_statement and its gradients by autograd in the per-row indexing of R.row_statement (R.ROW_NAMES, y taken from
+    inside), float64 on the inputs' device: the specification's own rows, the second yardstick of the per-row "high" rule."""
+    m = R.stitch32(tensors[1], tensors[2])
+    return R._rows_of(lambda *t, parts: split_statement(*t, eps=eps, terms=terms, parts=parts, m=m), tensors, g, torch.float64)[0]
 
 
 def ln_outputs(tensors, m=None, terms=3):
