@@ -1002,9 +1002,10 @@ int s360_error_map(const float* a, const float* b, int32_t height, int32_t width
  * forward's out is therefore not an argument).  The pass owned by query tiles runs first (Delta, then g_q), the pass owned by
  * key tiles second (g_k / g_v): every output element is written once, by one wave, in a fixed order — no atomics,
  * bit-identical from run to run and across streams.
- * No host synchronisation, no allocation.  channels outside {32, 64, 96, 128}: S360_E_UNSUPPORTED.  Null required pointers,
- * pointers not 16-byte aligned, sizes < 1, num_splits not dividing height and width, an unknown mask_rule, or 2^31 or more rows
- * or workgroups: S360_E_BADARG before any GPU work.
+ * No host synchronisation, no allocation.  channels outside {32, 64, 96, 128}: S360_E_UNSUPPORTED.  A null required pointer, a
+ * pointer that is not 16-byte aligned (q, k, v, out, lse, g_out, delta and every g_q, g_k, g_v that is given), an output that is an
+ * input or another output (q, k and v may be one another), sizes < 1, num_splits not dividing height and width, an unknown
+ * mask_rule, or 2^31 or more rows or workgroups: S360_E_BADARG before any GPU work, the pointers before the sizes.
  */
 #define S360_WA_MASK_REFERENCE 0
 #define S360_WA_MASK_ALIGNED 1
@@ -1033,8 +1034,9 @@ int s360_window_attention_backward(const float* q, const float* k, const float* 
  * 2 x the bytes of (q, k, v) and, for Lw >= 6, of (q, k, v, g_out).  The contents need no initialisation and nothing in it
  * is read by a later call: the backward splits again.
  * No atomics, no host synchronisation, no allocation; bit-identical from run to run and across streams.  Refusals as for
- * s360_window_attention_*; a null scratch or one not 16-byte aligned: S360_E_BADARG, scratch_bytes smaller than reported:
- * S360_E_WORKSPACE, both before any GPU work.
+ * s360_window_attention_*, the scratch being one more output: null, not 16-byte aligned, or an input or another output:
+ * S360_E_BADARG; or 2^31 or more work-items in a pre-pass launch: S360_E_BADARG; then scratch_bytes smaller than reported:
+ * S360_E_WORKSPACE, all before any GPU work.
  */
 size_t s360_window_attention_high_scratch_bytes(int32_t batch, int32_t partners, int32_t height, int32_t width, int32_t channels,
                                                 int32_t num_splits, int32_t backward);
@@ -1068,8 +1070,10 @@ int s360_window_attention_high_backward(const float* q, const float* k, const fl
  * Delta = sum_s P dP / sum_s P per query (sum P is 1 but for rounding; dividing by it makes sum_s dS = 0 hold for the P in use).  The pass owned by query tiles runs first (Delta, then the q rows), the pass owned by key tiles
  * second (the k and v rows): every element of g_qkv is written once, by one wave, in a fixed order — no atomics, bit-identical
  * from run to run and across streams.
- * No host synchronisation, no allocation.  ch != 32: S360_E_UNSUPPORTED.  Null pointers, sizes < 1, views not dividing
- * rows, an unknown order, g_qkv == qkv, or 2^31 or more joint tokens or workgroups: S360_E_BADARG before any GPU work.
+ * No host synchronisation, no allocation.  ch != 32: S360_E_UNSUPPORTED.  A null pointer, a pointer that is not 4-byte aligned
+ * (the float32 tensors move one dword per lane, and the float64 lse and delta are held to no more than these 4 bytes, though
+ * every float64 tensor has 8), an output that is an input or another output (g_qkv == qkv among them), sizes < 1, views not dividing rows, an unknown order, or 2^31 or more joint tokens or workgroups: S360_E_BADARG before
+ * any GPU work, the pointers before the sizes.
  */
 #define S360_QKV_LEGACY 0
 #define S360_QKV_NEW 1
@@ -1096,8 +1100,8 @@ int s360_qkv_attention_backward(const float* qkv, const double* lse, const float
  * (rows of q, k, v and g_out, transposed q, k and g_out — 1.75 x the bytes of qkv and g_out at Lpad tokens), 0 for arguments the
  * calls refuse.  The contents need no initialisation and nothing in it is read by a later call: the backward splits again.
  * No atomics, no host synchronisation, no allocation; bit-identical from run to run and across streams.  Refusals as for
- * s360_qkv_attention_*; a null scratch or one not 16-byte aligned: S360_E_BADARG, scratch_bytes smaller than reported:
- * S360_E_WORKSPACE, both before any GPU work.
+ * s360_qkv_attention_*, the scratch being one more output: null, not 16-byte aligned (its planes are read 16 bytes at a time), or
+ * an input or another output: S360_E_BADARG; then scratch_bytes smaller than reported: S360_E_WORKSPACE, all before any GPU work.
  */
 size_t s360_qkv_attention_high_scratch_bytes(int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens, int32_t backward);
 int s360_qkv_attention_high_forward(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens,

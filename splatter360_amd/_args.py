@@ -1,8 +1,10 @@
-"""The argument vocabulary of the operators' Python wrappers (transformer_ffn, mono_fusion): what a tensor argument must be, how it
-reaches the library, how the output buffers and a "high" call's scratch are taken or allocated.  `what` is the public function
-the message names.  What a tensor that is not on the GPU raises is the operator's own (ValueError for the FFN tail, RuntimeError
-for the mono fusion, each with its text; callers may rely on either): `tensor_rule` makes the operator's `tensor`, and `buffers`
-and `high_scratch` take it as their last argument."""
+"""The argument vocabulary of the operators' Python wrappers (transformer_ffn, mono_fusion, window_attention, qkv_attention): what
+a tensor argument must be, how it reaches the library, how the output buffers and a "high" call's scratch are taken or
+allocated.  `what` is the public function the message names.  What a tensor that is not on the GPU raises is the operator's own
+(ValueError for the FFN tail and the QKV attention, RuntimeError for the mono fusion and the window attention, each with its
+text; callers may rely on either): `tensor_rule` makes the operator's `tensor`, and `buffers` and `high_scratch` take it.  The
+QKV attention's kernels move one dword per lane, so its wrapper keeps `.detach().contiguous()` in place of `flat` and asks
+`buffers` for a float's alignment."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
@@ -37,9 +39,9 @@ def flat(t: Tensor) -> Tensor:
     return t.clone() if t.data_ptr() % 16 else t
 
 
-def buffers(what: str, names: Sequence[str], shapes, dtypes, device, given: Optional[dict], tensor) -> list:
-    """The output buffers of a call: `given` maps names to contiguous, 16-byte aligned buffers of the right shape and dtype on the
-    device to write into (every element is written); the others are allocated."""
+def buffers(what: str, names: Sequence[str], shapes, dtypes, device, given: Optional[dict], tensor, align: int = 16) -> list:
+    """The output buffers of a call: `given` maps names to contiguous, `align`-byte aligned buffers of the right shape and dtype on
+    the device to write into (every element is written); the others are allocated."""
     given = dict(given or {})
     unknown = set(given) - set(names)
     if unknown:
@@ -51,8 +53,8 @@ def buffers(what: str, names: Sequence[str], shapes, dtypes, device, given: Opti
             buf = torch.empty(tuple(shape), dtype=dtype, device=device)
         else:
             tensor(what, name, buf, shape, dtype=dtype, device=device)
-            if not buf.is_contiguous() or buf.data_ptr() % 16:
-                raise ValueError(f"{what}: the buffer {name} must be contiguous and 16-byte aligned")
+            if not buf.is_contiguous() or buf.data_ptr() % align:
+                raise ValueError(f"{what}: the buffer {name} must be contiguous and {align}-byte aligned")
         out.append(buf)
     return out
 

@@ -1,6 +1,5 @@
 // s360_launch.h — host-side rules every entry point of the library shares: the check after a launch, the bound on a grid,
-// pointer alignment, the pointer rule of an entry's inputs and outputs, the workspace-size protocol of include/s360.h and the
-// check of a "high" call's scratch.
+// pointer alignment, the pointer rule of an entry's inputs and outputs and the workspace-size protocol of include/s360.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,19 +37,35 @@ static inline bool s360_grid_fits(long long blocks) { return blocks <= 0x7ffffff
 static inline bool s360_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // The pointer rule of include/s360.h for one entry point: `in` is what the call reads, `out` what it writes, the caller's
-// scratch among them.  Every pointer is non-null and 16-byte aligned, no output is an input and no two outputs are the same.
-template <size_t NI, size_t NO>
-static inline bool s360_pointers_ok(const void* const (&in)[NI], const void* const (&out)[NO]) {
+// scratch among them, `opt` the outputs the caller may leave out (a null one is skipped, any other is an output like those of
+// `out`).  Every pointer is non-null and a multiple of `align` (16 bytes unless the operator's kernels ask for less), no output
+// is an input and no two outputs are the same; inputs may be one another.
+template <size_t NI, size_t NO, size_t NP>
+static inline bool s360_pointers_ok(const void* const (&in)[NI], const void* const (&out)[NO], const void* const (&opt)[NP],
+                                    size_t align = 16) {
     for (const void* p : in)
-        if (!p || !s360_aligned(p, 16)) return false;
-    for (size_t i = 0; i < NO; ++i) {
-        if (!out[i] || !s360_aligned(out[i], 16)) return false;
+        if (!p || !s360_aligned(p, align)) return false;
+    const void* w[NO + NP];
+    size_t n = 0;
+    for (const void* p : out) {
+        if (!p) return false;
+        w[n++] = p;
+    }
+    for (const void* p : opt)
+        if (p) w[n++] = p;
+    for (size_t i = 0; i < n; ++i) {
+        if (!s360_aligned(w[i], align)) return false;
         for (const void* p : in)
-            if (p == out[i]) return false;
-        for (size_t j = i + 1; j < NO; ++j)
-            if (out[j] == out[i]) return false;
+            if (p == w[i]) return false;
+        for (size_t j = i + 1; j < n; ++j)
+            if (w[j] == w[i]) return false;
     }
     return true;
+}
+template <size_t NI, size_t NO>
+static inline bool s360_pointers_ok(const void* const (&in)[NI], const void* const (&out)[NO]) {
+    const void* const none[] = {nullptr};
+    return s360_pointers_ok(in, out, none);
 }
 
 // The workspace-size protocol of include/s360.h.  workspace == NULL is the size query: *bytes = need, S360_OK.  Otherwise
@@ -64,11 +79,4 @@ static inline int s360_workspace(const void* workspace, size_t* bytes, size_t ne
     }
     if (!args_ok || !s360_aligned(workspace, align)) return S360_E_BADARG;
     return *bytes < need ? S360_E_WORKSPACE : S360_WS_READY;
-}
-
-// The caller's scratch of a "high" call (its size comes from the operator's *_scratch_bytes): S360_E_BADARG for a null or
-// misaligned one, then S360_E_WORKSPACE for a short one, S360_OK otherwise.
-static inline int s360_scratch(const void* scratch, size_t bytes, size_t need) {
-    if (!scratch || !s360_aligned(scratch, 16)) return S360_E_BADARG;
-    return bytes < need ? S360_E_WORKSPACE : S360_OK;
 }

@@ -414,53 +414,6 @@ __global__ __launch_bounds__(S360_BLOCK) void k_qa_backward_kv(QAArgs a, const d
     }
 }
 
-// shared argument check; fills the kernel arguments
-static int qa_setup(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens, int32_t order, QAArgs& a) {
-    if (!qkv || rows < 1 || views < 1 || heads < 1 || ch < 1 || tokens < 1 || (order != 0 && order != 1)) return S360_E_BADARG;
-    if (rows % views != 0) return S360_E_BADARG;
-    if (ch != QA_CH) return S360_E_UNSUPPORTED;
-    const int64_t L = (int64_t)views * tokens, B = rows / views;
-    if (L >= (int64_t)1 << 31 || (int64_t)heads * 3 * ch >= (int64_t)1 << 31) return S360_E_BADARG;
-    if (B * heads * ((L + QA_T - 1) / QA_T) >= (int64_t)1 << 31) return S360_E_BADARG;
-    a.qkv = qkv;
-    a.B = (int)B; a.views = views; a.heads = heads; a.T = tokens; a.L = (int)L; a.W = heads * 3 * ch;
-    a.order = order;
-    a.inv_scale = 1.0 / sqrt((double)ch);
-    return S360_OK;
-}
-
-static unsigned qa_grid(const QAArgs& a) { return (unsigned)((int64_t)a.B * a.heads * ((a.L + QA_T - 1) / QA_T)); }
-
-}  // namespace s360
-
-using namespace s360;
-
-extern "C" int s360_qkv_attention_forward(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens,
-                                          int32_t order, float* out, double* lse, void* stream) {
-    QAArgs a;
-    const int rc = qa_setup(qkv, rows, views, heads, ch, tokens, order, a);
-    if (rc != S360_OK) return rc;
-    if (!out || !lse) return S360_E_BADARG;
-    hipLaunchKernelGGL(k_qa_forward, dim3(qa_grid(a)), dim3(S360_BLOCK), 0, (hipStream_t)stream, a, out, lse);
-    return s360_launch_status();
-}
-
-extern "C" int s360_qkv_attention_backward(const float* qkv, const double* lse, const float* g_out, int32_t rows, int32_t views,
-                                           int32_t heads, int32_t ch, int32_t tokens, int32_t order, double* delta, float* g_qkv,
-                                           void* stream) {
-    QAArgs a;
-    const int rc = qa_setup(qkv, rows, views, heads, ch, tokens, order, a);
-    if (rc != S360_OK) return rc;
-    if (!lse || !g_out || !delta || !g_qkv || g_qkv == qkv) return S360_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(qa_grid(a)), block(S360_BLOCK);
-    // the query-owned pass first: it writes Delta for the key-owned one
-    hipLaunchKernelGGL(k_qa_backward_q, grid, block, 0, st, a, lse, g_out, delta, g_qkv);
-    S360_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_qa_backward_kv, grid, block, 0, st, a, lse, delta, g_out, g_qkv);
-    return s360_launch_status();
-}
-
 // ---------------------------------------------------------------------------------------------- the "high" mode (bf16 x 3)
 // The same function with every product as a bf16x3 product (s360_bf16x3.h: the split, the three terms and their order, the
 // B-operand register rule); q and k are split unscaled and 1 / sqrt(ch) multiplies the summed score (and g_q, g_k) once.
@@ -482,7 +435,6 @@ extern "C" int s360_qkv_attention_backward(const float* qkv, const double* lse, 
 // walked: the P recomputed in both backward passes is formed from the forward's sums bit for bit.
 // Walked fragments are read straight from the planes (they stay in L2: 256 KB per plane and head at L = 4096), the next tile's
 // loads issued before the current tile's products.
-namespace s360 {
 
 struct QAHPlanes {                                            // hi and lo planes of the operands; null where a call has none
     __bf16 *q_rh, *q_rl, *q_th, *q_tl;
@@ -837,9 +789,23 @@ __global__ __launch_bounds__(S360_BLOCK) void k_qah_backward_kv(QAArgs a, QAHPla
     }
 }
 
-// The scratch of a call: the planes in the order q, k, v, g (rows, then transposed; hi, then lo), n = B heads Lpad 32 elements
-// each.  Forward: rows of q and k, transposed v (12 n bytes: the padded qkv's).  Backward: rows of all four, transposed q, k
-// and g (28 n bytes: 1.75 x the padded qkv and g_out).
+// ---------------------------------------------------------------------------------------------- the entry points, both modes
+// The size rules of a call; "high" also asks that Lpad is an int and that both its grids fit.  Fills the size fields of `a`.
+static int qa_sizes(int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens, int32_t order, bool high, QAArgs& a) {
+    if (rows < 1 || views < 1 || heads < 1 || ch < 1 || tokens < 1 || (order != 0 && order != 1) || rows % views != 0) return S360_E_BADARG;
+    if (ch != QA_CH) return S360_E_UNSUPPORTED;
+    const int64_t L = (int64_t)views * tokens, B = rows / views;
+    if (L >= (int64_t)1 << 31 || (int64_t)heads * 3 * ch >= (int64_t)1 << 31) return S360_E_BADARG;
+    const int64_t grid = B * heads * ((L + QA_T - 1) / QA_T);
+    if (grid >= (int64_t)1 << 31 || (high && (L > INT32_MAX - QA_T || !s360_grid_fits(grid)))) return S360_E_BADARG;
+    a.B = (int)B; a.views = views; a.heads = heads; a.T = tokens; a.L = (int)L; a.W = heads * 3 * ch;
+    a.order = order; a.inv_scale = 1.0 / sqrt((double)ch);
+    return S360_OK;
+}
+
+// The scratch of a "high" call: the planes in the order q, k, v, g (rows, then transposed; hi, then lo), n = B heads Lpad 32
+// elements each.  Forward: rows of q and k, transposed v (12 n bytes: the padded qkv's).  Backward: rows of all four, transposed
+// q, k and g (28 n bytes: 1.75 x the padded qkv and g_out).
 static size_t qah_layout(const QAArgs& a, bool backward, char* base, QAHPlanes* pl) {
     const size_t n = (size_t)a.B * a.heads * qah_pad(a.L) * QA_CH;
     Bx3Carver c{base};
@@ -860,70 +826,102 @@ static size_t qah_layout(const QAArgs& a, bool backward, char* base, QAHPlanes* 
     return c.off;
 }
 
-// qa_setup and what the "high" calls ask beyond it: Lpad is an int, both grids fit
-static int qah_setup(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens, int32_t order, QAArgs& a) {
-    const int rc = qa_setup(qkv, rows, views, heads, ch, tokens, order, a);
+// What every launch entry starts with, in the order of include/s360.h's refusals: the pointer rule (a tensor, lse and delta too,
+// is held to a float's alignment, the planes of a "high" call's scratch to 16 bytes), the sizes, the scratch size.  Completes `a`.
+template <bool HIGH, size_t NI, size_t NO>
+static int qa_setup(const void* const (&in)[NI], const void* const (&outs)[NO], const void* scratch, size_t scratch_bytes, bool backward,
+                    int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens, int32_t order, QAArgs& a) {
+    const void* const opt[] = {scratch};
+    if ((HIGH && (!scratch || !s360_aligned(scratch, 16))) || !s360_pointers_ok(in, outs, opt, alignof(float))) return S360_E_BADARG;
+    const int rc = qa_sizes(rows, views, heads, ch, tokens, order, HIGH, a);
     if (rc != S360_OK) return rc;
-    if (a.L > INT32_MAX - QA_T || !s360_grid_fits((long long)qa_grid(a))) return S360_E_BADARG;
-    return S360_OK;
+    return HIGH && scratch_bytes < qah_layout(a, backward, nullptr, nullptr) ? S360_E_WORKSPACE : S360_OK;
 }
+
+static unsigned qa_grid(const QAArgs& a) { return (unsigned)((int64_t)a.B * a.heads * ((a.L + QA_T - 1) / QA_T)); }
 
 static void qah_split_launch(const QAArgs& a, const float* src, int which, __bf16* rh, __bf16* rl, __bf16* th, __bf16* tl, hipStream_t st) {
     const size_t n = (size_t)a.B * a.heads * qah_pad(a.L) * (QA_CH / 8);        // qa_grid(a) / 2 workgroups
     hipLaunchKernelGGL(k_qah_split, dim3((unsigned)((n + S360_BLOCK - 1) / S360_BLOCK)), dim3(S360_BLOCK), 0, st, a, src, which, rh, rl, th, tl);
 }
 
+// s360_qkv_attention_forward (HIGH = false: no scratch) and s360_qkv_attention_high_forward (true)
+template <bool HIGH>
+static int qa_forward(QAArgs a, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens, int32_t order, float* out,
+                      double* lse, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    const void* const in[] = {a.qkv};
+    const void* const outs[] = {out, lse};
+    const int rc = qa_setup<HIGH>(in, outs, scratch, scratch_bytes, false, rows, views, heads, ch, tokens, order, a);
+    if (rc != S360_OK) return rc;
+    if constexpr (HIGH) {
+        QAHPlanes pl;
+        qah_layout(a, false, static_cast<char*>(scratch), &pl);
+        qah_split_launch(a, a.qkv, 0, pl.q_rh, pl.q_rl, nullptr, nullptr, st);
+        qah_split_launch(a, a.qkv, 1, pl.k_rh, pl.k_rl, nullptr, nullptr, st);
+        qah_split_launch(a, a.qkv, 2, nullptr, nullptr, pl.v_th, pl.v_tl, st);
+        S360_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_qah_forward, dim3(qa_grid(a)), dim3(S360_BLOCK), 0, st, a, pl, out, lse);
+    } else hipLaunchKernelGGL(k_qa_forward, dim3(qa_grid(a)), dim3(S360_BLOCK), 0, st, a, out, lse);
+    return s360_launch_status();
+}
+
+// s360_qkv_attention_backward (HIGH = false) and s360_qkv_attention_high_backward; the query-owned pass first: it writes Delta
+template <bool HIGH>
+static int qa_backward(QAArgs a, const double* lse, const float* g_out, int32_t rows, int32_t views, int32_t heads, int32_t ch,
+                       int32_t tokens, int32_t order, double* delta, float* g_qkv, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    const void* const in[] = {a.qkv, lse, g_out};
+    const void* const outs[] = {delta, g_qkv};
+    const int rc = qa_setup<HIGH>(in, outs, scratch, scratch_bytes, true, rows, views, heads, ch, tokens, order, a);
+    if (rc != S360_OK) return rc;
+    const dim3 grid(qa_grid(a)), block(S360_BLOCK);
+    if constexpr (HIGH) {
+        QAHPlanes pl;
+        qah_layout(a, true, static_cast<char*>(scratch), &pl);
+        qah_split_launch(a, a.qkv, 0, pl.q_rh, pl.q_rl, pl.q_th, pl.q_tl, st);
+        qah_split_launch(a, a.qkv, 1, pl.k_rh, pl.k_rl, pl.k_th, pl.k_tl, st);
+        qah_split_launch(a, a.qkv, 2, pl.v_rh, pl.v_rl, nullptr, nullptr, st);
+        qah_split_launch(a, g_out, 3, pl.g_rh, pl.g_rl, pl.g_th, pl.g_tl, st);
+        S360_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_qah_backward_q, grid, block, 0, st, a, pl, lse, delta, g_qkv);
+        S360_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_qah_backward_kv, grid, block, 0, st, a, pl, lse, delta, g_qkv);
+    } else {
+        hipLaunchKernelGGL(k_qa_backward_q, grid, block, 0, st, a, lse, g_out, delta, g_qkv);
+        S360_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_qa_backward_kv, grid, block, 0, st, a, lse, delta, g_out, g_qkv);
+    }
+    return s360_launch_status();
+}
+
 }  // namespace s360
+
+using namespace s360;
+
+extern "C" int s360_qkv_attention_forward(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens,
+                                          int32_t order, float* out, double* lse, void* stream) {
+    return qa_forward<false>({qkv}, rows, views, heads, ch, tokens, order, out, lse, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int s360_qkv_attention_backward(const float* qkv, const double* lse, const float* g_out, int32_t rows, int32_t views,
+                                           int32_t heads, int32_t ch, int32_t tokens, int32_t order, double* delta, float* g_qkv,
+                                           void* stream) {
+    return qa_backward<false>({qkv}, lse, g_out, rows, views, heads, ch, tokens, order, delta, g_qkv, nullptr, 0, (hipStream_t)stream);
+}
 
 extern "C" size_t s360_qkv_attention_high_scratch_bytes(int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens,
                                                         int32_t backward) {
     QAArgs a;
-    const float* any = reinterpret_cast<const float*>((uintptr_t)16);           // qa_setup checks the pointer it is given; it is not read
-    if (qah_setup(any, rows, views, heads, ch, tokens, 0, a) != S360_OK) return 0;
-    return qah_layout(a, backward != 0, nullptr, nullptr);
+    return qa_sizes(rows, views, heads, ch, tokens, 0, true, a) != S360_OK ? 0 : qah_layout(a, backward != 0, nullptr, nullptr);
 }
 
 extern "C" int s360_qkv_attention_high_forward(const float* qkv, int32_t rows, int32_t views, int32_t heads, int32_t ch, int32_t tokens,
                                                int32_t order, float* out, double* lse, void* scratch, size_t scratch_bytes,
                                                void* stream) {
-    QAArgs a;
-    const int rc = qah_setup(qkv, rows, views, heads, ch, tokens, order, a);
-    if (rc != S360_OK) return rc;
-    if (!out || !lse) return S360_E_BADARG;
-    const int rs = s360_scratch(scratch, scratch_bytes, qah_layout(a, false, nullptr, nullptr));
-    if (rs != S360_OK) return rs;
-    QAHPlanes pl;
-    qah_layout(a, false, static_cast<char*>(scratch), &pl);
-    hipStream_t st = (hipStream_t)stream;
-    qah_split_launch(a, qkv, 0, pl.q_rh, pl.q_rl, nullptr, nullptr, st);
-    qah_split_launch(a, qkv, 1, pl.k_rh, pl.k_rl, nullptr, nullptr, st);
-    qah_split_launch(a, qkv, 2, nullptr, nullptr, pl.v_th, pl.v_tl, st);
-    S360_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_qah_forward, dim3(qa_grid(a)), dim3(S360_BLOCK), 0, st, a, pl, out, lse);
-    return s360_launch_status();
+    return qa_forward<true>({qkv}, rows, views, heads, ch, tokens, order, out, lse, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
 extern "C" int s360_qkv_attention_high_backward(const float* qkv, const double* lse, const float* g_out, int32_t rows, int32_t views,
                                                 int32_t heads, int32_t ch, int32_t tokens, int32_t order, double* delta, float* g_qkv,
                                                 void* scratch, size_t scratch_bytes, void* stream) {
-    QAArgs a;
-    const int rc = qah_setup(qkv, rows, views, heads, ch, tokens, order, a);
-    if (rc != S360_OK) return rc;
-    if (!lse || !g_out || !delta || !g_qkv || g_qkv == qkv) return S360_E_BADARG;
-    const int rs = s360_scratch(scratch, scratch_bytes, qah_layout(a, true, nullptr, nullptr));
-    if (rs != S360_OK) return rs;
-    QAHPlanes pl;
-    qah_layout(a, true, static_cast<char*>(scratch), &pl);
-    hipStream_t st = (hipStream_t)stream;
-    qah_split_launch(a, qkv, 0, pl.q_rh, pl.q_rl, pl.q_th, pl.q_tl, st);
-    qah_split_launch(a, qkv, 1, pl.k_rh, pl.k_rl, pl.k_th, pl.k_tl, st);
-    qah_split_launch(a, qkv, 2, pl.v_rh, pl.v_rl, nullptr, nullptr, st);
-    qah_split_launch(a, g_out, 3, pl.g_rh, pl.g_rl, pl.g_th, pl.g_tl, st);
-    S360_CHECK_LAUNCH();
-    const dim3 grid(qa_grid(a)), block(S360_BLOCK);
-    // the query-owned pass first: it writes Delta for the key-owned one
-    hipLaunchKernelGGL(k_qah_backward_q, grid, block, 0, st, a, pl, lse, delta, g_qkv);
-    S360_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_qah_backward_kv, grid, block, 0, st, a, pl, lse, delta, g_qkv);
-    return s360_launch_status();
+    return qa_backward<true>({qkv}, lse, g_out, rows, views, heads, ch, tokens, order, delta, g_qkv, scratch, scratch_bytes, (hipStream_t)stream);
 }

@@ -463,101 +463,6 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wa_backward_kv(WAArgs a, const d
     }
 }
 
-// shared argument check; fills the kernel arguments
-static int wa_setup(const float* q, const float* k, const float* v, int32_t batch, int32_t partners, int32_t height, int32_t width,
-                    int32_t channels, int32_t num_splits, int32_t with_shift, int32_t mask_rule, WAArgs& a) {
-    if (!q || !k || !v || batch < 1 || partners < 0 || height < 1 || width < 1 || num_splits < 1) return S360_E_BADARG;
-    if (channels < 32 || channels > 128 || channels % 32 != 0) return S360_E_UNSUPPORTED;
-    if (height % num_splits != 0 || width % num_splits != 0 || (mask_rule != 0 && mask_rule != 1)) return S360_E_BADARG;
-    if (!s360_aligned(q, 16) || !s360_aligned(k, 16) || !s360_aligned(v, 16)) return S360_E_BADARG;
-    const int64_t M = partners > 0 ? partners : 1, L = (int64_t)height * width;
-    const int64_t Lw = L / ((int64_t)num_splits * num_splits);
-    if (batch * M * L >= (int64_t)1 << 31 || Lw * M >= (int64_t)1 << 31) return S360_E_BADARG;
-    const int64_t wins = (int64_t)batch * num_splits * num_splits;
-    if (wins * ((Lw * M + WA_ROWS - 1) / WA_ROWS) >= (int64_t)1 << 31) return S360_E_BADARG;
-    a.q = q; a.k = k; a.v = v;
-    a.B = batch; a.M = (int)M; a.H = height; a.W = width; a.C = channels; a.K = num_splits;
-    a.wh = height / num_splits; a.ww = width / num_splits;
-    a.shift = with_shift ? 1 : 0;
-    a.sh = a.shift ? a.wh / 2 : 0; a.sw = a.shift ? a.ww / 2 : 0;
-    a.Lw = (int)Lw; a.Lk = (int)(Lw * M); a.L = (int)L;
-    a.aligned = mask_rule;
-    a.scale = (float)sqrt((double)channels);
-    a.inv_scale = 1.0 / sqrt((double)channels);
-    return S360_OK;
-}
-
-static unsigned wa_grid(const WAArgs& a, int owner_rows) {
-    return (unsigned)((int64_t)a.B * a.K * a.K * ((owner_rows + WA_ROWS - 1) / WA_ROWS));
-}
-
-template <int NCB>
-static void wa_launch_kv(const WAArgs& a, const double* lse, const double* delta, const float* g_out, float* g_k, float* g_v,
-                         hipStream_t st) {
-    const dim3 grid(wa_grid(a, a.Lk)), block(S360_BLOCK);
-    if (g_k && g_v) hipLaunchKernelGGL((k_wa_backward_kv<NCB, true, true>), grid, block, 0, st, a, lse, delta, g_out, g_k, g_v);
-    else if (g_k) hipLaunchKernelGGL((k_wa_backward_kv<NCB, true, false>), grid, block, 0, st, a, lse, delta, g_out, g_k, g_v);
-    else hipLaunchKernelGGL((k_wa_backward_kv<NCB, false, true>), grid, block, 0, st, a, lse, delta, g_out, g_k, g_v);
-}
-
-// f(std::integral_constant<int, NCB>()) with NCB = channels / 32 channel blocks (1 .. 4: wa_setup has checked the channels):
-// the one place where a call's channel count becomes the kernels' template argument, in both modes
-template <typename F>
-static void wa_with_ncb(int channels, F f) {
-    switch (channels / 32) {
-        case 1: f(std::integral_constant<int, 1>()); break;
-        case 2: f(std::integral_constant<int, 2>()); break;
-        case 3: f(std::integral_constant<int, 3>()); break;
-        default: f(std::integral_constant<int, 4>()); break;
-    }
-}
-
-}  // namespace s360
-
-using namespace s360;
-
-extern "C" int s360_window_attention_forward(const float* q, const float* k, const float* v, int32_t batch, int32_t partners,
-                                             int32_t height, int32_t width, int32_t channels, int32_t num_splits, int32_t with_shift,
-                                             int32_t mask_rule, float* out, double* lse, void* stream) {
-    WAArgs a;
-    const int rc = wa_setup(q, k, v, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, a);
-    if (rc != S360_OK) return rc;
-    if (!out || !lse || !s360_aligned(out, 16)) return S360_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
-    wa_with_ncb(channels, [&](auto ncb) { hipLaunchKernelGGL((k_wa_forward<decltype(ncb)::value>), grid, block, 0, st, a, out, lse); });
-    return s360_launch_status();
-}
-
-template <int NCB>
-static void wa_launch_q(const WAArgs& a, const double* lse, const float* g_out, double* delta, float* g_q, hipStream_t st) {
-    const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
-    if (g_q) hipLaunchKernelGGL((k_wa_backward_q<NCB, true>), grid, block, 0, st, a, lse, g_out, delta, g_q);
-    else hipLaunchKernelGGL((k_wa_backward_q<NCB, false>), grid, block, 0, st, a, lse, g_out, delta, g_q);
-}
-
-extern "C" int s360_window_attention_backward(const float* q, const float* k, const float* v, const double* lse, const float* g_out,
-                                              int32_t batch, int32_t partners, int32_t height, int32_t width, int32_t channels,
-                                              int32_t num_splits, int32_t with_shift, int32_t mask_rule, double* delta, float* g_q,
-                                              float* g_k, float* g_v, void* stream) {
-    WAArgs a;
-    const int rc = wa_setup(q, k, v, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, a);
-    if (rc != S360_OK) return rc;
-    if (!lse || !g_out || !delta || !s360_aligned(g_out, 16)) return S360_E_BADARG;
-    if ((g_q && !s360_aligned(g_q, 16)) || (g_k && !s360_aligned(g_k, 16)) || (g_v && !s360_aligned(g_v, 16))) return S360_E_BADARG;
-    if (!g_q && !g_k && !g_v) return S360_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (g_q || g_k) {                                         // the query-owned pass first: it writes Delta for the key-owned one
-        wa_with_ncb(channels, [&](auto ncb) { wa_launch_q<decltype(ncb)::value>(a, lse, g_out, delta, g_q, st); });
-        S360_CHECK_LAUNCH();
-    }
-    if (g_k || g_v) {
-        wa_with_ncb(channels, [&](auto ncb) { wa_launch_kv<decltype(ncb)::value>(a, lse, delta, g_out, g_k, g_v, st); });
-        S360_CHECK_LAUNCH();
-    }
-    return S360_OK;
-}
-
 // ---------------------------------------------------------------------------------------------- the "high" mode (bf16 x 3)
 // The same function with every product as a bf16x3 product (s360_bf16x3.h: the split, the three terms and their order, the
 // B-operand register rule), accumulated by the MFMA over all channels.  Roll, split and merge, the mask, the scaling, the
@@ -572,7 +477,6 @@ extern "C" int s360_window_attention_backward(const float* q, const float* k, co
 // 32 cb + r: registers 4 g .. 4 g + 3 of a lane are channels 32 cb + 8 g + 4 hf + (0 .. 3), one 16-byte store.
 // The terms of a score are in (q, k) order — (qh, kh), (ql, kh), (qh, kl) — and those of dP in (g, v) order, whichever side is
 // walked, so the backward's recomputed tiles are the forward's bit for bit.
-namespace s360 {
 
 struct WAHPlanes {                                            // hi and lo planes of the operands; null where a call has none
     __bf16 *q_rh, *q_rl, *q_th, *q_tl;
@@ -896,8 +800,32 @@ __global__ __launch_bounds__(S360_BLOCK) void k_wah_backward_kv(WAArgs a, WAHPla
     }
 }
 
-// The scratch of a call: the planes in the order q, k, v, g (rows, then transposed; hi, then lo), each a multiple of 64 bytes.
-// Forward: rows of q and k, transposed v.  Backward: rows of all four, transposed q, k and g.
+// ---------------------------------------------------------------------------------------------- the entry points, both modes
+// The size rules of a call, "high" with the grid of its largest pre-pass launch; fills the size fields of `a`.
+static int wa_sizes(int32_t batch, int32_t partners, int32_t height, int32_t width, int32_t channels, int32_t num_splits,
+                    int32_t with_shift, int32_t mask_rule, bool high, WAArgs& a) {
+    if (batch < 1 || partners < 0 || height < 1 || width < 1 || num_splits < 1) return S360_E_BADARG;
+    if (channels < 32 || channels > 128 || channels % 32 != 0) return S360_E_UNSUPPORTED;
+    if (height % num_splits != 0 || width % num_splits != 0 || (mask_rule != 0 && mask_rule != 1)) return S360_E_BADARG;
+    const int64_t M = partners > 0 ? partners : 1, L = (int64_t)height * width;
+    const int64_t Lw = L / ((int64_t)num_splits * num_splits);
+    if (batch * M * L >= (int64_t)1 << 31 || Lw * M >= (int64_t)1 << 31) return S360_E_BADARG;
+    const int64_t wins = (int64_t)batch * num_splits * num_splits;
+    if (wins * ((Lw * M + WA_ROWS - 1) / WA_ROWS) >= (int64_t)1 << 31) return S360_E_BADARG;
+    a.B = batch; a.M = (int)M; a.H = height; a.W = width; a.C = channels; a.K = num_splits;
+    a.wh = height / num_splits; a.ww = width / num_splits;
+    a.shift = with_shift ? 1 : 0;
+    a.sh = a.shift ? a.wh / 2 : 0; a.sw = a.shift ? a.ww / 2 : 0;
+    a.Lw = (int)Lw; a.Lk = (int)(Lw * M); a.L = (int)L;
+    a.aligned = mask_rule;
+    a.scale = (float)sqrt((double)channels);
+    a.inv_scale = 1.0 / sqrt((double)channels);
+    if (high && !s360_grid_fits((long long)(((size_t)wins * wah_pad4(a.Lk) * (a.C / 8) + S360_BLOCK - 1) / S360_BLOCK))) return S360_E_BADARG;
+    return S360_OK;
+}
+
+// The scratch of a "high" call: the planes in the order q, k, v, g (rows, then transposed; hi, then lo), each a multiple of 64
+// bytes.  Forward: rows of q and k, transposed v.  Backward: rows of all four, transposed q, k and g.
 static size_t wah_layout(const WAArgs& a, bool backward, char* base, WAHPlanes* pl) {
     const size_t nwin = (size_t)a.B * a.K * a.K;
     const size_t nq = nwin * a.Lw * a.C, nk = nwin * a.Lk * a.C;
@@ -920,42 +848,147 @@ static size_t wah_layout(const WAArgs& a, bool backward, char* base, WAHPlanes* 
     return c.off;
 }
 
-// launches k_wah_split for one operand; false if the grid does not fit
-static bool wah_split_launch(const WAArgs& a, const float* src, int keys, __bf16* rh, __bf16* rl, __bf16* th, __bf16* tl, hipStream_t st) {
+// What every launch entry starts with, in the order of include/s360.h's refusals: the pointer rule (the gradients may be null, and
+// so may the scratch, which only a "high" call must have), the sizes, the scratch size.  Completes `a` (the caller has set its
+// pointers) with the sizes.
+template <bool HIGH, size_t NI, size_t NO>
+static int wa_setup(const void* const (&in)[NI], const void* const (&outs)[NO], const void* g_q, const void* g_k, const void* g_v,
+                    const void* scratch, size_t scratch_bytes, bool backward, int32_t batch, int32_t partners, int32_t height, int32_t width,
+                    int32_t channels, int32_t num_splits, int32_t with_shift, int32_t mask_rule, WAArgs& a) {
+    const void* const opt[] = {g_q, g_k, g_v, scratch};
+    if ((HIGH && !scratch) || !s360_pointers_ok(in, outs, opt)) return S360_E_BADARG;
+    const int rc = wa_sizes(batch, partners, height, width, channels, num_splits, with_shift, mask_rule, HIGH, a);
+    if (rc != S360_OK) return rc;
+    return HIGH && scratch_bytes < wah_layout(a, backward, nullptr, nullptr) ? S360_E_WORKSPACE : S360_OK;
+}
+
+static unsigned wa_grid(const WAArgs& a, int owner_rows) {
+    return (unsigned)((int64_t)a.B * a.K * a.K * ((owner_rows + WA_ROWS - 1) / WA_ROWS));
+}
+
+// f(std::integral_constant<int, NCB>()) with NCB = channels / 32 channel blocks (1 .. 4: wa_sizes has checked the channels):
+// the one place where a call's channel count becomes the kernels' template argument, in both modes
+template <typename F>
+static void wa_with_ncb(int channels, F f) {
+    switch (channels / 32) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        default: f(std::integral_constant<int, 4>()); break;
+    }
+}
+
+// launches k_wah_split for one operand (wa_sizes has checked that the grid fits)
+static void wah_split_launch(const WAArgs& a, const float* src, int keys, __bf16* rh, __bf16* rl, __bf16* th, __bf16* tl, hipStream_t st) {
     const size_t n = (size_t)a.B * a.K * a.K * wah_pad4(keys ? a.Lk : a.Lw) * (a.C / 8);
-    const size_t blocks = (n + S360_BLOCK - 1) / S360_BLOCK;
-    if (!s360_grid_fits((long long)blocks)) return false;
-    hipLaunchKernelGGL(k_wah_split, dim3((unsigned)blocks), dim3(S360_BLOCK), 0, st, a, src, keys, rh, rl, th, tl);
-    return true;
+    hipLaunchKernelGGL(k_wah_split, dim3((unsigned)((n + S360_BLOCK - 1) / S360_BLOCK)), dim3(S360_BLOCK), 0, st, a, src, keys, rh, rl, th, tl);
 }
 
-static bool wah_split_fits(const WAArgs& a) {
-    return s360_grid_fits((long long)(((size_t)a.B * a.K * a.K * wah_pad4(a.Lk) * (a.C / 8) + S360_BLOCK - 1) / S360_BLOCK));
-}
-
-template <int NCB>
-static void wah_launch_q(const WAArgs& a, const WAHPlanes& pl, const double* lse, double* delta, float* g_q, hipStream_t st) {
+// the backward's query-owned and key-owned pass, with the gradients asked for as template arguments; `pl` serves "high" alone
+template <bool HIGH, int NCB>
+static void wa_launch_q(const WAArgs& a, const WAHPlanes& pl, const double* lse, const float* g_out, double* delta, float* g_q, hipStream_t st) {
     const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
-    if (g_q) hipLaunchKernelGGL((k_wah_backward_q<NCB, true>), grid, block, 0, st, a, pl, lse, delta, g_q);
-    else hipLaunchKernelGGL((k_wah_backward_q<NCB, false>), grid, block, 0, st, a, pl, lse, delta, g_q);
+    auto launch = [&](auto want_q) {
+        constexpr bool Q = decltype(want_q)::value;
+        if constexpr (HIGH) hipLaunchKernelGGL((k_wah_backward_q<NCB, Q>), grid, block, 0, st, a, pl, lse, delta, g_q);
+        else hipLaunchKernelGGL((k_wa_backward_q<NCB, Q>), grid, block, 0, st, a, lse, g_out, delta, g_q);
+    };
+    if (g_q) launch(std::true_type());
+    else launch(std::false_type());
 }
 
-template <int NCB>
-static void wah_launch_kv(const WAArgs& a, const WAHPlanes& pl, const double* lse, const double* delta, float* g_k, float* g_v,
-                          hipStream_t st) {
+template <bool HIGH, int NCB>
+static void wa_launch_kv(const WAArgs& a, const WAHPlanes& pl, const double* lse, const double* delta, const float* g_out, float* g_k,
+                         float* g_v, hipStream_t st) {
     const dim3 grid(wa_grid(a, a.Lk)), block(S360_BLOCK);
-    if (g_k && g_v) hipLaunchKernelGGL((k_wah_backward_kv<NCB, true, true>), grid, block, 0, st, a, pl, lse, delta, g_k, g_v);
-    else if (g_k) hipLaunchKernelGGL((k_wah_backward_kv<NCB, true, false>), grid, block, 0, st, a, pl, lse, delta, g_k, g_v);
-    else hipLaunchKernelGGL((k_wah_backward_kv<NCB, false, true>), grid, block, 0, st, a, pl, lse, delta, g_k, g_v);
+    auto launch = [&](auto want_k, auto want_v) {
+        constexpr bool K = decltype(want_k)::value, V = decltype(want_v)::value;
+        if constexpr (HIGH) hipLaunchKernelGGL((k_wah_backward_kv<NCB, K, V>), grid, block, 0, st, a, pl, lse, delta, g_k, g_v);
+        else hipLaunchKernelGGL((k_wa_backward_kv<NCB, K, V>), grid, block, 0, st, a, lse, delta, g_out, g_k, g_v);
+    };
+    if (g_k && g_v) launch(std::true_type(), std::true_type());
+    else if (g_k) launch(std::true_type(), std::false_type());
+    else launch(std::false_type(), std::true_type());
+}
+
+// s360_window_attention_forward (HIGH = false: no scratch) and s360_window_attention_high_forward (true)
+template <bool HIGH>
+static int wa_forward(WAArgs a, int32_t batch, int32_t partners, int32_t height, int32_t width, int32_t channels, int32_t num_splits,
+                      int32_t with_shift, int32_t mask_rule, float* out, double* lse, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    const void* const in[] = {a.q, a.k, a.v};
+    const void* const outs[] = {out, lse};
+    const int rc = wa_setup<HIGH>(in, outs, nullptr, nullptr, nullptr, scratch, scratch_bytes, false, batch, partners, height, width, channels, num_splits,
+                                  with_shift, mask_rule, a);
+    if (rc != S360_OK) return rc;
+    const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
+    if constexpr (HIGH) {
+        WAHPlanes pl;
+        wah_layout(a, false, static_cast<char*>(scratch), &pl);
+        wah_split_launch(a, a.q, 0, pl.q_rh, pl.q_rl, nullptr, nullptr, st);
+        wah_split_launch(a, a.k, 1, pl.k_rh, pl.k_rl, nullptr, nullptr, st);
+        wah_split_launch(a, a.v, 1, nullptr, nullptr, pl.v_th, pl.v_tl, st);
+        S360_CHECK_LAUNCH();
+        wa_with_ncb(channels, [&](auto ncb) { hipLaunchKernelGGL((k_wah_forward<decltype(ncb)::value>), grid, block, 0, st, a, pl, out, lse); });
+    } else {
+        wa_with_ncb(channels, [&](auto ncb) { hipLaunchKernelGGL((k_wa_forward<decltype(ncb)::value>), grid, block, 0, st, a, out, lse); });
+    }
+    return s360_launch_status();
+}
+
+// s360_window_attention_backward (HIGH = false: no scratch) and s360_window_attention_high_backward (true)
+template <bool HIGH>
+static int wa_backward(WAArgs a, const double* lse, const float* g_out, int32_t batch, int32_t partners, int32_t height, int32_t width,
+                       int32_t channels, int32_t num_splits, int32_t with_shift, int32_t mask_rule, double* delta, float* g_q, float* g_k,
+                       float* g_v, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    const void* const in[] = {a.q, a.k, a.v, lse, g_out};
+    const void* const outs[] = {delta};
+    const int rc = wa_setup<HIGH>(in, outs, g_q, g_k, g_v, scratch, scratch_bytes, true, batch, partners, height, width, channels, num_splits,
+                                  with_shift, mask_rule, a);
+    if (rc != S360_OK) return rc;
+    if (!g_q && !g_k && !g_v) return S360_OK;
+    WAHPlanes pl = {};
+    if constexpr (HIGH) {
+        wah_layout(a, true, static_cast<char*>(scratch), &pl);
+        wah_split_launch(a, a.q, 0, pl.q_rh, pl.q_rl, pl.q_th, pl.q_tl, st);
+        wah_split_launch(a, a.k, 1, pl.k_rh, pl.k_rl, pl.k_th, pl.k_tl, st);
+        wah_split_launch(a, a.v, 1, pl.v_rh, pl.v_rl, nullptr, nullptr, st);
+        wah_split_launch(a, g_out, 0, pl.g_rh, pl.g_rl, pl.g_th, pl.g_tl, st);
+        S360_CHECK_LAUNCH();
+    }
+    if (g_q || g_k) {                                         // the query-owned pass first: it writes Delta for the key-owned one
+        wa_with_ncb(channels, [&](auto ncb) { wa_launch_q<HIGH, decltype(ncb)::value>(a, pl, lse, g_out, delta, g_q, st); });
+        S360_CHECK_LAUNCH();
+    }
+    if (g_k || g_v) {
+        wa_with_ncb(channels, [&](auto ncb) { wa_launch_kv<HIGH, decltype(ncb)::value>(a, pl, lse, delta, g_out, g_k, g_v, st); });
+        S360_CHECK_LAUNCH();
+    }
+    return S360_OK;
 }
 
 }  // namespace s360
 
+using namespace s360;
+
+extern "C" int s360_window_attention_forward(const float* q, const float* k, const float* v, int32_t batch, int32_t partners,
+                                             int32_t height, int32_t width, int32_t channels, int32_t num_splits, int32_t with_shift,
+                                             int32_t mask_rule, float* out, double* lse, void* stream) {
+    return wa_forward<false>({q, k, v}, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, out, lse, nullptr, 0,
+                             (hipStream_t)stream);
+}
+
+extern "C" int s360_window_attention_backward(const float* q, const float* k, const float* v, const double* lse, const float* g_out,
+                                              int32_t batch, int32_t partners, int32_t height, int32_t width, int32_t channels,
+                                              int32_t num_splits, int32_t with_shift, int32_t mask_rule, double* delta, float* g_q,
+                                              float* g_k, float* g_v, void* stream) {
+    return wa_backward<false>({q, k, v}, lse, g_out, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, delta,
+                              g_q, g_k, g_v, nullptr, 0, (hipStream_t)stream);
+}
+
 extern "C" size_t s360_window_attention_high_scratch_bytes(int32_t batch, int32_t partners, int32_t height, int32_t width,
                                                            int32_t channels, int32_t num_splits, int32_t backward) {
     WAArgs a;
-    const float* any = reinterpret_cast<const float*>((uintptr_t)16);           // wa_setup checks the pointers it is given; none is read
-    if (wa_setup(any, any, any, batch, partners, height, width, channels, num_splits, 0, 0, a) != S360_OK) return 0;
+    if (wa_sizes(batch, partners, height, width, channels, num_splits, 0, 0, true, a) != S360_OK) return 0;
     return wah_layout(a, backward != 0, nullptr, nullptr);
 }
 
@@ -963,22 +996,8 @@ extern "C" int s360_window_attention_high_forward(const float* q, const float* k
                                                   int32_t height, int32_t width, int32_t channels, int32_t num_splits,
                                                   int32_t with_shift, int32_t mask_rule, float* out, double* lse, void* scratch,
                                                   size_t scratch_bytes, void* stream) {
-    WAArgs a;
-    const int rc = wa_setup(q, k, v, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, a);
-    if (rc != S360_OK) return rc;
-    if (!out || !lse || !s360_aligned(out, 16) || !wah_split_fits(a)) return S360_E_BADARG;
-    const int rs = s360_scratch(scratch, scratch_bytes, wah_layout(a, false, nullptr, nullptr));
-    if (rs != S360_OK) return rs;
-    WAHPlanes pl;
-    wah_layout(a, false, static_cast<char*>(scratch), &pl);
-    hipStream_t st = (hipStream_t)stream;
-    wah_split_launch(a, q, 0, pl.q_rh, pl.q_rl, nullptr, nullptr, st);
-    wah_split_launch(a, k, 1, pl.k_rh, pl.k_rl, nullptr, nullptr, st);
-    wah_split_launch(a, v, 1, nullptr, nullptr, pl.v_th, pl.v_tl, st);
-    S360_CHECK_LAUNCH();
-    const dim3 grid(wa_grid(a, a.Lw)), block(S360_BLOCK);
-    wa_with_ncb(channels, [&](auto ncb) { hipLaunchKernelGGL((k_wah_forward<decltype(ncb)::value>), grid, block, 0, st, a, pl, out, lse); });
-    return s360_launch_status();
+    return wa_forward<true>({q, k, v}, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, out, lse, scratch,
+                            scratch_bytes, (hipStream_t)stream);
 }
 
 extern "C" int s360_window_attention_high_backward(const float* q, const float* k, const float* v, const double* lse,
@@ -986,30 +1005,6 @@ extern "C" int s360_window_attention_high_backward(const float* q, const float* 
                                                    int32_t channels, int32_t num_splits, int32_t with_shift, int32_t mask_rule,
                                                    double* delta, float* g_q, float* g_k, float* g_v, void* scratch,
                                                    size_t scratch_bytes, void* stream) {
-    WAArgs a;
-    const int rc = wa_setup(q, k, v, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, a);
-    if (rc != S360_OK) return rc;
-    if (!lse || !g_out || !delta || !s360_aligned(g_out, 16)) return S360_E_BADARG;
-    if ((g_q && !s360_aligned(g_q, 16)) || (g_k && !s360_aligned(g_k, 16)) || (g_v && !s360_aligned(g_v, 16))) return S360_E_BADARG;
-    if (!wah_split_fits(a)) return S360_E_BADARG;
-    const int rs = s360_scratch(scratch, scratch_bytes, wah_layout(a, true, nullptr, nullptr));
-    if (rs != S360_OK) return rs;
-    if (!g_q && !g_k && !g_v) return S360_OK;
-    WAHPlanes pl;
-    wah_layout(a, true, static_cast<char*>(scratch), &pl);
-    hipStream_t st = (hipStream_t)stream;
-    wah_split_launch(a, q, 0, pl.q_rh, pl.q_rl, pl.q_th, pl.q_tl, st);
-    wah_split_launch(a, k, 1, pl.k_rh, pl.k_rl, pl.k_th, pl.k_tl, st);
-    wah_split_launch(a, v, 1, pl.v_rh, pl.v_rl, nullptr, nullptr, st);
-    wah_split_launch(a, g_out, 0, pl.g_rh, pl.g_rl, pl.g_th, pl.g_tl, st);
-    S360_CHECK_LAUNCH();
-    if (g_q || g_k) {                                         // the query-owned pass first: it writes Delta for the key-owned one
-        wa_with_ncb(channels, [&](auto ncb) { wah_launch_q<decltype(ncb)::value>(a, pl, lse, delta, g_q, st); });
-        S360_CHECK_LAUNCH();
-    }
-    if (g_k || g_v) {
-        wa_with_ncb(channels, [&](auto ncb) { wah_launch_kv<decltype(ncb)::value>(a, pl, lse, delta, g_k, g_v, st); });
-        S360_CHECK_LAUNCH();
-    }
-    return S360_OK;
+    return wa_backward<true>({q, k, v}, lse, g_out, batch, partners, height, width, channels, num_splits, with_shift, mask_rule, delta, g_q,
+                             g_k, g_v, scratch, scratch_bytes, (hipStream_t)stream);
 }

@@ -28,11 +28,13 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import precision as _prec
+from ._args import buffers as _buffers, positive_int as _positive, tensor_rule
 from ._call import call, ptr
 from .precision import PRECISIONS  # noqa: F401  (the name callers of this module use)
 
 ORDERS = {"legacy": _lib.QKV_LEGACY, "new": _lib.QKV_NEW}
 HEAD_CHANNELS = (32,)
+_tensor = tensor_rule(ValueError, "{what}: {name} must be a GPU tensor (there is no CPU path), got device {device}")
 
 
 def supported_head_channels(ch: int) -> bool:
@@ -50,17 +52,15 @@ def _scratch(qkv: Tensor, views: int, heads: int, backward: bool) -> Tensor:
 
 
 def _checked(what: str, qkv, n_heads, n_frames, cross_view, order) -> tuple:
-    """Shape, dtype and device checks of a call; returns (rows, views, heads, ch, tokens, order code)."""
+    """The shape checks of a call, then the tensor rule (the order they have always had); returns (rows, views, heads, ch, tokens, order code)."""
     if order not in ORDERS:
         raise ValueError(f"{what} knows the orders {sorted(ORDERS)}, got order={order!r}")
     if not isinstance(qkv, Tensor):
         raise ValueError(f"{what}: qkv must be a tensor, got {type(qkv).__name__}")
     if qkv.dim() != 3:
         raise ValueError(f"{what} expects qkv [N, heads * 3 * ch, T], got shape {tuple(qkv.shape)}")
-    if isinstance(n_heads, bool) or not isinstance(n_heads, int) or n_heads < 1:
-        raise ValueError(f"{what}: n_heads must be a positive integer, got {n_heads!r}")
-    if isinstance(n_frames, bool) or not isinstance(n_frames, int) or n_frames < 1:
-        raise ValueError(f"{what}: n_frames must be a positive integer, got {n_frames!r}")
+    _positive(what, "n_heads", n_heads)
+    _positive(what, "n_frames", n_frames)
     rows, width, tokens = (int(s) for s in qkv.shape)
     if qkv.numel() == 0:
         raise ValueError(f"{what}: qkv is empty, shape {tuple(qkv.shape)}")
@@ -72,20 +72,19 @@ def _checked(what: str, qkv, n_heads, n_frames, cross_view, order) -> tuple:
     views = n_frames if cross_view else 1
     if rows % views != 0:
         raise ValueError(f"{what}: n_frames = {n_frames} must divide the {rows} rows of qkv for cross-view attention")
-    if not qkv.is_cuda:
-        raise ValueError(f"{what}: qkv must be a GPU tensor (there is no CPU path), got device {qkv.device}")
-    if qkv.dtype != torch.float32:
-        raise ValueError(f"{what}: qkv must be float32, got {qkv.dtype}")
+    _tensor(what, "qkv", qkv)
     return rows, views, n_heads, ch, tokens, ORDERS[order]
 
 
 def attention_forward(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: bool = False, order: str = "legacy",
-                      precision: str = "highest") -> tuple:
+                      precision: str = "highest", _dims=None) -> tuple:
     """s360_qkv_attention_forward (precision "high": s360_qkv_attention_high_forward) -> (out [N, heads ch, T] float32,
-    lse [N / views, heads, views T] float64)."""
+    lse [N / views, heads, views T] float64).  `_dims` is not for callers: the autograd node sets it (_checked's
+    result) for a qkv that qkv_attention has checked and the node has made contiguous, and with it set nothing is checked here."""
     precision = _prec.check("qkv_attention", precision)
-    rows, views, heads, ch, tokens, code = _checked("attention_forward", qkv, n_heads, n_frames, cross_view, order)
-    qkv = qkv.detach().contiguous()
+    rows, views, heads, ch, tokens, code = _dims or _checked("attention_forward", qkv, n_heads, n_frames, cross_view, order)
+    if _dims is None:
+        qkv = qkv.detach().contiguous()
     out = torch.empty(rows, heads * ch, tokens, dtype=torch.float32, device=qkv.device)
     lse = torch.empty(rows // views, heads, views * tokens, dtype=torch.float64, device=qkv.device)
     args = (ptr(qkv), rows, views, heads, ch, tokens, code, ptr(out), ptr(lse))
@@ -98,24 +97,22 @@ def attention_forward(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_vie
 
 
 def attention_backward(qkv: Tensor, lse: Tensor, g_out: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: bool = False,
-                       order: str = "legacy", g_qkv: Optional[Tensor] = None, precision: str = "highest") -> Tensor:
+                       order: str = "legacy", g_qkv: Optional[Tensor] = None, precision: str = "highest", _dims=None) -> Tensor:
     """s360_qkv_attention_backward (precision "high": s360_qkv_attention_high_backward, with the lse of a "high" forward) -> g_qkv
     in qkv's shape and layout.  `g_qkv`: a contiguous float32 buffer of qkv's shape on its device to write into (every element is
-    written); allocated when None."""
+    written); allocated when None.  `_dims`: not for callers, as in attention_forward."""
     precision = _prec.check("qkv_attention", precision)
-    rows, views, heads, ch, tokens, code = _checked("attention_backward", qkv, n_heads, n_frames, cross_view, order)
-    if not isinstance(g_out, Tensor) or not g_out.is_cuda or g_out.dtype != torch.float32 or g_out.device != qkv.device \
-            or tuple(g_out.shape) != (rows, heads * ch, tokens):
-        raise ValueError(f"attention_backward: g_out must be a float32 [{rows}, {heads * ch}, {tokens}] tensor on {qkv.device}")
-    if not isinstance(lse, Tensor) or lse.dtype != torch.float64 or lse.device != qkv.device \
-            or tuple(lse.shape) != (rows // views, heads, views * tokens):
-        raise ValueError("attention_backward: lse must be the forward's float64 [N / views, heads, views * T] tensor")
-    qkv, lse, g_out = (t.detach().contiguous() for t in (qkv, lse, g_out))
+    rows, views, heads, ch, tokens, code = _dims or _checked("attention_backward", qkv, n_heads, n_frames, cross_view, order)
+    if _dims is None:
+        _tensor("attention_backward", "g_out", g_out, (rows, heads * ch, tokens), device=qkv.device)
+        _tensor("attention_backward", "lse", lse, (rows // views, heads, views * tokens), dtype=torch.float64, device=qkv.device)
+        qkv, lse, g_out = (t.detach().contiguous() for t in (qkv, lse, g_out))
     if g_qkv is None:
         g_qkv = torch.empty_like(qkv)
-    elif not isinstance(g_qkv, Tensor) or g_qkv.dtype != torch.float32 or g_qkv.device != qkv.device \
-            or tuple(g_qkv.shape) != tuple(qkv.shape) or not g_qkv.is_contiguous() or g_qkv.data_ptr() == qkv.data_ptr():
-        raise ValueError("attention_backward: g_qkv must be a contiguous float32 buffer of qkv's shape on its device, not qkv itself")
+    else:                                                     # the kernels move one dword per lane: a float's alignment, as for qkv
+        _buffers("attention_backward", ("g_qkv",), (qkv.shape,), (torch.float32,), qkv.device, {"g_qkv": g_qkv}, _tensor, align=4)
+        if g_qkv.data_ptr() == qkv.data_ptr():
+            raise ValueError("attention_backward: g_qkv must be a buffer of its own, not qkv itself")
     delta = torch.empty_like(lse)
     args = (ptr(qkv), ptr(lse), ptr(g_out), rows, views, heads, ch, tokens, code, ptr(delta), ptr(g_qkv))
     if precision == "high":
@@ -131,9 +128,9 @@ class _QKVAttention(torch.autograd.Function):
     the output is kept) and, in the "high" mode, none of the bf16 planes (the backward splits again)."""
 
     @staticmethod
-    def forward(ctx, qkv, n_heads, n_frames, cross_view, order, precision):
+    def forward(ctx, qkv, n_heads, n_frames, cross_view, order, precision, dims):
         qkv = qkv.detach().contiguous()
-        opts = dict(n_frames=n_frames, cross_view=cross_view, order=order, precision=precision)
+        opts = dict(n_frames=n_frames, cross_view=cross_view, order=order, precision=precision, _dims=dims)
         out, lse = attention_forward(qkv, n_heads, **opts)
         ctx.save_for_backward(qkv, lse)
         ctx.n_heads, ctx.opts = n_heads, opts
@@ -143,7 +140,7 @@ class _QKVAttention(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_out):
         qkv, lse = ctx.saved_tensors
-        return attention_backward(qkv, lse, g_out.to(torch.float32), ctx.n_heads, **ctx.opts), None, None, None, None, None
+        return attention_backward(qkv, lse, g_out.to(torch.float32).contiguous(), ctx.n_heads, **ctx.opts), None, None, None, None, None, None
 
 
 def qkv_attention(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: bool = False, order: str = "legacy",
@@ -159,5 +156,5 @@ def qkv_attention(qkv: Tensor, n_heads: int, *, n_frames: int = 1, cross_view: b
     forward and backward (the module's docstring).  Returns a [N, heads ch, T] in qkv's row order.  Differentiable (once) in qkv.
     Float32 GPU tensors, ch = 32; no CPU path; a non-contiguous qkv is copied once."""
     _prec.check("qkv_attention", precision)
-    _checked("qkv_attention", qkv, n_heads, n_frames, cross_view, order)
-    return _QKVAttention.apply(qkv, int(n_heads), int(n_frames), bool(cross_view), order, precision)
+    dims = _checked("qkv_attention", qkv, n_heads, n_frames, cross_view, order)
+    return _QKVAttention.apply(qkv, int(n_heads), int(n_frames), bool(cross_view), order, precision, dims)

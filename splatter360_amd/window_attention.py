@@ -25,11 +25,13 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import precision as _prec
-from ._call import _check_cuda_f32, call, ptr
+from ._args import flat as _flat, tensor_rule
+from ._call import call, ptr
 from .precision import PRECISIONS, resolve as resolve_precision  # noqa: F401  (the names callers of this module use)
 
 MASK_RULES = {"reference": 0, "aligned": 1}
 MIN_CHANNELS, MAX_CHANNELS, CHANNEL_STEP = 32, 128, 32
+_tensor = tensor_rule(RuntimeError, "{what} runs on the GPU only (no CPU path)")
 
 
 def supported_channels(c: int) -> bool:
@@ -48,12 +50,8 @@ def scratch_bytes(batch: int, partners: int, height: int, width: int, channels: 
                                                                    int(num_splits), int(bool(backward))))
 
 
-def _scratch(q: Tensor, partners: int, height: int, width: int, num_splits: int, backward: bool) -> Tensor:
-    return _prec.scratch(scratch_bytes(int(q.shape[0]), partners, height, width, int(q.shape[2]), num_splits, backward), q.device)
-
-
 def _checked(what: str, q: Tensor, k: Tensor, v: Tensor, height: int, width: int, num_splits: int) -> int:
-    """Shape, dtype and device checks of a call; returns `partners` (0 for 3-D keys)."""
+    """The shape checks of a call, then the tensor rule (so a CPU tensor of a wrong shape gets the shape's message); returns `partners`."""
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, Tensor):
             raise ValueError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
@@ -74,23 +72,26 @@ def _checked(what: str, q: Tensor, k: Tensor, v: Tensor, height: int, width: int
     partners = int(k.shape[1]) if k.dim() == 4 else 0
     if q.numel() == 0 or (k.dim() == 4 and partners < 1):
         raise ValueError(f"{what}: empty tensors")
-    _check_cuda_f32(what, q, k, v)
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _tensor(what, name, t, device=q.device)
     return partners
 
 
 def attention_forward(q: Tensor, k: Tensor, v: Tensor, *, height: int, width: int, num_splits: int, with_shift: bool = False,
-                      mask_rule: str = "reference", precision: str = "highest") -> tuple:
+                      mask_rule: str = "reference", precision: str = "highest", _partners=None) -> tuple:
     """s360_window_attention_forward (precision "high": s360_window_attention_high_forward) on contiguous float32 GPU tensors ->
-    (out [B, L, C] float32, lse [B, L] float64)."""
-    rule, precision = _rule(mask_rule), _prec.check("window_attention", precision)
-    partners = _checked("attention_forward", q, k, v, height, width, num_splits)
-    q, k, v = (t.detach().contiguous() for t in (q, k, v))
+    (out [B, L, C] float32, lse [B, L] float64).  `_partners` is not for callers: the autograd node sets it
+    for tensors that window_attention has checked and the node has flattened, and with it set nothing is checked here."""
+    rule, precision, partners = _rule(mask_rule), _prec.check("window_attention", precision), _partners
+    if partners is None:
+        partners = _checked("attention_forward", q, k, v, height, width, num_splits)
+        q, k, v = (_flat(t) for t in (q, k, v))
     b, l, c = (int(s) for s in q.shape)
     out = torch.empty_like(q)
     lse = torch.empty(b, l, dtype=torch.float64, device=q.device)
     args = (ptr(q), ptr(k), ptr(v), b, partners, int(height), int(width), c, int(num_splits), int(bool(with_shift)), rule, ptr(out), ptr(lse))
     if precision == "high":
-        scratch = _scratch(q, partners, height, width, num_splits, False)
+        scratch = _prec.scratch(scratch_bytes(b, partners, height, width, c, num_splits, False), q.device)
         call("s360_window_attention_high_forward", q.device, *args, ptr(scratch), scratch.numel())
     else:
         call("s360_window_attention_forward", q.device, *args)
@@ -99,17 +100,15 @@ def attention_forward(q: Tensor, k: Tensor, v: Tensor, *, height: int, width: in
 
 def attention_backward(q: Tensor, k: Tensor, v: Tensor, lse: Tensor, g_out: Tensor, *, height: int, width: int, num_splits: int,
                        with_shift: bool = False, mask_rule: str = "reference", needs=(True, True, True),
-                       precision: str = "highest") -> tuple:
+                       precision: str = "highest", _partners=None) -> tuple:
     """s360_window_attention_backward (precision "high": s360_window_attention_high_backward, with the lse of a "high" forward)
-    -> (g_q, g_k, g_v) in the inputs' shapes, None where `needs` is False."""
-    rule, precision = _rule(mask_rule), _prec.check("window_attention", precision)
-    partners = _checked("attention_backward", q, k, v, height, width, num_splits)
-    _check_cuda_f32("attention_backward", q, g_out)
-    if tuple(g_out.shape) != tuple(q.shape):
-        raise ValueError(f"attention_backward: g_out {tuple(g_out.shape)} must have q's shape {tuple(q.shape)}")
-    if lse.dtype != torch.float64 or tuple(lse.shape) != tuple(q.shape[:2]) or lse.device != q.device:
-        raise ValueError("attention_backward: lse must be the forward's float64 [B, L] tensor")
-    q, k, v, lse, g_out = (t.detach().contiguous() for t in (q, k, v, lse, g_out))
+    -> (g_q, g_k, g_v) in the inputs' shapes, None where `needs` is False.  `_partners`: not for callers, as in attention_forward."""
+    rule, precision, partners = _rule(mask_rule), _prec.check("window_attention", precision), _partners
+    if partners is None:
+        partners = _checked("attention_backward", q, k, v, height, width, num_splits)
+        _tensor("attention_backward", "g_out", g_out, q.shape, device=q.device)
+        _tensor("attention_backward", "lse", lse, q.shape[:2], dtype=torch.float64, device=q.device)
+        q, k, v, lse, g_out = (_flat(t) for t in (q, k, v, lse, g_out))
     b, l, c = (int(s) for s in q.shape)
     g_q, g_k, g_v = (torch.empty_like(t) if need else None for t, need in zip((q, k, v), needs))
     if g_q is None and g_k is None and g_v is None:
@@ -118,7 +117,7 @@ def attention_backward(q: Tensor, k: Tensor, v: Tensor, lse: Tensor, g_out: Tens
     args = (ptr(q), ptr(k), ptr(v), ptr(lse), ptr(g_out), b, partners, int(height), int(width), c, int(num_splits),
             int(bool(with_shift)), rule, ptr(delta), ptr(g_q), ptr(g_k), ptr(g_v))
     if precision == "high":
-        scratch = _scratch(q, partners, height, width, num_splits, True)
+        scratch = _prec.scratch(scratch_bytes(b, partners, height, width, c, num_splits, True), q.device)
         call("s360_window_attention_high_backward", q.device, *args, ptr(scratch), scratch.numel())
     else:
         call("s360_window_attention_backward", q.device, *args)
@@ -130,9 +129,8 @@ class _WindowAttention(torch.autograd.Function):
     so not even out is kept) and, in the "high" mode, none of the bf16 planes (the backward splits again)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, height, width, num_splits, with_shift, mask_rule, precision):
-        q, k, v = (t.detach().contiguous() for t in (q, k, v))
-        opts = dict(height=height, width=width, num_splits=num_splits, with_shift=with_shift, mask_rule=mask_rule, precision=precision)
+    def forward(ctx, q, k, v, opts):
+        q, k, v = (_flat(t) for t in (q, k, v))
         out, lse = attention_forward(q, k, v, **opts)
         ctx.save_for_backward(q, k, v, lse)
         ctx.opts = opts
@@ -142,8 +140,8 @@ class _WindowAttention(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_out):
         q, k, v, lse = ctx.saved_tensors
-        grads = attention_backward(q, k, v, lse, g_out.to(torch.float32), needs=tuple(ctx.needs_input_grad[:3]), **ctx.opts)
-        return (*grads, None, None, None, None, None, None)
+        grads = attention_backward(q, k, v, lse, _flat(g_out.to(torch.float32)), needs=tuple(ctx.needs_input_grad[:3]), **ctx.opts)
+        return (*grads, None)
 
 
 def window_attention(q: Tensor, k: Tensor, v: Tensor, *, height: int, width: int, num_splits: int, with_shift: bool = False,
@@ -157,11 +155,12 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, *, height: int, width: int
     column j the region of window token j mod Lw; "aligned" gives it the region of its own token j // m.  The two coincide at
     m <= 1 and without shift.  precision "highest": exact float32 products; "high": bf16x3 products on the bf16 MFMA, forward
     and backward (the module's docstring).  Returns out [B, L, C] in the original token order.  Differentiable (once) in q, k
-    and v.  Float32 GPU tensors, C a multiple of 32 in [32, 128]; no CPU path; non-contiguous inputs are copied once."""
+    and v.  Float32 GPU tensors, C a multiple of 32 in [32, 128]; no CPU path; non-contiguous or misaligned inputs are copied once."""
     _prec.check("window_attention", precision)
     _rule(mask_rule)
-    _checked("window_attention", q, k, v, height, width, num_splits)
-    return _WindowAttention.apply(q, k, v, int(height), int(width), int(num_splits), bool(with_shift), mask_rule, precision)
+    partners = _checked("window_attention", q, k, v, height, width, num_splits)
+    return _WindowAttention.apply(q, k, v, dict(height=int(height), width=int(width), num_splits=int(num_splits), with_shift=bool(with_shift),
+                                                mask_rule=mask_rule, precision=precision, _partners=partners))
 
 
 def full_attention(q: Tensor, k: Tensor, v: Tensor, precision: str = "highest") -> Tensor:

@@ -182,5 +182,5 @@ def test_the_three_entry_points_are_declared_bound_and_sized():
     # refusals that need no device memory: a null tensor, then a null scratch behind a valid-looking (never read) address
     assert lib.s360_qkv_attention_high_forward(None, 2, 1, 1, 32, 8, 0, None, None, None, 0, None) == -1
     assert lib.s360_qkv_attention_high_backward(None, None, None, 2, 1, 1, 32, 8, 0, None, None, None, 0, None) == -1
-    assert lib.s360_qkv_attention_high_forward(16, 2, 1, 1, 32, 8, 0, 16, 16, None, 1 << 20, None) == -1
-    assert lib.s360_qkv_attention_high_forward(16, 2, 1, 1, 16, 8, 0, 16, 16, 16, 1 << 20, None) == -4         # ch = 16: unsupported
+    assert lib.s360_qkv_attention_high_forward(16, 2, 1, 1, 32, 8, 0, 32, 48, None, 1 << 20, None) == -1
+    assert lib.s360_qkv_attention_high_forward(16, 2, 1, 1, 16, 8, 0, 32, 48, 64, 1 << 20, None) == -4         # ch = 16: unsupported

@@ -103,18 +103,19 @@ def test_abi_has_the_window_attention_entry_points_and_they_reject_bad_arguments
     assert "s360_window_attention.hip" in _lib.SOURCES
     assert (ROOT / "splatter360_amd" / "csrc" / "s360_window_attention.hip").exists()
     assert _lib.ABI_VERSION == 25 and lib.s360_abi_version() == 25                  # additive: the version stays
-    p = C.c_void_p(4096)                                                            # never dereferenced: every call below is refused
+    # distinct 16-byte aligned addresses, never dereferenced: every call below is refused
+    q, k, v, o, l, g, d, gq, gk, gv = (C.c_void_p(4096 * (i + 1)) for i in range(10))
     fwd, bwd = lib.s360_window_attention_forward, lib.s360_window_attention_backward
     ok = (2, 0, 8, 16, 128, 2, 1, 0)
-    assert fwd(None, p, p, *ok, p, p, None) == -1 and fwd(p, p, p, *ok, None, p, None) == -1 and fwd(p, p, p, *ok, p, None, None) == -1
+    assert fwd(None, k, v, *ok, o, l, None) == -1 and fwd(q, k, v, *ok, None, l, None) == -1 and fwd(q, k, v, *ok, o, None, None) == -1
     for dims in ((0, 0, 8, 16, 128, 2, 1, 0), (2, -1, 8, 16, 128, 2, 1, 0), (2, 0, 0, 16, 128, 2, 1, 0), (2, 0, 8, 16, 128, 0, 1, 0),
                  (2, 0, 8, 16, 128, 3, 1, 0), (2, 0, 8, 16, 128, 2, 1, 2)):
-        assert fwd(p, p, p, *dims, p, p, None) == -1, dims
-    assert fwd(C.c_void_p(4100), p, p, *ok, p, p, None) == -1                        # not 16-byte aligned
+        assert fwd(q, k, v, *dims, o, l, None) == -1, dims
+    assert fwd(C.c_void_p(4100), k, v, *ok, o, l, None) == -1                        # not 16-byte aligned
     for c in (16, 48, 160, 256):
-        assert fwd(p, p, p, 2, 0, 8, 16, c, 2, 1, 0, p, p, None) == -4, c            # S360_E_UNSUPPORTED
-    assert bwd(p, p, p, None, p, *ok, p, p, p, p, None) == -1 and bwd(p, p, p, p, p, *ok, None, p, p, p, None) == -1
-    assert bwd(p, p, p, p, p, *ok, p, None, None, None, None) == 0                   # nothing asked for: no GPU work
+        assert fwd(q, k, v, 2, 0, 8, 16, c, 2, 1, 0, o, l, None) == -4, c            # S360_E_UNSUPPORTED
+    assert bwd(q, k, v, None, g, *ok, d, gq, gk, gv, None) == -1 and bwd(q, k, v, l, g, *ok, None, gq, gk, gv, None) == -1
+    assert bwd(q, k, v, l, g, *ok, d, None, None, None, None) == 0                   # nothing asked for: no GPU work
 
 
 def test_python_layer_refuses_what_it_cannot_run():
